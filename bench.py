@@ -28,6 +28,11 @@ sequence of ATTEMPTS, each a set of fresh child processes (one per rank it is re
 The fastest attempt whose ranks end with bit-identical replicas is the line; every attempt's outcome is in it
 (`hosts_tried`).  A hang is a timed-out child with its stderr in the line, not a silent time-out of the whole run.
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds, for config 3 on one GPU, what the
+headline does not need: the CPU baseline, the -exact 1 run of the same schedule and the bin/frog whole-process run.
+--dump-outputs DIR writes the timed path's results after its last step (dump_outputs) for output-to-output comparisons
+of two builds; the inputs are generated from fixed seeds.
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md section 6).
 """
 import argparse
@@ -482,11 +487,13 @@ def run_native(args, rank, world, local_rank, transport, rdv):
                              "sweep_ms_total": [x["sweep_ms"] for x in everyone], "comm_est_ms_total": [x["comm_est_ms"] for x in everyone],
                              "note": "per rank over the timed region: wall time, sum of the bracketed kernels' device time "
                                      "(all groups with --kernel-times, else the half-link sweeps), estimated device time of the collectives"}
-        if world == 1 and not args.no_cpu_baseline and args.config == 3 and not was_proxy:
+        if world == 1 and args.full and not args.no_cpu_baseline and args.config == 3 and not was_proxy:
             line["cpu_baseline"] = cpu_baseline(pairs, n_lin, per_level, 10)
-    # (with the CPU baseline, i.e. on the full default line: the A/B scripts pass --no-cpu-baseline and get neither)
+        if args.dump_outputs and not was_proxy:
+            dump_outputs(args.dump_outputs, lib, ctx, pairs, res.final_E)
+    # (with the CPU baseline, i.e. on the --full line: the A/B scripts pass --no-cpu-baseline and get neither)
     end_to_end_pending = (world == 1 and rank == 0 and line is not None and not was_proxy and not args.no_end_to_end
-                          and (args.end_to_end or (not args.no_cpu_baseline and args.config == 3)))
+                          and (args.end_to_end or (args.full and not args.no_cpu_baseline and args.config == 3)))
     if comm:
         if world > 1:
             rdv.gather_json("done", {"rank": rank})          # nobody tears its communicator down while another still reduces
@@ -494,11 +501,56 @@ def run_native(args, rank, world, local_rank, transport, rdv):
         cl.frog_comm_destroy_all(1, arr)
     lib.frog_destroy(ctx)
     if (world == 1 and rank == 0 and line is not None and not was_proxy and not args.exact and not args.no_exact_mode
-            and (args.exact_mode or (not args.no_cpu_baseline and args.config == 3))):
+            and (args.exact_mode or (args.full and not args.no_cpu_baseline and args.config == 3))):
         line["exact_mode"] = exact_mode(args, pairs, levels, n_lin, per_level, local_rank)
     if end_to_end_pending:
         line["end_to_end"] = end_to_end(pairs, levels)
     return line, (world == 1 or len({x["hash"] for x in everyone}) == 1)
+
+
+DUMP_BYTES = 64_000_000        # --dump-outputs writes at most this much (64 MB)
+DUMP_POINT_BYTES = 32_000_000  # of which the registered coordinates take at most this much
+
+
+def dump_outputs(directory, lib, ctx, pairs, final_e):
+    """What a caller of the timed path receives once its last step is done, as DIR/<name>.npy (float32 / float64):
+    the registered coordinates of every point, every image's linear transform and mixture, the final energy and the
+    coefficients of every lattice of the chain.  Where the coordinates or the lattices would not fit into DUMP_BYTES, a
+    fixed, seeded sample of points / images is written instead (the same for every run of the same workload)."""
+    import numpy as np
+    from frog_amd import _abi
+    os.makedirs(directory, exist_ok=True)
+    n_images, n_pts = pairs.n_images, int(pairs.point_offset[-1])
+    xyz2 = np.empty((n_pts, 3), np.float32)
+    _abi.check(lib.frog_get_points(ctx, None, xyz2.ctypes.data_as(_abi.c_float_p)), "frog_get_points")
+    if xyz2.nbytes > DUMP_POINT_BYTES:
+        keep = DUMP_POINT_BYTES // (3 * 4)
+        xyz2 = xyz2[np.sort(np.random.default_rng(1).choice(n_pts, keep, replace=False))]
+    matrices = np.empty((n_images, 4, 4), np.float64)
+    em = np.empty((n_images, 3), np.float32)
+    for i in range(n_images):
+        _abi.check(lib.frog_get_linear(ctx, i, matrices[i].ctypes.data_as(_abi.c_double_p)), "frog_get_linear")
+        _abi.check(lib.frog_get_em(ctx, i, em[i].ctypes.data_as(_abi.c_float_p)), "frog_get_em")
+    out = {"points_xyz2": xyz2, "linear_matrices": matrices, "em_mixtures": em, "final_E": np.array([final_e], np.float64)}
+    infos = []
+    for k in range(lib.frog_num_grids(ctx)):
+        info = _abi.FrogGridInfo()
+        _abi.check(lib.frog_get_grid(ctx, 0, k, C.byref(info), None, 0), "frog_get_grid")
+        infos.append(info)
+    per_image = sum(12 * info.dims[0] * info.dims[1] * info.dims[2] for info in infos)
+    left = DUMP_BYTES - sum(a.nbytes for a in out.values())
+    images = np.arange(n_images)
+    if per_image * n_images > left:
+        images = np.sort(np.random.default_rng(2).choice(n_images, max(1, left // max(per_image, 1)), replace=False))
+    for k, info in enumerate(infos):
+        g = info.dims[0] * info.dims[1] * info.dims[2]
+        coeffs = np.empty((len(images), g, 3), np.float32)
+        for j, i in enumerate(images):
+            _abi.check(lib.frog_get_grid(ctx, int(i), k, C.byref(info), coeffs[j].ctypes.data_as(_abi.c_float_p), 3 * g),
+                       "frog_get_grid")
+        out[f"lattice{k:03d}_coeffs"] = coeffs
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def exact_mode(args, pairs, levels, n_lin, per_level, local_rank):
@@ -809,7 +861,7 @@ def run_torch(args, rank, world, local_rank, backend, rdv):
             line["comm_ms"] = grp.comm_ms
         if world > 1:
             line["replicas_identical"] = replicas_identical
-        if world == 1 and not args.no_cpu_baseline and args.config == 3:
+        if world == 1 and args.full and not args.no_cpu_baseline and args.config == 3:
             line["cpu_baseline"] = cpu_baseline(pairs, n_lin, per_level, grp.statIntervalUpdate)
     if world > 1:
         dist.barrier()
@@ -997,6 +1049,12 @@ def main():
                          "reference's own order and arithmetic, bit-equal to the oracle (DESIGN.md 2a); the line says so in config.mode")
     ap.add_argument("--no-exact-mode", action="store_true", help="skip the -exact 1 run of the same schedule after the timed region (N = 1)")
     ap.add_argument("--exact-mode", action="store_true", help="run it even with --no-cpu-baseline / another --config")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the CPU baseline, the -exact 1 run of the same schedule and the "
+                         "bin/frog whole-process run (config 3, N = 1); a plain run sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (registered coordinates, matrices, mixtures, "
+                         "final energy, lattice coefficients) as DIR/<name>.npy, at most 64 MB (N = 1, --host native)")
     ap.add_argument("--kernel-times", action="store_true",
                     help="HIP-event times of every kernel group, not only of the half-link sweeps (costs ~6 %% of the rate)")
     ap.add_argument("--child", choices=("preflight", "native", "torch"), default=None, help=argparse.SUPPRESS)
@@ -1005,6 +1063,12 @@ def main():
     ap.add_argument("--child-attempt", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     argv = [a for a in sys.argv[1:]]
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and (args.gpus != 1 or args.host != "native" or args.shard_of):
+        ap.error("--dump-outputs needs --gpus 1 --host native and no --shard-of")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -7,7 +7,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 O=gpurun_out/$TAG
 mkdir -p $O
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 python3 bench.py --no-cpu-baseline --kernel-times > $O/bench_kernel_times.json 2>> $O/bench.err
 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_steps20.json 2>> $O/bench.err     # the round-end driver's command line
 ARGS="bench.py --steps 65 --warmup 10 --no-cpu-baseline --kernel-times"

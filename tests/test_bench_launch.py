@@ -160,3 +160,64 @@ def test_a_failed_rank_stops_the_others_waiting(tmp_path):
     c.all_ready("context", timeout=5.0)
     d.put("result_1", json.dumps({"x": 2}).encode())
     assert c.gather_json("result", {"x": 1}, timeout=5.0) == [{"x": 1}, {"x": 2}]
+
+
+def test_dump_outputs_writes_float_arrays_within_budget_with_a_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs without a device: dump_outputs against a stand-in for the library's read-back calls.  Every file is
+    float32 / float64, the whole stays under the budget when the coordinates and lattices would not fit, and the sample
+    taken then is the same from run to run."""
+    import ctypes as C
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", (1 << 19) + 30000)
+    monkeypatch.setattr(bench, "DUMP_POINT_BYTES", 1 << 19)
+    n_images, n_pts, dims = 5, 60000, [(4, 4, 5), (9, 9, 11)]
+
+    class FakeLib:
+        def frog_get_points(self, ctx, xyz, xyz2):
+            a = np.ctypeslib.as_array(xyz2, (n_pts, 3))
+            a[:] = np.arange(3 * n_pts, dtype=np.float32).reshape(n_pts, 3)
+            return 0
+
+        def frog_get_linear(self, ctx, i, m):
+            np.ctypeslib.as_array(m, (16,))[:] = np.eye(4).ravel() * (i + 1)
+            return 0
+
+        def frog_get_em(self, ctx, i, v):
+            np.ctypeslib.as_array(v, (3,))[:] = (i, 2 * i, 0.5)
+            return 0
+
+        def frog_num_grids(self, ctx):
+            return len(dims)
+
+        def frog_get_grid(self, ctx, image, k, info, coeffs, cap):
+            info._obj.dims[:] = dims[k]
+            if coeffs:
+                g = int(np.prod(dims[k]))
+                assert cap == 3 * g and 0 <= image < n_images
+                np.ctypeslib.as_array(coeffs, (3 * g,))[:] = 1000 * k + image
+            return 0
+
+    class FakePairs:
+        point_offset = np.linspace(0, n_pts, n_images + 1).astype(np.uint64)
+    FakePairs.n_images = n_images
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), FakeLib(), C.c_void_p(), FakePairs(), 12.5)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert files == ["em_mixtures.npy", "final_E.npy", "lattice000_coeffs.npy", "lattice001_coeffs.npy", "linear_matrices.npy",
+                     "points_xyz2.npy"]
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= bench.DUMP_BYTES
+    xyz2 = np.load(tmp_path / "a" / "points_xyz2.npy")
+    assert xyz2.nbytes <= bench.DUMP_POINT_BYTES and len(xyz2) < n_pts
+    assert np.all(np.diff(xyz2[:, 0]) > 0) and np.all(xyz2[:, 0] % 3 == 0)     # rows of the whole table, in order
+    lat = np.load(tmp_path / "a" / "lattice001_coeffs.npy")
+    assert lat.shape[1:] == (9 * 9 * 11, 3) and 1 <= lat.shape[0] < n_images
+    assert np.load(tmp_path / "a" / "final_E.npy").tolist() == [12.5]
+    assert np.array_equal(np.load(tmp_path / "a" / "linear_matrices.npy")[2], 3 * np.eye(4))

@@ -605,3 +605,31 @@ def test_bench_as_ranks_of_torch_distributed_run(tmp_path):
     two = json.loads(lines[0])
     assert two["n_gpus"] == 2 and two["replicas_identical"] is True and two["hosts_tried"][0]["ok"] is True
     assert abs(two["config"]["final_E"] - one["config"]["final_E"]) <= 1e-6 * one["config"]["final_E"]
+
+
+def test_bench_dump_outputs_are_what_the_timed_path_left(tmp_path):
+    """bench.py --dump-outputs: the registered coordinates, matrices, mixtures, energy and lattice coefficients the timed C
+    loop ends with, as float32 / float64 .npy files, the same from run to run with the same arguments."""
+    import sys
+    args = ["--gpus", "1", "--images", "6", "--points", "2000", "--pairs-per-block", "1000", "--steps", "26", "--warmup", "3"]
+    lines = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args, "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == 26 and "cpu_baseline" not in line and "exact_mode" not in line and "end_to_end" not in line
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    lattices = [f for f in files if f.startswith("lattice")]
+    assert len(lattices) == len(line["iteration"]["lattices"]) >= 1
+    assert set(files) - set(lattices) == {"points_xyz2.npy", "linear_matrices.npy", "em_mixtures.npy", "final_E.npy"}
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)) and np.array_equal(a, b), f
+    assert np.load(tmp_path / "a" / "points_xyz2.npy").shape == (6 * 2000, 3)
+    assert np.load(tmp_path / "a" / "linear_matrices.npy").shape == (6, 4, 4)
+    assert np.load(tmp_path / "a" / "final_E.npy").tolist() == [line["config"]["final_E"]]
+    for f, la in zip(lattices, line["iteration"]["lattices"]):
+        assert np.load(tmp_path / "a" / f).shape == (6, la["dims"][0] * la["dims"][1] * la["dims"][2], 3), f
