@@ -95,18 +95,14 @@ constexpr int MAX_GROUPS = N_XCD * MAX_SUBPASS;
 //   (k / 128) * 128 + (k % 64) * 2 + (k % 128) / 64.
 // Every range is padded with null records to a whole number of chunks.
 constexpr int REC_CHUNK = 128;
-// Layout of the per-XCD partial sums of the deformable sweep (group_sums): false = [group][point] (a wavefront of the
-// sweep stores 64 consecutive float4: 8 full lines; the scatter reads 8 lines per point, about half of each used);
-// true = [point][group] (one 128-byte line per point for the scatter; the sweep's stores become 16-byte pieces of 64
-// lines that eight XCDs complete).  Measured (cfg 3): the second form takes the sweep from 0.32 to 0.475 ms -- partial
-// lines written from eight L2s -- and the scatter from 0.121 only to 0.113-0.120 ms.  Kept at false.
-#ifndef FROG_SUMS_POINT_MAJOR
-#define FROG_SUMS_POINT_MAJOR 0
-#endif
-constexpr bool SUMS_POINT_MAJOR = FROG_SUMS_POINT_MAJOR != 0;
+// Layout of the per-XCD partial sums of the deformable sweep (group_sums): [group][point] (a wavefront of the sweep stores
+// 64 consecutive float4: 8 full lines; the scatter reads 8 lines per point, about half of each used).  [point][group] (one
+// 128-byte line per point for the scatter; the sweep's stores become 16-byte pieces of 64 lines that eight XCDs complete)
+// was measured (cfg 3): the sweep 0.32 -> 0.475 ms -- partial lines written from eight L2s -- and the scatter
+// 0.121 -> 0.113-0.120 ms only.
 __host__ __device__ inline size_t group_sum_index(uint32_t group, uint32_t point, uint32_t own_points)
 {
-    return SUMS_POINT_MAJOR ? (size_t)point * N_XCD + group : (size_t)group * own_points + point;
+    return (size_t)group * own_points + point;
 }
 // Partner-image groups: n_groups = 8 * n_sub.  The sweep is launched n_sub times; launch `sub`
 // lets XCD x read group sub*8 + x and continues XCD x's partial sums, so that a group's xyz2 slice
@@ -252,7 +248,7 @@ struct frog_ctx {
     frog::DevBuf<frog::Tile> tiles_bo;        // the tiles in block order (zero tiles where tile_order has none)
     uint32_t n_order_blocks = 0;
     bool fused_sweep = false;
-    bool fused_forced = false;                // FROG_SWEEP_FUSED=1 / 2: also without a culling list
+    bool fused_forced = false;                // FROG_SWEEP_FUSED=1: also without a culling list
 
     // statistics
     frog::DevBuf<float4> em;                  // [nI] c1,c2,ratio,0
@@ -288,7 +284,6 @@ struct frog_ctx {
     hipEvent_t setup_fork = nullptr, setup_join = nullptr;
     bool setup_pending = false;               // host side: setup_join not yet waited for on `stream`
     bool setup_deferred = false;              // host side: the set-up's kernels are not queued yet (join_setup queues them)
-    bool setup_async = true;                  // FROG_SETUP_STREAM=0: everything on `stream`
     hipEvent_t energy_copied = nullptr;       // the four scalars of the last step are in h_energy
     bool xyz2_exported = false;               // frog_comm_buffer handed out pos2: its address must not change
     hipEvent_t sel_done[SEL_RING_MAX] = {};   // selection in buffer b complete (side stream)
@@ -330,7 +325,6 @@ struct frog_ctx {
     frog::DevBuf<unsigned char> scatter_blocks_tmp; // the same blocks in brick order
     frog::DevBuf<uint32_t> len_hist;          // [2][SCATTER_CHUNK + 1] block-length histogram, cursors
     uint32_t n_scatter_blocks = 0;            // launch grid of the scatter: an upper bound of the block count
-    uint32_t scatter_chunk = 384;             // points per scatter block of this context (<= SCATTER_CHUNK; frog_create)
     frog::DevBuf<float> bounds_scratch;       // [BOUNDS_BLOCKS][6] per-block min xyz, max xyz
     frog::DevBuf<unsigned int> stray;         // [0], [1]: points the scatter of an even / odd step found outside every brick (their taps went to
                                               // gradf), [2]: running total

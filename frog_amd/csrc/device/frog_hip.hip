@@ -175,11 +175,10 @@ static bool sweep_builds_list(const frog_ctx *ctx) { return ctx->rec_format.narr
 // Does this deformable sweep run in its fused form (k_links.hip.h FUSED)?  The one launch per list that walks EVERY record
 // (and writes the list) does not: its false matches gather from uniformly random places of their partner image, which the
 // per-group form keeps inside one XCD's 3 MB slice of the coordinates and the fused form does not (measured on cfg 3:
-// 0.62 against 0.76 ms; the steady-state launches 0.300 against 0.254 ms).  FROG_SWEEP_FUSED=2 fuses that launch too.
+// 0.62 against 0.76 ms; the steady-state launches 0.300 against 0.254 ms).
 static bool sweep_fused_now(const frog_ctx *ctx, bool build)
 {
-    static const bool fuse_build = [] { const char *e = getenv("FROG_SWEEP_FUSED"); return e && e[0] == '2'; }();
-    return ctx->fused_sweep && (!build || fuse_build);
+    return ctx->fused_sweep && !build;
 }
 
 template <int MODE>
@@ -217,8 +216,7 @@ static void launch_sweep(frog_ctx *ctx, uint32_t sub, hipStream_t s, hipEvent_t 
             // one block per tile, wavefront = partner group, ONE float4 of sums per point out (k_links.hip.h FUSED)
             const dim3 fgrid(ctx->n_order_blocks), fblock(512);
             const size_t flds = lds * N_XCD;
-            if (build) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_DEFORMABLE, true, false, true, true>), fgrid, fblock, flds, s, ea, eb, 0, args);
-            else if (ctx->rec_format.narrow) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_DEFORMABLE, true, false, false, true>), fgrid, fblock, flds, s, ea, eb, 0, args);
+            if (ctx->rec_format.narrow) hipExtLaunchKernelGGL((sweep_kernel<SWEEP_DEFORMABLE, true, false, false, true>), fgrid, fblock, flds, s, ea, eb, 0, args);
             else hipExtLaunchKernelGGL((sweep_kernel<SWEEP_DEFORMABLE, true, true, false, true>), fgrid, fblock, flds, s, ea, eb, 0, args);
             return;
         }
@@ -330,8 +328,8 @@ static int queue_setup_kernels(frog_ctx *ctx, hipStream_t s)
     // block table (k_grid.hip.h): blocks per brick -> staging slots (scan) -> blocks in brick order -> longest first.
     // Its length stays on the device (brick_slot_ptr[n_bricks_total]); the scatter is launched with an upper bound:
     // every non-empty brick ends with at most one partial block
-    const uint32_t max_blocks = scatter_max_blocks(n_bricks_total, nPts, ctx->scatter_chunk);
-    brick_chunks_kernel<<<div_up(n_bricks_total, 256), 256, 0, s>>>(ctx->key_ptr.p, n_bricks_total, keys_per_brick, ctx->scatter_chunk, chunks.p);
+    const uint32_t max_blocks = scatter_max_blocks(n_bricks_total, nPts, SCATTER_CHUNK);
+    brick_chunks_kernel<<<div_up(n_bricks_total, 256), 256, 0, s>>>(ctx->key_ptr.p, n_bricks_total, keys_per_brick, SCATTER_CHUNK, chunks.p);
     FROG_HIP_CHECK(hipGetLastError());
     rc = exclusive_scan(chunks.p, n_bricks_total, ctx->brick_slot_ptr.p, ctx->key_cursor.p /* scratch: the placement is done */);
     if (rc) return rc;
@@ -340,11 +338,11 @@ static int queue_setup_kernels(frog_ctx *ctx, hipStream_t s)
     uint32_t *len_hist = ctx->len_hist.p, *len_cursor = ctx->len_hist.p + (SCATTER_CHUNK + 1);
     const uint32_t *n_blocks_dev = ctx->brick_slot_ptr.p + n_bricks_total;
     block_fill_kernel<<<div_up(n_bricks_total, 256), 256, 0, s>>>(ctx->key_ptr.p, ctx->brick_slot_ptr.p, n_bricks_total, keys_per_brick,
-                                                                 ctx->scatter_chunk, blk_tmp, len_hist);
+                                                                 SCATTER_CHUNK, blk_tmp, len_hist);
     static_assert(SCATTER_CHUNK + 1 <= 1024, "block_len_base_kernel: one thread per block length");
     block_len_base_kernel<<<1, (SCATTER_CHUNK + 1 + 63) / 64 * 64, 0, s>>>(len_hist, len_cursor);
     if (max_blocks)
-        block_sort_kernel<<<div_up(max_blocks, 256), 256, 0, s>>>(blk_tmp, n_blocks_dev, ctx->scatter_chunk, len_cursor, blk);
+        block_sort_kernel<<<div_up(max_blocks, 256), 256, 0, s>>>(blk_tmp, n_blocks_dev, SCATTER_CHUNK, len_cursor, blk);
     if (g.sparse) {                             // the active (image, node) pairs of the new lattice, block by block; per node how many images lack it
         if (nPts && max_blocks) lattice_mask_kernel<<<max_blocks, 64, 0, s>>>(ctx->pos_b.p, blk, n_blocks_dev, gd, ctx->lat_mask.p);
         lattice_inactive_kernel<<<div_up((size_t)gd.n_cp, 256), 256, 0, s>>>(ctx->lat_mask.p, nO, gd, ctx->lat_inactive.p);
@@ -435,7 +433,7 @@ static int ref_alloc(frog_ctx *ctx)
     FROG_HIP_CHECK(ctx->ref_link_img.alloc(std::max<size_t>(1, ctx->L_own)));
     FROG_HIP_CHECK(ctx->ref_pt_energy.alloc(2 * (size_t)std::max(1u, nRows)));
     FROG_HIP_CHECK(ctx->ref_row_sums.alloc(std::max(1u, nRows)));
-    if (!ctx->ref_stream && !getenv("FROG_REF_ONE_STREAM")) {
+    if (!ctx->ref_stream) {
         FROG_HIP_CHECK(hipStreamCreateWithFlags(&ctx->ref_stream, hipStreamNonBlocking));
         FROG_HIP_CHECK(hipEventCreateWithFlags(&ctx->ref_fork, hipEventDisableTiming));
         FROG_HIP_CHECK(hipEventCreateWithFlags(&ctx->ref_join, hipEventDisableTiming));
@@ -631,8 +629,7 @@ static int ref_chain_build(frog_ctx *ctx)
     FROG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairsDescending(ctx->rc_temp.p, tb, ctx->rc_len.p, ctx->rc_len_sorted.p, ctx->rc_iota.p, ctx->rc_slot_node.p, n_slots, 0, 32, s));
     FROG_HIP_CHECK(hipMemsetAsync(ctx->rc_group_size.p, 0, ((size_t)n_groups + 1) * sizeof(uint64_t), s));
     // ... and look the sums up by owned row (see ref_chain_fill_kernel); landmark constraints edit the sums by point afterwards: by point then
-    static const int by_row_min = getenv("FROG_REF_BY_ROW_MIN") ? atoi(getenv("FROG_REF_BY_ROW_MIN")) : 300;
-    ctx->rc_by_row = !ctx->n_hard && !ctx->ref_literal && n_keys / std::max<uint64_t>(1, n_gnodes) >= (uint64_t)by_row_min;
+    ctx->rc_by_row = !ctx->n_hard && !ctx->ref_literal && n_keys / std::max<uint64_t>(1, n_gnodes) >= 300;
     ref_chain_group_kernel<<<div_up(n_slots, 256), 256, 0, s>>>(ctx->rc_len_sorted.p, (uint32_t)n_slots, n_groups, (uint32_t)ctx->rc_unroll, ctx->rc_group_len.p,
                                                                                   ctx->rc_group_size.p, ctx->rc_slot_node.p, ctx->rc_slot_of_node.p);
     tb = ctx->rc_temp.n;
@@ -741,16 +738,6 @@ void frog_destroy(frog_ctx *ctx)
     if (ctx->helper) { frog_destroy(ctx->helper); ctx->helper = nullptr; }
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-#ifdef FROG_W1_COUNT
-    {
-        unsigned long long h[8];
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_w1_count), sizeof h);
-        fprintf(stderr, "W1 steps %llu with-general %llu  lanes %llu general %llu skipped %llu general-below-lo %llu\n", h[0], h[1], h[2], h[3], h[4], h[5]);
-        std::vector<float4> em(ctx->nI); std::vector<frog::EmFast> ef(ctx->nI);
-        (void)hipMemcpy(em.data(), ctx->em.p, em.size() * 16, hipMemcpyDeviceToHost); (void)hipMemcpy(ef.data(), ctx->emf.p, ef.size() * 16, hipMemcpyDeviceToHost);
-        for (uint32_t i = 0; i < ctx->nI && i < 6; i++) fprintf(stderr, "  image %u c1 %g c2 %g r %g   l %g ds %g lo %g hi %g (d_hi %g)\n", i, em[i].x, em[i].y, em[i].z, ef[i].l, ef[i].ds, ef[i].lo, ef[i].hi, sqrt(ef[i].hi));
-    }
-#endif
 #ifdef FROG_SWEEP_TRACE
     if (const char *path = getenv("FROG_SWEEP_TRACE_FILE")) {
         std::vector<unsigned long long> h(8 * 8 * 16384);
@@ -827,16 +814,6 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
     c->poff.assign(m->point_offset, m->point_offset + c->nI + 1);
     c->P = c->poff[c->nI];
     c->own_pt_begin = c->poff[c->ib]; c->own_pt_end = c->poff[c->ie];
-    {
-        // Points per scatter block (k_grid.hip.h): SCATTER_CHUNK for every context.  Round 6 tried shorter blocks for contexts that
-        // own few points (a rank of eight of the benchmark group has 625 blocks of 384 for 1 024 SIMDs, its scatter lasts one block's
-        // 31 us): with 128 the scatter took 18 us -- and the lattice step, which adds a brick's staged tiles slot by slot, 40 instead
-        // of 21 (level 0; 30 / 19 and 33 / 26 on levels 1 and 2): 7 287 against 7 365 rank-iterations/s, and a brick's points are summed
-        // per block, so shardings would no longer agree to the bit.  The switch stays for experiments.
-        uint32_t chunk = (uint32_t)SCATTER_CHUNK;
-        if (const char *e = getenv("FROG_SCATTER_CHUNK_POINTS")) chunk = std::min<uint32_t>((uint32_t)SCATTER_CHUNK, std::max<uint32_t>(64u, (uint32_t)atoi(e) / 64u * 64u));
-        c->scatter_chunk = chunk;
-    }
     if (c->P >= 0x7FFFFFFFull) { delete c; return fail(FROG_E_INVALID, "more than 2^31-1 points"); }
 
     Layout lay;
@@ -996,7 +973,7 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
         const char *fe = getenv("FROG_SWEEP_FUSED");
         c->fused_sweep = c->n_sub == 1 && c->n_tiles > 0 && widest <= (uint32_t)EMD_LDS_IMAGES && sweep_lds_images(c) <= 64u
                          && !(fe && fe[0] == '0');
-        c->fused_forced = fe && (fe[0] == '1' || fe[0] == '2');
+        c->fused_forced = fe && fe[0] == '1';
     }
     CREATE_CHECK(c->tile_partial.alloc((size_t)std::max(1u, c->n_tiles) * c->n_groups * LINEAR_SUMS));
     CREATE_CHECK(c->tile_counts.alloc((size_t)std::max(1u, c->n_tiles) * c->n_groups * 2));
@@ -1020,11 +997,9 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
     CREATE_CHECK(c->samples.alloc((size_t)c->n_owned() * cap));
     CREATE_CHECK(c->em_guess.alloc((size_t)c->n_owned() * 4 * EM_GUESS_BATCHES));
     CREATE_CHECK(hipMemsetAsync(c->em_guess.p, 0, c->em_guess.bytes(), s));
-    // ring of pre-computed selections (ctx.h): FROG_SELECT_RING buffers (default 6: five refreshes ahead), fewer when they
-    // would take more than 1 GB
+    // ring of pre-computed selections (ctx.h): 80 buffers (a whole default run's), fewer when they would take more than 1 GB
     c->sel_ring = 80;
-    if (const char *e = getenv("FROG_SELECT_RING")) c->sel_ring = atoi(e);
-    c->sel_ring = std::max(2, std::min(c->sel_ring, (int)frog_ctx::SEL_RING_MAX));
+    static_assert(80 <= frog_ctx::SEL_RING_MAX, "the ring's buffers are fixed arrays of frog_ctx");
     while (c->sel_ring > 2 && (size_t)c->sel_ring * c->n_owned() * cap * 12 > ((size_t)1 << 30)) c->sel_ring--;
     for (int b = 0; b < c->sel_ring; b++) {
         CREATE_CHECK(c->sample_ord[b].alloc((size_t)c->n_owned() * cap));
@@ -1038,18 +1013,16 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
         // The replay is a latency chain on a few wavefronts per image.  With one selection ahead it had to finish within ten
         // iterations and ran at high priority -- where its wavefronts take issue slots from the kernels of the iteration
         // (measured on cfg 3 while it runs: sweeps +4 %, the one-block-per-CU lattice step +60 %).  With a ring it has
-        // (sel_ring - 1) x ten iterations and runs at LOW priority (FROG_SELECT_PRIORITY=high restores the old choice).
+        // (sel_ring - 1) x ten iterations and runs at LOW priority.
         int lo = 0, hi = 0;
         CREATE_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        const char *pe = getenv("FROG_SELECT_PRIORITY");
-        const bool high = pe ? pe[0] == 'h' : c->sel_ring < 3;
+        const bool high = c->sel_ring < 3;
         CREATE_CHECK(hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, high ? hi : lo));
     }
     CREATE_CHECK(hipEventCreateWithFlags(&c->energy_copied, hipEventDisableTiming));
     CREATE_CHECK(hipStreamCreateWithFlags(&c->setup_stream, hipStreamNonBlocking));
     CREATE_CHECK(hipEventCreateWithFlags(&c->setup_fork, hipEventDisableTiming));
     CREATE_CHECK(hipEventCreateWithFlags(&c->setup_join, hipEventDisableTiming));
-    if (const char *e = getenv("FROG_SETUP_STREAM")) c->setup_async = atoi(e) != 0;
     {
         // std::mt19937::seed(0); index 624 forces a regeneration at the first draw
         std::vector<uint32_t> st((size_t)c->n_owned() * MT_WORDS);
@@ -1101,14 +1074,14 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
     CREATE_CHECK(c->cut_now.alloc(c->nI));
     CREATE_CHECK(c->lin_listed.alloc(1));
     CREATE_CHECK(hipMemsetAsync(c->lin_listed.p, 0, sizeof(unsigned long long), s));
-    if (c->cull_enabled && (c->opt.inlier_threshold >= 1e-3f || c->cull_linear) && c->n_tiles > 0 && !getenv("FROG_CULL_LAZY")) {
+    if (c->cull_enabled && (c->opt.inlier_threshold >= 1e-3f || c->cull_linear) && c->n_tiles > 0) {
         if (int rc_ = cull_allocate(c)) { frog_destroy(c); return rc_; }
     }
     stats_publish_kernel<<<dim3(div_up(c->nI, 64), 2), 64, 0, s>>>(c->em.p, c->emd.p, c->emf.p, c->nI, c->opt.inlier_threshold, c->fast_theta(), c->cut_now.p, 1);
     CREATE_CHECK(hipGetLastError());
     CREATE_CHECK(hipStreamSynchronize(s));      // host staging vectors die here
     create_lap("+ everything else allocated, uploads done");
-    if (!getenv("FROG_LATTICE_LAZY")) {
+    {
         // the lattice buffers of level 0 (with their head-room) for the box of the model as it is: close enough to what
         // the first frog_deformable_setup will ask for that it finds them allocated
         double mn[3] = { 1e300, 1e300, 1e300 }, mx[3] = { -1e300, -1e300, -1e300 };
@@ -1160,7 +1133,7 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
                 if (make_geometry(c, finest, rmn, rmx, gh, ih) == FROG_OK && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
                     gh.n_cp = (int)std::min<size_t>(0x7FFFFFFF, (size_t)gh.n_cp * 3 / 2);       // the linear stage rescales the images; another anchor
                     const size_t nO = c->n_owned(), nPts = c->own_pt_end - c->own_pt_begin;
-                    const size_t blocks = scatter_max_blocks((uint32_t)std::min<size_t>(0xFFFFFFFFu, nO * (size_t)gh.n_bricks), (uint32_t)nPts, c->scatter_chunk);
+                    const size_t blocks = scatter_max_blocks((uint32_t)std::min<size_t>(0xFFFFFFFFu, nO * (size_t)gh.n_bricks), (uint32_t)nPts, SCATTER_CHUNK);
                     const size_t E = (size_t)gh.brick + 3;
                     size_t arena_h = 0;
                     for (int l = 0; l <= finest; l++) {
@@ -1462,20 +1435,15 @@ int frog_update_stats_local(frog_ctx *ctx)
         sample_distance_kernel<<<dim3(div_up(cap, 256), nO), 256, 0, s>>>(
             ctx->sample_ends[cur].p, ctx->sample_count[cur].p, cap, ctx->pos2.p, ctx->samples.p);
         FROG_HIP_CHECK(hipGetLastError());
-        const bool em_serial = getenv("FROG_EM_SERIAL") != nullptr;            // test hook: the term-by-term form
-        if (em_serial)
-            em_kernel<<<nO, 256, 0, s>>>(ctx->samples.p, ctx->sample_count[cur].p, cap, ctx->ib, ctx->em.p,
-                                         ctx->opt.stats_max_iterations, ctx->opt.stats_epsilon);
-        else
-            em_scan_kernel<<<nO, EM_THREADS, 0, s>>>(ctx->samples.p, ctx->sample_count[cur].p, cap, ctx->ib, ctx->em.p,
-                                                     ctx->opt.stats_max_iterations, ctx->opt.stats_epsilon, ctx->em_guess.p);
+        em_scan_kernel<<<nO, EM_THREADS, 0, s>>>(ctx->samples.p, ctx->sample_count[cur].p, cap, ctx->ib, ctx->em.p,
+                                                 ctx->opt.stats_max_iterations, ctx->opt.stats_epsilon, ctx->em_guess.p);
         FROG_HIP_CHECK(hipGetLastError());
     }
     FROG_HIP_CHECK(hipEventRecord(ctx->ord_read[cur], s));
     ctx->sel_used = cur;
     ctx->sel_consumed++;
     // More selections for the ring once it runs low (ctx.h SEL_LOW_WATER), never into the buffer this refresh consumed (it
-    // stays readable: getters): a short ring (FROG_SELECT_RING, or a group whose buffers would not fit) produces one per
+    // stays readable: getters): a short ring (a group whose 80 buffers would exceed 1 GB) produces one per
     // refresh as before, a long one never during the schedules it was sized for.
     if (ctx->sel_produced - ctx->sel_consumed < (uint64_t)std::min((int)frog_ctx::SEL_LOW_WATER, ctx->sel_ring - 1))
         while (ctx->sel_produced - ctx->sel_consumed < (uint64_t)(ctx->sel_ring - 1)) {
@@ -1690,7 +1658,7 @@ int frog_linear_step(frog_ctx *ctx, double *E)
     // into the shadow buffer, and its first thread hands the step's scalars to the host through pinned memory -- the host used
     // to wait for a copy of the scalars, return, and only then queue the transform: 20 us of idle GPU per linear iteration.
     const uint32_t n = ctx->own_pt_end - ctx->own_pt_begin;
-    if (!(ctx->whole_group() && ctx->h_energy_dev && n && !ctx->helper && !getenv("FROG_LINEAR_NO_SPECULATION")))
+    if (!(ctx->whole_group() && ctx->h_energy_dev && n && !ctx->helper))
         return frog_energy_read(ctx, E, nullptr);
     if (ctx->pos2_spec.n != ctx->P) FROG_HIP_CHECK(ctx->pos2_spec.alloc(ctx->P));
     const double seq = (double)(++ctx->scalar_seq);
@@ -1789,7 +1757,7 @@ static int lattice_alloc(frog_ctx *ctx, const GridGeom &g)
     const size_t reserve = ((size_t)nO * G * 64 * sizeof(float4) <= ((size_t)2 << 30)) ? 64 : (((size_t)nO * G * 8 * sizeof(float4) <= ((size_t)2 << 30)) ? 8 : 1);
     const size_t n_keys = (size_t)nO * g.n_bricks * (size_t)(g.brick * g.brick * g.brick);
     const size_t n_bricks_total = (size_t)nO * g.n_bricks;
-    const size_t max_blocks = std::max<size_t>(1, scatter_max_blocks((uint32_t)n_bricks_total, nPts, ctx->scatter_chunk));
+    const size_t max_blocks = std::max<size_t>(1, scatter_max_blocks((uint32_t)n_bricks_total, nPts, SCATTER_CHUNK));
     const size_t E = (size_t)g.brick + 3;
     const size_t LG = std::max(g.lat_entries(), (size_t)nO * G);       // entries of one lattice in its layout (blocked: nodes padded to 16)
     if (getenv("FROG_SETUP_TRACE"))
@@ -1905,20 +1873,15 @@ int frog_deformable_setup_bounds(frog_ctx *ctx, int level, const double mins[3],
     const uint32_t keys_per_brick = (uint32_t)(g.brick * g.brick * g.brick);
     const size_t n_keys64 = (size_t)nO * nb * keys_per_brick;
     if (n_keys64 >= 0x7FFFFFFFull) return fail(FROG_E_INVALID, "too many lattice cells");
-    ctx->n_scatter_blocks = scatter_max_blocks(nO * (uint32_t)nb, nPts, ctx->scatter_chunk);
+    ctx->n_scatter_blocks = scatter_max_blocks(nO * (uint32_t)nb, nPts, SCATTER_CHUNK);
     ctx->coeff_zero = true;
     // The device work of the set-up -- zeroing, the sort of the points, the block table -- is queued on the set-up stream,
     // behind what `stream` holds NOW (the re-based coordinates, the copy of the finished lattice, the last readers of the old
     // sort: the fork event), but not yet: the host queues it when the first consumer asks (join_setup: as a rule the step's
     // scatter, right after its half-link sweep has been launched), so that the transform, the statistics refresh and the
     // sweep that open the level are in the queue first and the set-up runs beside them instead of in front of them.
-    if (ctx->setup_async && ctx->setup_stream) {
-        FROG_HIP_CHECK(hipEventRecord(ctx->setup_fork, ctx->stream));
-        ctx->setup_deferred = true;
-    } else {
-        rc = queue_setup_kernels(ctx, ctx->stream);
-        if (rc) return rc;
-    }
+    FROG_HIP_CHECK(hipEventRecord(ctx->setup_fork, ctx->stream));
+    ctx->setup_deferred = true;
 
     if (!ctx->deformable) {
         // end of the linear stage: its list (if any) is counted for frog_cull_stats_linear, and the deformable stage starts
@@ -1989,7 +1952,7 @@ static int cull_allocate_buffers(frog_ctx *ctx)
         for (uint32_t i = 0; i < ctx->nI; i++) blocks += div_up(ctx->poff[i + 1] - ctx->poff[i], CULL_BLOCK_POINTS);
         // one slot per producer block: cull_disp_kernel's, or the B-spline transform's (at most one block per point + one per
         // SCATTER_CHUNK points in its tiled form)
-        FROG_HIP_CHECK(ctx->disp_part.alloc(std::max<size_t>(blocks, (size_t)ctx->P + ctx->P / ctx->scatter_chunk + 16)));
+        FROG_HIP_CHECK(ctx->disp_part.alloc(std::max<size_t>(blocks, (size_t)ctx->P + ctx->P / SCATTER_CHUNK + 16)));
     }
     FROG_HIP_CHECK(ctx->cull_state.alloc(2));
     FROG_HIP_CHECK(hipMemsetAsync(ctx->cull_state.p, 0, ctx->cull_state.bytes(), s));
@@ -2092,9 +2055,8 @@ int frog_deformable_phase_a(frog_ctx *ctx, float alpha)
         Span span(ctx, FROG_K_COMBINE);
         // the per-point sums are only materialised when something other than the scatter reads them (landmark
         // constraints here, frog_get_point_sums later): the scatter adds the N_XCD partial sums itself
-        static const bool always_combine = getenv("FROG_COMBINE") != nullptr;      // test hook
         const bool fused = sweep_fused_now(ctx, ctx->build_in_sweep && sweep_builds_list(ctx));
-        ctx->point_sums_stale = !(ctx->n_hard || always_combine || fused);     // the fused sweep writes the points' sums itself
+        ctx->point_sums_stale = !(ctx->n_hard || fused);        // the fused sweep writes the points' sums itself
         if (!ctx->point_sums_stale && !fused)
             combine_groups_kernel<<<div_up(ctx->own_pt_end - ctx->own_pt_begin, 256), 256, 0, s>>>(
                 ctx->group_sums.p, ctx->own_pt_end - ctx->own_pt_begin, ctx->own_pt_begin, ctx->point_sums.p);
@@ -2146,9 +2108,7 @@ int frog_deformable_phase_a(frog_ctx *ctx, float alpha)
         la.energy = ctx->energy.p;
         ctx->centered_in_a = ctx->whole_group();
         // a coarse lattice takes the narrow block shape: four times the blocks (k_grid.hip.h LS_CPB_SMALL)
-        static const int force_shape = [] { const char *e = getenv("FROG_LS_SHAPE"); return e ? atoi(e) : 0; }();      // 16 / 4: A/B
-        const bool narrow = force_shape ? force_shape == LS_CPB_SMALL : gd.n_cp < LS_SMALL_NODES;
-        if (narrow) {
+        if (gd.n_cp < LS_SMALL_NODES) {
             const dim3 lgrid(div_up(gd.n_cp, LS_CPB_SMALL));
             if (ctx->centered_in_a) lattice_step_kernel<true, LS_CPB_SMALL><<<lgrid, LS_CPB_SMALL * LS_IC, 0, s>>>(la, gd);
             else lattice_step_kernel<false, LS_CPB_SMALL><<<lgrid, LS_CPB_SMALL * LS_IC, 0, s>>>(la, gd);

@@ -654,10 +654,12 @@ __global__ __launch_bounds__(256) void gather_positions_kernel(const float4 *pos
 // the cloud hold few points -- dispatching the long ones first shortens the tail.  The order among blocks of equal
 // length comes from atomics and changes from run to run; it only decides WHEN a block runs, every block writes its own
 // staging slot.
-#ifndef FROG_SCATTER_CHUNK
-#define FROG_SCATTER_CHUNK 384
-#endif
-constexpr int SCATTER_CHUNK = FROG_SCATTER_CHUNK;
+// Every context cuts its bricks into blocks of SCATTER_CHUNK points.  Round 6 tried 128 for contexts that own few points (a
+// rank of eight of the benchmark group: 625 blocks of 384 for 1 024 SIMDs, the scatter lasts one block's 31 us): the scatter
+// took 18 us, but the lattice step, which adds a brick's staged tiles slot by slot, 40 instead of 21 (level 0): 7 287 against
+// 7 365 rank-iterations/s -- and since a brick's points are summed per block, shardings would no longer agree to the bit
+// (DESIGN.md section 8 row 35).
+constexpr int SCATTER_CHUNK = 384;
 
 
 struct ScatterBlock {
@@ -667,8 +669,7 @@ struct ScatterBlock {
 };
 
 // chunks[k] = number of scatter blocks of brick k
-// `chunk` (<= SCATTER_CHUNK): points per block of THIS context (frog_ctx::scatter_chunk) -- a context that owns few points cuts
-// its bricks into shorter blocks, so that they fill the chip instead of queueing as a few long ones
+// `chunk` (<= SCATTER_CHUNK): points per block (SCATTER_CHUNK at every call)
 __global__ void brick_chunks_kernel(const uint32_t *ptr, uint32_t n_bricks_total, uint32_t keys_per_brick, uint32_t chunk, uint32_t *chunks)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -735,30 +736,17 @@ __global__ void block_sort_kernel(const ScatterBlock *blocks, const uint32_t *n_
     else if (live) sorted[atomicAdd(&len_cursor[b.end - b.begin], 1u)] = b;
 }
 
-#ifndef FROG_TRANSFORM_WAVES
-#define FROG_TRANSFORM_WAVES 4
-#endif
-#ifndef FROG_K11_F32_UNROLL
-#define FROG_K11_F32_UNROLL 1          // z-planes of the f32 form unrolled together
-#endif
-// Strides of the tile's rows and planes in LDS, in float4 entries (bricks of 4^3 cells: a 7 x 7 x 7 tile), packed by default.
+// Strides of the tile's rows and planes in LDS, in float4 entries (bricks of 4^3 cells: a 7 x 7 x 7 tile), packed.
 // Round 6 built the conflict-free layout for VERDICT r5 item 6 -- rows 12 apart, planes 96: the entry of cell (cx, cy, cz) is then
 // cx - 4 cy mod 16 whatever cz, so any 16 consecutive cells of the points' sort order read 16 different groups of four banks, for
-// every tap -- and measured it against the packed one on one box (-DFROG_K11_TILE_SY=12 -DFROG_K11_TILE_SZ=96,
-// profiles/r06_ab_experiments.txt): level 2 0.0628 against 0.0627 ms, level 0 0.0394 against 0.0364 (the tile grows from 5.5 to
-// 10.3 KB: 15 resident blocks per CU instead of 16).  Bank conflicts of the tap reads are not what level 2 pays; DESIGN.md
-// section 8 row 33.
-#ifndef FROG_K11_TILE_SY
-#define FROG_K11_TILE_SY 7
-#endif
-#ifndef FROG_K11_TILE_SZ
-#define FROG_K11_TILE_SZ 49
-#endif
-constexpr int K11_SY = FROG_K11_TILE_SY, K11_SZ = FROG_K11_TILE_SZ;
+// every tap -- and measured it against the packed one on one box (profiles/r06_ab_experiments.txt): level 2 0.0628 against
+// 0.0627 ms, level 0 0.0394 against 0.0364 (the tile grows from 5.5 to 10.3 KB: 15 resident blocks per CU instead of 16).  Bank
+// conflicts of the tap reads are not what level 2 pays; DESIGN.md section 8 row 33.
+constexpr int K11_SY = 7, K11_SZ = 49;
 constexpr int K11_TILE_ENTRIES = 6 * K11_SZ + 6 * K11_SY + 7;      // bricks of 4^3 cells (the tiled form is not used with others)
 static_assert(K11_SY >= 7 && K11_SZ >= 7 * K11_SY, "tile rows / planes overlap");
 template <typename T>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FROG_TRANSFORM_WAVES)))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4)))
 void transform_bspline_tile_kernel(float4 *pos, const float4 *pos_b, P3 *pos2, const float4 *coeff,
                                    const uint32_t *perm, const ScatterBlock *blocks,
                                    const uint32_t *n_blocks, const GeomDev g, int apply,
@@ -867,7 +855,7 @@ void transform_bspline_tile_kernel(float4 *pos, const float4 *pos_b, P3 *pos2, c
             if constexpr (sizeof(T) == 4) {
                 const f32x4 *tile = reinterpret_cast<const f32x4 *>(tile4);
                 f32x4 acc = { 0.f, 0.f, 0.f, 0.f };
-                #pragma unroll FROG_K11_F32_UNROLL
+                #pragma unroll 1
                 for (int k = 0; k < 4; k++) {
                     f32x4 vz = { 0.f, 0.f, 0.f, 0.f };
                     #pragma unroll
@@ -969,9 +957,6 @@ void transform_bspline_tile_kernel(float4 *pos, const float4 *pos_b, P3 *pos2, c
 __device__ unsigned long long g_scatter_trace[4 * 65536];
 #endif
 constexpr int BRICK_CP_MAX = 11;            // brick 8 -> 11^3 control points
-#ifndef FROG_SCATTER_FMA
-#define FROG_SCATTER_FMA 1         // round 5: 0.0698 -> 0.0670 ms per launch (cfg 3), one rounding per tap as in the reference
-#endif
 
 
 // The energy reduction that rides on the scatter's launch (see scatter_kernel).
@@ -1022,10 +1007,8 @@ __device__ __forceinline__ void scatter_energy_block(const ScatterEnergy &en, co
 }
 
 // Per-point values handed from phase 1 (lane = point) to phase 2 (lane = tap) through LDS, one array per value
-// (lane-consecutive writes and reads: no bank conflicts).  The products wx[i] * wy[j] are formed in phase 1, where one
-// instruction serves 64 points; in phase 2 an instruction serves ONE point, and that loop is where a block spends its time
-// (per-block trace, -DFROG_SCATTER_TRACE + scripts/microbench/scatter_trace_an.py: 63 % of a block's 52 us before this
-// layout, with the three weights read separately and multiplied per point).
+// (lane-consecutive writes and reads: no bank conflicts).  In phase 2 an instruction serves ONE point, and that loop is where a
+// block spends its time (per-block trace, -DFROG_SCATTER_TRACE + scripts/microbench/scatter_trace_an.py: 63 % of a block's 52 us).
 #ifndef FROG_SCATTER_QUADS
 #define FROG_SCATTER_QUADS 1       // phase 2 reads the weights of FOUR points per LDS instruction (see there); 0: point by point (rounds 2-4)
 #endif
@@ -1035,21 +1018,15 @@ constexpr int SC_PTS = 64 + 4;                  // ... a group of four ahead, un
 #else
 constexpr int SC_PTS = 64 + SC_AHEAD;           // ... unconditionally, so up to SC_AHEAD entries past the batch are read (unused)
 #endif
-#ifndef FROG_SCATTER_WXY
-#define FROG_SCATTER_WXY 0         // 1: the 16 products wx wy formed in phase 1 and handed over (rounds 2-4); 0: the 12 weights, multiplied in phase 2
-#endif
 struct ScatterScratch {
-#if FROG_SCATTER_WXY
-    float wxy[16][SC_PTS];      // wx[i] * wy[j] at [4 j + i]: f32 products of the f32-rounded weights (imageGroup.cxx:322, left to right)
-#else
-    // Round 5: the twelve weights as they are -- 68 instead of 100 bytes per point, 4.6 instead of 6.7 KB per block, which with the
+    // Round 5: the twelve weights as they are, multiplied in phase 2 (rounds 2-4 handed over the 16 products wx wy formed in
+    // phase 1) -- 68 instead of 100 bytes per point, 4.6 instead of 6.7 KB per block, which with the
     // 5.5 KB tile is what decides how many one-wavefront blocks a CU holds: 16 (the register file's limit) instead of 12.  The
     // per-block trace (scripts/microbench/scatter_trace_an.py) shows the launch as rounds of resident blocks -- 5 527 blocks of
     // 23 us in 1.8 rounds of 3 072 on level 0 -- and phase 2 is not bound by its instruction count (a branch-free form for runs of
     // one cell issued half the instructions per point and was no faster), so one more read and one more multiplication per
     // point (wx wy, the same f32 product phase 1 used to form) cost less than the fourth block per SIMD gains.
     float wx[4][SC_PTS], wy[4][SC_PTS];
-#endif
     float wz[4][SC_PTS];
     float4 sm[SC_PTS];          // sDisp xyz, sWeight
     int base[SC_PTS];           // tile offset of tap (0,0,0)
@@ -1065,12 +1042,8 @@ static_assert(offsetof(ScatterScratch, sm) % 16 == 0, "ScatterScratch::sm is rea
 #define FROG_FMAC_DPP(D, S, Q) "v_fmac_f32_dpp %" #D ", %" #S ", %8 quad_perm:[" #Q "," #Q "," #Q "," #Q "] row_mask:0xf bank_mask:0xf\n\t"
 // (Round 6, ADVICE r5: the statement is `volatile` now, and tests/test_gpu_round6.py holds this form against a build without it
 // bit for bit.  s_nop 4 -- which would also cover a vector write of EXEC, v_cmpx, right in front of the statement; the compiler
-// forms its masks with s_and_saveexec here -- was measured: scatter 0.0645 against 0.0629 ms, 650 steps 2 212 against 2 232 it/s;
-// -DFROG_DPP_NOP='"s_nop 4"' builds it.)
-#ifndef FROG_DPP_NOP
-#define FROG_DPP_NOP "s_nop 1"
-#endif
-#define FROG_FMAC4_DPP(Q) asm volatile(FROG_DPP_NOP "\n\t" FROG_FMAC_DPP(0, 4, Q) FROG_FMAC_DPP(1, 5, Q) FROG_FMAC_DPP(2, 6, Q) FROG_FMAC_DPP(3, 7, Q)      \
+// forms its masks with s_and_saveexec here -- was measured: scatter 0.0645 against 0.0629 ms, 650 steps 2 212 against 2 232 it/s.)
+#define FROG_FMAC4_DPP(Q) asm volatile("s_nop 1\n\t" FROG_FMAC_DPP(0, 4, Q) FROG_FMAC_DPP(1, 5, Q) FROG_FMAC_DPP(2, 6, Q) FROG_FMAC_DPP(3, 7, Q)      \
                               : "+v"(run.x), "+v"(run.y), "+v"(run.z), "+v"(run.w) : "v"(s.x), "v"(s.y), "v"(s.z), "v"(s.w), "v"(w))
 template <int P> __device__ __forceinline__ void fmac4_quad_bcast(float4 &run, const float4 s, float w)
 {
@@ -1217,13 +1190,8 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
         const int n_live = __popcll(live);
         if (base >= 0) {
             const int slot = __popcll(live & ((1ull << lane) - 1ull));
-#if FROG_SCATTER_WXY
-            #pragma unroll
-            for (int k = 0; k < 16; k++) sc.wxy[k][slot] = wxy[k];
-#else
             #pragma unroll
             for (int k = 0; k < 4; k++) { sc.wx[k][slot] = wx4[k]; sc.wy[k][slot] = wy4[k]; }
-#endif
             #pragma unroll
             for (int k = 0; k < 4; k++) sc.wz[k][slot] = wz[k];
             sc.sm[slot] = sm;
@@ -1235,7 +1203,7 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
         const unsigned long long tb2 = wall_clock64();
 #endif
 
-        // ---- phase 2: lane = tap (i + 4 j + 16 k); per point two lane-constant reads (wxy[i + 4 j], wz[k]) and one
+        // ---- phase 2: lane = tap (i + 4 j + 16 k); per point three lane-constant reads (wx[i], wy[j], wz[k]) and one
         // broadcast (the sums), w = (wx wy) wz (imageGroup.cxx:322) and the four products added into REGISTERS: points
         // are sorted by cell, so consecutive points mostly share their 64 tap addresses and the LDS tile is touched (one
         // ds_read_b128 + ds_write_b128, no atomic: the 64 taps are 64 distinct control points and the tile is private)
@@ -1246,7 +1214,7 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
             const int before = lane == 0 ? run_base : (lane < n_live ? sc.base[lane - 1] : -1);
             chg = __ballot(lane < n_live && mine != before);
         }
-#if FROG_SCATTER_QUADS && !FROG_SCATTER_WXY
+#if FROG_SCATTER_QUADS
         // Round 5.  The launch is bound by the LDS: point by point a tap's three weights are three ds_read_b32 (2 LDS cycles
         // each for the wavefront, however many lanes share an address) and the sums a broadcast ds_read_b128 (4): 10 cycles per
         // point and CU, 7 800 points per CU -> 33 us of a 64 us launch (level 0; on level 2 the tile's read-add-write at nearly
@@ -1287,25 +1255,16 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
             }
         }
 #else
-        float rwxy[SC_RING], rwz[SC_RING];
+        float rwx[SC_RING], rwz[SC_RING];
         float4 rsm[SC_RING];
-#if FROG_SCATTER_WXY
-        const float *lane_wxy = sc.wxy[lane & 15], *lane_wz = sc.wz[lane >> 4];
-        auto fetch = [&](int q, int slot) __attribute__((always_inline)) {
-            rwxy[slot] = lane_wxy[q];
-            rwz[slot] = lane_wz[q];
-            rsm[slot] = sc.sm[q];
-        };
-#else
         float rwy[SC_RING];
         const float *lane_wx = sc.wx[lane & 3], *lane_wy = sc.wy[(lane >> 2) & 3], *lane_wz = sc.wz[lane >> 4];
         auto fetch = [&](int q, int slot) __attribute__((always_inline)) {
-            rwxy[slot] = lane_wx[q];
+            rwx[slot] = lane_wx[q];
             rwy[slot] = lane_wy[q];
             rwz[slot] = lane_wz[q];
             rsm[slot] = sc.sm[q];
         };
-#endif
         auto add_point = [&](int q, int slot) __attribute__((always_inline)) {
             if ((chg >> q) & 1ull) {                               // wave-uniform: cell changed -> spill the run
                 if (run_base >= 0) {
@@ -1316,19 +1275,12 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
                 run = make_float4(0.f, 0.f, 0.f, 0.f);
                 run_base = __builtin_amdgcn_readfirstlane(sc.base[q]);
             }
-#if FROG_SCATTER_WXY
-            const float w = rwxy[slot] * rwz[slot];
-#else
-            const float w = (rwxy[slot] * rwy[slot]) * rwz[slot];          // (wx wy) wz, imageGroup.cxx:322 left to right
-#endif
+            const float w = (rwx[slot] * rwy[slot]) * rwz[slot];           // (wx wy) wz, imageGroup.cxx:322 left to right
             const float4 csm = rsm[slot];
-#if FROG_SCATTER_FMA
             // g += w s with ONE rounding: what imageGroup.cxx:330-337 computes ((float)((double) g + w * s): the product of two
-            // f32 values is exact in f64), and two v_pk_fma_f32 instead of two v_pk_mul_f32 + two v_pk_add_f32
+            // f32 values is exact in f64), and two v_pk_fma_f32 instead of two v_pk_mul_f32 + two v_pk_add_f32 (round 5: 0.0698 ->
+            // 0.0670 ms per launch, cfg 3)
             run.x = fmaf(w, csm.x, run.x); run.y = fmaf(w, csm.y, run.y); run.z = fmaf(w, csm.z, run.z); run.w = fmaf(w, csm.w, run.w);
-#else
-            run.x += w * csm.x; run.y += w * csm.y; run.z += w * csm.z; run.w += w * csm.w;
-#endif
         };
         #pragma unroll
         for (int j = 0; j < SC_AHEAD; j++) fetch(j, j);

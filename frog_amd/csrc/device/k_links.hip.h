@@ -34,9 +34,6 @@
 namespace frog {
 
 enum { SWEEP_LINEAR = 0, SWEEP_DEFORMABLE = 1, SWEEP_COUNT = 2 };
-#ifndef FROG_W1
-#define FROG_W1 1       // 0: the deformable sweeps evaluate inlier_probability twice per half-link, as the other sweeps do (A/B builds)
-#endif
 // Prefetch pipeline of the sweep: the record stream runs CHUNK_AHEAD chunks (of two steps)
 // ahead of the arithmetic, the partner-point gather PT_AHEAD steps; the loop is unrolled over
 // one period of both rings.
@@ -244,9 +241,6 @@ __device__ __forceinline__ long long wave_sum_ll(long long v)
 // BUILD (deformable sweep, narrow records): while walking EVERY record of its range the wavefront also writes the culling
 // list for the coordinates it reads -- what cull_build_kernel does in a pass of its own (0.6 ms for 1e8 records: a record,
 // two coordinates and a distance per half-link, all of which this kernel has in hand anyway).
-#ifdef FROG_W1_COUNT
-__device__ unsigned long long g_w1_count[8];    // steps, steps with a lane in the general form, lanes, lanes in the general form, lanes skipped as outliers, general-form lanes below lo
-#endif
 #ifdef FROG_SWEEP_TRACE
 // per (block, wavefront) of the last fused steady-state launch: wall_clock64 at kernel entry, tile known, staging barrier passed,
 // first step done, walk done, final barrier passed, end; records walked (scripts/microbench/sweep_trace_an.py)
@@ -265,12 +259,12 @@ __device__ unsigned long long g_sweep_trace[8 * 8 * 16384];
 // small the other way instead: blocks are dealt so that block % 8 = the tile's eighth of its image along the Morton curve
 // (tile_order), and a true match's partner lies in the same eighth of the partner image -- with the certified outliers
 // gone from the list (k_cull.hip.h) nearly every gather is a true match.
+// (A launch-bounds minimum of 7 for the fused form, which caps it at 72 VGPRs -- six wavefronts per SIMD and room for the side
+// stream's selection kernel beside them --, was measured slower: 0.260 against 0.254 ms.)
 template <int MODE, bool EMD_LDS, bool WIDE, bool BUILD = false, bool FUSED = false>
-#ifndef FROG_FUSED_MIN_WAVES
-#define FROG_FUSED_MIN_WAVES 1      // 7 caps the kernel at 72 VGPRs (six wavefronts per SIMD and room for the side stream's selection kernel beside them): measured slower, 0.260 against 0.254 ms
-#endif
-__global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? FROG_FUSED_MIN_WAVES : 1) void sweep_kernel(const SweepArgs a)
+__global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const SweepArgs a)
 {
+    static_assert(!(BUILD && FUSED), "the fused sweep does not write the culling list");
     static_assert(!BUILD || (MODE != SWEEP_COUNT && EMD_LDS && !WIDE), "the list is built by the narrow linear / deformable sweeps");
     static_assert(!FUSED || (MODE == SWEEP_DEFORMABLE && EMD_LDS), "the fused form is the deformable sweep's");
     constexpr int WAVES = FUSED ? 8 : 4;                // wavefronts per block
@@ -300,7 +294,7 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? FROG_FUSED_MIN_WAVES : 1
     EmDerived *emd_s = reinterpret_cast<EmDerived *>(tables);
     EmFast *emf_s = reinterpret_cast<EmFast *>(tables);            // W1: the deformable sweeps keep the one-exponential form here instead
     static_assert(sizeof(EmFast) == sizeof(EmDerived), "the two tables share their place");
-    constexpr bool W1 = FROG_W1 && MODE == SWEEP_DEFORMABLE;
+    constexpr bool W1 = MODE == SWEEP_DEFORMABLE;
     uint32_t *img_base_s = reinterpret_cast<uint32_t *>(tables + (size_t)a.lds_images * sizeof(EmDerived));   // narrow records: first point of the group's images
     float *cut_s = reinterpret_cast<float *>(img_base_s + a.lds_images);      // BUILD: list cutoff of the group's images
     __shared__ uint32_t last_step_s[BUILD ? WAVES * TILE_POINTS : 1];         // BUILD: see cull_build_kernel
@@ -482,20 +476,6 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? FROG_FUSED_MIN_WAVES : 1
             w = inlier_weight_pair(d2, fA, fB, in_range);
             asm volatile("" : "+v"(w));                     // formed by every lane, in front of the branch: the compiler otherwise moves it --
                                                             // and the table read it starts with -- behind the range test, one more LDS round trip in the chain
-#ifdef FROG_W1_NOMID
-            in_range = true;
-#endif
-#ifdef FROG_W1_COUNT
-            if constexpr (FUSED && !BUILD) {
-                const bool skip = w < a.threshold - a.band, mid = !in_range && !skip;
-                const unsigned long long all = __ballot(true), mm = __ballot(mid), sk = __ballot(skip), lo_m = __ballot(mid && d2 < fB.lo);
-                if (lane == __builtin_ctzll(all)) {
-                    atomicAdd(&g_w1_count[0], 1ull); atomicAdd(&g_w1_count[1], mm ? 1ull : 0ull);
-                    atomicAdd(&g_w1_count[2], (unsigned long long)__popcll(all)); atomicAdd(&g_w1_count[3], (unsigned long long)__popcll(mm));
-                    atomicAdd(&g_w1_count[4], (unsigned long long)__popcll(sk)); atomicAdd(&g_w1_count[5], (unsigned long long)__popcll(lo_m));
-                }
-            }
-#endif
             if (!in_range && !(w < a.threshold - a.band)) { // rare: far tails of the inlier component, d < 0.1, degenerate mixtures
                 const uint32_t imgB = img_of(rq) + (WIDE && !EMD_LDS ? 0u : g_first);
                 w = fminf(inlier_probability(d2, eA), inlier_probability(d2, a.emd[imgB]));
@@ -641,8 +621,7 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, FUSED ? FROG_FUSED_MIN_WAVES : 1
             for (uint32_t k = lane; k < pt_count; k += 64) {                 // written once, read once: non-temporal
                 const float4 v = my[k];
                 float4 *dst = a.group_sums + group_sum_index(xcd, pt_begin - a.own_pt_begin + k, a.own_points);
-                if (SUMS_POINT_MAJOR) *dst = v;                              // pieces of a line other XCDs complete: let the caches merge them
-                else __builtin_nontemporal_store((v4f){ v.x, v.y, v.z, v.w }, reinterpret_cast<v4f *>(dst));
+                __builtin_nontemporal_store((v4f){ v.x, v.y, v.z, v.w }, reinterpret_cast<v4f *>(dst));
             }
         }
     } else {

@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256) void em_kernel(const float *samples, const uin
 // About one batch in five stops once; the chain of a batch costs ~60 instructions instead of 64 dependent additions
 // of 30+ cycles each.  The memberships t, which do not depend on each other, are computed by all sixteen wavefronts
 // of the block for a chunk of samples at a time (LDS), then three wavefronts run the four chains over the chunk.
-// Checked against em_kernel (the term-by-term form, kept: FROG_EM_SERIAL=1, frog_test_em_refit) bit for bit
+// Checked against em_kernel (the term-by-term form, kept for frog_test_em_refit) bit for bit
 // (tests/test_gpu_fullsize.py).
 constexpr int EM_THREADS = 1024;
 constexpr int EM_CHUNK = 8192;

@@ -320,10 +320,13 @@ __global__ __launch_bounds__(MATCH_BLOCK) void match_qrange_kernel(const MatchAr
 
 // hmax[query][2 * tile + half] = the largest product among the 16 candidates of that half tile that pass the query's
 // filters (-inf if none); blockIdx.y splits the candidate tiles of the query block's range.
-template <int D, bool ANAT, int G>
-__global__ __launch_bounds__(MATCH_BLOCK * 2 / G) void match_mfma_kernel(const MatchArgs a, const uint2 *ranges, const QRange *qr,
+template <int D, bool ANAT>
+__global__ __launch_bounds__(MATCH_BLOCK) void match_mfma_kernel(const MatchArgs a, const uint2 *ranges, const QRange *qr,
                                                                  const float *q_mf, const float *c_mf, float *hmax)
 {
+    // query groups per wavefront: 4 halves the candidate loads per product but needs 234 registers (2 wavefronts per SIMD
+    // instead of 3); measured the same within noise (5 971 vs 5 982 image pairs/s)
+    constexpr int G = 2;
     constexpr int STEPS = (D + 2) / 2;              // MFMA instructions per 32 x 32 tile (K = 2 each)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
@@ -1338,7 +1341,7 @@ int frog_matcher_run(frog_matcher *m, const uint16_t *first, const uint16_t *sec
     RCHECK(hipEventCreate(&t1));
     RCHECK(hipMemsetAsync(m->n_dist, 0, (STAT_BASE + 3 * STAT_SLOTS) * sizeof(unsigned long long), m->stream));
     RCHECK(hipEventRecord(t0, m->stream));
-    static const int n_streams = getenv("FROG_MATCH_STREAMS") ? std::min(4, std::max(1, atoi(getenv("FROG_MATCH_STREAMS")))) : 4;   // measured, image pairs/s: 1 stream 4537, 2: 5832, 3: 6345, 4: 6652 (a slot is reused only after the host has waited for it)
+    constexpr int n_streams = 4;        // stream + extra[]; measured, image pairs/s: 1 stream 4537, 2: 5832, 3: 6345, 4: 6652 (a slot is reused only after the host has waited for it)
     for (int k = 1; k < n_streams; k++) RCHECK(hipStreamWaitEvent(m->extra[k - 1], t0, 0));
 
     // upstream's `match` variable lives across the queries of one ComputeMatches call
@@ -1370,7 +1373,7 @@ int frog_matcher_run(frog_matcher *m, const uint16_t *first, const uint16_t *sec
     // pass since the filter moved to the bf16 cores.  Collector threads do it beside the thread that queues the work: a job's
     // passes (forward, then -sym's reverse) always go to the same thread, in order; a ring slot is reused once its pass has
     // been collected.
-    static const int n_collectors = getenv("FROG_MATCH_COLLECTORS") ? std::min(8, std::max(1, atoi(getenv("FROG_MATCH_COLLECTORS")))) : 3;
+    constexpr int n_collectors = 3;
     for (int r = 0; r < RING; r++) slot_free[r].store(true);
     for (int k = 0; k < n_collectors; k++)
         try { collectors.emplace_back([&, k]() {
@@ -1435,11 +1438,10 @@ int frog_matcher_run(frog_matcher *m, const uint16_t *first, const uint16_t *sec
                 // The bf16 form (round 5) multiplies a tile five times faster and pays the same for its block's query operands:
                 // 64 tiles per block (image pairs/s with 4 / 8 / 16 / 32 / 64 / 128: 7 957 / 8 606 / 8 475 / 8 474 / 9 209 / 8 562;
                 // the blocks of a pass no longer fill the chip -- 158 of them -- but four streams of passes do)
-                static const int tiles_env = getenv("FROG_MATCH_TILES") ? std::max(1, atoi(getenv("FROG_MATCH_TILES"))) : 0;
                 static const bool force_f32 = getenv("FROG_MATCH_F32") != nullptr;
                 const bool bf16 = !force_f32 && Q.bf16_ok && C.bf16_ok;
                 m->last_forms[bf16 ? 2 : 1]++;
-                const uint32_t tiles_per_block = tiles_env ? (uint32_t)tiles_env : (bf16 ? 64u : 8u);
+                const uint32_t tiles_per_block = bf16 ? 64u : 8u;
                 a.splits = std::max(1u, std::min(splits_max, (C.n / 5 / MF_TILE + tiles_per_block - 1) / tiles_per_block));
                 QRange *qr = qrange + (size_t)slot * max_n;
                 float *hm = hmax + (size_t)slot * hmax_slot;
@@ -1447,9 +1449,6 @@ int frog_matcher_run(frog_matcher *m, const uint16_t *first, const uint16_t *sec
                 const dim3 mgrid(q_blocks, a.splits);
                 int *dst = d_out + (size_t)slot * max_n;
                 const bool anat = o->anat != 0.f;
-                // query groups per wavefront: 4 halves the candidate loads per product but needs 234 registers (2 wavefronts per
-                // SIMD instead of 3); measured the same within noise (5 971 vs 5 982 image pairs/s), so 2 stays the default
-                static const int mf_groups = getenv("FROG_MATCH_GROUPS") && atoi(getenv("FROG_MATCH_GROUPS")) == 4 ? 4 : 2;
                 match_qrange_kernel<<<q_blocks, MATCH_BLOCK, 0, st>>>(a, qr, rg);
                 // the bf16 matrix cores by default (16 x the f32 rate, a wider but proven bound: match_mfma16_kernel);
                 // FROG_MATCH_F32=1 keeps the f32 chain (A/B, tests)
@@ -1457,8 +1456,7 @@ int frog_matcher_run(frog_matcher *m, const uint16_t *first, const uint16_t *sec
 #define MF_LAUNCH(DD, AA)                                                                                               \
                 do {                                                                                                    \
                     if (bf16) match_mfma16_kernel<DD, AA><<<mgrid, MATCH_BLOCK, 0, st>>>(a, rg, qr, (const uint4 *)Q.mfb16, (const uint4 *)C.mfa16, hm); \
-                    else if (mf_groups == 4) match_mfma_kernel<DD, AA, 4><<<mgrid, MATCH_BLOCK / 2, 0, st>>>(a, rg, qr, Q.mf, C.mf, hm); \
-                    else match_mfma_kernel<DD, AA, 2><<<mgrid, MATCH_BLOCK, 0, st>>>(a, rg, qr, Q.mf, C.mf, hm);       \
+                    else match_mfma_kernel<DD, AA><<<mgrid, MATCH_BLOCK, 0, st>>>(a, rg, qr, Q.mf, C.mf, hm);          \
                     match_scan_kernel<DD, AA><<<(nq + SCAN_BLOCK / 16 - 1) / (SCAN_BLOCK / 16), SCAN_BLOCK, 0, st>>>(a, rg, qr, Q.norm, C.norm_max, hm, \
                                                                                        o->threshold, o->dist2second, dst); \
                 } while (0)

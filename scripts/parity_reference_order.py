@@ -17,7 +17,7 @@ class Env:                       # the two calls of monkeypatch the test helper 
 
 
 tag = ""
-if "--tag" in sys.argv:                      # a suffix of the output file (scripts/bisect_parity.sh: one file per cell)
+if "--tag" in sys.argv:                      # a suffix of the output file (one file per cell of a bisection: profiles/r06_parity_bisect.txt)
     k = sys.argv.index("--tag"); tag = "_" + sys.argv[k + 1]; del sys.argv[k:k + 2]
 argv = [a for a in sys.argv[1:] if a != "--config5"]
 cfg5 = "--config5" in sys.argv[1:]          # BASELINE.json configs[4]: 500 images, ~60 partners each, five levels

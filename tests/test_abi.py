@@ -111,3 +111,29 @@ def test_host_threads_follow_the_usable_cpus(monkeypatch):
     assert int(subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout) == min(n, 64)
     env["OMP_NUM_THREADS"] = "1"
     assert int(subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout) == 1
+
+
+def test_environment_table_matches_the_sources():
+    """INTEGRATION.md section F has a row for every FROG_* variable the native sources read with getenv, and every variable
+    in its first column is still read: by the native sources, frog_amd/*.py, bench.py or bench_match.py."""
+    root = os.path.dirname(INC)
+    native = set()
+    for base, _, files in os.walk(os.path.join(root, "frog_amd", "csrc")):
+        for f in files:
+            if f.endswith((".cpp", ".h", ".hip")):
+                native |= set(re.findall(r'getenv\("(FROG_[A-Z0-9_]+)"\)', open(os.path.join(base, f), errors="ignore").read()))
+    python = set()
+    pkg = os.path.join(root, "frog_amd")
+    for path in [os.path.join(pkg, f) for f in os.listdir(pkg) if f.endswith(".py")] + \
+                [os.path.join(root, "bench.py"), os.path.join(root, "bench_match.py")]:
+        python |= set(re.findall(r'["\'](FROG_[A-Z0-9_]+)["\']', open(path).read()))
+    text = open(os.path.join(root, "INTEGRATION.md")).read()
+    section = text[text.index("## F. Environment switches"):]
+    section = section[:section.index("\n## ")] if "\n## " in section else section
+    table = set()
+    for line in section.splitlines():
+        if line.startswith("| `"):
+            table |= set(re.findall(r"\bFROG_[A-Z0-9_]+", re.split(r"(?<!\\)\|", line)[1]))
+    assert len(native) >= 30 and len(table) >= len(native)
+    assert sorted(native - table) == [], "read by the native sources, missing from INTEGRATION.md section F"
+    assert sorted(table - native - python) == [], "in INTEGRATION.md section F, read by nothing"

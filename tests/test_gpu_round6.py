@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 # ---- (1) product path vs reference-order mode, cfg 3, -li 50 -dl 3 -di 200 ------------------------------------------------------
-# Bisected in round 6 (scripts/bisect_parity.sh, profiles/r06_parity_bisect.txt): of round 5's two arithmetic
+# Bisected in round 6 (profiles/r06_parity_bisect.txt): of round 5's two arithmetic
 # changes the scatter's fused multiply-add moves NOTHING (cells fma / two roundings agree to three digits on every lattice), the
 # f32 form of the B-spline transform (K11) moves the raw coefficients of ONE rim node (second level-2 lattice, image 45 node 6037:
 # support 5.7e-8 from a single point, node weight 1.9e-20) from 2.0e-4 to 4.2e-3 of max|c| and the whole chain on a dense lattice
