@@ -254,6 +254,10 @@ HIP_SYMBOLS = {
                                    c_double_p]),
     "frog_chain_invert_links": (C.c_int, [C.POINTER(FrogChainLink), C.c_uint32, C.POINTER(FrogChainLink)]),
     "frog_chain_reslice": (C.c_int, [C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double]),
+    "frog_average_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "frog_average_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_int, C.c_double, C.POINTER(FrogVolume)]),
+    "frog_average_finish": (C.c_int, [C.c_void_p, c_float_p, c_float_p]),
+    "frog_average_destroy": (None, [C.c_void_p]),
     "frog_match_options_default": (None, [C.POINTER(FrogMatchOptions)]),
     "frog_matcher_create": (C.c_int, [C.POINTER(FrogKeypoints), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_matcher_destroy": (None, [C.c_void_p]),
@@ -326,6 +330,7 @@ HOST_SYMBOLS = {
     "frog_volume_view": (None, [C.c_void_p, C.POINTER(FrogVolume)]),
     "frog_volume_range": (C.c_int, [C.POINTER(FrogVolume), c_double_p, c_double_p]),
     "frog_volume_write": (C.c_int, [C.c_char_p, C.POINTER(FrogVolume)]),
+    "frog_bbox_grid": (C.c_int, [C.c_char_p, C.c_double, C.POINTER(FrogVolume)]),
     "frog_keypoints_read": (C.c_void_p, [C.c_char_p, C.POINTER(C.c_int)]),
     "frog_keypoints_free": (None, [C.c_void_p]),
     "frog_keypoints_count": (C.c_uint32, [C.c_void_p]),

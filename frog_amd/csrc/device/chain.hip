@@ -188,23 +188,28 @@ __device__ __forceinline__ S to_voxel(double v)
     }
 }
 
+// Geometry of one reslice: the source's voxel grid (s*) and the output grid (n*, o*), as frog_volume gives them.
+struct ResliceGrid {
+    int sx, sy, sz;
+    double so[3], ss[3];
+    uint32_t nx, ny, nz;
+    double oo[3], os[3];
+    int linear;
+    double background;
+};
+
+// Output voxel idx (x fastest) of a reslice: what reslice_kernel stores and reslice_accumulate_kernel adds.
 template <class S>
-__global__ __launch_bounds__(256) void reslice_kernel(const DevLink *links, int n_links, const S *__restrict__ src,
-                                                      int sx, int sy, int sz, double so0, double so1, double so2,
-                                                      double ss0, double ss1, double ss2,
-                                                      uint32_t nx, uint32_t ny, uint32_t nz, double oo0, double oo1, double oo2,
-                                                      double os0, double os1, double os2, int linear, double background,
-                                                      S *__restrict__ out)
+__device__ __forceinline__ S reslice_voxel(const DevLink *links, int n_links, const S *__restrict__ src, const ResliceGrid &g, size_t idx)
 {
-    const size_t total = (size_t)nx * ny * nz;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= total) return;
+    const uint32_t nx = g.nx, ny = g.ny;
+    const int sx = g.sx, sy = g.sy, sz = g.sz;
     const uint32_t i = (uint32_t)(idx % nx), j = (uint32_t)((idx / nx) % ny), k = (uint32_t)(idx / ((size_t)nx * ny));
-    double p[3] = { oo0 + i * os0, oo1 + j * os1, oo2 + k * os2 }, A[3][3];
+    double p[3] = { g.oo[0] + i * g.os[0], g.oo[1] + j * g.os[1], g.oo[2] + k * g.os[2] }, A[3][3];
     chain_point<false>(links, n_links, p, A);
-    const double c[3] = { (p[0] - so0) / ss0, (p[1] - so1) / ss1, (p[2] - so2) / ss2 };
+    const double c[3] = { (p[0] - g.so[0]) / g.ss[0], (p[1] - g.so[1]) / g.ss[1], (p[2] - g.so[2]) / g.ss[2] };
     const int dims[3] = { sx, sy, sz };
-    double v = background;
+    double v = g.background;
     bool inside = true;
     for (int a = 0; a < 3; a++) inside = inside && c[a] >= -0.5 && c[a] <= (double)dims[a] - 0.5;
     if (inside) {
@@ -214,7 +219,7 @@ __global__ __launch_bounds__(256) void reslice_kernel(const DevLink *links, int 
             z = z < 0 ? 0 : (z >= sz ? sz - 1 : z);
             return (double)src[(size_t)x + (size_t)sx * ((size_t)y + (size_t)sy * (size_t)z)];
         };
-        if (!linear) {
+        if (!g.linear) {
             v = at((int)floor(c[0] + 0.5), (int)floor(c[1] + 0.5), (int)floor(c[2] + 0.5));
         } else {
             const double f0 = floor(c[0]), f1 = floor(c[1]), f2 = floor(c[2]);
@@ -225,7 +230,65 @@ __global__ __launch_bounds__(256) void reslice_kernel(const DevLink *links, int 
               + fz * (ry * (rx * at(x0, y0, z0 + 1) + fx * at(x0 + 1, y0, z0 + 1)) + fy * (rx * at(x0, y0 + 1, z0 + 1) + fx * at(x0 + 1, y0 + 1, z0 + 1)));
         }
     }
-    out[idx] = to_voxel<S>(v);
+    return to_voxel<S>(v);
+}
+
+template <class S>
+__global__ __launch_bounds__(256) void reslice_kernel(const DevLink *links, int n_links, const S *__restrict__ src, const ResliceGrid g,
+                                                      S *__restrict__ out)
+{
+    const size_t total = (size_t)g.nx * g.ny * g.nz;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    out[idx] = reslice_voxel<S>(links, n_links, src, g, idx);
+}
+
+// ---- mean / stdev of a registered group (tools/AverageVolumes.cxx:47-59, :68-74) -----------------------------------------
+// One thread owns one voxel of the two f32 accumulators: the images are added in call order, no atomics, so the sums are
+// the reference's own sequence.  Each value goes to float first (vtkImageCast), then avg += v / n, sq += (v * v) / n with
+// n = (float)n_images; -ffp-contract=off keeps the product and the quotient separately rounded (no FMA), and gfx950's
+// f32 division and sqrt are the correctly rounded sequences under -fno-fast-math.
+template <class S>
+__device__ __forceinline__ void accumulate(float *__restrict__ avg, float *__restrict__ sq, size_t idx, S value, float n)
+{
+    const float v = (float)value;
+    avg[idx] += v / n;
+    sq[idx] += (v * v) / n;
+}
+
+// the source resliced onto the grid (reslice_voxel, the same code as reslice_kernel), then added; `out` (may be null)
+// receives the resliced voxel in the source's type, what VolumeTransform would have written
+template <class S>
+__global__ __launch_bounds__(256) void reslice_accumulate_kernel(const DevLink *links, int n_links, const S *__restrict__ src,
+                                                                 const ResliceGrid g, float n, float *__restrict__ avg,
+                                                                 float *__restrict__ sq, S *__restrict__ out)
+{
+    const size_t total = (size_t)g.nx * g.ny * g.nz;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const S r = reslice_voxel<S>(links, n_links, src, g, idx);
+    if (out) out[idx] = r;
+    accumulate<S>(avg, sq, idx, r, n);
+}
+
+// a source already on the grid (AverageVolumes' own inputs)
+template <class S>
+__global__ __launch_bounds__(256) void identity_accumulate_kernel(const S *__restrict__ src, size_t total, float n,
+                                                                  float *__restrict__ avg, float *__restrict__ sq)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    accumulate<S>(avg, sq, idx, src[idx], n);
+}
+
+// stdev = sqrt(sq - avg * avg) in place of sq: NaN where the f32 difference rounds negative, as in the reference
+__global__ __launch_bounds__(256) void average_finish_kernel(const float *__restrict__ avg, float *__restrict__ sq, size_t total)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const float a = avg[idx];
+    const float a2 = a * a;
+    sq[idx] = sqrtf(sq[idx] - a2);
 }
 
 __global__ __launch_bounds__(256) void chain_apply_kernel(const DevLink *links, int n_links, const double *in, double *out, size_t n)
@@ -435,6 +498,17 @@ int frog_chain_invert_links(const frog_chain_link *in, uint32_t n, frog_chain_li
 extern "C++" {
 namespace {
 
+ResliceGrid reslice_grid(const frog_volume *src, const frog_volume *out, int interpolation, double background)
+{
+    ResliceGrid g;
+    g.sx = (int)src->dims[0]; g.sy = (int)src->dims[1]; g.sz = (int)src->dims[2];
+    g.nx = out->dims[0]; g.ny = out->dims[1]; g.nz = out->dims[2];
+    for (int k = 0; k < 3; k++) { g.so[k] = src->origin[k]; g.ss[k] = src->spacing[k]; g.oo[k] = out->origin[k]; g.os[k] = out->spacing[k]; }
+    g.linear = interpolation != 0;
+    g.background = background;
+    return g;
+}
+
 template <class S>
 int reslice_typed(frog_chain *c, const frog_volume *src, frog_volume *out, int interpolation, double background)
 {
@@ -444,11 +518,8 @@ int reslice_typed(frog_chain *c, const frog_volume *src, frog_volume *out, int i
     if (hipMalloc((void **)&d_out, n_out * sizeof(S)) != hipSuccess) { (void)hipFree(d_src); return fail(FROG_E_NOMEM, "hipMalloc (output volume)"); }
     hipError_t e = hipMemcpy(d_src, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        reslice_kernel<S><<<(unsigned)((n_out + 255) / 256), 256>>>(
-            c->d_links, (int)c->h_links.size(), d_src, (int)src->dims[0], (int)src->dims[1], (int)src->dims[2],
-            src->origin[0], src->origin[1], src->origin[2], src->spacing[0], src->spacing[1], src->spacing[2],
-            out->dims[0], out->dims[1], out->dims[2], out->origin[0], out->origin[1], out->origin[2],
-            out->spacing[0], out->spacing[1], out->spacing[2], interpolation != 0, background, d_out);
+        reslice_kernel<S><<<(unsigned)((n_out + 255) / 256), 256>>>(c->d_links, (int)c->h_links.size(), d_src,
+                                                                     reslice_grid(src, out, interpolation, background), d_out);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out->data, d_out, n_out * sizeof(S), hipMemcpyDeviceToHost);
@@ -479,6 +550,149 @@ int frog_chain_reslice(frog_chain *c, const frog_volume *src, frog_volume *out, 
     case FROG_V_F32: return reslice_typed<float>(c, src, out, interpolation, background);
     default: return reslice_typed<double>(c, src, out, interpolation, background);
     }
+}
+
+
+// ---- frog_average: mean and stdev of a group on one grid ------------------------------------------------------------------
+
+struct frog_average {
+    int device = 0;
+    frog_volume grid;
+    uint32_t n_images = 0, added = 0;
+    bool finished = false;
+    size_t total = 0;
+    float *d_avg = nullptr, *d_sq = nullptr;
+    void *d_src = nullptr, *d_out = nullptr;       // staging of the current source / resliced volume, grown on demand
+    size_t src_bytes = 0, out_bytes = 0;
+};
+
+extern "C++" {
+namespace {
+
+int grow(void **p, size_t *have, size_t want)
+{
+    if (*have >= want) return FROG_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
+    if (hipMalloc(p, want) != hipSuccess) { *p = nullptr; return fail(FROG_E_NOMEM, "hipMalloc (average staging)"); }
+    *have = want;
+    return FROG_OK;
+}
+
+template <class S>
+int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+{
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    const unsigned blocks = (unsigned)((a->total + 255) / 256);
+    const float n = (float)a->n_images;
+    if (int rc = grow(&a->d_src, &a->src_bytes, n_src * sizeof(S))) return rc;
+    if (c && resliced) if (int rc = grow(&a->d_out, &a->out_bytes, a->total * sizeof(S))) return rc;
+    hipError_t e = hipMemcpy(a->d_src, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (c)
+            reslice_accumulate_kernel<S><<<blocks, 256>>>(c->d_links, (int)c->h_links.size(), (const S *)a->d_src,
+                                                          reslice_grid(src, &a->grid, interpolation, background), n, a->d_avg, a->d_sq,
+                                                          resliced ? (S *)a->d_out : nullptr);
+        else
+            identity_accumulate_kernel<S><<<blocks, 256>>>((const S *)a->d_src, a->total, n, a->d_avg, a->d_sq);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && resliced) {
+        if (c) e = hipMemcpy(resliced->data, a->d_out, a->total * sizeof(S), hipMemcpyDeviceToHost);
+        else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_average_add: ") + hipGetErrorString(e));
+    return FROG_OK;
+}
+
+} // namespace
+} // extern "C++"
+
+void frog_average_destroy(frog_average *a)
+{
+    if (!a) return;
+    if (a->d_avg || a->d_sq || a->d_src || a->d_out) {
+        (void)hipSetDevice(a->device);
+        for (void *p : { (void *)a->d_avg, (void *)a->d_sq, a->d_src, a->d_out }) if (p) (void)hipFree(p);
+    }
+    delete a;
+}
+
+int frog_average_create(const frog_volume *grid, uint32_t n_images, int device, frog_average **out)
+{
+    if (!grid || !out || !n_images) return fail(FROG_E_INVALID, "bad arguments to frog_average_create");
+    const size_t total = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
+    if (!total) return fail(FROG_E_INVALID, "empty grid");
+    // one thread per voxel, 256 per block: a grid above 2^31 voxels is refused here rather than launched
+    if (total > ((size_t)1 << 31)) return fail(FROG_E_INVALID, "grid above 2^31 voxels");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FROG_E_NODEVICE, "no HIP device: no CPU fallback");
+    if (device < 0 || device >= count) return fail(FROG_E_INVALID, "bad device index");
+    KCHECK(hipSetDevice(device));
+    frog_average *a = new (std::nothrow) frog_average;
+    if (!a) return fail(FROG_E_NOMEM, "out of host memory");
+    a->device = device;
+    a->grid = *grid;
+    a->grid.data = nullptr;
+    a->n_images = n_images;
+    a->total = total;
+    if (hipMalloc((void **)&a->d_avg, total * sizeof(float)) != hipSuccess || hipMalloc((void **)&a->d_sq, total * sizeof(float)) != hipSuccess) {
+        frog_average_destroy(a);
+        return fail(FROG_E_NOMEM, "hipMalloc (average accumulators)");
+    }
+    // both accumulators start at zero (the reference never clears its stdev image: AverageVolumes.cxx:31-43)
+    if (hipMemset(a->d_avg, 0, total * sizeof(float)) != hipSuccess || hipMemset(a->d_sq, 0, total * sizeof(float)) != hipSuccess) {
+        frog_average_destroy(a);
+        return fail(FROG_E_HIP, "hipMemset (average accumulators)");
+    }
+    *out = a;
+    return FROG_OK;
+}
+
+int frog_average_add(frog_average *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+{
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_average_add");
+    if (a->finished || a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_average_add: more volumes than n_images");
+    if (c && c->device != a->device) return fail(FROG_E_INVALID, "frog_average_add: chain and accumulator on different devices");
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    if (!n_src) return fail(FROG_E_INVALID, "empty volume");
+    for (int k = 0; k < 3; k++) {
+        if (c && (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad source geometry");
+        if (!c && src->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_average_add: volume dimensions differ from the grid's");
+        if (resliced && resliced->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_average_add: resliced volume is not grid-sized");
+    }
+    if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, "frog_average_add: resliced volume must have the source's type");
+    KCHECK(hipSetDevice(a->device));
+    int rc;
+    switch (src->dtype) {
+    case FROG_V_U8: rc = average_add_typed<uint8_t>(a, c, src, interpolation, background, resliced); break;
+    case FROG_V_I8: rc = average_add_typed<int8_t>(a, c, src, interpolation, background, resliced); break;
+    case FROG_V_U16: rc = average_add_typed<uint16_t>(a, c, src, interpolation, background, resliced); break;
+    case FROG_V_I16: rc = average_add_typed<int16_t>(a, c, src, interpolation, background, resliced); break;
+    case FROG_V_U32: rc = average_add_typed<uint32_t>(a, c, src, interpolation, background, resliced); break;
+    case FROG_V_I32: rc = average_add_typed<int32_t>(a, c, src, interpolation, background, resliced); break;
+    case FROG_V_F32: rc = average_add_typed<float>(a, c, src, interpolation, background, resliced); break;
+    default: rc = average_add_typed<double>(a, c, src, interpolation, background, resliced); break;
+    }
+    if (rc == FROG_OK) a->added++;
+    return rc;
+}
+
+int frog_average_finish(frog_average *a, float *mean, float *stdev)
+{
+    if (!a || !mean || !stdev) return fail(FROG_E_INVALID, "bad arguments to frog_average_finish");
+    if (a->added != a->n_images) return fail(FROG_E_INVALID, "frog_average_finish: fewer volumes added than n_images");
+    KCHECK(hipSetDevice(a->device));
+    hipError_t e = hipSuccess;
+    if (!a->finished) {
+        average_finish_kernel<<<(unsigned)((a->total + 255) / 256), 256>>>(a->d_avg, a->d_sq, a->total);
+        e = hipGetLastError();
+        a->finished = e == hipSuccess;                 // stdev now stands in place of sq: a second call only copies
+    }
+    if (e == hipSuccess) e = hipMemcpy(mean, a->d_avg, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(stdev, a->d_sq, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_average_finish: ") + hipGetErrorString(e));
+    return FROG_OK;
 }
 
 }

@@ -232,4 +232,39 @@ int frog_volume_geometry(const char *path, uint32_t dims[3], double spacing[3], 
     return nifti_geometry(raw, dims, spacing, origin, nullptr, nullptr, nullptr) ? FROG_OK : FROG_E_INVALID;
 }
 
+
+// DummyVolumeGenerator.cxx:43-67: the grid over the box that bbox.json records (ImageGroup::saveStatsJSON writes it):
+// origin = bbox[0], `spacing` on every axis, dims = ceil((max - min) / spacing) in double
+int frog_bbox_grid(const char *bbox_json, double spacing, frog_volume *grid)
+{
+    if (!bbox_json || !grid || !(spacing > 0) || !std::isfinite(spacing)) return FROG_E_INVALID;
+    std::ifstream in(bbox_json, std::ios::binary);
+    if (!in) return FROG_E_INVALID;
+    std::stringstream ss;
+    ss << in.rdbuf();
+    const std::string text = ss.str();
+    JParser jp{ text.data(), text.data() + text.size() };
+    const JValue root = jp.value();
+    const JValue *box = jp.ok ? root.get("bbox") : nullptr;
+    if (!box || box->kind != JValue::Array || box->arr.size() != 2) return FROG_E_INVALID;
+    for (const JValue &corner : box->arr) {
+        if (corner.kind != JValue::Array || corner.arr.size() != 3) return FROG_E_INVALID;
+        for (const JValue &v : corner.arr) if (v.kind != JValue::Number || !std::isfinite(v.num)) return FROG_E_INVALID;
+    }
+    frog_volume g;
+    std::memset(&g, 0, sizeof g);
+    for (int k = 0; k < 3; k++) {
+        const double mn = box->arr[0].arr[k].num, mx = box->arr[1].arr[k].num;
+        const double d = std::ceil((mx - mn) / spacing);
+        if (!(d >= 1) || d > 2147483647.0) return FROG_E_INVALID;     // an empty or inverted box, or beyond upstream's int dims
+        g.dims[k] = (uint32_t)d;
+        g.origin[k] = mn;
+        g.spacing[k] = spacing;
+    }
+    g.dtype = FROG_V_F32;
+    g.data = nullptr;
+    *grid = g;
+    return FROG_OK;
+}
+
 }

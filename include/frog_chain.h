@@ -94,6 +94,28 @@ static inline size_t frog_volume_voxel_bytes(int dtype)
  * type's range, as vtkImageReslice does. */
 int frog_chain_reslice(frog_chain *c, const frog_volume *source, frog_volume *out, int interpolation, double background);
 
+/* ---- mean and stdev of a registered group (tools/AverageVolumes.cxx; transform.sh's last two steps) ----------------
+ * An accumulator of n_images volumes on `grid` (dims, origin, spacing; its dtype and data are ignored).  Per voxel and in
+ * the order the volumes are added, as AverageVolumes.cxx:47-59 / :68-74 does it in f32:
+ *     v = (float)value;  avg += v / n;  sq += (v * v) / n;          n = (float)n_images
+ *     stdev = sqrt(sq - avg * avg)                                  correctly rounded f32 sqrt of the f32 difference
+ * Where that difference rounds negative the stdev is NaN, as in the reference.  One device thread owns each voxel, no
+ * atomics: the results are deterministic.  Two deviations from the reference: `sq` starts at zero (upstream never clears
+ * its stdev image), and a volume whose dims differ from the grid's is an error (upstream reads past its buffer).
+ * A grid above 2^31 voxels is refused (FROG_E_INVALID) before the device is touched. */
+typedef struct frog_average frog_average;
+int  frog_average_create(const frog_volume *grid, uint32_t n_images, int device, frog_average **out);
+/* chain == NULL: `source` is already on the grid (its dims must equal the grid's) -- AverageVolumes.
+ * chain != NULL: `source` is resliced onto the grid exactly as frog_chain_reslice(chain, source, out, interpolation,
+ * background) would (same device code), i.e. converted to the source's type (rounded half up and clamped), then added.
+ * `resliced` (may be NULL; dims the grid's, dtype the source's) receives that volume.  More than n_images calls, a chain
+ * on another device or bad geometry -> FROG_E_INVALID. */
+int  frog_average_add(frog_average *a, frog_chain *chain, const frog_volume *source, int interpolation, double background,
+                      frog_volume *resliced);
+/* After exactly n_images adds (else FROG_E_INVALID): float32 mean and stdev into grid-sized host buffers, x fastest. */
+int  frog_average_finish(frog_average *a, float *mean, float *stdev);
+void frog_average_destroy(frog_average *a);
+
 #ifdef __cplusplus
 }
 #endif

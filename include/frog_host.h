@@ -204,6 +204,12 @@ void frog_volume_view(const frog_volume_file *f, frog_volume *out);
 int frog_volume_range(const frog_volume *v, double *lo, double *hi);
 int frog_volume_write(const char *path, const frog_volume *v);
 
+/* ---- the common-space grid of the average image (tools/DummyVolumeGenerator.cxx:43-67) ----------------------------
+ * Reads bbox.json as ImageGroup::saveStatsJSON writes it ({"bbox": [[min x, y, z], [max x, y, z]], ...}) and fills `grid`:
+ * origin = min, `spacing` on every axis, dims[k] = ceil((max - min) / spacing) in double, dtype FROG_V_F32, data NULL.
+ * A missing file, a missing or malformed box, an empty box or spacing <= 0 -> FROG_E_INVALID. */
+int frog_bbox_grid(const char *bbox_json, double spacing, frog_volume *grid);
+
 #ifdef __cplusplus
 }
 #endif
