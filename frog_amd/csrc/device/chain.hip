@@ -6,7 +6,9 @@
 
 #include "frog_chain.h"
 
+#include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <type_traits>
@@ -54,7 +56,9 @@ __device__ __forceinline__ void link_forward(const DevLink &t, const double p[3]
     double F[3][4], G[3][4];
     int i0[3];
     for (int k = 0; k < 3; k++) {
-        const double u = (p[k] - t.origin[k]) / t.spacing[k];
+        // clamped before the int conversion (undefined beyond 2^31 cells, and for NaN): below -2 or from dims + 1 on no tap
+        // touches the lattice either way, so d = 0 and q = p (NaN stays NaN) exactly as without the clamp
+        const double u = fmin(fmax((p[k] - t.origin[k]) / t.spacing[k], -3.0), (double)t.dims[k] + 1.0);
         const double fl = floor(u);
         i0[k] = (int)fl - 1;
         basis(u - fl, F[k], G[k]);
@@ -234,11 +238,11 @@ __device__ __forceinline__ S reslice_voxel(const DevLink *links, int n_links, co
 }
 
 template <class S>
-__global__ __launch_bounds__(256) void reslice_kernel(const DevLink *links, int n_links, const S *__restrict__ src, const ResliceGrid g,
-                                                      S *__restrict__ out)
+__global__ __launch_bounds__(256) void reslice_kernel(size_t base, const DevLink *links, int n_links, const S *__restrict__ src,
+                                                      const ResliceGrid g, S *__restrict__ out)
 {
     const size_t total = (size_t)g.nx * g.ny * g.nz;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     out[idx] = reslice_voxel<S>(links, n_links, src, g, idx);
 }
@@ -259,12 +263,12 @@ __device__ __forceinline__ void accumulate(float *__restrict__ avg, float *__res
 // the source resliced onto the grid (reslice_voxel, the same code as reslice_kernel), then added; `out` (may be null)
 // receives the resliced voxel in the source's type, what VolumeTransform would have written
 template <class S>
-__global__ __launch_bounds__(256) void reslice_accumulate_kernel(const DevLink *links, int n_links, const S *__restrict__ src,
+__global__ __launch_bounds__(256) void reslice_accumulate_kernel(size_t base, const DevLink *links, int n_links, const S *__restrict__ src,
                                                                  const ResliceGrid g, float n, float *__restrict__ avg,
                                                                  float *__restrict__ sq, S *__restrict__ out)
 {
     const size_t total = (size_t)g.nx * g.ny * g.nz;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const S r = reslice_voxel<S>(links, n_links, src, g, idx);
     if (out) out[idx] = r;
@@ -273,42 +277,43 @@ __global__ __launch_bounds__(256) void reslice_accumulate_kernel(const DevLink *
 
 // a source already on the grid (AverageVolumes' own inputs)
 template <class S>
-__global__ __launch_bounds__(256) void identity_accumulate_kernel(const S *__restrict__ src, size_t total, float n,
+__global__ __launch_bounds__(256) void identity_accumulate_kernel(size_t base, const S *__restrict__ src, size_t total, float n,
                                                                   float *__restrict__ avg, float *__restrict__ sq)
 {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     accumulate<S>(avg, sq, idx, src[idx], n);
 }
 
 // stdev = sqrt(sq - avg * avg) in place of sq: NaN where the f32 difference rounds negative, as in the reference
-__global__ __launch_bounds__(256) void average_finish_kernel(const float *__restrict__ avg, float *__restrict__ sq, size_t total)
+__global__ __launch_bounds__(256) void average_finish_kernel(size_t base, const float *__restrict__ avg, float *__restrict__ sq, size_t total)
 {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const float a = avg[idx];
     const float a2 = a * a;
     sq[idx] = sqrtf(sq[idx] - a2);
 }
 
-__global__ __launch_bounds__(256) void chain_apply_kernel(const DevLink *links, int n_links, const double *in, double *out, size_t n)
+__global__ __launch_bounds__(256) void chain_apply_kernel(size_t base, const DevLink *links, int n_links, const double *in, double *out, size_t n)
 {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double p[3] = { in[3 * i], in[3 * i + 1], in[3 * i + 2] }, A[3][3];
     chain_point<false>(links, n_links, p, A);
     out[3 * i] = p[0]; out[3 * i + 1] = p[1]; out[3 * i + 2] = p[2];
 }
 
-// one thread per grid node; block-level reduction of (negative count, minimum determinant)
-__global__ __launch_bounds__(256) void chain_check_kernel(const DevLink *links, int n_links, double ox, double oy, double oz,
+// one thread per grid node; block-level reduction of (negative count, minimum determinant) into the block's slot, numbered
+// from the first block of the whole grid (base is a multiple of the block size: chunked_launch)
+__global__ __launch_bounds__(256) void chain_check_kernel(size_t base, const DevLink *links, int n_links, double ox, double oy, double oz,
                                                           double sx, double sy, double sz, uint32_t nx, uint32_t ny, uint32_t nz,
                                                           unsigned long long *n_negative, double *block_min)
 {
     __shared__ double mins[256];
     __shared__ unsigned int negs[256];
     const size_t total = (size_t)nx * ny * nz;
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     double det = INFINITY;
     unsigned int neg = 0;
     if (idx < total) {
@@ -326,7 +331,7 @@ __global__ __launch_bounds__(256) void chain_check_kernel(const DevLink *links, 
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        block_min[blockIdx.x] = mins[0];
+        block_min[base / 256 + blockIdx.x] = mins[0];
         if (negs[0]) atomicAdd(n_negative, (unsigned long long)negs[0]);
     }
 }
@@ -338,6 +343,37 @@ int fail(int code, const std::string &msg) { frog::set_last_error(msg); return c
         hipError_t e_ = (expr);                                                              \
         if (e_ != hipSuccess) return fail(FROG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+// Every launch in this file goes through chunked_launch: one work-item per element of [0, total), 256 per block, at most
+// 2^31 work-items per launch.  A dispatch packet's grid is 32-bit WORK-ITEMS per dimension; a larger 1-D launch returns no
+// error and the work-items past 2^32 never run.  launch(blocks, base) issues one chunk, whose kernel adds
+// `base` (a multiple of 256) to its own index and bound-checks against the total.
+constexpr size_t LAUNCH_BLOCK = 256;
+
+size_t launch_max()
+{
+    // (test hook: FROG_CHAIN_LAUNCH_MAX=n, at most n work-items per launch, rounded down to whole blocks)
+    static const size_t m = [] {
+        const size_t cap = (size_t)1 << 31;
+        const char *s = getenv("FROG_CHAIN_LAUNCH_MAX");
+        const long long v = s ? atoll(s) : 0;
+        return v > 0 ? std::max(LAUNCH_BLOCK, std::min(cap, (size_t)v) / LAUNCH_BLOCK * LAUNCH_BLOCK) : cap;
+    }();
+    return m;
+}
+
+template <class Launch>
+hipError_t chunked_launch(size_t total, Launch launch)
+{
+    const size_t step = launch_max();
+    for (size_t base = 0; base < total; base += step) {
+        const size_t n = std::min(step, total - base);
+        launch((unsigned)((n + LAUNCH_BLOCK - 1) / LAUNCH_BLOCK), base);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 } // namespace
 
@@ -422,8 +458,9 @@ int frog_chain_apply(frog_chain *c, const double *in, double *out, size_t n)
     if (hipMalloc((void **)&d_out, 3 * n * sizeof(double)) != hipSuccess) { (void)hipFree(d_in); return fail(FROG_E_HIP, "hipMalloc"); }
     hipError_t e = hipMemcpy(d_in, in, 3 * n * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        chain_apply_kernel<<<(unsigned)((n + 255) / 256), 256>>>(c->d_links, (int)c->h_links.size(), d_in, d_out, n);
-        e = hipGetLastError();
+        e = chunked_launch(n, [&](unsigned blocks, size_t base) {
+            chain_apply_kernel<<<blocks, LAUNCH_BLOCK>>>(base, c->d_links, (int)c->h_links.size(), d_in, d_out, n);
+        });
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out, 3 * n * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(d_in); (void)hipFree(d_out);
@@ -441,16 +478,17 @@ int frog_chain_check(frog_chain *c, const double origin[3], const double spacing
     if (!total) return FROG_OK;
     if (total > ((size_t)1 << 40)) return fail(FROG_E_INVALID, "grid too large");
     KCHECK(hipSetDevice(c->device));
-    const size_t blocks = (total + 255) / 256;
+    const size_t blocks = (total + LAUNCH_BLOCK - 1) / LAUNCH_BLOCK;     // one block_min slot per block of the whole grid
     unsigned long long *d_neg = nullptr;
     double *d_min = nullptr;
     KCHECK(hipMalloc((void **)&d_neg, sizeof(unsigned long long)));
     if (hipMalloc((void **)&d_min, blocks * sizeof(double)) != hipSuccess) { (void)hipFree(d_neg); return fail(FROG_E_HIP, "hipMalloc"); }
     hipError_t e = hipMemset(d_neg, 0, sizeof(unsigned long long));
     if (e == hipSuccess) {
-        chain_check_kernel<<<(unsigned)blocks, 256>>>(c->d_links, (int)c->h_links.size(), origin[0], origin[1], origin[2],
-                                                      spacing[0], spacing[1], spacing[2], dims[0], dims[1], dims[2], d_neg, d_min);
-        e = hipGetLastError();
+        e = chunked_launch(total, [&](unsigned nb, size_t base) {
+            chain_check_kernel<<<nb, LAUNCH_BLOCK>>>(base, c->d_links, (int)c->h_links.size(), origin[0], origin[1], origin[2],
+                                                     spacing[0], spacing[1], spacing[2], dims[0], dims[1], dims[2], d_neg, d_min);
+        });
     }
     unsigned long long neg = 0;
     std::vector<double> mins(blocks);
@@ -518,9 +556,10 @@ int reslice_typed(frog_chain *c, const frog_volume *src, frog_volume *out, int i
     if (hipMalloc((void **)&d_out, n_out * sizeof(S)) != hipSuccess) { (void)hipFree(d_src); return fail(FROG_E_NOMEM, "hipMalloc (output volume)"); }
     hipError_t e = hipMemcpy(d_src, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        reslice_kernel<S><<<(unsigned)((n_out + 255) / 256), 256>>>(c->d_links, (int)c->h_links.size(), d_src,
-                                                                     reslice_grid(src, out, interpolation, background), d_out);
-        e = hipGetLastError();
+        const ResliceGrid g = reslice_grid(src, out, interpolation, background);
+        e = chunked_launch(n_out, [&](unsigned blocks, size_t base) {
+            reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links, (int)c->h_links.size(), d_src, g, d_out);
+        });
     }
     if (e == hipSuccess) e = hipMemcpy(out->data, d_out, n_out * sizeof(S), hipMemcpyDeviceToHost);
     (void)hipFree(d_src); (void)hipFree(d_out);
@@ -582,19 +621,19 @@ template <class S>
 int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
 {
     const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    const unsigned blocks = (unsigned)((a->total + 255) / 256);
     const float n = (float)a->n_images;
     if (int rc = grow(&a->d_src, &a->src_bytes, n_src * sizeof(S))) return rc;
     if (c && resliced) if (int rc = grow(&a->d_out, &a->out_bytes, a->total * sizeof(S))) return rc;
     hipError_t e = hipMemcpy(a->d_src, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        if (c)
-            reslice_accumulate_kernel<S><<<blocks, 256>>>(c->d_links, (int)c->h_links.size(), (const S *)a->d_src,
-                                                          reslice_grid(src, &a->grid, interpolation, background), n, a->d_avg, a->d_sq,
-                                                          resliced ? (S *)a->d_out : nullptr);
-        else
-            identity_accumulate_kernel<S><<<blocks, 256>>>((const S *)a->d_src, a->total, n, a->d_avg, a->d_sq);
-        e = hipGetLastError();
+        const ResliceGrid g = reslice_grid(src, &a->grid, interpolation, background);
+        e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+            if (c)
+                reslice_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links, (int)c->h_links.size(), (const S *)a->d_src, g, n,
+                                                                       a->d_avg, a->d_sq, resliced ? (S *)a->d_out : nullptr);
+            else
+                identity_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, (const S *)a->d_src, a->total, n, a->d_avg, a->d_sq);
+        });
     }
     if (e == hipSuccess && resliced) {
         if (c) e = hipMemcpy(resliced->data, a->d_out, a->total * sizeof(S), hipMemcpyDeviceToHost);
@@ -685,8 +724,9 @@ int frog_average_finish(frog_average *a, float *mean, float *stdev)
     KCHECK(hipSetDevice(a->device));
     hipError_t e = hipSuccess;
     if (!a->finished) {
-        average_finish_kernel<<<(unsigned)((a->total + 255) / 256), 256>>>(a->d_avg, a->d_sq, a->total);
-        e = hipGetLastError();
+        e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+            average_finish_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_avg, a->d_sq, a->total);
+        });
         a->finished = e == hipSuccess;                 // stdev now stands in place of sq: a second call only copies
     }
     if (e == hipSuccess) e = hipMemcpy(mean, a->d_avg, a->total * sizeof(float), hipMemcpyDeviceToHost);

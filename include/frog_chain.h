@@ -50,12 +50,14 @@ int frog_chain_create(const frog_chain_link *links, uint32_t n_links, int device
 void frog_chain_destroy(frog_chain *c);
 uint32_t frog_chain_num_links(const frog_chain *c);
 
-/* out[i] = chain(in[i]), n points of 3 doubles (host arrays). */
+/* out[i] = chain(in[i]), n points of 3 doubles (host arrays).  A point whose taps all lie outside a lattice (however far
+ * out) passes that link unchanged; a NaN coordinate gives NaN. */
 int frog_chain_apply(frog_chain *c, const double *in3n, double *out3n, size_t n);
 
 /* Jacobian determinant of the chain at origin + (i,j,k)*spacing for every node of a dims grid
  * (CheckDiffeomorphism.cxx:67-85): number of nodes with a negative determinant and the
- * smallest determinant met. */
+ * smallest determinant met.  Up to 2^40 nodes (FROG_E_INVALID above); the device work goes out in launches of at most
+ * 2^31 nodes, so a grid past 2^32 nodes is counted whole. */
 int frog_chain_check(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3],
                      uint64_t *n_negative, double *min_determinant);
 
@@ -91,7 +93,11 @@ static inline size_t frog_volume_voxel_bytes(int dtype)
  * dtype must be the source's and its data buffer is filled.  interpolation: 0 nearest, otherwise
  * trilinear.  A sample more than half a voxel outside the source's voxel centres gives
  * `background` (VTK's default border); integer outputs are rounded half up and clamped to the
- * type's range, as vtkImageReslice does. */
+ * type's range, as vtkImageReslice does.  Exactly, in f64 with every voxel read as f64:
+ * c = (chain(out.origin + i * out.spacing) - source.origin) / source.spacing; inside iff
+ * -0.5 <= c <= dims - 0.5 on every axis; nearest reads voxel floor(c + 0.5); trilinear taps are
+ * clamped to the volume; integers get floor(v + 0.5) clamped (-2.5 -> -2, 2.5 -> 3), floats a
+ * cast.  The output may hold more than 2^32 voxels: it is filled in launches of at most 2^31. */
 int frog_chain_reslice(frog_chain *c, const frog_volume *source, frog_volume *out, int interpolation, double background);
 
 /* ---- mean and stdev of a registered group (tools/AverageVolumes.cxx; transform.sh's last two steps) ----------------

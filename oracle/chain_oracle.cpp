@@ -42,7 +42,8 @@ void link_apply(const frog_chain_link &t, const double x[3], double y[3], double
     double F[3][4], G[3][4];
     int i0[3];
     for (int k = 0; k < 3; k++) {
-        const double p = (x[k] - t.origin[k]) / t.spacing[k];
+        // clamped before the int conversion as the device does: outside [-2, dims + 1) no tap touches the lattice
+        const double p = std::fmin(std::fmax((x[k] - t.origin[k]) / t.spacing[k], -3.0), (double)t.dims[k] + 1.0);
         const double fl = std::floor(p);
         i0[k] = (int)fl - 1;
         basis(p - fl, F[k], G[k]);
