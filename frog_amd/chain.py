@@ -11,11 +11,12 @@ import numpy as np
 from . import _abi
 from ._abi import check
 
-LINEAR, BSPLINE, BSPLINE_INVERSE = 0, 1, 2
+LINEAR, BSPLINE, BSPLINE_INVERSE, FIELD = 0, 1, 2, 3
 
 
 class Link:
-    """One transform of a chain: Link.linear(matrix4x4) or Link.bspline(dims, origin, spacing, coeffs[G,3])."""
+    """One transform of a chain: Link.linear(matrix4x4), Link.bspline(dims, origin, spacing, coeffs[G,3]) or
+    Link.field(dims, origin, spacing, values[G,3])."""
 
     def __init__(self, kind, matrix=None, dims=None, origin=None, spacing=None, coeffs=None):
         self.kind = kind
@@ -35,6 +36,12 @@ class Link:
     def bspline(cls, dims, origin, spacing, coeffs):
         return cls(BSPLINE, dims=dims, origin=origin, spacing=spacing, coeffs=coeffs)
 
+    @classmethod
+    def field(cls, dims, origin, spacing, values):
+        """A sampled displacement field (FROG_T_FIELD): one f32 displacement per node of the grid, x fastest -- what
+        Chain.sample returns as float32, in its (nz, ny, nx, 3) shape or flat.  Forward evaluation only."""
+        return cls(FIELD, dims=dims, origin=origin, spacing=spacing, coeffs=values)
+
     def view(self):
         v = _abi.FrogChainLink()
         v.type = self.kind
@@ -48,7 +55,8 @@ class Link:
 
 def invert(links):
     """vtkGeneralTransform::Inverse() of a chain: reversed order, inverted matrices, lattices evaluated by
-    Newton's method (frog_chain_invert_links)."""
+    Newton's method (frog_chain_invert_links).  A field link has no inverse form and raises: sample the inverted
+    chain instead (Chain(invert(links)).sample)."""
     links = list(links)
     n = len(links)
     src = (_abi.FrogChainLink * max(1, n))(*[l.view() for l in links])
@@ -84,7 +92,7 @@ def read_nifti_lattice(path):
 
 
 def read_transform(path):
-    """transforms/<i>.json in either form (tools/transformIO.h:375-460): a list of Links."""
+    """transforms/<i>.json in either form (tools/transformIO.h:375-460), or with frogDisplacementField entries: a list of Links."""
     links = []
     for t in json.load(open(path))["transforms"]:
         if t["type"] == "vtkMatrixToLinearTransform":
@@ -95,6 +103,11 @@ def read_transform(path):
                 links.append(Link.bspline(dims, origin, spacing, vox[:, :3]))
             else:
                 links.append(Link.bspline(t["dimensions"], t["origin"], t["spacing"], np.array(t["coeffs"], np.float32).reshape(-1, 3)))
+        elif t["type"] == "frogDisplacementField":                 # this project's extension (bin/TransformField -w)
+            dims, origin, spacing, vox = read_nifti_lattice(os.path.join(os.path.dirname(str(path)), t["file"]))
+            if vox.shape[1] < 3:
+                raise ValueError(f"{t['file']}: a displacement field has 3 components")
+            links.append(Link.field(dims, origin, spacing, vox[:, :3]))
         else:
             raise ValueError(f"Error : transform type {t['type']} not supported")
     return links
@@ -147,3 +160,19 @@ class Chain:
         n, m = C.c_uint64(), C.c_double()
         check(self._lib.frog_chain_check(self._h, o, s, d, C.byref(n), C.byref(m)), "frog_chain_check")
         return int(n.value), float(m.value)
+
+    def sample(self, origin, spacing, dims, displacement=True, determinant=True, dtype=np.float32):
+        """The chain on the nodes origin + (i, j, k) * spacing of a dims grid (frog_chain_sample): the pair
+        (displacement[nz, ny, nx, 3], determinant[nz, ny, nx]) of chain(p) - p and of the Jacobian determinant, computed
+        in f64 and stored as `dtype` (float32 or float64); None in place of an output that was not asked for."""
+        dt = np.dtype(dtype)
+        if dt.name not in ("float32", "float64"):
+            raise ValueError("float32 or float64 expected")
+        nx, ny, nz = (int(v) for v in dims)
+        o = (C.c_double * 3)(*origin); s = (C.c_double * 3)(*spacing); d = (C.c_uint32 * 3)(nx, ny, nz)
+        disp = np.empty((nz, ny, nx, 3), dt) if displacement else None
+        det = np.empty((nz, ny, nx), dt) if determinant else None
+        check(self._lib.frog_chain_sample(self._h, o, s, d, _abi.FROG_V_DTYPES.index(dt.name),
+                                          None if disp is None else disp.ctypes.data, None if det is None else det.ctypes.data),
+              "frog_chain_sample")
+        return disp, det

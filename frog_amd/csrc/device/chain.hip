@@ -2,6 +2,8 @@
 // One thread per point, f64; the links live in device memory in application order.  The lattices
 // are small (<= a few 10^4 control points) and every thread of a wavefront reads nearby taps, so
 // the coefficient loads are L1/L2 hits; the kernel is f64-ALU work (4^3 taps x 12 products per link).
+// A sampled displacement field (FROG_T_FIELD) is a link too: eight node reads and a trilinear blend per point, which is
+// what frog_chain_sample collapses a whole chain (Newton inverses included) into.
 #include <hip/hip_runtime.h>
 
 #include "frog_chain.h"
@@ -42,17 +44,54 @@ __device__ __forceinline__ void basis(double f, double F[4], double G[4])
     G[3] = f * f / 2;
 }
 
-// one link, forward: q = T(p), J = dT/dp
+// A sampled displacement field (FROG_T_FIELD), forward: q = p + d(p), d the trilinear interpolant of the node values.
+// Per axis c = (p - origin) / spacing clamped to [0, dims - 1], cell min(floor(c), dims - 2) (0 where dims == 1), fraction
+// c - cell: the last node is the last cell's fraction 1, outside the grid the edge value continues.  The eight nodes are
+// widened to f64 and combined in reslice_voxel's order.  J = I + dd/dp of the interpolant inside the cell; the column of an
+// axis that was clamped, or has one node, is zero.  A NaN coordinate passes the comparisons and makes q NaN.
 template <bool JAC>
-__device__ __forceinline__ void link_forward(const DevLink &t, const double p[3], double q[3], double J[3][3])
+__device__ __forceinline__ void field_forward(const DevLink &t, const double p[3], double q[3], double J[3][3])
 {
-    if (t.type == FROG_T_LINEAR) {
-        for (int r = 0; r < 3; r++) {
-            q[r] = t.m[4 * r] * p[0] + t.m[4 * r + 1] * p[1] + t.m[4 * r + 2] * p[2] + t.m[4 * r + 3];
-            if (JAC) for (int c = 0; c < 3; c++) J[r][c] = t.m[4 * r + c];
-        }
-        return;
+    int i0[3], i1[3];
+    double f[3];
+    bool flat[3];
+    for (int k = 0; k < 3; k++) {
+        const int last = t.dims[k] - 1;
+        const double raw = (p[k] - t.origin[k]) / t.spacing[k];
+        const double c = raw < 0.0 ? 0.0 : (raw > (double)last ? (double)last : raw);
+        i0[k] = c < (double)last ? (int)floor(c) : (last > 0 ? last - 1 : 0);      // 0 <= c < last before the int conversion
+        i1[k] = last > 0 ? i0[k] + 1 : 0;
+        f[k] = c - (double)i0[k];
+        flat[k] = raw < 0.0 || raw > (double)last || last == 0;
     }
+    auto node = [&](int x, int y, int z) -> const float * {
+        return t.coeffs + 3 * ((size_t)x + (size_t)t.dims[0] * ((size_t)y + (size_t)t.dims[1] * (size_t)z));
+    };
+    const float *n000 = node(i0[0], i0[1], i0[2]), *n100 = node(i1[0], i0[1], i0[2]), *n010 = node(i0[0], i1[1], i0[2]),
+                *n110 = node(i1[0], i1[1], i0[2]), *n001 = node(i0[0], i0[1], i1[2]), *n101 = node(i1[0], i0[1], i1[2]),
+                *n011 = node(i0[0], i1[1], i1[2]), *n111 = node(i1[0], i1[1], i1[2]);
+    const double fx = f[0], fy = f[1], fz = f[2];
+    const double rx = 1 - fx, ry = 1 - fy, rz = 1 - fz;
+    for (int r = 0; r < 3; r++) {
+        const double a = n000[r], b = n100[r], c = n010[r], d = n110[r], e = n001[r], g = n101[r], h = n011[r], m = n111[r];
+        const double v = rz * (ry * (rx * a + fx * b) + fy * (rx * c + fx * d))
+                       + fz * (ry * (rx * e + fx * g) + fy * (rx * h + fx * m));
+        q[r] = p[r] + v;
+        if (JAC) {
+            const double gx = rz * (ry * (b - a) + fy * (d - c)) + fz * (ry * (g - e) + fy * (m - h));
+            const double gy = rz * (rx * (c - a) + fx * (d - b)) + fz * (rx * (h - e) + fx * (m - g));
+            const double gz = ry * (rx * (e - a) + fx * (g - b)) + fy * (rx * (h - c) + fx * (m - d));
+            J[r][0] = (r == 0 ? 1.0 : 0.0) + (flat[0] ? 0.0 : gx / t.spacing[0]);
+            J[r][1] = (r == 1 ? 1.0 : 0.0) + (flat[1] ? 0.0 : gy / t.spacing[1]);
+            J[r][2] = (r == 2 ? 1.0 : 0.0) + (flat[2] ? 0.0 : gz / t.spacing[2]);
+        }
+    }
+}
+
+// a B-spline lattice, forward: q = p + d(p), J = I + dd/dp
+template <bool JAC>
+__device__ __forceinline__ void bspline_forward(const DevLink &t, const double p[3], double q[3], double J[3][3])
+{
     double F[3][4], G[3][4];
     int i0[3];
     for (int k = 0; k < 3; k++) {
@@ -92,6 +131,21 @@ __device__ __forceinline__ void link_forward(const DevLink &t, const double p[3]
     }
 }
 
+// one link, forward: q = T(p), J = dT/dp
+template <bool JAC>
+__device__ __forceinline__ void link_forward(const DevLink &t, const double p[3], double q[3], double J[3][3])
+{
+    if (t.type == FROG_T_LINEAR) {
+        for (int r = 0; r < 3; r++) {
+            q[r] = t.m[4 * r] * p[0] + t.m[4 * r + 1] * p[1] + t.m[4 * r + 2] * p[2] + t.m[4 * r + 3];
+            if (JAC) for (int c = 0; c < 3; c++) J[r][c] = t.m[4 * r + c];
+        }
+        return;
+    }
+    if (t.type == FROG_T_FIELD) field_forward<JAC>(t, p, q, J);
+    else bspline_forward<JAC>(t, p, q, J);
+}
+
 // delta = J^-1 r  (Cramer; the lattices frog writes with -gd 1 have det J > 0)
 __device__ __forceinline__ void solve3(const double J[3][3], const double r[3], double delta[3])
 {
@@ -112,15 +166,13 @@ __device__ __forceinline__ void solve3(const double J[3][3], const double r[3], 
 template <bool JAC>
 __device__ void bspline_inverse(const DevLink &t, const double p[3], double q[3], double Jinv[3][3])
 {
-    DevLink f = t;
-    f.type = FROG_T_BSPLINE;
     const double tol2 = INVERSE_TOLERANCE * INVERSE_TOLERANCE;
     double x[3], fx[3], J[3][3], r[3], delta[3] = { 0, 0, 0 }, last_x[3], last_f = 0, fderiv = 0, frac = 1;
-    link_forward<false>(f, p, fx, J);
+    bspline_forward<false>(t, p, fx, J);
     for (int k = 0; k < 3; k++) { x[k] = p[k] - (fx[k] - p[k]); last_x[k] = x[k]; }
     int it = 0;
     for (; it < INVERSE_ITERATIONS; it++) {
-        link_forward<true>(f, x, fx, J);
+        bspline_forward<true>(t, x, fx, J);
         for (int k = 0; k < 3; k++) r[k] = fx[k] - p[k];
         const double fval = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
         if (it == 0 || fval < last_f) {
@@ -143,7 +195,7 @@ __device__ void bspline_inverse(const DevLink &t, const double p[3], double q[3]
     if (it >= INVERSE_ITERATIONS) for (int k = 0; k < 3; k++) x[k] = last_x[k];      // did not converge: best point seen
     for (int k = 0; k < 3; k++) q[k] = x[k];
     if (JAC) {
-        link_forward<true>(f, x, fx, J);
+        bspline_forward<true>(t, x, fx, J);
         for (int c = 0; c < 3; c++) {
             const double e[3] = { c == 0 ? 1.0 : 0.0, c == 1 ? 1.0 : 0.0, c == 2 ? 1.0 : 0.0 };
             double col[3];
@@ -336,6 +388,33 @@ __global__ __launch_bounds__(256) void chain_check_kernel(size_t base, const Dev
     }
 }
 
+// one thread per grid node of a slab [first, first + count) of the whole grid (first and base are multiples of the block size):
+// the node and the determinant as chain_check_kernel computes them, the displacement as chain_apply_kernel's output minus the
+// node, each stored with one cast.  DET selects chain_point<true>; without it no Jacobian is formed.
+template <bool DISP, bool DET, class T>
+__global__ __launch_bounds__(256) void chain_sample_kernel(size_t first, size_t base, size_t count, const DevLink *links, int n_links,
+                                                           double ox, double oy, double oz, double sx, double sy, double sz,
+                                                           uint32_t nx, uint32_t ny, T *__restrict__ displacement, T *__restrict__ determinant)
+{
+    const size_t local = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (local >= count) return;
+    const size_t idx = first + local;
+    const uint32_t i = (uint32_t)(idx % nx), j = (uint32_t)((idx / nx) % ny), k = (uint32_t)(idx / ((size_t)nx * ny));
+    double p[3] = { ox + i * sx, oy + j * sy, oz + k * sz }, A[3][3];
+    const double node[3] = { p[0], p[1], p[2] };
+    chain_point<DET>(links, n_links, p, A);
+    if (DISP) {
+        displacement[3 * local] = (T)(p[0] - node[0]);
+        displacement[3 * local + 1] = (T)(p[1] - node[1]);
+        displacement[3 * local + 2] = (T)(p[2] - node[2]);
+    }
+    if (DET) {
+        const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0])
+                         + A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+        determinant[local] = (T)det;
+    }
+}
+
 int fail(int code, const std::string &msg) { frog::set_last_error(msg); return code; }
 
 #define KCHECK(expr)                                                                         \
@@ -415,7 +494,8 @@ int frog_chain_create(const frog_chain_link *links, uint32_t n_links, int device
         if (t.type == FROG_T_LINEAR) {
             for (int k = 0; k < 12; k++) d.m[k] = t.matrix[k];
             c->d_coeffs.push_back(nullptr);
-        } else if (t.type == FROG_T_BSPLINE || t.type == FROG_T_BSPLINE_INVERSE) {
+        } else if (t.type == FROG_T_BSPLINE || t.type == FROG_T_BSPLINE_INVERSE || t.type == FROG_T_FIELD) {
+            // a field's nodes are validated and uploaded like a lattice's control points
             const size_t G = (size_t)t.dims[0] * t.dims[1] * t.dims[2];
             if (!G || !t.coeffs) { frog_chain_destroy(c); return fail(FROG_E_INVALID, "empty lattice"); }
             for (int k = 0; k < 3; k++) {
@@ -502,6 +582,75 @@ int frog_chain_check(frog_chain *c, const double origin[3], const double spacing
 }
 
 
+extern "C++" {
+namespace {
+
+// frog_chain_sample's device buffers hold one slab of the grid: whole launches (chunked_launch's step), at most
+// SAMPLE_SLAB_LAUNCHES of them, within SAMPLE_SLAB_BYTES and half of the free device memory; where one launch does not fit,
+// a part of one.  Each slab is computed, then copied to its place in the host arrays.
+constexpr size_t SAMPLE_SLAB_BYTES = (size_t)1 << 30;
+constexpr size_t SAMPLE_SLAB_LAUNCHES = 4;
+
+template <class T>
+int sample_typed(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3], size_t total,
+                 T *displacement, T *determinant)
+{
+    const size_t per_node = ((displacement ? 3 : 0) + (determinant ? 1 : 0)) * sizeof(T);
+    size_t free_bytes = 0, device_bytes = 0;
+    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
+    const size_t step = launch_max();
+    const size_t fit = std::max(LAUNCH_BLOCK, std::min(free_bytes / 2, SAMPLE_SLAB_BYTES) / per_node / LAUNCH_BLOCK * LAUNCH_BLOCK);
+    size_t slab = fit >= step ? std::min(fit / step, SAMPLE_SLAB_LAUNCHES) * step : fit;
+    slab = std::min(slab, (total + LAUNCH_BLOCK - 1) / LAUNCH_BLOCK * LAUNCH_BLOCK);
+    T *d_disp = nullptr, *d_det = nullptr;
+    if (displacement) KCHECK(hipMalloc((void **)&d_disp, 3 * slab * sizeof(T)));
+    if (determinant && hipMalloc((void **)&d_det, slab * sizeof(T)) != hipSuccess) {
+        if (d_disp) (void)hipFree(d_disp);
+        return fail(FROG_E_NOMEM, "hipMalloc (determinant slab)");
+    }
+    hipError_t e = hipSuccess;
+    for (size_t first = 0; first < total && e == hipSuccess; first += slab) {
+        const size_t count = std::min(slab, total - first);
+        e = chunked_launch(count, [&](unsigned blocks, size_t base) {
+            const DevLink *links = c->d_links;
+            const int n = (int)c->h_links.size();
+            if (displacement && determinant)
+                chain_sample_kernel<true, true, T><<<blocks, LAUNCH_BLOCK>>>(first, base, count, links, n, origin[0], origin[1], origin[2],
+                                                                             spacing[0], spacing[1], spacing[2], dims[0], dims[1], d_disp, d_det);
+            else if (displacement)
+                chain_sample_kernel<true, false, T><<<blocks, LAUNCH_BLOCK>>>(first, base, count, links, n, origin[0], origin[1], origin[2],
+                                                                              spacing[0], spacing[1], spacing[2], dims[0], dims[1], d_disp, d_det);
+            else
+                chain_sample_kernel<false, true, T><<<blocks, LAUNCH_BLOCK>>>(first, base, count, links, n, origin[0], origin[1], origin[2],
+                                                                              spacing[0], spacing[1], spacing[2], dims[0], dims[1], d_disp, d_det);
+        });
+        if (e == hipSuccess && displacement) e = hipMemcpy(displacement + 3 * first, d_disp, 3 * count * sizeof(T), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && determinant) e = hipMemcpy(determinant + first, d_det, count * sizeof(T), hipMemcpyDeviceToHost);
+    }
+    if (d_disp) (void)hipFree(d_disp);
+    if (d_det) (void)hipFree(d_det);
+    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_chain_sample: ") + hipGetErrorString(e));
+    return FROG_OK;
+}
+
+} // namespace
+} // extern "C++"
+
+int frog_chain_sample(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3],
+                      int dtype, void *displacement, void *determinant)
+{
+    if (!c || !origin || !spacing || !dims) return fail(FROG_E_INVALID, "bad arguments to frog_chain_sample");
+    if (!displacement && !determinant) return fail(FROG_E_INVALID, "frog_chain_sample: no output asked for");
+    if (dtype != FROG_V_F32 && dtype != FROG_V_F64) return fail(FROG_E_INVALID, "frog_chain_sample: the output type must be FROG_V_F32 or FROG_V_F64");
+    const size_t limit = (size_t)1 << 40, plane = (size_t)dims[0] * dims[1];
+    if (!plane || !dims[2]) return FROG_OK;
+    if (plane > limit || dims[2] > limit / plane) return fail(FROG_E_INVALID, "grid too large");
+    const size_t total = plane * dims[2];
+    KCHECK(hipSetDevice(c->device));
+    if (dtype == FROG_V_F32) return sample_typed<float>(c, origin, spacing, dims, total, (float *)displacement, (float *)determinant);
+    return sample_typed<double>(c, origin, spacing, dims, total, (double *)displacement, (double *)determinant);
+}
+
 int frog_chain_invert_links(const frog_chain_link *in, uint32_t n, frog_chain_link *out)
 {
     if (n && (!in || !out)) return fail(FROG_E_INVALID, "bad arguments to frog_chain_invert_links");
@@ -525,6 +674,8 @@ int frog_chain_invert_links(const frog_chain_link *in, uint32_t n, frog_chain_li
                 t.matrix[4 * r + 3] = -(inv[r][0] * m[3] + inv[r][1] * m[7] + inv[r][2] * m[11]);
             }
             t.matrix[12] = t.matrix[13] = t.matrix[14] = 0.0; t.matrix[15] = 1.0;
+        } else if (t.type == FROG_T_FIELD) {
+            return fail(FROG_E_INVALID, "a displacement field link has no inverse form: sample the inverted chain instead");
         } else {
             return fail(FROG_E_INVALID, "unknown transform type");
         }

@@ -1,7 +1,8 @@
 // transform_io.cpp -- reader of the transform files frog writes (transforms/<i>.json, with the
 // coefficients inline or in .nii.gz sidecars), i.e. what tools/transformIO.h:375-460
 // (readJSONfromString) rebuilds as a vtkGeneralTransform, here as a frog_chain_link list
-// (include/frog_chain.h).  Also the voxel grid of a NIfTI-1 / MetaImage volume, for
+// (include/frog_chain.h).  One entry form is this project's own: {"type": "frogDisplacementField", "file": ...}, a sampled
+// displacement field (FROG_T_FIELD) in the layout of a lattice sidecar.  Also the voxel grid of a NIfTI-1 / MetaImage volume, for
 // CheckDiffeomorphism's sampling grid.
 #include "frog_host.h"
 
@@ -156,6 +157,19 @@ frog_transform_file *frog_transform_read(const char *json_path, int *status)
     const size_t slash = dir.find_last_of("/\\");
     dir = slash == std::string::npos ? std::string(".") : dir.substr(0, slash);
     std::unique_ptr<frog_transform_file> f(new frog_transform_file);
+    // a 3-component FLOAT32 NIfTI next to the JSON (a lattice sidecar, a displacement field): grid from the header, values interleaved
+    auto sidecar = [&](const std::string &name, frog_chain_link &l, std::vector<float> &co) -> int {
+        std::vector<unsigned char> raw;
+        uint32_t nc = 0; size_t off = 0; int dt = 0;
+        if (!read_all(dir + "/" + name, raw)) return FROG_E_IO;
+        if (!nifti_geometry(raw, l.dims, l.spacing, l.origin, &nc, &off, &dt) || dt != 16 || nc < 3) return FROG_E_INVALID;
+        const size_t G = (size_t)l.dims[0] * l.dims[1] * l.dims[2];
+        if (raw.size() < off + G * nc * sizeof(float)) return FROG_E_INVALID;
+        co.resize(3 * G);
+        for (uint32_t c = 0; c < 3; c++)                               // stored plane by plane
+            for (size_t v = 0; v < G; v++) co[3 * v + c] = at<float>(raw, off + (c * G + v) * sizeof(float));
+        return FROG_OK;
+    };
     for (const JValue &t : list->arr) {
         const JValue *type = t.get("type");
         if (!type || type->kind != JValue::String) return fail(FROG_E_INVALID);
@@ -172,15 +186,7 @@ frog_transform_file *frog_transform_read(const char *json_path, int *status)
             std::vector<float> &co = *f->storage.back();
             const JValue *file = t.get("file");
             if (file && file->kind == JValue::String) {
-                std::vector<unsigned char> raw;
-                uint32_t nc = 0; size_t off = 0; int dt = 0;
-                if (!read_all(dir + "/" + file->str, raw)) return fail(FROG_E_IO);
-                if (!nifti_geometry(raw, l.dims, l.spacing, l.origin, &nc, &off, &dt) || dt != 16 || nc < 3) return fail(FROG_E_INVALID);
-                const size_t G = (size_t)l.dims[0] * l.dims[1] * l.dims[2];
-                if (raw.size() < off + G * nc * sizeof(float)) return fail(FROG_E_INVALID);
-                co.resize(3 * G);
-                for (uint32_t c = 0; c < 3; c++)                               // stored plane by plane
-                    for (size_t v = 0; v < G; v++) co[3 * v + c] = at<float>(raw, off + (c * G + v) * sizeof(float));
+                if (int rc = sidecar(file->str, l, co)) return fail(rc);
             } else {
                 const JValue *dm = t.get("dimensions"), *og = t.get("origin"), *sp = t.get("spacing"), *cf = t.get("coeffs");
                 if (!dm || !og || !sp || !cf || dm->arr.size() != 3 || og->arr.size() != 3 || sp->arr.size() != 3) return fail(FROG_E_INVALID);
@@ -191,6 +197,13 @@ frog_transform_file *frog_transform_read(const char *json_path, int *status)
                 for (size_t k = 0; k < 3 * G; k++) co[k] = (float)cf->arr[k].num;
             }
             l.coeffs = co.data();
+        } else if (type->str == "frogDisplacementField") {                     // this project's extension: no reference reader knows it
+            const JValue *file = t.get("file");
+            if (!file || file->kind != JValue::String) return fail(FROG_E_INVALID);
+            l.type = FROG_T_FIELD;
+            f->storage.emplace_back(new std::vector<float>);
+            if (int rc = sidecar(file->str, l, *f->storage.back())) return fail(rc);
+            l.coeffs = f->storage.back()->data();
         } else {
             return fail(FROG_E_INVALID);                                        // "Error : transform type ... not supported"
         }

@@ -20,6 +20,17 @@
  * Inverse of a B-spline link (FROG_T_BSPLINE_INVERSE): Newton's method with vtkWarpTransform's
  *              defaults (tolerance 1e-3, 500 iterations, step shortening when the residual grows);
  *              the inverse of a linear link is its inverted matrix (frog_chain_invert_links).
+ * Displacement field link (FROG_T_FIELD; an extension, the reference has no such transform): `dims`, `origin`, `spacing`
+ *              describe a grid of nodes, `coeffs` holds one f32 displacement per node, x fastest -- what frog_chain_sample
+ *              writes with FROG_V_F32.  Forward only, f64.  Exactly, per axis: c = (p - origin) / spacing clamped to
+ *              [0, dims - 1]; cell f0 = min(floor(c), dims - 2), 0 where dims == 1; fraction f = c - f0, r = 1 - f (the last
+ *              node is the last cell's fraction 1; outside the grid the edge value continues).  The eight nodes of the cell,
+ *              widened to f64, are blended in the order of the reslice's trilinear rule,
+ *              d = rz * (ry * (rx * a + fx * b) + fy * (rx * c + fx * d)) + fz * (ry * (...) + fy * (...)), and y = p + d.
+ *              Jacobian: I + dd/dp of that interpolant inside the cell (each partial divided by the axis' spacing); the
+ *              column of an axis is zero where c was clamped on that axis or dims == 1.  A NaN coordinate gives NaN.
+ *              There is no inverse form: frog_chain_invert_links refuses a field link.  The inverse of a transform as a
+ *              field is obtained by sampling the inverted chain (frog_chain_invert_links, then frog_chain_sample).
  */
 #ifndef FROG_CHAIN_H
 #define FROG_CHAIN_H
@@ -33,19 +44,20 @@
 extern "C" {
 #endif
 
-enum { FROG_T_LINEAR = 0, FROG_T_BSPLINE = 1, FROG_T_BSPLINE_INVERSE = 2 };
+enum { FROG_T_LINEAR = 0, FROG_T_BSPLINE = 1, FROG_T_BSPLINE_INVERSE = 2, FROG_T_FIELD = 3 };
 
 typedef struct frog_chain_link {
-    int type;                   /* FROG_T_LINEAR | FROG_T_BSPLINE | FROG_T_BSPLINE_INVERSE */
+    int type;                   /* FROG_T_LINEAR | FROG_T_BSPLINE | FROG_T_BSPLINE_INVERSE | FROG_T_FIELD */
     double matrix[16];          /* linear: row-major 4x4                                  */
-    uint32_t dims[3];           /* B-spline: control points per axis                      */
+    uint32_t dims[3];           /* B-spline: control points per axis; field: nodes per axis */
     double origin[3], spacing[3];
-    const float *coeffs;        /* B-spline: dims[0]*dims[1]*dims[2] x 3 floats, x fastest */
+    const float *coeffs;        /* B-spline, field: dims[0]*dims[1]*dims[2] x 3 floats, x fastest */
 } frog_chain_link;
 
 typedef struct frog_chain frog_chain;
 
-/* Copies the links (and their coefficients) to `device`. */
+/* Copies the links (and their coefficients) to `device`.  A lattice or a field needs a non-empty grid, non-NULL values and a
+ * spacing > 0 on every axis (FROG_E_INVALID otherwise). */
 int frog_chain_create(const frog_chain_link *links, uint32_t n_links, int device, frog_chain **out);
 void frog_chain_destroy(frog_chain *c);
 uint32_t frog_chain_num_links(const frog_chain *c);
@@ -64,7 +76,7 @@ int frog_chain_check(frog_chain *c, const double origin[3], const double spacing
 /* vtkGeneralTransform::Inverse() of a chain (tools/VolumeTransform.cxx:55-57, PointsTransform's -ti):
  * the links in reverse order, matrices inverted, lattices switched between forward and inverse
  * evaluation.  `out` receives n links (coefficient pointers are shared with `in`).  Returns
- * FROG_E_INVALID for a singular matrix. */
+ * FROG_E_INVALID for a singular matrix, and for a chain that holds a FROG_T_FIELD link. */
 int frog_chain_invert_links(const frog_chain_link *in, uint32_t n, frog_chain_link *out);
 
 /* ---- volume reslicing (tools/VolumeTransform.cxx:119-136 = vtkImageReslice) ----------------------
@@ -86,6 +98,23 @@ static inline size_t frog_volume_voxel_bytes(int dtype)
     default: return 0;
     }
 }
+
+/* The chain sampled on a grid: a dense displacement field and the map of its Jacobian determinant.
+ * For every node p = origin + (i,j,k)*spacing of a dims grid, x fastest:
+ *   displacement[3*idx + r] = chain(p)[r] - p[r]     (may be NULL)
+ *   determinant[idx]        = det(d chain / d p)     (may be NULL; not both NULL)
+ * computed in f64 exactly as frog_chain_apply and frog_chain_check compute them (the same device code: the node is
+ * origin + i * spacing, the displacement the f64 difference after the chain, the determinant the cofactor expansion along
+ * the first row of the product of the links' Jacobians), stored as dtype: FROG_V_F32 is one cast of the f64 value, or
+ * FROG_V_F64.  So on one grid the determinants' minimum and their count below zero are frog_chain_check's results.  With
+ * `determinant` NULL no Jacobian is formed; with `displacement` NULL nothing else is stored.  Host arrays; up to 2^40
+ * nodes.  The device holds one slab of the grid at a time (whole launches of at most 2^31 nodes, within 1 GiB and half of
+ * the free device memory), so the host arrays may be larger than device memory.  A grid with no nodes returns FROG_OK and
+ * writes nothing; the grid's spacing is not validated.  FROG_E_INVALID: a NULL chain, origin, spacing or dims; both
+ * outputs NULL; a dtype other than FROG_V_F32 / FROG_V_F64; more than 2^40 nodes.
+ * A FROG_V_F32 displacement array is the `coeffs` of a FROG_T_FIELD link on the same grid. */
+int frog_chain_sample(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3],
+                      int dtype, void *displacement, void *determinant);
 
 /* out(voxel) = source(chain(position of the voxel)): `chain` maps the output grid's space to the
  * source's (for a registration transform T of the source that is T^-1: frog_chain_invert_links).

@@ -182,7 +182,9 @@ int frog_keypoints_write(const char *path, const frog_keypoints *k);
 /* ---- transform files (what frog writes; tools/transformIO.h:375-460 reads) -----------
  * frog_transform_read parses transforms/<i>.json in either form (coefficients inline, or in
  * the .nii.gz sidecars named by "file", looked up next to the JSON) into the link list of
- * include/frog_chain.h; the object owns the coefficient arrays the links point to.
+ * include/frog_chain.h; the object owns the coefficient arrays the links point to.  One more entry form, this project's own:
+ * {"type": "frogDisplacementField", "file": "<name>.nii.gz"} becomes a FROG_T_FIELD link whose grid comes from the file's
+ * header and whose node values are its 3 components (the layout of a lattice sidecar; bin/TransformField writes it).
  * frog_volume_geometry returns the voxel grid of a NIfTI-1 (.nii/.nii.gz) or MetaImage (.mhd)
  * volume: the sampling grid of CheckDiffeomorphism. */
 typedef struct frog_transform_file frog_transform_file;
