@@ -195,6 +195,23 @@ class FrogVolume(C.Structure):
 FROG_V_DTYPES = ["uint8", "int8", "uint16", "int16", "uint32", "int32", "float32", "float64"]
 
 
+def volume_view(a, origin, spacing, dims=None):
+    """FrogVolume over the C-contiguous array a[z, y, x], which must outlive it; with a = None, the bare grid of
+    dims(x, y, z): float32, no voxels."""
+    if a is not None and (a.ndim != 3 or a.dtype.name not in FROG_V_DTYPES):
+        raise ValueError("3-D scalar volume of a supported type expected")
+    v = FrogVolume()
+    v.dims[:] = [int(d) for d in (dims if a is None else a.shape[::-1])]; v.origin[:] = origin; v.spacing[:] = spacing
+    v.dtype = FROG_V_DTYPES.index("float32" if a is None else a.dtype.name)
+    v.data = None if a is None else a.ctypes.data
+    return v
+
+
+def grid_triplet(origin, spacing, dims):
+    """(origin, spacing, dims) of a grid as the C arrays frog_chain_check and frog_chain_sample take."""
+    return (C.c_double * 3)(*origin), (C.c_double * 3)(*spacing), (C.c_uint32 * 3)(*dims)
+
+
 class FrogChainLink(C.Structure):
     """frog_chain_link (include/frog_chain.h)."""
     _fields_ = [("type", C.c_int), ("matrix", C.c_double * 16), ("dims", C.c_uint32 * 3), ("origin", C.c_double * 3),

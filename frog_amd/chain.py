@@ -143,20 +143,15 @@ class Chain:
         """vtkImageReslice as tools/VolumeTransform.cxx:119-136 uses it: `volume` is indexed [z, y, x]; the chain
         maps the output grid's space to the volume's.  Returns an array of the same dtype, shape out_dims[::-1]."""
         src = np.ascontiguousarray(volume)
-        if src.dtype.name not in _abi.FROG_V_DTYPES or src.ndim != 3:
-            raise ValueError("3-D scalar volume of a supported type expected")
+        a = _abi.volume_view(src, origin, spacing)
         out = np.empty(tuple(int(v) for v in out_dims[::-1]), src.dtype)
-        a, b = _abi.FrogVolume(), _abi.FrogVolume()
-        a.dims[:] = src.shape[::-1]; a.spacing[:] = spacing; a.origin[:] = origin
-        b.dims[:] = [int(v) for v in out_dims]; b.spacing[:] = out_spacing; b.origin[:] = out_origin
-        a.dtype = b.dtype = _abi.FROG_V_DTYPES.index(src.dtype.name)
-        a.data = src.ctypes.data; b.data = out.ctypes.data
+        b = _abi.volume_view(out, out_origin, out_spacing)
         check(self._lib.frog_chain_reslice(self._h, C.byref(a), C.byref(b), int(interpolation), float(background)), "frog_chain_reslice")
         return out
 
     def check(self, origin, spacing, dims):
         """(number of grid nodes with a negative Jacobian determinant, smallest determinant)."""
-        o = (C.c_double * 3)(*origin); s = (C.c_double * 3)(*spacing); d = (C.c_uint32 * 3)(*dims)
+        o, s, d = _abi.grid_triplet(origin, spacing, dims)
         n, m = C.c_uint64(), C.c_double()
         check(self._lib.frog_chain_check(self._h, o, s, d, C.byref(n), C.byref(m)), "frog_chain_check")
         return int(n.value), float(m.value)
@@ -169,7 +164,7 @@ class Chain:
         if dt.name not in ("float32", "float64"):
             raise ValueError("float32 or float64 expected")
         nx, ny, nz = (int(v) for v in dims)
-        o = (C.c_double * 3)(*origin); s = (C.c_double * 3)(*spacing); d = (C.c_uint32 * 3)(nx, ny, nz)
+        o, s, d = _abi.grid_triplet(origin, spacing, (nx, ny, nz))
         disp = np.empty((nz, ny, nx, 3), dt) if displacement else None
         det = np.empty((nz, ny, nx), dt) if determinant else None
         check(self._lib.frog_chain_sample(self._h, o, s, d, _abi.FROG_V_DTYPES.index(dt.name),

@@ -7,12 +7,15 @@
 #include <hip/hip_runtime.h>
 
 #include "frog_chain.h"
+#include "dev_buf.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <limits>
+#include <memory>
 #include <type_traits>
 #include <string>
 #include <vector>
@@ -224,6 +227,28 @@ __device__ void chain_point(const DevLink *links, int n_links, double p[3], doub
     }
 }
 
+// A regular grid of nodes, x fastest: what frog_chain_check and frog_chain_sample evaluate the chain on, and the output
+// side of a reslice.
+struct NodeGrid {
+    double origin[3], spacing[3];
+    uint32_t dims[3];
+};
+
+// node idx of the grid: p = origin + (i, j, k) * spacing
+__device__ __forceinline__ void grid_node(const NodeGrid &g, size_t idx, double p[3])
+{
+    const uint32_t nx = g.dims[0], ny = g.dims[1];
+    const uint32_t i = (uint32_t)(idx % nx), j = (uint32_t)((idx / nx) % ny), k = (uint32_t)(idx / ((size_t)nx * ny));
+    p[0] = g.origin[0] + i * g.spacing[0]; p[1] = g.origin[1] + j * g.spacing[1]; p[2] = g.origin[2] + k * g.spacing[2];
+}
+
+// cofactor expansion along the first row
+__device__ __forceinline__ double det3(const double A[3][3])
+{
+    return A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0])
+         + A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+}
+
 // ---- vtkImageReslice as tools/VolumeTransform.cxx:119-136 configures it ------------------------------------
 // One thread per output voxel: its position in the reference volume's frame goes through the chain (which
 // maps output space to source space), the source is sampled there in its own scalar type, the arithmetic is
@@ -244,12 +269,11 @@ __device__ __forceinline__ S to_voxel(double v)
     }
 }
 
-// Geometry of one reslice: the source's voxel grid (s*) and the output grid (n*, o*), as frog_volume gives them.
+// Geometry of one reslice: the source's voxel grid (s*) and the output grid, as frog_volume gives them.
 struct ResliceGrid {
     int sx, sy, sz;
     double so[3], ss[3];
-    uint32_t nx, ny, nz;
-    double oo[3], os[3];
+    NodeGrid out;
     int linear;
     double background;
 };
@@ -258,10 +282,9 @@ struct ResliceGrid {
 template <class S>
 __device__ __forceinline__ S reslice_voxel(const DevLink *links, int n_links, const S *__restrict__ src, const ResliceGrid &g, size_t idx)
 {
-    const uint32_t nx = g.nx, ny = g.ny;
     const int sx = g.sx, sy = g.sy, sz = g.sz;
-    const uint32_t i = (uint32_t)(idx % nx), j = (uint32_t)((idx / nx) % ny), k = (uint32_t)(idx / ((size_t)nx * ny));
-    double p[3] = { g.oo[0] + i * g.os[0], g.oo[1] + j * g.os[1], g.oo[2] + k * g.os[2] }, A[3][3];
+    double p[3], A[3][3];
+    grid_node(g.out, idx, p);
     chain_point<false>(links, n_links, p, A);
     const double c[3] = { (p[0] - g.so[0]) / g.ss[0], (p[1] - g.so[1]) / g.ss[1], (p[2] - g.so[2]) / g.ss[2] };
     const int dims[3] = { sx, sy, sz };
@@ -293,7 +316,7 @@ template <class S>
 __global__ __launch_bounds__(256) void reslice_kernel(size_t base, const DevLink *links, int n_links, const S *__restrict__ src,
                                                       const ResliceGrid g, S *__restrict__ out)
 {
-    const size_t total = (size_t)g.nx * g.ny * g.nz;
+    const size_t total = (size_t)g.out.dims[0] * g.out.dims[1] * g.out.dims[2];
     const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     out[idx] = reslice_voxel<S>(links, n_links, src, g, idx);
@@ -319,7 +342,7 @@ __global__ __launch_bounds__(256) void reslice_accumulate_kernel(size_t base, co
                                                                  const ResliceGrid g, float n, float *__restrict__ avg,
                                                                  float *__restrict__ sq, S *__restrict__ out)
 {
-    const size_t total = (size_t)g.nx * g.ny * g.nz;
+    const size_t total = (size_t)g.out.dims[0] * g.out.dims[1] * g.out.dims[2];
     const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const S r = reslice_voxel<S>(links, n_links, src, g, idx);
@@ -358,22 +381,20 @@ __global__ __launch_bounds__(256) void chain_apply_kernel(size_t base, const Dev
 
 // one thread per grid node; block-level reduction of (negative count, minimum determinant) into the block's slot, numbered
 // from the first block of the whole grid (base is a multiple of the block size: chunked_launch)
-__global__ __launch_bounds__(256) void chain_check_kernel(size_t base, const DevLink *links, int n_links, double ox, double oy, double oz,
-                                                          double sx, double sy, double sz, uint32_t nx, uint32_t ny, uint32_t nz,
+__global__ __launch_bounds__(256) void chain_check_kernel(size_t base, const DevLink *links, int n_links, const NodeGrid g,
                                                           unsigned long long *n_negative, double *block_min)
 {
     __shared__ double mins[256];
     __shared__ unsigned int negs[256];
-    const size_t total = (size_t)nx * ny * nz;
+    const size_t total = (size_t)g.dims[0] * g.dims[1] * g.dims[2];
     const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     double det = INFINITY;
     unsigned int neg = 0;
     if (idx < total) {
-        const uint32_t i = (uint32_t)(idx % nx), j = (uint32_t)((idx / nx) % ny), k = (uint32_t)(idx / ((size_t)nx * ny));
-        double p[3] = { ox + i * sx, oy + j * sy, oz + k * sz }, A[3][3];
+        double p[3], A[3][3];
+        grid_node(g, idx, p);
         chain_point<true>(links, n_links, p, A);
-        det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0])
-            + A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+        det = det3(A);
         neg = det < 0 ? 1u : 0u;
     }
     mins[threadIdx.x] = det; negs[threadIdx.x] = neg;
@@ -393,14 +414,13 @@ __global__ __launch_bounds__(256) void chain_check_kernel(size_t base, const Dev
 // node, each stored with one cast.  DET selects chain_point<true>; without it no Jacobian is formed.
 template <bool DISP, bool DET, class T>
 __global__ __launch_bounds__(256) void chain_sample_kernel(size_t first, size_t base, size_t count, const DevLink *links, int n_links,
-                                                           double ox, double oy, double oz, double sx, double sy, double sz,
-                                                           uint32_t nx, uint32_t ny, T *__restrict__ displacement, T *__restrict__ determinant)
+                                                           const NodeGrid g, T *__restrict__ displacement, T *__restrict__ determinant)
 {
     const size_t local = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (local >= count) return;
     const size_t idx = first + local;
-    const uint32_t i = (uint32_t)(idx % nx), j = (uint32_t)((idx / nx) % ny), k = (uint32_t)(idx / ((size_t)nx * ny));
-    double p[3] = { ox + i * sx, oy + j * sy, oz + k * sz }, A[3][3];
+    double p[3], A[3][3];
+    grid_node(g, idx, p);
     const double node[3] = { p[0], p[1], p[2] };
     chain_point<DET>(links, n_links, p, A);
     if (DISP) {
@@ -409,19 +429,72 @@ __global__ __launch_bounds__(256) void chain_sample_kernel(size_t first, size_t 
         displacement[3 * local + 2] = (T)(p[2] - node[2]);
     }
     if (DET) {
-        const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0])
-                         + A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-        determinant[local] = (T)det;
+        determinant[local] = (T)det3(A);
     }
 }
 
+} // namespace
+
+struct frog_chain {
+    int device = 0;
+    std::vector<DevLink> h_links;
+    std::deque<frog::DevBuf<float>> d_coeffs;       // one per lattice or field link; a deque never copies its elements
+    frog::DevBuf<DevLink> d_links;
+};
+
+// mean and stdev of a group on one grid
+struct frog_average {
+    int device = 0;
+    frog_volume grid;
+    uint32_t n_images = 0, added = 0;
+    bool finished = false;
+    size_t total = 0;
+    frog::DevBuf<float> d_avg, d_sq;
+    frog::DevBuf<unsigned char> d_src, d_out;       // staging of the current source / resliced volume, grown on demand
+};
+
+namespace {
+
 int fail(int code, const std::string &msg) { frog::set_last_error(msg); return code; }
+
+// a failed HIP call: a refused device allocation is FROG_E_NOMEM from every entry point, as frog_create reports it
+int hip_fail(const std::string &what, hipError_t e)
+{
+    return fail(e == hipErrorOutOfMemory ? FROG_E_NOMEM : FROG_E_HIP, what + ": " + hipGetErrorString(e));
+}
 
 #define KCHECK(expr)                                                                         \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return fail(FROG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+        if (e_ != hipSuccess) return hip_fail(#expr, e_);                                    \
     } while (0)
+
+// the device of a new handle, made current
+int select_device(int device)
+{
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FROG_E_NODEVICE, "no HIP device: no CPU fallback");
+    if (device < 0 || device >= count) return fail(FROG_E_INVALID, "bad device index");
+    KCHECK(hipSetDevice(device));
+    return FROG_OK;
+}
+
+// f(S()) with S the C type of a FROG_V_* value
+template <class F>
+int with_voxel_type(int dtype, F f)
+{
+    switch (dtype) {
+    case FROG_V_U8: return f(uint8_t());
+    case FROG_V_I8: return f(int8_t());
+    case FROG_V_U16: return f(uint16_t());
+    case FROG_V_I16: return f(int16_t());
+    case FROG_V_U32: return f(uint32_t());
+    case FROG_V_I32: return f(int32_t());
+    case FROG_V_F32: return f(float());
+    case FROG_V_F64: return f(double());
+    default: return fail(FROG_E_INVALID, "unknown scalar type");
+    }
+}
 
 // Every launch in this file goes through chunked_launch: one work-item per element of [0, total), 256 per block, at most
 // 2^31 work-items per launch.  A dispatch packet's grid is 32-bit WORK-ITEMS per dimension; a larger 1-D launch returns no
@@ -454,36 +527,115 @@ hipError_t chunked_launch(size_t total, Launch launch)
     return hipSuccess;
 }
 
-} // namespace
-
-struct frog_chain {
-    int device = 0;
-    std::vector<DevLink> h_links;
-    std::vector<float *> d_coeffs;
-    DevLink *d_links = nullptr;
-};
-
-extern "C" {
-
-void frog_chain_destroy(frog_chain *c)
+NodeGrid node_grid(const double origin[3], const double spacing[3], const uint32_t dims[3])
 {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    for (float *p : c->d_coeffs) if (p) (void)hipFree(p);
-    if (c->d_links) (void)hipFree(c->d_links);
-    delete c;
+    NodeGrid g;
+    for (int k = 0; k < 3; k++) { g.origin[k] = origin[k]; g.spacing[k] = spacing[k]; g.dims[k] = dims[k]; }
+    return g;
 }
 
-uint32_t frog_chain_num_links(const frog_chain *c) { return c ? (uint32_t)c->h_links.size() : 0; }
+// frog_chain_sample's device buffers hold one slab of the grid: whole launches (chunked_launch's step), at most
+// SAMPLE_SLAB_LAUNCHES of them, within SAMPLE_SLAB_BYTES and half of the free device memory; where one launch does not fit,
+// a part of one.  Each slab is computed, then copied to its place in the host arrays.
+constexpr size_t SAMPLE_SLAB_BYTES = (size_t)1 << 30;
+constexpr size_t SAMPLE_SLAB_LAUNCHES = 4;
+
+template <class T>
+int sample_typed(frog_chain *c, const NodeGrid &grid, size_t total, T *displacement, T *determinant)
+{
+    const size_t per_node = ((displacement ? 3 : 0) + (determinant ? 1 : 0)) * sizeof(T);
+    size_t free_bytes = 0, device_bytes = 0;
+    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
+    const size_t step = launch_max();
+    const size_t fit = std::max(LAUNCH_BLOCK, std::min(free_bytes / 2, SAMPLE_SLAB_BYTES) / per_node / LAUNCH_BLOCK * LAUNCH_BLOCK);
+    size_t slab = fit >= step ? std::min(fit / step, SAMPLE_SLAB_LAUNCHES) * step : fit;
+    slab = std::min(slab, (total + LAUNCH_BLOCK - 1) / LAUNCH_BLOCK * LAUNCH_BLOCK);
+    frog::DevBuf<T> d_disp, d_det;
+    if (displacement) KCHECK(d_disp.alloc(3 * slab));
+    if (determinant) KCHECK(d_det.alloc(slab));
+    const auto kernel = displacement && determinant ? chain_sample_kernel<true, true, T>
+                      : displacement ? chain_sample_kernel<true, false, T> : chain_sample_kernel<false, true, T>;
+    hipError_t e = hipSuccess;
+    for (size_t first = 0; first < total && e == hipSuccess; first += slab) {
+        const size_t count = std::min(slab, total - first);
+        e = chunked_launch(count, [&](unsigned blocks, size_t base) {
+            kernel<<<blocks, LAUNCH_BLOCK>>>(first, base, count, c->d_links.p, (int)c->h_links.size(), grid, d_disp.p, d_det.p);
+        });
+        if (e == hipSuccess && displacement) e = hipMemcpy(displacement + 3 * first, d_disp.p, 3 * count * sizeof(T), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && determinant) e = hipMemcpy(determinant + first, d_det.p, count * sizeof(T), hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return hip_fail("frog_chain_sample", e);
+    return FROG_OK;
+}
+
+ResliceGrid reslice_grid(const frog_volume *src, const frog_volume *out, int interpolation, double background)
+{
+    ResliceGrid g;
+    g.sx = (int)src->dims[0]; g.sy = (int)src->dims[1]; g.sz = (int)src->dims[2];
+    for (int k = 0; k < 3; k++) { g.so[k] = src->origin[k]; g.ss[k] = src->spacing[k]; }
+    g.out = node_grid(out->origin, out->spacing, out->dims);
+    g.linear = interpolation != 0;
+    g.background = background;
+    return g;
+}
+
+template <class S>
+int reslice_typed(frog_chain *c, const frog_volume *src, frog_volume *out, int interpolation, double background)
+{
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2], n_out = (size_t)out->dims[0] * out->dims[1] * out->dims[2];
+    frog::DevBuf<S> d_src, d_out;
+    KCHECK(d_src.alloc(n_src));
+    KCHECK(d_out.alloc(n_out));
+    hipError_t e = hipMemcpy(d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const ResliceGrid g = reslice_grid(src, out, interpolation, background);
+        e = chunked_launch(n_out, [&](unsigned blocks, size_t base) {
+            reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src.p, g, d_out.p);
+        });
+    }
+    if (e == hipSuccess) e = hipMemcpy(out->data, d_out.p, n_out * sizeof(S), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_chain_reslice", e);
+    return FROG_OK;
+}
+
+template <class S>
+int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+{
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    const float n = (float)a->n_images;
+    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
+    if (c && resliced) KCHECK(a->d_out.alloc(a->total * sizeof(S)));
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = (S *)a->d_out.p;
+    hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const ResliceGrid g = reslice_grid(src, &a->grid, interpolation, background);
+        e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+            if (c)
+                reslice_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, n,
+                                                                       a->d_avg.p, a->d_sq.p, resliced ? d_out : nullptr);
+            else
+                identity_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_src, a->total, n, a->d_avg.p, a->d_sq.p);
+        });
+    }
+    if (e == hipSuccess && resliced) {
+        if (c) e = hipMemcpy(resliced->data, d_out, a->total * sizeof(S), hipMemcpyDeviceToHost);
+        else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return hip_fail("frog_average_add", e);
+    return FROG_OK;
+}
+
+} // namespace
+
+extern "C" {
 
 int frog_chain_create(const frog_chain_link *links, uint32_t n_links, int device, frog_chain **out)
 {
     if (!out || (n_links && !links)) return fail(FROG_E_INVALID, "bad arguments to frog_chain_create");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FROG_E_NODEVICE, "no HIP device: no CPU fallback");
-    if (device < 0 || device >= count) return fail(FROG_E_INVALID, "bad device index");
-    KCHECK(hipSetDevice(device));
-    frog_chain *c = new (std::nothrow) frog_chain;
+    if (int rc = select_device(device)) return rc;
+    std::unique_ptr<frog_chain> c(new (std::nothrow) frog_chain);
     if (!c) return fail(FROG_E_NOMEM, "out of host memory");
     c->device = device;
     for (uint32_t l = 0; l < n_links; l++) {
@@ -493,58 +645,58 @@ int frog_chain_create(const frog_chain_link *links, uint32_t n_links, int device
         d.type = t.type;
         if (t.type == FROG_T_LINEAR) {
             for (int k = 0; k < 12; k++) d.m[k] = t.matrix[k];
-            c->d_coeffs.push_back(nullptr);
         } else if (t.type == FROG_T_BSPLINE || t.type == FROG_T_BSPLINE_INVERSE || t.type == FROG_T_FIELD) {
             // a field's nodes are validated and uploaded like a lattice's control points
             const size_t G = (size_t)t.dims[0] * t.dims[1] * t.dims[2];
-            if (!G || !t.coeffs) { frog_chain_destroy(c); return fail(FROG_E_INVALID, "empty lattice"); }
+            if (!G || !t.coeffs) return fail(FROG_E_INVALID, "empty lattice");
             for (int k = 0; k < 3; k++) {
-                if (!(t.spacing[k] > 0)) { frog_chain_destroy(c); return fail(FROG_E_INVALID, "lattice spacing must be positive"); }
+                if (!(t.spacing[k] > 0)) return fail(FROG_E_INVALID, "lattice spacing must be positive");
                 d.dims[k] = (int)t.dims[k]; d.origin[k] = t.origin[k]; d.spacing[k] = t.spacing[k];
             }
-            float *p = nullptr;
-            if (hipMalloc((void **)&p, 3 * G * sizeof(float)) != hipSuccess
-                || hipMemcpy(p, t.coeffs, 3 * G * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-                if (p) (void)hipFree(p);
-                frog_chain_destroy(c);
-                return fail(FROG_E_HIP, "cannot copy lattice coefficients to the device");
-            }
-            d.coeffs = p;
-            c->d_coeffs.push_back(p);
+            frog::DevBuf<float> &coeffs = c->d_coeffs.emplace_back();
+            hipError_t e = coeffs.alloc(3 * G);
+            if (e == hipSuccess) e = hipMemcpy(coeffs.p, t.coeffs, 3 * G * sizeof(float), hipMemcpyHostToDevice);
+            if (e != hipSuccess) return hip_fail("cannot copy lattice coefficients to the device", e);
+            d.coeffs = coeffs.p;
         } else {
-            frog_chain_destroy(c);
             return fail(FROG_E_INVALID, "unknown transform type");
         }
         c->h_links.push_back(d);
     }
     if (n_links) {
-        if (hipMalloc((void **)&c->d_links, n_links * sizeof(DevLink)) != hipSuccess
-            || hipMemcpy(c->d_links, c->h_links.data(), n_links * sizeof(DevLink), hipMemcpyHostToDevice) != hipSuccess) {
-            frog_chain_destroy(c);
-            return fail(FROG_E_HIP, "cannot copy the chain to the device");
-        }
+        hipError_t e = c->d_links.alloc(n_links);
+        if (e == hipSuccess) e = hipMemcpy(c->d_links.p, c->h_links.data(), n_links * sizeof(DevLink), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail("cannot copy the chain to the device", e);
     }
-    *out = c;
+    *out = c.release();
     return FROG_OK;
 }
+
+void frog_chain_destroy(frog_chain *c)
+{
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    delete c;
+}
+
+uint32_t frog_chain_num_links(const frog_chain *c) { return c ? (uint32_t)c->h_links.size() : 0; }
 
 int frog_chain_apply(frog_chain *c, const double *in, double *out, size_t n)
 {
     if (!c || (n && (!in || !out))) return fail(FROG_E_INVALID, "bad arguments to frog_chain_apply");
     if (!n) return FROG_OK;
     KCHECK(hipSetDevice(c->device));
-    double *d_in = nullptr, *d_out = nullptr;
-    KCHECK(hipMalloc((void **)&d_in, 3 * n * sizeof(double)));
-    if (hipMalloc((void **)&d_out, 3 * n * sizeof(double)) != hipSuccess) { (void)hipFree(d_in); return fail(FROG_E_HIP, "hipMalloc"); }
-    hipError_t e = hipMemcpy(d_in, in, 3 * n * sizeof(double), hipMemcpyHostToDevice);
+    frog::DevBuf<double> d_in, d_out;
+    KCHECK(d_in.alloc(3 * n));
+    KCHECK(d_out.alloc(3 * n));
+    hipError_t e = hipMemcpy(d_in.p, in, 3 * n * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         e = chunked_launch(n, [&](unsigned blocks, size_t base) {
-            chain_apply_kernel<<<blocks, LAUNCH_BLOCK>>>(base, c->d_links, (int)c->h_links.size(), d_in, d_out, n);
+            chain_apply_kernel<<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_in.p, d_out.p, n);
         });
     }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, 3 * n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d_in); (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_chain_apply: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = hipMemcpy(out, d_out.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_chain_apply", e);
     return FROG_OK;
 }
 
@@ -559,96 +711,25 @@ int frog_chain_check(frog_chain *c, const double origin[3], const double spacing
     if (total > ((size_t)1 << 40)) return fail(FROG_E_INVALID, "grid too large");
     KCHECK(hipSetDevice(c->device));
     const size_t blocks = (total + LAUNCH_BLOCK - 1) / LAUNCH_BLOCK;     // one block_min slot per block of the whole grid
-    unsigned long long *d_neg = nullptr;
-    double *d_min = nullptr;
-    KCHECK(hipMalloc((void **)&d_neg, sizeof(unsigned long long)));
-    if (hipMalloc((void **)&d_min, blocks * sizeof(double)) != hipSuccess) { (void)hipFree(d_neg); return fail(FROG_E_HIP, "hipMalloc"); }
-    hipError_t e = hipMemset(d_neg, 0, sizeof(unsigned long long));
+    frog::DevBuf<unsigned long long> d_neg;
+    frog::DevBuf<double> d_min;
+    KCHECK(d_neg.alloc(1));
+    KCHECK(d_min.alloc(blocks));
+    hipError_t e = hipMemset(d_neg.p, 0, sizeof(unsigned long long));
     if (e == hipSuccess) {
+        const NodeGrid grid = node_grid(origin, spacing, dims);
         e = chunked_launch(total, [&](unsigned nb, size_t base) {
-            chain_check_kernel<<<nb, LAUNCH_BLOCK>>>(base, c->d_links, (int)c->h_links.size(), origin[0], origin[1], origin[2],
-                                                     spacing[0], spacing[1], spacing[2], dims[0], dims[1], dims[2], d_neg, d_min);
+            chain_check_kernel<<<nb, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), grid, d_neg.p, d_min.p);
         });
     }
     unsigned long long neg = 0;
     std::vector<double> mins(blocks);
-    if (e == hipSuccess) e = hipMemcpy(&neg, d_neg, sizeof neg, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(mins.data(), d_min, blocks * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d_neg); (void)hipFree(d_min);
-    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_chain_check: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = hipMemcpy(&neg, d_neg.p, sizeof neg, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(mins.data(), d_min.p, blocks * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_chain_check", e);
     *n_negative = neg;
     if (min_determinant) { double m = INFINITY; for (double v : mins) m = std::fmin(m, v); *min_determinant = m; }
     return FROG_OK;
-}
-
-
-extern "C++" {
-namespace {
-
-// frog_chain_sample's device buffers hold one slab of the grid: whole launches (chunked_launch's step), at most
-// SAMPLE_SLAB_LAUNCHES of them, within SAMPLE_SLAB_BYTES and half of the free device memory; where one launch does not fit,
-// a part of one.  Each slab is computed, then copied to its place in the host arrays.
-constexpr size_t SAMPLE_SLAB_BYTES = (size_t)1 << 30;
-constexpr size_t SAMPLE_SLAB_LAUNCHES = 4;
-
-template <class T>
-int sample_typed(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3], size_t total,
-                 T *displacement, T *determinant)
-{
-    const size_t per_node = ((displacement ? 3 : 0) + (determinant ? 1 : 0)) * sizeof(T);
-    size_t free_bytes = 0, device_bytes = 0;
-    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
-    const size_t step = launch_max();
-    const size_t fit = std::max(LAUNCH_BLOCK, std::min(free_bytes / 2, SAMPLE_SLAB_BYTES) / per_node / LAUNCH_BLOCK * LAUNCH_BLOCK);
-    size_t slab = fit >= step ? std::min(fit / step, SAMPLE_SLAB_LAUNCHES) * step : fit;
-    slab = std::min(slab, (total + LAUNCH_BLOCK - 1) / LAUNCH_BLOCK * LAUNCH_BLOCK);
-    T *d_disp = nullptr, *d_det = nullptr;
-    if (displacement) KCHECK(hipMalloc((void **)&d_disp, 3 * slab * sizeof(T)));
-    if (determinant && hipMalloc((void **)&d_det, slab * sizeof(T)) != hipSuccess) {
-        if (d_disp) (void)hipFree(d_disp);
-        return fail(FROG_E_NOMEM, "hipMalloc (determinant slab)");
-    }
-    hipError_t e = hipSuccess;
-    for (size_t first = 0; first < total && e == hipSuccess; first += slab) {
-        const size_t count = std::min(slab, total - first);
-        e = chunked_launch(count, [&](unsigned blocks, size_t base) {
-            const DevLink *links = c->d_links;
-            const int n = (int)c->h_links.size();
-            if (displacement && determinant)
-                chain_sample_kernel<true, true, T><<<blocks, LAUNCH_BLOCK>>>(first, base, count, links, n, origin[0], origin[1], origin[2],
-                                                                             spacing[0], spacing[1], spacing[2], dims[0], dims[1], d_disp, d_det);
-            else if (displacement)
-                chain_sample_kernel<true, false, T><<<blocks, LAUNCH_BLOCK>>>(first, base, count, links, n, origin[0], origin[1], origin[2],
-                                                                              spacing[0], spacing[1], spacing[2], dims[0], dims[1], d_disp, d_det);
-            else
-                chain_sample_kernel<false, true, T><<<blocks, LAUNCH_BLOCK>>>(first, base, count, links, n, origin[0], origin[1], origin[2],
-                                                                              spacing[0], spacing[1], spacing[2], dims[0], dims[1], d_disp, d_det);
-        });
-        if (e == hipSuccess && displacement) e = hipMemcpy(displacement + 3 * first, d_disp, 3 * count * sizeof(T), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && determinant) e = hipMemcpy(determinant + first, d_det, count * sizeof(T), hipMemcpyDeviceToHost);
-    }
-    if (d_disp) (void)hipFree(d_disp);
-    if (d_det) (void)hipFree(d_det);
-    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_chain_sample: ") + hipGetErrorString(e));
-    return FROG_OK;
-}
-
-} // namespace
-} // extern "C++"
-
-int frog_chain_sample(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3],
-                      int dtype, void *displacement, void *determinant)
-{
-    if (!c || !origin || !spacing || !dims) return fail(FROG_E_INVALID, "bad arguments to frog_chain_sample");
-    if (!displacement && !determinant) return fail(FROG_E_INVALID, "frog_chain_sample: no output asked for");
-    if (dtype != FROG_V_F32 && dtype != FROG_V_F64) return fail(FROG_E_INVALID, "frog_chain_sample: the output type must be FROG_V_F32 or FROG_V_F64");
-    const size_t limit = (size_t)1 << 40, plane = (size_t)dims[0] * dims[1];
-    if (!plane || !dims[2]) return FROG_OK;
-    if (plane > limit || dims[2] > limit / plane) return fail(FROG_E_INVALID, "grid too large");
-    const size_t total = plane * dims[2];
-    KCHECK(hipSetDevice(c->device));
-    if (dtype == FROG_V_F32) return sample_typed<float>(c, origin, spacing, dims, total, (float *)displacement, (float *)determinant);
-    return sample_typed<double>(c, origin, spacing, dims, total, (double *)displacement, (double *)determinant);
 }
 
 int frog_chain_invert_links(const frog_chain_link *in, uint32_t n, frog_chain_link *out)
@@ -684,42 +765,21 @@ int frog_chain_invert_links(const frog_chain_link *in, uint32_t n, frog_chain_li
     return FROG_OK;
 }
 
-extern "C++" {
-namespace {
-
-ResliceGrid reslice_grid(const frog_volume *src, const frog_volume *out, int interpolation, double background)
+int frog_chain_sample(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3],
+                      int dtype, void *displacement, void *determinant)
 {
-    ResliceGrid g;
-    g.sx = (int)src->dims[0]; g.sy = (int)src->dims[1]; g.sz = (int)src->dims[2];
-    g.nx = out->dims[0]; g.ny = out->dims[1]; g.nz = out->dims[2];
-    for (int k = 0; k < 3; k++) { g.so[k] = src->origin[k]; g.ss[k] = src->spacing[k]; g.oo[k] = out->origin[k]; g.os[k] = out->spacing[k]; }
-    g.linear = interpolation != 0;
-    g.background = background;
-    return g;
+    if (!c || !origin || !spacing || !dims) return fail(FROG_E_INVALID, "bad arguments to frog_chain_sample");
+    if (!displacement && !determinant) return fail(FROG_E_INVALID, "frog_chain_sample: no output asked for");
+    if (dtype != FROG_V_F32 && dtype != FROG_V_F64) return fail(FROG_E_INVALID, "frog_chain_sample: the output type must be FROG_V_F32 or FROG_V_F64");
+    const size_t limit = (size_t)1 << 40, plane = (size_t)dims[0] * dims[1];
+    if (!plane || !dims[2]) return FROG_OK;
+    if (plane > limit || dims[2] > limit / plane) return fail(FROG_E_INVALID, "grid too large");
+    const size_t total = plane * dims[2];
+    KCHECK(hipSetDevice(c->device));
+    const NodeGrid grid = node_grid(origin, spacing, dims);
+    if (dtype == FROG_V_F32) return sample_typed<float>(c, grid, total, (float *)displacement, (float *)determinant);
+    return sample_typed<double>(c, grid, total, (double *)displacement, (double *)determinant);
 }
-
-template <class S>
-int reslice_typed(frog_chain *c, const frog_volume *src, frog_volume *out, int interpolation, double background)
-{
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2], n_out = (size_t)out->dims[0] * out->dims[1] * out->dims[2];
-    S *d_src = nullptr, *d_out = nullptr;
-    KCHECK(hipMalloc((void **)&d_src, n_src * sizeof(S)));
-    if (hipMalloc((void **)&d_out, n_out * sizeof(S)) != hipSuccess) { (void)hipFree(d_src); return fail(FROG_E_NOMEM, "hipMalloc (output volume)"); }
-    hipError_t e = hipMemcpy(d_src, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const ResliceGrid g = reslice_grid(src, out, interpolation, background);
-        e = chunked_launch(n_out, [&](unsigned blocks, size_t base) {
-            reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links, (int)c->h_links.size(), d_src, g, d_out);
-        });
-    }
-    if (e == hipSuccess) e = hipMemcpy(out->data, d_out, n_out * sizeof(S), hipMemcpyDeviceToHost);
-    (void)hipFree(d_src); (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_chain_reslice: ") + hipGetErrorString(e));
-    return FROG_OK;
-}
-
-} // namespace
-} // extern "C++"
 
 int frog_chain_reslice(frog_chain *c, const frog_volume *src, frog_volume *out, int interpolation, double background)
 {
@@ -730,82 +790,7 @@ int frog_chain_reslice(frog_chain *c, const frog_volume *src, frog_volume *out, 
     for (int k = 0; k < 3; k++)
         if (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0)) return fail(FROG_E_INVALID, "bad source geometry");
     KCHECK(hipSetDevice(c->device));
-    switch (src->dtype) {
-    case FROG_V_U8: return reslice_typed<uint8_t>(c, src, out, interpolation, background);
-    case FROG_V_I8: return reslice_typed<int8_t>(c, src, out, interpolation, background);
-    case FROG_V_U16: return reslice_typed<uint16_t>(c, src, out, interpolation, background);
-    case FROG_V_I16: return reslice_typed<int16_t>(c, src, out, interpolation, background);
-    case FROG_V_U32: return reslice_typed<uint32_t>(c, src, out, interpolation, background);
-    case FROG_V_I32: return reslice_typed<int32_t>(c, src, out, interpolation, background);
-    case FROG_V_F32: return reslice_typed<float>(c, src, out, interpolation, background);
-    default: return reslice_typed<double>(c, src, out, interpolation, background);
-    }
-}
-
-
-// ---- frog_average: mean and stdev of a group on one grid ------------------------------------------------------------------
-
-struct frog_average {
-    int device = 0;
-    frog_volume grid;
-    uint32_t n_images = 0, added = 0;
-    bool finished = false;
-    size_t total = 0;
-    float *d_avg = nullptr, *d_sq = nullptr;
-    void *d_src = nullptr, *d_out = nullptr;       // staging of the current source / resliced volume, grown on demand
-    size_t src_bytes = 0, out_bytes = 0;
-};
-
-extern "C++" {
-namespace {
-
-int grow(void **p, size_t *have, size_t want)
-{
-    if (*have >= want) return FROG_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    if (hipMalloc(p, want) != hipSuccess) { *p = nullptr; return fail(FROG_E_NOMEM, "hipMalloc (average staging)"); }
-    *have = want;
-    return FROG_OK;
-}
-
-template <class S>
-int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
-{
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    const float n = (float)a->n_images;
-    if (int rc = grow(&a->d_src, &a->src_bytes, n_src * sizeof(S))) return rc;
-    if (c && resliced) if (int rc = grow(&a->d_out, &a->out_bytes, a->total * sizeof(S))) return rc;
-    hipError_t e = hipMemcpy(a->d_src, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const ResliceGrid g = reslice_grid(src, &a->grid, interpolation, background);
-        e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-            if (c)
-                reslice_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links, (int)c->h_links.size(), (const S *)a->d_src, g, n,
-                                                                       a->d_avg, a->d_sq, resliced ? (S *)a->d_out : nullptr);
-            else
-                identity_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, (const S *)a->d_src, a->total, n, a->d_avg, a->d_sq);
-        });
-    }
-    if (e == hipSuccess && resliced) {
-        if (c) e = hipMemcpy(resliced->data, a->d_out, a->total * sizeof(S), hipMemcpyDeviceToHost);
-        else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_average_add: ") + hipGetErrorString(e));
-    return FROG_OK;
-}
-
-} // namespace
-} // extern "C++"
-
-void frog_average_destroy(frog_average *a)
-{
-    if (!a) return;
-    if (a->d_avg || a->d_sq || a->d_src || a->d_out) {
-        (void)hipSetDevice(a->device);
-        for (void *p : { (void *)a->d_avg, (void *)a->d_sq, a->d_src, a->d_out }) if (p) (void)hipFree(p);
-    }
-    delete a;
+    return with_voxel_type(src->dtype, [&](auto s) { return reslice_typed<decltype(s)>(c, src, out, interpolation, background); });
 }
 
 int frog_average_create(const frog_volume *grid, uint32_t n_images, int device, frog_average **out)
@@ -815,27 +800,20 @@ int frog_average_create(const frog_volume *grid, uint32_t n_images, int device, 
     if (!total) return fail(FROG_E_INVALID, "empty grid");
     // one thread per voxel, 256 per block: a grid above 2^31 voxels is refused here rather than launched
     if (total > ((size_t)1 << 31)) return fail(FROG_E_INVALID, "grid above 2^31 voxels");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(FROG_E_NODEVICE, "no HIP device: no CPU fallback");
-    if (device < 0 || device >= count) return fail(FROG_E_INVALID, "bad device index");
-    KCHECK(hipSetDevice(device));
-    frog_average *a = new (std::nothrow) frog_average;
+    if (int rc = select_device(device)) return rc;
+    std::unique_ptr<frog_average> a(new (std::nothrow) frog_average);
     if (!a) return fail(FROG_E_NOMEM, "out of host memory");
     a->device = device;
     a->grid = *grid;
     a->grid.data = nullptr;
     a->n_images = n_images;
     a->total = total;
-    if (hipMalloc((void **)&a->d_avg, total * sizeof(float)) != hipSuccess || hipMalloc((void **)&a->d_sq, total * sizeof(float)) != hipSuccess) {
-        frog_average_destroy(a);
-        return fail(FROG_E_NOMEM, "hipMalloc (average accumulators)");
-    }
+    KCHECK(a->d_avg.alloc(total));
+    KCHECK(a->d_sq.alloc(total));
     // both accumulators start at zero (the reference never clears its stdev image: AverageVolumes.cxx:31-43)
-    if (hipMemset(a->d_avg, 0, total * sizeof(float)) != hipSuccess || hipMemset(a->d_sq, 0, total * sizeof(float)) != hipSuccess) {
-        frog_average_destroy(a);
-        return fail(FROG_E_HIP, "hipMemset (average accumulators)");
-    }
-    *out = a;
+    KCHECK(hipMemset(a->d_avg.p, 0, total * sizeof(float)));
+    KCHECK(hipMemset(a->d_sq.p, 0, total * sizeof(float)));
+    *out = a.release();
     return FROG_OK;
 }
 
@@ -853,17 +831,7 @@ int frog_average_add(frog_average *a, frog_chain *c, const frog_volume *src, int
     }
     if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, "frog_average_add: resliced volume must have the source's type");
     KCHECK(hipSetDevice(a->device));
-    int rc;
-    switch (src->dtype) {
-    case FROG_V_U8: rc = average_add_typed<uint8_t>(a, c, src, interpolation, background, resliced); break;
-    case FROG_V_I8: rc = average_add_typed<int8_t>(a, c, src, interpolation, background, resliced); break;
-    case FROG_V_U16: rc = average_add_typed<uint16_t>(a, c, src, interpolation, background, resliced); break;
-    case FROG_V_I16: rc = average_add_typed<int16_t>(a, c, src, interpolation, background, resliced); break;
-    case FROG_V_U32: rc = average_add_typed<uint32_t>(a, c, src, interpolation, background, resliced); break;
-    case FROG_V_I32: rc = average_add_typed<int32_t>(a, c, src, interpolation, background, resliced); break;
-    case FROG_V_F32: rc = average_add_typed<float>(a, c, src, interpolation, background, resliced); break;
-    default: rc = average_add_typed<double>(a, c, src, interpolation, background, resliced); break;
-    }
+    const int rc = with_voxel_type(src->dtype, [&](auto s) { return average_add_typed<decltype(s)>(a, c, src, interpolation, background, resliced); });
     if (rc == FROG_OK) a->added++;
     return rc;
 }
@@ -876,14 +844,21 @@ int frog_average_finish(frog_average *a, float *mean, float *stdev)
     hipError_t e = hipSuccess;
     if (!a->finished) {
         e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-            average_finish_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_avg, a->d_sq, a->total);
+            average_finish_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_avg.p, a->d_sq.p, a->total);
         });
         a->finished = e == hipSuccess;                 // stdev now stands in place of sq: a second call only copies
     }
-    if (e == hipSuccess) e = hipMemcpy(mean, a->d_avg, a->total * sizeof(float), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(stdev, a->d_sq, a->total * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(FROG_E_HIP, std::string("frog_average_finish: ") + hipGetErrorString(e));
+    if (e == hipSuccess) e = hipMemcpy(mean, a->d_avg.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(stdev, a->d_sq.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_average_finish", e);
     return FROG_OK;
+}
+
+void frog_average_destroy(frog_average *a)
+{
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    delete a;
 }
 
 }

@@ -10,8 +10,7 @@
 // bit for bit.  -wt 1 also writes transformed<i>.nii.gz, the file transform.sh leaves behind.  Every transform and volume
 // header is checked before anything is written.  Volumes are read and inflated on host threads ahead of the device, a
 // bounded number at a time (volume_stream.h).
-#include "frog_chain.h"
-#include "frog_host.h"
+#include "tool_common.h"
 #include "volume_stream.h"
 
 #include <sys/stat.h>
@@ -25,8 +24,6 @@
 #include <iostream>
 #include <string>
 #include <vector>
-
-extern "C" const char *frog_last_error(void);
 
 namespace {
 
@@ -59,8 +56,7 @@ int main(int argc, char *argv[])
     std::vector<std::string> volumes;
     std::string transformsDir = "transforms", outDir = ".";
     int interpolation = 1, device = 0, writeTransformed = 0;
-    bool backGroundSet = false;
-    float backGroundLevel = 0;
+    BackgroundLevel background;
     auto is_flag = [](const char *a) {
         for (const char *f : { "-td", "-o", "-i", "-b", "-wt", "-dev" }) if (std::strcmp(a, f) == 0) return true;
         return false;
@@ -72,7 +68,7 @@ int main(int argc, char *argv[])
         if (std::strcmp(key, "-td") == 0) transformsDir = value;
         else if (std::strcmp(key, "-o") == 0) outDir = value;
         else if (std::strcmp(key, "-i") == 0) interpolation = atoi(value);
-        else if (std::strcmp(key, "-b") == 0) { backGroundLevel = atof(value); backGroundSet = true; }
+        else if (std::strcmp(key, "-b") == 0) background.parse(value);
         else if (std::strcmp(key, "-wt") == 0) writeTransformed = atoi(value);
         else if (std::strcmp(key, "-dev") == 0) device = atoi(value);
         else die(std::string("unknown option ") + key);
@@ -87,16 +83,15 @@ int main(int argc, char *argv[])
     // ---- everything is checked before the first output: the grid, every transform, every volume header
     frog_volume grid;
     if (frog_bbox_grid(argv[1], atof(argv[2]), &grid)) die(std::string("cannot read a bounding box from ") + argv[1] + " (or spacing " + argv[2] + " is not positive)");
-    std::vector<frog_transform_file *> files(n, nullptr);
+    ChainArguments transforms;                              // owns the files; every image has a chain of its own
     std::vector<std::vector<frog_chain_link>> inverse(n);
     for (size_t i = 0; i < n; i++) {
         const std::string path = transformsDir + "/" + std::to_string(i) + ".json";
-        int status = 0;
-        files[i] = frog_transform_read(path.c_str(), &status);
-        if (!files[i]) die("cannot read transform " + path);
-        const uint32_t nl = frog_transform_num_links(files[i]);
+        frog_transform_file *f = transforms.read(path.c_str());
+        if (!f) die("cannot read transform " + path);
+        const uint32_t nl = frog_transform_num_links(f);
         inverse[i].resize(nl);
-        if (frog_chain_invert_links(frog_transform_links(files[i]), nl, inverse[i].data())) die(path + ": " + frog_last_error());
+        if (frog_chain_invert_links(frog_transform_links(f), nl, inverse[i].data())) die(path + ": " + frog_last_error());
     }
     for (const auto &v : volumes) if (!header_ok(v)) die("cannot read volume " + v);
     if (mkdir(outDir.c_str(), 0755) != 0 && errno != EEXIST) die("cannot create " + outDir);
@@ -132,7 +127,7 @@ int main(int argc, char *argv[])
             out = &resliced;
         }
         t0 = clk::now();
-        if (frog_average_add(avg, chains[i], &it.view, interpolation, backGroundSet ? (double)backGroundLevel : it.lo, out))
+        if (frog_average_add(avg, chains[i], &it.view, interpolation, background.of(it.lo), out))
             die(volumes[i] + ": " + frog_last_error());
         device_s += seconds(t0);
         stream.release(i);
@@ -159,7 +154,6 @@ int main(int argc, char *argv[])
         if (frog_volume_write(path.c_str(), &grid)) die("cannot write " + path);
     }
     write_s += seconds(t0);
-    for (auto *f : files) frog_transform_free(f);
     char line[512];
     std::snprintf(line, sizeof line,
                   "read : %.3f s of %d host threads (device waited %.3f s)\ndevice : %.3f s (+ %.3f s set-up)\nwrite : %.3f s\ntotal : %.3f s",

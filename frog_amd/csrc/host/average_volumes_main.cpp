@@ -6,8 +6,7 @@
 // rounds negative).  Deviations: sq starts at zero (upstream never clears it) and a file whose dimensions differ from the
 // first's is an error (exit 1, nothing written) where upstream reads past its buffer.  Files are read and inflated on host
 // threads ahead of the device (volume_stream.h).  New: -dev <n> as the last two arguments selects the HIP device.
-#include "frog_chain.h"
-#include "frog_host.h"
+#include "tool_common.h"
 #include "volume_stream.h"
 
 #include <cstdlib>
@@ -15,8 +14,6 @@
 #include <iostream>
 #include <string>
 #include <vector>
-
-extern "C" const char *frog_last_error(void);
 
 int main(int argc, char *argv[])
 {

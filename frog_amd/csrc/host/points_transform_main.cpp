@@ -3,7 +3,7 @@
 // -t concatenates a transform file, -ti its inverse (reversed links, inverted matrices, Newton on the
 // lattices: frog_chain_invert_links).  The outer vtkGeneralTransform is in VTK's default PreMultiply mode
 // (:25-26), so of several -t/-ti the one given LAST is applied to the point FIRST.
-#include "chain_args.h"
+#include "tool_common.h"
 
 #include <cstdlib>
 #include <cstring>

@@ -3,12 +3,12 @@
 //   TransformField reference [-t transform] [-ti inverse_transform] [-s spacing] [-o field.nii.gz] [-j jacobian.nii.gz] [-w chain.json]
 // `reference` gives the grid (NIfTI-1 or MetaImage header; the voxels are not read); -s resamples it to an isotropic spacing
 // over the same extent by CheckDiffeomorphism's rule, n = max(1, round(n_old * old_spacing / spacing)) nodes per axis from
-// the same origin.  -t / -ti compose as in PointsTransform (chain_args.h).  -o writes the field, -j the determinants: NIfTI-1
+// the same origin.  -t / -ti compose as in PointsTransform (tool_common.h).  -o writes the field, -j the determinants: NIfTI-1
 // FLOAT32 with 3 and 1 components, in the layout of the lattice sidecars.  -w writes a one-entry transform file naming the -o
 // file, which the other tools read as a single field link (frog_chain.h); it goes into the directory of the -o file.  The
 // headers hold f32 numbers, so a spacing that is no f32 value is stored rounded.  Always prints CheckDiffeomorphism's line
 // about negative determinants, then their minimum and maximum.  New: -dev <n> selects the HIP device.
-#include "chain_args.h"
+#include "tool_common.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -60,10 +60,7 @@ int main(int argc, char *argv[])
     if (frog_volume_geometry(argv[1], dimensions, spacing, origin)) die(std::string("cannot read the grid of ") + argv[1]);
     if (resize > 0) {
         cout << "Resizing image with spacing : " << resize << endl;
-        for (int k = 0; k < 3; k++) {
-            dimensions[k] = (uint32_t)std::max(1.0, std::floor(dimensions[k] * spacing[k] / resize + 0.5));
-            spacing[k] = resize;
-        }
+        resize_isotropic(dimensions, spacing, resize);
     }
     const size_t n = (size_t)dimensions[0] * dimensions[1] * dimensions[2];
 

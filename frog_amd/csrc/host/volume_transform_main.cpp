@@ -7,8 +7,7 @@
 // vtkGeneralTransform is in VTK's default PreMultiply mode: of several -t/-ti the last one acts first.
 // Volumes: NIfTI-1 and MetaImage (frog_host.h); the reference reads more formats through
 // vtkRobustImageReader (absent submodule).  New: -dev <n> selects the HIP device.
-#include "frog_chain.h"
-#include "frog_host.h"
+#include "tool_common.h"
 
 #include <chrono>
 #include <cstdlib>
@@ -17,8 +16,6 @@
 #include <string>
 #include <thread>
 #include <vector>
-
-extern "C" const char *frog_last_error(void);
 
 int main(int argc, char *argv[])
 {
@@ -29,26 +26,18 @@ int main(int argc, char *argv[])
     int reverseX = 0, device = 0;
     char *outputFile = 0;
     int interpolation = 1;              // linear
-    bool backGroundSet = false;
-    float backGroundLevel = 0;
-    std::vector<frog_transform_file *> files;
-    std::vector<frog_chain_link> links;
+    BackgroundLevel background;
+    ChainArguments chainArguments;
+    std::string error;
     auto die = [](const std::string &what) { std::cout << "Error : " << what << std::endl; exit(1); };
 
     int argumentsIndex = 3;
     while (argumentsIndex < argc) {
         char *key = argv[argumentsIndex];
         char *value = argumentsIndex + 1 < argc ? argv[argumentsIndex + 1] : (char *)"";
-        if (strcmp(key, "-b") == 0) { backGroundLevel = atof(value); backGroundSet = true; }
-        if (strcmp(key, "-t") == 0 || strcmp(key, "-ti") == 0) {
-            int status = 0;
-            frog_transform_file *f = frog_transform_read(value, &status);
-            if (!f) die(std::string("cannot read transform ") + value);
-            files.push_back(f);
-            const uint32_t n = frog_transform_num_links(f);
-            std::vector<frog_chain_link> group(frog_transform_links(f), frog_transform_links(f) + n);
-            if (strcmp(key, "-t") == 0 && frog_chain_invert_links(frog_transform_links(f), n, group.data())) die(frog_last_error());
-            links.insert(links.begin(), group.begin(), group.end());
+        if (strcmp(key, "-b") == 0) background.parse(value);
+        if (strcmp(key, "-t") == 0 || strcmp(key, "-ti") == 0) {            // the reslice maps output to source: -t is the inverted one
+            if (!chainArguments.add(value, strcmp(key, "-t") == 0, error)) die(error);
         }
         if (strcmp(key, "-o") == 0) outputFile = value;
         if (strcmp(key, "-i") == 0) interpolation = atoi(value);
@@ -97,7 +86,7 @@ int main(int argc, char *argv[])
     std::cout << "center :" << center[0] << " " << center[1] << " " << center[2] << std::endl;
 
     frog_chain *chain = nullptr;
-    if (frog_chain_create(links.data(), (uint32_t)links.size(), device, &chain)) die(frog_last_error());
+    if (frog_chain_create(chainArguments.links.data(), (uint32_t)chainArguments.links.size(), device, &chain)) die(frog_last_error());
     if (frog_chain_apply(chain, center, transformedCenter, 1)) die(frog_last_error());
     std::cout << "transformed center :" << transformedCenter[0] << " " << transformedCenter[1] << " " << transformedCenter[2] << std::endl;
 
@@ -110,7 +99,7 @@ int main(int argc, char *argv[])
     std::vector<unsigned char> data(nOut * frog_volume_voxel_bytes(out.dtype));
     out.data = data.data();
     auto t0 = clk::now();
-    if (frog_chain_reslice(chain, &src, &out, interpolation, backGroundSet ? (double)backGroundLevel : valueRange[0])) die(frog_last_error());
+    if (frog_chain_reslice(chain, &src, &out, interpolation, background.of(valueRange[0]))) die(frog_last_error());
     std::cout << "Transform computed in " << std::chrono::duration<double>(clk::now() - t0).count() << "s" << std::endl;
 
     if (reverseX) {                                 // vtkImageFlip along x (:190-195): voxels mirrored, geometry kept
@@ -132,7 +121,6 @@ int main(int argc, char *argv[])
     std::cout << "File written in " << std::chrono::duration<double>(clk::now() - t0).count() << "s" << std::endl;
 
     frog_chain_destroy(chain);
-    for (auto *f : files) frog_transform_free(f);
     for (auto *v : volumes) frog_volume_free(v);
     return 0;
 }

@@ -29,12 +29,7 @@ def read_volume(path):
 def write_volume(path, voxels, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0)):
     """voxels[z, y, x] to .mhd (+ .zraw beside it), .nii or .nii.gz."""
     a = np.ascontiguousarray(voxels)
-    if a.ndim != 3 or a.dtype.name not in _abi.FROG_V_DTYPES:
-        raise ValueError("3-D scalar volume of a supported type expected")
-    v = _abi.FrogVolume()
-    v.dims[:] = a.shape[::-1]; v.origin[:] = origin; v.spacing[:] = spacing
-    v.dtype = _abi.FROG_V_DTYPES.index(a.dtype.name)
-    v.data = a.ctypes.data
+    v = _abi.volume_view(a, origin, spacing)
     rc = _abi.host_lib().frog_volume_write(str(path).encode(), C.byref(v))
     if rc:
         raise OSError(f"cannot write volume {path} (status {rc})")
@@ -55,16 +50,6 @@ def _as_volume(item):
     return np.ascontiguousarray(a), tuple(float(v) for v in o), tuple(float(v) for v in s)
 
 
-def _view(a, origin, spacing):
-    if a.ndim != 3 or a.dtype.name not in _abi.FROG_V_DTYPES:
-        raise ValueError("3-D scalar volume of a supported type expected")
-    v = _abi.FrogVolume()
-    v.dims[:] = a.shape[::-1]; v.origin[:] = origin; v.spacing[:] = spacing
-    v.dtype = _abi.FROG_V_DTYPES.index(a.dtype.name)
-    v.data = a.ctypes.data
-    return v
-
-
 class Average:
     """frog_average (include/frog_chain.h): n_images volumes added one by one on `grid` = (dims(x, y, z), origin, spacing),
     then the f32 mean and stdev of AverageVolumes.cxx."""
@@ -73,9 +58,7 @@ class Average:
         self._lib = _abi.hip_lib()
         dims, origin, spacing = grid
         self.dims = tuple(int(d) for d in dims)
-        self._grid = _abi.FrogVolume()
-        self._grid.dims[:] = self.dims; self._grid.origin[:] = origin; self._grid.spacing[:] = spacing
-        self._grid.dtype = _abi.FROG_V_DTYPES.index("float32")
+        self._grid = _abi.volume_view(None, origin, spacing, self.dims)
         self._h = C.c_void_p()
         _abi.check(self._lib.frog_average_create(C.byref(self._grid), int(n_images), int(device), C.byref(self._h)), "frog_average_create")
 
@@ -95,11 +78,11 @@ class Average:
         (frog_amd.chain.Chain, grid space -> volume space) it is resliced first as Chain.reslice does.  resliced=True
         returns that volume (source dtype, shape dims[::-1])."""
         a, o, s = _as_volume(volume)
-        src = _view(a, o, s)
+        src = _abi.volume_view(a, o, s)
         out, ov = None, None
         if resliced:
             out = np.empty(self.dims[::-1], a.dtype)
-            ov = _view(out, tuple(self._grid.origin), tuple(self._grid.spacing))
+            ov = _abi.volume_view(out, tuple(self._grid.origin), tuple(self._grid.spacing))
         _abi.check(self._lib.frog_average_add(self._h, chain._h if chain is not None else None, C.byref(src), int(interpolation),
                                               float(background), C.byref(ov) if ov is not None else None), "frog_average_add")
         return out
