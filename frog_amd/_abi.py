@@ -276,6 +276,13 @@ HIP_SYMBOLS = {
     "frog_average_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_int, C.c_double, C.POINTER(FrogVolume)]),
     "frog_average_finish": (C.c_int, [C.c_void_p, c_float_p, c_float_p]),
     "frog_average_destroy": (None, [C.c_void_p]),
+    "frog_labels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "frog_labels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
+    "frog_labels_finish": (C.c_int, [C.c_void_p, c_u32_p]),
+    "frog_labels_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "frog_labels_fused": (C.c_int, [C.c_void_p, C.POINTER(FrogVolume), c_float_p]),
+    "frog_labels_probability": (C.c_int, [C.c_void_p, C.c_int64, c_float_p]),
+    "frog_labels_destroy": (None, [C.c_void_p]),
     "frog_match_options_default": (None, [C.POINTER(FrogMatchOptions)]),
     "frog_matcher_create": (C.c_int, [C.POINTER(FrogKeypoints), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_matcher_destroy": (None, [C.c_void_p]),

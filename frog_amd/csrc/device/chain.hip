@@ -433,6 +433,169 @@ __global__ __launch_bounds__(256) void chain_sample_kernel(size_t first, size_t 
     }
 }
 
+// ---- majority-vote fusion of a group's label maps (frog_labels; no counterpart in the reference) --------------------------
+// Label values are sparse and unknown in advance (RadLex ids: 58, 1247, 40358, ...), so the distinct values are found on the
+// device: an open-addressing map (linear probing, load <= 1/2) from the value to a dense plane index, kept across adds.  The
+// dense indices depend on which thread inserts first; nothing that leaves the library depends on them (the table is sorted
+// by value, ties go to the smaller value).  Per label one plane of 16-bit vote counts, x fastest like the grid.
+constexpr long long LABEL_EMPTY = std::numeric_limits<long long>::min();     // no integer voxel type holds it
+constexpr uint32_t LABEL_NONE = 0xFFFFFFFFu;
+constexpr int LABEL_TABLE_ITEMS = 32;           // voxels per thread of labels_table_kernel
+constexpr size_t LABEL_SUM_STRIDE = 32;        // u64 words between the sums of two labels
+
+struct LabelMap {
+    long long *keys;            // slot -> value, LABEL_EMPTY where free
+    uint32_t *index;            // slot -> dense index
+    long long *values;          // dense index -> value
+    uint32_t *state;            // [0] dense indices handed out, [1] set when a value found no index or no slot
+    uint32_t mask;              // slots - 1 (a power of two)
+    int shift;                  // 64 - log2(slots)
+    uint32_t max_labels;
+};
+
+// Fibonacci hashing: the high bits of the product, so that runs of k * 8192 or k * 65536 do not share a slot
+__host__ __device__ __forceinline__ uint32_t label_slot(long long v, int shift)
+{
+    return (uint32_t)(((unsigned long long)v * 0x9E3779B97F4A7C15ull) >> shift);
+}
+
+// Makes `v` a key of the map.  Neighbouring voxels nearly always carry the same, already known label: a plain (L1) read of
+// the slot settles those.  A slot that reads otherwise is read again at the L2 (a CU's L1 may still hold the line from
+// before another CU's insert), and only a slot that is free there gets the compare-and-swap; the thread that wins it draws
+// the dense index.  Once the state's flag is up the call has failed as a whole and the threads stop probing.
+__device__ __forceinline__ void label_insert(const LabelMap &m, long long v)
+{
+    uint32_t slot = label_slot(v, m.shift);
+    for (uint32_t probe = 0; probe <= m.mask; probe++, slot = (slot + 1) & m.mask) {
+        if (m.keys[slot] == v) return;
+        long long k = __hip_atomic_load(&m.keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == LABEL_EMPTY)
+            k = (long long)atomicCAS((unsigned long long *)&m.keys[slot], (unsigned long long)LABEL_EMPTY, (unsigned long long)v);
+        else if (k != v && __hip_atomic_load(&m.state[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        if (k == LABEL_EMPTY) {                         // this thread's insert
+            const uint32_t idx = atomicAdd(&m.state[0], 1u);
+            if (idx < m.max_labels) { m.index[slot] = idx; m.values[idx] = v; }
+            else atomicExch(&m.state[1], 1u);
+            return;
+        }
+        if (k == v) return;
+    }
+    atomicExch(&m.state[1], 1u);                        // every slot taken by other values
+}
+
+// the dense index of a key (between kernels the map is at rest: plain reads); LABEL_NONE if `v` is no key
+__device__ __forceinline__ uint32_t label_find(const LabelMap &m, long long v)
+{
+    uint32_t slot = label_slot(v, m.shift);
+    for (uint32_t probe = 0; probe <= m.mask; probe++, slot = (slot + 1) & m.mask) {
+        const long long k = m.keys[slot];
+        if (k == v) return m.index[slot];
+        if (k == LABEL_EMPTY) break;
+    }
+    return LABEL_NONE;
+}
+
+// phase 1 of an add: the voxel's label (through the chain: reslice_voxel, the code of reslice_kernel, into `stage`; else the
+// source's own voxel) becomes a key of the map
+template <class S, bool CHAIN>
+__global__ __launch_bounds__(256) void labels_collect_kernel(size_t base, const DevLink *links, int n_links, const S *__restrict__ src,
+                                                             const ResliceGrid g, size_t total, S *__restrict__ stage, const LabelMap m)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    S label;
+    if (CHAIN) {
+        label = reslice_voxel<S>(links, n_links, src, g, idx);
+        stage[idx] = label;
+    } else {
+        label = src[idx];
+    }
+    label_insert(m, (long long)label);
+}
+
+// phase 2: the image's vote.  The thread owns the voxel in every plane, as in accumulate: no atomic.
+template <class S>
+__global__ __launch_bounds__(256) void labels_vote_kernel(size_t base, const S *__restrict__ labels, size_t total, const LabelMap m,
+                                                          uint16_t *const *__restrict__ planes, uint32_t n_planes)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t l = label_find(m, (long long)labels[idx]);
+    if (l < n_planes) planes[l][idx] += 1;
+}
+
+// Per label sum of c and of c (c - 1) / 2 over the voxels, c the label's count: a block takes LABEL_TABLE_ITEMS * 256
+// voxels of one plane (the work-items of a label are padded to whole blocks), two voxels per 4-byte load, reduces across the
+// wave and through LDS and adds once per sum.  The sums of a label have a 256-byte row of their own (LABEL_SUM_STRIDE), so
+// that the blocks' atomics spread over the memory channels.  Integer sums: the order of the blocks does not matter.
+__global__ __launch_bounds__(256) void labels_table_kernel(size_t base, const uint16_t *const *__restrict__ planes, uint32_t n_planes,
+                                                           size_t total, size_t blocks_per_plane, unsigned long long *__restrict__ sums)
+{
+    __shared__ unsigned long long s_c[4], s_p[4];
+    const size_t block = base / 256 + blockIdx.x;
+    const size_t plane = block / blocks_per_plane, tile = block % blocks_per_plane;
+    unsigned long long sc = 0, sp = 0;
+    if (plane < n_planes) {
+        const uint16_t *__restrict__ p = planes[plane];                 // hipMalloc's alignment: an even voxel is 4-byte aligned
+        const size_t first = tile * LABEL_TABLE_ITEMS * 256 + 2 * threadIdx.x;
+        uint32_t two[LABEL_TABLE_ITEMS / 2];
+        if (first - 2 * threadIdx.x + LABEL_TABLE_ITEMS * 256 <= total) {           // a whole tile: every load issued before the first use
+#pragma unroll
+            for (int j = 0; j < LABEL_TABLE_ITEMS / 2; j++) __builtin_memcpy(&two[j], __builtin_assume_aligned(p + first + j * 512, 4), 4);
+        } else {
+            for (int j = 0; j < LABEL_TABLE_ITEMS / 2; j++) {
+                const size_t v = first + j * 512;
+                two[j] = 0;
+                if (v + 1 < total) __builtin_memcpy(&two[j], __builtin_assume_aligned(p + v, 4), 4);
+                else if (v < total) two[j] = p[v];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < LABEL_TABLE_ITEMS / 2; j++) {
+            const unsigned long long c0 = two[j] & 0xFFFFu, c1 = two[j] >> 16;
+            sc += c0 + c1;
+            sp += (c0 * c0 - c0 + c1 * c1 - c1) / 2;                    // c (c - 1) is even: the sum halves exactly
+        }
+    }
+    for (int h = 32; h > 0; h >>= 1) { sc += __shfl_down(sc, h); sp += __shfl_down(sp, h); }
+    if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6] = sc; s_p[threadIdx.x >> 6] = sp; }
+    __syncthreads();
+    if (threadIdx.x == 0 && plane < n_planes) {
+        sc = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+        sp = s_p[0] + s_p[1] + s_p[2] + s_p[3];
+        if (sc) atomicAdd(&sums[LABEL_SUM_STRIDE * plane], sc);
+        if (sp) atomicAdd(&sums[LABEL_SUM_STRIDE * plane + 1], sp);
+    }
+}
+
+// The winner of a voxel: `planes` and `values` in ascending order of the values, a later label must have strictly more
+// votes, so a tie stays with the smallest value.  The loads of one plane are consecutive across the wave.
+// agreement = (float)c / (float)n: one correctly rounded f32 division (see accumulate).
+template <class T>
+__global__ __launch_bounds__(256) void labels_fused_kernel(size_t base, const uint16_t *const *__restrict__ planes,
+                                                           const long long *__restrict__ values, uint32_t n_labels, size_t total,
+                                                           float n, T *__restrict__ label, float *__restrict__ agreement)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    uint32_t best = planes[0][idx], winner = 0;
+    for (uint32_t l = 1; l < n_labels; l++) {
+        const uint32_t c = planes[l][idx];
+        if (c > best) { best = c; winner = l; }
+    }
+    if (label) label[idx] = (T)values[winner];
+    if (agreement) agreement[idx] = (float)best / n;
+}
+
+__global__ __launch_bounds__(256) void labels_probability_kernel(size_t base, const uint16_t *__restrict__ plane, size_t total, float n,
+                                                                 float *__restrict__ p)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    p[idx] = (float)plane[idx] / n;
+}
+
 } // namespace
 
 struct frog_chain {
@@ -451,6 +614,28 @@ struct frog_average {
     size_t total = 0;
     frog::DevBuf<float> d_avg, d_sq;
     frog::DevBuf<unsigned char> d_src, d_out;       // staging of the current source / resliced volume, grown on demand
+};
+
+// vote counts of a group's label maps on one grid
+struct frog_labels {
+    int device = 0;
+    frog_volume grid;
+    uint32_t n_images = 0, added = 0, max_labels = 0;
+    bool finished = false;
+    size_t total = 0;
+    LabelMap map{};                                 // device pointers into the five buffers below
+    frog::DevBuf<long long> d_keys, d_values;
+    frog::DevBuf<uint32_t> d_index, d_state;
+    std::vector<long long> known;                   // dense index -> value: the labels that have a plane
+    std::deque<frog::DevBuf<uint16_t>> planes;      // one per known label; growth never copies counts
+    frog::DevBuf<uint16_t *> d_planes;              // dense index -> plane
+    frog::DevBuf<unsigned char> d_src, d_stage;     // the current source / its resliced labels, grown on demand
+    // after finish: the table in ascending order of the values (labels without a vote dropped)
+    std::vector<long long> values;
+    std::vector<uint32_t> dense;                    // table position -> dense index
+    std::vector<uint64_t> voxels, pairs;
+    frog::DevBuf<uint16_t *> d_sorted_planes;
+    frog::DevBuf<long long> d_sorted_values;
 };
 
 namespace {
@@ -624,6 +809,109 @@ int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, in
     }
     if (e == hipSuccess) e = hipStreamSynchronize(0);
     if (e != hipSuccess) return hip_fail("frog_average_add", e);
+    return FROG_OK;
+}
+
+// The device map rebuilt from the known labels alone (at creation: empty): how a refused volume's inserts are taken back.
+hipError_t labels_reset_map(frog_labels *a)
+{
+    const size_t slots = (size_t)a->map.mask + 1;
+    std::vector<long long> keys(slots, LABEL_EMPTY);
+    std::vector<uint32_t> index(slots, 0);
+    for (size_t i = 0; i < a->known.size(); i++) {
+        uint32_t slot = label_slot(a->known[i], a->map.shift);
+        while (keys[slot] != LABEL_EMPTY) slot = (slot + 1) & a->map.mask;            // load <= 1/2: a free slot exists
+        keys[slot] = a->known[i];
+        index[slot] = (uint32_t)i;
+    }
+    const uint32_t state[2] = { (uint32_t)a->known.size(), 0 };
+    hipError_t e = hipMemcpy(a->d_keys.p, keys.data(), slots * sizeof(long long), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(a->d_index.p, index.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(a->d_state.p, state, sizeof state, hipMemcpyHostToDevice);
+    return e;
+}
+
+template <class S>
+int labels_add_typed(frog_labels *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
+{
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    const size_t n_known = a->known.size();
+    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
+    if (c) KCHECK(a->d_stage.alloc(a->total * sizeof(S)));
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_stage = (S *)a->d_stage.p;
+    const S *d_labels = c ? d_stage : d_src;
+    uint32_t state[2] = { 0, 0 };
+    hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail("frog_labels_add", e);
+    const ResliceGrid g = reslice_grid(src, &a->grid, 0, background);
+    e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            labels_collect_kernel<S, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->total, d_stage, a->map);
+        else
+            labels_collect_kernel<S, false><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, a->total, nullptr, a->map);
+    });
+    if (e == hipSuccess) e = hipMemcpy(state, a->d_state.p, sizeof state, hipMemcpyDeviceToHost);
+    // from here on the map may hold values without a plane: every failure takes them back, so the volume leaves no vote
+    auto refuse = [&](int rc) { (void)labels_reset_map(a); return rc; };
+    if (e != hipSuccess) return refuse(hip_fail("frog_labels_add", e));
+    if (state[1] || state[0] > a->max_labels)
+        return refuse(fail(FROG_E_INVALID, "frog_labels_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
+    const size_t n_now = state[0];
+    if (n_now > n_known) {
+        std::vector<long long> fresh(n_now - n_known);
+        std::vector<uint16_t *> pointers;
+        e = hipMemcpy(fresh.data(), a->d_values.p + n_known, fresh.size() * sizeof(long long), hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < fresh.size() && e == hipSuccess; i++) {
+            a->planes.emplace_back();
+            e = a->planes.back().alloc(a->total);
+            if (e == hipSuccess) e = hipMemset(a->planes.back().p, 0, a->total * sizeof(uint16_t));
+            pointers.push_back(a->planes.back().p);
+        }
+        if (e == hipSuccess) e = hipMemcpy(a->d_planes.p + n_known, pointers.data(), pointers.size() * sizeof(uint16_t *), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            while (a->planes.size() > n_known) a->planes.pop_back();
+            return refuse(hip_fail("frog_labels_add", e));
+        }
+        a->known.insert(a->known.end(), fresh.begin(), fresh.end());
+    }
+    e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        labels_vote_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_labels, a->total, a->map, a->d_planes.p, (uint32_t)n_now);
+    });
+    if (e == hipSuccess && resliced) {
+        if (c) e = hipMemcpy(resliced->data, d_stage, a->total * sizeof(S), hipMemcpyDeviceToHost);
+        else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return hip_fail("frog_labels_add", e);
+    return FROG_OK;
+}
+
+// every value of the table is a T
+template <class T>
+bool labels_fit(const frog_labels *a)
+{
+    for (const long long v : a->values)
+        if (v < (long long)std::numeric_limits<T>::lowest() || v > (long long)std::numeric_limits<T>::max()) return false;
+    return true;
+}
+
+template <class T>
+int labels_fused_typed(frog_labels *a, frog_volume *label, float *agreement)
+{
+    if (label && !labels_fit<T>(a)) return fail(FROG_E_INVALID, "frog_labels_fused: a label value does not fit the requested type");
+    frog::DevBuf<T> d_label;
+    frog::DevBuf<float> d_agreement;
+    if (label) KCHECK(d_label.alloc(a->total));
+    if (agreement) KCHECK(d_agreement.alloc(a->total));
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        labels_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
+                                                         (float)a->n_images, d_label.p, d_agreement.p);
+    });
+    if (e == hipSuccess && label) e = hipMemcpy(label->data, d_label.p, a->total * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && agreement) e = hipMemcpy(agreement, d_agreement.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_labels_fused", e);
     return FROG_OK;
 }
 
@@ -855,6 +1143,157 @@ int frog_average_finish(frog_average *a, float *mean, float *stdev)
 }
 
 void frog_average_destroy(frog_average *a)
+{
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    delete a;
+}
+
+int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_labels **out)
+{
+    if (!grid || !out) return fail(FROG_E_INVALID, "bad arguments to frog_labels_create");
+    const size_t total = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
+    if (!total) return fail(FROG_E_INVALID, "empty grid");
+    if (total > ((size_t)1 << 31)) return fail(FROG_E_INVALID, "grid above 2^31 voxels");
+    if (!n_images || n_images > 65535) return fail(FROG_E_INVALID, "frog_labels_create: 1 to 65535 images (16-bit vote counts)");
+    if (max_labels > 65536) return fail(FROG_E_INVALID, "frog_labels_create: max_labels above 65536");
+    if (int rc = select_device(device)) return rc;
+    std::unique_ptr<frog_labels> a(new (std::nothrow) frog_labels);
+    if (!a) return fail(FROG_E_NOMEM, "out of host memory");
+    a->device = device;
+    a->grid = *grid;
+    a->grid.data = nullptr;
+    a->n_images = n_images;
+    a->max_labels = max_labels ? max_labels : 1024;
+    a->total = total;
+    int bits = 4;                                       // at least 16 slots, at least two per label
+    while (((size_t)1 << bits) < 2 * (size_t)a->max_labels) bits++;
+    const size_t slots = (size_t)1 << bits;
+    KCHECK(a->d_keys.alloc(slots));
+    KCHECK(a->d_index.alloc(slots));
+    KCHECK(a->d_values.alloc(a->max_labels));
+    KCHECK(a->d_state.alloc(2));
+    KCHECK(a->d_planes.alloc(a->max_labels));
+    a->map = LabelMap{ a->d_keys.p, a->d_index.p, a->d_values.p, a->d_state.p, (uint32_t)(slots - 1), 64 - bits, a->max_labels };
+    KCHECK(labels_reset_map(a.get()));
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_labels_add(frog_labels *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
+{
+    if (!a || !src || !src->data) return fail(FROG_E_INVALID, "bad arguments to frog_labels_add");
+    if (src->dtype < FROG_V_U8 || src->dtype > FROG_V_I32) return fail(FROG_E_INVALID, "frog_labels_add: a label volume has an integer type");
+    if (!std::isfinite(background)) return fail(FROG_E_INVALID, "frog_labels_add: background is not finite");
+    if (a->finished || a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_labels_add: more volumes than n_images");
+    if (c && c->device != a->device) return fail(FROG_E_INVALID, "frog_labels_add: chain and accumulator on different devices");
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    if (!n_src) return fail(FROG_E_INVALID, "empty volume");
+    for (int k = 0; k < 3; k++) {
+        if (c && (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad source geometry");
+        if (!c && src->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_labels_add: volume dimensions differ from the grid's");
+        if (resliced && resliced->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_labels_add: resliced volume is not grid-sized");
+    }
+    if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, "frog_labels_add: resliced volume must have the source's type");
+    KCHECK(hipSetDevice(a->device));
+    int rc = FROG_OK;
+    switch (src->dtype) {
+    case FROG_V_U8: rc = labels_add_typed<uint8_t>(a, c, src, background, resliced); break;
+    case FROG_V_I8: rc = labels_add_typed<int8_t>(a, c, src, background, resliced); break;
+    case FROG_V_U16: rc = labels_add_typed<uint16_t>(a, c, src, background, resliced); break;
+    case FROG_V_I16: rc = labels_add_typed<int16_t>(a, c, src, background, resliced); break;
+    case FROG_V_U32: rc = labels_add_typed<uint32_t>(a, c, src, background, resliced); break;
+    default: rc = labels_add_typed<int32_t>(a, c, src, background, resliced); break;
+    }
+    if (rc == FROG_OK) a->added++;
+    return rc;
+}
+
+int frog_labels_finish(frog_labels *a, uint32_t *n_labels)
+{
+    if (!a || !n_labels) return fail(FROG_E_INVALID, "bad arguments to frog_labels_finish");
+    if (a->added != a->n_images) return fail(FROG_E_INVALID, "frog_labels_finish: fewer volumes added than n_images");
+    if (a->finished) { *n_labels = (uint32_t)a->values.size(); return FROG_OK; }
+    KCHECK(hipSetDevice(a->device));
+    const size_t n_planes = a->known.size();
+    std::vector<unsigned long long> sums(LABEL_SUM_STRIDE * n_planes, 0);
+    frog::DevBuf<unsigned long long> d_sums;
+    KCHECK(d_sums.alloc(sums.size()));
+    KCHECK(hipMemset(d_sums.p, 0, sums.size() * sizeof(unsigned long long)));
+    const size_t tile = (size_t)LABEL_TABLE_ITEMS * LAUNCH_BLOCK, blocks_per_plane = (a->total + tile - 1) / tile;
+    hipError_t e = chunked_launch(n_planes * blocks_per_plane * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
+        labels_table_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_planes.p, (uint32_t)n_planes, a->total, blocks_per_plane, d_sums.p);
+    });
+    if (e == hipSuccess) e = hipMemcpy(sums.data(), d_sums.p, sums.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_labels_finish", e);
+    std::vector<uint32_t> order;
+    for (size_t i = 0; i < n_planes; i++) if (sums[LABEL_SUM_STRIDE * i]) order.push_back((uint32_t)i);
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return a->known[x] < a->known[y]; });
+    std::vector<uint16_t *> sorted_planes;
+    a->values.clear(); a->voxels.clear(); a->pairs.clear();
+    for (const uint32_t i : order) {
+        a->values.push_back(a->known[i]);
+        a->voxels.push_back(sums[LABEL_SUM_STRIDE * i]);
+        a->pairs.push_back(sums[LABEL_SUM_STRIDE * i + 1]);
+        sorted_planes.push_back(a->planes[i].p);
+    }
+    a->dense = order;
+    KCHECK(a->d_sorted_planes.alloc(order.size()));
+    KCHECK(a->d_sorted_values.alloc(order.size()));
+    KCHECK(hipMemcpy(a->d_sorted_planes.p, sorted_planes.data(), order.size() * sizeof(uint16_t *), hipMemcpyHostToDevice));
+    KCHECK(hipMemcpy(a->d_sorted_values.p, a->values.data(), order.size() * sizeof(long long), hipMemcpyHostToDevice));
+    a->finished = true;
+    *n_labels = (uint32_t)order.size();
+    return FROG_OK;
+}
+
+int frog_labels_table(frog_labels *a, int64_t *values, uint64_t *voxels, uint64_t *pairs)
+{
+    if (!a || !values || !voxels || !pairs) return fail(FROG_E_INVALID, "bad arguments to frog_labels_table");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_labels_table: before frog_labels_finish");
+    for (size_t l = 0; l < a->values.size(); l++) { values[l] = a->values[l]; voxels[l] = a->voxels[l]; pairs[l] = a->pairs[l]; }
+    return FROG_OK;
+}
+
+int frog_labels_fused(frog_labels *a, frog_volume *label, float *agreement)
+{
+    if (!a || (!label && !agreement) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_labels_fused");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_labels_fused: before frog_labels_finish");
+    if (label) {
+        if (label->dtype < FROG_V_U8 || label->dtype > FROG_V_I32) return fail(FROG_E_INVALID, "frog_labels_fused: the fused map has an integer type");
+        for (int k = 0; k < 3; k++)
+            if (label->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_labels_fused: the fused map is not grid-sized");
+    }
+    KCHECK(hipSetDevice(a->device));
+    switch (label ? label->dtype : FROG_V_I32) {
+    case FROG_V_U8: return labels_fused_typed<uint8_t>(a, label, agreement);
+    case FROG_V_I8: return labels_fused_typed<int8_t>(a, label, agreement);
+    case FROG_V_U16: return labels_fused_typed<uint16_t>(a, label, agreement);
+    case FROG_V_I16: return labels_fused_typed<int16_t>(a, label, agreement);
+    case FROG_V_U32: return labels_fused_typed<uint32_t>(a, label, agreement);
+    default: return labels_fused_typed<int32_t>(a, label, agreement);
+    }
+}
+
+int frog_labels_probability(frog_labels *a, int64_t value, float *p)
+{
+    if (!a || !p) return fail(FROG_E_INVALID, "bad arguments to frog_labels_probability");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_labels_probability: before frog_labels_finish");
+    const auto it = std::lower_bound(a->values.begin(), a->values.end(), (long long)value);
+    if (it == a->values.end() || *it != (long long)value) return fail(FROG_E_INVALID, "frog_labels_probability: no such label in the table");
+    KCHECK(hipSetDevice(a->device));
+    const uint16_t *plane = a->planes[a->dense[it - a->values.begin()]].p;
+    frog::DevBuf<float> d_p;
+    KCHECK(d_p.alloc(a->total));
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        labels_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, plane, a->total, (float)a->n_images, d_p.p);
+    });
+    if (e == hipSuccess) e = hipMemcpy(p, d_p.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_labels_probability", e);
+    return FROG_OK;
+}
+
+void frog_labels_destroy(frog_labels *a)
 {
     if (!a) return;
     (void)hipSetDevice(a->device);

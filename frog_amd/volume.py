@@ -122,3 +122,128 @@ def average(volumes, chains=None, grid=None, interpolation=1, backgrounds=None, 
         return acc.finish()
     finally:
         acc.close()
+
+
+FUSED_DTYPES = ("uint8", "uint16", "int16", "int32", "uint32")
+
+
+def fused_dtype(values):
+    """The type bin/FuseLabels gives labels.nii.gz: the first of uint8, uint16, int16, int32, uint32 that holds every label
+    value; None if none does."""
+    lo, hi = (int(min(values)), int(max(values))) if len(values) else (0, 0)
+    for name in FUSED_DTYPES:
+        info = np.iinfo(name)
+        if info.min <= lo and hi <= info.max:
+            return np.dtype(name)
+    return None
+
+
+class Labels:
+    """frog_labels (include/frog_chain.h): n_images label maps added one by one on `grid` = (dims(x, y, z), origin, spacing),
+    then the majority vote, its agreement, per-label probabilities and the table of vote sums."""
+
+    def __init__(self, grid, n_images, max_labels=0, device=0):
+        self._lib = _abi.hip_lib()
+        dims, origin, spacing = grid
+        self.dims = tuple(int(d) for d in dims)
+        self.n_images = int(n_images)
+        self._grid = _abi.volume_view(None, origin, spacing, self.dims)
+        self._h = C.c_void_p()
+        self._n_labels = None
+        _abi.check(self._lib.frog_labels_create(C.byref(self._grid), self.n_images, int(max_labels), int(device), C.byref(self._h)),
+                   "frog_labels_create")
+
+    def close(self):
+        if self._h:
+            self._lib.frog_labels_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, volume, chain=None, background=0.0, resliced=False):
+        """Adds the integer label map `volume` ((voxels, origin, spacing) or an array already on the grid when chain is
+        None); with a chain (frog_amd.chain.Chain, grid space -> volume space) its labels are what Chain.reslice gives with
+        nearest-neighbour interpolation.  resliced=True returns that volume (source dtype, shape dims[::-1])."""
+        a, o, s = _as_volume(volume)
+        src = _abi.volume_view(a, o, s)
+        out, ov = None, None
+        if resliced:
+            out = np.empty(self.dims[::-1], a.dtype)
+            ov = _abi.volume_view(out, tuple(self._grid.origin), tuple(self._grid.spacing))
+        _abi.check(self._lib.frog_labels_add(self._h, chain._h if chain is not None else None, C.byref(src), float(background),
+                                             C.byref(ov) if ov is not None else None), "frog_labels_add")
+        return out
+
+    def finish(self):
+        """The number of distinct labels, after exactly n_images adds."""
+        n = C.c_uint32()
+        _abi.check(self._lib.frog_labels_finish(self._h, C.byref(n)), "frog_labels_finish")
+        self._n_labels = int(n.value)
+        return self._n_labels
+
+    def table(self):
+        """(values int64 ascending, voxels uint64, pairs uint64): per label the votes summed over the voxels and the image
+        pairs that agree on it, summed over the voxels."""
+        n = self._n_labels or 0
+        values, voxels, pairs = np.empty(n, np.int64), np.empty(n, np.uint64), np.empty(n, np.uint64)
+        _abi.check(self._lib.frog_labels_table(self._h, values.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               voxels.ctypes.data_as(C.POINTER(C.c_uint64)), pairs.ctypes.data_as(C.POINTER(C.c_uint64))),
+                   "frog_labels_table")
+        return values, voxels, pairs
+
+    def fused(self, dtype=None):
+        """(labels, agreement): the majority label per voxel (ties: the smallest value) as `dtype`, default the first of
+        uint8, uint16, int16, int32, uint32 that holds every label; float32 share of the images that voted for it."""
+        if dtype is None:
+            dtype = fused_dtype(self.table()[0])
+            if dtype is None:
+                raise ValueError("no integer type of at most 32 bits holds every label value")
+        labels = np.empty(self.dims[::-1], np.dtype(dtype))
+        agreement = np.empty(self.dims[::-1], np.float32)
+        lv = _abi.volume_view(labels, tuple(self._grid.origin), tuple(self._grid.spacing))
+        _abi.check(self._lib.frog_labels_fused(self._h, C.byref(lv), agreement.ctypes.data_as(_abi.c_float_p)), "frog_labels_fused")
+        return labels, agreement
+
+    def probability(self, value):
+        """float32 share of the images that carry label `value`, per voxel."""
+        p = np.empty(self.dims[::-1], np.float32)
+        _abi.check(self._lib.frog_labels_probability(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), "frog_labels_probability")
+        return p
+
+
+def group_dice(voxels, pairs, n_images):
+    """The pooled pairwise Dice overlap per label, 2 pairs / ((n_images - 1) voxels) in float64 (include/frog_chain.h); NaN
+    for a single image."""
+    voxels, pairs = np.asarray(voxels, np.float64), np.asarray(pairs, np.float64)
+    if n_images < 2:
+        return np.full(voxels.shape, np.nan)
+    return 2.0 * pairs / ((n_images - 1.0) * voxels)
+
+
+def fuse_labels(volumes, chains=None, grid=None, background=0.0, max_labels=0, device=0):
+    """Majority-vote fusion of a group's label maps on the device (bin/FuseLabels).  `volumes`, `chains` and `grid` as in
+    average(); every volume has an integer type.  Returns (labels, agreement, values, dice): the fused map, the float32
+    share of the images that agree with it, the distinct label values in ascending order and per label the pooled pairwise
+    Dice overlap across the group (float64)."""
+    vols = [_as_volume(v) for v in volumes]
+    if not vols:
+        raise ValueError("no volumes")
+    if chains is not None and len(chains) != len(vols):
+        raise ValueError("one chain per volume expected")
+    if grid is None:
+        a, o, s = vols[0]
+        grid = (a.shape[::-1], o, s)
+    acc = Labels(grid, len(vols), max_labels, device)
+    try:
+        for k, v in enumerate(vols):
+            acc.add(v, None if chains is None else chains[k], background)
+        acc.finish()
+        values, voxels, pairs = acc.table()
+        labels, agreement = acc.fused()
+        return labels, agreement, values, group_dice(voxels, pairs, len(vols))
+    finally:
+        acc.close()

@@ -151,6 +151,44 @@ int  frog_average_add(frog_average *a, frog_chain *chain, const frog_volume *sou
 int  frog_average_finish(frog_average *a, float *mean, float *stdev);
 void frog_average_destroy(frog_average *a);
 
+/* ---- majority-vote fusion of a registered group's label maps (an extension: the reference stops at N x VolumeTransform -i 0) --
+ * An accumulator of n_images label volumes on `grid` (dims, origin, spacing; its dtype and data are ignored).  Per voxel v
+ * and label value l it counts the images that carry l at v: count[l][v], 16-bit, one device thread per voxel, no atomics on
+ * the counts.  Everything that leaves it is integer arithmetic on those counts (or one f32 division): exact and independent
+ * of scheduling.  The distinct values are found on the device; max_labels (0: 1024) bounds their number, and the device
+ * holds one plane of 2 bytes x the grid's voxels per distinct value.
+ * FROG_E_INVALID, before the device is touched: a NULL argument, an empty grid or one above 2^31 voxels, n_images == 0 or
+ * > 65535 (the counters' width), max_labels > 65536. */
+typedef struct frog_labels frog_labels;
+int  frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_labels **out);
+/* `source` has one of the six integer types (FROG_E_INVALID for FROG_V_F32 / FROG_V_F64, and for a background that is not
+ * finite).  chain == NULL: it is already on the grid (its dims must equal the grid's).  chain != NULL: every grid voxel gets
+ * the voxel frog_chain_reslice(chain, source, out, 0, background) stores there (nearest neighbour; the same device code),
+ * and `resliced` (may be NULL; dims the grid's, dtype the source's) receives that volume.  The background is a label like
+ * any other.  The image's vote at v goes to the label it has there: count[label][v] += 1.  More than n_images calls, a chain
+ * on another device or bad geometry -> FROG_E_INVALID.  A volume that would bring the number of distinct labels above
+ * max_labels is refused with FROG_E_INVALID (the message names the limit), a refused device allocation with FROG_E_NOMEM:
+ * either way the volume leaves no vote and no label behind, the call does not count as one of the n_images, and another
+ * volume may be added in its place. */
+int  frog_labels_add(frog_labels *a, frog_chain *chain, const frog_volume *source, double background, frog_volume *resliced);
+/* After exactly n_images adds (else FROG_E_INVALID): the number of distinct labels that received a vote.  The four getters
+ * below are valid only after it (FROG_E_INVALID before). */
+int  frog_labels_finish(frog_labels *a, uint32_t *n_labels);
+/* n_labels entries each, in ascending signed order of the values: voxels[l] = sum over v of c, pairs[l] = sum over v of
+ * c (c - 1) / 2, c = count[l][v]; exact in u64.  The pooled pairwise Dice overlap of label l across the group,
+ *     sum_{i<j} 2 |A_i n A_j| / sum_{i<j} (|A_i| + |A_j|)  =  2 pairs[l] / ((n_images - 1) voxels[l]),
+ * because sum_{i<j} |A_i n A_j| = sum_v C(c, 2) and sum_{i<j} (|A_i| + |A_j|) = (n_images - 1) sum_i |A_i|.  Callers form the
+ * quotient in f64 (undefined for n_images == 1). */
+int  frog_labels_table(frog_labels *a, int64_t *values, uint64_t *voxels, uint64_t *pairs);
+/* Per voxel the label with the most votes, a tie going to the smallest value (signed comparison), stored as label->dtype
+ * (any of the six integer types; dims the grid's); agreement[v] = (float)c_winner / (float)n_images, one correctly rounded
+ * f32 division.  Either output may be NULL, not both.  A table value that does not fit label->dtype -> FROG_E_INVALID and
+ * nothing is written. */
+int  frog_labels_fused(frog_labels *a, frog_volume *label, float *agreement);
+/* p[v] = (float)count[value][v] / (float)n_images; a value that is not in the table -> FROG_E_INVALID. */
+int  frog_labels_probability(frog_labels *a, int64_t value, float *p);
+void frog_labels_destroy(frog_labels *a);
+
 #ifdef __cplusplus
 }
 #endif
