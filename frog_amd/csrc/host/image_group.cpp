@@ -25,7 +25,7 @@
 
 #include "../../../include/frog_comm.h"
 
-#include "comm_api.h"
+#include "rank_steps.h"
 
 // libfrog_comm.so (RCCL) is loaded on demand, for -ng / -ngl and frog_run_schedule only: a process that brings its own
 // communicator (the Python drivers over torch.distributed) uses this library without ever mapping a second RCCL.
@@ -99,14 +99,12 @@ ImageGroup::ImageGroup()
 ImageGroup::~ImageGroup()
 {
     if (!comms.empty() && g_comm.destroy_all) g_comm.destroy_all((int)comms.size(), comms.data());
-    if (!ctxs.empty()) { for (frog_ctx *c : ctxs) if (c) frog_destroy(c); }
-    else if (ctx) frog_destroy(ctx);
+    for (frog_ctx *c : ctxs) if (c) frog_destroy(c);
     if (pairs && ownPairs) frog_pairs_free(pairs);
 }
 
 frog_ctx *ImageGroup::ctxOf(uint32_t image) const
 {
-    if (ctxs.empty()) return ctx;
     for (size_t r = 0; r + 1 < shardBegin.size(); r++)
         if (image >= shardBegin[r] && image < shardBegin[r + 1]) return ctxs[r];
     return ctx;
@@ -134,12 +132,9 @@ void ImageGroup::planShards()
     shardBegin.push_back(nI);
 }
 
-void ImageGroup::createShardedContexts()
+// The solver's options from the fields (ImageGroup ctor state + setupStats, :1151: the reservoirs are sized in frog_create)
+frog_options ImageGroup::solverOptions() const
 {
-    std::string err;
-    if (!g_comm.load(err)) { cout << "Error : cannot load libfrog_comm.so (" << err << ")" << endl; exit(1); }
-    if (numberOfFixedImages) { cout << "Error : -fi cannot be combined with -ng / -ngl" << endl; exit(1); }
-    planShards();
     frog_options o;
     frog_options_default(&o);
     o.linear_alpha = linearAlpha; o.use_scale = useScale; o.initial_grid_size = initialGridSize;
@@ -148,6 +143,30 @@ void ImageGroup::createShardedContexts()
     o.max_levels_hint = deformableLevels; o.stats_max_size = statsMaxSize; o.stats_max_iterations = statsMaxIterations; o.stats_epsilon = statsEpsilon;
     o.reference_order = exact;
     o.selections_in_background = 1;             // a whole run: the ahead-of-time draws beside the first iterations
+    o.n_fixed_images = numberOfFixedImages;
+    return o;
+}
+
+// Point::hardLinks, weight :237; a sharded context keeps the links of its own points
+void ImageGroup::uploadHardLinks(frog_ctx *c, const frog_model &m)
+{
+    if (hardLinks.empty()) return;
+    std::vector<uint64_t> a, b;
+    for (const auto &hl : hardLinks) {
+        a.push_back((uint64_t)m.point_offset[hl.first.image] + hl.first.point);
+        b.push_back((uint64_t)m.point_offset[hl.second.image] + hl.second.point);
+    }
+    const float constraintWeight = m.n_images * landmarksConstraintsWeight;
+    check(frog_set_hard_links(c, a.data(), b.data(), a.size(), constraintWeight * constraintWeight), "frog_set_hard_links");
+}
+
+void ImageGroup::createShardedContexts()
+{
+    std::string err;
+    if (!g_comm.load(err)) { cout << "Error : cannot load libfrog_comm.so (" << err << ")" << endl; exit(1); }
+    if (numberOfFixedImages) { cout << "Error : -fi cannot be combined with -ng / -ngl" << endl; exit(1); }
+    planShards();
+    const frog_options o = solverOptions();
     frog_model m;
     frog_pairs_model(pairs, &m);
     std::vector<int> devices(nGpus);
@@ -159,216 +178,12 @@ void ImageGroup::createShardedContexts()
     cout << "Images sharded over " << nGpus << (loopback ? " contexts on device " : " GPUs, first device ") << device << " :";
     for (int r = 0; r < nGpus; r++) cout << " [" << shardBegin[r] << "," << shardBegin[r + 1] << ")";
     cout << endl;
-    for (int r = 0; r < nGpus; r++)        // one after the other: the layout build of each context already uses all host threads
+    for (int r = 0; r < nGpus; r++) {      // one after the other: the layout build of each context already uses all host threads
         check(frog_create(&m, &o, devices[r], shardBegin[r], shardBegin[r + 1], &ctxs[r]), "frog_create");
+        uploadHardLinks(ctxs[r], m);
+    }
     ctx = ctxs[0];
-    if (!hardLinks.empty()) {
-        std::vector<uint64_t> a, b;
-        for (const auto &hl : hardLinks) {
-            a.push_back((uint64_t)m.point_offset[hl.first.image] + hl.first.point);
-            b.push_back((uint64_t)m.point_offset[hl.second.image] + hl.second.point);
-        }
-        const float constraintWeight = m.n_images * landmarksConstraintsWeight;
-        for (frog_ctx *c : ctxs)        // every context keeps the links of its own points
-            check(frog_set_hard_links(c, a.data(), b.data(), a.size(), constraintWeight * constraintWeight), "frog_set_hard_links");
-    }
     counts.assign(m.n_images, frog_counts{});
-}
-
-// run()'s loops for images sharded over several GPUs (imageGroup.cxx:31-128): one host thread per rank, all executing
-// the same control flow on their own context; the places where the reference's loops read another image's state are
-// collectives (include/frog_comm.h).  E and the oversize count are all-reduced, so every rank takes the same branch.
-// Rank 0 prints and records the measures.
-void ImageGroup::runSharded()
-{
-    using clk = std::chrono::steady_clock;
-    const int N = nGpus;
-    std::vector<uint64_t> replicaHashes(N, 0);
-    #pragma omp parallel num_threads(N)
-    {
-        const int r = omp_get_thread_num();
-        frog_ctx *c = ctxs[r];
-        frog_comm *cm = comms[r];
-        const bool root = r == 0;
-        auto ck = [&](int rc, const char *what) { if (rc) { 
-            #pragma omp critical
-            { cout << "Error : " << what << " failed on rank " << r << " (" << rc << "): " << frog_last_error() << endl; exit(1); } } };
-        // two collectives per deformable iteration, one per linear iteration (include/frog_hip.h frog_comm_mode; rank_schedule.cpp
-        // has the same flow); FROG_THREE_COLLECTIVES=1: the flow of rounds 2-4
-        const bool two = !getenv("FROG_THREE_COLLECTIVES");
-        const bool speculate = two && !getenv("FROG_NO_SPECULATION");      // the next step's phase A queued before this step's decision (frog_step_speculate)
-        bool gathered = false, phaseAQueued = false;
-        ck(frog_comm_mode(c, two ? 1 : 0), "frog_comm_mode");
-        auto transformPoints = [&](int apply) {
-            if (two) {
-                const bool done = gathered && !apply;
-                gathered = false;
-                if (!done) ck(g_comm.gather_points(cm, apply, 0, 0u), "frog_comm_gather_points");
-                return;
-            }
-            ck(frog_transform_points_local(c, apply), "frog_transform_points_local");
-            ck(g_comm.all_gather_xyz2(cm), "frog_comm_all_gather_xyz2");
-        };
-        auto updateStats = [&]() {
-            ck(frog_update_stats_local(c), "frog_update_stats_local");
-            ck(g_comm.all_reduce(cm, FROG_BUF_EM), "frog_comm_all_reduce");
-            ck(frog_stats_publish(c), "frog_stats_publish");
-        };
-        auto setup = [&](int level) {
-            double mn[3], mx[3];
-            frog_grid_info info;
-            ck(frog_bounds_local(c, mn, mx), "frog_bounds_local");
-            ck(g_comm.all_reduce_bounds(cm, mn, mx), "frog_comm_all_reduce_bounds");
-            ck(frog_deformable_setup_bounds(c, level, mn, mx, &info), "frog_deformable_setup_bounds");
-            if (root) {
-                double length[3];
-                for (int k = 0; k < 3; k++) length[k] = info.bbox[2 * k + 1] - info.bbox[2 * k];
-                cout << "Bounding box : "; print(info.bbox, 6);
-                cout << "Box length : "; print(length, 3);
-                cout << "Grid origin : "; print(info.origin, 3);
-                cout << "Grid spacing : "; print(info.spacing, 3);
-                cout << "Grid dimensions (control points): "; print(info.dims, 3);
-            }
-        };
-        auto census = [&]() {
-            ck(frog_count_inliers(c, counts.data()), "frog_count_inliers");       // every rank fills its own images' entries
-            g_comm.barrier(cm);
-            if (root) {
-                long long nPairs = 0, nInliers = 0, nOutliers = 0;
-                for (const auto &x : counts) { nPairs += x.pairs; nInliers += x.inliers; nOutliers += x.outliers; }
-                cout << "Stats:" << endl << nPairs << " half pairs" << endl << nInliers << " inliers" << endl << nOutliers << " outliers" << endl;
-                cout << "Outlier ratio (%): " << (float)100 * nOutliers / nPairs << endl;
-            }
-            g_comm.barrier(cm);
-        };
-
-        std::vector<uint32_t> sb(shardBegin);
-        ck(g_comm.bind(cm, c, sb.data()), "frog_comm_bind");
-        ck(frog_linear_init(c, linearInitializationAnchor), "frog_linear_init");       // :37
-        transformPoints(0);                                                           // :38
-
-        if (root) cout << endl << "Linear registration" << endl;
-        g_comm.barrier(cm);
-        auto t0 = clk::now();
-        for (int iteration = 0; iteration < linearIterations; iteration++) {
-            if (root && !quiet) cout << "Linear registration, iteration " << iteration + 1 << "/" << linearIterations << endl;
-            if (!(iteration % statIntervalUpdate)) updateStats();
-            ck(frog_linear_step_local(c), "frog_linear_step_local");
-            double E = 0;
-            if (two) {
-                ck(g_comm.gather_points(cm, 0, 0, 0xBu), "frog_comm_gather_points");        // the two sums ride on the gather
-                ck(frog_step_finish(c, &E), "frog_step_finish");
-                gathered = true;
-            } else {
-                ck(g_comm.all_reduce(cm, FROG_BUF_ENERGY), "frog_comm_all_reduce");
-                ck(frog_energy_read(c, &E, nullptr), "frog_energy_read");
-            }
-            transformPoints(0);
-            if (root) computeLandmarkDistances((float)E);
-        }
-        g_comm.barrier(cm);
-        if (root) { loopSeconds += std::chrono::duration<double>(clk::now() - t0).count(); loopIterations += linearIterations; }
-        transformPoints(1);                                                           // :70
-        ck(frog_synchronize(c), "frog_synchronize");
-        g_comm.barrier(cm);
-        if (root) saveDistanceHistograms("histograms_linear.csv");                    // :71 (reads every rank's samples)
-        g_comm.barrier(cm);
-
-        if (deformableLevels) {
-            if (root) cout << endl << "Deformable registration" << endl;
-            census();                                                                 // :76
-            for (int level = 0; level < deformableLevels; level++) {
-                if (root) cout << endl << "Level " << level + 1 << "/" << deformableLevels << endl;
-                setup(level);                                                         // :81
-                transformPoints(0);
-                int numberOfGrids = 1;
-                float alpha = deformableAlpha;
-                if (root) cout << "alpha = " << alpha << endl;
-                int numberOfDiffeomorphicIterations = 0;
-                g_comm.barrier(cm);
-                t0 = clk::now();
-                for (int iteration = 0; iteration < deformableIterations; iteration++) {
-                    if (root && !quiet)
-                        cout << "Level " << level + 1 << "/" << deformableLevels << ", Iteration " << iteration + 1 << "/"
-                             << deformableIterations << endl;
-                    if (!(iteration % statIntervalUpdate)) updateStats();
-                    if (!phaseAQueued) ck(frog_deformable_phase_a(c, alpha), "frog_deformable_phase_a");
-                    phaseAQueued = false;
-                    ck(g_comm.all_reduce(cm, FROG_BUF_GRIDSUM), "frog_comm_all_reduce");        // the shared common-space grid, :400-432
-                    ck(frog_deformable_phase_b(c), "frog_deformable_phase_b");
-                    double E = 0;
-                    if (two) {
-                        // the oversize count rides on the coordinate gather, the transform queued speculatively (frog_hip.h)
-                        ck(g_comm.gather_points(cm, 0, 1, 0x4u), "frog_comm_gather_points");
-                        if (speculate && iteration + 1 < deformableIterations && (iteration + 1) % statIntervalUpdate != 0) {
-                            ck(frog_step_speculate(c), "frog_step_speculate");
-                            ck(frog_deformable_phase_a(c, alpha), "frog_deformable_phase_a");
-                            phaseAQueued = true;
-                        }
-                        ck(frog_step_finish(c, &E), "frog_step_finish");
-                        gathered = (float)E >= 0;
-                        if (!gathered) phaseAQueued = false;        // rejected: rolled back
-                    } else {
-                        ck(g_comm.all_reduce(cm, FROG_BUF_ENERGY), "frog_comm_all_reduce");         // energy sums + oversize count
-                        ck(frog_deformable_phase_c(c, &E), "frog_deformable_phase_c");
-                    }
-                    const float e = (float)E;
-                    if (e < 0) {                                                  // :97-115, the same on every rank
-                        if (root) cout << endl << "Diffeomorphism is not guaranteed : Iteration canceled" << endl;
-                        if (numberOfDiffeomorphicIterations == 0) {
-                            alpha /= 2;
-                            if (root) cout << "Halving alpha. New Value : " << alpha << endl;
-                        }
-                        if (root) cout << " creating new grid" << endl;
-                        numberOfGrids++;
-                        iteration--;
-                        transformPoints(1);
-                        setup(level);
-                        transformPoints(0);
-                        numberOfDiffeomorphicIterations = 0;
-                        continue;
-                    }
-                    numberOfDiffeomorphicIterations++;
-                    transformPoints(0);
-                    if (root) computeLandmarkDistances(e);
-                }
-                g_comm.barrier(cm);
-                if (root) { loopSeconds += std::chrono::duration<double>(clk::now() - t0).count(); loopIterations += deformableIterations; }
-                census();                                                             // :123
-                if (root) {
-                    cout << "Number of grids for this level : " << numberOfGrids << endl;
-                    gridsPerLevel.push_back(numberOfGrids);
-                }
-                transformPoints(1);
-            }
-        }
-        ck(frog_synchronize(c), "frog_synchronize");
-        g_comm.barrier(cm);
-        if (std::getenv("FROG_CHECK_REPLICAS")) {
-            // every rank holds a replica of all transformed coordinates (the all-gather's product) and of the mixture table:
-            // they must be the same bits everywhere, whatever carried the collectives
-            const uint64_t nP = frog_num_points(c);
-            const uint32_t nI = frog_num_images(c);
-            std::vector<float> xyz(3 * nP), xyz2(3 * nP), em(3 * (size_t)nI);
-            ck(frog_get_points(c, xyz.data(), xyz2.data()), "frog_get_points");
-            for (uint32_t i = 0; i < nI; i++) ck(frog_get_em(c, i, &em[3 * (size_t)i]), "frog_get_em");
-            uint64_t h = 1469598103934665603ull;            // FNV-1a over the bit patterns
-            auto eat = [&](const std::vector<float> &v) {
-                for (float f : v) { uint32_t b; std::memcpy(&b, &f, 4); h = (h ^ b) * 1099511628211ull; }
-            };
-            eat(xyz2); eat(em);
-            #pragma omp critical
-            replicaHashes[r] = h;
-            g_comm.barrier(cm);
-            if (root) {
-                bool same = true;
-                for (int k = 1; k < N; k++) same = same && replicaHashes[k] == replicaHashes[0];
-                cout << "Replicas identical : " << (same ? "yes" : "NO") << " (" << N << " contexts, xyz2 of " << nP << " points + " << nI << " mixtures)" << endl;
-                if (!same) exit(1);
-            }
-            g_comm.barrier(cm);
-        }
-    }
 }
 
 void ImageGroup::check(int rc, const char *what)
@@ -404,38 +219,17 @@ void ImageGroup::usePairs(frog_pairs *p)
     ownPairs = false;
 }
 
-// ImageGroup ctor state + setupStats (:1151): the reservoirs are sized in frog_create.
 // Called from run() so that -ss/-emi/-se given after the file name take effect, as in
 // the reference where setupStats runs inside run().
 void ImageGroup::createContext()
 {
-    frog_options o;
-    frog_options_default(&o);
-    o.linear_alpha = linearAlpha;
-    o.use_scale = useScale;
-    o.initial_grid_size = initialGridSize;
-    o.bounding_box_margin = boundingBoxMargin;
-    o.inlier_threshold = inlierThreshold;
-    o.guarantee_diffeomorphism = guaranteeDiffeomorphism;
-    o.max_displacement_ratio = maxDisplacementRatio;
-    o.max_levels_hint = deformableLevels; o.stats_max_size = statsMaxSize;
-    o.reference_order = exact;
-    o.selections_in_background = 1;             // a whole run: the ahead-of-time draws beside the first iterations
-    o.stats_max_iterations = statsMaxIterations;
-    o.stats_epsilon = statsEpsilon;
-    o.n_fixed_images = numberOfFixedImages;
+    const frog_options o = solverOptions();
     frog_model m;
     frog_pairs_model(pairs, &m);
-    check(frog_create(&m, &o, device, 0, m.n_images, &ctx), "frog_create");
-    if (!hardLinks.empty()) {                                           // Point::hardLinks, weight :237
-        std::vector<uint64_t> a, b;
-        for (const auto &hl : hardLinks) {
-            a.push_back((uint64_t)m.point_offset[hl.first.image] + hl.first.point);
-            b.push_back((uint64_t)m.point_offset[hl.second.image] + hl.second.point);
-        }
-        const float constraintWeight = m.n_images * landmarksConstraintsWeight;
-        check(frog_set_hard_links(ctx, a.data(), b.data(), a.size(), constraintWeight * constraintWeight), "frog_set_hard_links");
-    }
+    ctxs.assign(1, nullptr);                    // the one rank of a plain run
+    shardBegin = { 0, m.n_images };
+    check(frog_create(&m, &o, device, 0, m.n_images, &ctxs[0]), "frog_create");
+    uploadHardLinks(ctx = ctxs[0], m);
     counts.assign(m.n_images, frog_counts{});
 }
 
@@ -484,29 +278,81 @@ void ImageGroup::run()
     // FROG_SHARDED_ALWAYS: `-ng 1` also takes the sharded host (one rank, a real RCCL communicator of one device): the only
     // way to execute that code path -- ncclCommInitAll, grouped broadcasts, all-reduces on the context's stream -- on a
     // machine with a single GPU (tests)
-    if (nGpus > 1 || (nGpus == 1 && std::getenv("FROG_SHARDED_ALWAYS"))) {
-        // images sharded over several GPUs: the loops run in runSharded(), everything after them (error maps, files)
-        // below is shared with the single-GPU path and asks the context that owns each image
-        { const auto t_ctx = clk::now(); createShardedContexts();
-          if (std::getenv("FROG_TIMING")) cout << "[timing] frog_create x " << nGpus << " : " << std::chrono::duration<double>(clk::now() - t_ctx).count() << "s" << endl; }
-        runSharded();
-        finishRun();
-        return;
+    const bool sharded = nGpus > 1 || (nGpus == 1 && std::getenv("FROG_SHARDED_ALWAYS"));
+    const bool timing = std::getenv("FROG_TIMING") != nullptr;
+    std::vector<uint64_t> replicaHashes(nGpus, 0);
+    if (!sharded && numberOfFixedImages) readAndApplyFixedImagesTransforms();       // :34
+    const auto t_ctx = clk::now();
+    if (sharded) {
+        // images sharded over several GPUs: one host thread per rank, all executing runRank() on their own context; everything
+        // after the loops (error maps, files) is shared with the single-GPU path and asks the context that owns each image
+        createShardedContexts();
+        if (timing) cout << "[timing] frog_create x " << nGpus << " : " << std::chrono::duration<double>(clk::now() - t_ctx).count() << "s" << endl;
+        #pragma omp parallel num_threads(nGpus)
+        runRank(omp_get_thread_num(), replicaHashes);
+    } else {
+        createContext();                                                // :36 setupStats
+        double part[3] = { 0, 0, 0 };
+        if (timing) cout << "[timing] frog_create : " << std::chrono::duration<double>(clk::now() - t_ctx).count() << "s" << endl;
+        if (timing && frog_create_seconds(ctx, part, nullptr) == FROG_OK)
+            cout << "[timing] frog_create, layout build : " << part[0] << "s" << endl << "[timing] frog_create, allocations + uploads : " << part[1] << "s" << endl
+                 << "[timing] frog_create, selections queued : " << part[2] << "s" << endl;
+        runRank(0, replicaHashes);  // not a parallel region of one thread: the OpenMP loops of the libraries would become nested and serial
     }
-    if (numberOfFixedImages) readAndApplyFixedImagesTransforms();       // :34
-    { const auto t_ctx = clk::now(); createContext();                   // :36 setupStats
-      if (std::getenv("FROG_TIMING")) {
-          cout << "[timing] frog_create : " << std::chrono::duration<double>(clk::now() - t_ctx).count() << "s" << endl;
-          double part[3] = { 0, 0, 0 };
-          if (frog_create_seconds(ctx, part, nullptr) == FROG_OK)
-              cout << "[timing] frog_create, layout build : " << part[0] << "s" << endl << "[timing] frog_create, allocations + uploads : " << part[1] << "s" << endl
-                   << "[timing] frog_create, selections queued : " << part[2] << "s" << endl;
-      } }
-    check(frog_linear_init(ctx, linearInitializationAnchor), "frog_linear_init");   // :37
-    check(frog_transform_points(ctx, 0), "frog_transform_points");      // :38
+    finishRun();
+}
+
+// run()'s loops (imageGroup.cxx:37-128) as one rank executes them, over the steps of rank_steps.h: alone on the whole group,
+// or in lockstep with the other ranks' threads, each on its own context -- E and the oversize count are the group's on every
+// rank, so all take the same branch.  Rank 0 prints and records the measures; where it reads the other ranks' contexts, that
+// stands between barriers (nothing without a communicator).
+void ImageGroup::runRank(int r, std::vector<uint64_t> &replicaHashes)
+{
+    using clk = std::chrono::steady_clock;
+    const bool sharded = !comms.empty(), root = r == 0;
+    frog_ctx *c = ctxs[r];
+    RankSteps s;
+    auto live = [&] {               // the steps keep the first failure and do nothing after it
+        if (!s.rc) return;
+        #pragma omp critical
+        { cout << "Error : " << s.failed << " failed" << (sharded ? " on rank " + std::to_string(r) : "") << " (" << s.rc << "): " << frog_last_error() << endl; exit(1); }
+    };
+    auto setup = [&](int level) {
+        frog_grid_info info;
+        s.setup(level, info);
+        live();
+        if (!root) return;
+        double length[3];
+        for (int k = 0; k < 3; k++) length[k] = info.bbox[2 * k + 1] - info.bbox[2 * k];
+        cout << "Bounding box : "; print(info.bbox, 6);
+        cout << "Box length : "; print(length, 3);
+        cout << "Grid origin : "; print(info.origin, 3);
+        cout << "Grid spacing : "; print(info.spacing, 3);
+        cout << "Grid dimensions (control points): "; print(info.dims, 3);
+    };
+    auto census = [&] {             // countInliers (:988-1060); every rank fills its own images' entries
+        s.ok(frog_count_inliers(c, counts.data()), "frog_count_inliers");
+        s.barrier();
+        live();
+        if (root) {
+            long long nPairs = 0, nInliers = 0, nOutliers = 0;
+            for (const auto &x : counts) { nPairs += x.pairs; nInliers += x.inliers; nOutliers += x.outliers; }
+            cout << "Stats:" << endl << nPairs << " half pairs" << endl << nInliers << " inliers" << endl << nOutliers << " outliers" << endl;
+            cout << "Outlier ratio (%): " << (float)100 * nOutliers / nPairs << endl;
+        }
+        s.barrier();
+    };
+    s.init(c, sharded ? comms[r] : nullptr, nullptr, numberOfFixedImages);
+    live();
+    if (sharded) s.ok(g_comm.bind(s.cm, c, shardBegin.data()), "frog_comm_bind");
+    s.ok(frog_linear_init(c, linearInitializationAnchor), "frog_linear_init");          // :37
+    s.transformPoints(0);                                                               // :38
+    live();
+    // -dstats / -dlinear inside the loops: the plain flavour only, a sharded run prints neither there
+    const bool showStats = printStats && !sharded, showLinear = printLinear && !sharded;
 
     auto t0 = clk::now();
-    if (useRANSAC && numberOfFixedImages) {                             // :40-49
+    if (useRANSAC && numberOfFixedImages) {                             // :40-49 (-fi: never sharded)
         frog_model m;
         frog_pairs_model(pairs, &m);
         frog_ransac_options ro;
@@ -523,92 +369,108 @@ void ImageGroup::run()
             cout << inliers << " inliers, computed in " << std::chrono::duration<float>(end - start).count() << "s" << endl;
             ransacInliers.push_back({ (int)i, (long long)inliers });
         }
-        check(frog_transform_points(ctx, 0), "frog_transform_points");
-        check(frog_update_stats(ctx), "frog_update_stats");
+        s.transformPoints(0);
+        s.updateStats();
+        live();
         if (printStats) displayStats();
         if (printLinear) displayLinearTransforms();
     } else {
-        cout << endl << "Linear registration" << endl;
+        if (root) cout << endl << "Linear registration" << endl;
+        s.barrier();
         t0 = clk::now();
         for (int iteration = 0; iteration < linearIterations; iteration++) {
-            if (!quiet) cout << "Linear registration, iteration " << iteration + 1 << "/" << linearIterations << endl;
-            if (!(iteration % statIntervalUpdate)) check(frog_update_stats(ctx), "frog_update_stats");
-            if (printStats) displayStats();
-            double E = 0;
-            check(frog_linear_step(ctx, &E), "frog_linear_step");
-            float e = (float)E;
-            if (printLinear) displayLinearTransforms();
-            check(frog_transform_points(ctx, 0), "frog_transform_points");
-            computeLandmarkDistances(e);
+            if (root && !quiet) cout << "Linear registration, iteration " << iteration + 1 << "/" << linearIterations << endl;
+            if (!(iteration % statIntervalUpdate)) s.updateStats();
+            live();
+            if (showStats) displayStats();
+            const float e = (float)s.linearStep();
+            live();
+            if (showLinear) displayLinearTransforms();
+            s.transformPoints(0);
+            live();
+            if (root) computeLandmarkDistances(e);
         }
-        loopSeconds += std::chrono::duration<double>(clk::now() - t0).count();
-        loopIterations += linearIterations;
-
+        s.barrier();
+        if (root) { loopSeconds += std::chrono::duration<double>(clk::now() - t0).count(); loopIterations += linearIterations; }
     }
 
-    check(frog_transform_points(ctx, 1), "frog_transform_points");      // :70
-    saveDistanceHistograms("histograms_linear.csv");                    // :71
+    s.transformPoints(1);                                               // :70
+    if (sharded) s.ok(frog_synchronize(c), "frog_synchronize");
+    s.barrier();
+    live();
+    if (root) saveDistanceHistograms("histograms_linear.csv");          // :71 (reads every rank's samples)
+    s.barrier();
 
     if (deformableLevels) {
-        cout << endl << "Deformable registration" << endl;
-        countInliers();                                                 // :76
+        if (root) cout << endl << "Deformable registration" << endl;
+        census();                                                       // :76
         for (int level = 0; level < deformableLevels; level++) {
-            cout << endl << "Level " << level + 1 << "/" << deformableLevels << endl;
-            auto setup = [&]() {
-                frog_grid_info info;
-                check(frog_deformable_setup(ctx, level, &info), "frog_deformable_setup");
-                double length[3];
-                for (int k = 0; k < 3; k++) length[k] = info.bbox[2 * k + 1] - info.bbox[2 * k];
-                cout << "Bounding box : "; print(info.bbox, 6);
-                cout << "Box length : "; print(length, 3);
-                cout << "Grid origin : "; print(info.origin, 3);
-                cout << "Grid spacing : "; print(info.spacing, 3);
-                cout << "Grid dimensions (control points): "; print(info.dims, 3);
-            };
-            setup();                                                    // :81
-            check(frog_transform_points(ctx, 0), "frog_transform_points");
+            if (root) cout << endl << "Level " << level + 1 << "/" << deformableLevels << endl;
+            setup(level);                                               // :81
+            s.transformPoints(0);
             int numberOfGrids = 1;
             float alpha = deformableAlpha;
-            cout << "alpha = " << alpha << endl;
+            if (root) cout << "alpha = " << alpha << endl;
             int numberOfDiffeomorphicIterations = 0;
+            s.barrier();
             t0 = clk::now();
             for (int iteration = 0; iteration < deformableIterations; iteration++) {
-                if (!quiet)
+                if (root && !quiet)
                     cout << "Level " << level + 1 << "/" << deformableLevels << ", Iteration " << iteration + 1 << "/"
                          << deformableIterations << endl;
-                if (!(iteration % statIntervalUpdate)) check(frog_update_stats(ctx), "frog_update_stats");
-                if (printStats) displayStats();
-                double E = 0;
-                check(frog_deformable_step(ctx, alpha, &E), "frog_deformable_step");
-                float e = (float)E;
-                if (e < 0) {                                            // :97-115
-                    cout << endl << "Diffeomorphism is not guaranteed : Iteration canceled" << endl;
+                if (!(iteration % statIntervalUpdate)) s.updateStats();
+                live();
+                if (showStats) displayStats();
+                const float e = (float)s.deformableStep(alpha, iteration + 1 < deformableIterations && (iteration + 1) % statIntervalUpdate != 0);
+                live();
+                if (e < 0) {                                            // :97-115, the same on every rank
+                    if (root) cout << endl << "Diffeomorphism is not guaranteed : Iteration canceled" << endl;
                     if (numberOfDiffeomorphicIterations == 0) {
                         alpha /= 2;
-                        cout << "Halving alpha. New Value : " << alpha << endl;
+                        if (root) cout << "Halving alpha. New Value : " << alpha << endl;
                     }
-                    cout << " creating new grid" << endl;
+                    if (root) cout << " creating new grid" << endl;
                     numberOfGrids++;
                     iteration--;
-                    check(frog_transform_points(ctx, 1), "frog_transform_points");
-                    setup();
-                    check(frog_transform_points(ctx, 0), "frog_transform_points");
+                    s.transformPoints(1);
+                    setup(level);
+                    s.transformPoints(0);
                     numberOfDiffeomorphicIterations = 0;
                     continue;
                 }
                 numberOfDiffeomorphicIterations++;
-                check(frog_transform_points(ctx, 0), "frog_transform_points");
-                computeLandmarkDistances(e);
+                s.transformPoints(0);
+                live();
+                if (root) computeLandmarkDistances(e);
             }
-            loopSeconds += std::chrono::duration<double>(clk::now() - t0).count();
-            loopIterations += deformableIterations;
-            countInliers();                                             // :123
-            cout << "Number of grids for this level : " << numberOfGrids << endl;
-            gridsPerLevel.push_back(numberOfGrids);
-            check(frog_transform_points(ctx, 1), "frog_transform_points");
+            s.barrier();
+            if (root) { loopSeconds += std::chrono::duration<double>(clk::now() - t0).count(); loopIterations += deformableIterations; }
+            census();                                                   // :123
+            if (root) {
+                cout << "Number of grids for this level : " << numberOfGrids << endl;
+                gridsPerLevel.push_back(numberOfGrids);
+            }
+            s.transformPoints(1);
         }
     }
-    finishRun();
+    if (sharded) s.ok(frog_synchronize(c), "frog_synchronize");
+    s.barrier();
+    live();
+    if (sharded && std::getenv("FROG_CHECK_REPLICAS")) {
+        const uint64_t h = s.replicaHash();
+        live();
+        #pragma omp critical
+        replicaHashes[r] = h;
+        s.barrier();
+        if (root) {
+            bool same = true;
+            for (uint64_t other : replicaHashes) same = same && other == replicaHashes[0];
+            cout << "Replicas identical : " << (same ? "yes" : "NO") << " (" << ctxs.size() << " contexts, xyz2 of " << frog_num_points(c) << " points + "
+                 << s.nI << " mixtures)" << endl;
+            if (!same) exit(1);
+        }
+        s.barrier();
+    }
 }
 
 // run(), imageGroup.cxx:130-155: everything after the iteration loops
@@ -647,8 +509,7 @@ void ImageGroup::finishRun()
 void ImageGroup::saveErrorMaps()
 {
     std::filesystem::create_directory(errorMapsSubdirectory.c_str());
-    if (ctxs.empty()) check(frog_residual_sums(ctx), "frog_residual_sums");
-    else for (frog_ctx *c : ctxs) check(frog_residual_sums(c), "frog_residual_sums");      // every rank: its own images
+    for (frog_ctx *c : ctxs) check(frog_residual_sums(c), "frog_residual_sums");            // every rank: its own images
     const uint32_t n = frog_num_images(ctx);
     std::vector<frog_grid_info> infos(n);
     std::vector<std::vector<float>> maps(n);
@@ -923,19 +784,6 @@ void ImageGroup::displayLinearTransforms()
     }
 }
 
-// countInliers, imageGroup.cxx:988-1060
-void ImageGroup::countInliers()
-{
-    check(frog_count_inliers(ctx, counts.data()), "frog_count_inliers");
-    long long nPairs = 0, nInliers = 0, nOutliers = 0;
-    for (const auto &c : counts) { nPairs += c.pairs; nInliers += c.inliers; nOutliers += c.outliers; }
-    cout << "Stats:" << endl;
-    cout << nPairs << " half pairs" << endl;
-    cout << nInliers << " inliers" << endl;
-    cout << nOutliers << " outliers" << endl;
-    cout << "Outlier ratio (%): " << (float)100 * nOutliers / nPairs << endl;
-}
-
 // saveDistanceHistograms, imageGroup.cxx:850-885
 void ImageGroup::saveDistanceHistograms(const char *file)
 {
@@ -1111,16 +959,14 @@ void ImageGroup::saveStatsJSON()
     const uint64_t P = frog_num_points(ctx);
     std::vector<float> xyz(3 * P);
     check(frog_get_points(ctx, xyz.data(), nullptr), "frog_get_points");
-    if (!ctxs.empty()) {
-        // a context re-bases only its own images' xyz: take every image's rows from its owner
-        frog_model m;
-        frog_pairs_model(pairs, &m);
-        std::vector<float> part(3 * P);
-        for (size_t r = 1; r < ctxs.size(); r++) {
-            check(frog_get_points(ctxs[r], part.data(), nullptr), "frog_get_points");
-            const size_t b = 3 * (size_t)m.point_offset[shardBegin[r]], e = 3 * (size_t)m.point_offset[shardBegin[r + 1]];
-            std::copy(part.begin() + b, part.begin() + e, xyz.begin() + b);
-        }
+    // a context re-bases only its own images' xyz: take every image's rows from its owner
+    frog_model m;
+    frog_pairs_model(pairs, &m);
+    std::vector<float> part(ctxs.size() > 1 ? 3 * P : 0);
+    for (size_t r = 1; r < ctxs.size(); r++) {
+        check(frog_get_points(ctxs[r], part.data(), nullptr), "frog_get_points");
+        const size_t b = 3 * (size_t)m.point_offset[shardBegin[r]], e = 3 * (size_t)m.point_offset[shardBegin[r + 1]];
+        std::copy(part.begin() + b, part.begin() + e, xyz.begin() + b);
     }
     double mn[3] = { 1e300, 1e300, 1e300 }, mx[3] = { -1e300, -1e300, -1e300 };
     for (uint64_t p = 0; p < P; p++)

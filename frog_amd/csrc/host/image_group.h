@@ -77,17 +77,19 @@ protected:
     bool ownPairs = false;
     frog_ctx *ctx = nullptr;     // rank 0's context (the only one with one GPU)
     std::vector<frog_counts> counts;
-    // -ng N: one context and one communicator per rank, rank r owns images [shardBegin[r], shardBegin[r + 1])
+    // one context per rank, rank r owns images [shardBegin[r], shardBegin[r + 1]); -ng N: and one communicator per rank
     std::vector<frog_ctx *> ctxs;
     std::vector<struct frog_comm *> comms;
     std::vector<uint32_t> shardBegin;
     frog_ctx *ctxOf(uint32_t image) const;       // the context that owns (updates) `image`
     void planShards();
     void createShardedContexts();
-    void runSharded();                           // run()'s loops, executed by one thread per rank in lockstep
+    void runRank(int r, std::vector<uint64_t> &replicaHashes);     // run()'s loops: the one rank, or one thread per rank in lockstep
     void finishRun();                            // :130-155, everything after the loops
 
     void createContext();
+    frog_options solverOptions() const;
+    void uploadHardLinks(frog_ctx *c, const frog_model &m);
     void readAndApplyFixedImagesTransforms();    // :1419
     void check(int rc, const char *what);
     void computeLandmarkDistances(float e);      // :1229
@@ -95,7 +97,6 @@ protected:
     void saveLandmarkDistances();                // :1318
     void displayStats();                         // :899
     void displayLinearTransforms();              // :600
-    void countInliers();                         // :988
     void saveDistanceHistograms(const char *file);   // :850
     void saveMeasures(const char *file);         // :1475
     void saveTransforms();                       // :1458

@@ -101,7 +101,7 @@ int frog_pairs_set_points(frog_pairs *p, uint32_t image, const float *xyz);
  * an interpreter between two iterations.  `comm` = NULL: the context owns the whole group (or is a stand-alone proxy of one
  * rank: see proxy_*), no collective is issued; otherwise the context's communicator of include/frog_comm.h (one process per
  * GPU: frog_comm_create_rank over RCCL, or frog_comm_create_shm), bound to `ctx`, and the places where the reference's loops
- * read another image's state are its collectives, exactly as in `bin/frog -ng N` (image_group.cpp runSharded).
+ * read another image's state are its collectives, exactly as in `bin/frog -ng N` (image_group.cpp runRank, over the same steps: host/rank_steps.h).
  *
  * Sequence: setupLinearTransforms, transformPoints, warmup_linear untimed linear iterations; then, between two barriers
  * (frog_comm_barrier + frog_synchronize), `linear` linear iterations, transformPoints(apply), and for every level with

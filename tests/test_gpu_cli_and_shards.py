@@ -495,7 +495,7 @@ def test_cli_sharded_over_two_gpus_rccl(tmp_path, small_pairs):
 
 
 def test_cli_sharded_host_over_a_one_device_rccl_communicator(tmp_path, small_pairs):
-    """The C++ multi-GPU host (runSharded) with ONE rank on a real RCCL communicator (ncclCommInitAll of one device):
+    """The C++ multi-GPU host (ImageGroup::runRank over a communicator) with ONE rank on a real RCCL communicator (ncclCommInitAll of one device):
     every collective of include/frog_comm.h is issued on the context's stream exactly as with N ranks -- what a box with
     a single GPU can execute of `bin/frog -ng N`.  Same files as the plain single-context run."""
     one, sharded = tmp_path / "one", tmp_path / "sharded"
@@ -514,6 +514,28 @@ def test_cli_sharded_host_over_a_one_device_rccl_communicator(tmp_path, small_pa
     small_pairs.write(three / "pairs.bin")
     _run_frog(three, "-ng", "1", env=dict(os.environ, FROG_SHARDED_ALWAYS="1", FROG_COMM_EXERCISE_SINGLE_RANK="1", FROG_THREE_COLLECTIVES="1"))
     _compare_runs(one, three, small_pairs.n_images)
+
+
+def _cli_transcripts():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("cli_transcripts", os.path.join(ROOT, "tests", "golden", "cli_transcripts.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("name", ["plain", "ngl3", "cancel"])
+def test_cli_transcript_wording(small_pairs, name):
+    """What bin/frog prints is an interface (a UI greps it): the stdout of a plain run, of -ngl 3 and of a plain run whose
+    -da makes it cancel iterations, per-iteration lines included and every numeric token masked, line for line what the
+    build before the one stepper of host/rank_steps.h printed (tests/golden/cli_transcripts.py made the files from it)."""
+    t = _cli_transcripts()
+    got, want = t.transcript(os.path.join(ROOT, "bin", "frog"), small_pairs, name), t.golden(name)
+    if name == "cancel":
+        assert sum("Iteration canceled" in line for line in want) == t.CANCEL_LINES > 0
+    for n, (a, b) in enumerate(zip(got, want)):
+        assert a == b, f"line {n + 1}: {a!r} != {b!r}"
+    assert len(got) == len(want)
 
 
 def test_native_communicator_single_rank_over_rccl():
