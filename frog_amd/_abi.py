@@ -276,6 +276,11 @@ HIP_SYMBOLS = {
     "frog_average_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_int, C.c_double, C.POINTER(FrogVolume)]),
     "frog_average_finish": (C.c_int, [C.c_void_p, c_float_p, c_float_p]),
     "frog_average_destroy": (None, [C.c_void_p]),
+    "frog_cover_create": (C.c_int, [C.POINTER(FrogVolume), C.c_int, C.POINTER(C.c_void_p)]),
+    "frog_cover_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double,
+                                 C.POINTER(FrogVolume)]),
+    "frog_cover_finish": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, c_float_p, c_float_p, C.POINTER(C.c_uint16)]),
+    "frog_cover_destroy": (None, [C.c_void_p]),
     "frog_labels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_labels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
     "frog_labels_finish": (C.c_int, [C.c_void_p, c_u32_p]),

@@ -278,19 +278,31 @@ struct ResliceGrid {
     double background;
 };
 
-// Output voxel idx (x fastest) of a reslice: what reslice_kernel stores and reslice_accumulate_kernel adds.
-template <class S>
-__device__ __forceinline__ S reslice_voxel(const DevLink *links, int n_links, const S *__restrict__ src, const ResliceGrid &g, size_t idx)
+// The position of output voxel idx (x fastest) after the chain, in the space of whatever is sampled there.
+__device__ __forceinline__ void reslice_position(const DevLink *links, int n_links, const NodeGrid &out, size_t idx, double p[3])
 {
-    const int sx = g.sx, sy = g.sy, sz = g.sz;
-    double p[3], A[3][3];
-    grid_node(g.out, idx, p);
+    double A[3][3];
+    grid_node(out, idx, p);
     chain_point<false>(links, n_links, p, A);
-    const double c[3] = { (p[0] - g.so[0]) / g.ss[0], (p[1] - g.so[1]) / g.ss[1], (p[2] - g.so[2]) / g.ss[2] };
+}
+
+// p in the voxel coordinates of a volume (dims sx, sy, sz at origin o, spacing s), and the inside test with the half-voxel
+// border.  A NaN coordinate fails it.
+__device__ __forceinline__ bool voxel_coordinates(const double p[3], const double o[3], const double s[3], int sx, int sy, int sz, double c[3])
+{
+    c[0] = (p[0] - o[0]) / s[0]; c[1] = (p[1] - o[1]) / s[1]; c[2] = (p[2] - o[2]) / s[2];
     const int dims[3] = { sx, sy, sz };
-    double v = g.background;
     bool inside = true;
     for (int a = 0; a < 3; a++) inside = inside && c[a] >= -0.5 && c[a] <= (double)dims[a] - 0.5;
+    return inside;
+}
+
+// The voxel a reslice stores for a sample at voxel coordinates c of the source: the background where it is not inside.
+template <class S>
+__device__ __forceinline__ S reslice_sample(const S *__restrict__ src, const ResliceGrid &g, const double c[3], bool inside)
+{
+    const int sx = g.sx, sy = g.sy, sz = g.sz;
+    double v = g.background;
     if (inside) {
         auto at = [&](int x, int y, int z) -> double {
             x = x < 0 ? 0 : (x >= sx ? sx - 1 : x);
@@ -310,6 +322,16 @@ __device__ __forceinline__ S reslice_voxel(const DevLink *links, int n_links, co
         }
     }
     return to_voxel<S>(v);
+}
+
+// Output voxel idx (x fastest) of a reslice: what reslice_kernel stores and reslice_accumulate_kernel adds.
+template <class S>
+__device__ __forceinline__ S reslice_voxel(const DevLink *links, int n_links, const S *__restrict__ src, const ResliceGrid &g, size_t idx)
+{
+    double p[3], c[3];
+    reslice_position(links, n_links, g.out, idx, p);
+    const bool inside = voxel_coordinates(p, g.so, g.ss, g.sx, g.sy, g.sz, c);
+    return reslice_sample<S>(src, g, c, inside);
 }
 
 template <class S>
@@ -368,6 +390,92 @@ __global__ __launch_bounds__(256) void average_finish_kernel(size_t base, const 
     const float a = avg[idx];
     const float a2 = a * a;
     sq[idx] = sqrtf(sq[idx] - a2);
+}
+
+// ---- mean / stdev / count over the images that cover a voxel (frog_cover; no counterpart in the reference) -----------------
+// Three accumulators per voxel, owned by one thread as in accumulate: the running mean and sum of squared deviations
+// (Welford) and the number of images that were valid there.  One f32 operation per statement (-ffp-contract=off), in the
+// order include/frog_chain.h states.  The new mean is a rounded value between the old mean and x (rounding is monotone), so
+// x - mean_new has d's sign or is zero, d * (x - mean_new) >= 0 and m2 never decreases: sqrtf(m2 / k) has no difference
+// under the root and gives no NaN unless a difference overflows.
+__device__ __forceinline__ void cover_update(float *__restrict__ mean, float *__restrict__ m2, uint16_t *__restrict__ count, size_t idx, float x)
+{
+    const uint32_t k = (uint32_t)count[idx] + 1u;
+    const float m = mean[idx];
+    const float d = x - m;
+    const float q = d / (float)k;
+    const float m_new = m + q;
+    const float e = x - m_new;
+    const float t = d * e;
+    mean[idx] = m_new;
+    m2[idx] = m2[idx] + t;
+    count[idx] = (uint16_t)k;
+}
+
+// The geometry of a mask (u8, non-zero = valid), which need not be the source's.
+struct MaskGrid {
+    int sx, sy, sz;
+    double so[3], ss[3];
+};
+
+// The chain is evaluated once: the position it gives is turned into the source's voxel coordinates (reslice_sample, the code
+// of reslice_kernel, gives the value and `out`) and, where the source covers it, into the mask's, whose nearest voxel
+// (floor(c + 0.5), as a nearest-neighbour reslice reads it) decides.
+template <class S>
+__global__ __launch_bounds__(256) void cover_reslice_kernel(size_t base, const DevLink *links, int n_links, const S *__restrict__ src,
+                                                            const ResliceGrid g, const uint8_t *__restrict__ mask, const MaskGrid mg,
+                                                            float *__restrict__ mean, float *__restrict__ m2,
+                                                            uint16_t *__restrict__ count, S *__restrict__ out)
+{
+    const size_t total = (size_t)g.out.dims[0] * g.out.dims[1] * g.out.dims[2];
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    double p[3], c[3];
+    reslice_position(links, n_links, g.out, idx, p);
+    bool valid = voxel_coordinates(p, g.so, g.ss, g.sx, g.sy, g.sz, c);
+    const S r = reslice_sample<S>(src, g, c, valid);
+    if (out) out[idx] = r;
+    if (valid && mask) {
+        valid = voxel_coordinates(p, mg.so, mg.ss, mg.sx, mg.sy, mg.sz, c);
+        if (valid) {
+            int x = (int)floor(c[0] + 0.5), y = (int)floor(c[1] + 0.5), z = (int)floor(c[2] + 0.5);
+            x = x < 0 ? 0 : (x >= mg.sx ? mg.sx - 1 : x);
+            y = y < 0 ? 0 : (y >= mg.sy ? mg.sy - 1 : y);
+            z = z < 0 ? 0 : (z >= mg.sz ? mg.sz - 1 : z);
+            valid = mask[(size_t)x + (size_t)mg.sx * ((size_t)y + (size_t)mg.sy * (size_t)z)] != 0;
+        }
+    }
+    if (valid) cover_update(mean, m2, count, idx, (float)r);
+}
+
+// a source (and a mask) already on the grid: every voxel is inside
+template <class S>
+__global__ __launch_bounds__(256) void cover_identity_kernel(size_t base, const S *__restrict__ src, const uint8_t *__restrict__ mask, size_t total,
+                                                             float *__restrict__ mean, float *__restrict__ m2, uint16_t *__restrict__ count)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    if (!mask || mask[idx] != 0) cover_update(mean, m2, count, idx, (float)src[idx]);
+}
+
+// where count >= min_count the mean as held and sqrt(m2 / count), elsewhere `fill` and 0; any output may be null
+__global__ __launch_bounds__(256) void cover_finish_kernel(size_t base, const float *__restrict__ mean, const float *__restrict__ m2,
+                                                           const uint16_t *__restrict__ count, size_t total, uint32_t min_count, float fill,
+                                                           float *__restrict__ out_mean, float *__restrict__ out_stdev)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const uint32_t k = count[idx];
+    const bool enough = k >= min_count;
+    if (out_mean) out_mean[idx] = enough ? mean[idx] : fill;
+    if (out_stdev) {
+        float s = 0.0f;
+        if (enough) {
+            const float variance = m2[idx] / (float)k;
+            s = sqrtf(variance);
+        }
+        out_stdev[idx] = s;
+    }
 }
 
 __global__ __launch_bounds__(256) void chain_apply_kernel(size_t base, const DevLink *links, int n_links, const double *in, double *out, size_t n)
@@ -616,6 +724,18 @@ struct frog_average {
     frog::DevBuf<unsigned char> d_src, d_out;       // staging of the current source / resliced volume, grown on demand
 };
 
+// running mean, squared deviations and count of the images that cover each voxel of one grid
+struct frog_cover {
+    int device = 0;
+    frog_volume grid;
+    uint32_t added = 0;
+    size_t total = 0;
+    frog::DevBuf<float> d_mean, d_m2;
+    frog::DevBuf<uint16_t> d_count;
+    frog::DevBuf<unsigned char> d_src, d_out, d_mask;   // staging of the current source / resliced volume / u8 mask, grown on demand
+    std::vector<unsigned char> h_mask;                  // the mask as value != 0, before its upload
+};
+
 // vote counts of a group's label maps on one grid
 struct frog_labels {
     int device = 0;
@@ -810,6 +930,54 @@ int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, in
     if (e == hipSuccess) e = hipStreamSynchronize(0);
     if (e != hipSuccess) return hip_fail("frog_average_add", e);
     return FROG_OK;
+}
+
+template <class S>
+int cover_add_typed(frog_cover *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background,
+                    frog_volume *resliced)
+{
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    const size_t n_mask = mask ? (size_t)mask->dims[0] * mask->dims[1] * mask->dims[2] : 0;
+    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
+    if (mask) KCHECK(a->d_mask.alloc(n_mask));
+    if (c && resliced) KCHECK(a->d_out.alloc(a->total * sizeof(S)));
+    const S *d_src = (const S *)a->d_src.p;
+    const uint8_t *d_mask = mask ? a->d_mask.p : nullptr;
+    S *d_out = (S *)a->d_out.p;
+    hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
+    if (e == hipSuccess && mask) e = hipMemcpy(a->d_mask.p, a->h_mask.data(), n_mask, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const ResliceGrid g = reslice_grid(src, &a->grid, interpolation, background);
+        MaskGrid mg{};
+        if (mask) {
+            mg.sx = (int)mask->dims[0]; mg.sy = (int)mask->dims[1]; mg.sz = (int)mask->dims[2];
+            for (int k = 0; k < 3; k++) { mg.so[k] = mask->origin[k]; mg.ss[k] = mask->spacing[k]; }
+        }
+        e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+            if (c)
+                cover_reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg,
+                                                                  a->d_mean.p, a->d_m2.p, a->d_count.p, resliced ? d_out : nullptr);
+            else
+                cover_identity_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_src, d_mask, a->total, a->d_mean.p, a->d_m2.p, a->d_count.p);
+        });
+    }
+    if (e == hipSuccess && resliced) {
+        if (c) e = hipMemcpy(resliced->data, d_out, a->total * sizeof(S), hipMemcpyDeviceToHost);
+        else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return hip_fail("frog_cover_add", e);
+    return FROG_OK;
+}
+
+// h_mask = (value != 0) of an integer mask volume
+template <class M>
+void cover_mask_bytes(frog_cover *a, const frog_volume *mask)
+{
+    const size_t n = (size_t)mask->dims[0] * mask->dims[1] * mask->dims[2];
+    const M *v = (const M *)mask->data;
+    a->h_mask.resize(n);
+    for (size_t i = 0; i < n; i++) a->h_mask[i] = v[i] != 0;
 }
 
 // The device map rebuilt from the known labels alone (at creation: empty): how a refused volume's inserts are taken back.
@@ -1143,6 +1311,92 @@ int frog_average_finish(frog_average *a, float *mean, float *stdev)
 }
 
 void frog_average_destroy(frog_average *a)
+{
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    delete a;
+}
+
+int frog_cover_create(const frog_volume *grid, int device, frog_cover **out)
+{
+    if (!grid || !out) return fail(FROG_E_INVALID, "bad arguments to frog_cover_create");
+    const size_t total = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
+    if (!total) return fail(FROG_E_INVALID, "empty grid");
+    if (total > ((size_t)1 << 31)) return fail(FROG_E_INVALID, "grid above 2^31 voxels");
+    if (int rc = select_device(device)) return rc;
+    std::unique_ptr<frog_cover> a(new (std::nothrow) frog_cover);
+    if (!a) return fail(FROG_E_NOMEM, "out of host memory");
+    a->device = device;
+    a->grid = *grid;
+    a->grid.data = nullptr;
+    a->total = total;
+    KCHECK(a->d_mean.alloc(total));
+    KCHECK(a->d_m2.alloc(total));
+    KCHECK(a->d_count.alloc(total));
+    KCHECK(hipMemset(a->d_mean.p, 0, total * sizeof(float)));
+    KCHECK(hipMemset(a->d_m2.p, 0, total * sizeof(float)));
+    KCHECK(hipMemset(a->d_count.p, 0, total * sizeof(uint16_t)));
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_cover_add(frog_cover *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background,
+                   frog_volume *resliced)
+{
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_cover_add");
+    if (a->added >= 65535) return fail(FROG_E_INVALID, "frog_cover_add: more than 65535 volumes (16-bit counts)");
+    if (c && c->device != a->device) return fail(FROG_E_INVALID, "frog_cover_add: chain and accumulator on different devices");
+    if (mask && !mask->data) return fail(FROG_E_INVALID, "frog_cover_add: a mask without voxels");
+    if (mask && (mask->dtype < FROG_V_U8 || mask->dtype > FROG_V_I32)) return fail(FROG_E_INVALID, "frog_cover_add: a mask has an integer type");
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    if (!n_src || (mask && !((size_t)mask->dims[0] * mask->dims[1] * mask->dims[2]))) return fail(FROG_E_INVALID, "empty volume");
+    for (int k = 0; k < 3; k++) {
+        if (c && (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad source geometry");
+        if (c && mask && (mask->dims[k] > 0x7FFFFFFFu || !(mask->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad mask geometry");
+        if (!c && src->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_cover_add: volume dimensions differ from the grid's");
+        if (!c && mask && mask->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_cover_add: mask dimensions differ from the grid's");
+        if (resliced && resliced->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_cover_add: resliced volume is not grid-sized");
+    }
+    if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, "frog_cover_add: resliced volume must have the source's type");
+    if (mask) {
+        switch (mask->dtype) {
+        case FROG_V_U8: cover_mask_bytes<uint8_t>(a, mask); break;
+        case FROG_V_I8: cover_mask_bytes<int8_t>(a, mask); break;
+        case FROG_V_U16: cover_mask_bytes<uint16_t>(a, mask); break;
+        case FROG_V_I16: cover_mask_bytes<int16_t>(a, mask); break;
+        case FROG_V_U32: cover_mask_bytes<uint32_t>(a, mask); break;
+        default: cover_mask_bytes<int32_t>(a, mask); break;
+        }
+    }
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_voxel_type(src->dtype, [&](auto s) { return cover_add_typed<decltype(s)>(a, c, src, mask, interpolation, background, resliced); });
+    if (rc == FROG_OK) a->added++;
+    return rc;
+}
+
+int frog_cover_finish(frog_cover *a, uint32_t min_count, float fill, float *mean, float *stdev, uint16_t *count)
+{
+    if (!a || (!mean && !stdev && !count)) return fail(FROG_E_INVALID, "bad arguments to frog_cover_finish");
+    if (!min_count) return fail(FROG_E_INVALID, "frog_cover_finish: min_count must be at least 1");
+    if (!a->added) return fail(FROG_E_INVALID, "frog_cover_finish: before the first frog_cover_add");
+    KCHECK(hipSetDevice(a->device));
+    frog::DevBuf<float> d_mean, d_stdev;
+    if (mean) KCHECK(d_mean.alloc(a->total));
+    if (stdev) KCHECK(d_stdev.alloc(a->total));
+    hipError_t e = hipSuccess;
+    if (mean || stdev) {
+        e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+            cover_finish_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_mean.p, a->d_m2.p, a->d_count.p, a->total, min_count, fill, d_mean.p, d_stdev.p);
+        });
+    }
+    if (e == hipSuccess && mean) e = hipMemcpy(mean, d_mean.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && stdev) e = hipMemcpy(stdev, d_stdev.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count) e = hipMemcpy(count, a->d_count.p, a->total * sizeof(uint16_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_cover_finish", e);
+    return FROG_OK;
+}
+
+void frog_cover_destroy(frog_cover *a)
 {
     if (!a) return;
     (void)hipSetDevice(a->device);

@@ -2,7 +2,7 @@
 // DummyVolumeGenerator, one VolumeTransform per image and AverageVolumes, without writing and re-reading N volumes and
 // without N + 2 HIP runtime starts.
 //   AverageImage bbox.json spacing v_0 ... v_{N-1} [-td transformsDir] [-o outDir] [-i interpolation] [-b background]
-//                [-wt 1] [-dev n]
+//                [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid); image i is resliced through the inverse of <transformsDir>/<i>.json
 // (default "transforms"; -j and sidecar forms) exactly as `VolumeTransform v_i dummy.mhd -t transforms/i.json` does it
 // (same device code; background = the image's minimum unless -b, linear unless -i 0), converted to its own type and added
@@ -10,6 +10,12 @@
 // bit for bit.  -wt 1 also writes transformed<i>.nii.gz, the file transform.sh leaves behind.  Every transform and volume
 // header is checked before anything is written.  Volumes are read and inflated on host threads ahead of the device, a
 // bounded number at a time (volume_stream.h).
+// -c 1 (coverage-aware; no counterpart upstream): image i is added only where it covers the grid voxel (frog_cover_add), so
+// average.nii.gz and stdev.nii.gz are the mean and the population stdev over the covering images, and coverage.nii.gz
+// (uint16) is their number.  -ml names a text file with one mask path per line, N lines (the list format of FROG.py -m):
+// image i then counts only where mask i, an integer volume of its own geometry, is non-zero at the nearest voxel; the masks
+// are streamed like the images.  -mc: voxels that fewer than minCount (default 1) images cover get the mean -f (default 0)
+// and the stdev 0.  -ml, -mc or -f without -c 1 is an error.  transformed<i>.nii.gz is the same file either way.
 #include "tool_common.h"
 #include "volume_stream.h"
 
@@ -21,27 +27,53 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <iostream>
+#include <memory>
 #include <string>
 #include <vector>
 
 namespace {
 
-// the header of a volume parses (NIfTI-1: sizeof_hdr; MetaImage: DimSize present), without inflating its data
-bool header_ok(const std::string &path)
+// the header of a volume parses (NIfTI-1: sizeof_hdr; MetaImage: DimSize present), without inflating its data; `is_float`
+// (may be null) receives whether it declares a float type (NIfTI-1: datatype 16 or 64 at byte 70; MetaImage: ElementType)
+bool header_ok(const std::string &path, bool *is_float = nullptr)
 {
     auto has_suffix = [&](const char *s) { const size_t n = std::strlen(s); return path.size() >= n && path.compare(path.size() - n, n, s) == 0; };
+    if (is_float) *is_float = false;
     if (has_suffix(".mhd") || has_suffix(".mha")) {
         uint32_t d[3]; double sp[3], o[3];
-        return frog_volume_geometry(path.c_str(), d, sp, o) == FROG_OK;
+        if (frog_volume_geometry(path.c_str(), d, sp, o) != FROG_OK) return false;
+        std::ifstream f(path);
+        for (std::string line; is_float && std::getline(f, line) && line.compare(0, 15, "ElementDataFile") != 0;)
+            if (line.compare(0, 11, "ElementType") == 0 && (line.find("MET_FLOAT") != std::string::npos || line.find("MET_DOUBLE") != std::string::npos))
+                *is_float = true;
+        return true;
     }
     if (!has_suffix(".nii") && !has_suffix(".nii.gz")) return false;
     gzFile f = gzopen(path.c_str(), "rb");
     if (!f) return false;
-    int32_t n = 0;
-    const bool ok = gzread(f, &n, sizeof n) == (int)sizeof n && n == 348;
+    unsigned char h[72];
+    const bool read = gzread(f, h, sizeof h) == (int)sizeof h;
     gzclose(f);
-    return ok;
+    int32_t n = 0;
+    int16_t datatype = 0;
+    std::memcpy(&n, h, sizeof n);
+    std::memcpy(&datatype, h + 70, sizeof datatype);
+    if (is_float) *is_float = datatype == 16 || datatype == 64;
+    return read && n == 348;
+}
+
+// the lines of a list file (FROG.py -m's format: one path per line), without their line ends; blank lines are dropped
+bool read_list(const std::string &path, std::vector<std::string> &lines)
+{
+    std::ifstream f(path);
+    if (!f) return false;
+    for (std::string line; std::getline(f, line);) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (!line.empty()) lines.push_back(line);
+    }
+    return true;
 }
 
 } // namespace
@@ -54,11 +86,14 @@ int main(int argc, char *argv[])
     // reader threads may still be inflating: leave without running static destructors under them
     auto die = [](const std::string &what) { std::cout << "Error : " << what << std::endl; std::_Exit(1); };
     std::vector<std::string> volumes;
-    std::string transformsDir = "transforms", outDir = ".";
-    int interpolation = 1, device = 0, writeTransformed = 0;
+    std::string transformsDir = "transforms", outDir = ".", maskList;
+    int interpolation = 1, device = 0, writeTransformed = 0, coverage = 0;
+    long minCount = 1;
+    float fill = 0;
+    bool coverageOption = false;                            // -ml, -mc or -f was given
     BackgroundLevel background;
     auto is_flag = [](const char *a) {
-        for (const char *f : { "-td", "-o", "-i", "-b", "-wt", "-dev" }) if (std::strcmp(a, f) == 0) return true;
+        for (const char *f : { "-td", "-o", "-i", "-b", "-wt", "-dev", "-c", "-ml", "-mc", "-f" }) if (std::strcmp(a, f) == 0) return true;
         return false;
     };
     int a = 3;
@@ -71,14 +106,26 @@ int main(int argc, char *argv[])
         else if (std::strcmp(key, "-b") == 0) background.parse(value);
         else if (std::strcmp(key, "-wt") == 0) writeTransformed = atoi(value);
         else if (std::strcmp(key, "-dev") == 0) device = atoi(value);
+        else if (std::strcmp(key, "-c") == 0) coverage = atoi(value);
+        else if (std::strcmp(key, "-ml") == 0) { maskList = value; coverageOption = true; }
+        else if (std::strcmp(key, "-mc") == 0) { minCount = atol(value); coverageOption = true; }
+        else if (std::strcmp(key, "-f") == 0) { fill = (float)atof(value); coverageOption = true; }
         else die(std::string("unknown option ") + key);
     }
     if (argc < 4 || volumes.empty()) {
         std::cout << "Usage : AverageImage bbox.json spacing image_0 ... image_N-1 [-td transformsDir] [-o outDir] [-i interpolation] "
-                     "[-b background] [-wt 1] [-dev n]" << std::endl;
+                     "[-b background] [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]]" << std::endl;
         return 1;
     }
     const size_t n = volumes.size();
+    if (coverageOption && coverage != 1) die("-ml, -mc and -f need -c 1");
+    if (minCount < 1 || minCount > 65535) die("-mc takes a count from 1 to 65535");
+    if (coverage == 1 && n > 65535) die("-c 1 takes at most 65535 images (16-bit counts)");
+    std::vector<std::string> masks;
+    if (!maskList.empty()) {
+        if (!read_list(maskList, masks)) die("cannot read the mask list " + maskList);
+        if (masks.size() != n) die(maskList + " holds " + std::to_string(masks.size()) + " masks for " + std::to_string(n) + " images");
+    }
 
     // ---- everything is checked before the first output: the grid, every transform, every volume header
     frog_volume grid;
@@ -94,6 +141,11 @@ int main(int argc, char *argv[])
         if (frog_chain_invert_links(frog_transform_links(f), nl, inverse[i].data())) die(path + ": " + frog_last_error());
     }
     for (const auto &v : volumes) if (!header_ok(v)) die("cannot read volume " + v);
+    for (const auto &m : masks) {
+        bool is_float = false;
+        if (!header_ok(m, &is_float)) die("cannot read mask " + m);
+        if (is_float) die(m + " is a float volume: masks have an integer type");
+    }
     if (mkdir(outDir.c_str(), 0755) != 0 && errno != EEXIST) die("cannot create " + outDir);
     std::cout << n << " images, grid " << grid.dims[0] << " x " << grid.dims[1] << " x " << grid.dims[2] << " (spacing " << grid.spacing[0]
               << ", origin " << grid.origin[0] << " " << grid.origin[1] << " " << grid.origin[2] << ")" << std::endl;
@@ -101,7 +153,9 @@ int main(int argc, char *argv[])
     int threads;
     size_t window;
     frog::volume_stream_shape(n, &threads, &window);
+    if (!masks.empty()) threads = std::max(1, threads / 2);  // the masks have readers of their own
     frog::VolumeStream stream(volumes, threads, window);     // reading starts now, beside the device set-up below
+    std::unique_ptr<frog::VolumeStream> maskStream(masks.empty() ? nullptr : new frog::VolumeStream(masks, threads, window));
 
     double device_s = 0, write_s = 0, waited_s = 0;
     auto t0 = clk::now();
@@ -109,7 +163,8 @@ int main(int argc, char *argv[])
     for (size_t i = 0; i < n; i++)
         if (frog_chain_create(inverse[i].data(), (uint32_t)inverse[i].size(), device, &chains[i])) die("transform " + std::to_string(i) + ": " + frog_last_error());
     frog_average *avg = nullptr;
-    if (frog_average_create(&grid, (uint32_t)n, device, &avg)) die(frog_last_error());
+    frog_cover *cover = nullptr;
+    if (coverage == 1 ? frog_cover_create(&grid, device, &cover) : frog_average_create(&grid, (uint32_t)n, device, &avg)) die(frog_last_error());
     const double setup_s = seconds(t0);
 
     const size_t total = (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2];
@@ -119,6 +174,13 @@ int main(int argc, char *argv[])
         frog::VolumeStream::Item &it = stream.get(i, &waited);
         waited_s += waited;
         if (!it.file) die("cannot read volume " + volumes[i]);
+        const frog_volume *mask = nullptr;
+        if (maskStream) {
+            frog::VolumeStream::Item &m = maskStream->get(i, &waited);
+            waited_s += waited;
+            if (!m.file) die("cannot read mask " + masks[i]);
+            mask = &m.view;
+        }
         frog_volume resliced = grid, *out = nullptr;
         if (writeTransformed) {
             resliced.dtype = it.view.dtype;
@@ -127,10 +189,12 @@ int main(int argc, char *argv[])
             out = &resliced;
         }
         t0 = clk::now();
-        if (frog_average_add(avg, chains[i], &it.view, interpolation, background.of(it.lo), out))
+        if (cover ? frog_cover_add(cover, chains[i], &it.view, mask, interpolation, background.of(it.lo), out)
+                  : frog_average_add(avg, chains[i], &it.view, interpolation, background.of(it.lo), out))
             die(volumes[i] + ": " + frog_last_error());
         device_s += seconds(t0);
         stream.release(i);
+        if (maskStream) maskStream->release(i);
         frog_chain_destroy(chains[i]);
         chains[i] = nullptr;
         if (out) {
@@ -141,8 +205,10 @@ int main(int argc, char *argv[])
         }
     }
     std::vector<float> mean(total), stdev(total);
+    std::vector<uint16_t> count(cover ? total : 0);
     t0 = clk::now();
-    if (frog_average_finish(avg, mean.data(), stdev.data())) die(frog_last_error());
+    if (cover ? frog_cover_finish(cover, (uint32_t)minCount, fill, mean.data(), stdev.data(), count.data())
+              : frog_average_finish(avg, mean.data(), stdev.data())) die(frog_last_error());
     device_s += seconds(t0);
     frog_average_destroy(avg);
 
@@ -153,11 +219,19 @@ int main(int argc, char *argv[])
         const std::string path = outDir + "/" + name;
         if (frog_volume_write(path.c_str(), &grid)) die("cannot write " + path);
     }
+    if (cover) {
+        frog_cover_destroy(cover);
+        grid.dtype = FROG_V_U16;
+        grid.data = count.data();
+        const std::string path = outDir + "/coverage.nii.gz";
+        if (frog_volume_write(path.c_str(), &grid)) die("cannot write " + path);
+    }
     write_s += seconds(t0);
     char line[512];
     std::snprintf(line, sizeof line,
                   "read : %.3f s of %d host threads (device waited %.3f s)\ndevice : %.3f s (+ %.3f s set-up)\nwrite : %.3f s\ntotal : %.3f s",
-                  stream.read_seconds(), stream.threads(), waited_s, device_s, setup_s, write_s, seconds(t_start));
+                  stream.read_seconds() + (maskStream ? maskStream->read_seconds() : 0.0),
+                  stream.threads() + (maskStream ? maskStream->threads() : 0), waited_s, device_s, setup_s, write_s, seconds(t_start));
     std::cout << line << std::endl;
     return 0;
 }

@@ -124,6 +124,86 @@ def average(volumes, chains=None, grid=None, interpolation=1, backgrounds=None, 
         acc.close()
 
 
+class CoverAverage:
+    """frog_cover (include/frog_chain.h): volumes added one by one on `grid` = (dims(x, y, z), origin, spacing), each only
+    where it covers the voxel (and its mask is non-zero); then the f32 mean and stdev over the covering images and their
+    count."""
+
+    def __init__(self, grid, device=0):
+        self._lib = _abi.hip_lib()
+        dims, origin, spacing = grid
+        self.dims = tuple(int(d) for d in dims)
+        self._grid = _abi.volume_view(None, origin, spacing, self.dims)
+        self._h = C.c_void_p()
+        _abi.check(self._lib.frog_cover_create(C.byref(self._grid), int(device), C.byref(self._h)), "frog_cover_create")
+
+    def close(self):
+        if self._h:
+            self._lib.frog_cover_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, volume, chain=None, mask=None, interpolation=1, background=0.0, resliced=False):
+        """Adds `volume` ((voxels, origin, spacing) or an array already on the grid when chain is None) where it is valid:
+        with a chain (frog_amd.chain.Chain, grid space -> volume space) where the sample lies inside the volume as
+        Chain.reslice decides it, without one everywhere; and, with `mask` (an integer volume of its own geometry, given
+        like `volume`), where the mask's nearest voxel is non-zero.  resliced=True returns the volume Chain.reslice would
+        give with `background` (source dtype, shape dims[::-1])."""
+        a, o, s = _as_volume(volume)
+        src = _abi.volume_view(a, o, s)
+        mv = None
+        if mask is not None:
+            m, mo, ms = _as_volume(mask)
+            mv = _abi.volume_view(m, mo, ms)
+        out, ov = None, None
+        if resliced:
+            out = np.empty(self.dims[::-1], a.dtype)
+            ov = _abi.volume_view(out, tuple(self._grid.origin), tuple(self._grid.spacing))
+        _abi.check(self._lib.frog_cover_add(self._h, chain._h if chain is not None else None, C.byref(src),
+                                            C.byref(mv) if mv is not None else None, int(interpolation), float(background),
+                                            C.byref(ov) if ov is not None else None), "frog_cover_add")
+        return out
+
+    def finish(self, min_count=1, fill=0.0):
+        """(mean, stdev, count): float32, float32 and uint16 arrays of shape dims[::-1]; where fewer than min_count images
+        were valid the mean is `fill` and the stdev 0.  May be called again, and after further adds."""
+        mean = np.empty(self.dims[::-1], np.float32)
+        stdev = np.empty_like(mean)
+        count = np.empty(self.dims[::-1], np.uint16)
+        _abi.check(self._lib.frog_cover_finish(self._h, int(min_count), float(fill), mean.ctypes.data_as(_abi.c_float_p),
+                                               stdev.ctypes.data_as(_abi.c_float_p), count.ctypes.data_as(C.POINTER(C.c_uint16))),
+                   "frog_cover_finish")
+        return mean, stdev, count
+
+
+def cover_average(volumes, chains=None, masks=None, grid=None, interpolation=1, min_count=1, fill=0.0, device=0):
+    """Voxel-wise mean, stdev and count over the images that cover each grid voxel (bin/AverageImage -c 1).  `volumes`,
+    `chains` and `grid` as in average(); `masks`: None or one integer volume (or None) per image.  Returns
+    (mean float32, stdev float32, count uint16)."""
+    vols = [_as_volume(v) for v in volumes]
+    if not vols:
+        raise ValueError("no volumes")
+    if chains is not None and len(chains) != len(vols):
+        raise ValueError("one chain per volume expected")
+    if masks is not None and len(masks) != len(vols):
+        raise ValueError("one mask per volume expected")
+    if grid is None:
+        a, o, s = vols[0]
+        grid = (a.shape[::-1], o, s)
+    acc = CoverAverage(grid, device)
+    try:
+        for k, v in enumerate(vols):
+            acc.add(v, None if chains is None else chains[k], None if masks is None else masks[k], interpolation)
+        return acc.finish(min_count, fill)
+    finally:
+        acc.close()
+
+
 FUSED_DTYPES = ("uint8", "uint16", "int16", "int32", "uint32")
 
 

@@ -151,6 +151,36 @@ int  frog_average_add(frog_average *a, frog_chain *chain, const frog_volume *sou
 int  frog_average_finish(frog_average *a, float *mean, float *stdev);
 void frog_average_destroy(frog_average *a);
 
+/* ---- mean, stdev and count over the images that cover a voxel (an extension: the reference averages the background in) --------
+ * frog_average adds `background` wherever a grid voxel lies outside an image, so the mean of a group with different fields
+ * of view is dimmed and its stdev inflated where only some images overlap.  This accumulator on `grid` (dims, origin,
+ * spacing; its dtype and data are ignored) adds an image only where it is VALID and counts how many were.  Three values per
+ * voxel: mean f32, m2 f32, count u16; one device thread owns a voxel, images in call order, no atomics: deterministic.
+ * Per valid voxel, every line one correctly rounded f32 operation (Welford's update):
+ *     k = count + 1;  d = x - mean;  mean = mean + d / (float)k;  m2 = m2 + d * (x - mean);  count = k
+ * m2 never decreases, so the stdev is never the root of a negative difference.
+ * FROG_E_INVALID, before the device is touched: a NULL argument, an empty grid or one above 2^31 voxels. */
+typedef struct frog_cover frog_cover;
+int  frog_cover_create(const frog_volume *grid, int device, frog_cover **out);
+/* The value x = (float)r, r the voxel frog_chain_reslice(chain, source, out, interpolation, background) stores (the same
+ * device code, in the source's type: integers rounded half up and clamped); `resliced` (may be NULL; dims the grid's, dtype
+ * the source's) receives r for every voxel, valid or not, and is the only place `background` shows.
+ * chain != NULL: the voxel is valid iff its position after the chain passes the reslice's inside test against the source
+ * (-0.5 <= c <= dims - 0.5 on every axis; NaN fails) and, with a mask, the same position passes that test against the mask's
+ * own geometry and the mask voxel floor(c_mask + 0.5) is non-zero.  The chain is evaluated once per voxel.  The mask (may be
+ * NULL) has any of the six integer types and its own dims, origin and spacing; negative values count as non-zero.
+ * chain == NULL: the source's dims, and a mask's, must equal the grid's; every voxel is inside, and valid where the mask
+ * is non-zero; `resliced` receives the source.
+ * FROG_E_INVALID, before any device work: a float mask, bad geometry, a chain on another device, the 65 536th add. */
+int  frog_cover_add(frog_cover *a, frog_chain *chain, const frog_volume *source, const frog_volume *mask, int interpolation,
+                    double background, frog_volume *resliced);
+/* After at least one add (FROG_E_INVALID before), as often as wanted, and more adds may follow: grid-sized host buffers, x
+ * fastest.  Where count >= min_count: the mean as held and stdev = sqrtf(m2 / (float)count) (the population stdev of the
+ * valid images); elsewhere mean = fill and stdev = 0.  `count` always receives the raw count.  min_count >= 1
+ * (FROG_E_INVALID for 0).  Any output may be NULL, not all three. */
+int  frog_cover_finish(frog_cover *a, uint32_t min_count, float fill, float *mean, float *stdev, uint16_t *count);
+void frog_cover_destroy(frog_cover *a);
+
 /* ---- majority-vote fusion of a registered group's label maps (an extension: the reference stops at N x VolumeTransform -i 0) --
  * An accumulator of n_images label volumes on `grid` (dims, origin, spacing; its dtype and data are ignored).  Per voxel v
  * and label value l it counts the images that carry l at v: count[l][v], 16-bit, one device thread per voxel, no atomics on
