@@ -20,6 +20,9 @@
  * Inverse of a B-spline link (FROG_T_BSPLINE_INVERSE): Newton's method with vtkWarpTransform's
  *              defaults (tolerance 1e-3, 500 iterations, step shortening when the residual grows);
  *              the inverse of a linear link is its inverted matrix (frog_chain_invert_links).
+ *              A point that has not converged after the 500 iterations (a folded lattice) returns the last point at which
+ *              the residual |T(x) - p| decreased, never a worse one than the first guess p - d(p).  A NaN or infinite
+ *              coordinate returns NaN in that coordinate and, no tap being read on that axis, the other two unchanged.
  * Displacement field link (FROG_T_FIELD; an extension, the reference has no such transform): `dims`, `origin`, `spacing`
  *              describe a grid of nodes, `coeffs` holds one f32 displacement per node, x fastest -- what frog_chain_sample
  *              writes with FROG_V_F32.  Forward only, f64.  Exactly, per axis: c = (p - origin) / spacing clamped to

@@ -6,7 +6,10 @@
 // tools/CheckDiffeomorphism.cxx:67-85), which is absent from this image.  The restatement
 // follows VTK's documented semantics (double path): see include/frog_chain.h.  Checked by
 // closed-form cases in tests/test_chain.py (identity, pure matrix, a lattice whose displacement
-// is an exact quadratic/linear function of position).
+// is an exact quadratic/linear function of position).  The Newton inverse is pinned for accuracy
+// as well, by tests/inverse_restate.py (a NumPy restatement of the forward link and a plain Newton
+// polish): distance to the polished root, decreasing residual on a folded lattice, composition,
+// Jacobian and non-finite input, in tests/test_chain.py.  Parity with VTK stays unpinned.
 #include "../include/frog_chain.h"
 
 #include <algorithm>

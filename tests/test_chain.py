@@ -8,6 +8,7 @@ import json
 import numpy as np
 import pytest
 
+import inverse_restate as ir
 from frog_amd import _abi
 from frog_amd.chain import Link, read_transform
 from oracle.oracle_api import chain_apply, chain_check
@@ -191,3 +192,71 @@ def test_invert_links_is_host_side_and_involutive():
     with pytest.raises(RuntimeError):
         invert(singular)
     assert invert([]) == []
+
+
+# ---- the Newton inverse on strong and folded lattices: the oracle held to tests/inverse_restate.py --------------------------------
+# The same assertions as tests/test_gpu_inverse.py makes of the device, with chain_apply as the evaluator.
+
+@pytest.mark.parametrize("case", ["strong", "folded", "pyramid"])
+def test_restated_forward_matches_oracle(case):
+    links = {"strong": [ir.strong_lattice(ir.STRONG_FRAC)], "folded": [ir.strong_lattice(ir.FOLDED_FRAC)],
+             "pyramid": list(ir.pyramid_chain())}[case]
+    pts = ir.sample_points(5)
+    none, partial = ir.support(links[-1], pts)
+    assert none.sum() >= 1000 and partial.sum() >= 1000            # every branch of the tap loop is compared
+    want, wantJ = chain_apply(links, pts, jacobian=True)
+    got, gotJ = ir.chain_forward(links, pts)
+    assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max()
+    assert np.abs(gotJ - wantJ).max() <= 1e-12 * np.abs(wantJ).max()
+
+
+def test_inverse_inputs_are_what_the_tests_rely_on():
+    n, m = chain_check([ir.strong_lattice(ir.STRONG_FRAC)], *ir.CHECK_GRID)
+    assert n == 0 and m > 0.1
+    n, m = chain_check(list(ir.pyramid_chain()), *ir.CHECK_GRID)
+    assert n == 0 and m > 0.1
+    n, m = chain_check([ir.strong_lattice(ir.FOLDED_FRAC)], *ir.CHECK_GRID)
+    assert n > 10000 and m < -1
+
+
+def test_oracle_inverse_on_a_strong_lattice():
+    ir.check_strong(chain_apply)
+
+
+def test_oracle_inverse_composes_link_by_link():
+    from frog_amd.chain import invert
+    inv = invert(list(ir.pyramid_chain()))
+    p, x = ir.check_stages(chain_apply, inv)
+    ir.check_round_trip(p, x)
+
+
+def test_oracle_inverse_jacobian_is_the_inverse_at_the_returned_point():
+    from field_restate import node_list
+    from frog_amd.chain import invert
+    inv = invert(list(ir.pyramid_chain()))
+    nodes = node_list(*ir.JACOBIAN_GRID)
+    x, J = chain_apply(inv, nodes, jacobian=True)
+    det = np.linalg.det(J)
+    F = ir.stage_jacobian(chain_apply, inv, nodes)
+    assert np.abs(J @ F - np.eye(3)).max() < 1e-9                    # the whole matrix, not only its determinant
+    assert np.abs(det * np.linalg.det(F) - 1).max() < 1e-9
+    n, m = chain_check(inv, *ir.JACOBIAN_GRID)
+    assert n == 0 and abs(m - det.min()) <= 1e-12 * det.min()      # chain_check's cofactor expansion against LAPACK's
+    assert np.array_equal(x, chain_apply(inv, nodes))
+
+
+def test_oracle_inverse_on_a_folded_lattice_ends_at_a_better_point():
+    ir.check_folded(chain_apply)          # the share of unsolved points included: at most 5 %
+
+
+def test_oracle_inverse_of_non_finite_points():
+    """A non-finite coordinate comes back NaN; through one lattice the other two coordinates come back unchanged (no tap
+    is read on the axis, so d = 0 and the first guess is the point itself, which is also the fallback)."""
+    from frog_amd.chain import invert
+    pts = ir.non_finite_points()
+    bad = ~np.isfinite(pts)
+    assert (bad.sum(1) == 1).all()
+    out = chain_apply([ir.inverse_link(ir.strong_lattice(ir.STRONG_FRAC))], pts)
+    assert np.array_equal(np.isnan(out), bad) and np.array_equal(out[~bad], pts[~bad])
+    out = chain_apply(invert(list(ir.pyramid_chain())), pts)
+    assert np.isnan(out).all()              # the inverted matrix mixes the coordinates
