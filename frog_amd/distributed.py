@@ -22,7 +22,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi
+from . import _abi, schedule
 from ._abi import check
 
 
@@ -551,44 +551,20 @@ class ShardedImageGroup:
             return r
         return self._dist.get_global_rank(self.group, r)
 
-    # -- run(), imageGroup.cxx:31-157 ------------------------------------------------
+    # -- run(), imageGroup.cxx:31-157: the loops are frog_amd.schedule's ----------------
+    def _on(self, tag, sides, e=None, infos=None):
+        k = schedule.kind(tag)
+        if k in ("linear", "deformable"):
+            self.measures.append(float(np.float32(e[0])))
+        if k == "deformable":
+            self.lattices[-1]["iterations"] += 1
+
     def run(self):
         self.measures, self.gridsPerLevel = [], []
-        self.setupLinearTransforms()
-        self.transformPoints()
-        for it in range(self.linearIterations):
-            if it % self.statIntervalUpdate == 0:
-                self.updateStats()
-            e = self.updateLinearTransforms()
-            self.transformPoints()
-            self.measures.append(float(np.float32(e)))
-        self.transformPoints(True)
-        for level in range(self.deformableLevels):
-            self.gridsPerLevel.append(self.run_level(level, self.deformableIterations))
+        self.gridsPerLevel = schedule.run([self], self.linearIterations, [self.deformableIterations] * self.deformableLevels,
+                                          self.statIntervalUpdate, self.deformableAlpha, self._on)
         return self.measures
 
     def run_level(self, level, iterations):
-        """One deformable level with the regrid / alpha-halving state machine (:78-128)."""
-        self.setupDeformableTransforms(level)
-        self.transformPoints()
-        n_grids, alpha, n_diffeo, it = 1, np.float32(self.deformableAlpha), 0, 0
-        while it < iterations:
-            if it % self.statIntervalUpdate == 0:
-                self.updateStats()
-            e = self.updateDeformableTransforms(float(alpha))
-            if e < 0:
-                if n_diffeo == 0:
-                    alpha = np.float32(alpha / np.float32(2))
-                n_grids += 1
-                self.transformPoints(True)
-                self.setupDeformableTransforms(level)
-                self.transformPoints()
-                n_diffeo = 0
-                continue
-            n_diffeo += 1
-            self.transformPoints()
-            self.measures.append(float(np.float32(e)))
-            self.lattices[-1]["iterations"] += 1
-            it += 1
-        self.transformPoints(True)
-        return n_grids
+        """One deformable level with the regrid / alpha-halving state machine (:78-128); returns the lattices made."""
+        return schedule.run_level([self], level, iterations, self.statIntervalUpdate, self.deformableAlpha, self._on)

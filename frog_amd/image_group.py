@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi
+from . import _abi, schedule
 from ._abi import check
 
 
@@ -133,45 +133,19 @@ class ImageGroup:
         check(self._lib.frog_profile_read(self._ctx, arr, int(reset)), "frog_profile_read")
         return {n: (arr[i].ms_total, arr[i].launches) for i, n in enumerate(_abi.FROG_K_NAMES)}
 
-    # -- run(), imageGroup.cxx:31-157 (no fixed images, no landmarks) ------------------
+    # -- run(), imageGroup.cxx:31-157 (no fixed images, no landmarks): the loops are frog_amd.schedule's -------------
     def run(self, log=None):
         say = log if log else (lambda *_: None)
         self.measures = []
         self.gridsPerLevel = []
-        self.setupLinearTransforms()
-        self.transformPoints()
-        say("Linear registration")
-        for it in range(self.linearIterations):
-            if it % self.statIntervalUpdate == 0:
-                self.updateStats()
-            e = self.updateLinearTransforms()
-            self.transformPoints()
-            self._measure(e, say)
-        self.transformPoints(True)
-        for level in range(self.deformableLevels):
-            self.setupDeformableTransforms(level)
-            self.transformPoints()
-            n_grids, alpha, n_diffeo = 1, np.float32(self.deformableAlpha), 0
-            it = 0
-            while it < self.deformableIterations:
-                if it % self.statIntervalUpdate == 0:
-                    self.updateStats()
-                e = self.updateDeformableTransforms(float(alpha))
-                if e < 0:
-                    if n_diffeo == 0:
-                        alpha = np.float32(alpha / np.float32(2))
-                    n_grids += 1
-                    self.transformPoints(True)
-                    self.setupDeformableTransforms(level)
-                    self.transformPoints()
-                    n_diffeo = 0
-                    continue                      # same iteration index is replayed (:108-113)
-                n_diffeo += 1
-                self.transformPoints()
-                self._measure(e, say)
-                it += 1
-            self.gridsPerLevel.append(n_grids)
-            self.transformPoints(True)
+
+        def on(tag, sides, e=None, infos=None):
+            if tag == "init":
+                say("Linear registration")
+            elif schedule.kind(tag) in ("linear", "deformable"):
+                self._measure(e[0], say)
+        self.gridsPerLevel = schedule.run([self], self.linearIterations, [self.deformableIterations] * self.deformableLevels,
+                                          self.statIntervalUpdate, self.deformableAlpha, on)
         return self.measures
 
     def _measure(self, e, say):

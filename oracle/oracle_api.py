@@ -259,6 +259,17 @@ class OracleGroup:
     def deformable_step(self, alpha):
         return self.L.frogo_deformable_step(self.h, alpha)
 
+    # the reference's names for the six calls above: an oracle is a side of frog_amd.schedule as it stands
+    setupLinearTransforms = linear_init
+    transformPoints = transform_points
+    updateStats = update_stats
+    updateLinearTransforms = linear_step
+    updateDeformableTransforms = deformable_step
+
+    def setupDeformableTransforms(self, level):
+        from frog_amd import _abi
+        return self.deformable_setup(level, _abi.FrogGridInfo())
+
     def error_map(self, image, n_cp):
         out = np.empty((n_cp, 4), np.float32)
         rc = self.L.frogo_error_map(self.h, image, out.ctypes.data_as(fp), out.size)

@@ -4,13 +4,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import numpy as np
 from frog_amd.pairs import Pairs
-import test_gpu_reference_order as T
+from frog_amd import schedule
+from gpu_util import Side
 
 pairs = Pairs.synthetic(500, 20000, 16667, seed=1, partners_per_image=60)
 os.environ["FROG_REFERENCE_ORDER"] = "1"
-ref = T.Side(pairs)
+ref = Side(pairs)
 del os.environ["FROG_REFERENCE_ORDER"]
-fast = T.Side(pairs)
+fast = Side(pairs)
 po = np.asarray(pairs.point_offset)
 
 
@@ -51,6 +52,6 @@ def check(tag, sides, e=None, infos=None):
 
 
 try:
-    T.lockstep([fast, ref], 20, 5, 40, check)
+    schedule.run([fast, ref], 20, [40] * 5, on=check)
 except Stop:
     pass

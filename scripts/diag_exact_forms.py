@@ -6,6 +6,8 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from frog_amd.pairs import Pairs
+from frog_amd import schedule
+from gpu_util import Side
 import test_gpu_reference_order as T
 
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -15,9 +17,9 @@ else:
     pairs, images, default = Pairs.synthetic(100, 20000, 10101, seed=1), list(range(0, 100, 9)), [10, 3, 12]
 li, dl, di = ([int(x) for x in argv[:3]] + default[len(argv):])[:3]
 os.environ["FROG_REFERENCE_ORDER"] = "1"
-fast = T.Side(pairs)
+fast = Side(pairs)
 os.environ["FROG_REF_LITERAL"] = "1"
-lit = T.Side(pairs)
+lit = Side(pairs)
 del os.environ["FROG_REF_LITERAL"], os.environ["FROG_REFERENCE_ORDER"]
 counters = {"steps": 0}
 inner = T.equality_checker(images, counters)
@@ -42,5 +44,5 @@ def check(tag, sides, e=None, infos=None):
         print(tag, "equal", e, flush=True)
 
 
-T.lockstep([fast, lit], li, dl, di, check)
+schedule.run([fast, lit], li, [di] * dl, on=check)
 print("equal over the whole schedule", counters)

@@ -10,15 +10,16 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import numpy as np
 from frog_amd.pairs import Pairs
-import test_gpu_reference_order as T
+from frog_amd import schedule
+from gpu_util import Side
 
 n_images = int(sys.argv[1]) if len(sys.argv) > 1 else 40
 li, dl, di = (int(v) for v in sys.argv[2:5]) if len(sys.argv) > 4 else (20, 5, 12)
 pairs = Pairs.synthetic(n_images, 20000, 16667, seed=2, partners_per_image=20)
 os.environ["FROG_REFERENCE_ORDER"] = "1"
-ref = T.Side(pairs)
+ref = Side(pairs)
 del os.environ["FROG_REFERENCE_ORDER"]
-fast = T.Side(pairs)
+fast = Side(pairs)
 po = np.asarray(pairs.point_offset)
 
 
@@ -84,4 +85,4 @@ def check(tag, sides, e=None, infos=None):
           f"max |dc| on them {worst_in:.3e}, elsewhere {worst_out:.3e} ({n_big_out} beyond 1e-3), max |c| {scale:.3e}", flush=True)
 
 
-T.lockstep([fast, ref], li, dl, di, check)
+schedule.run([fast, ref], li, [di] * dl, on=check)

@@ -4,14 +4,15 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import numpy as np
 from frog_amd.pairs import Pairs
-import test_gpu_reference_order as T
+from frog_amd import schedule
+from gpu_util import Side
 from lattice_util import lattice_taps
 
 pairs = Pairs.synthetic(40, 20000, 16667, seed=2, partners_per_image=20)
 os.environ["FROG_REFERENCE_ORDER"] = "1"
-ref = T.Side(pairs)
+ref = Side(pairs)
 del os.environ["FROG_REFERENCE_ORDER"]
-fast = T.Side(pairs)
+fast = Side(pairs)
 po = np.asarray(pairs.point_offset)
 n_it = int(sys.argv[1]) if len(sys.argv) > 1 else 4
 
@@ -58,6 +59,6 @@ def check(tag, sides, e=None, infos=None):
 
 
 try:
-    T.lockstep([fast, ref], 20, 5, 12, check)
+    schedule.run([fast, ref], 20, [12] * 5, on=check)
 except Stop:
     pass

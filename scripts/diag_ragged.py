@@ -5,7 +5,7 @@ import numpy as np
 from frog_amd import _abi
 from frog_amd.image_group import ImageGroup
 from oracle.oracle_api import OracleGroup
-from test_gpu_parity import ragged_pairs
+from gpu_util import ragged_pairs
 pairs = ragged_pairs()
 opt = dict(stats_max_size=500)
 g = ImageGroup(pairs, **opt); ref = OracleGroup(pairs.model, _abi.FrogOptions.default(**opt)); ref.setup_stats()

@@ -6,15 +6,16 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import numpy as np
 from frog_amd.pairs import Pairs
-import test_gpu_reference_order as T
+from frog_amd import schedule
+from gpu_util import Side
 
 a = [int(x) for x in sys.argv[1:]] or [6, 3000, 1500, 50, 3, 200]
 # optional 7th argument: partner images per image (0 = every image pair), 8th: seed
 pairs = Pairs.synthetic(a[0], a[1], a[2], seed=(a[7] if len(a) > 7 else 7), partners_per_image=(a[6] if len(a) > 6 else 0))
 os.environ["FROG_REFERENCE_ORDER"] = "1"
-ref = T.Side(pairs)
+ref = Side(pairs)
 del os.environ["FROG_REFERENCE_ORDER"]
-fast = T.Side(pairs)
+fast = Side(pairs)
 prev = [0.0]
 def check(tag, sides, e=None, infos=None):
     if e is None or tag[0] == "step" or e[0] < 0:
@@ -30,4 +31,4 @@ def check(tag, sides, e=None, infos=None):
         census = {i: c for i, c in enumerate(census) if c}
     print(tag, f"dE {de:.2e} max|dxyz2| {dx:.2e} mm census diff {census}{flag}", flush=True)
     prev[0] = de
-T.lockstep([fast, ref], a[3], a[4], a[5], check)
+schedule.run([fast, ref], a[3], [a[5]] * a[4], on=check)

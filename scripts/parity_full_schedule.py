@@ -17,16 +17,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np                                               # noqa: E402
 
-from frog_amd import _abi                                        # noqa: E402
+from frog_amd import _abi, schedule                              # noqa: E402
 from frog_amd.image_group import ImageGroup                      # noqa: E402
 from frog_amd.pairs import Pairs                                 # noqa: E402
 from oracle.oracle_api import OracleGroup                        # noqa: E402
 from lattice_util import lattice_deviation, node_weights        # noqa: E402
-
-
-def relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30))
+from gpu_util import relerr                                      # noqa: E402
 
 
 def main():
@@ -40,53 +36,28 @@ def main():
     ref = OracleGroup(pairs.model, _abi.FrogOptions.default())
     ref.setup_stats()
     po = np.asarray(pairs.point_offset)
-    g.setupLinearTransforms(); ref.linear_init()
-    g.transformPoints(); ref.transform_points()
-    e_dev, e_ref = [], []
-    for it in range(li):
-        if it % 10 == 0:
-            g.updateStats(); ref.update_stats()
-        e_dev.append(g.updateLinearTransforms()); e_ref.append(ref.linear_step())
-        g.transformPoints(); ref.transform_points()
-        if it % 10 == 9:
-            print(f"[{time.time() - t0:6.0f}s] linear {it + 1}/{li}  E {e_dev[-1]:.6f} / {e_ref[-1]:.6f}", flush=True)
-    worst_m = 0.0
-    for i in range(pairs.n_images):
-        m, mr = g.matrix(i), ref.matrix(i)
-        worst_m = max(worst_m, relerr(np.diag(m)[:3], np.diag(mr)[:3]), relerr(m[:3, 3], mr[:3, 3]))
-    g.transformPoints(True); ref.transform_points(True)
-    snapshots, levels, grids, rejects = [], [], [], 0
-    for level in range(dl):
-        def setup():
-            info = g.setupDeformableTransforms(level)
-            rinfo = ref.deformable_setup(level, _abi.FrogGridInfo())
-            assert list(info.dims) == list(rinfo.dims), f"lattice dimensions differ at level {level}"
-            snapshots.append(ref.xyz().copy()); levels.append(level)
-            g.transformPoints(); ref.transform_points()
-        setup()
-        alpha, nd, it, n_g = np.float32(0.02), 0, 0, 1
-        while it < di:
-            if it % 10 == 0:
-                g.updateStats(); ref.update_stats()
-            e, er = g.updateDeformableTransforms(float(alpha)), ref.deformable_step(float(alpha))
-            assert (e < 0) == (er < 0), f"guard decisions differ at level {level}, iteration {it}"
-            if e < 0:
-                rejects += 1
-                if nd == 0:
-                    alpha = np.float32(alpha / np.float32(2))
-                n_g += 1
-                g.transformPoints(True); ref.transform_points(True)
-                setup()
-                nd = 0
-                continue
-            nd += 1
-            g.transformPoints(); ref.transform_points()
-            e_dev.append(e); e_ref.append(er)
-            it += 1
-            if it % 25 == 0:
-                print(f"[{time.time() - t0:6.0f}s] level {level} iteration {it}/{di}  lattices {n_g}  E {e:.6f} / {er:.6f}", flush=True)
-        grids.append(n_g)
-        g.transformPoints(True); ref.transform_points(True)
+    e_dev, e_ref, snapshots, levels, count = [], [], [], [], {"rejects": 0, "matrices": 0.0}
+
+    def on(tag, sides, e=None, infos=None):
+        kind = schedule.kind(tag)
+        if kind in ("linear", "deformable"):
+            e_dev.append(e[0]); e_ref.append(e[1])
+            it = tag[-1] + 1
+            if kind == "linear" and it % 10 == 0:
+                print(f"[{time.time() - t0:6.0f}s] linear {it}/{li}  E {e[0]:.6f} / {e[1]:.6f}", flush=True)
+            if kind == "deformable" and it % 25 == 0:
+                print(f"[{time.time() - t0:6.0f}s] level {tag[1]} iteration {it}/{di}  lattices so far {len(levels)}  E {e[0]:.6f} / {e[1]:.6f}", flush=True)
+        elif kind == "linear_done":
+            for i in range(pairs.n_images):
+                m, mr = g.matrix(i), ref.matrix(i)
+                count["matrices"] = max(count["matrices"], relerr(np.diag(m)[:3], np.diag(mr)[:3]), relerr(m[:3, 3], mr[:3, 3]))
+        elif kind == "setup":
+            assert list(infos[0].dims) == list(infos[1].dims), f"lattice dimensions differ at level {tag[1]}"
+            snapshots.append(ref.xyz().copy()); levels.append(tag[1])
+        elif kind == "step" and e[0] < 0:
+            count["rejects"] += 1
+    grids = schedule.run([g, ref], li, [di] * dl, on=on)
+    rejects, worst_m = count["rejects"], count["matrices"]
     e_dev, e_ref = np.array(e_dev), np.array(e_ref)
     res = {"workload": f"100 images x 20000 keypoints, {pairs.n_half_links} half-links, -li {li} -dl {dl} -di {di}",
            "iterations": int(len(e_dev)), "guard_rejections": rejects, "grids_per_level": grids,

@@ -8,7 +8,7 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from frog_amd.pairs import Pairs
-import test_gpu_reference_order as T
+from gpu_util import fast_against_reference_order
 
 
 class Env:                       # the two calls of monkeypatch the test helper uses
@@ -29,7 +29,7 @@ else:
     pairs = Pairs.synthetic(100, 20000, 10101, seed=1)
     images = range(0, 100, 9)
 t0 = time.time()
-r = T.fast_against_reference_order(pairs, li, dl, di, Env(), images)
+r = fast_against_reference_order(pairs, li, dl, di, Env(), images)
 r["seconds"] = time.time() - t0
 r["schedule"] = {"li": li, "dl": dl, "di": di}
 r["workload"] = "%d images x 20 000 keypoints, %d half-links" % (pairs.n_images, pairs.n_half_links)

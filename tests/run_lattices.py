@@ -8,11 +8,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from frog_amd import schedule               # noqa: E402
 from frog_amd.pairs import Pairs            # noqa: E402
-import test_gpu_reference_order as T        # noqa: E402
+from gpu_util import Side                   # noqa: E402
 
 pairs = Pairs.synthetic(6, 3000, 1500, seed=7)
-s = T.Side(pairs)
+s = Side(pairs)
 energies = []
 
 
@@ -21,7 +22,7 @@ def check(tag, sides, e=None, infos=None):
         energies.append(float(e[0]))
 
 
-grids = T.lockstep([s], 8, 3, 12, check)
+grids = schedule.run([s], 8, [12] * 3, on=check)
 out = {"xyz2": s.xyz2(), "E": np.array(energies), "grids": np.array(grids)}
 for k in range(s.num_grids()):
     out[f"lattice{k}"] = np.stack([s.grid(i, k)[1] for i in range(pairs.n_images)])

@@ -9,18 +9,14 @@ import subprocess
 import numpy as np
 import pytest
 
-from frog_amd import _abi
+from frog_amd import _abi, schedule
 from frog_amd.pairs import Pairs
 from oracle.oracle_api import OracleGroup
+from gpu_util import _compare_runs, relerr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REL = 1e-4
-
-
-def relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30)
 
 
 def test_cli_outputs_match_oracle(tmp_path, small_pairs):
@@ -31,30 +27,19 @@ def test_cli_outputs_match_oracle(tmp_path, small_pairs):
     assert "Linear registration" in r.stdout and "Total time" in r.stdout and "half pairs" in r.stdout
 
     ref = OracleGroup(small_pairs.model, _abi.FrogOptions.default())
-    # histograms_linear.csv is written before the deformable stage: replay run() by hand
-    ref.setup_stats(); ref.linear_init(); ref.transform_points()
-    E = []
-    for it in range(20):
-        if it % 10 == 0:
-            ref.update_stats()
-        E.append(ref.linear_step()); ref.transform_points()
-    ref.transform_points(True)
-    hist_lin = [ref.histogram(i) for i in range(small_pairs.n_images)]
-    for level in range(2):
-        ref.deformable_setup(level, _abi.FrogGridInfo()); ref.transform_points()
-        alpha, nd, it = np.float32(0.02), 0, 0
-        while it < 15:
-            if it % 10 == 0:
-                ref.update_stats()
-            e = np.float32(ref.deformable_step(float(alpha)))
-            if e < 0:
-                if nd == 0:
-                    alpha = np.float32(alpha / np.float32(2))
-                ref.transform_points(True); ref.deformable_setup(level, _abi.FrogGridInfo()); ref.transform_points()
-                nd = 0
-                continue
-            nd += 1; ref.transform_points(); E.append(float(e)); it += 1
-        ref.transform_points(True)
+    # histograms_linear.csv is written before the deformable stage: taken at the driver's "linear_done"
+    ref.setup_stats()
+    E, hist_lin = [], []
+
+    def on(tag, sides, e=None, infos=None):
+        kind = schedule.kind(tag)
+        if kind == "linear":
+            E.append(e[0])
+        elif kind == "linear_done":
+            hist_lin.extend(ref.histogram(i) for i in range(small_pairs.n_images))
+        elif kind == "deformable":
+            E.append(float(np.float32(e[0])))
+    schedule.run([ref], 20, [15] * 2, on=on)
 
     rows = list(csv.reader(open(tmp_path / "measures.csv")))
     assert rows[0] == ["Iteration", " E", " landmarkAv", " landmarkMax", " landmarkSTD"]
@@ -431,24 +416,6 @@ def _run_frog(cwd, *flags, env=None):
                        cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return r.stdout
-
-
-def _compare_runs(a, b, n_images, tol=1e-6):
-    ea = np.array([float(x[1]) for x in list(csv.reader(open(a / "measures.csv")))[1:]])
-    eb = np.array([float(x[1]) for x in list(csv.reader(open(b / "measures.csv")))[1:]])
-    assert len(ea) == len(eb) and np.max(np.abs(ea - eb) / eb) < 1e-5       # six printed digits
-    for i in range(n_images):
-        ta = json.load(open(a / "transforms" / f"{i}.json"))["transforms"]
-        tb = json.load(open(b / "transforms" / f"{i}.json"))["transforms"]
-        assert len(ta) == len(tb)
-        assert relerr(ta[0]["matrix"], tb[0]["matrix"]) < tol
-        for x, y in zip(ta[1:], tb[1:]):
-            assert x["dimensions"] == y["dimensions"] and relerr(x["coeffs"], y["coeffs"]) < 10 * tol
-    ba, bb = json.load(open(a / "bbox.json")), json.load(open(b / "bbox.json"))
-    assert ba["halfPairs"] == bb["halfPairs"] and abs(ba["inliers"] - bb["inliers"]) <= 2
-    assert relerr(ba["bbox"], bb["bbox"]) < tol
-    ha = list(csv.reader(open(a / "histograms.csv"))); hb = list(csv.reader(open(b / "histograms.csv")))
-    assert ha[0] == hb[0] and len(ha) == len(hb)
 
 
 def test_cli_sharded_over_three_contexts_on_one_gpu(tmp_path, small_pairs):

@@ -26,21 +26,10 @@ from frog_amd.pairs import Pairs
 from oracle.oracle_api import OracleGroup
 from nifti_util import read_nifti
 from lattice_util import lattice_taps
+from gpu_util import note, relerr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30))
-
-
-def note(name, value):
-    d = os.path.join(ROOT, "gpurun_out")
-    if os.path.isdir(d):
-        with open(os.path.join(d, "test_numbers.txt"), "a") as fh:
-            fh.write(f"{name} {value}\n")
 
 
 def moved_keypoints(n_images, n_points, seed):

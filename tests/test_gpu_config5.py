@@ -9,17 +9,13 @@ an oversize step without touching the state, the culling list leaves the false m
 import numpy as np
 import pytest
 
-from frog_amd import _abi
+from frog_amd import _abi, schedule
 from frog_amd.image_group import ImageGroup
 from frog_amd.pairs import Pairs
 from oracle.oracle_api import OracleGroup
+from gpu_util import relerr
 
 pytestmark = pytest.mark.gpu
-
-
-def relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30))
 
 
 def test_config5_on_one_gpu():
@@ -54,46 +50,39 @@ def test_config5_on_one_gpu():
     g.transformPoints(True)
     c0 = g.countInliers()
     assert sum(c.pairs for c in c0) == pairs.n_half_links
-    grids_per_level = []
+    state, e_level = {}, []           # the current lattice's info, the level's accepted energies
+
+    def on(tag, sides, e=None, infos=None):
+        kind = schedule.kind(tag)
+        if kind == "setup":
+            state["info"] = infos[0]
+        elif kind == "deformable":
+            e_level.append(e[0])
+        elif kind == "level_done":
+            level, info = tag[1], state["info"]
+            assert all(np.isfinite(e_level)) and e_level[-1] <= e_level[0]
+            if level <= 1:
+                # zero cross-image mean, all 500 images (small lattices only: the finest is 12 MB per image)
+                k = g.num_grids() - 1
+                tot, mx = None, 0.0
+                for i in range(pairs.n_images):
+                    c = g.grid(i, k)[1].astype(np.float64)
+                    tot = c if tot is None else tot + c
+                    mx = max(mx, float(np.max(np.abs(c))))
+                assert np.max(np.abs(tot)) <= 1e-5 * max(mx, 1e-3) * pairs.n_images
+            if level == 4:
+                n_cp = info.dims[0] * info.dims[1] * info.dims[2]
+                assert n_cp > 2e5                                        # the HBM-bound stress: a lattice of ~1e6 control points per image
+                # the guard: an absurd step is rejected and leaves the state alone (imageGroup.cxx:434-439)
+                before = g.grid(7, g.num_grids() - 1)[1].copy()
+                x_before = g.points()[1][:1000].copy()
+                assert g.updateDeformableTransforms(1e4) == -1.0
+                g.transformPoints()
+                assert np.array_equal(g.grid(7, g.num_grids() - 1)[1], before)
+                assert np.array_equal(g.points()[1][:1000], x_before)
     for level in range(5):
-        info = g.setupDeformableTransforms(level)
-        g.transformPoints()
-        alpha, n_grids, nd, it = np.float32(0.02), 1, 0, 0
-        e_level = []
-        while it < 3:
-            if it % 10 == 0:
-                g.updateStats()
-            e = g.updateDeformableTransforms(float(alpha))
-            if e < 0:
-                if nd == 0:
-                    alpha = np.float32(alpha / np.float32(2))
-                n_grids += 1
-                g.transformPoints(True); info = g.setupDeformableTransforms(level); g.transformPoints()
-                nd = 0
-                continue
-            nd += 1; g.transformPoints(); e_level.append(e); it += 1
-        assert all(np.isfinite(e_level)) and e_level[-1] <= e_level[0]
-        grids_per_level.append(n_grids)
-        if level <= 1:
-            # zero cross-image mean, all 500 images (small lattices only: the finest is 12 MB per image)
-            k = g.num_grids() - 1
-            tot, mx = None, 0.0
-            for i in range(pairs.n_images):
-                c = g.grid(i, k)[1].astype(np.float64)
-                tot = c if tot is None else tot + c
-                mx = max(mx, float(np.max(np.abs(c))))
-            assert np.max(np.abs(tot)) <= 1e-5 * max(mx, 1e-3) * pairs.n_images
-        if level == 4:
-            n_cp = info.dims[0] * info.dims[1] * info.dims[2]
-            assert n_cp > 2e5                                        # the HBM-bound stress: a lattice of ~1e6 control points per image
-            # the guard: an absurd step is rejected and leaves the state alone (imageGroup.cxx:434-439)
-            before = g.grid(7, g.num_grids() - 1)[1].copy()
-            x_before = g.points()[1][:1000].copy()
-            assert g.updateDeformableTransforms(1e4) == -1.0
-            g.transformPoints()
-            assert np.array_equal(g.grid(7, g.num_grids() - 1)[1], before)
-            assert np.array_equal(g.points()[1][:1000], x_before)
-        g.transformPoints(True)
+        e_level.clear()
+        schedule.run_level([g], level, 3, 10, 0.02, on)
     c1 = g.countInliers()
     assert sum(c.pairs for c in c1) == pairs.n_half_links
     # every point was scattered through the LDS tile of the brick it was sorted into (round 2 found a launch past 2^32

@@ -13,14 +13,10 @@ from frog_amd import _abi
 from frog_amd.image_group import ImageGroup
 from frog_amd.pairs import Pairs
 from oracle.oracle_api import OracleGroup
+from gpu_util import relerr
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
-
-
-def relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30)
 
 
 def test_config2_linear_only_against_oracle():

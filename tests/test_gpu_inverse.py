@@ -3,7 +3,7 @@ lattices, against tests/inverse_restate.py: a NumPy restatement of the forward l
 oracle's restatement of the same algorithm.  tests/test_chain.py makes the same assertions of the oracle.
 
 The figures worth keeping (the device's distance to the oracle, its unsolved share on the folded lattice) are kept
-as inverse_* where test_gpu_match.note keeps a GPU run's numbers: recorded, not asserted.  See DESIGN.md, "Inverse chains and volume reslicing"."""
+as inverse_* where gpu_util.note keeps a GPU run's numbers: recorded, not asserted.  See DESIGN.md, "Inverse chains and volume reslicing"."""
 import numpy as np
 import pytest
 
@@ -11,12 +11,12 @@ import inverse_restate as ir
 from field_restate import node_list
 from frog_amd.chain import Chain, invert
 from oracle.oracle_api import chain_apply
-from test_gpu_match import note as record
+from gpu_util import note as record
 
 pytestmark = pytest.mark.gpu
 
 
-def note(name, value):
+def keep(name, value):
     record("inverse_" + name, value)
 
 
@@ -29,16 +29,16 @@ def device_apply(links, points):
 
 
 def test_strong_lattice_converges_onto_the_root():
-    x = ir.check_strong(device_apply, note)
+    x = ir.check_strong(device_apply, keep)
     link, p = ir.strong_lattice(ir.STRONG_FRAC), ir.sample_points(5)
     apart = np.linalg.norm(x - chain_apply([ir.inverse_link(link)], p), axis=1).max()
-    note("strong_max_device_to_oracle", apart)
+    keep("strong_max_device_to_oracle", apart)
     assert apart <= ir.PAIR_DISTANCE        # both within ROOT_DISTANCE of the one root; a shortened point may take another branch
 
 
 def test_inverted_pyramid_is_its_links_one_at_a_time():
     p, x = ir.check_stages(device_apply, invert(list(ir.pyramid_chain())))
-    ir.check_round_trip(p, x, note)
+    ir.check_round_trip(p, x, keep)
 
 
 def test_jacobian_of_the_inverse_is_the_inverse_at_the_returned_point():
@@ -54,13 +54,13 @@ def test_jacobian_of_the_inverse_is_the_inverse_at_the_returned_point():
     assert none is None and disp.tobytes() == only_disp.tobytes()       # chain_point<true> and <false> walk the same points
     assert (x - nodes).tobytes() == disp.tobytes()
     product = det.ravel() * ir.stage_determinant(device_apply, inv, nodes)
-    note("jacobian_max_product_error", np.abs(product - 1).max())
+    keep("jacobian_max_product_error", np.abs(product - 1).max())
     assert np.abs(product - 1).max() < 1e-9
     assert n == 0 and m == det.min()
 
 
 def test_folded_lattice_ends_at_a_point_no_worse_than_the_first_guess():
-    ir.check_folded(device_apply, note)
+    ir.check_folded(device_apply, keep)
 
 
 def test_non_finite_points_return_as_the_oracle_has_them():

@@ -5,17 +5,9 @@ import pytest
 
 from frog_amd.match import Keypoints, Matcher, all_pairs, synthetic_keypoints
 from oracle.oracle_api import match_run
+from gpu_util import note
 
 pytestmark = pytest.mark.gpu
-
-
-def note(name, value):
-    """Numbers worth keeping from a GPU run (gpurun_out/test_numbers.txt travels back with the call)."""
-    import os
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    if os.path.isdir(d):
-        with open(os.path.join(d, "test_numbers.txt"), "a") as fh:
-            fh.write(f"{name} {value}\n")
 
 
 def same(got, want):

@@ -13,6 +13,7 @@ from frog_amd import _abi
 from frog_amd.image_group import ImageGroup
 from oracle.oracle_api import OracleGroup
 from lattice_util import compare_lattice, node_weights
+from gpu_util import ragged_pairs, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +27,6 @@ def make(pairs, setup_stats=True, **opt):
     if setup_stats:                     # OracleGroup.run() does it itself, like ImageGroup::run
         ref.setup_stats()
     return g, ref
-
-
-def relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30)
 
 
 def same_inputs(g, ref):
@@ -210,40 +206,6 @@ def test_full_run_parity(small_pairs):
             assert list(info.dims) == list(rinfo.dims)
             assert relerr(c, rc) < REL, f"lattice {k} image {i}"
     assert relerr(g.points()[0], ref.xyz()) < REL
-
-
-def ragged_pairs(seed=5):
-    """Images of 25 .. 1500 points observing subsets of one landmark cloud: true matches between
-    co-observed landmarks, 25 % false matches, points without any link, one image pair with heavy
-    duplication (400 links of ONE point into the same partner image) and one image pair whose
-    block appears twice in the file."""
-    rng = np.random.default_rng(seed)
-    sizes = [1500, 25, 700, 40, 1100, 260]
-    po = np.concatenate([[0], np.cumsum(sizes)])
-    cloud = rng.uniform(0, 300, size=(1500, 3))
-    seen = [rng.permutation(1500)[:n] for n in sizes]            # landmark of every point
-    xyz = np.concatenate([(cloud[seen[i]] * rng.uniform(0.9, 1.1, 3) + rng.uniform(-30, 30, 3)
-                           + rng.normal(0, 1.5, (sizes[i], 3))).astype(np.float32) for i in range(len(sizes))])
-    where = []
-    for i in range(len(sizes)):
-        w = -np.ones(1500, np.int64); w[seen[i]] = np.arange(sizes[i]); where.append(w)
-    blocks = []
-    for i in range(len(sizes)):
-        for j in range(i + 1, len(sizes)):
-            both = np.nonzero((where[i] >= 0) & (where[j] >= 0))[0]
-            both = both[rng.random(len(both)) < 0.8]             # some co-observed landmarks stay unlinked
-            p1, p2 = where[i][both], where[j][both]
-            nf = max(2, len(both) // 3)
-            p1 = np.concatenate([p1, rng.integers(0, sizes[i], nf)])
-            p2 = np.concatenate([p2, rng.integers(0, sizes[j], nf)])
-            if (i, j) == (0, 2):
-                p1 = np.concatenate([p1, np.full(400, 7)])       # 400 links of point 7 of image 0 into image 2
-                p2 = np.concatenate([p2, rng.integers(0, 20, 400)])
-            order = np.argsort(p1, kind="stable")
-            blocks.append((i, j, p1[order].astype(np.uint32), p2[order].astype(np.uint32)))
-    blocks.append(blocks[1])                                     # the same image pair appears twice in the file
-    from frog_amd.pairs import Pairs
-    return Pairs.from_arrays(po, xyz, blocks)
 
 
 def test_ragged_group_with_duplicate_links():

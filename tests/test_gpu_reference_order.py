@@ -14,135 +14,25 @@ read-modify-write, the transform without fused multiply-adds.
     displacement field on a DENSE lattice over the group's bounding box (what tools/VolumeTransform.cxx:119-136 samples),
     not only at the keypoints.
 """
-import os
-
 import numpy as np
 import pytest
 
-from frog_amd import _abi
-from frog_amd.image_group import ImageGroup
+from frog_amd import schedule
 from frog_amd.pairs import Pairs
-from oracle.oracle_api import OracleGroup
-from lattice_util import lattice_deviation, node_weights, lattice_taps, face_crossing_nodes
+from gpu_util import Side, fast_against_reference_order, note, ragged_pairs, report
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
 RAW_REL = 1e-3      # raw coefficients, product path vs reference-order mode, levels 0-3 at benchmark sizes: measured <= 2.7e-4 (a ten-fold regression fails)
 
 
-def note(name, value):
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    if os.path.isdir(d):
-        with open(os.path.join(d, "test_numbers.txt"), "a") as fh:
-            fh.write(f"{name} {value}\n")
-
-
-class Side:
-    """One driver interface over the HIP path (ImageGroup) and the oracle (OracleGroup)."""
-
-    def __init__(self, pairs, oracle=False, **opt):
-        self.oracle = oracle
-        self.pairs = pairs
-        self.first = int(opt.get("n_fixed_images", 0))       # -fi: the first images are fixed, the context owns the others
-        if oracle:
-            self.g = OracleGroup(pairs.model, _abi.FrogOptions.default(**opt))
-            self.g.setup_stats()
-            self.g.keep_raw_gradient(True)
-        else:
-            self.g = ImageGroup(pairs, **opt)
-
-    def init(self):
-        (self.g.linear_init if self.oracle else self.g.setupLinearTransforms)()
-
-    def transform(self, apply=False):
-        (self.g.transform_points if self.oracle else self.g.transformPoints)(apply)
-
-    def stats(self):
-        (self.g.update_stats if self.oracle else self.g.updateStats)()
-
-    def linear(self):
-        return self.g.linear_step() if self.oracle else self.g.updateLinearTransforms()
-
-    def setup(self, level):
-        return self.g.deformable_setup(level, _abi.FrogGridInfo()) if self.oracle else self.g.setupDeformableTransforms(level)
-
-    def deformable(self, alpha):
-        return self.g.deformable_step(alpha) if self.oracle else self.g.updateDeformableTransforms(alpha)
-
-    def xyz(self):
-        return self.g.xyz() if self.oracle else self.g.points()[0]
-
-    def xyz2(self):
-        return self.g.xyz2() if self.oracle else self.g.points()[1]
-
-    def matrices(self):
-        return np.stack([self.g.matrix(i) for i in range(self.first, self.pairs.n_images)])
-
-    def ems(self):
-        return np.stack([self.g.em(i) for i in range(self.pairs.n_images)])
-
-    def point_sums(self):
-        return self.g.point_sums()
-
-    def gradient_raw(self, image, n_cp):
-        return self.g.gradient_raw(image, n_cp) if self.oracle else self.g.gradient(image, n_cp)
-
-    def grid(self, image, k):
-        return self.g.grid(image, k, _abi.FrogGridInfo()) if self.oracle else self.g.grid(image, k)
-
-    def num_grids(self):
-        return self.g.num_grids()
-
-
-def lockstep(sides, li, dl, di, check, alpha0=0.02):
-    """ImageGroup::run's schedule (imageGroup.cxx:54-128) on every side, each on its own state; `check(tag, ...)` is called
-    with the sides after every step.  Returns the lattices created per level."""
-    for s in sides: s.init()
-    for s in sides: s.transform()
-    check("init", sides)
-    for it in range(li):
-        if it % 10 == 0:
-            for s in sides: s.stats()
-        e = [s.linear() for s in sides]
-        for s in sides: s.transform()
-        check(("linear", it), sides, e)
-    for s in sides: s.transform(True)
-    grids = []
-    for level in range(dl):
-        def setup():
-            infos = [s.setup(level) for s in sides]
-            for s in sides: s.transform()
-            check(("setup", level), sides, infos=infos)
-        setup()
-        alpha, nd, it, n_g = np.float32(alpha0), 0, 0, 1
-        while it < di:
-            if it % 10 == 0:
-                for s in sides: s.stats()
-            e = [s.deformable(float(alpha)) for s in sides]
-            assert len({x < 0 for x in e}) == 1, f"guard decisions differ at level {level}, iteration {it}: {e}"
-            check(("step", level, it), sides, e)
-            if e[0] < 0:
-                if nd == 0:
-                    alpha = np.float32(alpha / np.float32(2))
-                n_g += 1
-                for s in sides: s.transform(True)
-                setup()
-                nd = 0
-                continue
-            nd += 1
-            for s in sides: s.transform()
-            check(("deformable", level, it), sides, e)
-            it += 1
-        grids.append(n_g)
-        for s in sides: s.transform(True)
-    return grids
-
-
 def equality_checker(images, counters):
     """Every comparable state of two sides, with np.array_equal."""
     def check(tag, sides, e=None, infos=None):
         a, b = sides
-        kind = tag if isinstance(tag, str) else tag[0]
+        kind = schedule.kind(tag)
+        if kind in ("linear_done", "level_done"):
+            return
         if infos is not None:
             for f in ("dims", "origin", "spacing"):
                 assert list(getattr(infos[0], f)) == list(getattr(infos[1], f)), (tag, f)
@@ -175,7 +65,7 @@ def run_equal(pairs, li, dl, di, monkeypatch, images=None, **opt):
     ref = Side(pairs, oracle=True, **opt)
     images = list(images if images is not None else range(dev.first, pairs.n_images))
     counters = {"steps": 0}
-    grids = lockstep([dev, ref], li, dl, di, equality_checker(images, counters))
+    grids = schedule.run([dev, ref], li, [di] * dl, on=equality_checker(images, counters))
     assert dev.num_grids() == ref.num_grids() == sum(grids)
     for k in range(ref.num_grids()):                       # every lattice of the chain, finished ones included
         for i in range(dev.first, pairs.n_images):
@@ -205,124 +95,6 @@ def test_reference_order_mode_equals_the_oracle_config5_shaped(monkeypatch):
 
 
 # ---- the product path against reference-order mode, both on the device --------------------------------------------------
-
-def dense_field_deviation(a, b, k, images, xyz, n_per_axis=24, skip=None):
-    """Displacement of lattice k on both sides on a dense lattice of points over the bounding box of the coordinates the
-    lattice acts on (what a resampler evaluates: tools/VolumeTransform.cxx:119-136), relative to the largest displacement.
-    skip: mask of control points whose difference is left out (tests/lattice_util.py face_crossing_nodes)."""
-    lo, hi = xyz.min(axis=0).astype(np.float64), xyz.max(axis=0).astype(np.float64)
-    axes = [np.linspace(lo[d], hi[d], n_per_axis) for d in range(3)]
-    pts = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1).reshape(-1, 3)
-    worst, scale = 0.0, 0.0
-    for i in images:
-        info, ca = a.grid(i, k)
-        _, cb = b.grid(i, k)
-        idx, wt = lattice_taps(pts, info)
-        diff = ca.astype(np.float64) - cb
-        if skip is not None:
-            diff[skip] = 0.0
-        db = np.einsum("nt,ntk->nk", wt, cb.astype(np.float64)[idx])
-        worst = max(worst, float(np.max(np.abs(np.einsum("nt,ntk->nk", wt, diff[idx])))))
-        scale = max(scale, float(np.max(np.abs(db))))
-    return worst / max(scale, 1e-30), scale
-
-
-class RefAsOracle:
-    """Adapter: a reference-order device side seen through the oracle's getter names (for tests/lattice_util.py)."""
-
-    def __init__(self, side):
-        self.s = side
-        self.n_images = side.pairs.n_images
-
-    def grid(self, image, k, info=None):
-        return self.s.g.grid(image, k)
-
-
-def fast_against_reference_order(pairs, li, dl, di, monkeypatch, images, **opt):
-    monkeypatch.setenv("FROG_REFERENCE_ORDER", "1")
-    ref = Side(pairs, **opt)
-    monkeypatch.delenv("FROG_REFERENCE_ORDER")
-    fast = Side(pairs, **opt)
-    po = np.asarray(pairs.point_offset)
-    snaps, snaps_fast, worst = [], [], {"E": 0.0}
-
-    def check(tag, sides, e=None, infos=None):
-        if infos is not None:
-            assert list(infos[0].dims) == list(infos[1].dims), tag
-            snaps.append(sides[1].xyz().copy())
-            snaps_fast.append(sides[0].xyz().copy())
-        if e is not None and e[0] >= 0 and tag[0] != "step":
-            worst["E"] = max(worst["E"], abs(e[0] - e[1]) / abs(e[1]))
-    grids = lockstep([fast, ref], li, dl, di, check)
-    out = []
-    adapter = RefAsOracle(ref)
-    for k in range(ref.num_grids()):
-        w = node_weights(adapter, k, po, snaps[k])
-        d = {"raw": 0.0, "weighted": 0.0, "field": 0.0}
-        for i in images:
-            r = lattice_deviation(fast.g, adapter, k, i, snaps[k][po[i]:po[i + 1]], w)
-            if r["raw"] >= d["raw"]:
-                d["raw_image"] = int(i)
-                for key in ("raw_node", "raw_node_weight", "raw_node_support", "raw_node_points"):
-                    d[key] = r[key]
-            for key in ("raw", "weighted", "field"):
-                d[key] = max(d[key], r[key])
-            d["weak"], d["nodes"] = r["weak"], r["nodes"]
-        d["dense_field"], d["max_disp"] = dense_field_deviation(fast.g, ref.g, k, images, snaps[k])
-        # control points one of the two runs reaches across a cell face (tests/lattice_util.py): counted, and the same two
-        # numbers without them
-        info = ref.g.grid(0 + ref.first, k)[0]
-        crossing, skip = face_crossing_nodes(snaps_fast[k], snaps[k], info)
-        d["face_crossings"], d["crossing_nodes"] = int(len(crossing)), int(skip.sum())
-        d["raw_elsewhere"], d["dense_field_elsewhere"] = d["raw"], d["dense_field"]
-        if len(crossing):
-            d["raw_elsewhere"], scale = 0.0, 0.0
-            for i in images:
-                ca, cb = fast.g.grid(i, k)[1], ref.g.grid(i, k)[1]
-                d["raw_elsewhere"] = max(d["raw_elsewhere"], float(np.abs(ca.astype(np.float64) - cb)[~skip].max()))
-                scale = max(scale, float(np.abs(cb).max()))
-            d["raw_elsewhere"] /= max(scale, 1e-30)
-            d["dense_field_elsewhere"] = dense_field_deviation(fast.g, ref.g, k, images, snaps[k], skip=skip)[0]
-        out.append(d)
-    # the WHOLE chain of an image (matrix, then every lattice in creation order: what transforms/<i>.json holds and
-    # tools/VolumeTransform.cxx / PointsTransform.cxx evaluate) on a dense lattice of points over the image's own keypoint
-    # box, through the device's chain evaluation (include/frog_chain.h): deviation of the displacement T(x) - x
-    from frog_amd.chain import Chain, Link
-    chain = {"rel": 0.0, "mm": 0.0, "max_disp_mm": 0.0}
-    x0 = np.asarray(pairs.xyz, np.float64).reshape(-1, 3)
-    for i in images:
-        pts_i = x0[po[i]:po[i + 1]]
-        lo, hi = pts_i.min(axis=0), pts_i.max(axis=0)
-        grid = np.stack(np.meshgrid(*[np.linspace(lo[d], hi[d], 20) for d in range(3)], indexing="ij"), axis=-1).reshape(-1, 3)
-        disp = []
-        for side in (fast, ref):
-            links = [Link.linear(side.g.matrix(i))]
-            for k in range(side.num_grids()):
-                info, c = side.g.grid(i, k)
-                links.append(Link.bspline(list(info.dims), list(info.origin), list(info.spacing), c))
-            ch = Chain(links)
-            disp.append(ch.apply(grid) - grid)
-            ch.close()
-        dev = float(np.max(np.abs(disp[0] - disp[1])))
-        scale = float(np.max(np.abs(disp[1])))
-        chain["mm"] = max(chain["mm"], dev); chain["max_disp_mm"] = max(chain["max_disp_mm"], scale)
-        chain["rel"] = max(chain["rel"], dev / max(scale, 1e-30))
-    mf, mr = fast.matrices(), ref.matrices()
-    diag = lambda a: np.stack([a[:, 0, 0], a[:, 1, 1], a[:, 2, 2]])
-    m = max(float(np.max(np.abs(diag(mf) - diag(mr))) / np.max(np.abs(diag(mr)))),
-            float(np.max(np.abs(mf[:, :3, 3] - mr[:, :3, 3])) / np.max(np.abs(mr[:, :3, 3]))))
-    x = float(np.max(np.abs(fast.xyz().astype(np.float64) - ref.xyz())) / np.max(np.abs(ref.xyz())))
-    ca, cb = fast.g.countInliers(), ref.g.countInliers()
-    census = sum(abs(ca[i].inliers - cb[i].inliers) for i in range(pairs.n_images))
-    return {"lattices": out, "grids": grids, "E": worst["E"], "matrices": m, "xyz": x, "census": census, "chain": chain}
-
-
-def report(name, r):
-    note(name, f"E {r['E']:.2e} matrices {r['matrices']:.2e} xyz {r['xyz']:.2e} grids {r['grids']} census_differs_by {r['census']} "
-               f"whole_chain_dense rel {r['chain']['rel']:.2e} abs {r['chain']['mm']:.2e} mm of {r['chain']['max_disp_mm']:.1f} mm")
-    for k, d in enumerate(r["lattices"]):
-        note(f"{name}_lattice_{k}", " ".join(f"{a} {b:.2e}" if isinstance(b, float) else f"{a} {b}" for a, b in d.items()))
-
 
 def test_fast_path_against_reference_order_small_group(monkeypatch):
     """The product path against the mode the tests above hold equal to the CPU oracle, on the same group and schedule
@@ -411,9 +183,8 @@ def test_fast_path_against_reference_order_config5_shaped_long_level4(monkeypatc
 
 def test_reference_order_mode_equals_the_oracle_ragged_group_with_duplicate_links(monkeypatch):
     """Images of 25 .. 1 500 points, points without links, 400 duplicate links of ONE point into one partner image, an image
-    pair whose block appears twice in the file (tests/test_gpu_parity.py ragged_pairs), a reservoir smaller than the link
+    pair whose block appears twice in the file (tests/gpu_util.py ragged_pairs), a reservoir smaller than the link
     count: 12 linear + 2 x 8 deformable iterations, every quantity equal to the oracle's after every step."""
-    from test_gpu_parity import ragged_pairs
     pairs = ragged_pairs()
     grids, counters = run_equal(pairs, 12, 2, 8, monkeypatch, stats_max_size=500)
     assert counters["linear"] == 12 and counters["deformable"] == 16
@@ -443,7 +214,7 @@ def test_reference_order_mode_equals_the_oracle_with_landmark_constraints_and_er
     ref = Side(pairs, oracle=True)
     dev.g.set_hard_links(point, partner, w2); ref.g.set_hard_links(point, partner, w2)
     counters = {"steps": 0}
-    lockstep([dev, ref], 12, 2, 6, equality_checker(range(6), counters))
+    schedule.run([dev, ref], 12, [6] * 2, on=equality_checker(range(6), counters))
     assert counters["deformable"] == 12
     dev.g.residualSums()
     info = dev.grid(0, dev.num_grids() - 1)[0]

@@ -4,31 +4,18 @@ cases, certified outlier culling bit-identical to the full sweep, and the layout
 listed (more than 2048 images, shuffled block order, a context that owns only empty images).
 All through the C ABI (include/frog_hip.h)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-from frog_amd import _abi
+from frog_amd import _abi, schedule
 from frog_amd.image_group import ImageGroup, device_inlier_probability, device_inlier_weight_pair
 from frog_amd.pairs import Pairs
 from oracle.oracle_api import OracleGroup, Stats, ref_lib
+from gpu_util import note, relerr
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
-
-
-def relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30))
-
-
-def note(name, value):
-    """Numbers DESIGN.md quotes: appended to gpurun_out/test_numbers.txt when that directory exists."""
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    if os.path.isdir(d):
-        with open(os.path.join(d, "test_numbers.txt"), "a") as fh:
-            fh.write(f"{name} {value}\n")
 
 
 # ---- S4 on the device against the reference build ----------------------------------------------------------
@@ -173,14 +160,7 @@ def lockstep_to_deformable(pairs, iters=20, **opt):
     g = ImageGroup(pairs, **opt)
     ref = OracleGroup(pairs.model, _abi.FrogOptions.default(**opt))
     ref.setup_stats()
-    g.setupLinearTransforms(); ref.linear_init()
-    g.transformPoints(); ref.transform_points()
-    for it in range(iters):
-        if it % 10 == 0:
-            g.updateStats(); ref.update_stats()
-        g.updateLinearTransforms(); ref.linear_step()
-        g.transformPoints(); ref.transform_points()
-    g.transformPoints(True); ref.transform_points(True)
+    schedule.run([g, ref], iters, [])
     return g, ref
 
 
@@ -276,47 +256,19 @@ def test_parity_sweep(case):
     ref = OracleGroup(pairs.model, _abi.FrogOptions.default(**opt))
     ref.setup_stats()
     po = np.asarray(pairs.point_offset)
-    li, dl, di = 50, 3, 40
-    g.setupLinearTransforms(); ref.linear_init()
-    g.transformPoints(); ref.transform_points()
-    worst_e = 0.0
-    for it in range(li):
-        if it % 10 == 0:
-            g.updateStats(); ref.update_stats()
-        e, er = g.updateLinearTransforms(), ref.linear_step()
-        g.transformPoints(); ref.transform_points()
-        worst_e = max(worst_e, abs(e - er) / er)
-    g.transformPoints(True); ref.transform_points(True)
     snapshots = []                      # per lattice: the reference's re-based coordinates it acts on
-    grids, rgrids = [], []
-    for level in range(dl):
-        def setup():
-            g.setupDeformableTransforms(level)
-            ref.deformable_setup(level, _abi.FrogGridInfo())
+    worst = {"E": 0.0}
+
+    def on(tag, sides, e=None, infos=None):
+        kind = schedule.kind(tag)
+        if kind == "setup":
             snapshots.append(ref.xyz().copy())
-            g.transformPoints(); ref.transform_points()
-        setup()
-        alpha, ralpha, nd, rnd_, it, n_g, n_r = np.float32(0.02), np.float32(0.02), 0, 0, 0, 1, 1
-        while it < di:
-            if it % 10 == 0:
-                g.updateStats(); ref.update_stats()
-            e, er = g.updateDeformableTransforms(float(alpha)), ref.deformable_step(float(ralpha))
-            assert (e < 0) == (er < 0), f"guard decisions differ at level {level}, iteration {it}"
-            if e < 0:
-                if nd == 0:
-                    alpha = np.float32(alpha / np.float32(2)); ralpha = alpha
-                n_g += 1; n_r += 1
-                g.transformPoints(True); ref.transform_points(True)
-                setup()
-                nd = 0
-                continue
-            nd += 1
-            g.transformPoints(); ref.transform_points()
-            worst_e = max(worst_e, abs(e - er) / er)
-            it += 1
-        grids.append(n_g); rgrids.append(n_r)
-        g.transformPoints(True); ref.transform_points(True)
-    assert grids == rgrids and g.num_grids() == ref.num_grids() == len(snapshots)
+        elif kind in ("linear", "deformable"):
+            worst["E"] = max(worst["E"], abs(e[0] - e[1]) / e[1])
+    # (the driver asserts at every step that both sides' guards decide alike)
+    schedule.run([g, ref], 50, [40] * 3, on=on)
+    worst_e = worst["E"]
+    assert g.num_grids() == ref.num_grids() == len(snapshots)
     assert worst_e < REL
     for i in range(pairs.n_images):
         m, mr = g.matrix(i), ref.matrix(i)

@@ -11,26 +11,15 @@ import os
 import numpy as np
 import pytest
 
-from frog_amd import _abi
+from frog_amd import _abi, schedule
 from frog_amd.image_group import ImageGroup
 from frog_amd.pairs import Pairs
 from oracle.oracle_api import OracleGroup
 from lattice_util import lattice_deviation, node_weights
+from gpu_util import note, relerr
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
-
-
-def relerr(a, b):
-    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
-    return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30))
-
-
-def note(name, value):
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    if os.path.isdir(d):
-        with open(os.path.join(d, "test_numbers.txt"), "a") as fh:
-            fh.write(f"{name} {value}\n")
 
 
 def free_run(pairs, li, dl, di, images=None, **opt):
@@ -40,49 +29,21 @@ def free_run(pairs, li, dl, di, images=None, **opt):
     ref = OracleGroup(pairs.model, _abi.FrogOptions.default(**opt))
     ref.setup_stats()
     po = np.asarray(pairs.point_offset)
-    g.setupLinearTransforms(); ref.linear_init()
-    g.transformPoints(); ref.transform_points()
-    worst_e = 0.0
-    for it in range(li):
-        if it % 10 == 0:
-            g.updateStats(); ref.update_stats()
-        e, er = g.updateLinearTransforms(), ref.linear_step()
-        g.transformPoints(); ref.transform_points()
-        worst_e = max(worst_e, abs(e - er) / er)
-    worst_m = 0.0
-    for i in range(pairs.n_images):
-        m, mr = g.matrix(i), ref.matrix(i)
-        worst_m = max(worst_m, relerr(np.diag(m)[:3], np.diag(mr)[:3]), relerr(m[:3, 3], mr[:3, 3]))
-    g.transformPoints(True); ref.transform_points(True)
-    snapshots, levels, grids = [], [], []
-    for level in range(dl):
-        def setup():
-            info = g.setupDeformableTransforms(level)
-            rinfo = ref.deformable_setup(level, _abi.FrogGridInfo())
-            assert list(info.dims) == list(rinfo.dims), f"lattice dimensions differ at level {level}"
-            snapshots.append(ref.xyz().copy()); levels.append(level)
-            g.transformPoints(); ref.transform_points()
-        setup()
-        alpha, nd, it, n_g = np.float32(0.02), 0, 0, 1
-        while it < di:
-            if it % 10 == 0:
-                g.updateStats(); ref.update_stats()
-            e, er = g.updateDeformableTransforms(float(alpha)), ref.deformable_step(float(alpha))
-            assert (e < 0) == (er < 0), f"guard decisions differ at level {level}, iteration {it}"
-            if e < 0:
-                if nd == 0:
-                    alpha = np.float32(alpha / np.float32(2))
-                n_g += 1
-                g.transformPoints(True); ref.transform_points(True)
-                setup()
-                nd = 0
-                continue
-            nd += 1
-            g.transformPoints(); ref.transform_points()
-            worst_e = max(worst_e, abs(e - er) / er)
-            it += 1
-        grids.append(n_g)
-        g.transformPoints(True); ref.transform_points(True)
+    snapshots, levels, worst = [], [], {"E": 0.0, "matrices": 0.0}
+
+    def on(tag, sides, e=None, infos=None):
+        kind = schedule.kind(tag)
+        if kind in ("linear", "deformable"):
+            worst["E"] = max(worst["E"], abs(e[0] - e[1]) / e[1])
+        elif kind == "linear_done":
+            for i in range(pairs.n_images):
+                m, mr = g.matrix(i), ref.matrix(i)
+                worst["matrices"] = max(worst["matrices"], relerr(np.diag(m)[:3], np.diag(mr)[:3]), relerr(m[:3, 3], mr[:3, 3]))
+        elif kind == "setup":
+            assert list(infos[0].dims) == list(infos[1].dims), f"lattice dimensions differ at level {tag[1]}"
+            snapshots.append(ref.xyz().copy()); levels.append(tag[1])
+    grids = schedule.run([g, ref], li, [di] * dl, on=on)
+    worst_e, worst_m = worst["E"], worst["matrices"]
     assert g.num_grids() == ref.num_grids() == len(snapshots)
     per_lattice = []
     for k in range(ref.num_grids()):

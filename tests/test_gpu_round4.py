@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from frog_amd import schedule
 from frog_amd.image_group import ImageGroup
 from frog_amd.pairs import Pairs
 
@@ -85,32 +86,13 @@ def test_the_c_loop_and_the_python_loop_end_on_the_same_bits():
     lib.frog_destroy(ctx)
 
     g = ImageGroup(pairs, max_levels_hint=3)
-    g.setupLinearTransforms(); g.transformPoints()
-    it, e = 0, 0.0
-    for _ in range(4 + 11):
-        if it % 10 == 0:
-            g.updateStats()
-        e = g.updateLinearTransforms(); g.transformPoints()
-        it += 1
-    g.transformPoints(True)
-    grids = []
-    for level, n_it in enumerate((14, 13, 12)):
-        g.setupDeformableTransforms(level); g.transformPoints()
-        alpha, nd, k, ng = np.float32(0.02), 0, 0, 1
-        while k < n_it:
-            if k % 10 == 0:
-                g.updateStats()
-            ee = g.updateDeformableTransforms(float(alpha))
-            if ee < 0:
-                if nd == 0:
-                    alpha = np.float32(alpha / np.float32(2))
-                ng += 1
-                g.transformPoints(True); g.setupDeformableTransforms(level); g.transformPoints()
-                nd = 0
-                continue
-            nd += 1; g.transformPoints(); e = ee; k += 1
-        grids.append(ng)
-        g.transformPoints(True)
+    last = {}
+
+    def on(tag, sides, e=None, infos=None):
+        if schedule.kind(tag) in ("linear", "deformable"):
+            last["E"] = e[0]
+    # (the C loop's warm-up iterations count on in its linear stage: one counter, one refresh phase)
+    grids = schedule.run([g], 4 + 11, (14, 13, 12), on=on)
     assert list(res.grids_per_level[:3]) == grids
-    assert float(np.float32(e)) == res.final_E
+    assert float(np.float32(last["E"])) == res.final_E
     assert np.array_equal(g.points()[0], xyz_c)

@@ -6,10 +6,11 @@ import os
 import numpy as np
 import pytest
 
-from frog_amd import _abi
+from frog_amd import _abi, schedule
 from frog_amd.image_group import ImageGroup
 from frog_amd.pairs import Pairs
 from oracle import oracle_api
+from gpu_util import _compare_runs, _frog, _same_files
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -42,29 +43,14 @@ def run_schedule(pairs, monkeypatch, f64, li=6, dl=3, di=8, forms=(None,)):
     """A free-running li + dl x di schedule; returns final coordinates, energies, lattices of image 0."""
     monkeypatch.setenv("FROG_K11_F64", "1" if f64 else "0")
     g = ImageGroup(pairs, device=0)
-    g.setupLinearTransforms(); g.transformPoints()
     E = []
-    for it in range(li):
-        if it % 10 == 0:
-            g.updateStats()
-        E.append(g.updateLinearTransforms()); g.transformPoints()
-    g.transformPoints(True)
-    for level in range(dl):
-        g.setupDeformableTransforms(level); g.transformPoints()
-        alpha, it, first = 0.02, 0, True
-        while it < di:
-            if it % 10 == 0:
-                g.updateStats()
-            e = g.updateDeformableTransforms(alpha)
-            if e < 0:
-                if first:
-                    alpha /= 2
-                g.transformPoints(True); g.setupDeformableTransforms(level); g.transformPoints()
-                first = True
-                continue
-            first = False
-            E.append(e); g.transformPoints(); it += 1
-        g.transformPoints(True)
+
+    def on(tag, sides, e=None, infos=None):
+        if schedule.kind(tag) in ("linear", "deformable"):
+            E.append(e[0])
+    # (this loop used to carry alpha as a Python float: the C ABI takes a float and a halving is exact, so the driver's f32
+    # alpha gives the same bits)
+    schedule.run([g], li, [di] * dl, on=on)
     return g.points()[1].copy(), np.array(E), [g.grid(0, k)[1].copy() for k in range(g.num_grids())]
 
 
@@ -113,24 +99,6 @@ def test_f32_transform_against_the_f64_form(monkeypatch):
 
 # ---- two collectives per deformable iteration (include/frog_hip.h frog_comm_mode) ------------------------------------------
 
-def _frog(cwd, *flags, env_extra=None):
-    import subprocess
-    env = dict(os.environ)
-    env.pop("FROG_THREE_COLLECTIVES", None)
-    env.update(env_extra or {})
-    r = subprocess.run([os.path.join(os.path.dirname(HERE), "bin", "frog"), "pairs.bin", "-li", "12", "-dl", "2", "-di", "10", "-j", "-q", "1", *flags],
-                       cwd=cwd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return r.stdout
-
-
-def _same_files(a, b, n_images):
-    """measures.csv and every transforms/<i>.json: the same text."""
-    assert open(a / "measures.csv").read() == open(b / "measures.csv").read()
-    for i in range(n_images):
-        assert open(a / "transforms" / f"{i}.json").read() == open(b / "transforms" / f"{i}.json").read(), i
-
-
 @pytest.mark.parametrize("ranks", [3, 8])
 def test_two_collectives_give_the_files_of_three(tmp_path, ranks):
     """bin/frog -ngl N (the C++ multi-GPU host, ranks sharing the one GPU, host-staged transport): the flow of round 5 -- energy
@@ -159,7 +127,6 @@ def test_two_collectives_with_rejected_steps(tmp_path):
     did not happen; run()'s reject path (imageGroup.cxx:97-115) re-bases from the standing coefficients, makes a new lattice
     and gathers again.  Three ranks: same files as the three-collective flow, same lattices / energies / coefficients as ONE
     context (sums over ranks associate differently: 1e-6)."""
-    from test_gpu_cli_and_shards import _compare_runs
     pairs = Pairs.synthetic(9, 3000, 1200, seed=4)
     one, two, three = tmp_path / "one", tmp_path / "two", tmp_path / "three"
     for d in (one, two, three):

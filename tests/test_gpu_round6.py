@@ -5,8 +5,9 @@ literal forms of rounds 4-5, bit for bit."""
 import numpy as np
 import pytest
 
+from frog_amd import schedule
 from frog_amd.pairs import Pairs
-import test_gpu_reference_order as T
+from gpu_util import Side, _frog, _same_files, fast_against_reference_order, ragged_pairs, report
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +29,12 @@ BARS = {
 @pytest.mark.parametrize("k11", ["f32", "f64"])
 def test_fast_path_against_reference_order_config3_whole_default_schedule(monkeypatch, k11):
     """BASELINE.json configs[2] at its size over the reference's whole default schedule: 650 accepted iterations, 65 refreshes,
-    the guard's rejections (1 / 2 / 4 lattices per level).  Same guard decisions (lockstep asserts them at every step), census
+    the guard's rejections (1 / 2 / 4 lattices per level).  Same guard decisions (frog_amd.schedule asserts them at every step), census
     equal, and per lattice the bars above -- a ten-fold regression of any of them fails here, not in a script."""
     monkeypatch.setenv("FROG_K11_F64", "1" if k11 == "f64" else "0")
     pairs = Pairs.synthetic(100, 20000, 10101, seed=1)
-    r = T.fast_against_reference_order(pairs, 50, 3, 200, monkeypatch, range(0, 100, 9))
-    T.report(f"fast_vs_reference_order_cfg3_whole_schedule_{k11}", r)
+    r = fast_against_reference_order(pairs, 50, 3, 200, monkeypatch, range(0, 100, 9))
+    report(f"fast_vs_reference_order_cfg3_whole_schedule_{k11}", r)
     raw, dense, field, weighted, chain, e = BARS[k11]
     assert r["grids"] == [1, 2, 4]
     for k, d in enumerate(r["lattices"]):
@@ -48,14 +49,14 @@ def run_reference_order(pairs, monkeypatch, li, dl, di, images, **env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     monkeypatch.setenv("FROG_REFERENCE_ORDER", "1")
-    s = T.Side(pairs)
+    s = Side(pairs)
     monkeypatch.delenv("FROG_REFERENCE_ORDER")
     for k in env:
         monkeypatch.delenv(k)
     trace = []
 
     def check(tag, sides, e=None, infos=None):
-        kind = tag if isinstance(tag, str) else tag[0]
+        kind = schedule.kind(tag)
         if kind == "step":
             info = s.grid(images[0], s.num_grids() - 1)[0]
             n_cp = info.dims[0] * info.dims[1] * info.dims[2]
@@ -63,7 +64,7 @@ def run_reference_order(pairs, monkeypatch, li, dl, di, images, **env):
             trace.append(("grad", np.stack([s.gradient_raw(i, n_cp) for i in images])))
         elif kind in ("linear", "deformable"):
             trace.append((kind, s.xyz2().copy(), s.matrices().copy(), float(e[0])))
-    grids = T.lockstep([s], li, dl, di, check)
+    grids = schedule.run([s], li, [di] * dl, on=check)
     lattices = [np.stack([s.grid(i, k)[1] for i in images]) for k in range(s.num_grids())]
     return grids, trace, lattices
 
@@ -88,7 +89,6 @@ def test_reference_order_fast_forms_equal_the_literal_forms(monkeypatch, group):
     if group == "small":
         pairs, sched, images = Pairs.synthetic(6, 3000, 1500, seed=7), (12, 3, 25), list(range(6))
     elif group == "ragged":
-        from test_gpu_parity import ragged_pairs
         pairs = ragged_pairs()
         sched, images = (8, 2, 6), list(range(pairs.n_images))
     else:
@@ -107,11 +107,12 @@ def test_reference_order_chain_launches_folded_into_two_grid_dimensions():
     code = (
         "import sys, os, numpy as np\n"
         "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "from frog_amd import schedule\n"
         "from frog_amd.pairs import Pairs\n"
-        "import test_gpu_reference_order as T\n"
+        "from gpu_util import Side\n"
         "os.environ['FROG_REFERENCE_ORDER'] = '1'\n"
-        "s = T.Side(Pairs.synthetic(6, 3000, 1500, seed=7))\n"
-        "grids = T.lockstep([s], 6, 3, 8, lambda *a, **k: None)\n"
+        "s = Side(Pairs.synthetic(6, 3000, 1500, seed=7))\n"
+        "grids = schedule.run([s], 6, [8] * 3)\n"
         "np.savez(sys.argv[1], xyz2=s.xyz2(), m=s.matrices(), **{'g%%d' %% k: np.stack([s.grid(i, k)[1] for i in range(6)]) for k in range(s.num_grids())})\n"
     ) % (os.path.dirname(here), here)
     outs = []
@@ -150,7 +151,6 @@ def test_two_collectives_flow_with_the_scalars_by_copy(tmp_path):
     """FROG_SCALARS_COPY=1 = the state a failed hipHostGetDevicePointer leaves: frog_comm_unpack_slab_step used to return
     FROG_E_STATE there, i.e. every multi-rank run aborted at its first linear iteration.  Now the summed scalars reach the host by
     hipMemcpyAsync + event and frog_step_finish waits for the event: same files as the default hand-off, rejections included."""
-    from test_gpu_round5 import _frog, _same_files
     pairs = Pairs.synthetic(9, 3000, 1200, seed=4)
     direct, copy = tmp_path / "direct", tmp_path / "copy"
     for d in (direct, copy):
@@ -174,7 +174,6 @@ def test_blocked_and_sparse_lattices_give_the_same_files(tmp_path, flags, forms)
     node holds the same float -- 0 minus the node's means so far -- kept once per node).  Identical measures.csv and transforms for
     one context, three sharded contexts (phase B by cp_center_kernel, the speculative third lattice and its companion) and a run whose
     guard rejects steps (retired lattices read back through their own layout, mask and shared values)."""
-    from test_gpu_round5 import _frog, _same_files
     pairs = Pairs.synthetic(9, 3000, 1200, seed=4)
     plain, other = tmp_path / "plain", tmp_path / "other"
     for d in (plain, other):
@@ -193,7 +192,6 @@ def test_xcd_order_of_the_transform_blocks_changes_no_bit(tmp_path, flags):
     never choose them, in both forms of the transform, against both forbidden -- identical measures.csv and transforms, for one
     context, three sharded contexts and a run whose guard rejects steps (the per-block displacement maxima of the culling list are
     written under the new block numbers)."""
-    from test_gpu_round5 import _frog, _same_files
     pairs = Pairs.synthetic(9, 3000, 1200, seed=4)
     runs = {"tiled_plain": {"FROG_K11_TILED": "1", "FROG_K11_BY_XCD": "0"}, "tiled_xcd": {"FROG_K11_TILED": "1", "FROG_K11_BY_XCD": "1"},
             "point_plain": {"FROG_K11_POINTWISE": "1", "FROG_K11_POINT_BY_XCD": "0"}, "point_xcd": {"FROG_K11_POINTWISE": "1", "FROG_K11_POINT_BY_XCD": "1"}}
@@ -243,8 +241,8 @@ def test_selections_in_background_change_nothing(monkeypatch):
     pairs = Pairs.synthetic(12, 4000, 1500, seed=5)
     out = []
     for flag in (0, 1):
-        s = T.Side(pairs, selections_in_background=flag)
-        grids = T.lockstep([s], 30, 3, 30, lambda *a, **k: None)
+        s = Side(pairs, selections_in_background=flag)
+        grids = schedule.run([s], 30, [30] * 3)
         out.append((grids, s.xyz2().copy(), s.matrices().copy(), np.stack([s.g.em(i) for i in range(pairs.n_images)]),
                     [np.stack([s.grid(i, k)[1] for i in range(pairs.n_images)]) for k in range(s.num_grids())]))
     a, b = out
@@ -264,9 +262,9 @@ def test_no_lattice_allocation_after_create_when_the_levels_are_announced():
     at cfg 5's size, refused as more than half of the device's memory, and the set-up of level 4 paid three hipMalloc of 7.4 GB
     inside the loops (17 to 1 230 ms, box to box).  Without the hint the set-ups allocate: the counter counts."""
     pairs = Pairs.synthetic(40, 20000, 16667, seed=2, partners_per_image=20)
-    hinted = T.Side(pairs, max_levels_hint=5)
-    T.lockstep([hinted], 4, 5, 2, lambda *a, **k: None)
+    hinted = Side(pairs, max_levels_hint=5)
+    schedule.run([hinted], 4, [2] * 5)
     assert hinted.g.lattice_reallocations() == 0
-    plain = T.Side(pairs)
-    T.lockstep([plain], 4, 5, 2, lambda *a, **k: None)
+    plain = Side(pairs)
+    schedule.run([plain], 4, [2] * 5)
     assert plain.g.lattice_reallocations() >= 1

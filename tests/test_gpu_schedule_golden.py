@@ -36,18 +36,12 @@ if __name__ == "__main__":                      # run as a script: the repositor
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from frog_amd.image_group import ImageGroup
 from frog_amd.pairs import Pairs
+from gpu_util import note
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "schedule_golden.npz")
 GOLDEN_CFG5 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "schedule_golden_cfg5.npz")
 GOLDEN_CFG2 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "schedule_golden_cfg2.npz")
-
-
-def note(name, value):
-    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-    if os.path.isdir(d):
-        with open(os.path.join(d, "test_numbers.txt"), "a") as fh:
-            fh.write(f"{name} {value}\n")
 
 
 def compare_with_golden(reference_order, cfg5=False, cfg2=False):
