@@ -16,6 +16,8 @@ from oracle.oracle_api import OracleGroup
 from lattice_util import lattice_deviation, node_weights, lattice_taps, face_crossing_nodes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# k_links.hip.h INLIER_PROBABILITY_BOUND: the derived bound of the fast inlier weight against the reference's form
+INLIER_PROBABILITY_BOUND = 2.0 ** -16
 
 
 def note(name, value):
