@@ -30,6 +30,24 @@ inline int fail(int code, const std::string &msg)
             return ::frog::fail(FROG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// ---- a solver step's four scalars on their way to the host ------------------------------------
+// In this order in frog_ctx::energy, in a slab slot's trailer and at the head of the pinned block frog_ctx::h_energy:
+constexpr int SC_ENERGY = 0, SC_COUNT = 1;  // the energy's sums: E = sqrt([0] / [1])
+constexpr int SC_OVERSIZE = 2;              // proposals beyond the guard's limit (imageGroup.cxx:434-439)
+constexpr int SC_LIST_STALE = 3;            // > 0: a sweep found its culling list out of date (it walked every record)
+constexpr int N_SCALARS = 4;
+// The pinned block, in doubles: the scalars, frog_bounds_local's bounding box (six floats), the sequence number of the step
+// whose scalars a kernel wrote there (k_grid.hip.h store_step_scalars).
+constexpr int HS_BBOX = 4, HS_SEQ = 7, HS_DOUBLES = 8;
+// A hand-off that has been posted and not yet awaited (frog_hip.hip post_step_scalars / await_step_scalars), and what it yields
+struct ScalarHandoff {
+    enum How { NONE, BY_KERNEL, BY_COPY, BY_COPY_SYNC } how = NONE;
+    double seq = 0.0;           // BY_KERNEL: the number the carrying kernel stores last
+};
+struct StepScalars {
+    double E, n_oversize;
+};
+
 // ---- link layout (built on the host in prep.h) --------------------------------
 
 constexpr int TILE_POINTS = 256;     // points per sweep tile (one wavefront each)
@@ -247,9 +265,9 @@ struct frog_ctx {
     frog::DevBuf<double> energy_blocks;       // [ENERGY_BLOCKS][2] stage-1 sums
     frog::DevBuf<double> img_energy;          // [nOwned][2] per-image (sDistances, sWeights) of the last linear step
     frog::DevBuf<unsigned int> energy_ticket; // [0] blocks done in energy_reduce_kernel
-    double *h_energy = nullptr;               // pinned [8]
+    double *h_energy = nullptr;               // pinned [HS_DOUBLES]
     double *h_energy_dev = nullptr;           // the same memory as the device sees it (null: scalars come by copy)
-    uint64_t scalar_seq = 0;                  // steps whose scalars were handed over through h_energy[7]
+    uint64_t scalar_seq = 0;                  // steps whose scalars were handed over through h_energy[HS_SEQ]
 
     // deformable
     bool deformable = false;
@@ -263,6 +281,25 @@ struct frog_ctx {
     frog::DevBuf<uint32_t> lat_mask;          // [owned images][mask_words]: a bit per node
     frog::DevBuf<uint32_t> lat_inactive;      // [G] owned images for which the node is inactive
     frog::DevBuf<float4> ucoeff, ugrad, ugrad_spare;   // [G]
+    // How a step's decision moves the lattices (imageGroup.cxx:441-468 costs nothing: buffers change roles).  Accepted: the
+    // proposals become the coefficients.
+    void commit_proposal() { coeff.swap(grad); ucoeff.swap(ugrad); coeff_zero = false; }
+    // As if accepted, ahead of the decision (frog_step_speculate), the spare lattice taking the next proposals:
+    // (coeff, grad, spare) <- (grad, spare, coeff); what is needed to undo it stays in spec_coeff_zero ...
+    void speculate_commit()
+    {
+        spec_coeff_zero = coeff_zero;
+        coeff.swap(grad); grad.swap(grad_spare);
+        ucoeff.swap(ugrad); ugrad.swap(ugrad_spare);
+        coeff_zero = false;
+    }
+    // ... and its inverse, the same exchanges backwards: (coeff, grad, spare) <- (spare, coeff, grad)
+    void rollback_speculation()
+    {
+        grad.swap(grad_spare); coeff.swap(grad);
+        ugrad.swap(ugrad_spare); ucoeff.swap(ugrad);
+        coeff_zero = spec_coeff_zero;
+    }
     frog::DevBuf<double> gridsum;             // [3G] (+ 4: frog_comm_mode)
     frog::DevBuf<uint32_t> perm;              // owned points sorted by (image, brick)
     frog::DevBuf<uint32_t> key_ptr;           // [nOwned*n_bricks*B^3 + 1] (image, brick, cell) -> perm range
@@ -309,8 +346,7 @@ struct frog_ctx {
     bool finish_deformable = false; // ... and they decide a deformable step (frog_step_finish commits or rejects it)
     bool speculated = false;        // frog_step_speculate has exchanged the lattices' roles ahead of the decision
     bool spec_coeff_zero = false;
-    bool scalars_by_copy = false;   // the scalars of the pending step come by hipMemcpyAsync + energy_copied (no device-visible pinned block)
-    double pending_seq = 0.0;       // sequence number of the scalars frog_comm_unpack_slab_step published and frog_step_finish has not read yet
+    frog::ScalarHandoff pending;    // the scalars frog_comm_unpack_slab_step posted and frog_step_finish has not awaited yet
     bool k11_f64 = false;           // FROG_K11_F64=1: the B-spline transform's weights and sums in f64 (rounds 1-4), for comparison
     frog::DevBuf<uint32_t> ref_own;           // [L_own] own point (internal numbering) of every half-link, reference order
     frog::DevBuf<float> ref_w, ref_d;         // [L_own] weight and distance of every half-link (linear step)

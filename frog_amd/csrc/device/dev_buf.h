@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <utility>
 #include <vector>
 
 namespace frog {
@@ -26,6 +27,8 @@ template <class T> struct DevBuf {
         p = nullptr; n = 0; cap = 0; borrowed = false;
     }
     void borrow(T *from, size_t count) { release(); p = from; n = count; cap = count; borrowed = true; }
+    // (the solver's lattices change roles this way; they are only ever alloc()'d -- GridRecord::kept* alone borrow -- but ownership travels with the block)
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(cap, o.cap); std::swap(borrowed, o.borrowed); }
     // `reserve` (>= count): capacity to allocate when a new block is needed at all
     hipError_t alloc(size_t count, size_t reserve = 0)
     {

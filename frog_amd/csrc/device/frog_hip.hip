@@ -8,6 +8,7 @@
 #include "k_links.hip.h"
 #include "k_stats.hip.h"
 #include "k_grid.hip.h"
+#include "k_comm.hip.h"
 #include "k_cull.hip.h"
 #include "k_ransac.hip.h"
 #include "k_reforder.hip.h"
@@ -383,22 +384,65 @@ static int join_setup_positions(frog_ctx *ctx)
     return FROG_OK;
 }
 
-// Spins until the kernel that carries a step's scalars (publish_step_scalars) has written sequence number `seq` to pinned memory.
-static int wait_step_scalars(frog_ctx *ctx, double seq)
+// ---- the end of a solver step: its four scalars reach the host (ctx.h ScalarHandoff), the guard decides ------------------------------
+// Starts the hand-off of the scalars in ctx->energy.  BY_KERNEL: the kernel the caller queues next carries them -- given
+// h_energy_dev and h.seq, its first thread stores them, then the number, into the pinned block (store_step_scalars); without a
+// device-visible address of the block (hipHostGetDevicePointer failed, or FROG_SCALARS_COPY=1) that becomes BY_COPY:
+// hipMemcpyAsync + energy_copied, queued here.  BY_COPY_SYNC: the copy alone, awaited with the whole stream (frog_energy_read).
+static int post_step_scalars(frog_ctx *ctx, ScalarHandoff::How how, ScalarHandoff &h)
 {
-    volatile double *h = ctx->h_energy;
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (h[7] != seq) {
-        __builtin_ia32_pause();
-        if ((++spins & 0xFFFFu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-            // the kernel never ran (a launch failure shows here): wait for the stream and report
-            FROG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            if (h[7] != seq) return fail(FROG_E_HIP, "the step's scalars never arrived");
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
+    h.how = how == ScalarHandoff::BY_KERNEL && !ctx->h_energy_dev ? ScalarHandoff::BY_COPY : how;
+    h.seq = h.how == ScalarHandoff::BY_KERNEL ? (double)(++ctx->scalar_seq) : 0.0;
+    if (h.how == ScalarHandoff::BY_KERNEL) return FROG_OK;
+    FROG_HIP_CHECK(hipMemcpyAsync(ctx->h_energy, ctx->energy.p, N_SCALARS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (h.how == ScalarHandoff::BY_COPY) FROG_HIP_CHECK(hipEventRecord(ctx->energy_copied, ctx->stream));
     return FROG_OK;
+}
+
+// Waits for a posted hand-off (BY_KERNEL: spins on the sequence number) and reads it; `h` is free again either way.
+static int await_step_scalars(frog_ctx *ctx, ScalarHandoff &h, StepScalars &out)
+{
+    const ScalarHandoff posted = h;
+    h = ScalarHandoff{};
+    volatile double *hs = ctx->h_energy;
+    if (posted.how == ScalarHandoff::BY_KERNEL) {
+        const auto t0 = std::chrono::steady_clock::now();
+        unsigned spins = 0;
+        while (hs[HS_SEQ] != posted.seq) {
+            __builtin_ia32_pause();
+            if ((++spins & 0xFFFFu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+                // the kernel never ran (a launch failure shows here): wait for the stream and report
+                FROG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                if (hs[HS_SEQ] != posted.seq) return fail(FROG_E_HIP, "the step's scalars never arrived");
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+    } else if (posted.how == ScalarHandoff::BY_COPY) FROG_HIP_CHECK(hipEventSynchronize(ctx->energy_copied));
+    else FROG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (ctx->h_energy[SC_LIST_STALE] > 0) ctx->cull_need_build = true;       // a sweep found its culling list out of date (it walked every record)
+    out.E = std::sqrt(ctx->h_energy[SC_ENERGY] / ctx->h_energy[SC_COUNT]);
+    out.n_oversize = ctx->h_energy[SC_OVERSIZE];
+    return FROG_OK;
+}
+
+// the guard of imageGroup.cxx:434-439
+static bool step_rejected(const frog_ctx *ctx, double n_oversize) { return ctx->opt.guarantee_diffeomorphism && n_oversize > 0; }
+
+// ---- disp_part: the per-block maxima of the points' displacement from the culling list's snapshot -----------------------------
+// After a transform of the owned rows into `out` -- the table, or a copy that becomes current when it is published (pos2_spec, a
+// slab slot).  measured: the kernel left n_blocks maxima; not measured: the check before the next sweep does it.
+static void record_displacement(frog_ctx *ctx, const P3 *out, bool measured, uint32_t n_blocks)
+{
+    if (measured) ctx->disp_n = ctx->disp_own_n = n_blocks;
+    ctx->disp_others = false;
+    ctx->disp_current = measured && out == ctx->pos2.p;
+    if (out != ctx->pos2.p) ctx->disp_spec = measured;
+}
+// ... and after the other ranks' rows arrived (unpack_slab), measured into the n_blocks entries behind the own rows'
+static void record_displacement_others(frog_ctx *ctx, bool measured, uint32_t n_blocks)
+{
+    if (measured) { ctx->disp_n = ctx->disp_own_n + n_blocks; ctx->disp_others = true; }
+    else { ctx->disp_current = false; ctx->disp_others = false; }      // measured by the check before the next sweep
 }
 
 // Queues, on the side stream, the selection of the next refresh not yet selected (k_stats.hip.h select_kernel: the
@@ -877,9 +921,8 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
         (void)hipGetLastError();
     }
     create_lap("stream, memory pool");
-    // [0..3] energy scalars, [4..6] bounding box (6 floats), [7] sequence number of the step whose scalars a kernel wrote here
-    CREATE_CHECK(hipHostMalloc((void **)&c->h_energy, 8 * sizeof(double), hipHostMallocMapped));
-    std::memset(c->h_energy, 0, 8 * sizeof(double));
+    CREATE_CHECK(hipHostMalloc((void **)&c->h_energy, HS_DOUBLES * sizeof(double), hipHostMallocMapped));      // (layout: ctx.h)
+    std::memset(c->h_energy, 0, HS_DOUBLES * sizeof(double));
     if (hipHostGetDevicePointer((void **)&c->h_energy_dev, c->h_energy, 0) != hipSuccess) { (void)hipGetLastError(); c->h_energy_dev = nullptr; }
     if (getenv("FROG_SCALARS_COPY")) c->h_energy_dev = nullptr;      // the copy + event hand-off (A/B, fallback)
     hipStream_t s = c->stream;
@@ -1300,8 +1343,6 @@ int frog_linear_init(frog_ctx *ctx, const float anchor_pos[3])
 }
 
 // ---- transformPoints (imageGroup.cxx:910-916, image.cxx:3-13) -----------------------
-__global__ void slab_trailer_kernel(const double *energy, double *trailer) { write_slab_trailer(energy, trailer); }
-
 // `trailer` (null in every call but frog_transform_points_slab's): where the kernel's first thread leaves the step's four
 // scalars as they stand on this rank (k_grid.hip.h write_slab_trailer)
 static int launch_transform(frog_ctx *ctx, P3 *out, int apply, bool after_step = false, double scalar_seq = 0.0, double *trailer = nullptr)
@@ -1319,20 +1360,15 @@ static int launch_transform(frog_ctx *ctx, P3 *out, int apply, bool after_step =
                                                                         ctx->disp_allow.p, ctx->cull_state.p, ctx->energy.p,
                                                                         host_scalars, scalar_seq, trailer);
         trailer = nullptr;
-        if (with_disp) ctx->disp_n = ctx->disp_own_n = div_up(n, 256);
-        ctx->disp_others = false;
-        if (out == ctx->pos2.p) ctx->disp_current = with_disp;
-        else { ctx->disp_spec = with_disp; ctx->disp_current = false; }
+        record_displacement(ctx, out, with_disp, div_up(n, 256));
     } else if (ctx->coeff_zero && !after_step) {
         // a fresh lattice: identity (k_grid.hip.h); the displacement against the culling list's snapshot is measured by
         // the check before the next sweep instead
-        ctx->disp_current = false;
-        if (out != ctx->pos2.p) ctx->disp_spec = false;
+        record_displacement(ctx, out, false, 0);
         transform_zero_lattice_kernel<<<div_up(n, 256), 256, 0, ctx->stream>>>(ctx->pos.p, out, ctx->own_pt_begin, ctx->own_pt_end, apply);
     } else if (ctx->ref_order) {
         { const int rc = join_setup(ctx); if (rc) return rc; }
-        ctx->disp_current = false;
-        if (out != ctx->pos2.p) ctx->disp_spec = false;
+        record_displacement(ctx, out, false, 0);
         ref_transform_bspline_kernel<<<div_up(n, 256), 256, 0, ctx->stream>>>(ctx->pos.p, out, ctx->coeff.p, ctx->own_pt_begin, ctx->own_pt_end,
                                                                              ctx->ib, to_dev(ctx->geom), apply, after_step ? ctx->grad.p : nullptr,
                                                                              ctx->energy.p, ctx->opt.guarantee_diffeomorphism, host_scalars, scalar_seq);
@@ -1367,7 +1403,7 @@ static int launch_transform(frog_ctx *ctx, P3 *out, int apply, bool after_step =
                 with_disp ? ctx->pos2_snap.p : nullptr, ctx->disp_part.p,
                 after_step ? ctx->grad.p : nullptr, ctx->energy.p, ctx->opt.guarantee_diffeomorphism,
                 ctx->disp_allow.p, ctx->cull_state.p, host_scalars, scalar_seq, trailer, by_xcd ? ctx->n_scatter_blocks : 0u);
-            if (with_disp) ctx->disp_n = ctx->disp_own_n = ctx->n_scatter_blocks;
+            record_displacement(ctx, out, with_disp, ctx->n_scatter_blocks);
         } else {
             auto kernel = ctx->k11_f64 ? transform_bspline_kernel<double> : (ctx->geom.brick == 8 ? transform_bspline_kernel<float, 2> : transform_bspline_kernel<float>);
             // FROG_K11_POINT_BY_XCD=1 / 0 forces / forbids the XCD-aware order of the blocks (k_grid.hip.h); default: from 8 192 blocks
@@ -1381,13 +1417,9 @@ static int launch_transform(frog_ctx *ctx, P3 *out, int apply, bool after_step =
                                                                              ctx->opt.guarantee_diffeomorphism,
                                                                              ctx->disp_allow.p, ctx->cull_state.p, host_scalars, scalar_seq, trailer,
                                                                              pt_xcd ? nb : 0u);
-            if (with_disp) ctx->disp_n = ctx->disp_own_n = div_up(n, 256);
+            record_displacement(ctx, out, with_disp, nb);
         }
         trailer = nullptr;
-        ctx->disp_others = false;
-        // the per-block maxima now describe `out`: the current xyz2, or the speculative copy until it is published
-        if (out == ctx->pos2.p) ctx->disp_current = with_disp;
-        else { ctx->disp_spec = with_disp; ctx->disp_current = false; }
     }
     // the forms that do not write the trailer themselves (fresh lattice, reference-order mode)
     if (trailer) slab_trailer_kernel<<<1, 1, 0, ctx->stream>>>(ctx->energy.p, trailer);
@@ -1642,11 +1674,12 @@ int frog_linear_step_local(frog_ctx *ctx)
 int frog_energy_read(frog_ctx *ctx, double *E, double *n_oversize)
 {
     CTX_GUARD(ctx);
-    FROG_HIP_CHECK(hipMemcpyAsync(ctx->h_energy, ctx->energy.p, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    FROG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_energy[3] > 0) ctx->cull_need_build = true;       // the sweep found its list out of date (it walked every record)
-    if (E) *E = std::sqrt(ctx->h_energy[0] / ctx->h_energy[1]);
-    if (n_oversize) *n_oversize = ctx->h_energy[2];
+    ScalarHandoff h; StepScalars sc;
+    int rc = post_step_scalars(ctx, ScalarHandoff::BY_COPY_SYNC, h);
+    if (!rc) rc = await_step_scalars(ctx, h, sc);
+    if (rc) return rc;
+    if (E) *E = sc.E;
+    if (n_oversize) *n_oversize = sc.n_oversize;
     return FROG_OK;
 }
 
@@ -1661,14 +1694,15 @@ int frog_linear_step(frog_ctx *ctx, double *E)
     if (!(ctx->whole_group() && ctx->h_energy_dev && n && !ctx->helper))
         return frog_energy_read(ctx, E, nullptr);
     if (ctx->pos2_spec.n != ctx->P) FROG_HIP_CHECK(ctx->pos2_spec.alloc(ctx->P));
-    const double seq = (double)(++ctx->scalar_seq);
-    rc = launch_transform(ctx, ctx->pos2_spec.p, 0, false, seq);
+    ScalarHandoff h; StepScalars sc;
+    rc = post_step_scalars(ctx, ScalarHandoff::BY_KERNEL, h);
+    if (rc) return rc;
+    rc = launch_transform(ctx, ctx->pos2_spec.p, 0, false, h.seq);
     if (rc) return rc;
     ctx->xyz2_fresh = true;
-    rc = wait_step_scalars(ctx, seq);
+    rc = await_step_scalars(ctx, h, sc);
     if (rc) return rc;
-    if (ctx->h_energy[3] > 0) ctx->cull_need_build = true;       // the sweep found its list out of date (it walked every record)
-    if (E) *E = std::sqrt(ctx->h_energy[0] / ctx->h_energy[1]);
+    if (E) *E = sc.E;
     return FROG_OK;
 }
 
@@ -1680,7 +1714,7 @@ int frog_bounds_local(frog_ctx *ctx, double mins[3], double maxs[3])
     bounds_kernel<<<BOUNDS_BLOCKS, 256, 0, s>>>(ctx->pos.p, ctx->own_pt_begin, ctx->own_pt_end, ctx->bounds_scratch.p);
     bounds_final_kernel<<<1, 256, 0, s>>>(ctx->bounds_scratch.p, BOUNDS_BLOCKS, ctx->bounds_scratch.p + (size_t)BOUNDS_BLOCKS * 6);
     FROG_HIP_CHECK(hipGetLastError());
-    float *h = reinterpret_cast<float *>(ctx->h_energy + 4);       // pinned
+    float *h = reinterpret_cast<float *>(ctx->h_energy + HS_BBOX);       // pinned
     FROG_HIP_CHECK(hipMemcpyAsync(h, ctx->bounds_scratch.p + (size_t)BOUNDS_BLOCKS * 6, 6 * sizeof(float), hipMemcpyDeviceToHost, s));
     FROG_HIP_CHECK(hipStreamSynchronize(s));
     // an empty range leaves (+FLT_MAX, -FLT_MAX): neutral in the callers' min / max reduction over ranks
@@ -2155,36 +2189,19 @@ int frog_deformable_phase_c(frog_ctx *ctx, double *E)
     // The scalars reach the host without a copy of their own when a transform through the lattice follows (it does unless the
     // context owns no point): its first thread writes them, then the step's sequence number, into pinned memory the host
     // spins on (k_grid.hip.h publish_step_scalars).
-    const bool direct = ctx->h_energy_dev && ctx->own_pt_end > ctx->own_pt_begin;
-    double seq = 0.0;
-    if (direct) {
-        seq = (double)(++ctx->scalar_seq);
-    } else {
-        FROG_HIP_CHECK(hipMemcpyAsync(ctx->h_energy, ctx->energy.p, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        FROG_HIP_CHECK(hipEventRecord(ctx->energy_copied, ctx->stream));
-    }
+    ScalarHandoff h; StepScalars sc;
+    int rc = post_step_scalars(ctx, ctx->own_pt_end > ctx->own_pt_begin ? ScalarHandoff::BY_KERNEL : ScalarHandoff::BY_COPY, h);
+    if (rc) return rc;
     // the transformPoints() that run() calls next, from the lattice the guard's decision selects (on the device)
-    int rc = launch_transform(ctx, ctx->pos2_spec.p, 0, true, seq);  // xyz2 itself changes only when the caller asks
+    rc = launch_transform(ctx, ctx->pos2_spec.p, 0, true, h.seq);  // xyz2 itself changes only when the caller asks
     if (rc) return rc;
     ctx->xyz2_fresh = true;
-    if (direct) {
-        rc = wait_step_scalars(ctx, seq);
-        if (rc) return rc;
-    } else {
-        FROG_HIP_CHECK(hipEventSynchronize(ctx->energy_copied));
-    }
-    const double e = std::sqrt(ctx->h_energy[0] / ctx->h_energy[1]), nbig = ctx->h_energy[2];
-    if (ctx->h_energy[3] > 0) ctx->cull_need_build = true;       // this step's sweep found the culling list out of date
-    if (!(ctx->opt.guarantee_diffeomorphism && nbig > 0)) {
-        // accepted (:441-468): the proposal lattice becomes the coefficients -- the two buffers change roles
-        std::swap(ctx->coeff.p, ctx->grad.p);
-        std::swap(ctx->coeff.cap, ctx->grad.cap);
-        std::swap(ctx->coeff.n, ctx->grad.n);
-        std::swap(ctx->ucoeff.p, ctx->ugrad.p); std::swap(ctx->ucoeff.cap, ctx->ugrad.cap); std::swap(ctx->ucoeff.n, ctx->ugrad.n);   // (sparse lattices: their companions)
-        ctx->coeff_zero = false;
-    }
+    rc = await_step_scalars(ctx, h, sc);
+    if (rc) return rc;
+    const bool rejected = step_rejected(ctx, sc.n_oversize);
+    if (!rejected) ctx->commit_proposal();      // accepted (:441-468)
     ctx->phase = 0;
-    if (E) *E = (ctx->opt.guarantee_diffeomorphism && nbig > 0) ? -1.0 : e;      // :434-439
+    if (E) *E = rejected ? -1.0 : sc.E;
     return FROG_OK;
 }
 
@@ -2741,93 +2758,62 @@ int frog_profile_read(frog_ctx *ctx, frog_kernel_time *out, int reset)
     return FROG_OK;
 }
 
-// rows [row_begin[r], row_begin[r + 1]) of every rank r != self: slab slot r -> the coordinate table
-constexpr int UNPACK_MAX_RANKS = 64;
-struct UnpackArgs {
-    uint64_t row_begin[UNPACK_MAX_RANKS + 1];
-    uint64_t slot_bytes;            // distance between two ranks' slots
-    uint32_t world, self;           // self == world: the own rows are copied too (frog_comm_unpack_slab_step)
-    // frog_comm_unpack_slab_step: the slots' trailers (4 doubles at slot + trailer_off) are added up over the ranks for the scalars in
-    // sum_mask and the step's four scalars handed to the host (k_grid.hip.h publish_step_scalars)
-    uint64_t trailer_off;
-    uint32_t sum_mask;
-    double *energy, *host_scalars;
-    double seq;
-};
-// `snap` (null: no list to check): the block also leaves the largest distance of the rows it copies from the culling list's
-// snapshot in disp_part[blockIdx.y * gridDim.x + blockIdx.x] (k_cull.hip.h: what cull_disp_kernel computes in a pass of its own)
-__global__ __launch_bounds__(256) void unpack_slab_kernel(const P3 *slab, P3 *pos2, const UnpackArgs a, const P3 *snap, uint32_t *disp_part)
-{
-    __shared__ uint32_t sh[4];
-    const uint32_t r = blockIdx.y;
-    if (a.sum_mask && blockIdx.x == 0 && r == 0 && threadIdx.x == 0) {
-        // the ranks' trailers in rank order: integers (oversize counts, flags) add exactly; the energy sums of a linear step
-        // in the same order on every rank, so every rank prints the same E
-        for (int k = 0; k < 4; k++) {
-            if (!(a.sum_mask >> k & 1u)) continue;
-            double sum = 0.0;
-            for (uint32_t q = 0; q < a.world; q++)
-                sum += reinterpret_cast<const double *>(reinterpret_cast<const unsigned char *>(slab) + q * a.slot_bytes + a.trailer_off)[k];
-            a.energy[k] = sum;
-        }
-        __threadfence();
-        if (a.host_scalars) {               // null: the host gets them by copy + event (frog_comm_unpack_slab_step)
-            #pragma unroll
-            for (int k = 0; k < 4; k++) __hip_atomic_store(&a.host_scalars[k], a.energy[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __threadfence_system();
-            __hip_atomic_store(&a.host_scalars[7], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    uint32_t m = 0;
-    if (r != a.self) {
-        const uint64_t n = a.row_begin[r + 1] - a.row_begin[r];
-        const P3 *slot = reinterpret_cast<const P3 *>(reinterpret_cast<const unsigned char *>(slab) + r * a.slot_bytes);
-        for (uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x; k < n; k += (uint64_t)gridDim.x * 256u) {
-            const P3 v = slot[k];
-            pos2[a.row_begin[r] + k] = v;
-            if (snap) {
-                const P3 q = snap[a.row_begin[r] + k];
-                const float dx = v.x - q.x, dy = v.y - q.y, dz = v.z - q.z;
-                m = max(m, __float_as_uint(__builtin_sqrtf(dx * dx + dy * dy + dz * dz)) & 0x7FFFFFFFu);
-            }
-        }
-    }
-    if (!snap) return;
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_down((int)m, off, 64));
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) disp_part[blockIdx.y * gridDim.x + blockIdx.x] = max(max(sh[0], sh[1]), max(sh[2], sh[3]));
-}
-
-int frog_comm_unpack_slab(frog_ctx *ctx, const void *slab, uint64_t slot_rows, uint32_t world_size, const uint64_t *row_begin, uint32_t self)
+// Slab slots -> the coordinate table, for both ABI forms.  own_rows_too (frog_comm_unpack_slab_step): the slots carry trailers
+// (FROG_SLAB_SLOT_BYTES apart, not slot_rows rows), every slot is copied, the own one included -- row_begin[self] must be this
+// context's shard --, the trailers' scalars in sum_mask are added up and posted for frog_step_finish, and the own rows'
+// displacement is what the transform that wrote the slot measured (recorded as "speculative": its output was not the table).
+static int unpack_slab(frog_ctx *ctx, const void *slab, uint64_t slot_rows, uint32_t world, const uint64_t *row_begin, uint32_t self,
+                       uint32_t sum_mask, bool own_rows_too)
 {
     CTX_GUARD(ctx);
-    if (!slab || !row_begin || world_size < 1 || world_size > (uint32_t)UNPACK_MAX_RANKS || self >= world_size)
+    if (!slab || !row_begin || world < 1 || world > (uint32_t)UNPACK_MAX_RANKS || self >= world || sum_mask > 15u)
         return fail(FROG_E_INVALID, "bad slab arguments");
     UnpackArgs a{};
     uint64_t longest = 0;
-    for (uint32_t r = 0; r <= world_size; r++) a.row_begin[r] = row_begin[r];
-    for (uint32_t r = 0; r < world_size; r++) {
+    for (uint32_t r = 0; r <= world; r++) a.row_begin[r] = row_begin[r];
+    for (uint32_t r = 0; r < world; r++) {
         if (row_begin[r + 1] < row_begin[r] || row_begin[r + 1] > ctx->P) return fail(FROG_E_INVALID, "rows must be ascending and inside the table");
         longest = std::max(longest, row_begin[r + 1] - row_begin[r]);
     }
     if (longest > slot_rows) return fail(FROG_E_INVALID, "slot shorter than the longest shard");
-    a.slot_bytes = slot_rows * sizeof(P3); a.world = world_size; a.self = self;
-    if (longest == 0) return FROG_OK;
-    const dim3 grid((unsigned)std::min<uint64_t>(div_up(longest, 256), 1024), world_size);
+    if (own_rows_too && (row_begin[self] != ctx->own_pt_begin || row_begin[self + 1] != ctx->own_pt_end))
+        return fail(FROG_E_INVALID, "row_begin[self] is not this context's shard");
+    a.slot_bytes = own_rows_too ? FROG_SLAB_SLOT_BYTES(slot_rows) : slot_rows * sizeof(P3);
+    a.world = world; a.self = own_rows_too ? world : self;
+    if (own_rows_too) a.trailer_off = a.slot_bytes - FROG_SLAB_TRAILER_BYTES;
+    else if (longest == 0) return FROG_OK;      // nothing to copy (the step form still adds the trailers up: a grid of one block at least)
+    // The scalars go to the host with the kernel's first thread -- or, without a device-visible address of the pinned block, by a
+    // copy queued behind the kernel, which leaves the sums in ctx->energy either way; frog_step_finish awaits them.
+    const bool carried = sum_mask && ctx->h_energy_dev;
+    if (sum_mask) {
+        a.sum_mask = sum_mask; a.energy = ctx->energy.p;
+        if (carried) {
+            const int rc = post_step_scalars(ctx, ScalarHandoff::BY_KERNEL, ctx->pending);
+            if (rc) return rc;
+            a.host_scalars = ctx->h_energy_dev; a.seq = ctx->pending.seq;
+        }
+        ctx->finish_deformable = ctx->phase == 2;
+    }
+    const dim3 grid((unsigned)std::min<uint64_t>(std::max<uint64_t>(div_up(longest, 256), 1), 1024), world);
+    if (own_rows_too) { ctx->disp_current = ctx->disp_spec; ctx->disp_spec = false; }
     // The own rows' displacement against the culling list's snapshot was measured by the transform that produced them
     // (disp_part[0 .. disp_own_n)); the rows arriving here are measured as they are copied, behind those entries -- the check
     // before the next sweep then has every row covered without a pass of its own over the whole table.
+    // (own_rows_too: the own slot's rows are measured twice when `measure`, by the transform and here -- a maximum does not mind)
     const bool list = ctx->deformable ? (cull_active(ctx) && ctx->cull_builds > 0) : (cull_active_linear(ctx) && ctx->cull_lin_builds > 0);
     const bool measure = ctx->disp_current && list && !ctx->cull_need_build && ctx->pos2_snap.p && ctx->disp_part.p
                          && (size_t)ctx->disp_own_n + (size_t)grid.x * grid.y <= ctx->disp_part.n;
     unpack_slab_kernel<<<grid, 256, 0, ctx->stream>>>(reinterpret_cast<const P3 *>(slab), ctx->pos2.p, a,
                                                       measure ? ctx->pos2_snap.p : nullptr, measure ? ctx->disp_part.p + ctx->disp_own_n : nullptr);
     FROG_HIP_CHECK(hipGetLastError());
-    if (measure) { ctx->disp_n = ctx->disp_own_n + grid.x * grid.y; ctx->disp_others = true; }
-    else { ctx->disp_current = false; ctx->disp_others = false; }      // measured by the check before the next sweep
+    record_displacement_others(ctx, measure, grid.x * grid.y);
+    if (sum_mask && !carried) return post_step_scalars(ctx, ScalarHandoff::BY_COPY, ctx->pending);
     return FROG_OK;
+}
+
+int frog_comm_unpack_slab(frog_ctx *ctx, const void *slab, uint64_t slot_rows, uint32_t world_size, const uint64_t *row_begin, uint32_t self)
+{
+    return unpack_slab(ctx, slab, slot_rows, world_size, row_begin, self, 0, false);
 }
 
 // ---- sharded contexts: two collectives per deformable iteration, one per linear iteration (include/frog_hip.h) -----------------
@@ -2868,67 +2854,19 @@ int frog_transform_points_slab(frog_ctx *ctx, int apply, int after_step, void *s
 int frog_comm_unpack_slab_step(frog_ctx *ctx, const void *slab, uint64_t slot_rows, uint32_t world_size, const uint64_t *row_begin,
                                uint32_t self, uint32_t sum_mask)
 {
-    CTX_GUARD(ctx);
-    if (!slab || !row_begin || world_size < 1 || world_size > (uint32_t)UNPACK_MAX_RANKS || self >= world_size || sum_mask > 15u)
-        return fail(FROG_E_INVALID, "bad slab arguments");
-    UnpackArgs a{};
-    uint64_t longest = 0;
-    for (uint32_t r = 0; r <= world_size; r++) a.row_begin[r] = row_begin[r];
-    for (uint32_t r = 0; r < world_size; r++) {
-        if (row_begin[r + 1] < row_begin[r] || row_begin[r + 1] > ctx->P) return fail(FROG_E_INVALID, "rows must be ascending and inside the table");
-        longest = std::max(longest, row_begin[r + 1] - row_begin[r]);
-    }
-    if (longest > slot_rows) return fail(FROG_E_INVALID, "slot shorter than the longest shard");
-    if (row_begin[self] != ctx->own_pt_begin || row_begin[self + 1] != ctx->own_pt_end) return fail(FROG_E_INVALID, "row_begin[self] is not this context's shard");
-    a.slot_bytes = FROG_SLAB_SLOT_BYTES(slot_rows); a.world = world_size; a.self = world_size;      // every slot, the own one included
-    a.trailer_off = a.slot_bytes - FROG_SLAB_TRAILER_BYTES;
-    a.sum_mask = sum_mask;
-    if (sum_mask) {
-        a.energy = ctx->energy.p; a.host_scalars = ctx->h_energy_dev;
-        a.seq = (double)(++ctx->scalar_seq);
-        ctx->pending_seq = a.seq;
-        ctx->finish_deformable = ctx->phase == 2;
-    }
-    const dim3 grid((unsigned)std::min<uint64_t>(std::max<uint64_t>(div_up(longest, 256), 1), 1024), world_size);
-    // the own rows' displacement against the culling list's snapshot: measured by the transform that wrote them into the slab
-    // (disp_part[0 .. disp_own_n), recorded as "speculative" because its output was not the table); the other ranks' as they are copied
-    ctx->disp_current = ctx->disp_spec; ctx->disp_spec = false;
-    const bool list = ctx->deformable ? (cull_active(ctx) && ctx->cull_builds > 0) : (cull_active_linear(ctx) && ctx->cull_lin_builds > 0);
-    const bool measure = ctx->disp_current && list && !ctx->cull_need_build && ctx->pos2_snap.p && ctx->disp_part.p
-                         && (size_t)ctx->disp_own_n + (size_t)grid.x * grid.y <= ctx->disp_part.n;
-    unpack_slab_kernel<<<grid, 256, 0, ctx->stream>>>(reinterpret_cast<const P3 *>(slab), ctx->pos2.p, a,
-                                                      measure ? ctx->pos2_snap.p : nullptr, measure ? ctx->disp_part.p + ctx->disp_own_n : nullptr);
-    FROG_HIP_CHECK(hipGetLastError());
-    // (the own slot's rows are measured twice when `measure`: once by the transform, once here -- a maximum does not mind)
-    if (measure) { ctx->disp_n = ctx->disp_own_n + grid.x * grid.y; ctx->disp_others = true; }
-    else { ctx->disp_current = false; ctx->disp_others = false; }      // measured by the check before the next sweep
-    // No device-visible address of the pinned scalar block (hipHostGetDevicePointer failed, or FROG_SCALARS_COPY=1): the summed
-    // scalars reach the host by copy + event, as in frog_deformable_phase_c, and frog_step_finish waits for the event.
-    ctx->scalars_by_copy = sum_mask && !ctx->h_energy_dev;
-    if (ctx->scalars_by_copy) {
-        FROG_HIP_CHECK(hipMemcpyAsync(ctx->h_energy, ctx->energy.p, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        FROG_HIP_CHECK(hipEventRecord(ctx->energy_copied, ctx->stream));
-    }
-    return FROG_OK;
+    return unpack_slab(ctx, slab, slot_rows, world_size, row_begin, self, sum_mask, true);
 }
 
 int frog_step_speculate(frog_ctx *ctx)
 {
     CTX_GUARD(ctx);
-    if (ctx->pending_seq == 0.0 || !ctx->finish_deformable || ctx->phase != 2 || ctx->speculated)
+    if (ctx->pending.how == ScalarHandoff::NONE || !ctx->finish_deformable || ctx->phase != 2 || ctx->speculated)
         return fail(FROG_E_STATE, "frog_step_speculate needs a deformable step whose scalars are on their way (frog_comm_unpack_slab_step)");
     if (ctx->grad_spare.n != ctx->grad.n) {
         // (frog_comm_mode was switched on after the lattice was made: the one allocation outside a set-up)
         FROG_HIP_CHECK(ctx->grad_spare.alloc(ctx->grad.n, ctx->grad.cap));
     }
-    // as if accepted (imageGroup.cxx:441-468): the proposal lattice becomes the coefficients, the spare one takes the next proposals;
-    // what is needed to undo it stays in spec_*
-    ctx->spec_coeff_zero = ctx->coeff_zero;
-    auto rotate = [](DevBuf<float4> &a, DevBuf<float4> &b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); std::swap(a.n, b.n); };
-    rotate(ctx->coeff, ctx->grad);              // coeff = proposal, grad = old coefficients
-    rotate(ctx->grad, ctx->grad_spare);         // grad = spare, spare = old coefficients
-    rotate(ctx->ucoeff, ctx->ugrad); rotate(ctx->ugrad, ctx->ugrad_spare);      // (sparse lattices: their companions)
-    ctx->coeff_zero = false;
+    ctx->speculate_commit();
     ctx->speculated = true;
     ctx->phase = 0;
     return FROG_OK;
@@ -2937,40 +2875,32 @@ int frog_step_speculate(frog_ctx *ctx)
 int frog_step_finish(frog_ctx *ctx, double *E)
 {
     CTX_GUARD(ctx);
-    if (ctx->pending_seq == 0.0) return fail(FROG_E_STATE, "frog_step_finish without frog_comm_unpack_slab_step(sum_mask != 0)");
-    int rc = FROG_OK;
-    if (ctx->scalars_by_copy) { ctx->scalars_by_copy = false; FROG_HIP_CHECK(hipEventSynchronize(ctx->energy_copied)); }
-    else rc = wait_step_scalars(ctx, ctx->pending_seq);
-    ctx->pending_seq = 0.0;
+    if (ctx->pending.how == ScalarHandoff::NONE) return fail(FROG_E_STATE, "frog_step_finish without frog_comm_unpack_slab_step(sum_mask != 0)");
+    StepScalars sc;
+    const int rc = await_step_scalars(ctx, ctx->pending, sc);
     if (rc) return rc;
-    if (ctx->h_energy[3] > 0) ctx->cull_need_build = true;       // a rank's sweep found its culling list out of date
-    const double e = std::sqrt(ctx->h_energy[0] / ctx->h_energy[1]), nbig = ctx->h_energy[2];
-    if (ctx->finish_deformable) {
-        // updateDeformableTransforms' decision (imageGroup.cxx:434-439) and commit (:441-468), as frog_deformable_phase_c
-        ctx->finish_deformable = false;
-        const bool rejected = ctx->opt.guarantee_diffeomorphism && nbig > 0;
-        auto rotate = [](DevBuf<float4> &a, DevBuf<float4> &b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); std::swap(a.n, b.n); };
-        if (ctx->speculated) {
-            ctx->speculated = false;
-            if (rejected) {
-                // undo frog_step_speculate: the lattices take their old roles; the phase A queued meanwhile worked on coordinates of
-                // a step that did not happen -- per-point sums, staged tiles, proposals in the spare lattice: nothing of it is read again
-                rotate(ctx->grad, ctx->grad_spare);
-                rotate(ctx->coeff, ctx->grad);
-                rotate(ctx->ugrad, ctx->ugrad_spare); rotate(ctx->ucoeff, ctx->ugrad);
-                ctx->coeff_zero = ctx->spec_coeff_zero;
-                ctx->phase = 0;
-                ctx->xyz2_fresh = false; ctx->res_valid = false;
-            }
-        } else {
-            if (ctx->phase != 2) return fail(FROG_E_STATE, "frog_step_finish: no deformable step pending");
-            if (!rejected) { rotate(ctx->coeff, ctx->grad); rotate(ctx->ucoeff, ctx->ugrad); ctx->coeff_zero = false; }
-            ctx->phase = 0;
-        }
-        if (E) *E = rejected ? -1.0 : e;
+    if (!ctx->finish_deformable) {
+        if (E) *E = sc.E;
         return FROG_OK;
     }
-    if (E) *E = e;
+    // updateDeformableTransforms' decision (imageGroup.cxx:434-439) and commit (:441-468), as frog_deformable_phase_c
+    ctx->finish_deformable = false;
+    const bool rejected = step_rejected(ctx, sc.n_oversize);
+    if (ctx->speculated) {
+        ctx->speculated = false;
+        if (rejected) {
+            // undo frog_step_speculate: the lattices take their old roles; the phase A queued meanwhile worked on coordinates of
+            // a step that did not happen -- per-point sums, staged tiles, proposals in the spare lattice: nothing of it is read again
+            ctx->rollback_speculation();
+            ctx->phase = 0;
+            ctx->xyz2_fresh = false; ctx->res_valid = false;
+        }
+    } else {
+        if (ctx->phase != 2) return fail(FROG_E_STATE, "frog_step_finish: no deformable step pending");
+        if (!rejected) ctx->commit_proposal();
+        ctx->phase = 0;
+    }
+    if (E) *E = rejected ? -1.0 : sc.E;
     return FROG_OK;
 }
 

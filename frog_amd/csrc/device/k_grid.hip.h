@@ -99,14 +99,17 @@ __device__ __forceinline__ f32x4 as_f32x4(const float4 v) { return f32x4{ v.x, v
 // pinned host memory by the first thread of the transform that is queued behind the step -- the kernel that starts once
 // the scalars are final -- followed by the step's sequence number, which the host spins on.  A copy kernel + event between
 // the lattice step and the transform cost every iteration 4 us of copy, a dependent-launch gap and the event's wake-up.
+// store_step_scalars: the stores themselves, for the ONE thread of a launch that makes them (no guard).
+__device__ __forceinline__ void store_step_scalars(double *host, const double *v, double seq)
+{
+    #pragma unroll
+    for (int k = 0; k < N_SCALARS; k++) __hip_atomic_store(&host[k], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+    __hip_atomic_store(&host[HS_SEQ], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 __device__ __forceinline__ void publish_step_scalars(const double *energy, double *host, double seq)
 {
-    if (host && blockIdx.x == 0 && threadIdx.x == 0) {
-        #pragma unroll
-        for (int k = 0; k < 4; k++) __hip_atomic_store(&host[k], energy[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __threadfence_system();
-        __hip_atomic_store(&host[7], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (host && blockIdx.x == 0 && threadIdx.x == 0) store_step_scalars(host, energy, seq);
 }
 
 // Sharded contexts, two collectives per iteration (include/frog_hip.h frog_transform_points_slab): the transform writes the rank's rows
@@ -118,7 +121,7 @@ __device__ __forceinline__ void write_slab_trailer(const double *energy, double 
 {
     if (trailer && blockIdx.x == 0 && threadIdx.x == 0) {
         #pragma unroll
-        for (int k = 0; k < 4; k++) trailer[k] = energy[k];
+        for (int k = 0; k < N_SCALARS; k++) trailer[k] = energy[k];
     }
 }
 

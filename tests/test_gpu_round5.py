@@ -143,6 +143,57 @@ def test_two_collectives_with_rejected_steps(tmp_path):
     _compare_runs(one, two, pairs.n_images)
 
 
+class _Refusing(ImageGroup):
+    """An ImageGroup whose every step also makes the calls the C ABI must refuse (FROG_E_STATE) where it makes them."""
+
+    def _refused(self, rc, what):
+        assert rc == _abi.FROG_E_STATE, (what, rc)
+
+    def _nothing_pending(self):
+        e = C.c_double()
+        self._refused(self._lib.frog_step_finish(self._ctx, C.byref(e)), "frog_step_finish with nothing pending")
+        self._refused(self._lib.frog_step_speculate(self._ctx), "frog_step_speculate with nothing pending")
+
+    def updateLinearTransforms(self):
+        self._nothing_pending()
+        return super().updateLinearTransforms()
+
+    def updateDeformableTransforms(self, alpha):
+        lib, ctx, e = self._lib, self._ctx, C.c_double()
+        self._nothing_pending()
+        self._refused(lib.frog_deformable_phase_b(ctx), "phase_b before phase_a")
+        self._refused(lib.frog_deformable_phase_c(ctx, C.byref(e)), "phase_c before phase_a")
+        _abi.check(lib.frog_deformable_phase_a(ctx, alpha), "frog_deformable_phase_a")
+        self._refused(lib.frog_comm_mode(ctx, 1), "frog_comm_mode after phase_a")
+        self._refused(lib.frog_deformable_phase_c(ctx, C.byref(e)), "phase_c before phase_b")
+        self._nothing_pending()
+        _abi.check(lib.frog_deformable_phase_b(ctx), "frog_deformable_phase_b")
+        self._refused(lib.frog_comm_mode(ctx, 1), "frog_comm_mode after phase_b")
+        self._refused(lib.frog_deformable_phase_b(ctx), "phase_b twice")
+        self._nothing_pending()
+        _abi.check(lib.frog_deformable_phase_c(ctx, C.byref(e)), "frog_deformable_phase_c")
+        self._nothing_pending()
+        return e.value
+
+
+def test_refused_calls_leave_the_context_untouched():
+    """Calls out of order are refused with FROG_E_STATE and change nothing: a context that makes them between the calls of a short
+    schedule (frog_step_finish and frog_step_speculate with nothing pending, phase B before phase A, phase C before phase B,
+    frog_comm_mode inside a step) prints the energies of a context that does not, and ends on the same coordinates, bit for bit."""
+    pairs = Pairs.synthetic(9, 3000, 1200, seed=4)
+    energies, xyz2 = [], []
+    for cls in (ImageGroup, _Refusing):
+        g = cls(pairs)
+        es = []
+        schedule.run([g], 4, [10], on=lambda tag, sides, e=None, infos=None: es.append(e[0]) if e is not None else None)
+        energies.append(es)
+        xyz2.append(g.points()[1].copy())
+        g.close()
+    assert len(energies[0]) >= 4 + 10 + 10       # a deformable step is reported before the guard's branch and, accepted, after it
+    assert energies[1] == energies[0]
+    assert np.array_equal(xyz2[0], xyz2[1])
+
+
 # ---- sampled timing of the sweeps (frog_profile_enable(ctx, 3)) ------------------------------------------------------------
 
 @pytest.mark.gpu

@@ -163,6 +163,21 @@ def test_two_collectives_flow_with_the_scalars_by_copy(tmp_path):
     _same_files(direct, copy, pairs.n_images)
 
 
+def test_one_context_with_the_scalars_by_copy_and_rejected_steps(tmp_path):
+    """The same fallback in ONE context: frog_deformable_phase_c then gets the step's scalars by hipMemcpyAsync + event instead of
+    from the transform queued behind the step.  With -gm 0.004 the guard rejects steps either way: same files, same rejections."""
+    pairs = Pairs.synthetic(9, 3000, 1200, seed=4)
+    direct, copy = tmp_path / "direct", tmp_path / "copy"
+    for d in (direct, copy):
+        d.mkdir()
+        pairs.write(d / "pairs.bin")
+    flags = ("-gm", "0.004")
+    out_direct = _frog(direct, *flags)
+    out_copy = _frog(copy, *flags, env_extra={"FROG_SCALARS_COPY": "1"})
+    assert out_direct.count("Iteration canceled") >= 2 and out_copy.count("Iteration canceled") >= 2
+    _same_files(direct, copy, pairs.n_images)
+
+
 # ---- (4) fine lattices of many images: blocks of 16 nodes across the images, entries for active pairs only (k_grid.hip.h) ------------
 
 @pytest.mark.parametrize("flags", [(), ("-ngl", "3"), ("-gm", "0.004")])
