@@ -212,6 +212,17 @@ def grid_triplet(origin, spacing, dims):
     return (C.c_double * 3)(*origin), (C.c_double * 3)(*spacing), (C.c_uint32 * 3)(*dims)
 
 
+class FrogScoreSums(C.Structure):
+    """frog_score_sums (include/frog_chain.h)."""
+    _fields_ = [("n", C.c_uint64), ("n_nonfinite", C.c_uint64), ("sx", C.c_double), ("sy", C.c_double), ("sxx", C.c_double),
+                ("syy", C.c_double), ("sxy", C.c_double), ("sad", C.c_double)]
+
+
+class FrogScoreMetrics(C.Structure):
+    """frog_score_metrics (include/frog_host.h)."""
+    _fields_ = [("ncc", C.c_double), ("mean_abs_diff", C.c_double), ("rmse", C.c_double), ("mi", C.c_double), ("nmi", C.c_double)]
+
+
 class FrogChainLink(C.Structure):
     """frog_chain_link (include/frog_chain.h)."""
     _fields_ = [("type", C.c_int), ("matrix", C.c_double * 16), ("dims", C.c_uint32 * 3), ("origin", C.c_double * 3),
@@ -280,6 +291,9 @@ HIP_SYMBOLS = {
     "frog_cover_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double,
                                  C.POINTER(FrogVolume)]),
     "frog_cover_finish": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, c_float_p, c_float_p, C.POINTER(C.c_uint16)]),
+    "frog_cover_score": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double,
+                                   C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_float, C.POINTER(FrogScoreSums),
+                                   C.POINTER(C.c_uint64)]),
     "frog_cover_destroy": (None, [C.c_void_p]),
     "frog_labels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_labels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
@@ -361,6 +375,7 @@ HOST_SYMBOLS = {
     "frog_volume_range": (C.c_int, [C.POINTER(FrogVolume), c_double_p, c_double_p]),
     "frog_volume_write": (C.c_int, [C.c_char_p, C.POINTER(FrogVolume)]),
     "frog_bbox_grid": (C.c_int, [C.c_char_p, C.c_double, C.POINTER(FrogVolume)]),
+    "frog_score_metrics_from": (C.c_int, [C.POINTER(FrogScoreSums), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(FrogScoreMetrics)]),
     "frog_keypoints_read": (C.c_void_p, [C.c_char_p, C.POINTER(C.c_int)]),
     "frog_keypoints_free": (None, [C.c_void_p]),
     "frog_keypoints_count": (C.c_uint32, [C.c_void_p]),

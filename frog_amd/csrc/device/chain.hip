@@ -418,6 +418,18 @@ struct MaskGrid {
     double so[3], ss[3];
 };
 
+// Whether the mask counts position p (after the chain): inside the mask's own geometry and its nearest voxel non-zero.
+__device__ __forceinline__ bool mask_covers(const double p[3], const uint8_t *__restrict__ mask, const MaskGrid &mg)
+{
+    double c[3];
+    if (!voxel_coordinates(p, mg.so, mg.ss, mg.sx, mg.sy, mg.sz, c)) return false;
+    int x = (int)floor(c[0] + 0.5), y = (int)floor(c[1] + 0.5), z = (int)floor(c[2] + 0.5);
+    x = x < 0 ? 0 : (x >= mg.sx ? mg.sx - 1 : x);
+    y = y < 0 ? 0 : (y >= mg.sy ? mg.sy - 1 : y);
+    z = z < 0 ? 0 : (z >= mg.sz ? mg.sz - 1 : z);
+    return mask[(size_t)x + (size_t)mg.sx * ((size_t)y + (size_t)mg.sy * (size_t)z)] != 0;
+}
+
 // The chain is evaluated once: the position it gives is turned into the source's voxel coordinates (reslice_sample, the code
 // of reslice_kernel, gives the value and `out`) and, where the source covers it, into the mask's, whose nearest voxel
 // (floor(c + 0.5), as a nearest-neighbour reslice reads it) decides.
@@ -435,16 +447,7 @@ __global__ __launch_bounds__(256) void cover_reslice_kernel(size_t base, const D
     bool valid = voxel_coordinates(p, g.so, g.ss, g.sx, g.sy, g.sz, c);
     const S r = reslice_sample<S>(src, g, c, valid);
     if (out) out[idx] = r;
-    if (valid && mask) {
-        valid = voxel_coordinates(p, mg.so, mg.ss, mg.sx, mg.sy, mg.sz, c);
-        if (valid) {
-            int x = (int)floor(c[0] + 0.5), y = (int)floor(c[1] + 0.5), z = (int)floor(c[2] + 0.5);
-            x = x < 0 ? 0 : (x >= mg.sx ? mg.sx - 1 : x);
-            y = y < 0 ? 0 : (y >= mg.sy ? mg.sy - 1 : y);
-            z = z < 0 ? 0 : (z >= mg.sz ? mg.sz - 1 : z);
-            valid = mask[(size_t)x + (size_t)mg.sx * ((size_t)y + (size_t)mg.sy * (size_t)z)] != 0;
-        }
-    }
+    if (valid && mask) valid = mask_covers(p, mask, mg);
     if (valid) cover_update(mean, m2, count, idx, (float)r);
 }
 
@@ -476,6 +479,132 @@ __global__ __launch_bounds__(256) void cover_finish_kernel(size_t base, const fl
         }
         out_stdev[idx] = s;
     }
+}
+
+// ---- one image against the accumulator's mean (frog_cover_score) ------------------------------------------------------------
+// A reduction over the volume instead of a volume: per voxel the value x the add would have used and the reference y formed
+// from the held mean and count, six f64 sums and two counts per TILE of SCORE_TILE consecutive voxels, and a joint histogram.
+// No floating-point atomic anywhere: the order of every f64 addition is the one include/frog_chain.h states (thread, then
+// the wave's shuffle tree, then the four waves, then -- on the host -- the tiles), and a block is a tile whatever the launch
+// chunk, so the sums do not depend on scheduling or on FROG_CHAIN_LAUNCH_MAX.  The histogram is integer: one u32 image in LDS
+// per block, LDS atomics, one 64-bit global atomic per non-zero bin and block.
+constexpr int SCORE_ITEMS = 8;                              // voxels per thread
+constexpr size_t SCORE_TILE = SCORE_ITEMS * 256;            // voxels per block
+
+struct ScorePartial {           // one tile: seven 8-byte words
+    double s[6];                // sx sy sxx syy sxy sad
+    uint32_t n, n_nonfinite;
+};
+
+struct ScoreParams {
+    uint32_t need;              // the smallest count that takes part: max(2 or 1, min_count)
+    int leave_one_out;
+    uint32_t bins;              // 0: no histogram
+    float lo, scale;            // scale = (float)bins / (hi - lo)
+};
+
+// min(bins - 1, max(0, floorf((t - lo) * scale))), clamped before the conversion to int (t may be +-inf after a cast)
+__device__ __forceinline__ uint32_t score_bin(const ScoreParams &sp, float t)
+{
+    const float d = t - sp.lo;
+    const float f = floorf(d * sp.scale);
+    return !(f >= 0.0f) ? 0u : (f >= (float)sp.bins ? sp.bins - 1u : (uint32_t)f);
+}
+
+// one voxel whose image is valid there: x against the accumulator's (m, k)
+__device__ __forceinline__ void score_voxel(const ScoreParams &sp, float x, float m, uint32_t k, ScorePartial &acc, uint32_t *hist)
+{
+    if (k < sp.need) return;
+    const double xd = (double)x;
+    double y = (double)m;
+    if (sp.leave_one_out) {
+        const double mk = y * (double)k;
+        const double others = mk - xd;
+        y = others / (double)(k - 1u);
+    }
+    if (!(isfinite(xd) && isfinite(y))) { acc.n_nonfinite++; return; }
+    const double xx = xd * xd, yy = y * y, xy = xd * y, diff = xd - y;
+    acc.n++;
+    acc.s[0] += xd; acc.s[1] += y; acc.s[2] += xx; acc.s[3] += yy; acc.s[4] += xy; acc.s[5] += fabs(diff);
+    if (sp.bins) atomicAdd(&hist[score_bin(sp, x) * sp.bins + score_bin(sp, (float)y)], 1u);
+}
+
+// The block's end: lane 0 of each wave gets the wave's sums by __shfl_down 32, 16, 8, 4, 2, 1, thread 0 adds the four waves
+// in ascending order into partials[tile], and the LDS histogram's non-zero bins go to the device histogram.
+__device__ __forceinline__ void score_block_end(ScorePartial &acc, size_t tile, uint32_t cells, const uint32_t *hist,
+                                                ScorePartial *__restrict__ partials, unsigned long long *__restrict__ histogram)
+{
+    __shared__ ScorePartial waves[4];
+    for (int h = 32; h > 0; h >>= 1) {
+        for (int q = 0; q < 6; q++) acc.s[q] += __shfl_down(acc.s[q], h);
+        acc.n += __shfl_down(acc.n, h);
+        acc.n_nonfinite += __shfl_down(acc.n_nonfinite, h);
+    }
+    if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = acc;
+    __syncthreads();                                        // also: every LDS histogram update of the block is done
+    if (threadIdx.x == 0) {
+        ScorePartial t = waves[0];
+        for (int w = 1; w < 4; w++) {
+            for (int q = 0; q < 6; q++) t.s[q] += waves[w].s[q];
+            t.n += waves[w].n;
+            t.n_nonfinite += waves[w].n_nonfinite;
+        }
+        partials[tile] = t;
+    }
+    for (uint32_t b = threadIdx.x; b < cells; b += 256) {
+        const uint32_t c = hist[b];
+        if (c) atomicAdd(&histogram[b], (unsigned long long)c);
+    }
+}
+
+// validity and value exactly as cover_reslice_kernel forms them; thread t of tile T takes voxels T * SCORE_TILE + j * 256 + t
+template <class S>
+__global__ __launch_bounds__(256) void cover_score_kernel(size_t base, const DevLink *links, int n_links, const S *__restrict__ src,
+                                                          const ResliceGrid g, const uint8_t *__restrict__ mask, const MaskGrid mg,
+                                                          const float *__restrict__ mean, const uint16_t *__restrict__ count,
+                                                          const ScoreParams sp, ScorePartial *__restrict__ partials,
+                                                          unsigned long long *__restrict__ histogram)
+{
+    extern __shared__ uint32_t score_hist[];
+    const size_t total = (size_t)g.out.dims[0] * g.out.dims[1] * g.out.dims[2];
+    const size_t tile = base / 256 + blockIdx.x;
+    const uint32_t cells = sp.bins * sp.bins;
+    for (uint32_t b = threadIdx.x; b < cells; b += 256) score_hist[b] = 0;
+    __syncthreads();
+    ScorePartial acc{};
+#pragma unroll 1
+    for (int j = 0; j < SCORE_ITEMS; j++) {
+        const size_t idx = tile * SCORE_TILE + (size_t)j * 256 + threadIdx.x;
+        if (idx >= total) break;
+        double p[3], c[3];
+        reslice_position(links, n_links, g.out, idx, p);
+        bool valid = voxel_coordinates(p, g.so, g.ss, g.sx, g.sy, g.sz, c);
+        const S r = reslice_sample<S>(src, g, c, valid);
+        if (valid && mask) valid = mask_covers(p, mask, mg);
+        if (valid) score_voxel(sp, (float)r, mean[idx], count[idx], acc, score_hist);
+    }
+    score_block_end(acc, tile, cells, score_hist, partials, histogram);
+}
+
+// a source (and a mask) already on the grid: every voxel is inside
+template <class S>
+__global__ __launch_bounds__(256) void cover_score_identity_kernel(size_t base, const S *__restrict__ src, const uint8_t *__restrict__ mask,
+                                                                   size_t total, const float *__restrict__ mean,
+                                                                   const uint16_t *__restrict__ count, const ScoreParams sp,
+                                                                   ScorePartial *__restrict__ partials, unsigned long long *__restrict__ histogram)
+{
+    extern __shared__ uint32_t score_hist[];
+    const size_t tile = base / 256 + blockIdx.x;
+    const uint32_t cells = sp.bins * sp.bins;
+    for (uint32_t b = threadIdx.x; b < cells; b += 256) score_hist[b] = 0;
+    __syncthreads();
+    ScorePartial acc{};
+#pragma unroll
+    for (int j = 0; j < SCORE_ITEMS; j++) {
+        const size_t idx = tile * SCORE_TILE + (size_t)j * 256 + threadIdx.x;
+        if (idx < total && (!mask || mask[idx] != 0)) score_voxel(sp, (float)src[idx], mean[idx], count[idx], acc, score_hist);
+    }
+    score_block_end(acc, tile, cells, score_hist, partials, histogram);
 }
 
 __global__ __launch_bounds__(256) void chain_apply_kernel(size_t base, const DevLink *links, int n_links, const double *in, double *out, size_t n)
@@ -970,6 +1099,59 @@ int cover_add_typed(frog_cover *a, frog_chain *c, const frog_volume *src, const 
     return FROG_OK;
 }
 
+template <class S>
+int cover_score_typed(frog_cover *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background,
+                      const ScoreParams &sp, frog_score_sums *sums, uint64_t *histogram)
+{
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    const size_t n_mask = mask ? (size_t)mask->dims[0] * mask->dims[1] * mask->dims[2] : 0;
+    const size_t tiles = (a->total + SCORE_TILE - 1) / SCORE_TILE, cells = (size_t)sp.bins * sp.bins;
+    frog::DevBuf<ScorePartial> d_partials;
+    frog::DevBuf<unsigned long long> d_hist;
+    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
+    if (mask) KCHECK(a->d_mask.alloc(n_mask));
+    KCHECK(d_partials.alloc(tiles));
+    if (cells) KCHECK(d_hist.alloc(cells));
+    const S *d_src = (const S *)a->d_src.p;
+    const uint8_t *d_mask = mask ? a->d_mask.p : nullptr;
+    std::vector<ScorePartial> partials(tiles);
+    hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
+    if (e == hipSuccess && mask) e = hipMemcpy(a->d_mask.p, a->h_mask.data(), n_mask, hipMemcpyHostToDevice);
+    if (e == hipSuccess && cells) e = hipMemset(d_hist.p, 0, cells * sizeof(unsigned long long));
+    if (e == hipSuccess) {
+        const ResliceGrid g = reslice_grid(src, &a->grid, interpolation, background);
+        MaskGrid mg{};
+        if (mask) {
+            mg.sx = (int)mask->dims[0]; mg.sy = (int)mask->dims[1]; mg.sz = (int)mask->dims[2];
+            for (int k = 0; k < 3; k++) { mg.so[k] = mask->origin[k]; mg.ss[k] = mask->spacing[k]; }
+        }
+        const size_t lds = cells * sizeof(uint32_t);
+        // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
+        e = chunked_launch(tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
+            if (c)
+                cover_score_kernel<S><<<blocks, LAUNCH_BLOCK, lds>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg,
+                                                                     a->d_mean.p, a->d_count.p, sp, d_partials.p, d_hist.p);
+            else
+                cover_score_identity_kernel<S><<<blocks, LAUNCH_BLOCK, lds>>>(base, d_src, d_mask, a->total, a->d_mean.p, a->d_count.p, sp,
+                                                                              d_partials.p, d_hist.p);
+        });
+    }
+    if (e == hipSuccess) e = hipMemcpy(partials.data(), d_partials.p, tiles * sizeof(ScorePartial), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && cells) e = hipMemcpy(histogram, d_hist.p, cells * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_cover_score", e);
+    // the last pass of the stated order: the tiles in ascending index, serially, f64 (this file is built with -ffp-contract=off)
+    frog_score_sums t{};
+    double s[6] = { 0, 0, 0, 0, 0, 0 };
+    for (const ScorePartial &p : partials) {
+        for (int q = 0; q < 6; q++) s[q] += p.s[q];
+        t.n += p.n;
+        t.n_nonfinite += p.n_nonfinite;
+    }
+    t.sx = s[0]; t.sy = s[1]; t.sxx = s[2]; t.syy = s[3]; t.sxy = s[4]; t.sad = s[5];
+    *sums = t;
+    return FROG_OK;
+}
+
 // h_mask = (value != 0) of an integer mask volume
 template <class M>
 void cover_mask_bytes(frog_cover *a, const frog_volume *mask)
@@ -978,6 +1160,37 @@ void cover_mask_bytes(frog_cover *a, const frog_volume *mask)
     const M *v = (const M *)mask->data;
     a->h_mask.resize(n);
     for (size_t i = 0; i < n; i++) a->h_mask[i] = v[i] != 0;
+}
+
+// the mask of an add or a score as bytes in a->h_mask
+void cover_mask(frog_cover *a, const frog_volume *mask)
+{
+    switch (mask->dtype) {
+    case FROG_V_U8: cover_mask_bytes<uint8_t>(a, mask); break;
+    case FROG_V_I8: cover_mask_bytes<int8_t>(a, mask); break;
+    case FROG_V_U16: cover_mask_bytes<uint16_t>(a, mask); break;
+    case FROG_V_I16: cover_mask_bytes<int16_t>(a, mask); break;
+    case FROG_V_U32: cover_mask_bytes<uint32_t>(a, mask); break;
+    default: cover_mask_bytes<int32_t>(a, mask); break;
+    }
+}
+
+// what frog_cover_add and frog_cover_score refuse alike: the chain's device, the mask's type, the geometry
+int cover_inputs(const frog_cover *a, const frog_chain *c, const frog_volume *src, const frog_volume *mask, const char *where)
+{
+    const std::string w = std::string(where) + ": ";
+    if (c && c->device != a->device) return fail(FROG_E_INVALID, w + "chain and accumulator on different devices");
+    if (mask && !mask->data) return fail(FROG_E_INVALID, w + "a mask without voxels");
+    if (mask && (mask->dtype < FROG_V_U8 || mask->dtype > FROG_V_I32)) return fail(FROG_E_INVALID, w + "a mask has an integer type");
+    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    if (!n_src || (mask && !((size_t)mask->dims[0] * mask->dims[1] * mask->dims[2]))) return fail(FROG_E_INVALID, "empty volume");
+    for (int k = 0; k < 3; k++) {
+        if (c && (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad source geometry");
+        if (c && mask && (mask->dims[k] > 0x7FFFFFFFu || !(mask->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad mask geometry");
+        if (!c && src->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, w + "volume dimensions differ from the grid's");
+        if (!c && mask && mask->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, w + "mask dimensions differ from the grid's");
+    }
+    return FROG_OK;
 }
 
 // The device map rebuilt from the known labels alone (at creation: empty): how a refused volume's inserts are taken back.
@@ -1345,33 +1558,39 @@ int frog_cover_add(frog_cover *a, frog_chain *c, const frog_volume *src, const f
 {
     if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_cover_add");
     if (a->added >= 65535) return fail(FROG_E_INVALID, "frog_cover_add: more than 65535 volumes (16-bit counts)");
-    if (c && c->device != a->device) return fail(FROG_E_INVALID, "frog_cover_add: chain and accumulator on different devices");
-    if (mask && !mask->data) return fail(FROG_E_INVALID, "frog_cover_add: a mask without voxels");
-    if (mask && (mask->dtype < FROG_V_U8 || mask->dtype > FROG_V_I32)) return fail(FROG_E_INVALID, "frog_cover_add: a mask has an integer type");
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    if (!n_src || (mask && !((size_t)mask->dims[0] * mask->dims[1] * mask->dims[2]))) return fail(FROG_E_INVALID, "empty volume");
-    for (int k = 0; k < 3; k++) {
-        if (c && (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad source geometry");
-        if (c && mask && (mask->dims[k] > 0x7FFFFFFFu || !(mask->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad mask geometry");
-        if (!c && src->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_cover_add: volume dimensions differ from the grid's");
-        if (!c && mask && mask->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_cover_add: mask dimensions differ from the grid's");
+    if (int rc = cover_inputs(a, c, src, mask, "frog_cover_add")) return rc;
+    for (int k = 0; k < 3; k++)
         if (resliced && resliced->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_cover_add: resliced volume is not grid-sized");
-    }
     if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, "frog_cover_add: resliced volume must have the source's type");
-    if (mask) {
-        switch (mask->dtype) {
-        case FROG_V_U8: cover_mask_bytes<uint8_t>(a, mask); break;
-        case FROG_V_I8: cover_mask_bytes<int8_t>(a, mask); break;
-        case FROG_V_U16: cover_mask_bytes<uint16_t>(a, mask); break;
-        case FROG_V_I16: cover_mask_bytes<int16_t>(a, mask); break;
-        case FROG_V_U32: cover_mask_bytes<uint32_t>(a, mask); break;
-        default: cover_mask_bytes<int32_t>(a, mask); break;
-        }
-    }
+    if (mask) cover_mask(a, mask);
     KCHECK(hipSetDevice(a->device));
     const int rc = with_voxel_type(src->dtype, [&](auto s) { return cover_add_typed<decltype(s)>(a, c, src, mask, interpolation, background, resliced); });
     if (rc == FROG_OK) a->added++;
     return rc;
+}
+
+int frog_cover_score(frog_cover *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background,
+                     uint32_t min_count, int leave_one_out, uint32_t bins, float lo, float hi, frog_score_sums *sums, uint64_t *histogram)
+{
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype) || !sums) return fail(FROG_E_INVALID, "bad arguments to frog_cover_score");
+    if (int rc = cover_inputs(a, c, src, mask, "frog_cover_score")) return rc;
+    if (!a->added) return fail(FROG_E_INVALID, "frog_cover_score: before the first frog_cover_add");
+    if (!min_count) return fail(FROG_E_INVALID, "frog_cover_score: min_count must be at least 1");
+    ScoreParams sp{};
+    sp.leave_one_out = leave_one_out != 0;
+    sp.need = std::max(sp.leave_one_out ? 2u : 1u, min_count);
+    if (bins || histogram) {
+        if (!histogram || bins < 2 || bins > 64) return fail(FROG_E_INVALID, "frog_cover_score: 2 to 64 bins and a histogram, or neither");
+        const float width = hi - lo;
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo) || !std::isfinite(width))
+            return fail(FROG_E_INVALID, "frog_cover_score: the histogram needs a finite range with hi > lo");
+        sp.bins = bins;
+        sp.lo = lo;
+        sp.scale = (float)bins / width;
+    }
+    if (mask) cover_mask(a, mask);
+    KCHECK(hipSetDevice(a->device));
+    return with_voxel_type(src->dtype, [&](auto s) { return cover_score_typed<decltype(s)>(a, c, src, mask, interpolation, background, sp, sums, histogram); });
 }
 
 int frog_cover_finish(frog_cover *a, uint32_t min_count, float fill, float *mean, float *stdev, uint16_t *count)

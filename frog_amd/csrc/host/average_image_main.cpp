@@ -2,7 +2,7 @@
 // DummyVolumeGenerator, one VolumeTransform per image and AverageVolumes, without writing and re-reading N volumes and
 // without N + 2 HIP runtime starts.
 //   AverageImage bbox.json spacing v_0 ... v_{N-1} [-td transformsDir] [-o outDir] [-i interpolation] [-b background]
-//                [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]]
+//                [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]] [-q 1 [-qb bins] [-qr lo hi]]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid); image i is resliced through the inverse of <transformsDir>/<i>.json
 // (default "transforms"; -j and sidecar forms) exactly as `VolumeTransform v_i dummy.mhd -t transforms/i.json` does it
 // (same device code; background = the image's minimum unless -b, linear unless -i 0), converted to its own type and added
@@ -16,6 +16,15 @@
 // image i then counts only where mask i, an integer volume of its own geometry, is non-zero at the nearest voxel; the masks
 // are streamed like the images.  -mc: voxels that fewer than minCount (default 1) images cover get the mean -f (default 0)
 // and the stdev 0.  -ml, -mc or -f without -c 1 is an error.  transformed<i>.nii.gz is the same file either way.
+// -q 1 (with -c 1; which images registered badly?): after the average is written the images and masks are streamed a second
+// time, in the same order, and each is scored against the mean of the OTHER images over the voxels it covers and at least
+// max(2, minCount) images do (frog_cover_score with leave_one_out, frog_score_metrics_from).  quality.csv in outDir has one
+// row per image: image,file,voxels,covered_fraction,ncc,nmi,mi,mean_abs_diff,rmse,ncc_robust_z -- voxels = the voxels that
+// entered the sums, covered_fraction = voxels / grid voxels, ncc_robust_z = (ncc - median) / (1.4826 MAD) over the group's
+// finite nccs (0 where the MAD is 0; the median of an even number is the mean of the middle two); doubles as %.17g, NaN as
+// nan.  -qb: bins per axis of the joint histogram behind mi and nmi (2..64, default 64).  -qr lo hi: its value range, by
+// default the smallest finite value of the mean over the voxels that minCount images cover and the float after the largest;
+// the range used is printed.  The average's files and the first pass are the same with and without -q 1.
 #include "tool_common.h"
 #include "volume_stream.h"
 
@@ -23,7 +32,9 @@
 #include <cerrno>
 #include <zlib.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -76,6 +87,23 @@ bool read_list(const std::string &path, std::vector<std::string> &lines)
     return true;
 }
 
+// the median of a non-empty list: the middle value, or the mean of the middle two
+double median(std::vector<double> v)
+{
+    std::sort(v.begin(), v.end());
+    const size_t n = v.size();
+    return n % 2 ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0;
+}
+
+// %.17g, which reads back to the same double; a NaN of either sign as "nan"
+std::string csv_double(double v)
+{
+    if (std::isnan(v)) return "nan";
+    char buf[40];
+    std::snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
 } // namespace
 
 int main(int argc, char *argv[])
@@ -87,13 +115,14 @@ int main(int argc, char *argv[])
     auto die = [](const std::string &what) { std::cout << "Error : " << what << std::endl; std::_Exit(1); };
     std::vector<std::string> volumes;
     std::string transformsDir = "transforms", outDir = ".", maskList;
-    int interpolation = 1, device = 0, writeTransformed = 0, coverage = 0;
-    long minCount = 1;
-    float fill = 0;
+    int interpolation = 1, device = 0, writeTransformed = 0, coverage = 0, quality = 0;
+    long minCount = 1, qualityBins = 64;
+    float fill = 0, qualityLo = 0, qualityHi = 0;
+    bool qualityOption = false, qualityRange = false;       // -qb or -qr was given; -qr was given
     bool coverageOption = false;                            // -ml, -mc or -f was given
     BackgroundLevel background;
     auto is_flag = [](const char *a) {
-        for (const char *f : { "-td", "-o", "-i", "-b", "-wt", "-dev", "-c", "-ml", "-mc", "-f" }) if (std::strcmp(a, f) == 0) return true;
+        for (const char *f : { "-td", "-o", "-i", "-b", "-wt", "-dev", "-c", "-ml", "-mc", "-f", "-q", "-qb", "-qr" }) if (std::strcmp(a, f) == 0) return true;
         return false;
     };
     int a = 3;
@@ -110,16 +139,29 @@ int main(int argc, char *argv[])
         else if (std::strcmp(key, "-ml") == 0) { maskList = value; coverageOption = true; }
         else if (std::strcmp(key, "-mc") == 0) { minCount = atol(value); coverageOption = true; }
         else if (std::strcmp(key, "-f") == 0) { fill = (float)atof(value); coverageOption = true; }
+        else if (std::strcmp(key, "-q") == 0) quality = atoi(value);
+        else if (std::strcmp(key, "-qb") == 0) { qualityBins = atol(value); qualityOption = true; }
+        else if (std::strcmp(key, "-qr") == 0) {            // two values
+            qualityLo = (float)atof(value);
+            qualityHi = (float)atof(a + 2 < argc ? argv[a + 2] : "");
+            qualityOption = qualityRange = true;
+            a++;
+        }
         else die(std::string("unknown option ") + key);
     }
     if (argc < 4 || volumes.empty()) {
         std::cout << "Usage : AverageImage bbox.json spacing image_0 ... image_N-1 [-td transformsDir] [-o outDir] [-i interpolation] "
-                     "[-b background] [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]]" << std::endl;
+                     "[-b background] [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]] [-q 1 [-qb bins] [-qr lo hi]]" << std::endl;
         return 1;
     }
     const size_t n = volumes.size();
     if (coverageOption && coverage != 1) die("-ml, -mc and -f need -c 1");
     if (minCount < 1 || minCount > 65535) die("-mc takes a count from 1 to 65535");
+    if (quality == 1 && coverage != 1) die("-q 1 scores the images against the coverage-aware average: it needs -c 1");
+    if (qualityOption && quality != 1) die("-qb and -qr need -q 1");
+    if (qualityBins < 2 || qualityBins > 64) die("-qb takes 2 to 64 bins");
+    if (qualityRange && !(std::isfinite(qualityLo) && std::isfinite(qualityHi) && qualityHi > qualityLo && std::isfinite(qualityHi - qualityLo)))
+        die("-qr takes two finite values lo < hi");
     if (coverage == 1 && n > 65535) die("-c 1 takes at most 65535 images (16-bit counts)");
     std::vector<std::string> masks;
     if (!maskList.empty()) {
@@ -195,8 +237,10 @@ int main(int argc, char *argv[])
         device_s += seconds(t0);
         stream.release(i);
         if (maskStream) maskStream->release(i);
-        frog_chain_destroy(chains[i]);
-        chains[i] = nullptr;
+        if (quality != 1) {                                 // the second pass evaluates the chain again
+            frog_chain_destroy(chains[i]);
+            chains[i] = nullptr;
+        }
         if (out) {
             t0 = clk::now();
             const std::string name = outDir + "/transformed" + std::to_string(i) + ".nii.gz";
@@ -220,18 +264,84 @@ int main(int argc, char *argv[])
         if (frog_volume_write(path.c_str(), &grid)) die("cannot write " + path);
     }
     if (cover) {
-        frog_cover_destroy(cover);
         grid.dtype = FROG_V_U16;
         grid.data = count.data();
         const std::string path = outDir + "/coverage.nii.gz";
         if (frog_volume_write(path.c_str(), &grid)) die("cannot write " + path);
     }
     write_s += seconds(t0);
+
+    // ---- -q 1: every image against the mean of the others, the files streamed once more in the same order
+    double quality_s = 0;
+    if (quality == 1) {
+        t0 = clk::now();
+        if (!qualityRange) {
+            bool any = false;
+            for (size_t v = 0; v < total; v++) {
+                if (count[v] < minCount || !std::isfinite(mean[v])) continue;
+                if (!any || mean[v] < qualityLo) qualityLo = mean[v];
+                if (!any || mean[v] > qualityHi) qualityHi = mean[v];
+                any = true;
+            }
+            if (!any) die("-q 1: no voxel with a finite mean that " + std::to_string(minCount) + " images cover");
+            qualityHi = std::nextafterf(qualityHi, INFINITY);
+        }
+        std::cout << "quality : " << qualityBins << " x " << qualityBins << " bins over [" << csv_double(qualityLo) << ", " << csv_double(qualityHi) << ")" << std::endl;
+        frog::VolumeStream again(volumes, threads, window);
+        std::unique_ptr<frog::VolumeStream> maskAgain(masks.empty() ? nullptr : new frog::VolumeStream(masks, threads, window));
+        std::vector<frog_score_sums> sums(n);
+        std::vector<frog_score_metrics> metrics(n);
+        std::vector<uint64_t> histogram((size_t)qualityBins * qualityBins);
+        for (size_t i = 0; i < n; i++) {
+            frog::VolumeStream::Item &it = again.get(i, nullptr);
+            if (!it.file) die("cannot read volume " + volumes[i]);
+            const frog_volume *mask = nullptr;
+            if (maskAgain) {
+                frog::VolumeStream::Item &m = maskAgain->get(i, nullptr);
+                if (!m.file) die("cannot read mask " + masks[i]);
+                mask = &m.view;
+            }
+            if (frog_cover_score(cover, chains[i], &it.view, mask, interpolation, background.of(it.lo), (uint32_t)minCount, 1,
+                                 (uint32_t)qualityBins, qualityLo, qualityHi, &sums[i], histogram.data())
+                || frog_score_metrics_from(&sums[i], histogram.data(), (uint32_t)qualityBins, &metrics[i]))
+                die(volumes[i] + ": " + frog_last_error());
+            again.release(i);
+            if (maskAgain) maskAgain->release(i);
+            frog_chain_destroy(chains[i]);
+            chains[i] = nullptr;
+        }
+        std::vector<double> finite;
+        for (const auto &m : metrics) if (std::isfinite(m.ncc)) finite.push_back(m.ncc);
+        double mid = 0, mad = 0;
+        if (!finite.empty()) {
+            mid = median(finite);
+            for (double &v : finite) v = std::fabs(v - mid);
+            mad = median(finite);
+        }
+        const std::string path = outDir + "/quality.csv";
+        std::ofstream csv(path);
+        csv << "image,file,voxels,covered_fraction,ncc,nmi,mi,mean_abs_diff,rmse,ncc_robust_z\n";
+        for (size_t i = 0; i < n; i++) {
+            const frog_score_metrics &m = metrics[i];
+            const double z = !std::isfinite(m.ncc) ? NAN : (mad > 0 ? (m.ncc - mid) / (1.4826 * mad) : 0.0);
+            csv << i << "," << volumes[i] << "," << sums[i].n << "," << csv_double((double)sums[i].n / (double)total) << "," << csv_double(m.ncc)
+                << "," << csv_double(m.nmi) << "," << csv_double(m.mi) << "," << csv_double(m.mean_abs_diff) << "," << csv_double(m.rmse)
+                << "," << csv_double(z) << "\n";
+        }
+        csv.close();
+        if (!csv) die("cannot write " + path);
+        quality_s = seconds(t0);
+    }
+    frog_cover_destroy(cover);
     char line[512];
     std::snprintf(line, sizeof line,
                   "read : %.3f s of %d host threads (device waited %.3f s)\ndevice : %.3f s (+ %.3f s set-up)\nwrite : %.3f s\ntotal : %.3f s",
                   stream.read_seconds() + (maskStream ? maskStream->read_seconds() : 0.0),
                   stream.threads() + (maskStream ? maskStream->threads() : 0), waited_s, device_s, setup_s, write_s, seconds(t_start));
     std::cout << line << std::endl;
+    if (quality == 1) {
+        std::snprintf(line, sizeof line, "quality : %.3f s", quality_s);
+        std::cout << line << std::endl;
+    }
     return 0;
 }

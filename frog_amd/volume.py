@@ -180,6 +180,51 @@ class CoverAverage:
                    "frog_cover_finish")
         return mean, stdev, count
 
+    def score(self, volume, chain=None, mask=None, interpolation=1, background=None, min_count=1, leave_one_out=True, bins=64,
+              value_range=None):
+        """One image against the accumulator's mean (frog_cover_score), over the voxels where add() with the same `volume`,
+        `chain`, `mask` and `interpolation` counts it and at least max(2 if leave_one_out else 1, min_count) images do.
+        leave_one_out: the image is one of the adds and is taken out of the mean again; False for an image that is not.
+        `background` (default the volume's minimum) never enters a sum.  bins=0: no histogram; else `value_range` = (lo, hi)
+        of the bins x bins joint histogram (row = the image's bin), default quality_range(min_count).  Returns a dict: the
+        sums n, n_nonfinite, sx, sy, sxx, syy, sxy, sad; covered_fraction = n / grid voxels; `histogram` (uint64, (bins,
+        bins)) or None; and ncc, mean_abs_diff, rmse, mi, nmi from frog_score_metrics_from.  Leaves the accumulator as it is."""
+        a, o, s = _as_volume(volume)
+        src = _abi.volume_view(a, o, s)
+        mv = None
+        if mask is not None:
+            m, mo, ms = _as_volume(mask)
+            mv = _abi.volume_view(m, mo, ms)
+        if background is None:
+            background = float(a.min())
+        bins = int(bins)
+        hist, lo, hi = None, 0.0, 0.0
+        if bins:
+            lo, hi = self.quality_range(min_count) if value_range is None else value_range
+            hist = np.zeros((bins, bins), np.uint64)
+        hist_p = hist.ctypes.data_as(C.POINTER(C.c_uint64)) if hist is not None else None
+        sums = _abi.FrogScoreSums()
+        _abi.check(self._lib.frog_cover_score(self._h, chain._h if chain is not None else None, C.byref(src),
+                                              C.byref(mv) if mv is not None else None, int(interpolation), float(background),
+                                              int(min_count), int(bool(leave_one_out)), bins, float(lo), float(hi), C.byref(sums),
+                                              hist_p), "frog_cover_score")
+        metrics = _abi.FrogScoreMetrics()
+        _abi.check(_abi.host_lib().frog_score_metrics_from(C.byref(sums), hist_p, bins, C.byref(metrics)), "frog_score_metrics_from")
+        out = {name: getattr(sums, name) for name, _ in sums._fields_}
+        out["covered_fraction"] = sums.n / float(np.prod(self.dims))
+        out["histogram"] = hist
+        out.update({name: getattr(metrics, name) for name, _ in metrics._fields_})
+        return out
+
+    def quality_range(self, min_count=1):
+        """The default histogram range of score(), and of bin/AverageImage -q 1: (lo, hi) = the smallest finite value of the
+        mean over the voxels with count >= min_count, and the float32 after the largest."""
+        mean, _, count = self.finish(min_count)
+        v = mean[(count >= min_count) & np.isfinite(mean)]
+        if not v.size:
+            raise ValueError("no voxel with a finite mean and at least min_count images")
+        return float(v.min()), float(np.nextafter(v.max(), np.float32(np.inf)))
+
 
 def cover_average(volumes, chains=None, masks=None, grid=None, interpolation=1, min_count=1, fill=0.0, device=0):
     """Voxel-wise mean, stdev and count over the images that cover each grid voxel (bin/AverageImage -c 1).  `volumes`,
@@ -202,6 +247,60 @@ def cover_average(volumes, chains=None, masks=None, grid=None, interpolation=1, 
         return acc.finish(min_count, fill)
     finally:
         acc.close()
+
+
+def robust_z(values):
+    """(v - median) / (1.4826 MAD) over the finite entries, in float64; 0 everywhere where the MAD is 0, NaN where v is not
+    finite.  The median of an even number is the mean of the middle two."""
+    v = np.asarray(values, np.float64)
+    finite = np.isfinite(v)
+    z = np.full(v.shape, np.nan)
+    if finite.any():
+        median = _median(v[finite])
+        mad = _median(np.abs(v[finite] - median))
+        z[finite] = (v[finite] - median) / (1.4826 * mad) if mad > 0 else 0.0
+    return z
+
+
+def _median(v):
+    s = np.sort(v)
+    n = len(s)
+    return s[n // 2] if n % 2 else (s[n // 2 - 1] + s[n // 2]) / 2.0
+
+
+def group_quality(volumes, chains=None, masks=None, grid=None, interpolation=1, min_count=1, bins=64, value_range=None, device=0):
+    """Which images of a registered group registered badly (bin/AverageImage -c 1 -q 1): the coverage-aware average of the
+    group, then every image against the mean of the others over the voxels it covers (CoverAverage.score with
+    leave_one_out).  Arguments as in cover_average(); the background of image k is its minimum.  Returns one dict per image,
+    score()'s plus `image` (its index) and `ncc_robust_z` (robust_z of the group's ncc): a low ncc or nmi, and a strongly
+    negative z, single out an image that does not match the rest."""
+    vols = [_as_volume(v) for v in volumes]
+    if not vols:
+        raise ValueError("no volumes")
+    if chains is not None and len(chains) != len(vols):
+        raise ValueError("one chain per volume expected")
+    if masks is not None and len(masks) != len(vols):
+        raise ValueError("one mask per volume expected")
+    if grid is None:
+        a, o, s = vols[0]
+        grid = (a.shape[::-1], o, s)
+    acc = CoverAverage(grid, device)
+    try:
+        for k, v in enumerate(vols):
+            acc.add(v, None if chains is None else chains[k], None if masks is None else masks[k], interpolation)
+        if bins and value_range is None:
+            value_range = acc.quality_range(min_count)
+        rows = []
+        for k, v in enumerate(vols):
+            row = acc.score(v, None if chains is None else chains[k], None if masks is None else masks[k], interpolation, None,
+                            min_count, True, bins, value_range)
+            row["image"] = k
+            rows.append(row)
+    finally:
+        acc.close()
+    for row, z in zip(rows, robust_z([r["ncc"] for r in rows])):
+        row["ncc_robust_z"] = float(z)
+    return rows
 
 
 FUSED_DTYPES = ("uint8", "uint16", "int16", "int32", "uint32")

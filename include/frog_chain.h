@@ -184,6 +184,54 @@ int  frog_cover_add(frog_cover *a, frog_chain *chain, const frog_volume *source,
 int  frog_cover_finish(frog_cover *a, uint32_t min_count, float fill, float *mean, float *stdev, uint16_t *count);
 void frog_cover_destroy(frog_cover *a);
 
+/* ---- one image against the mean of the group (which images registered badly?) -------------------------------------------------
+ * Sums over the grid voxels of an image's value x and a reference y taken from the accumulator, and their joint histogram:
+ * what normalised cross-correlation and mutual information are formed from (frog_score_metrics_from, frog_host.h).  The call
+ * reads the accumulator and leaves mean, m2 and count as they are: it may come after any add, in any order with
+ * frog_cover_finish and with further adds.
+ * Per grid voxel v:
+ *   valid   : exactly where frog_cover_add(a, chain, source, mask, interpolation, background, NULL) would count the voxel (the
+ *             same device code: with a chain the inside test against the source, then the mask at the same position; without
+ *             one equal dims, every voxel inside, the mask's own voxel).
+ *   x       : (float)r, r the voxel frog_chain_reslice stores there, as in frog_cover_add.
+ *   y (f64) : k = count[v], m = mean[v].
+ *             leave_one_out != 0: the voxel takes part iff k >= max(2, min_count), and
+ *                 y = ((double)m * (double)k - (double)x) / (double)(k - 1)         three f64 operations, no contraction
+ *             -- the mean of the OTHER images, up to Welford's f32 rounding, for an image that is one of the adds.
+ *             leave_one_out == 0: the voxel takes part iff k >= max(1, min_count), and y = (double)m -- for an image that is
+ *             not in the accumulator (a new subject against an atlas).
+ *   A valid voxel that takes part and whose x or y is not finite adds one to n_nonfinite and to nothing else.  Every other
+ *   such voxel adds one to n, the six terms  (double)x, y, x * x, y * y, x * y, |x - y|  (each one f64 operation on (double)x
+ *   and y) to sx, sy, sxx, syy, sxy, sad, and one to a histogram bin.
+ *   histogram: scale = (float)bins / (hi - lo), formed once on the host in f32;
+ *              bin(t) = min(bins - 1, max(0, floorf((t - lo) * scale))) in f32, one operation per step, the clamp applied
+ *              to the float before the conversion (so +-inf, which (float)y may be, lands in the last or first bin);
+ *              histogram[bin(x) * bins + bin((float)y)] += 1.  Integer counts: exact, and their sum is n.
+ * The order of the f64 additions, complete (no floating-point atomic is used; the result does not depend on scheduling, on
+ * the device's load or on how the work is cut into launches):
+ *   1. The grid's voxels, x fastest, are cut into tiles of 2048 consecutive voxels; tile T holds voxels [2048 T, 2048 T + 2048).
+ *      The last tile may be partial.
+ *   2. A tile belongs to 256 threads; thread t (0..255) starts six sums at +0.0 and adds the terms of the voxels
+ *      2048 T + 256 j + t for j = 0, 1, ..., 7 in that order; a voxel that adds nothing (past the grid, invalid, too few
+ *      images, not finite) is skipped.
+ *   3. Threads 64 w .. 64 w + 63 form wave w (0..3), thread 64 w + l being lane l.  For h = 32, 16, 8, 4, 2, 1 in turn every
+ *      lane l < h replaces its sum by (its sum) + (the sum of lane l + h); lane 0 then holds the wave's sum.
+ *   4. The tile's sum is ((wave 0 + wave 1) + wave 2) + wave 3.
+ *   5. The result is the tiles' sums added one by one in ascending T, starting from +0.0.
+ * n and n_nonfinite travel the same way as integers.
+ * bins == 0 with histogram == NULL: no histogram, lo and hi are ignored.  Otherwise 2 <= bins <= 64, lo and hi finite,
+ * hi > lo and hi - lo finite in f32.  `histogram` is a host array of bins * bins counts, row = x bin.
+ * FROG_E_INVALID, before any device work: a NULL accumulator, source or sums; the geometry and mask errors of frog_cover_add;
+ * a chain on another device; a call before the first add; min_count == 0; bins, range or histogram other than stated. */
+typedef struct frog_score_sums {
+    uint64_t n;             /* voxels that entered the sums and the histogram                 */
+    uint64_t n_nonfinite;   /* valid, counted voxels skipped because x or y was not finite    */
+    double   sx, sy, sxx, syy, sxy, sad;    /* sums of x, y, x^2, y^2, x y, |x - y|, f64      */
+} frog_score_sums;
+int  frog_cover_score(frog_cover *a, frog_chain *chain, const frog_volume *source, const frog_volume *mask, int interpolation,
+                      double background, uint32_t min_count, int leave_one_out, uint32_t bins, float lo, float hi,
+                      frog_score_sums *sums, uint64_t *histogram);
+
 /* ---- majority-vote fusion of a registered group's label maps (an extension: the reference stops at N x VolumeTransform -i 0) --
  * An accumulator of n_images label volumes on `grid` (dims, origin, spacing; its dtype and data are ignored).  Per voxel v
  * and label value l it counts the images that carry l at v: count[l][v], 16-bit, one device thread per voxel, no atomics on

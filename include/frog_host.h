@@ -206,6 +206,23 @@ void frog_volume_view(const frog_volume_file *f, frog_volume *out);
 int frog_volume_range(const frog_volume *v, double *lo, double *hi);
 int frog_volume_write(const char *path, const frog_volume *v);
 
+/* ---- the scores of one image against the group's mean, from the sums of frog_cover_score (frog_chain.h) -----------------------
+ * No device is touched.  All arithmetic is f64, one operation per step in the order written, n = (double)s->n:
+ *   cx = sxx - (sx * sx) / n;  cy = syy - (sy * sy) / n;  cxy = sxy - (sx * sy) / n
+ *   ncc = cxy / sqrt(cx * cy)                  NaN unless cx > 0 and cy > 0
+ *   mean_abs_diff = sad / n
+ *   rmse = sqrt(((sxx - 2 * sxy) + syy) / n)   0 where the quotient is negative
+ * With the joint histogram h (bins x bins, row = x bin; its counts sum to s->n): the row sums rx[i] and the column sums
+ * ry[j] are formed exactly in u64; an entropy is H = -(sum of p * log(p)), p = (double)count / n, natural logarithm, the
+ * counts taken in ascending index (the joint one row by row), empty ones skipped, the sum started at +0.0:
+ *   mi  = (H(rx) + H(ry)) - H(h)
+ *   nmi = (H(rx) + H(ry)) / H(h)               Studholme's form, 1 (independent) .. 2 (one determines the other); 1 where
+ *                                              H(h) == 0 (everything in one bin)
+ * s->n == 0: every field is NaN.  histogram == NULL (then bins is ignored): mi and nmi are NaN.
+ * FROG_E_INVALID: a NULL s or out, or a histogram with bins outside 2..64. */
+typedef struct frog_score_metrics { double ncc, mean_abs_diff, rmse, mi, nmi; } frog_score_metrics;
+int frog_score_metrics_from(const frog_score_sums *s, const uint64_t *histogram, uint32_t bins, frog_score_metrics *out);
+
 /* ---- the common-space grid of the average image (tools/DummyVolumeGenerator.cxx:43-67) ----------------------------
  * Reads bbox.json as ImageGroup::saveStatsJSON writes it ({"bbox": [[min x, y, z], [max x, y, z]], ...}) and fills `grid`:
  * origin = min, `spacing` on every axis, dims[k] = ceil((max - min) / spacing) in double, dtype FROG_V_F32, data NULL.
