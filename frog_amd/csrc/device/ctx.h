@@ -12,6 +12,7 @@
 
 #include "../../../include/frog_hip.h"
 #include "dev_buf.h"
+#include "switches.h"
 
 namespace frog {
 
@@ -175,6 +176,7 @@ struct frog_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     frog_options opt{};
+    frog::Switches sw;                        // its FROG_* switches, as the environment had them when frog_create was called (switches.h)
 
     uint32_t nI = 0, ib = 0, ie = 0;          // images, owned range
     uint64_t P = 0;                           // all points
@@ -212,8 +214,7 @@ struct frog_ctx {
     frog::DevBuf<uint32_t> tile_order;        // [n_order_blocks] tile of every block, 0xFFFFFFFF = none; block % 8 = the tile's eighth of its image
     frog::DevBuf<frog::Tile> tiles_bo;        // the tiles in block order (zero tiles where tile_order has none)
     uint32_t n_order_blocks = 0;
-    bool fused_sweep = false;
-    bool fused_forced = false;                // FROG_SWEEP_FUSED=1: also without a culling list
+    bool fused_sweep = false;                 // (with exact_weights, ref_order, cull_enabled, cull_linear: frog_hip.hip resolve_modes)
 
     // statistics
     frog::DevBuf<float4> em;                  // [nI] c1,c2,ratio,0
@@ -347,7 +348,6 @@ struct frog_ctx {
     bool speculated = false;        // frog_step_speculate has exchanged the lattices' roles ahead of the decision
     bool spec_coeff_zero = false;
     frog::ScalarHandoff pending;    // the scalars frog_comm_unpack_slab_step posted and frog_step_finish has not awaited yet
-    bool k11_f64 = false;           // FROG_K11_F64=1: the B-spline transform's weights and sums in f64 (rounds 1-4), for comparison
     frog::DevBuf<uint32_t> ref_own;           // [L_own] own point (internal numbering) of every half-link, reference order
     frog::DevBuf<float> ref_w, ref_d;         // [L_own] weight and distance of every half-link (linear step)
     frog::DevBuf<uint64_t> ref_img_link;      // [nOwned + 1] first half-link of every owned image (relative, reference order)
@@ -361,7 +361,6 @@ struct frog_ctx {
     frog::DevBuf<uint16_t> rr_ent_img;
     frog::DevBuf<uint64_t> rr_group_ptr;
     bool rc_valid = false;                    // the chains below belong to the current lattice and the current `pos`
-    bool ref_literal = false;                   // FROG_REF_LITERAL=1: the literal form (ref_scatter_kernel), for comparison
     uint32_t rc_n_groups = 0, rc_n_gnodes = 0;
     hipStream_t ref_stream = nullptr;         // the energy chains of a deformable step run here, beside the scatter
     hipEvent_t ref_fork = nullptr, ref_join = nullptr;
@@ -380,16 +379,12 @@ struct frog_ctx {
 
     // certified outlier culling of the deformable sweep (k_cull.hip.h)
     bool exact_weights = false;               // FROG_WEIGHT_EXACT=1 (test hook): inlier_probability_exact for every weight
-    bool general_weights = false;             // FROG_WEIGHT_GENERAL=1 (test hook): no image gets a range for the one-exponential form
-                                              // (k_stats.hip.h em_fast_of with theta = NaN), the deformable sweeps evaluate inlier_probability twice
-    float fast_theta() const { return general_weights ? __builtin_nanf("") : opt.inlier_threshold - 1e-4f; }
+    float fast_theta() const { return sw.weight_general ? __builtin_nanf("") : opt.inlier_threshold - 1e-4f; }
     bool cull_enabled = true;                 // FROG_CULL=0 turns it off (every sweep walks all records)
     bool cull_need_build = true;              // host side: (re)build the list before the next deformable sweep
-    float cull_scale = 2.0f, cull_pad = 25.0f; // list cutoff = scale * certified cutoff + pad (the skin)
     // the same machinery for the LINEAR stage (weights that are exactly zero, k_cull.hip.h cull_cutoff_linear_of): on unless
-    // FROG_CULL_LINEAR=0; its own skin (the cutoffs are 14.5 c1: far out, where a tighter skin still lasts for iterations)
+    // FROG_CULL_LINEAR=0; the two skins are sw.cull_scale / cull_pad and sw.cull_lin_scale / cull_lin_pad
     bool cull_linear = true;
-    float cull_lin_scale = 1.25f, cull_lin_pad = 10.0f;
     uint64_t cull_lin_builds = 0;             // statistics: lists built during the linear stage
     frog::DevBuf<unsigned long long> lin_listed;   // [0] half-links in the last list of the linear stage
     frog::DevBuf<uint32_t> act_recs32;        // listed records (narrow form), or ...

@@ -490,7 +490,7 @@ static int ref_alloc(frog_ctx *ctx)
                                                                           ctx->ref_own.p, ctx->ref_link_img.p);
     FROG_HIP_CHECK(hipGetLastError());
     // the other table that depends on the model alone: the rows of half-links side by side (the deformable stage's per-point sums)
-    return ctx->ref_literal ? FROG_OK : ref_rows_build(ctx);
+    return ctx->sw.ref_literal ? FROG_OK : ref_rows_build(ctx);
 }
 
 // The rows of half-links side by side (k_refchain.hip.h), once per context.
@@ -542,7 +542,7 @@ static int ref_linear_step(frog_ctx *ctx)
     { const int rc = ref_alloc(ctx); if (rc) return rc; }
     hipStream_t s = ctx->stream;
     const uint32_t nO = ctx->n_owned(), nRows = ctx->own_pt_end - ctx->own_pt_begin;
-    if (ctx->ref_literal) {
+    if (ctx->sw.ref_literal) {
         if (nRows)
             ref_link_terms_kernel<<<div_up(nRows, 256), 256, 0, s>>>(ctx->ref_rowptr.p, ctx->ref_link.p, ctx->new_of_old.p, nRows, ctx->pos.p,
                                                                      ctx->pos2.p, ctx->em.p, ctx->ref_own.p, ctx->ref_w.p, ctx->ref_d.p);
@@ -570,7 +570,7 @@ static int ref_point_sums(frog_ctx *ctx, bool with_energy)
     { const int rc = ref_alloc(ctx); if (rc) return rc; }
     hipStream_t s = ctx->stream;
     const uint32_t nO = ctx->n_owned(), nRows = ctx->own_pt_end - ctx->own_pt_begin;
-    if (nRows && ctx->ref_literal) {
+    if (nRows && ctx->sw.ref_literal) {
         ref_point_sums_kernel<<<div_up(nRows, 256), 256, 0, s>>>(ctx->ref_rowptr.p, ctx->ref_link.p, ctx->new_of_old.p, nRows, ctx->pos.p,
                                                                  ctx->pos2.p, ctx->em.p, ctx->opt.inlier_threshold, ctx->point_sums.p,
                                                                  with_energy ? ctx->ref_pt_energy.p : nullptr);
@@ -587,12 +587,12 @@ static int ref_point_sums(frog_ctx *ctx, bool with_energy)
         // The energy's two chains per image (20 000 dependent f64 additions each at cfg 3: 0.19 ms on 100 of 256 CUs) need nothing
         // the scatter produces and produce nothing it needs: on a stream of their own beside it, joined by ref_deformable_phase_a.
         hipStream_t se = s;
-        if (!ctx->ref_literal && !ctx->n_hard && ctx->ref_stream) {
+        if (!ctx->sw.ref_literal && !ctx->n_hard && ctx->ref_stream) {
             FROG_HIP_CHECK(hipEventRecord(ctx->ref_fork, s));
             FROG_HIP_CHECK(hipStreamWaitEvent(ctx->ref_stream, ctx->ref_fork, 0));
             se = ctx->ref_stream;
         }
-        if (ctx->ref_literal) ref_image_energy_kernel<<<nO, 64, 0, se>>>(ctx->ref_pt_energy.p, ctx->d_poff.p, ctx->ib, ctx->own_pt_begin, ctx->img_energy.p);
+        if (ctx->sw.ref_literal) ref_image_energy_kernel<<<nO, 64, 0, se>>>(ctx->ref_pt_energy.p, ctx->d_poff.p, ctx->ib, ctx->own_pt_begin, ctx->img_energy.p);
         else ref_image_energy2_kernel<<<nO, RE_STEP, 0, se>>>(ctx->ref_pt_energy.p, ctx->d_poff.p, ctx->ib, ctx->own_pt_begin, ctx->img_energy.p);
         ref_energy_total_kernel<<<1, 1, 0, se>>>(ctx->img_energy.p, nO, ctx->energy.p);
         if (se != s) { FROG_HIP_CHECK(hipEventRecord(ctx->ref_join, se)); ctx->ref_join_pending = true; }
@@ -612,10 +612,9 @@ static int ref_point_sums(frog_ctx *ctx, bool with_energy)
 // finest lattice has 3.4e7 groups, x 256 threads = 8.8e9 -- the launch returned no error and the groups past 2^32 / 256 were
 // never filled (round 6: found by scripts/diag_exact_forms.py at full size).  So: at most 2^22 workgroups in x, the rest in the
 // second dimension; the kernels bound-check blockIdx.y * gridDim.x + blockIdx.x against the group count.
-static inline dim3 rc_grid(uint32_t n_groups)
+static inline dim3 rc_grid(const frog_ctx *ctx, uint32_t n_groups)
 {
-    static const uint32_t max_x = getenv("FROG_RC_GRID_X") ? (uint32_t)std::max(1, atoi(getenv("FROG_RC_GRID_X"))) : 1u << 22;      // (test hook: the fold on small groups)
-    const uint32_t gx = std::min(std::max(1u, n_groups), max_x);
+    const uint32_t gx = std::min(std::max(1u, n_groups), ctx->sw.rc_grid_x);
     return dim3(gx, div_up(std::max(1u, n_groups), gx));
 }
 
@@ -623,7 +622,7 @@ static int ref_chain_build(frog_ctx *ctx)
 {
     if (ctx->rc_valid) return FROG_OK;
     hipStream_t s = ctx->stream;
-    static const bool trace = getenv("FROG_REF_TRACE") != nullptr;
+    const bool trace = ctx->sw.ref_trace;
     const auto t_in = std::chrono::steady_clock::now();
     auto mark = [&](const char *what) {
         if (trace) std::fprintf(stderr, "[ref_chain_build] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count());
@@ -673,7 +672,7 @@ static int ref_chain_build(frog_ctx *ctx)
     FROG_HIP_CHECK(hipcub::DeviceRadixSort::SortPairsDescending(ctx->rc_temp.p, tb, ctx->rc_len.p, ctx->rc_len_sorted.p, ctx->rc_iota.p, ctx->rc_slot_node.p, n_slots, 0, 32, s));
     FROG_HIP_CHECK(hipMemsetAsync(ctx->rc_group_size.p, 0, ((size_t)n_groups + 1) * sizeof(uint64_t), s));
     // ... and look the sums up by owned row (see ref_chain_fill_kernel); landmark constraints edit the sums by point afterwards: by point then
-    ctx->rc_by_row = !ctx->n_hard && !ctx->ref_literal && n_keys / std::max<uint64_t>(1, n_gnodes) >= 300;
+    ctx->rc_by_row = !ctx->n_hard && !ctx->sw.ref_literal && n_keys / std::max<uint64_t>(1, n_gnodes) >= 300;
     ref_chain_group_kernel<<<div_up(n_slots, 256), 256, 0, s>>>(ctx->rc_len_sorted.p, (uint32_t)n_slots, n_groups, (uint32_t)ctx->rc_unroll, ctx->rc_group_len.p,
                                                                                   ctx->rc_group_size.p, ctx->rc_slot_node.p, ctx->rc_slot_of_node.p);
     tb = ctx->rc_temp.n;
@@ -702,8 +701,8 @@ static int ref_chain_build(frog_ctx *ctx)
     FROG_HIP_CHECK(ctx->rc_ent.alloc(std::max<uint64_t>(1, seats), std::max<uint64_t>(1, seats + seats / 4)));
     FROG_HIP_CHECK(ctx->rc_wt.alloc(std::max<uint64_t>(1, seats), std::max<uint64_t>(1, seats + seats / 4)));
     const unsigned j_tiles = div_up(std::max(1u, longest), 64u);
-    if (n_entries && !ctx->ref_literal && j_tiles <= 65535u) {
-        const dim3 gg = rc_grid(n_groups);
+    if (n_entries && !ctx->sw.ref_literal && j_tiles <= 65535u) {
+        const dim3 gg = rc_grid(ctx, n_groups);
         ref_chain_fill_tiled_kernel<<<dim3(gg.x, j_tiles, gg.y), 256, 0, s>>>(sorted, rbits, ctx->rc_node_ptr.p, ctx->rc_slot_node.p, ctx->rc_group_ptr.p,
                                                                              ctx->rc_group_len.p, ctx->pos.p, ctx->new_of_old.p, ctx->d_poff.p, ctx->ib,
                                                                              ctx->own_pt_begin, gd, ctx->rc_by_row ? 1 : 0, n_groups, ctx->rc_ent.p, ctx->rc_wt.p);
@@ -733,7 +732,7 @@ static int ref_deformable_phase_a(frog_ctx *ctx, float alpha)
     if (rc) return rc;
     rc = join_setup(ctx);                       // the set-up's stream zeroes and sorts: wait before gradf is touched
     if (rc) return rc;
-    if (ctx->ref_literal) {
+    if (ctx->sw.ref_literal) {
         FROG_HIP_CHECK(hipMemsetAsync(ctx->gradf.p, 0, (size_t)nO * gd.n_cp * sizeof(float4), s));       // Fill(0), :249
         ref_scatter_kernel<<<nO, 64, 0, s>>>(ctx->pos.p, ctx->point_sums.p, ctx->new_of_old.p, ctx->d_poff.p, ctx->ib, ctx->own_pt_begin, gd,
                                              ctx->gradf.p);
@@ -742,10 +741,10 @@ static int ref_deformable_phase_a(frog_ctx *ctx, float alpha)
         if (rc) return rc;
         const float4 *sums = ctx->rc_by_row ? ctx->ref_row_sums.p : ctx->point_sums.p;
         if (ctx->rc_unroll == 16)
-            ref_chain_kernel<16><<<rc_grid(ctx->rc_n_groups), 64, 0, s>>>(ctx->rc_ent.p, ctx->rc_wt.p, ctx->rc_group_ptr.p, ctx->rc_group_len.p, ctx->rc_slot_node.p,
+            ref_chain_kernel<16><<<rc_grid(ctx, ctx->rc_n_groups), 64, 0, s>>>(ctx->rc_ent.p, ctx->rc_wt.p, ctx->rc_group_ptr.p, ctx->rc_group_len.p, ctx->rc_slot_node.p,
                                                                          sums, ctx->rc_n_groups, ctx->gradf.p);
         else
-            ref_chain_kernel<8><<<rc_grid(ctx->rc_n_groups), 64, 0, s>>>(ctx->rc_ent.p, ctx->rc_wt.p, ctx->rc_group_ptr.p, ctx->rc_group_len.p, ctx->rc_slot_node.p,
+            ref_chain_kernel<8><<<rc_grid(ctx, ctx->rc_n_groups), 64, 0, s>>>(ctx->rc_ent.p, ctx->rc_wt.p, ctx->rc_group_ptr.p, ctx->rc_group_len.p, ctx->rc_slot_node.p,
                                                                         sums, ctx->rc_n_groups, ctx->gradf.p);
     }
     ref_cp_step_kernel<<<div_up(gd.n_cp, 256), 256, 0, s>>>(ctx->gradf.p, ctx->coeff.p, ctx->grad.p, nO, gd.n_cp, alpha, ctx->gridsum.p);
@@ -813,80 +812,76 @@ void frog_destroy(frog_ctx *ctx)
     delete ctx;
 }
 
-int frog_create(const frog_model *m, const frog_options *o, int device,
-                uint32_t image_begin, uint32_t image_end, frog_ctx **out)
+} // extern "C"
+
+// ---- frog_create, stage by stage: each returns a FROG_* code, create_stages calls them in order, frog_create lets go of the
+// context at one place when one fails.  The [timing] laps mark the order of the device work.
+#define CREATE_CHECK(expr)                                                                           \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess)                                                                        \
+            return fail(e_ == hipErrorOutOfMemory ? FROG_E_NOMEM : FROG_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// FROG_TIMING=1: the device part of frog_create by stage, from the moment the host layout is built and the device chosen
+struct CreateClock {
+    bool on;
+    std::chrono::steady_clock::time_point t0;
+    void lap(const char *what) const { if (on) std::printf("[timing] frog_create device part, %s : %gs\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); }
+};
+
+// The switches that decide HOW a context runs, together, in the order in which one overrides the other.
+static void resolve_modes(frog_ctx *c)
 {
-    if (!m || !o || !out) return fail(FROG_E_INVALID, "null argument");
-    *out = nullptr;
-    if (m->n_images < 1 || image_begin >= image_end || image_end > m->n_images)
-        return fail(FROG_E_INVALID, "bad image range");
-    for (size_t i = 0; i < sizeof(o->reserved) / sizeof(o->reserved[0]); i++)
-        if (o->reserved[i]) return fail(FROG_E_INVALID, "reserved option fields must be 0");
-    if (o->stats_max_size < 1) return fail(FROG_E_INVALID, "stats_max_size < 1");
-    if (o->n_fixed_images) {
-        // fixed images (-fi, imageGroup.cxx:34): a context for the moving images plus a stats-only one
-        const uint32_t nf = (uint32_t)o->n_fixed_images;
-        if (o->n_fixed_images < 0 || nf >= m->n_images) return fail(FROG_E_INVALID, "n_fixed_images must leave at least one moving image");
-        if (image_begin != 0 || image_end != m->n_images)
-            return fail(FROG_E_INVALID, "n_fixed_images needs the whole group in one context");
-        frog_options o2 = *o;
-        o2.n_fixed_images = 0;
-        frog_ctx *moving = nullptr, *fixed = nullptr;
-        int rc = frog_create(m, &o2, device, nf, m->n_images, &moving);
-        if (rc) return rc;
-        frog_options o3 = o2;
-        o3.max_levels_hint = 0;                                     // a statistics-only context never holds a lattice
-        rc = frog_create(m, &o3, device, 0, nf, &fixed);
-        if (rc) { frog_destroy(moving); return rc; }
-        fixed->cull_enabled = false;                                // a statistics-only context never sweeps a lattice step
-        fixed->act_recs32.release(); fixed->act_recs.release(); fixed->act_cnt.release(); fixed->pos2_snap.release();
-        rc = frog_set_stream(fixed, moving->stream);
-        if (rc) { frog_destroy(fixed); frog_destroy(moving); return rc; }
-        moving->helper = fixed;
-        moving->nf = nf;
-        moving->opt.n_fixed_images = o->n_fixed_images;
-        *out = moving;
-        return FROG_OK;
-    }
-    // (the first HIP call of a process waits for the runtime to come up -- 0.05-0.2 s; bin/frog starts that on a thread of its own
-    // beside readPairs (frog_device_warm), and the host-side layout build below needs no device: the device is asked for after it)
-    frog_ctx *c = new (std::nothrow) frog_ctx;
-    if (!c) return fail(FROG_E_NOMEM, "out of host memory");
-    c->device = device;
-    c->opt = *o;
-    c->nI = m->n_images; c->ib = image_begin; c->ie = image_end;
+    const Switches &sw = c->sw;
+    // static + dynamic LDS of the fused block must stay under the 64 KB a block gets without asking for more
+    uint32_t widest = 0;
+    for (uint32_t g = 0; g < c->n_groups; g++) widest = std::max(widest, c->group_begin[g + 1] - c->group_begin[g]);
+    c->fused_sweep = c->n_sub == 1 && c->n_tiles > 0 && widest <= (uint32_t)EMD_LDS_IMAGES && sweep_lds_images(c) <= 64u && sw.fused != 0;
+    c->cull_enabled = sw.cull;
+    // without the culling list a third of a typical group's gathers are false matches with random partners: the fused sweep's
+    // spatial XCD mapping does nothing for them, the per-group form keeps them in L2 (unless FROG_SWEEP_FUSED=1 insists)
+    if (!(c->cull_enabled && c->opt.inlier_threshold >= 1e-3f) && sw.fused != 1) c->fused_sweep = false;
+    c->exact_weights = sw.weight_exact;
+    // test hook: the solver loops in the reference's own order and arithmetic (k_reforder.hip.h); no list, no fast weight
+    c->ref_order = c->opt.reference_order != 0;                // frog_options::reference_order (bin/frog -exact 1)
+    if (sw.reference_order >= 0) c->ref_order = sw.reference_order != 0;                    // the tests' switch, overrides
+    if (c->ref_order) { c->cull_enabled = false; c->exact_weights = true; c->fused_sweep = false; }
+    c->cull_linear = sw.cull_linear;
+}
+
+// (the first HIP call of a process waits for the runtime to come up -- 0.05-0.2 s; bin/frog starts that on a thread of its own
+// beside readPairs (frog_device_warm), and the host-side layout build needs no device: the device is asked for after it)
+static int create_host_layout(frog_ctx *c, const frog_model *m, Layout &lay)
+{
+    c->nI = m->n_images;
     c->poff.assign(m->point_offset, m->point_offset + c->nI + 1);
     c->P = c->poff[c->nI];
     c->own_pt_begin = c->poff[c->ib]; c->own_pt_end = c->poff[c->ie];
-    if (c->P >= 0x7FFFFFFFull) { delete c; return fail(FROG_E_INVALID, "more than 2^31-1 points"); }
-
-    Layout lay;
-    std::string err;
-    // FROG_WIDE_RECORDS=1 keeps the 8-byte record form where the 4-byte one would fit (test hook)
-    const char *wide_env = getenv("FROG_WIDE_RECORDS");
-    // partner groups: 8 (one sweep launch per pass) unless FROG_SUBPASSES asks for 8 * n launches-worth
-    // (ctx.h: measured no gain from keeping the slices L2-sized, so it is not automatic)
-    c->n_sub = 1;
-    if (const char *e = getenv("FROG_SUBPASSES")) c->n_sub = (uint32_t)std::min(MAX_SUBPASS, std::max(1, atoi(e)));
+    if (c->P >= 0x7FFFFFFFull) return fail(FROG_E_INVALID, "more than 2^31-1 points");
+    c->n_sub = (uint32_t)c->sw.subpasses;
     c->n_groups = N_XCD * c->n_sub;
-    const auto t_create0 = std::chrono::steady_clock::now();
-    int rc = build_layout(*m, c->ib, c->ie, wide_env && wide_env[0] == '1', (int)c->n_groups, lay, err);
-    if (rc) { delete c; return fail(rc, err); }
-    {
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); delete c; return fail(FROG_E_NODEVICE, "no HIP device: libfrog_hip has no CPU fallback"); }
-        if (device < 0 || device >= ndev) { delete c; return fail(FROG_E_INVALID, "device index out of range"); }
-        if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); delete c; return fail(FROG_E_HIP, "hipSetDevice failed"); }
-    }
-    const auto t_layout = std::chrono::steady_clock::now();
-    c->create_s[0] = std::chrono::duration<double>(t_layout - t_create0).count();
+    std::string err;
+    const int rc = build_layout(*m, c->ib, c->ie, c->sw.wide_records, (int)c->n_groups, c->sw.timing, lay, err);
+    return rc ? fail(rc, err) : FROG_OK;
+}
+
+static int create_select_device(frog_ctx *c)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); return fail(FROG_E_NODEVICE, "no HIP device: libfrog_hip has no CPU fallback"); }
+    if (c->device < 0 || c->device >= ndev) return fail(FROG_E_INVALID, "device index out of range");
+    if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return fail(FROG_E_HIP, "hipSetDevice failed"); }
+    return FROG_OK;
+}
+
+static int create_adopt_layout(frog_ctx *c, const Layout &lay)
+{
     c->L_own = lay.ref_link.size();
     c->rec_format = lay.format;
     for (uint32_t g = 0; lay.format.narrow && g < c->n_groups; g++)
-        if (lay.group_begin[g + 1] - lay.group_begin[g] > (uint32_t)EMD_LDS_IMAGES) {
-            delete c;
+        if (lay.group_begin[g + 1] - lay.group_begin[g] > (uint32_t)EMD_LDS_IMAGES)
             return fail(FROG_E_INVALID, "internal: narrow link records chosen for a partner group of more than 256 images");
-        }
     c->L_recs = lay.format.narrow ? lay.recs32.size() : lay.recs.size();
     c->n_tiles = (uint32_t)lay.tiles.size();
     for (uint32_t g = 0; g <= c->n_groups; g++) c->group_begin[g] = lay.group_begin[g];
@@ -894,41 +889,37 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
     c->h_new_of_old = lay.new_of_old;
     c->h_img_tile_ptr = lay.img_tile_ptr;
     c->img_link_begin = lay.img_link_begin;
+    return FROG_OK;
+}
 
-#define CREATE_CHECK(expr)                                                                           \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            std::string msg_ = std::string(#expr) + ": " + hipGetErrorString(e_);                    \
-            frog_destroy(c);                                                                         \
-            return fail(e_ == hipErrorOutOfMemory ? FROG_E_NOMEM : FROG_E_HIP, msg_);                \
-        }                                                                                            \
-    } while (0)
-
-    auto create_lap = [&](const char *what) {
-        if (getenv("FROG_TIMING")) std::printf("[timing] frog_create device part, %s : %gs\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_layout).count());
-    };
+// the main stream and the pinned scalar block (the other streams: create_statistics)
+static int create_streams(frog_ctx *c, const CreateClock &clock)
+{
     CREATE_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->own_stream = true;
     {
         // retired lattices are allocated stream-ordered (hipMallocAsync): keep freed blocks in the pool instead of
         // returning them to the driver at the next synchronisation
         hipMemPool_t pool = nullptr;
-        if (hipDeviceGetDefaultMemPool(&pool, device) == hipSuccess && pool) {
+        if (hipDeviceGetDefaultMemPool(&pool, c->device) == hipSuccess && pool) {
             uint64_t keep = ~0ull;
             (void)hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep);
         }
         (void)hipGetLastError();
     }
-    create_lap("stream, memory pool");
+    clock.lap("stream, memory pool");
     CREATE_CHECK(hipHostMalloc((void **)&c->h_energy, HS_DOUBLES * sizeof(double), hipHostMallocMapped));      // (layout: ctx.h)
     std::memset(c->h_energy, 0, HS_DOUBLES * sizeof(double));
     if (hipHostGetDevicePointer((void **)&c->h_energy_dev, c->h_energy, 0) != hipSuccess) { (void)hipGetLastError(); c->h_energy_dev = nullptr; }
-    if (getenv("FROG_SCALARS_COPY")) c->h_energy_dev = nullptr;      // the copy + event hand-off (A/B, fallback)
-    hipStream_t s = c->stream;
+    if (c->sw.scalars_copy) c->h_energy_dev = nullptr;
+    clock.lap("+ pinned scalar block");
+    return FROG_OK;
+}
 
-    create_lap("+ pinned scalar block");
-    // points: xyz | image id
+// points: xyz | image id, renumbered (prep.h), with every image's bounding box on the way
+static int create_points(frog_ctx *c, const frog_model *m, const Layout &lay, const CreateClock &clock)
+{
+    hipStream_t s = c->stream;
     std::vector<float4> hp(c->P);
     c->h_img_bbox.assign((size_t)c->nI * 6, 0.0);
     #pragma omp parallel for schedule(dynamic, 1) num_threads(host_threads())
@@ -946,9 +937,9 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
         }
         for (int k = 0; k < 3; k++) { c->h_img_bbox[(size_t)i * 6 + k] = mn[k]; c->h_img_bbox[(size_t)i * 6 + 3 + k] = mx[k]; }
     }
-    create_lap("+ points renumbered on the host");
+    clock.lap("+ points renumbered on the host");
     CREATE_CHECK(c->pos.upload(hp, s));
-    create_lap("+ first upload queued");
+    clock.lap("+ first upload queued");
     {
         std::vector<P3> hp2(c->P);
         #pragma omp parallel for num_threads(host_threads())
@@ -956,11 +947,16 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
         CREATE_CHECK(c->pos2.upload(hp2, s));
         CREATE_CHECK(hipStreamSynchronize(s));
     }
-    create_lap("+ points uploaded"); 
+    clock.lap("+ points uploaded");
     CREATE_CHECK(c->d_poff.upload(c->poff, s));
     CREATE_CHECK(c->point_sums.alloc(c->P));
     CREATE_CHECK(hipMemsetAsync(c->point_sums.p, 0, c->point_sums.bytes(), s));
+    return FROG_OK;
+}
 
+static int create_reference_links(frog_ctx *c, const Layout &lay, const CreateClock &clock)
+{
+    hipStream_t s = c->stream;
     CREATE_CHECK(c->ref_rowptr.upload(lay.ref_rowptr, s));
     CREATE_CHECK(c->ref_link.upload(lay.ref_link, s));
     {
@@ -968,62 +964,47 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
         CREATE_CHECK(c->new_of_old.upload(own, s));
         CREATE_CHECK(hipStreamSynchronize(s));
     }
-    create_lap("+ reference-order links uploaded");
+    clock.lap("+ reference-order links uploaded");
+    return FROG_OK;
+}
+
+static int create_records(frog_ctx *c, const Layout &lay, const CreateClock &clock)
+{
+    hipStream_t s = c->stream;
     CREATE_CHECK(c->tiles.upload(lay.tiles, s));
     if (lay.format.narrow) { CREATE_CHECK(c->recs32.upload(lay.recs32, s)); }
     else { CREATE_CHECK(c->recs.upload(lay.recs, s)); }
     CREATE_CHECK(c->img_tile_ptr.upload(lay.img_tile_ptr, s));
-    create_lap("+ records queued");
+    clock.lap("+ records queued");
+    return FROG_OK;
+}
+
+// the fused sweep's block order (prep.h fused_block_order) and the sweeps' partial sums
+static int create_sweep_tables(frog_ctx *c, const Layout &lay)
+{
+    hipStream_t s = c->stream;
+    std::vector<uint32_t> order;
+    c->n_order_blocks = fused_block_order(lay, c->ib, c->ie, c->sw.tile_slices, order);
+    CREATE_CHECK(c->tile_order.upload(order, s));
     {
-        // Fused deformable sweep (k_links.hip.h FUSED): block b works on tile order[b], and b % 8 -- the XCD the block lands on
-        // under round-robin dispatch -- is the tile's eighth of its image along the Morton curve, so that an XCD's L2 sees the
-        // same eighth of every image: its own tiles' and, since true matches are spatial neighbours, nearly all their partners'.
-        // Within an XCD's list the tiles go slice by slice, image by image inside a slice (a slice = one of FROG_TILE_SLICES
-        // equal parts of the eighth, along the curve): the blocks resident on an XCD at any time then gather from 1/16 of every
-        // partner image instead of 1/8 (1.5 MB of coordinates instead of 3 MB beside the record stream in a 4 MB L2).
-        // Measured on cfg 3: 0.2486 -> 0.2446 ms with two slices; 3, 4 and 8 slices the same as two (0.2451-0.2460).  A context
-        // that owns an eighth of that group (12-13 images, 118 tiles per list: little more than one round of resident blocks)
-        // keeps gaining: 0.0702 / 0.0663 / 0.0651 / 0.0641 ms with 1 / 2 / 4 / 8 slices -- hence eight below 64 owned images.
-        std::vector<uint32_t> lists[N_XCD];
-        const int n_slices = [&] {
-            const char *e = getenv("FROG_TILE_SLICES");
-            const int v = e ? atoi(e) : (c->ie - c->ib >= 64u ? 2 : 8);
-            return v < 1 ? 1 : v > 64 ? 64 : v;
-        }();
-        for (int sl = 0; sl < n_slices; sl++)
-            for (uint32_t i = c->ib; i < c->ie; i++) {
-                const uint32_t tb = lay.img_tile_ptr[i], nt = lay.img_tile_ptr[i + 1] - tb;
-                for (uint32_t j = 0; j < nt; j++)
-                    if ((int)(((size_t)j * N_XCD * n_slices / nt) % n_slices) == sl) lists[(size_t)j * N_XCD / nt].push_back(tb + j);
-            }
-        size_t rounds = 0;
-        for (auto &l : lists) rounds = std::max(rounds, l.size());
-        std::vector<uint32_t> order(std::max<size_t>(1, rounds * N_XCD), 0xFFFFFFFFu);
-        for (int x = 0; x < N_XCD; x++)
-            for (size_t r = 0; r < lists[x].size(); r++) order[r * N_XCD + x] = lists[x][r];
-        c->n_order_blocks = (uint32_t)(rounds * N_XCD);
-        CREATE_CHECK(c->tile_order.upload(order, s));
-        {
-            std::vector<Tile> bo(order.size(), Tile{});
-            for (size_t b = 0; b < order.size(); b++) if (order[b] != 0xFFFFFFFFu) bo[b] = lay.tiles[order[b]];
-            CREATE_CHECK(c->tiles_bo.upload(bo, s));
-            CREATE_CHECK(hipStreamSynchronize(s));
-        }
+        std::vector<Tile> bo(order.size(), Tile{});
+        for (size_t b = 0; b < order.size(); b++) if (order[b] != 0xFFFFFFFFu) bo[b] = lay.tiles[order[b]];
+        CREATE_CHECK(c->tiles_bo.upload(bo, s));
         CREATE_CHECK(hipStreamSynchronize(s));
-        // static + dynamic LDS of the fused block must stay under the 64 KB a block gets without asking for more
-        uint32_t widest = 0;
-        for (uint32_t g = 0; g < c->n_groups; g++) widest = std::max(widest, c->group_begin[g + 1] - c->group_begin[g]);
-        const char *fe = getenv("FROG_SWEEP_FUSED");
-        c->fused_sweep = c->n_sub == 1 && c->n_tiles > 0 && widest <= (uint32_t)EMD_LDS_IMAGES && sweep_lds_images(c) <= 64u
-                         && !(fe && fe[0] == '0');
-        c->fused_forced = fe && fe[0] == '1';
     }
+    CREATE_CHECK(hipStreamSynchronize(s));
     CREATE_CHECK(c->tile_partial.alloc((size_t)std::max(1u, c->n_tiles) * c->n_groups * LINEAR_SUMS));
     CREATE_CHECK(c->tile_counts.alloc((size_t)std::max(1u, c->n_tiles) * c->n_groups * 2));
     CREATE_CHECK(c->group_sums.alloc((size_t)N_XCD * std::max(1u, c->own_pt_end - c->own_pt_begin)));
     CREATE_CHECK(c->img_counts.alloc((size_t)c->n_owned() * 2));
+    return FROG_OK;
+}
 
-    // statistics: Stats ctor (stats.h:94-99) + setupStats (imageGroup.cxx:1151-1159)
+// statistics: Stats ctor (stats.h:94-99) + setupStats (imageGroup.cxx:1151-1159); the side stream of the selections, and the
+// set-up stream with its events
+static int create_statistics(frog_ctx *c, const Layout &lay)
+{
+    hipStream_t s = c->stream;
     std::vector<float4> hem(c->nI, make_float4(10.f, 300.f, 0.5f, 0.f));
     CREATE_CHECK(c->em.upload(hem, s));
     CREATE_CHECK(c->emd.alloc(c->nI));
@@ -1033,7 +1014,7 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
     for (uint32_t i = c->ib; i < c->ie; i++) {
         uint64_t v = lay.img_link_begin[i + 1] - lay.img_link_begin[i];
         c->h_virtual[i - c->ib] = (uint32_t)v;
-        cap = std::max<uint32_t>(cap, (uint32_t)std::min<uint64_t>(v, (uint64_t)o->stats_max_size));
+        cap = std::max<uint32_t>(cap, (uint32_t)std::min<uint64_t>(v, (uint64_t)c->opt.stats_max_size));
     }
     c->sample_cap = (int)cap;
     CREATE_CHECK(c->d_virtual.upload(c->h_virtual, s));
@@ -1076,7 +1057,13 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
         for (uint32_t i = 0; i < c->n_owned(); i++) std::memcpy(&st[(size_t)i * MT_WORDS], x, sizeof x);
         CREATE_CHECK(c->mt_state.upload(st, s));
     }
+    return FROG_OK;
+}
 
+// matrices, energy and counters, the modes, the culling list's buffers, the first two kernels; the stream idle at the end
+static int create_solver_buffers(frog_ctx *c, const CreateClock &clock)
+{
+    hipStream_t s = c->stream;
     std::vector<double> hm((size_t)c->nI * 16, 0.0);
     for (uint32_t i = 0; i < c->nI; i++) for (int k = 0; k < 4; k++) hm[(size_t)i * 16 + 5 * k] = 1.0;
     CREATE_CHECK(c->mat.upload(hm, s));
@@ -1091,164 +1078,233 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
     CREATE_CHECK(c->bounds_scratch.alloc((size_t)BOUNDS_BLOCKS * 6 + 6));
     em_derive_kernel<<<div_up(c->nI, 256), 256, 0, s>>>(c->em.p, c->emd.p, c->emf.p, c->nI, c->fast_theta());
     CREATE_CHECK(hipGetLastError());
-    // certified outlier culling (k_cull.hip.h): FROG_CULL=0 off; FROG_CULL_SKIN="scale,pad" sets the list cutoff
-    if (const char *e = getenv("FROG_CULL")) c->cull_enabled = atoi(e) != 0;
-    // without the culling list a third of a typical group's gathers are false matches with random partners: the fused sweep's
-    // spatial XCD mapping does nothing for them, the per-group form keeps them in L2 (unless FROG_SWEEP_FUSED=1 insists)
-    if (!(c->cull_enabled && c->opt.inlier_threshold >= 1e-3f) && !c->fused_forced) c->fused_sweep = false;
-    // test hook: every inlier weight through the form with the reference's own promotions (ten times the arithmetic)
-    if (const char *e = getenv("FROG_WEIGHT_EXACT")) c->exact_weights = atoi(e) != 0;
-    if (const char *e = getenv("FROG_WEIGHT_GENERAL")) c->general_weights = atoi(e) != 0;
-    // test hook: the solver loops in the reference's own order and arithmetic (k_reforder.hip.h); no list, no fast weight
-    c->ref_order = o->reference_order != 0;                    // frog_options::reference_order (bin/frog -exact 1)
-    if (const char *e = getenv("FROG_REFERENCE_ORDER")) c->ref_order = atoi(e) != 0;        // the tests' switch, overrides
-    if (const char *e = getenv("FROG_K11_F64")) c->k11_f64 = atoi(e) != 0;
-    if (c->ref_order) { c->cull_enabled = false; c->exact_weights = true; c->fused_sweep = false; }
-    c->ref_literal = getenv("FROG_REF_LITERAL") != nullptr;
-    if (const char *e = getenv("FROG_CULL_LINEAR")) c->cull_linear = atoi(e) != 0;
-    if (const char *e = getenv("FROG_CULL_SKIN_LINEAR")) {
-        float a = 0, b = 0;
-        if (sscanf(e, "%f,%f", &a, &b) == 2 && a >= 1.0f && b >= 0.0f) { c->cull_lin_scale = a; c->cull_lin_pad = b; }
-    }
-    if (const char *e = getenv("FROG_CULL_SKIN")) {
-        float a = 0, b = 0;
-        if (sscanf(e, "%f,%f", &a, &b) == 2 && a >= 1.0f && b >= 0.0f) { c->cull_scale = a; c->cull_pad = b; }
-    }
+    resolve_modes(c);
     CREATE_CHECK(c->cut_now.alloc(c->nI));
     CREATE_CHECK(c->lin_listed.alloc(1));
     CREATE_CHECK(hipMemsetAsync(c->lin_listed.p, 0, sizeof(unsigned long long), s));
     if (c->cull_enabled && (c->opt.inlier_threshold >= 1e-3f || c->cull_linear) && c->n_tiles > 0) {
-        if (int rc_ = cull_allocate(c)) { frog_destroy(c); return rc_; }
+        if (int rc_ = cull_allocate(c)) return rc_;
     }
     stats_publish_kernel<<<dim3(div_up(c->nI, 64), 2), 64, 0, s>>>(c->em.p, c->emd.p, c->emf.p, c->nI, c->opt.inlier_threshold, c->fast_theta(), c->cut_now.p, 1);
     CREATE_CHECK(hipGetLastError());
     CREATE_CHECK(hipStreamSynchronize(s));      // host staging vectors die here
-    create_lap("+ everything else allocated, uploads done");
-    {
-        // the lattice buffers of level 0 (with their head-room) for the box of the model as it is: close enough to what
-        // the first frog_deformable_setup will ask for that it finds them allocated
-        double mn[3] = { 1e300, 1e300, 1e300 }, mx[3] = { -1e300, -1e300, -1e300 };
-        for (uint32_t i = c->ib; i < c->ie; i++)
-            for (int k = 0; k < 3; k++) {
-                if (c->poff[i + 1] == c->poff[i]) continue;
-                mn[k] = std::min(mn[k], c->h_img_bbox[(size_t)i * 6 + k]); mx[k] = std::max(mx[k], c->h_img_bbox[(size_t)i * 6 + 3 + k]);
-            }
-        GridGeom g0{};
-        frog_grid_info i0{};
-        if (mn[0] <= mx[0] && make_geometry(c, 0, mn, mx, g0, i0) == FROG_OK) {
-            g0.n_cp = (int)std::min<size_t>(0x7FFFFFFF, (size_t)g0.n_cp * 3 / 2);      // the registered box differs a little
-            if (int rc_ = lattice_alloc(c, g0)) { (void)rc_; (void)hipGetLastError(); }  // best effort: the set-up allocates again
-            // Finished lattices stay on the device (retire_current_grid).  A stream-ordered allocation per lattice cost 0.25 ms
-            // of host time with the GPU idle at the set-up of level 2 (the pool grows by a driver call whenever it is asked
-            // for a size it has not served yet, however much it holds): one block for them, about what three levels with their
-            // regrids take (1 + 2 x 8 + 3 x 64 lattices of level 0), best effort.
-            const size_t lattice0 = (size_t)c->n_owned() * (size_t)g0.n_cp;
-            size_t arena = std::min<size_t>(((size_t)2 << 30) / sizeof(float4), 224 * lattice0);
-            // The caller said how many levels it will run (frog_options::max_levels_hint): the buffers of the FINEST of them now,
-            // and an arena for three finished lattices per level.  A group of 500 images reaches 7.7 GB per lattice buffer at its
-            // fifth level; hipMalloc of such blocks took between 5 and 1 500 ms on the test boxes, inside the timed loops (the
-            // 130-step figure of BASELINE configs[4] moved between 45 and 166 it/s with it).  Best effort, and only while it leaves
-            // half of the free memory alone.
-            if (o->max_levels_hint > 1) {
-                const int finest = std::min(o->max_levels_hint, 12) - 1;
-                GridGeom gh{};
-                frog_grid_info ih{};
-                size_t free_b = 0, total_b = 0;
-                // The box the finest level will see is the REGISTERED group's, not the model's: frog_linear_init moves every image's
-                // anchor (the centre of its box, by default) onto the images' mean anchor, so the union of the images' boxes centred
-                // on one point is what is left of, say, +-100 mm of translation between them.  Estimated here from the per-image
-                // boxes; the union of the boxes where they lie (mn, mx) overstated cfg 5's finest lattice 3.8 times (4.4e6 control
-                // points against 0.92e6), `need` came to 320 GB of 293 and nothing was reserved: the set-up of level 4 then paid three
-                // hipMalloc of 7.4 GB inside the loops -- 17 ms on one box, 730-1 230 ms on another (round 6; FROG_SETUP_TRACE=1).
-                double rmn[3], rmx[3];
-                for (int k = 0; k < 3; k++) {
-                    double centre = 0, half = 0;
-                    uint32_t n_img = 0;
-                    for (uint32_t i = 0; i < c->nI; i++) {
-                        if (c->poff[i + 1] == c->poff[i]) continue;
-                        const double lo = c->h_img_bbox[(size_t)i * 6 + k], hi = c->h_img_bbox[(size_t)i * 6 + 3 + k];
-                        centre += 0.5 * (lo + hi); half = std::max(half, 0.5 * (hi - lo)); n_img++;
-                    }
-                    centre /= std::max(1u, n_img);
-                    rmn[k] = std::max(mn[k], centre - half); rmx[k] = std::min(mx[k], centre + half);
-                    if (!(rmn[k] < rmx[k])) { rmn[k] = mn[k]; rmx[k] = mx[k]; }
-                }
-                if (make_geometry(c, finest, rmn, rmx, gh, ih) == FROG_OK && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                    gh.n_cp = (int)std::min<size_t>(0x7FFFFFFF, (size_t)gh.n_cp * 3 / 2);       // the linear stage rescales the images; another anchor
-                    const size_t nO = c->n_owned(), nPts = c->own_pt_end - c->own_pt_begin;
-                    const size_t blocks = scatter_max_blocks((uint32_t)std::min<size_t>(0xFFFFFFFFu, nO * (size_t)gh.n_bricks), (uint32_t)nPts, SCATTER_CHUNK);
-                    const size_t E = (size_t)gh.brick + 3;
-                    size_t arena_h = 0;
-                    for (int l = 0; l <= finest; l++) {
-                        GridGeom gl{};
-                        frog_grid_info il{};
-                        if (make_geometry(c, l, rmn, rmx, gl, il) == FROG_OK) {
-                            arena_h += 3 * ((nO * (size_t)gl.n_cp * 5 / 4 + 63) / 64 * 64);
-                            // a sparse lattice retires with its bit maps and shared values (retire_current_grid): room for them too
-                            if (gl.sparse) arena_h += 3 * (((nO * (size_t)gl.mask_words + 3) / 4 + (size_t)gl.n_cp) * 5 / 4 + 128);
-                        }
-                    }
-                    // first the buffers of the level itself, then -- if that still leaves half of the free memory -- the arena
-                    const size_t need_level = (3 * nO * (size_t)gh.n_cp + blocks * E * E * E) * sizeof(float4)
-                                              + 3 * nO * (size_t)gh.n_bricks * (size_t)(gh.brick * gh.brick * gh.brick) * sizeof(uint32_t);
-                    const size_t need = need_level + arena_h * sizeof(float4);
-                    if (getenv("FROG_SETUP_TRACE"))
-                        std::fprintf(stderr, "[create] finest level %d: %d control points x %zu images (with head-room): %.2f GB for the level, %.2f GB with the arena, "
-                                     "%.2f GB free of %.2f: %s\n", finest, gh.n_cp, nO, need_level / 1e9, need / 1e9, free_b / 1e9, total_b / 1e9,
-                                     need < free_b / 2 ? "both reserved now" : need_level < free_b / 2 ? "the level's buffers reserved now" : "NOT reserved");
-                    if (need_level < free_b / 2) {
-                        if (int rc_ = lattice_alloc(c, gh)) { (void)rc_; (void)hipGetLastError(); }
-                        if (need < free_b / 2) arena = std::max(arena, arena_h);
-                    }
-                }
-                (void)hipGetLastError();
-            }
-            if (c->retired_arena.alloc(arena) != hipSuccess) (void)hipGetLastError();
-            c->retired_used = 0;
-        }
-    }
-    create_lap("+ lattices allocated");
-    {
-        // Resolve the kernels of the deformable stage now: the runtime creates a kernel's function object at its first
-        // launch, which cost the first deformable step of a run 0.1-0.15 ms of host time with the GPU idle (rocprofv3
-        // kernel trace: a gap in front of the first transform through a lattice).  Asking for the attributes does the same work.
-        const void *kernels[] = {
-            (const void *)sweep_kernel<SWEEP_DEFORMABLE, true, false, false, false>, (const void *)sweep_kernel<SWEEP_DEFORMABLE, true, false, true, false>,
-            (const void *)sweep_kernel<SWEEP_DEFORMABLE, true, false, false, true>, (const void *)sweep_kernel<SWEEP_COUNT, true, false, false, false>,
-            (const void *)scatter_kernel, (const void *)lattice_step_kernel<true>, (const void *)lattice_step_kernel<false>,
-            (const void *)transform_bspline_tile_kernel<float>, (const void *)transform_bspline_kernel<float>, (const void *)transform_bspline_kernel<float, 2>, (const void *)transform_zero_lattice_kernel,
-            (const void *)cp_center_kernel, (const void *)bounds_kernel, (const void *)bounds_final_kernel, (const void *)zero_buffers_kernel,
-            (const void *)brick_count_kernel, (const void *)brick_place_kernel, (const void *)cell_order_kernel, (const void *)brick_chunks_kernel,
-            (const void *)scan_block_sums_kernel, (const void *)scan_of_sums_kernel, (const void *)scan_apply_kernel,
-            (const void *)block_fill_kernel, (const void *)block_len_base_kernel, (const void *)block_sort_kernel,
-            (const void *)cull_list_cutoff_kernel, (const void *)cull_allow_kernel, (const void *)cull_validate_kernel, (const void *)cull_disp_kernel,
-            (const void *)count_reduce_kernel, (const void *)combine_groups_kernel, (const void *)energy_reduce_kernel,
-            (const void *)lattice_step_kernel<true, LS_CPB_SMALL>, (const void *)lattice_step_kernel<false, LS_CPB_SMALL>,
-            (const void *)stats_publish_kernel, (const void *)cull_allow_validate_kernel, (const void *)cull_count_kernel,
-            (const void *)sweep_kernel<SWEEP_LINEAR, true, false, true, false>, (const void *)sweep_kernel<SWEEP_LINEAR, true, false, false, false>,
-        };
+    clock.lap("+ everything else allocated, uploads done");
+    return FROG_OK;
+}
 
-        for (const void *k : kernels) { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, k); }
-        (void)hipGetLastError();
+// The box the finest level will see is the REGISTERED group's, not the model's: frog_linear_init moves every image's
+// anchor (the centre of its box, by default) onto the images' mean anchor, so the union of the images' boxes centred
+// on one point is what is left of, say, +-100 mm of translation between them.  Estimated here from the per-image
+// boxes; the union of the boxes where they lie (mn, mx) overstated cfg 5's finest lattice 3.8 times (4.4e6 control
+// points against 0.92e6), `need` came to 320 GB of 293 and nothing was reserved: the set-up of level 4 then paid three
+// hipMalloc of 7.4 GB inside the loops -- 17 ms on one box, 730-1 230 ms on another (round 6; FROG_SETUP_TRACE=1).
+static void registered_box(const frog_ctx *c, const double mn[3], const double mx[3], double rmn[3], double rmx[3])
+{
+    for (int k = 0; k < 3; k++) {
+        double centre = 0, half = 0;
+        uint32_t n_img = 0;
+        for (uint32_t i = 0; i < c->nI; i++) {
+            if (c->poff[i + 1] == c->poff[i]) continue;
+            const double lo = c->h_img_bbox[(size_t)i * 6 + k], hi = c->h_img_bbox[(size_t)i * 6 + 3 + k];
+            centre += 0.5 * (lo + hi); half = std::max(half, 0.5 * (hi - lo)); n_img++;
+        }
+        centre /= std::max(1u, n_img);
+        rmn[k] = std::max(mn[k], centre - half); rmx[k] = std::min(mx[k], centre + half);
+        if (!(rmn[k] < rmx[k])) { rmn[k] = mn[k]; rmx[k] = mx[k]; }
     }
-    scratch_warm_kernel<<<1, 64, 0, s>>>(c->stray.p, 0);
+}
+
+// the lattice buffers of level 0 (with their head-room) for the box of the model as it is: close enough to what
+// the first frog_deformable_setup will ask for that it finds them allocated.  Best effort throughout.
+static void reserve_lattices(frog_ctx *c, const CreateClock &clock)
+{
+    double mn[3] = { 1e300, 1e300, 1e300 }, mx[3] = { -1e300, -1e300, -1e300 };
+    for (uint32_t i = c->ib; i < c->ie; i++)
+        for (int k = 0; k < 3; k++) {
+            if (c->poff[i + 1] == c->poff[i]) continue;
+            mn[k] = std::min(mn[k], c->h_img_bbox[(size_t)i * 6 + k]); mx[k] = std::max(mx[k], c->h_img_bbox[(size_t)i * 6 + 3 + k]);
+        }
+    GridGeom g0{};
+    frog_grid_info i0{};
+    if (mn[0] <= mx[0] && make_geometry(c, 0, mn, mx, g0, i0) == FROG_OK) {
+        g0.n_cp = (int)std::min<size_t>(0x7FFFFFFF, (size_t)g0.n_cp * 3 / 2);      // the registered box differs a little
+        if (int rc_ = lattice_alloc(c, g0)) { (void)rc_; (void)hipGetLastError(); }  // best effort: the set-up allocates again
+        // Finished lattices stay on the device (retire_current_grid).  A stream-ordered allocation per lattice cost 0.25 ms
+        // of host time with the GPU idle at the set-up of level 2 (the pool grows by a driver call whenever it is asked
+        // for a size it has not served yet, however much it holds): one block for them, about what three levels with their
+        // regrids take (1 + 2 x 8 + 3 x 64 lattices of level 0), best effort.
+        const size_t lattice0 = (size_t)c->n_owned() * (size_t)g0.n_cp;
+        size_t arena = std::min<size_t>(((size_t)2 << 30) / sizeof(float4), 224 * lattice0);
+        // The caller said how many levels it will run (frog_options::max_levels_hint): the buffers of the FINEST of them now,
+        // and an arena for three finished lattices per level.  A group of 500 images reaches 7.7 GB per lattice buffer at its
+        // fifth level; hipMalloc of such blocks took between 5 and 1 500 ms on the test boxes, inside the timed loops (the
+        // 130-step figure of BASELINE configs[4] moved between 45 and 166 it/s with it).  Best effort, and only while it leaves
+        // half of the free memory alone.
+        if (c->opt.max_levels_hint > 1) {
+            const int finest = std::min(c->opt.max_levels_hint, 12) - 1;
+            GridGeom gh{};
+            frog_grid_info ih{};
+            size_t free_b = 0, total_b = 0;
+            double rmn[3], rmx[3];
+            registered_box(c, mn, mx, rmn, rmx);
+            if (make_geometry(c, finest, rmn, rmx, gh, ih) == FROG_OK && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+                gh.n_cp = (int)std::min<size_t>(0x7FFFFFFF, (size_t)gh.n_cp * 3 / 2);       // the linear stage rescales the images; another anchor
+                const size_t nO = c->n_owned(), nPts = c->own_pt_end - c->own_pt_begin;
+                const size_t blocks = scatter_max_blocks((uint32_t)std::min<size_t>(0xFFFFFFFFu, nO * (size_t)gh.n_bricks), (uint32_t)nPts, SCATTER_CHUNK);
+                const size_t E = (size_t)gh.brick + 3;
+                size_t arena_h = 0;
+                for (int l = 0; l <= finest; l++) {
+                    GridGeom gl{};
+                    frog_grid_info il{};
+                    if (make_geometry(c, l, rmn, rmx, gl, il) == FROG_OK) {
+                        arena_h += 3 * ((nO * (size_t)gl.n_cp * 5 / 4 + 63) / 64 * 64);
+                        // a sparse lattice retires with its bit maps and shared values (retire_current_grid): room for them too
+                        if (gl.sparse) arena_h += 3 * (((nO * (size_t)gl.mask_words + 3) / 4 + (size_t)gl.n_cp) * 5 / 4 + 128);
+                    }
+                }
+                // first the buffers of the level itself, then -- if that still leaves half of the free memory -- the arena
+                const size_t need_level = (3 * nO * (size_t)gh.n_cp + blocks * E * E * E) * sizeof(float4)
+                                          + 3 * nO * (size_t)gh.n_bricks * (size_t)(gh.brick * gh.brick * gh.brick) * sizeof(uint32_t);
+                const size_t need = need_level + arena_h * sizeof(float4);
+                if (c->sw.setup_trace)
+                    std::fprintf(stderr, "[create] finest level %d: %d control points x %zu images (with head-room): %.2f GB for the level, %.2f GB with the arena, "
+                                 "%.2f GB free of %.2f: %s\n", finest, gh.n_cp, nO, need_level / 1e9, need / 1e9, free_b / 1e9, total_b / 1e9,
+                                 need < free_b / 2 ? "both reserved now" : need_level < free_b / 2 ? "the level's buffers reserved now" : "NOT reserved");
+                if (need_level < free_b / 2) {
+                    if (int rc_ = lattice_alloc(c, gh)) { (void)rc_; (void)hipGetLastError(); }
+                    if (need < free_b / 2) arena = std::max(arena, arena_h);
+                }
+            }
+            (void)hipGetLastError();
+        }
+        if (c->retired_arena.alloc(arena) != hipSuccess) (void)hipGetLastError();
+        c->retired_used = 0;
+    }
+    clock.lap("+ lattices allocated");
+}
+
+// Resolve the kernels of the deformable stage now: the runtime creates a kernel's function object at its first
+// launch, which cost the first deformable step of a run 0.1-0.15 ms of host time with the GPU idle (rocprofv3
+// kernel trace: a gap in front of the first transform through a lattice).  Asking for the attributes does the same work.
+static void resolve_kernels(frog_ctx *c, const CreateClock &clock)
+{
+    const void *kernels[] = {
+        (const void *)sweep_kernel<SWEEP_DEFORMABLE, true, false, false, false>, (const void *)sweep_kernel<SWEEP_DEFORMABLE, true, false, true, false>,
+        (const void *)sweep_kernel<SWEEP_DEFORMABLE, true, false, false, true>, (const void *)sweep_kernel<SWEEP_COUNT, true, false, false, false>,
+        (const void *)scatter_kernel, (const void *)lattice_step_kernel<true>, (const void *)lattice_step_kernel<false>,
+        (const void *)transform_bspline_tile_kernel<float>, (const void *)transform_bspline_kernel<float>, (const void *)transform_bspline_kernel<float, 2>, (const void *)transform_zero_lattice_kernel,
+        (const void *)cp_center_kernel, (const void *)bounds_kernel, (const void *)bounds_final_kernel, (const void *)zero_buffers_kernel,
+        (const void *)brick_count_kernel, (const void *)brick_place_kernel, (const void *)cell_order_kernel, (const void *)brick_chunks_kernel,
+        (const void *)scan_block_sums_kernel, (const void *)scan_of_sums_kernel, (const void *)scan_apply_kernel,
+        (const void *)block_fill_kernel, (const void *)block_len_base_kernel, (const void *)block_sort_kernel,
+        (const void *)cull_list_cutoff_kernel, (const void *)cull_allow_kernel, (const void *)cull_validate_kernel, (const void *)cull_disp_kernel,
+        (const void *)count_reduce_kernel, (const void *)combine_groups_kernel, (const void *)energy_reduce_kernel,
+        (const void *)lattice_step_kernel<true, LS_CPB_SMALL>, (const void *)lattice_step_kernel<false, LS_CPB_SMALL>,
+        (const void *)stats_publish_kernel, (const void *)cull_allow_validate_kernel, (const void *)cull_count_kernel,
+        (const void *)sweep_kernel<SWEEP_LINEAR, true, false, true, false>, (const void *)sweep_kernel<SWEEP_LINEAR, true, false, false, false>,
+    };
+    for (const void *k : kernels) { hipFuncAttributes fa; (void)hipFuncGetAttributes(&fa, k); }
     (void)hipGetLastError();
-    (void)hipStreamSynchronize(s);
-    create_lap("+ kernels resolved, stream idle");
-    const auto t_resident = std::chrono::steady_clock::now();
-    c->create_s[1] = std::chrono::duration<double>(t_resident - t_layout).count();
-    // selections of the first sel_ring - 1 refreshes, ahead of time -- and awaited: a context leaves frog_create with an idle
-    // side stream (80 replays are 0.12 s of one-block-per-image work that would otherwise run beside the first iterations)
+    scratch_warm_kernel<<<1, 64, 0, c->stream>>>(c->stray.p, 0);
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(c->stream);
+    clock.lap("+ kernels resolved, stream idle");
+}
+
+// selections of the first sel_ring - 1 refreshes, ahead of time -- and awaited: a context leaves frog_create with an idle
+// side stream (80 replays are 0.12 s of one-block-per-image work that would otherwise run beside the first iterations)
+static int replay_selections(frog_ctx *c)
+{
     for (int k = 0; k + 1 < c->sel_ring; k++)
-        if (int rc_ = produce_selection(c)) { frog_destroy(c); return rc_; }
+        if (int rc_ = produce_selection(c)) return rc_;
     if (!c->opt.selections_in_background && hipStreamSynchronize(c->side) != hipSuccess) { (void)hipGetLastError(); }
-    c->create_s[2] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_resident).count();
     c->create_selections = c->sel_ring > 0 ? c->sel_ring - 1 : 0;
-    c->created = true;
+    return FROG_OK;
+}
+#undef CREATE_CHECK
+
+// One context for [image_begin, image_end), without fixed images.  create_s: [0] the host layout and the wait for the device,
+// [1] allocations + uploads + first kernels, [2] the selections replayed ahead.
+static int create_stages(frog_ctx *c, const frog_model *m)
+{
+    using clk = std::chrono::steady_clock;
+    auto seconds = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    int rc;
+    const auto t_create0 = clk::now();
     // (The host copy of the layout -- 0.8 GB for the benchmark group -- dies with this scope: 0.07 s of unmapping.  Round 6 gave it
     // to a thread of its own; the first iterations then ran beside the unmapping of memory the runtime had pinned for the uploads,
     // and in one run of two the linear stage of a timed loop took 52 ms instead of 19.  Not kept.)
-#undef CREATE_CHECK
+    Layout lay;
+    if ((rc = create_host_layout(c, m, lay))) return rc;
+    if ((rc = create_select_device(c))) return rc;
+    const CreateClock clock{ c->sw.timing, clk::now() };
+    c->create_s[0] = seconds(t_create0, clock.t0);
+    if ((rc = create_adopt_layout(c, lay))) return rc;
+    if ((rc = create_streams(c, clock))) return rc;
+    if ((rc = create_points(c, m, lay, clock))) return rc;
+    if ((rc = create_reference_links(c, lay, clock))) return rc;
+    if ((rc = create_records(c, lay, clock))) return rc;
+    if ((rc = create_sweep_tables(c, lay))) return rc;
+    if ((rc = create_statistics(c, lay))) return rc;
+    if ((rc = create_solver_buffers(c, clock))) return rc;
+    reserve_lattices(c, clock);
+    resolve_kernels(c, clock);
+    const auto t_resident = clk::now();
+    c->create_s[1] = seconds(clock.t0, t_resident);
+    if ((rc = replay_selections(c))) return rc;
+    c->create_s[2] = seconds(t_resident, clk::now());
+    c->created = true;
+    return FROG_OK;
+}
+
+extern "C" {
+
+int frog_create(const frog_model *m, const frog_options *o, int device,
+                uint32_t image_begin, uint32_t image_end, frog_ctx **out)
+{
+    if (!m || !o || !out) return fail(FROG_E_INVALID, "null argument");
+    *out = nullptr;
+    if (m->n_images < 1 || image_begin >= image_end || image_end > m->n_images)
+        return fail(FROG_E_INVALID, "bad image range");
+    for (size_t i = 0; i < sizeof(o->reserved) / sizeof(o->reserved[0]); i++)
+        if (o->reserved[i]) return fail(FROG_E_INVALID, "reserved option fields must be 0");
+    if (o->stats_max_size < 1) return fail(FROG_E_INVALID, "stats_max_size < 1");
+    if (o->n_fixed_images) {
+        // fixed images (-fi, imageGroup.cxx:34): a context for the moving images plus a stats-only one
+        const uint32_t nf = (uint32_t)o->n_fixed_images;
+        if (o->n_fixed_images < 0 || nf >= m->n_images) return fail(FROG_E_INVALID, "n_fixed_images must leave at least one moving image");
+        if (image_begin != 0 || image_end != m->n_images)
+            return fail(FROG_E_INVALID, "n_fixed_images needs the whole group in one context");
+        frog_options o2 = *o;
+        o2.n_fixed_images = 0;
+        frog_ctx *moving = nullptr, *fixed = nullptr;
+        int rc = frog_create(m, &o2, device, nf, m->n_images, &moving);
+        if (rc) return rc;
+        frog_options o3 = o2;
+        o3.max_levels_hint = 0;                                     // a statistics-only context never holds a lattice
+        rc = frog_create(m, &o3, device, 0, nf, &fixed);
+        if (rc) { frog_destroy(moving); return rc; }
+        fixed->cull_enabled = false;                                // a statistics-only context never sweeps a lattice step
+        fixed->act_recs32.release(); fixed->act_recs.release(); fixed->act_cnt.release(); fixed->pos2_snap.release();
+        rc = frog_set_stream(fixed, moving->stream);
+        if (rc) { frog_destroy(fixed); frog_destroy(moving); return rc; }
+        moving->helper = fixed;
+        moving->nf = nf;
+        moving->opt.n_fixed_images = o->n_fixed_images;
+        *out = moving;
+        return FROG_OK;
+    }
+    frog_ctx *c = new (std::nothrow) frog_ctx;
+    if (!c) return fail(FROG_E_NOMEM, "out of host memory");
+    c->sw = read_switches(MAX_SUBPASS);
+    c->device = device;
+    c->opt = *o;
+    c->ib = image_begin; c->ie = image_end;
+    if (const int rc = create_stages(c, m)) {
+        // (before its stream exists a context holds nothing of the device's, and the device index may be what was wrong: no HIP call then)
+        if (c->stream) frog_destroy(c); else delete c;
+        return rc;
+    }
     *out = c;
     return FROG_OK;
 }
@@ -1385,16 +1441,15 @@ static int launch_transform(frog_ctx *ctx, P3 *out, int apply, bool after_step =
         // A block is one wavefront walking up to SCATTER_CHUNK points: below about a million points (one rank of eight of cfg 3:
         // 240 000) there are too few of them to fill the chip and the thread-per-point form wins (16 against 29 us).
         // FROG_K11_POINTWISE / FROG_K11_TILED force one form (tests).
-        const bool tiled = ctx->n_scatter_blocks > 0 && ctx->geom.brick == 4 && !getenv("FROG_K11_POINTWISE")
-                           && (n >= 1000000u || getenv("FROG_K11_TILED"));
+        const bool tiled = ctx->n_scatter_blocks > 0 && ctx->geom.brick == 4 && !ctx->sw.k11_pointwise
+                           && (n >= 1000000u || ctx->sw.k11_tiled);
         if (tiled) {
             // one wavefront per scatter block, the brick's coefficients in LDS (k_grid.hip.h)
             const GeomDev gd = to_dev(ctx->geom);
             const size_t lds = (size_t)K11_TILE_ENTRIES * sizeof(float4);      // brick == 4 (checked above): the strided 7^3 tile
-            auto kernel = ctx->k11_f64 ? transform_bspline_tile_kernel<double> : transform_bspline_tile_kernel<float>;
+            auto kernel = ctx->sw.k11_f64 ? transform_bspline_tile_kernel<double> : transform_bspline_tile_kernel<float>;
             // FROG_K11_BY_XCD=1 / 0 forces / forbids the brick-order walk (k_grid.hip.h); default: on lattices with many small blocks
-            static const int by_xcd_env = getenv("FROG_K11_BY_XCD") ? atoi(getenv("FROG_K11_BY_XCD")) : -1;
-            const bool by_xcd = by_xcd_env >= 0 ? by_xcd_env != 0 : ctx->n_scatter_blocks >= 16384u;
+            const bool by_xcd = ctx->sw.k11_by_xcd >= 0 ? ctx->sw.k11_by_xcd != 0 : ctx->n_scatter_blocks >= 16384u;
             const uint32_t grid = by_xcd ? ((ctx->n_scatter_blocks + 7u) & ~7u) : ctx->n_scatter_blocks;     // the walk's grid: a multiple of 8
             kernel<<<grid, 64, lds, ctx->stream>>>(
                 ctx->pos.p, ctx->pos_b.p, out, ctx->coeff.p, ctx->perm.p,
@@ -1405,11 +1460,10 @@ static int launch_transform(frog_ctx *ctx, P3 *out, int apply, bool after_step =
                 ctx->disp_allow.p, ctx->cull_state.p, host_scalars, scalar_seq, trailer, by_xcd ? ctx->n_scatter_blocks : 0u);
             record_displacement(ctx, out, with_disp, ctx->n_scatter_blocks);
         } else {
-            auto kernel = ctx->k11_f64 ? transform_bspline_kernel<double> : (ctx->geom.brick == 8 ? transform_bspline_kernel<float, 2> : transform_bspline_kernel<float>);
+            auto kernel = ctx->sw.k11_f64 ? transform_bspline_kernel<double> : (ctx->geom.brick == 8 ? transform_bspline_kernel<float, 2> : transform_bspline_kernel<float>);
             // FROG_K11_POINT_BY_XCD=1 / 0 forces / forbids the XCD-aware order of the blocks (k_grid.hip.h); default: from 8 192 blocks
-            static const int pt_xcd_env = getenv("FROG_K11_POINT_BY_XCD") ? atoi(getenv("FROG_K11_POINT_BY_XCD")) : -1;
             const uint32_t nb = div_up(n, 256);
-            const bool pt_xcd = pt_xcd_env >= 0 ? pt_xcd_env != 0 : nb >= 8192u;
+            const bool pt_xcd = ctx->sw.k11_point_by_xcd >= 0 ? ctx->sw.k11_point_by_xcd != 0 : nb >= 8192u;
             kernel<<<pt_xcd ? ((nb + 7u) & ~7u) : nb, 256, 0, ctx->stream>>>(ctx->pos.p, ctx->pos_b.p, out, ctx->coeff.p,
                                                                              ctx->perm.p, n, ctx->ib, to_dev(ctx->geom), apply,
                                                                              with_disp ? ctx->pos2_snap.p : nullptr, ctx->disp_part.p,
@@ -1751,7 +1805,7 @@ static int make_geometry(const frog_ctx *ctx, int level, const double mins[3], c
     // brick edge: 4 cells (5.5 KB tile, many resident wavefronts) while bricks keep enough points to
     // amortise their flush, else 8
     g.brick = ((double)nPts / ((double)nO * (double)bricks_for(4)) >= 24.0) ? 4 : 8;
-    if (const char *e = getenv("FROG_BRICK")) { const int b = atoi(e); if (b == 4 || b == 8) g.brick = b; }      // test hook
+    if (ctx->sw.brick) g.brick = ctx->sw.brick;     // test hook
     for (int k = 0; k < 3; k++) g.nbricks[k] = (g.cells[k] + g.brick - 1) / g.brick;
     const size_t nb = bricks_for(g.brick);
     if (nb * nO >= 0x7FFFFFFFull) return fail(FROG_E_INVALID, "too many bricks");
@@ -1768,11 +1822,9 @@ static int make_geometry(const frog_ctx *ctx, int level, const double mins[3], c
     // FROG_LATTICE_BLOCKED / FROG_LATTICE_SPARSE = 0 / 1 force a form (A/B, tests); reference-order mode keeps the plain one.
     g.lat_images = nO;
     {
-        static const char *e = getenv("FROG_LATTICE_BLOCKED");
-        static const char *es = getenv("FROG_LATTICE_SPARSE");
         const bool fine = nO >= 32u && (size_t)nO * G >= ((size_t)1 << 27);
-        g.blocked = e ? atoi(e) != 0 : fine;
-        g.sparse = es ? atoi(es) != 0 : fine;
+        g.blocked = ctx->sw.lattice_blocked >= 0 ? ctx->sw.lattice_blocked != 0 : fine;
+        g.sparse = ctx->sw.lattice_sparse >= 0 ? ctx->sw.lattice_sparse != 0 : fine;
         if (ctx->ref_order) g.blocked = g.sparse = false;
         g.mask_words = (uint32_t)((G + 31) / 32) + 1u;          // per image: a bit per node (+ 1: a tile row may be written through the word behind its last bit)
     }
@@ -1794,7 +1846,7 @@ static int lattice_alloc(frog_ctx *ctx, const GridGeom &g)
     const size_t max_blocks = std::max<size_t>(1, scatter_max_blocks((uint32_t)n_bricks_total, nPts, SCATTER_CHUNK));
     const size_t E = (size_t)g.brick + 3;
     const size_t LG = std::max(g.lat_entries(), (size_t)nO * G);       // entries of one lattice in its layout (blocked: nodes padded to 16)
-    if (getenv("FROG_SETUP_TRACE"))
+    if (ctx->sw.setup_trace)
         std::fprintf(stderr, "[lattice_alloc] %zu entries per lattice (capacity now %zu), %zu keys (capacity %zu), %zu blocks, mask %zu words (capacity %zu)\n",
                      LG, ctx->coeff.cap, n_keys, ctx->key_counts.cap, max_blocks, g.sparse ? (size_t)nO * g.mask_words : (size_t)0, ctx->lat_mask.cap);
     if (ctx->created && (LG > ctx->coeff.cap || LG > ctx->grad.cap || LG > ctx->gradf.cap || n_keys > ctx->key_counts.cap)) ctx->lattice_reallocs++;
@@ -1876,12 +1928,10 @@ int frog_deformable_setup_bounds(frog_ctx *ctx, int level, const double mins[3],
     CTX_GUARD(ctx);
     if (level < 0 || level > 30) return fail(FROG_E_INVALID, "bad level");
     ctx->xyz2_fresh = false; ctx->res_valid = false; ctx->rc_valid = false;
-    // FROG_SETUP_TRACE=1: where the host's time in this call goes (a level's first lattice has been seen to take 0.7 s of it on
-    // some boxes and 0.016 s on others)
-    static const bool setup_trace = getenv("FROG_SETUP_TRACE") != nullptr;
+    // FROG_SETUP_TRACE=1: where the host's time in this call goes
     const auto t_setup = std::chrono::steady_clock::now();
     auto setup_lap = [&](const char *what) {
-        if (setup_trace) std::fprintf(stderr, "[setup level %d] %-28s %9.3f ms\n", level, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_setup).count());
+        if (ctx->sw.setup_trace) std::fprintf(stderr, "[setup level %d] %-28s %9.3f ms\n", level, what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_setup).count());
     };
     int rc = join_setup(ctx);                   // a set-up right behind a set-up
     if (rc) return rc;
@@ -1964,7 +2014,7 @@ static int cull_allocate(frog_ctx *ctx)
     ctx->act_recs32.release(); ctx->act_recs.release(); ctx->act_cnt.release(); ctx->pos2_snap.release();
     ctx->cut_list.release(); ctx->disp_part.release(); ctx->cull_state.release(); ctx->disp_allow.release();
     ctx->cull_enabled = false;
-    ctx->fused_sweep = ctx->fused_sweep && ctx->fused_forced;
+    ctx->fused_sweep = ctx->fused_sweep && ctx->sw.fused == 1;
     return FROG_OK;
 }
 
@@ -2006,12 +2056,12 @@ static int cull_prepare(frog_ctx *ctx)
     if (rc) return rc;
     if (!ctx->cull_enabled) return FROG_OK;     // the buffers did not fit
     if (ctx->cull_need_build) {
-        cull_list_cutoff_kernel<<<div_up(nI, 64), 64, 0, s>>>(ctx->cut_now.p, nI, ctx->deformable ? ctx->cull_scale : ctx->cull_lin_scale,
-                                                              ctx->deformable ? ctx->cull_pad : ctx->cull_lin_pad, ctx->cut_list.p);
+        cull_list_cutoff_kernel<<<div_up(nI, 64), 64, 0, s>>>(ctx->cut_now.p, nI, ctx->deformable ? ctx->sw.cull_scale : ctx->sw.cull_lin_scale,
+                                                              ctx->deformable ? ctx->sw.cull_pad : ctx->sw.cull_lin_pad, ctx->cut_list.p);
         FROG_HIP_CHECK(hipMemcpyAsync(ctx->pos2_snap.p, ctx->pos2.p, ctx->P * sizeof(P3), hipMemcpyDeviceToDevice, s));
         // the list itself: written by the sweep this call prepares (it walks every record anyway: k_links.hip.h BUILD), or,
         // for the record formats that sweep does not cover, by a pass of its own
-        ctx->build_in_sweep = sweep_builds_list(ctx) && !getenv("FROG_CULL_BUILD_PASS");
+        ctx->build_in_sweep = sweep_builds_list(ctx) && !ctx->sw.cull_build_pass;
         if (!ctx->build_in_sweep) {
             const SweepArgs args = sweep_args(ctx, 0);
             const dim3 grid(sweep_blocks(ctx), ctx->n_sub);
@@ -2097,7 +2147,7 @@ int frog_deformable_phase_a(frog_ctx *ctx, float alpha)
         // the energy sums: by the first blocks of the scatter's launch (k_grid.hip.h), unless something between here and the
         // scatter needs them (landmark constraints add to them) or there is no scatter to ride on
         ctx->stray_parity ^= 1u;
-        fused_energy = ctx->n_scatter_blocks && !ctx->n_hard && !getenv("FROG_ENERGY_PASS");
+        fused_energy = ctx->n_scatter_blocks && !ctx->n_hard && !ctx->sw.energy_pass;
         if (!fused_energy)
             energy_reduce_kernel<<<ENERGY_BLOCKS, 256, 0, s>>>(ctx->tile_partial.p, ctx->n_tiles * ctx->n_groups, 2, 0, ctx->energy_blocks.p,
                                                                ctx->energy_ticket.p, ctx->energy.p, culled ? ctx->cull_state.p : nullptr,

@@ -132,13 +132,13 @@ inline void build_numbering(const frog_model &m, Layout &out)
     }
 }
 
-inline int build_layout(const frog_model &m, uint32_t ib, uint32_t ie, bool force_wide, int n_groups, Layout &out, std::string &err)
+inline int build_layout(const frog_model &m, uint32_t ib, uint32_t ie, bool force_wide, int n_groups, bool timing, Layout &out, std::string &err)
 {
     const uint32_t nI = m.n_images;
     const uint32_t *poff = m.point_offset;
     const auto t_in = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
-        if (std::getenv("FROG_TIMING")) std::printf("[timing] build_layout, %s : %gs\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_in).count());
+        if (timing) std::printf("[timing] build_layout, %s : %gs\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_in).count());
     };
     build_numbering(m, out);
     lap("numbering");
@@ -298,6 +298,35 @@ inline int build_layout(const frog_model &m, uint32_t ib, uint32_t ie, bool forc
 
     lap("+ records placed");
     return FROG_OK;
+}
+
+// Fused deformable sweep (k_links.hip.h FUSED): block b works on tile order[b], and b % 8 -- the XCD the block lands on
+// under round-robin dispatch -- is the tile's eighth of its image along the Morton curve, so that an XCD's L2 sees the
+// same eighth of every image: its own tiles' and, since true matches are spatial neighbours, nearly all their partners'.
+// Within an XCD's list the tiles go slice by slice, image by image inside a slice (a slice = one of FROG_TILE_SLICES
+// equal parts of the eighth, along the curve): the blocks resident on an XCD at any time then gather from 1/16 of every
+// partner image instead of 1/8 (1.5 MB of coordinates instead of 3 MB beside the record stream in a 4 MB L2).
+// Measured on cfg 3: 0.2486 -> 0.2446 ms with two slices; 3, 4 and 8 slices the same as two (0.2451-0.2460).  A context
+// that owns an eighth of that group (12-13 images, 118 tiles per list: little more than one round of resident blocks)
+// keeps gaining: 0.0702 / 0.0663 / 0.0651 / 0.0641 ms with 1 / 2 / 4 / 8 slices -- hence eight below 64 owned images.
+// tile_slices: Switches::tile_slices (0: that default).  Returns the number of blocks; `order` holds at least one entry,
+// 0xFFFFFFFF where a block has no tile.
+inline uint32_t fused_block_order(const Layout &lay, uint32_t ib, uint32_t ie, int tile_slices, std::vector<uint32_t> &order)
+{
+    std::vector<uint32_t> lists[N_XCD];
+    const int n_slices = tile_slices ? tile_slices : (ie - ib >= 64u ? 2 : 8);
+    for (int sl = 0; sl < n_slices; sl++)
+        for (uint32_t i = ib; i < ie; i++) {
+            const uint32_t tb = lay.img_tile_ptr[i], nt = lay.img_tile_ptr[i + 1] - tb;
+            for (uint32_t j = 0; j < nt; j++)
+                if ((int)(((size_t)j * N_XCD * n_slices / nt) % n_slices) == sl) lists[(size_t)j * N_XCD / nt].push_back(tb + j);
+        }
+    size_t rounds = 0;
+    for (auto &l : lists) rounds = std::max(rounds, l.size());
+    order.assign(std::max<size_t>(1, rounds * N_XCD), 0xFFFFFFFFu);
+    for (int x = 0; x < N_XCD; x++)
+        for (size_t r = 0; r < lists[x].size(); r++) order[r * N_XCD + x] = lists[x][r];
+    return (uint32_t)(rounds * N_XCD);
 }
 
 } // namespace frog

@@ -65,6 +65,7 @@ def run_reference_order(pairs, monkeypatch, li, dl, di, images, **env):
         elif kind in ("linear", "deformable"):
             trace.append((kind, s.xyz2().copy(), s.matrices().copy(), float(e[0])))
     grids = schedule.run([s], li, [di] * dl, on=check)
+    trace.append(("final", s.xyz2().copy(), s.matrices().copy()))
     lattices = [np.stack([s.grid(i, k)[1] for i in images]) for k in range(s.num_grids())]
     return grids, trace, lattices
 
@@ -98,38 +99,17 @@ def test_reference_order_fast_forms_equal_the_literal_forms(monkeypatch, group):
     same_trace(fast, literal)
 
 
-def test_reference_order_chain_launches_folded_into_two_grid_dimensions():
-    """rc_grid() with at most 5 workgroups in x (FROG_RC_GRID_X=5, read once per process: a child): the fill's and the chain
-    kernel's groups come from blockIdx.z / .y * gridDim.x + blockIdx.x with a bound check, as on cfg 5's finest lattice where
-    the fold is needed -- same lattices, coordinates and energies as the unfolded launch."""
-    import os, subprocess, sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = (
-        "import sys, os, numpy as np\n"
-        "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
-        "from frog_amd import schedule\n"
-        "from frog_amd.pairs import Pairs\n"
-        "from gpu_util import Side\n"
-        "os.environ['FROG_REFERENCE_ORDER'] = '1'\n"
-        "s = Side(Pairs.synthetic(6, 3000, 1500, seed=7))\n"
-        "grids = schedule.run([s], 6, [8] * 3)\n"
-        "np.savez(sys.argv[1], xyz2=s.xyz2(), m=s.matrices(), **{'g%%d' %% k: np.stack([s.grid(i, k)[1] for i in range(6)]) for k in range(s.num_grids())})\n"
-    ) % (os.path.dirname(here), here)
-    outs = []
-    for fold in (None, "5"):
-        env = dict(os.environ)
-        env.pop("FROG_RC_GRID_X", None)
-        if fold:
-            env["FROG_RC_GRID_X"] = fold
-        out = os.path.join(os.environ.get("TMPDIR", "/tmp"), "frog_rc_grid_%s_%d.npz" % (fold or "plain", os.getpid()))
-        r = subprocess.run([sys.executable, "-c", code, out], env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        outs.append(np.load(out))
-        os.remove(out)
-    a, b = outs
-    assert sorted(a.files) == sorted(b.files) and len(a.files) >= 5
-    for k in a.files:
-        assert np.array_equal(a[k], b[k]), k
+def test_reference_order_chain_launches_folded_into_two_grid_dimensions(monkeypatch):
+    """rc_grid() with at most 5 workgroups in x (FROG_RC_GRID_X=5, a switch of the context like every other): the fill's and the
+    chain kernel's groups come from blockIdx.z / .y * gridDim.x + blockIdx.x with a bound check, as on cfg 5's finest lattice
+    where the fold is needed -- same per-step sums, gradients, energies, coordinates, matrices and lattices as the unfolded
+    launch.  The folded context is the SECOND of the process: a cap that the first context fixed for everyone would test nothing."""
+    monkeypatch.delenv("FROG_RC_GRID_X", raising=False)
+    pairs, images = Pairs.synthetic(6, 3000, 1500, seed=7), list(range(6))
+    plain = run_reference_order(pairs, monkeypatch, 6, 3, 8, images)
+    folded = run_reference_order(pairs, monkeypatch, 6, 3, 8, images, FROG_RC_GRID_X="5")
+    assert len(plain[2]) >= 3 and plain[1][-1][0] == "final"      # with the final coordinates and matrices: five arrays or more
+    same_trace(plain, folded)
 
 
 def test_reference_order_fast_forms_equal_the_literal_forms_at_config5_size(monkeypatch):
