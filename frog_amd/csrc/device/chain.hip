@@ -842,43 +842,40 @@ struct frog_chain {
     frog::DevBuf<DevLink> d_links;
 };
 
-// mean and stdev of a group on one grid
-struct frog_average {
+// What every group accumulator holds: its device and grid, and the staging of the volume an add was given.
+struct frog_group {
     int device = 0;
     frog_volume grid;
-    uint32_t n_images = 0, added = 0;
-    bool finished = false;
     size_t total = 0;
-    frog::DevBuf<float> d_avg, d_sq;
     frog::DevBuf<unsigned char> d_src, d_out;       // staging of the current source / resliced volume, grown on demand
 };
 
+// mean and stdev of a group on one grid
+struct frog_average : frog_group {
+    uint32_t n_images = 0, added = 0;
+    bool finished = false;
+    frog::DevBuf<float> d_avg, d_sq;
+};
+
 // running mean, squared deviations and count of the images that cover each voxel of one grid
-struct frog_cover {
-    int device = 0;
-    frog_volume grid;
+struct frog_cover : frog_group {
     uint32_t added = 0;
-    size_t total = 0;
     frog::DevBuf<float> d_mean, d_m2;
     frog::DevBuf<uint16_t> d_count;
-    frog::DevBuf<unsigned char> d_src, d_out, d_mask;   // staging of the current source / resliced volume / u8 mask, grown on demand
-    std::vector<unsigned char> h_mask;                  // the mask as value != 0, before its upload
+    frog::DevBuf<unsigned char> d_mask;             // staging of the current u8 mask, grown on demand
+    std::vector<unsigned char> h_mask;              // the mask as value != 0, before its upload
 };
 
 // vote counts of a group's label maps on one grid
-struct frog_labels {
-    int device = 0;
-    frog_volume grid;
+struct frog_labels : frog_group {
     uint32_t n_images = 0, added = 0, max_labels = 0;
     bool finished = false;
-    size_t total = 0;
     LabelMap map{};                                 // device pointers into the five buffers below
     frog::DevBuf<long long> d_keys, d_values;
     frog::DevBuf<uint32_t> d_index, d_state;
     std::vector<long long> known;                   // dense index -> value: the labels that have a plane
     std::deque<frog::DevBuf<uint16_t>> planes;      // one per known label; growth never copies counts
     frog::DevBuf<uint16_t *> d_planes;              // dense index -> plane
-    frog::DevBuf<unsigned char> d_src, d_stage;     // the current source / its resliced labels, grown on demand
     // after finish: the table in ascending order of the values (labels without a vote dropped)
     std::vector<long long> values;
     std::vector<uint32_t> dense;                    // table position -> dense index
@@ -913,9 +910,11 @@ int select_device(int device)
     return FROG_OK;
 }
 
-// f(S()) with S the C type of a FROG_V_* value
+bool integer_voxel_type(int dtype) { return dtype >= FROG_V_U8 && dtype <= FROG_V_I32; }
+
+// f(S()) with S the C type of an integer FROG_V_* value, which the caller has checked with integer_voxel_type
 template <class F>
-int with_voxel_type(int dtype, F f)
+int with_integer_voxel_type(int dtype, F f)
 {
     switch (dtype) {
     case FROG_V_U8: return f(uint8_t());
@@ -923,12 +922,23 @@ int with_voxel_type(int dtype, F f)
     case FROG_V_U16: return f(uint16_t());
     case FROG_V_I16: return f(int16_t());
     case FROG_V_U32: return f(uint32_t());
-    case FROG_V_I32: return f(int32_t());
+    default: return f(int32_t());
+    }
+}
+
+// f(S()) with S the C type of a FROG_V_* value
+template <class F>
+int with_voxel_type(int dtype, F f)
+{
+    if (integer_voxel_type(dtype)) return with_integer_voxel_type(dtype, f);
+    switch (dtype) {
     case FROG_V_F32: return f(float());
     case FROG_V_F64: return f(double());
     default: return fail(FROG_E_INVALID, "unknown scalar type");
     }
 }
+
+size_t voxel_count(const frog_volume *v) { return (size_t)v->dims[0] * v->dims[1] * v->dims[2]; }
 
 // Every launch in this file goes through chunked_launch: one work-item per element of [0, total), 256 per block, at most
 // 2^31 work-items per launch.  A dispatch packet's grid is 32-bit WORK-ITEMS per dimension; a larger 1-D launch returns no
@@ -1016,7 +1026,7 @@ ResliceGrid reslice_grid(const frog_volume *src, const frog_volume *out, int int
 template <class S>
 int reslice_typed(frog_chain *c, const frog_volume *src, frog_volume *out, int interpolation, double background)
 {
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2], n_out = (size_t)out->dims[0] * out->dims[1] * out->dims[2];
+    const size_t n_src = voxel_count(src), n_out = voxel_count(out);
     frog::DevBuf<S> d_src, d_out;
     KCHECK(d_src.alloc(n_src));
     KCHECK(d_out.alloc(n_out));
@@ -1032,32 +1042,105 @@ int reslice_typed(frog_chain *c, const frog_volume *src, frog_volume *out, int i
     return FROG_OK;
 }
 
-template <class S>
-int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+// The geometry of a mask for the kernels: zeros without one.
+MaskGrid mask_grid(const frog_volume *mask)
 {
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    const float n = (float)a->n_images;
-    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
-    if (c && resliced) KCHECK(a->d_out.alloc(a->total * sizeof(S)));
-    const S *d_src = (const S *)a->d_src.p;
-    S *d_out = (S *)a->d_out.p;
-    hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const ResliceGrid g = reslice_grid(src, &a->grid, interpolation, background);
-        e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-            if (c)
-                reslice_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, n,
-                                                                       a->d_avg.p, a->d_sq.p, resliced ? d_out : nullptr);
-            else
-                identity_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_src, a->total, n, a->d_avg.p, a->d_sq.p);
-        });
+    MaskGrid mg{};
+    if (mask) {
+        mg.sx = (int)mask->dims[0]; mg.sy = (int)mask->dims[1]; mg.sz = (int)mask->dims[2];
+        for (int k = 0; k < 3; k++) { mg.so[k] = mask->origin[k]; mg.ss[k] = mask->spacing[k]; }
     }
+    return mg;
+}
+
+// ---- what the adds of frog_average, frog_cover (and its score) and frog_labels share -----------------------------------------
+
+// A volume whose voxels a chain's positions can be turned into: dimensions an int holds, spacings that divide.
+bool chain_samples(const frog_volume *v)
+{
+    for (int k = 0; k < 3; k++)
+        if (v->dims[k] > 0x7FFFFFFFu || !(v->spacing[k] != 0.0)) return false;
+    return true;
+}
+
+bool grid_sized(const frog_group *a, const frog_volume *v)
+{
+    return v->dims[0] == a->grid.dims[0] && v->dims[1] == a->grid.dims[1] && v->dims[2] == a->grid.dims[2];
+}
+
+// What every add, and the score, refuses alike, in this order: a chain on another device than the accumulator's; an empty
+// source; with a chain a source it cannot sample, without one a source that is not grid-sized; a resliced volume (null: none
+// asked for, and the score has none) that is not grid-sized; one without voxels or of another type than the source's.
+// `where`, the entry point, goes in front of the messages that name it.
+int add_inputs(const char *where, const frog_group *a, const frog_chain *c, const frog_volume *src, const frog_volume *resliced)
+{
+    const std::string w = std::string(where) + ": ";
+    if (c && c->device != a->device) return fail(FROG_E_INVALID, w + "chain and accumulator on different devices");
+    if (!voxel_count(src)) return fail(FROG_E_INVALID, "empty volume");
+    if (c && !chain_samples(src)) return fail(FROG_E_INVALID, "bad source geometry");
+    if (!c && !grid_sized(a, src)) return fail(FROG_E_INVALID, w + "volume dimensions differ from the grid's");
+    if (resliced && !grid_sized(a, resliced)) return fail(FROG_E_INVALID, w + "resliced volume is not grid-sized");
+    if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, w + "resliced volume must have the source's type");
+    return FROG_OK;
+}
+
+// The staging step of an add: a->d_src grown and filled with the source, a->d_out grown to a grid-sized volume of S where
+// `want_out` says the kernel stores the resliced volume; *g receives the geometry the kernels take.
+template <class S>
+int stage_source(const char *where, frog_group *a, const frog_volume *src, bool want_out, int interpolation, double background, ResliceGrid *g)
+{
+    const size_t n_src = voxel_count(src);
+    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
+    if (want_out) KCHECK(a->d_out.alloc(a->total * sizeof(S)));
+    const hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(where, e);
+    *g = reslice_grid(src, &a->grid, interpolation, background);
+    return FROG_OK;
+}
+
+// The return step of an add, after launches that ended with `e`: the resliced volume where one is asked for (what the chain
+// kernel stored in a->d_out; without a chain the source itself), then the stream drained.
+template <class S>
+int return_resliced(const char *where, frog_group *a, const frog_chain *c, const frog_volume *src, frog_volume *resliced, hipError_t e)
+{
     if (e == hipSuccess && resliced) {
-        if (c) e = hipMemcpy(resliced->data, d_out, a->total * sizeof(S), hipMemcpyDeviceToHost);
+        if (c) e = hipMemcpy(resliced->data, a->d_out.p, a->total * sizeof(S), hipMemcpyDeviceToHost);
         else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
     }
     if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return hip_fail("frog_average_add", e);
+    if (e != hipSuccess) return hip_fail(where, e);
+    return FROG_OK;
+}
+
+template <class S>
+int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+{
+    ResliceGrid g;
+    if (int rc = stage_source<S>("frog_average_add", a, src, c && resliced, interpolation, background, &g)) return rc;
+    const float n = (float)a->n_images;
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = (S *)a->d_out.p;
+    const hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            reslice_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, n,
+                                                                   a->d_avg.p, a->d_sq.p, resliced ? d_out : nullptr);
+        else
+            identity_accumulate_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_src, a->total, n, a->d_avg.p, a->d_sq.p);
+    });
+    return return_resliced<S>("frog_average_add", a, c, src, resliced, e);
+}
+
+// cover's part of the staging step: the mask of an add or a score, which cover_mask left as bytes in a->h_mask, on the
+// device; a null pointer without one
+int cover_stage_mask(const char *where, frog_cover *a, const frog_volume *mask, const uint8_t **d_mask)
+{
+    *d_mask = nullptr;
+    if (!mask) return FROG_OK;
+    const size_t n_mask = voxel_count(mask);
+    KCHECK(a->d_mask.alloc(n_mask));
+    const hipError_t e = hipMemcpy(a->d_mask.p, a->h_mask.data(), n_mask, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(where, e);
+    *d_mask = a->d_mask.p;
     return FROG_OK;
 }
 
@@ -1065,66 +1148,41 @@ template <class S>
 int cover_add_typed(frog_cover *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background,
                     frog_volume *resliced)
 {
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    const size_t n_mask = mask ? (size_t)mask->dims[0] * mask->dims[1] * mask->dims[2] : 0;
-    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
-    if (mask) KCHECK(a->d_mask.alloc(n_mask));
-    if (c && resliced) KCHECK(a->d_out.alloc(a->total * sizeof(S)));
+    ResliceGrid g;
+    const uint8_t *d_mask;
+    if (int rc = stage_source<S>("frog_cover_add", a, src, c && resliced, interpolation, background, &g)) return rc;
+    if (int rc = cover_stage_mask("frog_cover_add", a, mask, &d_mask)) return rc;
+    const MaskGrid mg = mask_grid(mask);
     const S *d_src = (const S *)a->d_src.p;
-    const uint8_t *d_mask = mask ? a->d_mask.p : nullptr;
     S *d_out = (S *)a->d_out.p;
-    hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
-    if (e == hipSuccess && mask) e = hipMemcpy(a->d_mask.p, a->h_mask.data(), n_mask, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const ResliceGrid g = reslice_grid(src, &a->grid, interpolation, background);
-        MaskGrid mg{};
-        if (mask) {
-            mg.sx = (int)mask->dims[0]; mg.sy = (int)mask->dims[1]; mg.sz = (int)mask->dims[2];
-            for (int k = 0; k < 3; k++) { mg.so[k] = mask->origin[k]; mg.ss[k] = mask->spacing[k]; }
-        }
-        e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-            if (c)
-                cover_reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg,
-                                                                  a->d_mean.p, a->d_m2.p, a->d_count.p, resliced ? d_out : nullptr);
-            else
-                cover_identity_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_src, d_mask, a->total, a->d_mean.p, a->d_m2.p, a->d_count.p);
-        });
-    }
-    if (e == hipSuccess && resliced) {
-        if (c) e = hipMemcpy(resliced->data, d_out, a->total * sizeof(S), hipMemcpyDeviceToHost);
-        else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return hip_fail("frog_cover_add", e);
-    return FROG_OK;
+    const hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            cover_reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg,
+                                                              a->d_mean.p, a->d_m2.p, a->d_count.p, resliced ? d_out : nullptr);
+        else
+            cover_identity_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_src, d_mask, a->total, a->d_mean.p, a->d_m2.p, a->d_count.p);
+    });
+    return return_resliced<S>("frog_cover_add", a, c, src, resliced, e);
 }
 
 template <class S>
 int cover_score_typed(frog_cover *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background,
                       const ScoreParams &sp, frog_score_sums *sums, uint64_t *histogram)
 {
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    const size_t n_mask = mask ? (size_t)mask->dims[0] * mask->dims[1] * mask->dims[2] : 0;
     const size_t tiles = (a->total + SCORE_TILE - 1) / SCORE_TILE, cells = (size_t)sp.bins * sp.bins;
     frog::DevBuf<ScorePartial> d_partials;
     frog::DevBuf<unsigned long long> d_hist;
-    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
-    if (mask) KCHECK(a->d_mask.alloc(n_mask));
     KCHECK(d_partials.alloc(tiles));
     if (cells) KCHECK(d_hist.alloc(cells));
-    const S *d_src = (const S *)a->d_src.p;
-    const uint8_t *d_mask = mask ? a->d_mask.p : nullptr;
     std::vector<ScorePartial> partials(tiles);
-    hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
-    if (e == hipSuccess && mask) e = hipMemcpy(a->d_mask.p, a->h_mask.data(), n_mask, hipMemcpyHostToDevice);
-    if (e == hipSuccess && cells) e = hipMemset(d_hist.p, 0, cells * sizeof(unsigned long long));
+    ResliceGrid g;
+    const uint8_t *d_mask;
+    if (int rc = stage_source<S>("frog_cover_score", a, src, false, interpolation, background, &g)) return rc;
+    if (int rc = cover_stage_mask("frog_cover_score", a, mask, &d_mask)) return rc;
+    const MaskGrid mg = mask_grid(mask);
+    const S *d_src = (const S *)a->d_src.p;
+    hipError_t e = cells ? hipMemset(d_hist.p, 0, cells * sizeof(unsigned long long)) : hipSuccess;
     if (e == hipSuccess) {
-        const ResliceGrid g = reslice_grid(src, &a->grid, interpolation, background);
-        MaskGrid mg{};
-        if (mask) {
-            mg.sx = (int)mask->dims[0]; mg.sy = (int)mask->dims[1]; mg.sz = (int)mask->dims[2];
-            for (int k = 0; k < 3; k++) { mg.so[k] = mask->origin[k]; mg.ss[k] = mask->spacing[k]; }
-        }
         const size_t lds = cells * sizeof(uint32_t);
         // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
         e = chunked_launch(tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
@@ -1152,44 +1210,30 @@ int cover_score_typed(frog_cover *a, frog_chain *c, const frog_volume *src, cons
     return FROG_OK;
 }
 
-// h_mask = (value != 0) of an integer mask volume
-template <class M>
-void cover_mask_bytes(frog_cover *a, const frog_volume *mask)
-{
-    const size_t n = (size_t)mask->dims[0] * mask->dims[1] * mask->dims[2];
-    const M *v = (const M *)mask->data;
-    a->h_mask.resize(n);
-    for (size_t i = 0; i < n; i++) a->h_mask[i] = v[i] != 0;
-}
-
-// the mask of an add or a score as bytes in a->h_mask
+// the mask of an add or a score as bytes, value != 0, in a->h_mask
 void cover_mask(frog_cover *a, const frog_volume *mask)
 {
-    switch (mask->dtype) {
-    case FROG_V_U8: cover_mask_bytes<uint8_t>(a, mask); break;
-    case FROG_V_I8: cover_mask_bytes<int8_t>(a, mask); break;
-    case FROG_V_U16: cover_mask_bytes<uint16_t>(a, mask); break;
-    case FROG_V_I16: cover_mask_bytes<int16_t>(a, mask); break;
-    case FROG_V_U32: cover_mask_bytes<uint32_t>(a, mask); break;
-    default: cover_mask_bytes<int32_t>(a, mask); break;
-    }
+    with_integer_voxel_type(mask->dtype, [&](auto m) {
+        const size_t n = voxel_count(mask);
+        const decltype(m) *v = (const decltype(m) *)mask->data;
+        a->h_mask.resize(n);
+        for (size_t i = 0; i < n; i++) a->h_mask[i] = v[i] != 0;
+        return FROG_OK;
+    });
 }
 
-// what frog_cover_add and frog_cover_score refuse alike: the chain's device, the mask's type, the geometry
-int cover_inputs(const frog_cover *a, const frog_chain *c, const frog_volume *src, const frog_volume *mask, const char *where)
+// what frog_cover_add and frog_cover_score refuse alike: add_inputs, then what concerns the mask
+int cover_inputs(const char *where, const frog_cover *a, const frog_chain *c, const frog_volume *src, const frog_volume *mask,
+                 const frog_volume *resliced)
 {
+    if (int rc = add_inputs(where, a, c, src, resliced)) return rc;
+    if (!mask) return FROG_OK;
     const std::string w = std::string(where) + ": ";
-    if (c && c->device != a->device) return fail(FROG_E_INVALID, w + "chain and accumulator on different devices");
-    if (mask && !mask->data) return fail(FROG_E_INVALID, w + "a mask without voxels");
-    if (mask && (mask->dtype < FROG_V_U8 || mask->dtype > FROG_V_I32)) return fail(FROG_E_INVALID, w + "a mask has an integer type");
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    if (!n_src || (mask && !((size_t)mask->dims[0] * mask->dims[1] * mask->dims[2]))) return fail(FROG_E_INVALID, "empty volume");
-    for (int k = 0; k < 3; k++) {
-        if (c && (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad source geometry");
-        if (c && mask && (mask->dims[k] > 0x7FFFFFFFu || !(mask->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad mask geometry");
-        if (!c && src->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, w + "volume dimensions differ from the grid's");
-        if (!c && mask && mask->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, w + "mask dimensions differ from the grid's");
-    }
+    if (!mask->data) return fail(FROG_E_INVALID, w + "a mask without voxels");
+    if (!integer_voxel_type(mask->dtype)) return fail(FROG_E_INVALID, w + "a mask has an integer type");
+    if (!voxel_count(mask)) return fail(FROG_E_INVALID, "empty volume");
+    if (c && !chain_samples(mask)) return fail(FROG_E_INVALID, "bad mask geometry");
+    if (!c && !grid_sized(a, mask)) return fail(FROG_E_INVALID, w + "mask dimensions differ from the grid's");
     return FROG_OK;
 }
 
@@ -1215,20 +1259,16 @@ hipError_t labels_reset_map(frog_labels *a)
 template <class S>
 int labels_add_typed(frog_labels *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
 {
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
+    ResliceGrid g;
+    if (int rc = stage_source<S>("frog_labels_add", a, src, c != nullptr, 0, background, &g)) return rc;
     const size_t n_known = a->known.size();
-    KCHECK(a->d_src.alloc(n_src * sizeof(S)));
-    if (c) KCHECK(a->d_stage.alloc(a->total * sizeof(S)));
     const S *d_src = (const S *)a->d_src.p;
-    S *d_stage = (S *)a->d_stage.p;
-    const S *d_labels = c ? d_stage : d_src;
+    S *d_out = (S *)a->d_out.p;                     // with a chain the votes are read from the resliced labels
+    const S *d_labels = c ? d_out : d_src;
     uint32_t state[2] = { 0, 0 };
-    hipError_t e = hipMemcpy(a->d_src.p, src->data, n_src * sizeof(S), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail("frog_labels_add", e);
-    const ResliceGrid g = reslice_grid(src, &a->grid, 0, background);
-    e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
         if (c)
-            labels_collect_kernel<S, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->total, d_stage, a->map);
+            labels_collect_kernel<S, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->total, d_out, a->map);
         else
             labels_collect_kernel<S, false><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, a->total, nullptr, a->map);
     });
@@ -1260,13 +1300,7 @@ int labels_add_typed(frog_labels *a, frog_chain *c, const frog_volume *src, doub
     e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
         labels_vote_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_labels, a->total, a->map, a->d_planes.p, (uint32_t)n_now);
     });
-    if (e == hipSuccess && resliced) {
-        if (c) e = hipMemcpy(resliced->data, d_stage, a->total * sizeof(S), hipMemcpyDeviceToHost);
-        else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return hip_fail("frog_labels_add", e);
-    return FROG_OK;
+    return return_resliced<S>("frog_labels_add", a, c, src, resliced, e);
 }
 
 // every value of the table is a T
@@ -1294,6 +1328,40 @@ int labels_fused_typed(frog_labels *a, frog_volume *label, float *agreement)
     if (e == hipSuccess && agreement) e = hipMemcpy(agreement, d_agreement.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail("frog_labels_fused", e);
     return FROG_OK;
+}
+
+// The opening of every accumulator's create: what it refuses without asking for a device, and the grid's voxels.  The
+// accumulator's own argument checks follow, then group_new.
+int group_arguments(const char *where, const frog_volume *grid, const void *out, size_t *total)
+{
+    if (!grid || !out) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    *total = voxel_count(grid);
+    if (!*total) return fail(FROG_E_INVALID, "empty grid");
+    // one thread per voxel, 256 per block: a grid above 2^31 voxels is refused here rather than launched (DESIGN 2c)
+    if (*total > ((size_t)1 << 31)) return fail(FROG_E_INVALID, "grid above 2^31 voxels");
+    return FROG_OK;
+}
+
+// an accumulator A on `device`, made current, that holds the grid and nothing else yet
+template <class A>
+int group_new(const frog_volume *grid, size_t total, int device, std::unique_ptr<A> &a)
+{
+    if (int rc = select_device(device)) return rc;
+    a.reset(new (std::nothrow) A);
+    if (!a) return fail(FROG_E_NOMEM, "out of host memory");
+    a->device = device;
+    a->grid = *grid;
+    a->grid.data = nullptr;
+    a->total = total;
+    return FROG_OK;
+}
+
+template <class A>
+void group_destroy(A *a)
+{
+    if (!a) return;
+    (void)hipSetDevice(a->device);
+    delete a;
 }
 
 } // namespace
@@ -1454,29 +1522,20 @@ int frog_chain_reslice(frog_chain *c, const frog_volume *src, frog_volume *out, 
 {
     if (!c || !src || !out || !src->data || !out->data) return fail(FROG_E_INVALID, "bad arguments to frog_chain_reslice");
     if (out->dtype != src->dtype || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "output and source scalar types must match");
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2], n_out = (size_t)out->dims[0] * out->dims[1] * out->dims[2];
-    if (!n_src || !n_out) return fail(FROG_E_INVALID, "empty volume");
-    for (int k = 0; k < 3; k++)
-        if (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0)) return fail(FROG_E_INVALID, "bad source geometry");
+    if (!voxel_count(src) || !voxel_count(out)) return fail(FROG_E_INVALID, "empty volume");
+    if (!chain_samples(src)) return fail(FROG_E_INVALID, "bad source geometry");
     KCHECK(hipSetDevice(c->device));
     return with_voxel_type(src->dtype, [&](auto s) { return reslice_typed<decltype(s)>(c, src, out, interpolation, background); });
 }
 
 int frog_average_create(const frog_volume *grid, uint32_t n_images, int device, frog_average **out)
 {
-    if (!grid || !out || !n_images) return fail(FROG_E_INVALID, "bad arguments to frog_average_create");
-    const size_t total = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
-    if (!total) return fail(FROG_E_INVALID, "empty grid");
-    // one thread per voxel, 256 per block: a grid above 2^31 voxels is refused here rather than launched (DESIGN 2c)
-    if (total > ((size_t)1 << 31)) return fail(FROG_E_INVALID, "grid above 2^31 voxels");
-    if (int rc = select_device(device)) return rc;
-    std::unique_ptr<frog_average> a(new (std::nothrow) frog_average);
-    if (!a) return fail(FROG_E_NOMEM, "out of host memory");
-    a->device = device;
-    a->grid = *grid;
-    a->grid.data = nullptr;
+    size_t total;
+    if (int rc = group_arguments("frog_average_create", grid, out, &total)) return rc;
+    if (!n_images) return fail(FROG_E_INVALID, "bad arguments to frog_average_create");
+    std::unique_ptr<frog_average> a;
+    if (int rc = group_new(grid, total, device, a)) return rc;
     a->n_images = n_images;
-    a->total = total;
     KCHECK(a->d_avg.alloc(total));
     KCHECK(a->d_sq.alloc(total));
     // both accumulators start at zero (the reference never clears its stdev image: AverageVolumes.cxx:31-43)
@@ -1490,15 +1549,7 @@ int frog_average_add(frog_average *a, frog_chain *c, const frog_volume *src, int
 {
     if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_average_add");
     if (a->finished || a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_average_add: more volumes than n_images");
-    if (c && c->device != a->device) return fail(FROG_E_INVALID, "frog_average_add: chain and accumulator on different devices");
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    if (!n_src) return fail(FROG_E_INVALID, "empty volume");
-    for (int k = 0; k < 3; k++) {
-        if (c && (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad source geometry");
-        if (!c && src->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_average_add: volume dimensions differ from the grid's");
-        if (resliced && resliced->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_average_add: resliced volume is not grid-sized");
-    }
-    if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, "frog_average_add: resliced volume must have the source's type");
+    if (int rc = add_inputs("frog_average_add", a, c, src, resliced)) return rc;
     KCHECK(hipSetDevice(a->device));
     const int rc = with_voxel_type(src->dtype, [&](auto s) { return average_add_typed<decltype(s)>(a, c, src, interpolation, background, resliced); });
     if (rc == FROG_OK) a->added++;
@@ -1523,26 +1574,14 @@ int frog_average_finish(frog_average *a, float *mean, float *stdev)
     return FROG_OK;
 }
 
-void frog_average_destroy(frog_average *a)
-{
-    if (!a) return;
-    (void)hipSetDevice(a->device);
-    delete a;
-}
+void frog_average_destroy(frog_average *a) { group_destroy(a); }
 
 int frog_cover_create(const frog_volume *grid, int device, frog_cover **out)
 {
-    if (!grid || !out) return fail(FROG_E_INVALID, "bad arguments to frog_cover_create");
-    const size_t total = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
-    if (!total) return fail(FROG_E_INVALID, "empty grid");
-    if (total > ((size_t)1 << 31)) return fail(FROG_E_INVALID, "grid above 2^31 voxels");
-    if (int rc = select_device(device)) return rc;
-    std::unique_ptr<frog_cover> a(new (std::nothrow) frog_cover);
-    if (!a) return fail(FROG_E_NOMEM, "out of host memory");
-    a->device = device;
-    a->grid = *grid;
-    a->grid.data = nullptr;
-    a->total = total;
+    size_t total;
+    if (int rc = group_arguments("frog_cover_create", grid, out, &total)) return rc;
+    std::unique_ptr<frog_cover> a;
+    if (int rc = group_new(grid, total, device, a)) return rc;
     KCHECK(a->d_mean.alloc(total));
     KCHECK(a->d_m2.alloc(total));
     KCHECK(a->d_count.alloc(total));
@@ -1558,10 +1597,7 @@ int frog_cover_add(frog_cover *a, frog_chain *c, const frog_volume *src, const f
 {
     if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_cover_add");
     if (a->added >= 65535) return fail(FROG_E_INVALID, "frog_cover_add: more than 65535 volumes (16-bit counts)");
-    if (int rc = cover_inputs(a, c, src, mask, "frog_cover_add")) return rc;
-    for (int k = 0; k < 3; k++)
-        if (resliced && resliced->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_cover_add: resliced volume is not grid-sized");
-    if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, "frog_cover_add: resliced volume must have the source's type");
+    if (int rc = cover_inputs("frog_cover_add", a, c, src, mask, resliced)) return rc;
     if (mask) cover_mask(a, mask);
     KCHECK(hipSetDevice(a->device));
     const int rc = with_voxel_type(src->dtype, [&](auto s) { return cover_add_typed<decltype(s)>(a, c, src, mask, interpolation, background, resliced); });
@@ -1573,7 +1609,7 @@ int frog_cover_score(frog_cover *a, frog_chain *c, const frog_volume *src, const
                      uint32_t min_count, int leave_one_out, uint32_t bins, float lo, float hi, frog_score_sums *sums, uint64_t *histogram)
 {
     if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype) || !sums) return fail(FROG_E_INVALID, "bad arguments to frog_cover_score");
-    if (int rc = cover_inputs(a, c, src, mask, "frog_cover_score")) return rc;
+    if (int rc = cover_inputs("frog_cover_score", a, c, src, mask, nullptr)) return rc;
     if (!a->added) return fail(FROG_E_INVALID, "frog_cover_score: before the first frog_cover_add");
     if (!min_count) return fail(FROG_E_INVALID, "frog_cover_score: min_count must be at least 1");
     ScoreParams sp{};
@@ -1615,30 +1651,18 @@ int frog_cover_finish(frog_cover *a, uint32_t min_count, float fill, float *mean
     return FROG_OK;
 }
 
-void frog_cover_destroy(frog_cover *a)
-{
-    if (!a) return;
-    (void)hipSetDevice(a->device);
-    delete a;
-}
+void frog_cover_destroy(frog_cover *a) { group_destroy(a); }
 
 int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_labels **out)
 {
-    if (!grid || !out) return fail(FROG_E_INVALID, "bad arguments to frog_labels_create");
-    const size_t total = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
-    if (!total) return fail(FROG_E_INVALID, "empty grid");
-    if (total > ((size_t)1 << 31)) return fail(FROG_E_INVALID, "grid above 2^31 voxels");
+    size_t total;
+    if (int rc = group_arguments("frog_labels_create", grid, out, &total)) return rc;
     if (!n_images || n_images > 65535) return fail(FROG_E_INVALID, "frog_labels_create: 1 to 65535 images (16-bit vote counts)");
     if (max_labels > 65536) return fail(FROG_E_INVALID, "frog_labels_create: max_labels above 65536");
-    if (int rc = select_device(device)) return rc;
-    std::unique_ptr<frog_labels> a(new (std::nothrow) frog_labels);
-    if (!a) return fail(FROG_E_NOMEM, "out of host memory");
-    a->device = device;
-    a->grid = *grid;
-    a->grid.data = nullptr;
+    std::unique_ptr<frog_labels> a;
+    if (int rc = group_new(grid, total, device, a)) return rc;
     a->n_images = n_images;
     a->max_labels = max_labels ? max_labels : 1024;
-    a->total = total;
     int bits = 4;                                       // at least 16 slots, at least two per label
     while (((size_t)1 << bits) < 2 * (size_t)a->max_labels) bits++;
     const size_t slots = (size_t)1 << bits;
@@ -1656,28 +1680,12 @@ int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_
 int frog_labels_add(frog_labels *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
 {
     if (!a || !src || !src->data) return fail(FROG_E_INVALID, "bad arguments to frog_labels_add");
-    if (src->dtype < FROG_V_U8 || src->dtype > FROG_V_I32) return fail(FROG_E_INVALID, "frog_labels_add: a label volume has an integer type");
+    if (!integer_voxel_type(src->dtype)) return fail(FROG_E_INVALID, "frog_labels_add: a label volume has an integer type");
     if (!std::isfinite(background)) return fail(FROG_E_INVALID, "frog_labels_add: background is not finite");
     if (a->finished || a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_labels_add: more volumes than n_images");
-    if (c && c->device != a->device) return fail(FROG_E_INVALID, "frog_labels_add: chain and accumulator on different devices");
-    const size_t n_src = (size_t)src->dims[0] * src->dims[1] * src->dims[2];
-    if (!n_src) return fail(FROG_E_INVALID, "empty volume");
-    for (int k = 0; k < 3; k++) {
-        if (c && (src->dims[k] > 0x7FFFFFFFu || !(src->spacing[k] != 0.0))) return fail(FROG_E_INVALID, "bad source geometry");
-        if (!c && src->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_labels_add: volume dimensions differ from the grid's");
-        if (resliced && resliced->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_labels_add: resliced volume is not grid-sized");
-    }
-    if (resliced && (!resliced->data || resliced->dtype != src->dtype)) return fail(FROG_E_INVALID, "frog_labels_add: resliced volume must have the source's type");
+    if (int rc = add_inputs("frog_labels_add", a, c, src, resliced)) return rc;
     KCHECK(hipSetDevice(a->device));
-    int rc = FROG_OK;
-    switch (src->dtype) {
-    case FROG_V_U8: rc = labels_add_typed<uint8_t>(a, c, src, background, resliced); break;
-    case FROG_V_I8: rc = labels_add_typed<int8_t>(a, c, src, background, resliced); break;
-    case FROG_V_U16: rc = labels_add_typed<uint16_t>(a, c, src, background, resliced); break;
-    case FROG_V_I16: rc = labels_add_typed<int16_t>(a, c, src, background, resliced); break;
-    case FROG_V_U32: rc = labels_add_typed<uint32_t>(a, c, src, background, resliced); break;
-    default: rc = labels_add_typed<int32_t>(a, c, src, background, resliced); break;
-    }
+    const int rc = with_integer_voxel_type(src->dtype, [&](auto s) { return labels_add_typed<decltype(s)>(a, c, src, background, resliced); });
     if (rc == FROG_OK) a->added++;
     return rc;
 }
@@ -1733,19 +1741,11 @@ int frog_labels_fused(frog_labels *a, frog_volume *label, float *agreement)
     if (!a || (!label && !agreement) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_labels_fused");
     if (!a->finished) return fail(FROG_E_INVALID, "frog_labels_fused: before frog_labels_finish");
     if (label) {
-        if (label->dtype < FROG_V_U8 || label->dtype > FROG_V_I32) return fail(FROG_E_INVALID, "frog_labels_fused: the fused map has an integer type");
-        for (int k = 0; k < 3; k++)
-            if (label->dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, "frog_labels_fused: the fused map is not grid-sized");
+        if (!integer_voxel_type(label->dtype)) return fail(FROG_E_INVALID, "frog_labels_fused: the fused map has an integer type");
+        if (!grid_sized(a, label)) return fail(FROG_E_INVALID, "frog_labels_fused: the fused map is not grid-sized");
     }
     KCHECK(hipSetDevice(a->device));
-    switch (label ? label->dtype : FROG_V_I32) {
-    case FROG_V_U8: return labels_fused_typed<uint8_t>(a, label, agreement);
-    case FROG_V_I8: return labels_fused_typed<int8_t>(a, label, agreement);
-    case FROG_V_U16: return labels_fused_typed<uint16_t>(a, label, agreement);
-    case FROG_V_I16: return labels_fused_typed<int16_t>(a, label, agreement);
-    case FROG_V_U32: return labels_fused_typed<uint32_t>(a, label, agreement);
-    default: return labels_fused_typed<int32_t>(a, label, agreement);
-    }
+    return with_integer_voxel_type(label ? label->dtype : FROG_V_I32, [&](auto t) { return labels_fused_typed<decltype(t)>(a, label, agreement); });
 }
 
 int frog_labels_probability(frog_labels *a, int64_t value, float *p)
@@ -1766,11 +1766,6 @@ int frog_labels_probability(frog_labels *a, int64_t value, float *p)
     return FROG_OK;
 }
 
-void frog_labels_destroy(frog_labels *a)
-{
-    if (!a) return;
-    (void)hipSetDevice(a->device);
-    delete a;
-}
+void frog_labels_destroy(frog_labels *a) { group_destroy(a); }
 
 }

@@ -25,15 +25,10 @@
 // nan.  -qb: bins per axis of the joint histogram behind mi and nmi (2..64, default 64).  -qr lo hi: its value range, by
 // default the smallest finite value of the mean over the voxels that minCount images cover and the float after the largest;
 // the range used is printed.  The average's files and the first pass are the same with and without -q 1.
-#include "tool_common.h"
+#include "group_tool.h"
 #include "volume_stream.h"
 
-#include <sys/stat.h>
-#include <cerrno>
-#include <zlib.h>
-
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -45,35 +40,6 @@
 #include <vector>
 
 namespace {
-
-// the header of a volume parses (NIfTI-1: sizeof_hdr; MetaImage: DimSize present), without inflating its data; `is_float`
-// (may be null) receives whether it declares a float type (NIfTI-1: datatype 16 or 64 at byte 70; MetaImage: ElementType)
-bool header_ok(const std::string &path, bool *is_float = nullptr)
-{
-    auto has_suffix = [&](const char *s) { const size_t n = std::strlen(s); return path.size() >= n && path.compare(path.size() - n, n, s) == 0; };
-    if (is_float) *is_float = false;
-    if (has_suffix(".mhd") || has_suffix(".mha")) {
-        uint32_t d[3]; double sp[3], o[3];
-        if (frog_volume_geometry(path.c_str(), d, sp, o) != FROG_OK) return false;
-        std::ifstream f(path);
-        for (std::string line; is_float && std::getline(f, line) && line.compare(0, 15, "ElementDataFile") != 0;)
-            if (line.compare(0, 11, "ElementType") == 0 && (line.find("MET_FLOAT") != std::string::npos || line.find("MET_DOUBLE") != std::string::npos))
-                *is_float = true;
-        return true;
-    }
-    if (!has_suffix(".nii") && !has_suffix(".nii.gz")) return false;
-    gzFile f = gzopen(path.c_str(), "rb");
-    if (!f) return false;
-    unsigned char h[72];
-    const bool read = gzread(f, h, sizeof h) == (int)sizeof h;
-    gzclose(f);
-    int32_t n = 0;
-    int16_t datatype = 0;
-    std::memcpy(&n, h, sizeof n);
-    std::memcpy(&datatype, h + 70, sizeof datatype);
-    if (is_float) *is_float = datatype == 16 || datatype == 64;
-    return read && n == 348;
-}
 
 // the lines of a list file (FROG.py -m's format: one path per line), without their line ends; blank lines are dropped
 bool read_list(const std::string &path, std::vector<std::string> &lines)
@@ -108,11 +74,7 @@ std::string csv_double(double v)
 
 int main(int argc, char *argv[])
 {
-    using clk = std::chrono::steady_clock;
-    const auto t_start = clk::now();
-    auto seconds = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
-    // reader threads may still be inflating: leave without running static destructors under them
-    auto die = [](const std::string &what) { std::cout << "Error : " << what << std::endl; std::_Exit(1); };
+    PhaseTimes times;
     std::vector<std::string> volumes;
     std::string transformsDir = "transforms", outDir = ".", maskList;
     int interpolation = 1, device = 0, writeTransformed = 0, coverage = 0, quality = 0;
@@ -121,12 +83,7 @@ int main(int argc, char *argv[])
     bool qualityOption = false, qualityRange = false;       // -qb or -qr was given; -qr was given
     bool coverageOption = false;                            // -ml, -mc or -f was given
     BackgroundLevel background;
-    auto is_flag = [](const char *a) {
-        for (const char *f : { "-td", "-o", "-i", "-b", "-wt", "-dev", "-c", "-ml", "-mc", "-f", "-q", "-qb", "-qr" }) if (std::strcmp(a, f) == 0) return true;
-        return false;
-    };
-    int a = 3;
-    for (; a < argc && !is_flag(argv[a]); a++) volumes.push_back(argv[a]);
+    int a = positional_arguments(argc, argv, 3, { "-td", "-o", "-i", "-b", "-wt", "-dev", "-c", "-ml", "-mc", "-f", "-q", "-qb", "-qr" }, volumes);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
         if (std::strcmp(key, "-td") == 0) transformsDir = value;
@@ -172,25 +129,15 @@ int main(int argc, char *argv[])
     // ---- everything is checked before the first output: the grid, every transform, every volume header
     frog_volume grid;
     if (frog_bbox_grid(argv[1], atof(argv[2]), &grid)) die(std::string("cannot read a bounding box from ") + argv[1] + " (or spacing " + argv[2] + " is not positive)");
-    ChainArguments transforms;                              // owns the files; every image has a chain of its own
-    std::vector<std::vector<frog_chain_link>> inverse(n);
-    for (size_t i = 0; i < n; i++) {
-        const std::string path = transformsDir + "/" + std::to_string(i) + ".json";
-        frog_transform_file *f = transforms.read(path.c_str());
-        if (!f) die("cannot read transform " + path);
-        const uint32_t nl = frog_transform_num_links(f);
-        inverse[i].resize(nl);
-        if (frog_chain_invert_links(frog_transform_links(f), nl, inverse[i].data())) die(path + ": " + frog_last_error());
-    }
-    for (const auto &v : volumes) if (!header_ok(v)) die("cannot read volume " + v);
+    ChainArguments transforms;
+    const auto inverse = inverse_transforms(transforms, transformsDir, n);
+    for (const auto &v : volumes) if (!peek_header(v).ok) die("cannot read volume " + v);
     for (const auto &m : masks) {
-        bool is_float = false;
-        if (!header_ok(m, &is_float)) die("cannot read mask " + m);
-        if (is_float) die(m + " is a float volume: masks have an integer type");
+        const VolumeHeader h = peek_header(m);
+        if (!h.ok) die("cannot read mask " + m);
+        if (h.is_float) die(m + " is a float volume: masks have an integer type");
     }
-    if (mkdir(outDir.c_str(), 0755) != 0 && errno != EEXIST) die("cannot create " + outDir);
-    std::cout << n << " images, grid " << grid.dims[0] << " x " << grid.dims[1] << " x " << grid.dims[2] << " (spacing " << grid.spacing[0]
-              << ", origin " << grid.origin[0] << " " << grid.origin[1] << " " << grid.origin[2] << ")" << std::endl;
+    begin_output(outDir, n, "images", grid);
 
     int threads;
     size_t window;
@@ -199,42 +146,33 @@ int main(int argc, char *argv[])
     frog::VolumeStream stream(volumes, threads, window);     // reading starts now, beside the device set-up below
     std::unique_ptr<frog::VolumeStream> maskStream(masks.empty() ? nullptr : new frog::VolumeStream(masks, threads, window));
 
-    double device_s = 0, write_s = 0, waited_s = 0;
     auto t0 = clk::now();
-    std::vector<frog_chain *> chains(n, nullptr);
-    for (size_t i = 0; i < n; i++)
-        if (frog_chain_create(inverse[i].data(), (uint32_t)inverse[i].size(), device, &chains[i])) die("transform " + std::to_string(i) + ": " + frog_last_error());
+    std::vector<frog_chain *> chains = create_chains(inverse, device);
     frog_average *avg = nullptr;
     frog_cover *cover = nullptr;
     if (coverage == 1 ? frog_cover_create(&grid, device, &cover) : frog_average_create(&grid, (uint32_t)n, device, &avg)) die(frog_last_error());
-    const double setup_s = seconds(t0);
+    times.setup_s = seconds(t0);
 
     const size_t total = (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2];
-    std::vector<unsigned char> resliced_data;
+    ReslicedVolume resliced;
     for (size_t i = 0; i < n; i++) {
         double waited = 0;
         frog::VolumeStream::Item &it = stream.get(i, &waited);
-        waited_s += waited;
+        times.waited_s += waited;
         if (!it.file) die("cannot read volume " + volumes[i]);
         const frog_volume *mask = nullptr;
         if (maskStream) {
             frog::VolumeStream::Item &m = maskStream->get(i, &waited);
-            waited_s += waited;
+            times.waited_s += waited;
             if (!m.file) die("cannot read mask " + masks[i]);
             mask = &m.view;
         }
-        frog_volume resliced = grid, *out = nullptr;
-        if (writeTransformed) {
-            resliced.dtype = it.view.dtype;
-            resliced_data.resize(total * frog_volume_voxel_bytes(it.view.dtype));
-            resliced.data = resliced_data.data();
-            out = &resliced;
-        }
+        frog_volume *out = resliced.stage(writeTransformed, grid, it.view.dtype);
         t0 = clk::now();
         if (cover ? frog_cover_add(cover, chains[i], &it.view, mask, interpolation, background.of(it.lo), out)
                   : frog_average_add(avg, chains[i], &it.view, interpolation, background.of(it.lo), out))
             die(volumes[i] + ": " + frog_last_error());
-        device_s += seconds(t0);
+        times.device_s += seconds(t0);
         stream.release(i);
         if (maskStream) maskStream->release(i);
         if (quality != 1) {                                 // the second pass evaluates the chain again
@@ -243,9 +181,8 @@ int main(int argc, char *argv[])
         }
         if (out) {
             t0 = clk::now();
-            const std::string name = outDir + "/transformed" + std::to_string(i) + ".nii.gz";
-            if (frog_volume_write(name.c_str(), out)) die("cannot write " + name);
-            write_s += seconds(t0);
+            resliced.write(outDir, "transformed", i);
+            times.write_s += seconds(t0);
         }
     }
     std::vector<float> mean(total), stdev(total);
@@ -253,7 +190,7 @@ int main(int argc, char *argv[])
     t0 = clk::now();
     if (cover ? frog_cover_finish(cover, (uint32_t)minCount, fill, mean.data(), stdev.data(), count.data())
               : frog_average_finish(avg, mean.data(), stdev.data())) die(frog_last_error());
-    device_s += seconds(t0);
+    times.device_s += seconds(t0);
     frog_average_destroy(avg);
 
     t0 = clk::now();
@@ -269,7 +206,7 @@ int main(int argc, char *argv[])
         const std::string path = outDir + "/coverage.nii.gz";
         if (frog_volume_write(path.c_str(), &grid)) die("cannot write " + path);
     }
-    write_s += seconds(t0);
+    times.write_s += seconds(t0);
 
     // ---- -q 1: every image against the mean of the others, the files streamed once more in the same order
     double quality_s = 0;
@@ -333,13 +270,9 @@ int main(int argc, char *argv[])
         quality_s = seconds(t0);
     }
     frog_cover_destroy(cover);
-    char line[512];
-    std::snprintf(line, sizeof line,
-                  "read : %.3f s of %d host threads (device waited %.3f s)\ndevice : %.3f s (+ %.3f s set-up)\nwrite : %.3f s\ntotal : %.3f s",
-                  stream.read_seconds() + (maskStream ? maskStream->read_seconds() : 0.0),
-                  stream.threads() + (maskStream ? maskStream->threads() : 0), waited_s, device_s, setup_s, write_s, seconds(t_start));
-    std::cout << line << std::endl;
+    times.print(stream.read_seconds() + (maskStream ? maskStream->read_seconds() : 0.0), stream.threads() + (maskStream ? maskStream->threads() : 0));
     if (quality == 1) {
+        char line[64];
         std::snprintf(line, sizeof line, "quality : %.3f s", quality_s);
         std::cout << line << std::endl;
     }

@@ -6,7 +6,7 @@
 // rounds negative).  Deviations: sq starts at zero (upstream never clears it) and a file whose dimensions differ from the
 // first's is an error (exit 1, nothing written) where upstream reads past its buffer.  Files are read and inflated on host
 // threads ahead of the device (volume_stream.h).  New: -dev <n> as the last two arguments selects the HIP device.
-#include "tool_common.h"
+#include "group_tool.h"
 #include "volume_stream.h"
 
 #include <cstdlib>
@@ -24,8 +24,6 @@ int main(int argc, char *argv[])
         return 1;
     }
     std::vector<std::string> files(argv + 1, argv + n_args);
-    // reader threads may still be inflating: leave without running static destructors under them
-    auto die = [](const std::string &what) { std::cout << "Error : " << what << std::endl; std::_Exit(1); };
     static std::thread warm;                        // the HIP runtime comes up while the first file inflates
     warm = std::thread([device] { (void)frog_device_warm(device); });
     std::atexit([] { if (warm.joinable()) warm.join(); });

@@ -50,21 +50,24 @@ def _as_volume(item):
     return np.ascontiguousarray(a), tuple(float(v) for v in o), tuple(float(v) for v in s)
 
 
-class Average:
-    """frog_average (include/frog_chain.h): n_images volumes added one by one on `grid` = (dims(x, y, z), origin, spacing),
-    then the f32 mean and stdev of AverageVolumes.cxx."""
+class _Accumulator:
+    """What Average, CoverAverage and Labels share: the grid (`dims`, `_grid`), the handle `_h` that the library's
+    frog_<_NAME>_create gives and its frog_<_NAME>_destroy takes back, and the views an add hands to the library."""
 
-    def __init__(self, grid, n_images, device=0):
+    _NAME = None
+
+    def __init__(self, grid, *create_args):
         self._lib = _abi.hip_lib()
         dims, origin, spacing = grid
         self.dims = tuple(int(d) for d in dims)
         self._grid = _abi.volume_view(None, origin, spacing, self.dims)
         self._h = C.c_void_p()
-        _abi.check(self._lib.frog_average_create(C.byref(self._grid), int(n_images), int(device), C.byref(self._h)), "frog_average_create")
+        where = f"frog_{self._NAME}_create"
+        _abi.check(getattr(self._lib, where)(C.byref(self._grid), *create_args, C.byref(self._h)), where)
 
     def close(self):
         if self._h:
-            self._lib.frog_average_destroy(self._h)
+            getattr(self._lib, f"frog_{self._NAME}_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -73,18 +76,53 @@ class Average:
         except Exception:
             pass
 
+    def _views(self, volume, mask=None, resliced=False):
+        """(voxels, source, mask, view, out): the source's array; what the library takes as the source, as the mask and as
+        the resliced volume, the last a view of the new grid-sized array `out` of the source's type (None where there is no
+        mask, or no resliced volume is wanted).  Each reference keeps the array behind it alive."""
+        def ref(a, origin, spacing):
+            v = _abi.volume_view(a, origin, spacing)
+            v.voxels = a                                            # _as_volume may have made a contiguous copy
+            return C.byref(v)
+
+        a, o, s = _as_volume(volume)
+        out = np.empty(self.dims[::-1], a.dtype) if resliced else None
+        return (a, ref(a, o, s), None if mask is None else ref(*_as_volume(mask)),
+                ref(out, tuple(self._grid.origin), tuple(self._grid.spacing)) if resliced else None, out)
+
+
+def _group(volumes, chains, masks, grid):
+    """The arguments average(), cover_average(), group_quality() and fuse_labels() share, checked: the volumes as
+    (voxels, origin, spacing) and the grid, by default the first volume's."""
+    vols = [_as_volume(v) for v in volumes]
+    if not vols:
+        raise ValueError("no volumes")
+    if chains is not None and len(chains) != len(vols):
+        raise ValueError("one chain per volume expected")
+    if masks is not None and len(masks) != len(vols):
+        raise ValueError("one mask per volume expected")
+    if grid is None:
+        a, o, s = vols[0]
+        grid = (a.shape[::-1], o, s)
+    return vols, grid
+
+
+class Average(_Accumulator):
+    """frog_average (include/frog_chain.h): n_images volumes added one by one on `grid` = (dims(x, y, z), origin, spacing),
+    then the f32 mean and stdev of AverageVolumes.cxx."""
+
+    _NAME = "average"
+
+    def __init__(self, grid, n_images, device=0):
+        super().__init__(grid, int(n_images), int(device))
+
     def add(self, volume, chain=None, interpolation=1, background=0.0, resliced=False):
         """Adds `volume` ((voxels, origin, spacing) or an array already on the grid when chain is None); with a chain
         (frog_amd.chain.Chain, grid space -> volume space) it is resliced first as Chain.reslice does.  resliced=True
         returns that volume (source dtype, shape dims[::-1])."""
-        a, o, s = _as_volume(volume)
-        src = _abi.volume_view(a, o, s)
-        out, ov = None, None
-        if resliced:
-            out = np.empty(self.dims[::-1], a.dtype)
-            ov = _abi.volume_view(out, tuple(self._grid.origin), tuple(self._grid.spacing))
-        _abi.check(self._lib.frog_average_add(self._h, chain._h if chain is not None else None, C.byref(src), int(interpolation),
-                                              float(background), C.byref(ov) if ov is not None else None), "frog_average_add")
+        _, src, _, ov, out = self._views(volume, None, resliced)
+        _abi.check(self._lib.frog_average_add(self._h, chain._h if chain is not None else None, src, int(interpolation),
+                                              float(background), ov), "frog_average_add")
         return out
 
     def finish(self):
@@ -103,14 +141,7 @@ def average(volumes, chains=None, grid=None, interpolation=1, backgrounds=None, 
     `grid`: (dims(x, y, z), origin, spacing), default the first volume's; `backgrounds`: None (each volume's minimum, as
     VolumeTransform), a number or one per volume.  Returns float32 (mean, stdev), NaN where upstream's f32 variance
     rounds negative."""
-    vols = [_as_volume(v) for v in volumes]
-    if not vols:
-        raise ValueError("no volumes")
-    if chains is not None and len(chains) != len(vols):
-        raise ValueError("one chain per volume expected")
-    if grid is None:
-        a, o, s = vols[0]
-        grid = (a.shape[::-1], o, s)
+    vols, grid = _group(volumes, chains, None, grid)
     if backgrounds is None:
         backgrounds = [float(a.min()) for a, _, _ in vols]
     elif np.ndim(backgrounds) == 0:
@@ -124,29 +155,15 @@ def average(volumes, chains=None, grid=None, interpolation=1, backgrounds=None, 
         acc.close()
 
 
-class CoverAverage:
+class CoverAverage(_Accumulator):
     """frog_cover (include/frog_chain.h): volumes added one by one on `grid` = (dims(x, y, z), origin, spacing), each only
     where it covers the voxel (and its mask is non-zero); then the f32 mean and stdev over the covering images and their
     count."""
 
+    _NAME = "cover"
+
     def __init__(self, grid, device=0):
-        self._lib = _abi.hip_lib()
-        dims, origin, spacing = grid
-        self.dims = tuple(int(d) for d in dims)
-        self._grid = _abi.volume_view(None, origin, spacing, self.dims)
-        self._h = C.c_void_p()
-        _abi.check(self._lib.frog_cover_create(C.byref(self._grid), int(device), C.byref(self._h)), "frog_cover_create")
-
-    def close(self):
-        if self._h:
-            self._lib.frog_cover_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(grid, int(device))
 
     def add(self, volume, chain=None, mask=None, interpolation=1, background=0.0, resliced=False):
         """Adds `volume` ((voxels, origin, spacing) or an array already on the grid when chain is None) where it is valid:
@@ -154,19 +171,9 @@ class CoverAverage:
         Chain.reslice decides it, without one everywhere; and, with `mask` (an integer volume of its own geometry, given
         like `volume`), where the mask's nearest voxel is non-zero.  resliced=True returns the volume Chain.reslice would
         give with `background` (source dtype, shape dims[::-1])."""
-        a, o, s = _as_volume(volume)
-        src = _abi.volume_view(a, o, s)
-        mv = None
-        if mask is not None:
-            m, mo, ms = _as_volume(mask)
-            mv = _abi.volume_view(m, mo, ms)
-        out, ov = None, None
-        if resliced:
-            out = np.empty(self.dims[::-1], a.dtype)
-            ov = _abi.volume_view(out, tuple(self._grid.origin), tuple(self._grid.spacing))
-        _abi.check(self._lib.frog_cover_add(self._h, chain._h if chain is not None else None, C.byref(src),
-                                            C.byref(mv) if mv is not None else None, int(interpolation), float(background),
-                                            C.byref(ov) if ov is not None else None), "frog_cover_add")
+        _, src, mv, ov, out = self._views(volume, mask, resliced)
+        _abi.check(self._lib.frog_cover_add(self._h, chain._h if chain is not None else None, src, mv, int(interpolation),
+                                            float(background), ov), "frog_cover_add")
         return out
 
     def finish(self, min_count=1, fill=0.0):
@@ -189,12 +196,7 @@ class CoverAverage:
         of the bins x bins joint histogram (row = the image's bin), default quality_range(min_count).  Returns a dict: the
         sums n, n_nonfinite, sx, sy, sxx, syy, sxy, sad; covered_fraction = n / grid voxels; `histogram` (uint64, (bins,
         bins)) or None; and ncc, mean_abs_diff, rmse, mi, nmi from frog_score_metrics_from.  Leaves the accumulator as it is."""
-        a, o, s = _as_volume(volume)
-        src = _abi.volume_view(a, o, s)
-        mv = None
-        if mask is not None:
-            m, mo, ms = _as_volume(mask)
-            mv = _abi.volume_view(m, mo, ms)
+        a, src, mv, _, _ = self._views(volume, mask)
         if background is None:
             background = float(a.min())
         bins = int(bins)
@@ -204,10 +206,9 @@ class CoverAverage:
             hist = np.zeros((bins, bins), np.uint64)
         hist_p = hist.ctypes.data_as(C.POINTER(C.c_uint64)) if hist is not None else None
         sums = _abi.FrogScoreSums()
-        _abi.check(self._lib.frog_cover_score(self._h, chain._h if chain is not None else None, C.byref(src),
-                                              C.byref(mv) if mv is not None else None, int(interpolation), float(background),
-                                              int(min_count), int(bool(leave_one_out)), bins, float(lo), float(hi), C.byref(sums),
-                                              hist_p), "frog_cover_score")
+        _abi.check(self._lib.frog_cover_score(self._h, chain._h if chain is not None else None, src, mv, int(interpolation),
+                                              float(background), int(min_count), int(bool(leave_one_out)), bins, float(lo),
+                                              float(hi), C.byref(sums), hist_p), "frog_cover_score")
         metrics = _abi.FrogScoreMetrics()
         _abi.check(_abi.host_lib().frog_score_metrics_from(C.byref(sums), hist_p, bins, C.byref(metrics)), "frog_score_metrics_from")
         out = {name: getattr(sums, name) for name, _ in sums._fields_}
@@ -230,16 +231,7 @@ def cover_average(volumes, chains=None, masks=None, grid=None, interpolation=1, 
     """Voxel-wise mean, stdev and count over the images that cover each grid voxel (bin/AverageImage -c 1).  `volumes`,
     `chains` and `grid` as in average(); `masks`: None or one integer volume (or None) per image.  Returns
     (mean float32, stdev float32, count uint16)."""
-    vols = [_as_volume(v) for v in volumes]
-    if not vols:
-        raise ValueError("no volumes")
-    if chains is not None and len(chains) != len(vols):
-        raise ValueError("one chain per volume expected")
-    if masks is not None and len(masks) != len(vols):
-        raise ValueError("one mask per volume expected")
-    if grid is None:
-        a, o, s = vols[0]
-        grid = (a.shape[::-1], o, s)
+    vols, grid = _group(volumes, chains, masks, grid)
     acc = CoverAverage(grid, device)
     try:
         for k, v in enumerate(vols):
@@ -274,16 +266,7 @@ def group_quality(volumes, chains=None, masks=None, grid=None, interpolation=1, 
     leave_one_out).  Arguments as in cover_average(); the background of image k is its minimum.  Returns one dict per image,
     score()'s plus `image` (its index) and `ncc_robust_z` (robust_z of the group's ncc): a low ncc or nmi, and a strongly
     negative z, single out an image that does not match the rest."""
-    vols = [_as_volume(v) for v in volumes]
-    if not vols:
-        raise ValueError("no volumes")
-    if chains is not None and len(chains) != len(vols):
-        raise ValueError("one chain per volume expected")
-    if masks is not None and len(masks) != len(vols):
-        raise ValueError("one mask per volume expected")
-    if grid is None:
-        a, o, s = vols[0]
-        grid = (a.shape[::-1], o, s)
+    vols, grid = _group(volumes, chains, masks, grid)
     acc = CoverAverage(grid, device)
     try:
         for k, v in enumerate(vols):
@@ -317,44 +300,24 @@ def fused_dtype(values):
     return None
 
 
-class Labels:
+class Labels(_Accumulator):
     """frog_labels (include/frog_chain.h): n_images label maps added one by one on `grid` = (dims(x, y, z), origin, spacing),
     then the majority vote, its agreement, per-label probabilities and the table of vote sums."""
 
+    _NAME = "labels"
+
     def __init__(self, grid, n_images, max_labels=0, device=0):
-        self._lib = _abi.hip_lib()
-        dims, origin, spacing = grid
-        self.dims = tuple(int(d) for d in dims)
         self.n_images = int(n_images)
-        self._grid = _abi.volume_view(None, origin, spacing, self.dims)
-        self._h = C.c_void_p()
         self._n_labels = None
-        _abi.check(self._lib.frog_labels_create(C.byref(self._grid), self.n_images, int(max_labels), int(device), C.byref(self._h)),
-                   "frog_labels_create")
-
-    def close(self):
-        if self._h:
-            self._lib.frog_labels_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(grid, self.n_images, int(max_labels), int(device))
 
     def add(self, volume, chain=None, background=0.0, resliced=False):
         """Adds the integer label map `volume` ((voxels, origin, spacing) or an array already on the grid when chain is
         None); with a chain (frog_amd.chain.Chain, grid space -> volume space) its labels are what Chain.reslice gives with
         nearest-neighbour interpolation.  resliced=True returns that volume (source dtype, shape dims[::-1])."""
-        a, o, s = _as_volume(volume)
-        src = _abi.volume_view(a, o, s)
-        out, ov = None, None
-        if resliced:
-            out = np.empty(self.dims[::-1], a.dtype)
-            ov = _abi.volume_view(out, tuple(self._grid.origin), tuple(self._grid.spacing))
-        _abi.check(self._lib.frog_labels_add(self._h, chain._h if chain is not None else None, C.byref(src), float(background),
-                                             C.byref(ov) if ov is not None else None), "frog_labels_add")
+        _, src, _, ov, out = self._views(volume, None, resliced)
+        _abi.check(self._lib.frog_labels_add(self._h, chain._h if chain is not None else None, src, float(background), ov),
+                   "frog_labels_add")
         return out
 
     def finish(self):
@@ -408,14 +371,7 @@ def fuse_labels(volumes, chains=None, grid=None, background=0.0, max_labels=0, d
     average(); every volume has an integer type.  Returns (labels, agreement, values, dice): the fused map, the float32
     share of the images that agree with it, the distinct label values in ascending order and per label the pooled pairwise
     Dice overlap across the group (float64)."""
-    vols = [_as_volume(v) for v in volumes]
-    if not vols:
-        raise ValueError("no volumes")
-    if chains is not None and len(chains) != len(vols):
-        raise ValueError("one chain per volume expected")
-    if grid is None:
-        a, o, s = vols[0]
-        grid = (a.shape[::-1], o, s)
+    vols, grid = _group(volumes, chains, None, grid)
     acc = Labels(grid, len(vols), max_labels, device)
     try:
         for k, v in enumerate(vols):
