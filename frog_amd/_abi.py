@@ -341,6 +341,7 @@ HIP_SYMBOLS = {
     "frog_cull_stats_linear": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "frog_test_stray_points": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "frog_test_cull_ranges": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "frog_test_cull_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "frog_test_em_refit": (C.c_int, [C.c_void_p, C.c_int]),
     "frog_test_inlier_probability": (C.c_int, [C.c_int, c_float_p, c_float_p, C.c_size_t, c_float_p, c_float_p]),
     "frog_test_inlier_weight_pair": (C.c_int, [C.c_int, c_float_p, c_float_p, C.c_float, c_float_p, C.c_size_t, c_float_p,

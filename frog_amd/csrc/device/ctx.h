@@ -390,6 +390,8 @@ struct frog_ctx {
     frog::DevBuf<uint32_t> act_recs32;        // listed records (narrow form), or ...
     frog::DevBuf<frog::LinkRec> act_recs;     // ... wide form; same offsets as recs32 / recs
     frog::DevBuf<uint32_t> act_cnt;           // [n_tiles][n_groups]
+    frog::DevBuf<uint32_t> act_steps;         // one bit per step (64 records) of record storage: the listed step holds a point twice
+                                              // (k_links.hip.h SweepArgs::act_steps); zeroed before every list is written
     bool pos_b_stale = true;                  // pos was written (`apply`) since pos_b was gathered
     frog::DevBuf<float4> pos_b;               // pos in the order of perm (brick, cell, index): written by every lattice set-up,
                                               // read (coalesced) by the scatter and the B-spline transforms of that lattice --

@@ -151,8 +151,8 @@ static SweepArgs sweep_args(frog_ctx *ctx, uint32_t sub)
     a.band = ctx->exact_weights ? __builtin_inff() : THRESHOLD_BAND;
     a.tile_partial = ctx->tile_partial.p; a.tile_counts = ctx->tile_counts.p; a.group_sums = ctx->group_sums.p;
     a.own_pt_begin = ctx->own_pt_begin; a.own_points = ctx->own_pt_end - ctx->own_pt_begin;
-    a.act_recs = nullptr; a.act_cnt = nullptr; a.cull_state = nullptr;
-    a.cut_list = nullptr; a.build_recs = nullptr; a.build_cnt = nullptr;
+    a.act_recs = nullptr; a.act_cnt = nullptr; a.act_steps = nullptr; a.cull_state = nullptr;
+    a.cut_list = nullptr; a.build_recs = nullptr; a.build_cnt = nullptr; a.build_steps = nullptr;
     a.point_sums = ctx->point_sums.p; a.tile_order = ctx->tile_order.p; a.tiles_bo = ctx->tiles_bo.p;
     return a;
 }
@@ -195,6 +195,7 @@ static void launch_sweep(frog_ctx *ctx, uint32_t sub, hipStream_t s, hipEvent_t 
     if (use_list) {         // the caller has run cull_check() for the coordinates this launch reads
         args.act_recs = ctx->rec_format.narrow ? (const void *)ctx->act_recs32.p : (const void *)ctx->act_recs.p;
         args.act_cnt = ctx->act_cnt.p;
+        args.act_steps = ctx->act_steps.p;
         args.cull_state = ctx->cull_state.p;
     }
     const dim3 grid(sweep_blocks(ctx)), block(256);
@@ -212,6 +213,7 @@ static void launch_sweep(frog_ctx *ctx, uint32_t sub, hipStream_t s, hipEvent_t 
         if (build) {
             args.act_recs = nullptr; args.act_cnt = nullptr;         // walks every record
             args.cut_list = ctx->cut_list.p; args.build_recs = ctx->act_recs32.p; args.build_cnt = ctx->act_cnt.p;
+            args.build_steps = ctx->act_steps.p;
         }
         if (sweep_fused_now(ctx, build)) {
             // one block per tile, wavefront = partner group, ONE float4 of sums per point out (k_links.hip.h FUSED)
@@ -1285,7 +1287,7 @@ int frog_create(const frog_model *m, const frog_options *o, int device,
         rc = frog_create(m, &o3, device, 0, nf, &fixed);
         if (rc) { frog_destroy(moving); return rc; }
         fixed->cull_enabled = false;                                // a statistics-only context never sweeps a lattice step
-        fixed->act_recs32.release(); fixed->act_recs.release(); fixed->act_cnt.release(); fixed->pos2_snap.release();
+        fixed->act_recs32.release(); fixed->act_recs.release(); fixed->act_cnt.release(); fixed->act_steps.release(); fixed->pos2_snap.release();
         rc = frog_set_stream(fixed, moving->stream);
         if (rc) { frog_destroy(fixed); frog_destroy(moving); return rc; }
         moving->helper = fixed;
@@ -2011,12 +2013,14 @@ static int cull_allocate(frog_ctx *ctx)
     const int rc = cull_allocate_buffers(ctx);
     if (rc == FROG_OK) return rc;
     (void)hipGetLastError();
-    ctx->act_recs32.release(); ctx->act_recs.release(); ctx->act_cnt.release(); ctx->pos2_snap.release();
+    ctx->act_recs32.release(); ctx->act_recs.release(); ctx->act_cnt.release(); ctx->act_steps.release(); ctx->pos2_snap.release();
     ctx->cut_list.release(); ctx->disp_part.release(); ctx->cull_state.release(); ctx->disp_allow.release();
     ctx->cull_enabled = false;
     ctx->fused_sweep = ctx->fused_sweep && ctx->sw.fused == 1;
     return FROG_OK;
 }
+
+static size_t cull_step_words(const frog_ctx *ctx) { return (size_t)((ctx->L_recs / 64 + 31) / 32); }
 
 static int cull_allocate_buffers(frog_ctx *ctx)
 {
@@ -2029,6 +2033,9 @@ static int cull_allocate_buffers(frog_ctx *ctx)
         FROG_HIP_CHECK(hipMemsetAsync(ctx->act_recs.p, 0, ctx->act_recs.bytes(), s));
     }
     FROG_HIP_CHECK(ctx->act_cnt.alloc(std::max<size_t>(1, (size_t)ctx->n_tiles * ctx->n_groups)));
+    // a bit per step of record storage; a sweep reads the three words its range's first STEP_WINDOW bits may lie in
+    FROG_HIP_CHECK(ctx->act_steps.alloc(cull_step_words(ctx) + 2));
+    FROG_HIP_CHECK(hipMemsetAsync(ctx->act_steps.p, 0, ctx->act_steps.bytes(), s));
     FROG_HIP_CHECK(ctx->pos2_snap.alloc(ctx->P));
     FROG_HIP_CHECK(ctx->cut_list.alloc(ctx->nI));
     {
@@ -2062,13 +2069,16 @@ static int cull_prepare(frog_ctx *ctx)
         // the list itself: written by the sweep this call prepares (it walks every record anyway: k_links.hip.h BUILD), or,
         // for the record formats that sweep does not cover, by a pass of its own
         ctx->build_in_sweep = sweep_builds_list(ctx) && !ctx->sw.cull_build_pass;
+        // no step of the new list is marked yet, whoever writes it; the linear stage's list marks none (its sweep has no election)
+        FROG_HIP_CHECK(hipMemsetAsync(ctx->act_steps.p, 0, ctx->act_steps.bytes(), s));
+        uint32_t *steps = ctx->deformable ? ctx->act_steps.p : nullptr;
         if (!ctx->build_in_sweep) {
             const SweepArgs args = sweep_args(ctx, 0);
             const dim3 grid(sweep_blocks(ctx), ctx->n_sub);
             if (ctx->rec_format.narrow)
-                cull_build_kernel<false><<<grid, 256, 0, s>>>(args, ctx->cut_list.p, ctx->act_recs32.p, ctx->act_cnt.p);
+                cull_build_kernel<false><<<grid, 256, 0, s>>>(args, ctx->cut_list.p, ctx->act_recs32.p, ctx->act_cnt.p, steps);
             else
-                cull_build_kernel<true><<<grid, 256, 0, s>>>(args, ctx->cut_list.p, ctx->act_recs.p, ctx->act_cnt.p);
+                cull_build_kernel<true><<<grid, 256, 0, s>>>(args, ctx->cut_list.p, ctx->act_recs.p, ctx->act_cnt.p, steps);
             FROG_HIP_CHECK(hipGetLastError());
         }
         ctx->cull_need_build = false;
@@ -2739,6 +2749,22 @@ int frog_test_cull_ranges(frog_ctx *ctx, uint64_t *ranges, uint64_t *with_electi
             if (v & ~CULL_DUP_BIT) (*ranges)++;
             if (v & CULL_DUP_BIT) (*with_election)++;
         }
+    }
+    return FROG_OK;
+}
+
+int frog_test_cull_steps(frog_ctx *ctx, uint64_t *listed_steps, uint64_t *steps_with_election)
+{
+    CTX_GUARD(ctx);
+    if (!listed_steps || !steps_with_election) return fail(FROG_E_INVALID, "null output");
+    *listed_steps = 0; *steps_with_election = 0;
+    if (ctx->cull_builds && ctx->act_cnt.n) {
+        std::vector<uint32_t> h(ctx->act_cnt.n), bits(ctx->act_steps.n);
+        FROG_HIP_CHECK(hipMemcpyAsync(h.data(), ctx->act_cnt.p, ctx->act_cnt.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        FROG_HIP_CHECK(hipMemcpyAsync(bits.data(), ctx->act_steps.p, ctx->act_steps.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        FROG_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (uint32_t v : h) *listed_steps += ((v & ~CULL_DUP_BIT) + 63u) / 64u;
+        for (uint32_t v : bits) *steps_with_election += (uint64_t)__builtin_popcount(v);
     }
     return FROG_OK;
 }

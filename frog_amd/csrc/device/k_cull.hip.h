@@ -146,8 +146,11 @@ __global__ void cull_list_cutoff_kernel(const float *cut_now, uint32_t n_images,
 // act_recs, at the same offsets and in the same chunked / transposed storage as the full array (ctx.h REC_CHUNK), in
 // their order; act_cnt[tile][group] = how many.  One wavefront per range, as the sweep; grid.y = sub-pass.  The
 // distance is the sweep's own expression (f32, no contraction).  Runs when the list is (re)built only: no pipeline.
+// act_steps (null for the linear stage's list, whose sweep has no election): the steps that hold a point twice, as the
+// sweep's own list-writing form marks them (k_links.hip.h dup_steps_add).
 template <bool WIDE>
-__global__ __launch_bounds__(256) void cull_build_kernel(const SweepArgs a, const float *cut_list, void *act_recs, uint32_t *act_cnt)
+__global__ __launch_bounds__(256) void cull_build_kernel(const SweepArgs a, const float *cut_list, void *act_recs, uint32_t *act_cnt,
+                                                         uint32_t *act_steps)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t xcd = blockIdx.x % N_XCD;
@@ -174,6 +177,7 @@ __global__ __launch_bounds__(256) void cull_build_kernel(const SweepArgs a, cons
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     bool dup = false;
+    DupSteps dup_steps;
     uint32_t base = 0;
     // UNROLL steps of 64 records per trip, all their loads issued before the first is used (a dependent chain of
     // record -> two coordinates per step left the wavefront idle most of the time: 0.77 ms for 1e8 records)
@@ -211,15 +215,19 @@ __global__ __launch_bounds__(256) void cull_build_kernel(const SweepArgs a, cons
             const float cut = have[u] ? fminf(cutA, cut_list[imgB[u]]) : 0.f;
             const bool keep = have[u] && !(d2 >= cut * cut);  // as the sweep's own list-writing form (k_links.hip.h BUILD)
             const unsigned long long m = __ballot(keep);
+            const uint32_t to = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            bool hit = false;
             if (keep) {
-                const uint32_t to = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
                 dst[phys(to)] = rq[u];
-                dup |= atomicExch(&last_step[(uint32_t)rq[u] & 0xFFu], to >> 6) == (to >> 6);
+                hit = atomicExch(&last_step[(uint32_t)rq[u] & 0xFFu], to >> 6) == (to >> 6);
             }
+            dup |= hit;
+            if (act_steps) dup_steps_add(act_steps, dup_steps, rec_lo >> 6, hit, to, base, lane);
             base += (uint32_t)__popcll(m);
         }
     }
     const bool any_dup = __ballot(dup) != 0ull;
+    if (act_steps) dup_steps_flush(act_steps, dup_steps, lane);
     if (lane == 0) act_cnt[(size_t)t * a.n_groups + grp] = base | (any_dup ? CULL_DUP_BIT : 0u);
     // null records as far as a listed sweep's run-ahead reaches behind the list (k_links.hip.h, the sweep's own list-writing form)
     const uint32_t cap = (rec_n + REC_CHUNK - 1) / REC_CHUNK * REC_CHUNK;

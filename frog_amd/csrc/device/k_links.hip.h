@@ -47,8 +47,9 @@ static_assert(BODY_STEPS == 2 * CHUNK_RING && BODY_STEPS % PT_RING == 0 && PT_AH
               && 2 * CHUNK_AHEAD >= PT_AHEAD + 2, "ring periods must divide the unrolled body; a gather needs its record");
 constexpr int EMD_LDS_IMAGES = 256;     // partner groups up to this many images keep their constants in LDS
 // act_cnt: set when some step of the listed range holds two records of one own point (k_cull.hip.h); a range without
-// one is swept without the lane election
+// one is swept without the lane election, a range with one elects on the steps that act_steps marks
 constexpr uint32_t CULL_DUP_BIT = 0x80000000u;
+constexpr int STEP_WINDOW = 64;         // steps of a listed range whose act_steps bits the sweep keeps in scalar registers
 constexpr int OWNER_WORDS = TILE_POINTS / 2;      // election words per wavefront (deformable sweep)
 static_assert((OWNER_WORDS & (OWNER_WORDS - 1)) == 0, "the election word of a point is its index masked");
 static_assert(EMD_LDS_IMAGES == 1 << 8, "prep.h admits narrow records for img_bits <= 8 only");
@@ -84,12 +85,15 @@ struct SweepArgs {
     // certified outlier culling (k_cull.hip.h), deformable sweep only; all three null = walk every record
     const void *act_recs;       // the listed records, same offsets and storage as `recs`
     const uint32_t *act_cnt;    // [n_tiles][n_groups] listed records per range | CULL_DUP_BIT
+    const uint32_t *act_steps;  // one bit per step of record storage, bit rec_lo / 64 + step of a range that starts at record rec_lo:
+                                // the listed step holds some own point twice (0 behind a list's end); two readable words behind the last
     const uint32_t *cull_state; // [0] != 0: the list is not valid for the current coordinates -> walk every record
     // BUILD launches (the sweep that walks every record also writes the next list, k_cull.hip.h): per-image list cutoffs
     // and the list's storage
     const float *cut_list;
     void *build_recs;
     uint32_t *build_cnt;
+    uint32_t *build_steps;      // deformable sweep only (zeroed by the host before the launch)
 };
 
 // The sweep is bound by vector-instruction issue (rocprofv3), and the compiler's generic
@@ -219,6 +223,31 @@ __device__ __forceinline__ float inlier_weight_pair(float d2, const EmFast a, co
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(e));
 }
 
+// The list writers' record of WHICH steps of a list hold an own point twice (SweepArgs::act_steps; the BUILD form below and
+// cull_build_kernel).  Steps are met in ascending order, so a wavefront collects the bits of one word at a time in a
+// wave-uniform pair and ORs a finished word into the zeroed array: words are shared with the neighbouring ranges at a
+// range's two ends only, and an integer OR does not depend on who comes first.
+struct DupSteps { uint32_t word = 0xFFFFFFFFu, bits = 0u; };
+__device__ __forceinline__ void dup_steps_flush(uint32_t *steps, const DupSteps &d, int lane)
+{
+    if (d.bits != 0u && lane == 0) atomicOr(&steps[d.word], d.bits);
+}
+__device__ __forceinline__ void dup_steps_mark(uint32_t *steps, DupSteps &d, uint32_t bit, int lane)
+{
+    if ((bit >> 5) != d.word) { dup_steps_flush(steps, d, lane); d.word = bit >> 5; d.bits = 0u; }
+    d.bits |= 1u << (bit & 31u);
+}
+// Called by all 64 lanes after a trip of the compaction: `hit` = the lane's record went to a step that already held its own
+// point, `to` = its place in the list, `built` = the list's length before the trip (the trip's records land in step built / 64
+// or the one after it), `bit0` = the bit of the range's first step.
+__device__ __forceinline__ void dup_steps_add(uint32_t *steps, DupSteps &d, uint32_t bit0, bool hit, uint32_t to, uint32_t built, int lane)
+{
+    if (__ballot(hit) == 0ull) return;
+    const uint32_t s0 = built >> 6;
+    if (__ballot(hit && (to >> 6) == s0) != 0ull) dup_steps_mark(steps, d, bit0 + s0, lane);
+    if (__ballot(hit && (to >> 6) != s0) != 0ull) dup_steps_mark(steps, d, bit0 + s0 + 1u, lane);
+}
+
 __device__ __forceinline__ double wave_sum(double v)
 {
     #pragma unroll
@@ -321,17 +350,33 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
     bool listed = false;
     if constexpr (MODE != SWEEP_COUNT) listed = a.act_cnt != nullptr && a.cull_state[0] == 0u;
     bool elect = true;          // wave-uniform: lanes of one step may meet on a point (always assumed for unlisted ranges)
+    bool by_step = false;       // wave-uniform: ... and act_steps says in which steps (a listed range whose flag is set)
+    uint32_t sw[3] = { 0u, 0u, 0u };
     if (listed && live) {
+        // the range's step bits are asked for side by side with its count: their address needs the tile, not the count
+        if constexpr (MODE == SWEEP_DEFORMABLE) {
+            const uint32_t *w = a.act_steps + (rec_lo >> 11);
+            sw[0] = w[0]; sw[1] = w[1]; sw[2] = w[2];
+            __builtin_amdgcn_sched_barrier(0);          // (the scheduler otherwise waits for the count first: read the assembly)
+        }
         const uint32_t c = a.act_cnt[(size_t)t * a.n_groups + grp];
         rec_n = c & ~CULL_DUP_BIT;
         elect = (c & CULL_DUP_BIT) != 0u;
+        by_step = elect && MODE == SWEEP_DEFORMABLE;
     }
     elect = __builtin_amdgcn_readfirstlane((uint32_t)elect) != 0u;
+    by_step = __builtin_amdgcn_readfirstlane((uint32_t)by_step) != 0u;
     rec_lo = __builtin_amdgcn_readfirstlane(rec_lo);      // the same in every lane: keep them in SGPRs
     rec_n = __builtin_amdgcn_readfirstlane(rec_n);
     pt_begin = __builtin_amdgcn_readfirstlane(pt_begin);
     pt_count = __builtin_amdgcn_readfirstlane(pt_count);
     image = __builtin_amdgcn_readfirstlane(image);
+    // bits of the range's first STEP_WINDOW steps, bit k = step k (ranges start at even steps, anywhere in a word)
+    const uint32_t win_sh = (rec_lo >> 6) & 31u;
+    const uint32_t win_lo = __builtin_amdgcn_readfirstlane((uint32_t)((((unsigned long long)sw[1] << 32) | sw[0]) >> win_sh));
+    const uint32_t win_hi = __builtin_amdgcn_readfirstlane((uint32_t)((((unsigned long long)sw[2] << 32) | sw[1]) >> win_sh));
+    const unsigned long long win = ((unsigned long long)win_hi << 32) | win_lo;
+    static_assert(STEP_WINDOW == 64, "the window is one 64-bit scalar");
     float4 *my = acc + (MODE == SWEEP_DEFORMABLE ? wave * TILE_POINTS : 0);
     unsigned int *own = owner + (MODE == SWEEP_DEFORMABLE ? wave * OWNER_WORDS : 0);
 
@@ -400,6 +445,7 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
     const float cutA = BUILD ? a.cut_list[image] : 0.f;
     uint32_t built = 0;                 // BUILD: records listed so far
     bool dup = false;                   //        some step of the list holds one point twice
+    DupSteps dup_steps;                 //        ... and which (deformable sweep)
 
     const EmDerived eA = a.emd[image];
     const EmFast fA = a.emf[image];
@@ -442,8 +488,9 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
     #pragma unroll
     for (int k = 0; k < PT_RING; k++) pbq[k] = (k < PT_AHEAD) ? gather((k & 1) ? cq[k / 2].y : cq[k / 2].x) : P3{ 0.f, 0.f, 0.f };
 
-    auto step = [&](const Rec rq, const P3 pb, auto elect_c, const bool valid) __attribute__((always_inline)) {
-        constexpr bool ELECT = decltype(elect_c)::value;
+    // elect_c: 0 = no step of the walk holds a point twice, 1 = any may, 2 = this one does if `elect_now` (wave-uniform)
+    auto step = [&](const Rec rq, const P3 pb, auto elect_c, const bool elect_now, const bool valid) __attribute__((always_inline)) {
+        constexpr int ELECT = decltype(elect_c)::value;
         const uint32_t ia = own_of(rq);                 // own point inside the tile
         const P3 pa = { px[ia], px[ia + PLANE], px[ia + 2 * PLANE] };
         EmDerived eB;
@@ -462,11 +509,14 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
             const float cut = fminf(cutA, cut_s[img_of(rq)]);
             const bool keep = valid && !(d2 >= cut * cut);  // a NaN distance is listed (the linear sweep's sums must see it, as the full sweep's do)
             const unsigned long long m = __ballot(keep);
+            const uint32_t to = built + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            bool hit = false;
             if (keep) {
-                const uint32_t to = built + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
                 reinterpret_cast<Rec *>(a.build_recs)[(size_t)rec_lo + (to / REC_CHUNK) * REC_CHUNK + (to % 64u) * 2u + (to % REC_CHUNK) / 64u] = rq;
-                dup |= atomicExch(&last_step[ia], to >> 6) == (to >> 6);
+                hit = atomicExch(&last_step[ia], to >> 6) == (to >> 6);
             }
+            dup |= hit;
+            if constexpr (MODE == SWEEP_DEFORMABLE) dup_steps_add(a.build_steps, dup_steps, rec_lo >> 6, hit, to, built, lane);
             built += (uint32_t)__popcll(m);
             if (!valid) return;
         }
@@ -516,7 +566,7 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
             const float w2 = w * w;
             s[1] += (double)(inlier ? w2 : 0.0f);         // adding +0.0 leaves the f64 sums unchanged
             s[0] += (double)(inlier ? w2 * d2 : 0.0f);
-            if constexpr (!ELECT) {
+            if (ELECT == 0 || (ELECT == 2 && !elect_now)) {
                 // no two lanes of this step hold the same point (certified when the list was built)
                 if (inlier) {
                     float4 t = my[ia];
@@ -552,6 +602,9 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
     const uint32_t n_steps = (rec_n + 63) / 64;          // wave-uniform
     auto walk = [&](auto elect_c) __attribute__((always_inline)) {
         for (uint32_t base = 0; base < n_steps; base += BODY_STEPS) {
+            // the trip's step bits, bit j = step base + j; ones behind the window: a flagged range elects on every step there
+            uint32_t trip = 0u;
+            if constexpr (decltype(elect_c)::value == 2) trip = base < (uint32_t)STEP_WINDOW ? ~(uint32_t)(~win >> base) : ~0u;
             #pragma unroll
             for (int j = 0; j < BODY_STEPS; j++) {
                 const uint32_t r = lane + 64 * (base + j);   // step base+j, lane -> record r of the range
@@ -560,15 +613,20 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
                     const Chunk ahead = cq[((j + PT_AHEAD) / 2) % CHUNK_RING];
                     pbq[(j + PT_AHEAD) % PT_RING] = gather(((j + PT_AHEAD) & 1) ? ahead.y : ahead.x);
                 }
-                if (BUILD || r < rec_n) step((j & 1) ? cq[j / 2].y : cq[j / 2].x, pbq[j % PT_RING], elect_c, r < rec_n);
+                if (BUILD || r < rec_n) step((j & 1) ? cq[j / 2].y : cq[j / 2].x, pbq[j % PT_RING], elect_c, (trip >> j & 1u) != 0u, r < rec_n);
 #ifdef FROG_SWEEP_TRACE
                 if (base == 0 && j == 0) FROG_TR(3);
 #endif
             }
         }
     };
-    if (MODE != SWEEP_DEFORMABLE || elect) walk(std::true_type{});
-    else walk(std::false_type{});
+    // Three instantiations of the walk: a certified range never elects, a flagged range of a list elects where its step bits
+    // say so (ONE body: the step's arithmetic, then a scalar branch on the trip's bit j to the election loop or to the plain
+    // read-add-write -- every load of the step is issued in front of it, so the counted waits stay counted), and everything
+    // unlisted (a list-writing launch, an invalid list, FROG_CULL=0, the other sweeps) elects on every step.
+    if (MODE == SWEEP_DEFORMABLE && !elect) walk(std::integral_constant<int, 0>{});
+    else if (MODE == SWEEP_DEFORMABLE && by_step) walk(std::integral_constant<int, 2>{});
+    else walk(std::integral_constant<int, 1>{});
     FROG_TR(4);
 
     if constexpr (BUILD) {
@@ -598,6 +656,7 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
         }
         if constexpr (BUILD) {
             const bool any_dup = __ballot(dup) != 0ull;
+            dup_steps_flush(a.build_steps, dup_steps, lane);
             if (lane == 0 && live) a.build_cnt[(size_t)t * a.n_groups + grp] = built | (any_dup ? CULL_DUP_BIT : 0u);
         }
         __syncthreads();

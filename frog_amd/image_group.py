@@ -255,6 +255,12 @@ class ImageGroup:
         check(self._lib.frog_test_cull_ranges(self._ctx, C.byref(a), C.byref(b)), "frog_test_cull_ranges")
         return a.value, b.value
 
+    def cull_steps(self):
+        """(steps of 64 records in the culling list, steps that hold a point twice and elect) -- frog_test_cull_steps."""
+        a, b = C.c_uint64(), C.c_uint64()
+        check(self._lib.frog_test_cull_steps(self._ctx, C.byref(a), C.byref(b)), "frog_test_cull_steps")
+        return a.value, b.value
+
     def stray_points(self):
         """Points the scatter found outside their brick since creation (frog_test_stray_points): 0 unless the sort is broken."""
         n = C.c_uint64()

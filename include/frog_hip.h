@@ -302,6 +302,9 @@ int frog_test_stray_points(frog_ctx *ctx, uint64_t *n);
 /* test hook: non-empty (tile, partner group) ranges of the current culling list, and how many of them hold a step in
  * which two lanes carry the same point (those are swept with the lane election, the others without; k_cull.hip.h) */
 int frog_test_cull_ranges(frog_ctx *ctx, uint64_t *ranges, uint64_t *with_election);
+/* test hook: steps (64 listed records, the lanes of one sweep step) of the current culling list, and how many of them hold
+ * a point twice: a range counted by frog_test_cull_ranges' second output elects in exactly those steps */
+int frog_test_cull_steps(frog_ctx *ctx, uint64_t *listed_steps, uint64_t *steps_with_election);
 
 /* Test hook: Stats::estimateDistribution (stats.cxx:14-70) again, on the samples the last refresh retained and from
  * the CURRENT (c1, c2, ratio) of every owned image (set them with frog_set_em first), with the term-by-term form of
