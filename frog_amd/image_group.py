@@ -111,6 +111,13 @@ class ImageGroup:
         check(self._lib.frog_deformable_setup(self._ctx, level, C.byref(info)), "frog_deformable_setup")
         return info
 
+    def deformable_setup_bounds(self, level, mins, maxs):
+        """setupDeformableTransforms over a bounding box of the caller's (frog_deformable_setup_bounds)."""
+        info = _abi.FrogGridInfo()
+        check(self._lib.frog_deformable_setup_bounds(self._ctx, level, (C.c_double * 3)(*mins), (C.c_double * 3)(*maxs),
+                                                     C.byref(info)), "frog_deformable_setup_bounds")
+        return info
+
     def updateDeformableTransforms(self, alpha):
         e = C.c_double()
         check(self._lib.frog_deformable_step(self._ctx, alpha, C.byref(e)), "frog_deformable_step")
