@@ -302,6 +302,16 @@ HIP_SYMBOLS = {
     "frog_labels_fused": (C.c_int, [C.c_void_p, C.POINTER(FrogVolume), c_float_p]),
     "frog_labels_probability": (C.c_int, [C.c_void_p, C.c_int64, c_float_p]),
     "frog_labels_destroy": (None, [C.c_void_p]),
+    "frog_wlabels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int,
+                                      C.POINTER(C.c_void_p)]),
+    "frog_wlabels_target": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_int, C.c_double, C.POINTER(FrogVolume)]),
+    "frog_wlabels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double,
+                                   C.c_double, C.POINTER(FrogVolume), C.POINTER(FrogVolume)]),
+    "frog_wlabels_finish": (C.c_int, [C.c_void_p, c_u32_p]),
+    "frog_wlabels_values": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "frog_wlabels_fused": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(FrogVolume), c_float_p]),
+    "frog_wlabels_probability": (C.c_int, [C.c_void_p, C.c_int64, c_float_p]),
+    "frog_wlabels_destroy": (None, [C.c_void_p]),
     "frog_match_options_default": (None, [C.POINTER(FrogMatchOptions)]),
     "frog_matcher_create": (C.c_int, [C.POINTER(FrogKeypoints), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_matcher_destroy": (None, [C.c_void_p]),

@@ -833,6 +833,215 @@ __global__ __launch_bounds__(256) void labels_probability_kernel(size_t base, co
     p[idx] = (float)plane[idx] / n;
 }
 
+// ---- locally weighted label fusion (frog_wlabels; no counterpart in the reference) -------------------------------------------
+// An add has two phases.  Phase 1 evaluates the chain once per voxel and leaves the atlas on the grid: its image as an f32
+// plane in which a voxel that is not valid (outside the source, or not finite) is a NaN -- a non-finite value is no member
+// anyway, so the plane needs no mask beside it -- and its label map in the labels' own type, every label a key of the
+// LabelMap.  Phase 2 (wlabels_vote_kernel) forms the patch sums from that plane and the target's and adds the weight to the
+// label's plane.  The target's plane is made once by the kernel of phase 1 without the labels.
+
+// a staged value: x = (float)r where the voxel is valid and x is finite, else NaN
+template <class S>
+__device__ __forceinline__ float wlabels_stage(S r, bool valid)
+{
+    const float x = (float)r;
+    return valid && isfinite(x) ? x : __builtin_nanf("");
+}
+
+// voxel idx of a volume of one of the six integer types, picked at run time: one read per voxel, where 48 instantiations of a
+// kernel that inlines the whole chain (image type x label type) would only lengthen the build
+__device__ __forceinline__ long long label_load(const void *__restrict__ v, int dtype, size_t idx)
+{
+    switch (dtype) {
+    case FROG_V_U8: return ((const uint8_t *)v)[idx];
+    case FROG_V_I8: return ((const int8_t *)v)[idx];
+    case FROG_V_U16: return ((const uint16_t *)v)[idx];
+    case FROG_V_I16: return ((const int16_t *)v)[idx];
+    case FROG_V_U32: return ((const uint32_t *)v)[idx];
+    default: return ((const int32_t *)v)[idx];
+    }
+}
+
+__device__ __forceinline__ void label_store(void *__restrict__ v, int dtype, size_t idx, long long label)
+{
+    switch (dtype) {
+    case FROG_V_U8: ((uint8_t *)v)[idx] = (uint8_t)label; break;
+    case FROG_V_I8: ((int8_t *)v)[idx] = (int8_t)label; break;
+    case FROG_V_U16: ((uint16_t *)v)[idx] = (uint16_t)label; break;
+    case FROG_V_I16: ((int16_t *)v)[idx] = (int16_t)label; break;
+    case FROG_V_U32: ((uint32_t *)v)[idx] = (uint32_t)label; break;
+    default: ((int32_t *)v)[idx] = (int32_t)label; break;
+    }
+}
+
+// The voxel a nearest-neighbour reslice of the label map stores for position p (after the chain): reslice_sample's nearest
+// branch with the type picked at run time.  An integer voxel passes to_voxel unchanged, so inside the map it is the voxel
+// itself; outside it is the background rounded half up and clamped to the type.
+__device__ __forceinline__ long long label_nearest(const void *__restrict__ src, int dtype, const ResliceGrid &g, const double p[3])
+{
+    double c[3];
+    if (voxel_coordinates(p, g.so, g.ss, g.sx, g.sy, g.sz, c)) {
+        int x = (int)floor(c[0] + 0.5), y = (int)floor(c[1] + 0.5), z = (int)floor(c[2] + 0.5);
+        x = x < 0 ? 0 : (x >= g.sx ? g.sx - 1 : x);
+        y = y < 0 ? 0 : (y >= g.sy ? g.sy - 1 : y);
+        z = z < 0 ? 0 : (z >= g.sz ? g.sz - 1 : z);
+        return label_load(src, dtype, (size_t)x + (size_t)g.sx * ((size_t)y + (size_t)g.sy * (size_t)z));
+    }
+    switch (dtype) {
+    case FROG_V_U8: return to_voxel<uint8_t>(g.background);
+    case FROG_V_I8: return to_voxel<int8_t>(g.background);
+    case FROG_V_U16: return to_voxel<uint16_t>(g.background);
+    case FROG_V_I16: return to_voxel<int16_t>(g.background);
+    case FROG_V_U32: return to_voxel<uint32_t>(g.background);
+    default: return to_voxel<int32_t>(g.background);
+    }
+}
+
+// Phase 1.  LABELS false: the target.  The image goes through reslice_sample (the code of reslice_kernel) into `plane` (and,
+// in its own type, into `out`, which may be null); with LABELS the label at the same position goes into `lout` in the
+// labels' type and into the map.  Without a chain both volumes are on the grid: every voxel is inside, and phase 2 reads the
+// labels where they are.
+template <class S, bool CHAIN, bool LABELS>
+__global__ __launch_bounds__(256) void wlabels_collect_kernel(size_t base, const DevLink *links, int n_links, const S *__restrict__ src,
+                                                              const ResliceGrid g, const void *__restrict__ lsrc, int ltype, const ResliceGrid lg,
+                                                              size_t total, float *__restrict__ plane, S *__restrict__ out,
+                                                              void *__restrict__ lout, const LabelMap m)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    if (CHAIN) {
+        double p[3], c[3];
+        reslice_position(links, n_links, g.out, idx, p);
+        const bool valid = voxel_coordinates(p, g.so, g.ss, g.sx, g.sy, g.sz, c);
+        const S r = reslice_sample<S>(src, g, c, valid);
+        if (out) out[idx] = r;
+        plane[idx] = wlabels_stage<S>(r, valid);
+        if (LABELS) {
+            const long long label = label_nearest(lsrc, ltype, lg, p);
+            label_store(lout, ltype, idx, label);
+            label_insert(m, label);
+        }
+    } else {
+        plane[idx] = wlabels_stage<S>(src[idx], true);
+        if (LABELS) label_insert(m, label_load(lsrc, ltype, idx));
+    }
+}
+
+// Phase 2, the vote.  A block owns a tile of 32 x 8 x 4 voxels (x fastest), thread (lx, ly) the column of its four z.  The
+// tile and a halo of R voxels go to LDS as one (T, A) pair per voxel -- T a NaN where the voxel is no member of the patch
+// (outside the grid, or the target or the atlas not valid there), A then 0 -- so a tap is one 8-byte LDS read, and the 32
+// lanes of a lane group read 32 consecutive pairs: no bank conflict whatever the row length.  With the halo of R = 4 the
+// tile holds 40 x 16 x 12 pairs = 61 440 bytes, within 64 KB; a tile 64 wide would need 72 x 12 x 12 pairs, 82 944 bytes.
+// The six sums run over z, then y, then x ascending as the header states; a non-member adds +0.0 (and 0 to the count), which
+// leaves every sum's bits as skipping it does: they start at +0.0 and never become -0.0.  One f64 operation per statement
+// (-ffp-contract=off); the thread owns its voxel in every plane: no atomic.
+constexpr int WL_TX = 32, WL_TY = 8, WL_TZ = 4;
+
+struct WlabelsTiles {
+    uint32_t nx, ny, nz;            // the grid
+    uint32_t tx, ty;                // tiles along x and y
+    size_t tiles;
+};
+
+template <int R>
+__global__ __launch_bounds__(256) void wlabels_vote_kernel(size_t base, const float *__restrict__ target, const float *__restrict__ atlas,
+                                                           const void *__restrict__ labels, int ltype, const WlabelsTiles w,
+                                                           uint32_t power, float floor_c, const LabelMap m,
+                                                           float *const *__restrict__ planes, uint32_t n_planes)
+{
+    constexpr int HX = WL_TX + 2 * R, HY = WL_TY + 2 * R, HZ = WL_TZ + 2 * R;
+    __shared__ float2 s_ta[HX * HY * HZ];
+    const size_t tile = base / 256 + blockIdx.x;            // one block per tile: the same for every thread of the block
+    if (tile >= w.tiles) return;
+    const int x0 = (int)(tile % w.tx) * WL_TX, y0 = (int)((tile / w.tx) % w.ty) * WL_TY, z0 = (int)(tile / ((size_t)w.tx * w.ty)) * WL_TZ;
+    for (int i = threadIdx.x; i < HX * HY * HZ; i += 256) {
+        const int x = x0 - R + i % HX, y = y0 - R + (i / HX) % HY, z = z0 - R + i / (HX * HY);
+        float2 ta = make_float2(__builtin_nanf(""), 0.0f);
+        if (x >= 0 && y >= 0 && z >= 0 && x < (int)w.nx && y < (int)w.ny && z < (int)w.nz) {
+            const size_t idx = (size_t)x + (size_t)w.nx * ((size_t)y + (size_t)w.ny * (size_t)z);
+            const float t = target[idx], a = atlas[idx];
+            if (t == t && a == a) ta = make_float2(t, a);
+        }
+        s_ta[i] = ta;
+    }
+    __syncthreads();
+    const int lx = threadIdx.x % WL_TX, ly = threadIdx.x / WL_TX;
+    const int x = x0 + lx, y = y0 + ly;
+    if (x >= (int)w.nx || y >= (int)w.ny) return;
+    for (int lz = 0; lz < WL_TZ && z0 + lz < (int)w.nz; lz++) {
+        const float2 centre = s_ta[((lz + R) * HY + ly + R) * HX + lx + R];
+        if (!(centre.x == centre.x)) continue;              // no member: no vote from this atlas
+        uint32_t count = 0;
+        double st = 0.0, sa = 0.0, stt = 0.0, saa = 0.0, sta = 0.0;
+        for (int dz = 0; dz <= 2 * R; dz++) {
+            for (int dy = 0; dy <= 2 * R; dy++) {
+                const float2 *row = &s_ta[((lz + dz) * HY + ly + dy) * HX + lx];
+#pragma unroll
+                for (int dx = 0; dx <= 2 * R; dx++) {
+                    const float2 ta = row[dx];
+                    const bool member = ta.x == ta.x;
+                    const double T = member ? (double)ta.x : 0.0, A = (double)ta.y;
+                    const double tt = T * T, aa = A * A, tA = T * A;
+                    count += member ? 1u : 0u;
+                    st = st + T; sa = sa + A; stt = stt + tt; saa = saa + aa; sta = sta + tA;
+                }
+            }
+        }
+        const double n = (double)count;
+        const double cov = n * sta - st * sa, vt = n * stt - st * st, va = n * saa - sa * sa;
+        float c = 0.0f;
+        if (count >= 2 && vt > 0.0 && va > 0.0 && cov > 0.0) {
+            const double num = cov * cov, den = vt * va;
+            const float q = (float)(num / den);
+            c = sqrtf(q);
+            if (isfinite(c)) c = fminf(c, 1.0f);
+        }
+        c = fmaxf(c, floor_c);
+        float weight = c;
+        for (uint32_t k = 1; k < power; k++) weight = weight * c;
+        const size_t idx = (size_t)x + (size_t)w.nx * ((size_t)y + (size_t)w.ny * (size_t)(z0 + lz));
+        const uint32_t l = label_find(m, label_load(labels, ltype, idx));
+        if (l < n_planes) planes[l][idx] = planes[l][idx] + weight;
+    }
+}
+
+// The winner of a voxel and its share: `planes` and `values` in ascending order of the values.  total is the planes' f32 sum
+// in that order from +0.0; a later label must have a strictly larger score, and the first must be > 0, so a tie stays with
+// the smallest value.  No weight at all: the fill label and 0.
+template <class T>
+__global__ __launch_bounds__(256) void wlabels_fused_kernel(size_t base, const float *const *__restrict__ planes,
+                                                            const long long *__restrict__ values, uint32_t n_labels, size_t total,
+                                                            T fill, T *__restrict__ label, float *__restrict__ confidence)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    float sum = 0.0f, best = 0.0f;
+    uint32_t winner = 0;
+    for (uint32_t l = 0; l < n_labels; l++) {
+        const float s = planes[l][idx];
+        sum = sum + s;
+        if (s > best) { best = s; winner = l; }
+    }
+    const bool some = sum != 0.0f;
+    if (label) label[idx] = some ? (T)values[winner] : fill;
+    if (confidence) confidence[idx] = some ? best / sum : 0.0f;
+}
+
+// score / total of label `which` of the sorted planes; 0 where no weight arrived
+__global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, const float *const *__restrict__ planes, uint32_t n_labels,
+                                                                  uint32_t which, size_t total, float *__restrict__ p)
+{
+    const size_t idx = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    float sum = 0.0f, score = 0.0f;
+    for (uint32_t l = 0; l < n_labels; l++) {
+        const float s = planes[l][idx];
+        sum = sum + s;
+        if (l == which) score = s;
+    }
+    p[idx] = sum != 0.0f ? score / sum : 0.0f;
+}
+
 } // namespace
 
 struct frog_chain {
@@ -881,6 +1090,26 @@ struct frog_labels : frog_group {
     std::vector<uint32_t> dense;                    // table position -> dense index
     std::vector<uint64_t> voxels, pairs;
     frog::DevBuf<uint16_t *> d_sorted_planes;
+    frog::DevBuf<long long> d_sorted_values;
+};
+
+// weighted votes of a group of atlases for a target image on one grid
+struct frog_wlabels : frog_group {
+    uint32_t n_images = 0, added = 0, max_labels = 0, radius = 0, power = 0;
+    float floor = 0;
+    bool has_target = false, finished = false;
+    LabelMap map{};                                 // as in frog_labels
+    frog::DevBuf<long long> d_keys, d_values;
+    frog::DevBuf<uint32_t> d_index, d_state;
+    std::vector<long long> known;                   // dense index -> value: the labels that have a plane
+    std::deque<frog::DevBuf<float>> planes;         // one f32 score plane per known label
+    frog::DevBuf<float *> d_planes;                 // dense index -> plane
+    frog::DevBuf<float> d_target, d_atlas;          // t and a on the grid, NaN where not valid
+    frog::DevBuf<unsigned char> d_lsrc, d_lout;     // staging of the current label map / resliced label map
+    // after finish: the table in ascending order of the values
+    std::vector<long long> values;
+    std::vector<uint32_t> dense;                    // table position -> dense index
+    frog::DevBuf<float *> d_sorted_planes;
     frog::DevBuf<long long> d_sorted_values;
 };
 
@@ -1238,7 +1467,9 @@ int cover_inputs(const char *where, const frog_cover *a, const frog_chain *c, co
 }
 
 // The device map rebuilt from the known labels alone (at creation: empty): how a refused volume's inserts are taken back.
-hipError_t labels_reset_map(frog_labels *a)
+// A: frog_labels or frog_wlabels.
+template <class A>
+hipError_t labels_reset_map(A *a)
 {
     const size_t slots = (size_t)a->map.mask + 1;
     std::vector<long long> keys(slots, LABEL_EMPTY);
@@ -1256,12 +1487,56 @@ hipError_t labels_reset_map(frog_labels *a)
     return e;
 }
 
+// The empty device map of a new accumulator (A: frog_labels or frog_wlabels) for a->max_labels labels, and its table of
+// plane pointers: at least 16 slots, at least two per label.
+template <class A>
+int labels_new_map(A *a)
+{
+    int bits = 4;
+    while (((size_t)1 << bits) < 2 * (size_t)a->max_labels) bits++;
+    const size_t slots = (size_t)1 << bits;
+    KCHECK(a->d_keys.alloc(slots));
+    KCHECK(a->d_index.alloc(slots));
+    KCHECK(a->d_values.alloc(a->max_labels));
+    KCHECK(a->d_state.alloc(2));
+    KCHECK(a->d_planes.alloc(a->max_labels));
+    a->map = LabelMap{ a->d_keys.p, a->d_index.p, a->d_values.p, a->d_state.p, (uint32_t)(slots - 1), 64 - bits, a->max_labels };
+    KCHECK(labels_reset_map(a));
+    return FROG_OK;
+}
+
+// The planes of the labels an add has found beyond the n_known that had one: their values from the device map, a zeroed
+// plane of P each, the pointers behind d_planes.  On a failure the new planes are gone again and `known` is as it was.
+template <class P>
+hipError_t labels_grow_planes(size_t total, size_t n_now, const long long *d_values, std::vector<long long> &known,
+                              std::deque<frog::DevBuf<P>> &planes, P **d_planes)
+{
+    const size_t n_known = known.size();
+    if (n_now <= n_known) return hipSuccess;
+    std::vector<long long> fresh(n_now - n_known);
+    std::vector<P *> pointers;
+    hipError_t e = hipMemcpy(fresh.data(), d_values + n_known, fresh.size() * sizeof(long long), hipMemcpyDeviceToHost);
+    for (size_t i = 0; i < fresh.size() && e == hipSuccess; i++) {
+        planes.emplace_back();
+        e = planes.back().alloc(total);
+        if (e == hipSuccess) e = hipMemset(planes.back().p, 0, total * sizeof(P));
+        pointers.push_back(planes.back().p);
+    }
+    if (e == hipSuccess) e = hipMemcpy(d_planes + n_known, pointers.data(), pointers.size() * sizeof(P *), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        while (planes.size() > n_known) planes.pop_back();
+        return e;
+    }
+    known.insert(known.end(), fresh.begin(), fresh.end());
+    return hipSuccess;
+}
+
 template <class S>
 int labels_add_typed(frog_labels *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
 {
     ResliceGrid g;
     if (int rc = stage_source<S>("frog_labels_add", a, src, c != nullptr, 0, background, &g)) return rc;
-    const size_t n_known = a->known.size();
     const S *d_src = (const S *)a->d_src.p;
     S *d_out = (S *)a->d_out.p;                     // with a chain the votes are read from the resliced labels
     const S *d_labels = c ? d_out : d_src;
@@ -1279,24 +1554,8 @@ int labels_add_typed(frog_labels *a, frog_chain *c, const frog_volume *src, doub
     if (state[1] || state[0] > a->max_labels)
         return refuse(fail(FROG_E_INVALID, "frog_labels_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
     const size_t n_now = state[0];
-    if (n_now > n_known) {
-        std::vector<long long> fresh(n_now - n_known);
-        std::vector<uint16_t *> pointers;
-        e = hipMemcpy(fresh.data(), a->d_values.p + n_known, fresh.size() * sizeof(long long), hipMemcpyDeviceToHost);
-        for (size_t i = 0; i < fresh.size() && e == hipSuccess; i++) {
-            a->planes.emplace_back();
-            e = a->planes.back().alloc(a->total);
-            if (e == hipSuccess) e = hipMemset(a->planes.back().p, 0, a->total * sizeof(uint16_t));
-            pointers.push_back(a->planes.back().p);
-        }
-        if (e == hipSuccess) e = hipMemcpy(a->d_planes.p + n_known, pointers.data(), pointers.size() * sizeof(uint16_t *), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            while (a->planes.size() > n_known) a->planes.pop_back();
-            return refuse(hip_fail("frog_labels_add", e));
-        }
-        a->known.insert(a->known.end(), fresh.begin(), fresh.end());
-    }
+    e = labels_grow_planes<uint16_t>(a->total, n_now, a->d_values.p, a->known, a->planes, a->d_planes.p);
+    if (e != hipSuccess) return refuse(hip_fail("frog_labels_add", e));
     e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
         labels_vote_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_labels, a->total, a->map, a->d_planes.p, (uint32_t)n_now);
     });
@@ -1304,8 +1563,8 @@ int labels_add_typed(frog_labels *a, frog_chain *c, const frog_volume *src, doub
 }
 
 // every value of the table is a T
-template <class T>
-bool labels_fit(const frog_labels *a)
+template <class T, class A>
+bool labels_fit(const A *a)
 {
     for (const long long v : a->values)
         if (v < (long long)std::numeric_limits<T>::lowest() || v > (long long)std::numeric_limits<T>::max()) return false;
@@ -1327,6 +1586,108 @@ int labels_fused_typed(frog_labels *a, frog_volume *label, float *agreement)
     if (e == hipSuccess && label) e = hipMemcpy(label->data, d_label.p, a->total * sizeof(T), hipMemcpyDeviceToHost);
     if (e == hipSuccess && agreement) e = hipMemcpy(agreement, d_agreement.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail("frog_labels_fused", e);
+    return FROG_OK;
+}
+
+// the tiles of wlabels_vote_kernel over the accumulator's grid
+WlabelsTiles wlabels_tiles(const frog_wlabels *a)
+{
+    WlabelsTiles w;
+    w.nx = a->grid.dims[0]; w.ny = a->grid.dims[1]; w.nz = a->grid.dims[2];
+    w.tx = (w.nx + WL_TX - 1) / WL_TX;
+    w.ty = (w.ny + WL_TY - 1) / WL_TY;
+    w.tiles = (size_t)w.tx * w.ty * ((w.nz + WL_TZ - 1) / WL_TZ);
+    return w;
+}
+
+template <class S>
+int wlabels_target_typed(frog_wlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+{
+    ResliceGrid g;
+    if (int rc = stage_source<S>("frog_wlabels_target", a, src, c && resliced, interpolation, background, &g)) return rc;
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = resliced ? (S *)a->d_out.p : nullptr;
+    const hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            wlabels_collect_kernel<S, true, false><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, nullptr, 0, g,
+                                                                             a->total, a->d_target.p, d_out, nullptr, a->map);
+        else
+            wlabels_collect_kernel<S, false, false><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, nullptr, 0, g, a->total, a->d_target.p,
+                                                                              nullptr, nullptr, a->map);
+    });
+    return return_resliced<S>("frog_wlabels_target", a, c, src, resliced, e);
+}
+
+// S: the image's type; the label map's is a run-time argument of the kernels
+template <class S>
+int wlabels_add_typed(frog_wlabels *a, frog_chain *c, const frog_volume *image, const frog_volume *labels, int interpolation,
+                      double image_background, double label_background, frog_volume *resliced_image, frog_volume *resliced_labels)
+{
+    ResliceGrid g;
+    if (int rc = stage_source<S>("frog_wlabels_add", a, image, c && resliced_image, interpolation, image_background, &g)) return rc;
+    const size_t label_bytes = frog_volume_voxel_bytes(labels->dtype), n_labels_src = voxel_count(labels);
+    KCHECK(a->d_lsrc.alloc(n_labels_src * label_bytes));
+    if (c) KCHECK(a->d_lout.alloc(a->total * label_bytes));
+    KCHECK(hipMemcpy(a->d_lsrc.p, labels->data, n_labels_src * label_bytes, hipMemcpyHostToDevice));
+    const ResliceGrid lg = reslice_grid(labels, &a->grid, 0, label_background);
+    const int ltype = labels->dtype;
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = resliced_image ? (S *)a->d_out.p : nullptr;
+    const void *d_labels = c ? a->d_lout.p : a->d_lsrc.p;      // with a chain the votes are read from the resliced labels
+    uint32_t state[2] = { 0, 0 };
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            wlabels_collect_kernel<S, true, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->d_lsrc.p, ltype, lg,
+                                                                            a->total, a->d_atlas.p, d_out, a->d_lout.p, a->map);
+        else
+            wlabels_collect_kernel<S, false, true><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, a->d_lsrc.p, ltype, lg, a->total,
+                                                                             a->d_atlas.p, nullptr, nullptr, a->map);
+    });
+    if (e == hipSuccess) e = hipMemcpy(state, a->d_state.p, sizeof state, hipMemcpyDeviceToHost);
+    // as in labels_add_typed: from here on the map may hold values without a plane, and every failure takes them back
+    auto refuse = [&](int rc) { (void)labels_reset_map(a); return rc; };
+    if (e != hipSuccess) return refuse(hip_fail("frog_wlabels_add", e));
+    if (state[1] || state[0] > a->max_labels)
+        return refuse(fail(FROG_E_INVALID, "frog_wlabels_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
+    const size_t n_now = state[0];
+    e = labels_grow_planes<float>(a->total, n_now, a->d_values.p, a->known, a->planes, a->d_planes.p);
+    if (e != hipSuccess) return refuse(hip_fail("frog_wlabels_add", e));
+    const WlabelsTiles w = wlabels_tiles(a);
+    // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
+    e = chunked_launch(w.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
+#define WLABELS_VOTE(R) wlabels_vote_kernel<R><<<blocks, LAUNCH_BLOCK>>>(base, a->d_target.p, a->d_atlas.p, d_labels, ltype, w, a->power, a->floor, \
+                                                                        a->map, a->d_planes.p, (uint32_t)n_now)
+        switch (a->radius) {
+        case 1: WLABELS_VOTE(1); break;
+        case 2: WLABELS_VOTE(2); break;
+        case 3: WLABELS_VOTE(3); break;
+        default: WLABELS_VOTE(4); break;
+        }
+#undef WLABELS_VOTE
+    });
+    if (e == hipSuccess && resliced_labels) {
+        if (c) e = hipMemcpy(resliced_labels->data, a->d_lout.p, a->total * label_bytes, hipMemcpyDeviceToHost);
+        else std::memcpy(resliced_labels->data, labels->data, a->total * label_bytes);
+    }
+    return return_resliced<S>("frog_wlabels_add", a, c, image, resliced_image, e);
+}
+
+template <class T>
+int wlabels_fused_typed(frog_wlabels *a, long long fill, frog_volume *label, float *confidence)
+{
+    if (label && (!labels_fit<T>(a) || fill < (long long)std::numeric_limits<T>::lowest() || fill > (long long)std::numeric_limits<T>::max()))
+        return fail(FROG_E_INVALID, "frog_wlabels_fused: a label value or the fill label does not fit the requested type");
+    frog::DevBuf<T> d_label;
+    frog::DevBuf<float> d_confidence;
+    if (label) KCHECK(d_label.alloc(a->total));
+    if (confidence) KCHECK(d_confidence.alloc(a->total));
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        wlabels_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
+                                                          (T)fill, d_label.p, d_confidence.p);
+    });
+    if (e == hipSuccess && label) e = hipMemcpy(label->data, d_label.p, a->total * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && confidence) e = hipMemcpy(confidence, d_confidence.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_wlabels_fused", e);
     return FROG_OK;
 }
 
@@ -1663,16 +2024,7 @@ int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_
     if (int rc = group_new(grid, total, device, a)) return rc;
     a->n_images = n_images;
     a->max_labels = max_labels ? max_labels : 1024;
-    int bits = 4;                                       // at least 16 slots, at least two per label
-    while (((size_t)1 << bits) < 2 * (size_t)a->max_labels) bits++;
-    const size_t slots = (size_t)1 << bits;
-    KCHECK(a->d_keys.alloc(slots));
-    KCHECK(a->d_index.alloc(slots));
-    KCHECK(a->d_values.alloc(a->max_labels));
-    KCHECK(a->d_state.alloc(2));
-    KCHECK(a->d_planes.alloc(a->max_labels));
-    a->map = LabelMap{ a->d_keys.p, a->d_index.p, a->d_values.p, a->d_state.p, (uint32_t)(slots - 1), 64 - bits, a->max_labels };
-    KCHECK(labels_reset_map(a.get()));
+    if (int rc = labels_new_map(a.get())) return rc;
     *out = a.release();
     return FROG_OK;
 }
@@ -1767,5 +2119,126 @@ int frog_labels_probability(frog_labels *a, int64_t value, float *p)
 }
 
 void frog_labels_destroy(frog_labels *a) { group_destroy(a); }
+
+int frog_wlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, uint32_t radius, uint32_t power, float floor,
+                        int device, frog_wlabels **out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_wlabels_create", grid, out, &total)) return rc;
+    if (!n_images) return fail(FROG_E_INVALID, "frog_wlabels_create: at least one image");
+    if (max_labels > 65536) return fail(FROG_E_INVALID, "frog_wlabels_create: max_labels above 65536");
+    if (radius < 1 || radius > 4) return fail(FROG_E_INVALID, "frog_wlabels_create: a radius from 1 to 4");
+    if (power < 1 || power > 8) return fail(FROG_E_INVALID, "frog_wlabels_create: a power from 1 to 8");
+    if (!(floor >= 0.0f && floor <= 1.0f)) return fail(FROG_E_INVALID, "frog_wlabels_create: a floor in [0, 1]");
+    std::unique_ptr<frog_wlabels> a;
+    if (int rc = group_new(grid, total, device, a)) return rc;
+    a->n_images = n_images;
+    a->max_labels = max_labels ? max_labels : 1024;
+    a->radius = radius;
+    a->power = power;
+    a->floor = floor;
+    KCHECK(a->d_target.alloc(total));
+    KCHECK(a->d_atlas.alloc(total));
+    if (int rc = labels_new_map(a.get())) return rc;
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_wlabels_target(frog_wlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+{
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_target");
+    if (a->has_target) return fail(FROG_E_INVALID, "frog_wlabels_target: the target is given once, before the first add");
+    if (int rc = add_inputs("frog_wlabels_target", a, c, src, resliced)) return rc;
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_voxel_type(src->dtype, [&](auto s) { return wlabels_target_typed<decltype(s)>(a, c, src, interpolation, background, resliced); });
+    if (rc == FROG_OK) a->has_target = true;
+    return rc;
+}
+
+int frog_wlabels_add(frog_wlabels *a, frog_chain *c, const frog_volume *image, const frog_volume *labels, int interpolation,
+                     double image_background, double label_background, frog_volume *resliced_image, frog_volume *resliced_labels)
+{
+    if (!a || !image || !image->data || !frog_volume_voxel_bytes(image->dtype) || !labels || !labels->data)
+        return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_add");
+    if (!integer_voxel_type(labels->dtype)) return fail(FROG_E_INVALID, "frog_wlabels_add: a label volume has an integer type");
+    if (!std::isfinite(image_background) || !std::isfinite(label_background)) return fail(FROG_E_INVALID, "frog_wlabels_add: background is not finite");
+    if (!a->has_target) return fail(FROG_E_INVALID, "frog_wlabels_add: before frog_wlabels_target");
+    if (a->finished || a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_wlabels_add: more atlases than n_images");
+    if (int rc = add_inputs("frog_wlabels_add", a, c, image, resliced_image)) return rc;
+    if (int rc = add_inputs("frog_wlabels_add", a, c, labels, resliced_labels)) return rc;
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_voxel_type(image->dtype, [&](auto s) {
+        return wlabels_add_typed<decltype(s)>(a, c, image, labels, interpolation, image_background, label_background, resliced_image, resliced_labels);
+    });
+    if (rc == FROG_OK) a->added++;
+    return rc;
+}
+
+int frog_wlabels_finish(frog_wlabels *a, uint32_t *n_labels)
+{
+    if (!a || !n_labels) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_finish");
+    if (a->added != a->n_images) return fail(FROG_E_INVALID, "frog_wlabels_finish: fewer atlases added than n_images");
+    if (a->finished) { *n_labels = (uint32_t)a->values.size(); return FROG_OK; }
+    KCHECK(hipSetDevice(a->device));
+    std::vector<uint32_t> order(a->known.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return a->known[x] < a->known[y]; });
+    std::vector<float *> sorted_planes;
+    a->values.clear();
+    for (const uint32_t i : order) {
+        a->values.push_back(a->known[i]);
+        sorted_planes.push_back(a->planes[i].p);
+    }
+    a->dense = order;
+    KCHECK(a->d_sorted_planes.alloc(order.size()));
+    KCHECK(a->d_sorted_values.alloc(order.size()));
+    KCHECK(hipMemcpy(a->d_sorted_planes.p, sorted_planes.data(), order.size() * sizeof(float *), hipMemcpyHostToDevice));
+    KCHECK(hipMemcpy(a->d_sorted_values.p, a->values.data(), order.size() * sizeof(long long), hipMemcpyHostToDevice));
+    a->finished = true;
+    *n_labels = (uint32_t)order.size();
+    return FROG_OK;
+}
+
+int frog_wlabels_values(frog_wlabels *a, int64_t *values)
+{
+    if (!a || !values) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_values");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_wlabels_values: before frog_wlabels_finish");
+    for (size_t l = 0; l < a->values.size(); l++) values[l] = a->values[l];
+    return FROG_OK;
+}
+
+int frog_wlabels_fused(frog_wlabels *a, int64_t fill_label, frog_volume *label, float *confidence)
+{
+    if (!a || (!label && !confidence) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_fused");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_wlabels_fused: before frog_wlabels_finish");
+    if (label) {
+        if (!integer_voxel_type(label->dtype)) return fail(FROG_E_INVALID, "frog_wlabels_fused: the fused map has an integer type");
+        if (!grid_sized(a, label)) return fail(FROG_E_INVALID, "frog_wlabels_fused: the fused map is not grid-sized");
+    }
+    KCHECK(hipSetDevice(a->device));
+    return with_integer_voxel_type(label ? label->dtype : FROG_V_I32, [&](auto t) {
+        return wlabels_fused_typed<decltype(t)>(a, label ? (long long)fill_label : 0, label, confidence);
+    });
+}
+
+int frog_wlabels_probability(frog_wlabels *a, int64_t value, float *p)
+{
+    if (!a || !p) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_probability");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_wlabels_probability: before frog_wlabels_finish");
+    const auto it = std::lower_bound(a->values.begin(), a->values.end(), (long long)value);
+    if (it == a->values.end() || *it != (long long)value) return fail(FROG_E_INVALID, "frog_wlabels_probability: no such label in the table");
+    KCHECK(hipSetDevice(a->device));
+    frog::DevBuf<float> d_p;
+    KCHECK(d_p.alloc(a->total));
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        wlabels_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, (uint32_t)a->values.size(), (uint32_t)(it - a->values.begin()),
+                                                             a->total, d_p.p);
+    });
+    if (e == hipSuccess) e = hipMemcpy(p, d_p.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_wlabels_probability", e);
+    return FROG_OK;
+}
+
+void frog_wlabels_destroy(frog_wlabels *a) { group_destroy(a); }
 
 }

@@ -41,18 +41,6 @@
 
 namespace {
 
-// the lines of a list file (FROG.py -m's format: one path per line), without their line ends; blank lines are dropped
-bool read_list(const std::string &path, std::vector<std::string> &lines)
-{
-    std::ifstream f(path);
-    if (!f) return false;
-    for (std::string line; std::getline(f, line);) {
-        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
-        if (!line.empty()) lines.push_back(line);
-    }
-    return true;
-}
-
 // the median of a non-empty list: the middle value, or the mean of the middle two
 double median(std::vector<double> v)
 {

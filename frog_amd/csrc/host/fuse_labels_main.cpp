@@ -27,22 +27,6 @@
 #include <string>
 #include <vector>
 
-namespace {
-
-// the first of u8, u16, i16, i32, u32 that holds every value; -1 if none does
-int fused_type(const std::vector<int64_t> &values)
-{
-    int64_t lo = 0, hi = 0;
-    if (!values.empty()) { lo = values.front(); hi = values.back(); }         // ascending
-    const struct { int dtype; int64_t lo, hi; } types[] = {
-        { FROG_V_U8, 0, 255 }, { FROG_V_U16, 0, 65535 }, { FROG_V_I16, -32768, 32767 },
-        { FROG_V_I32, -2147483647LL - 1, 2147483647LL }, { FROG_V_U32, 0, 4294967295LL } };
-    for (const auto &t : types) if (t.lo <= lo && hi <= t.hi) return t.dtype;
-    return -1;
-}
-
-} // namespace
-
 int main(int argc, char *argv[])
 {
     PhaseTimes times;

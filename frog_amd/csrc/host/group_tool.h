@@ -1,5 +1,5 @@
 // group_tool.h -- what the tools over a registered group (AverageImage, FuseLabels) share: leaving on an error, the header
-// peek, the positional arguments, one inverted chain per image from <transformsDir>/<i>.json, the first output lines, the
+// peek, the positional arguments, a list file's lines, a fused map's type, one inverted chain per image from <transformsDir>/<i>.json, the first output lines, the
 // resliced volume an add hands back and its file, the phase timers and the lines that close the run.  Each tool keeps its own
 // flags, validation and outputs.  AverageVolumes takes `die` from here.
 #ifndef FROG_GROUP_TOOL_H
@@ -77,6 +77,31 @@ inline int positional_arguments(int argc, char *argv[], int first, std::initiali
     int a = first;
     for (; a < argc && !is_flag(argv[a]); a++) positional.push_back(argv[a]);
     return a;
+}
+
+// the lines of a list file (FROG.py -m's format: one path per line), without their line ends; blank lines are dropped
+inline bool read_list(const std::string &path, std::vector<std::string> &lines)
+{
+    std::ifstream f(path);
+    if (!f) return false;
+    for (std::string line; std::getline(f, line);) {
+        while (!line.empty() && (line.back() == '\r' || line.back() == ' ' || line.back() == '\t')) line.pop_back();
+        if (!line.empty()) lines.push_back(line);
+    }
+    return true;
+}
+
+// The type of a fused label map: the first of u8, u16, i16, i32, u32 that holds every one of the ascending `values`; -1 if none
+// does.
+inline int fused_type(const std::vector<int64_t> &values)
+{
+    int64_t lo = 0, hi = 0;
+    if (!values.empty()) { lo = values.front(); hi = values.back(); }
+    const struct { int dtype; int64_t lo, hi; } types[] = {
+        { FROG_V_U8, 0, 255 }, { FROG_V_U16, 0, 65535 }, { FROG_V_I16, -32768, 32767 },
+        { FROG_V_I32, -2147483647LL - 1, 2147483647LL }, { FROG_V_U32, 0, 4294967295LL } };
+    for (const auto &t : types) if (t.lo <= lo && hi <= t.hi) return t.dtype;
+    return -1;
 }
 
 // <transformsDir>/<i>.json of each of n images, read (`transforms` owns the files from here on) and inverted: every image

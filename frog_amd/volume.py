@@ -382,3 +382,98 @@ def fuse_labels(volumes, chains=None, grid=None, background=0.0, max_labels=0, d
         return labels, agreement, values, group_dice(voxels, pairs, len(vols))
     finally:
         acc.close()
+
+
+class WeightedLabels(_Accumulator):
+    """frog_wlabels (include/frog_chain.h): locally weighted label fusion.  The target image first, then n_images atlases
+    (image + label map through one chain) on `grid` = (dims(x, y, z), origin, spacing); every atlas votes for its label with
+    the local normalised cross-correlation between its image and the target over a (2 radius + 1)^3 patch, raised to
+    `power` and at least `floor`.  Then the fused map, its confidence and per-label probabilities."""
+
+    _NAME = "wlabels"
+
+    def __init__(self, grid, n_images, max_labels=0, radius=2, power=2, floor=2.0 ** -10, device=0):
+        self.n_images = int(n_images)
+        self._n_labels = None
+        super().__init__(grid, self.n_images, int(max_labels), int(radius), int(power), float(floor), int(device))
+
+    def target(self, volume, chain=None, interpolation=1, background=0.0, resliced=False):
+        """The image to segment ((voxels, origin, spacing) or an array already on the grid when chain is None), once, before
+        the first add; with a chain (frog_amd.chain.Chain, grid space -> volume space) it is resliced as Chain.reslice does.
+        resliced=True returns that volume (source dtype, shape dims[::-1])."""
+        _, src, _, ov, out = self._views(volume, None, resliced)
+        _abi.check(self._lib.frog_wlabels_target(self._h, chain._h if chain is not None else None, src, int(interpolation),
+                                                 float(background), ov), "frog_wlabels_target")
+        return out
+
+    def add(self, image, labels, chain=None, interpolation=1, image_background=0.0, label_background=0.0, resliced=False):
+        """One atlas: `image` and the integer label map `labels` (each (voxels, origin, spacing) with its own geometry, or an
+        array already on the grid when chain is None) through one chain.  resliced=True returns (image, labels) as
+        Chain.reslice gives them (the labels with nearest-neighbour interpolation)."""
+        _, src, _, ov, out = self._views(image, None, resliced)
+        _, lsrc, _, lv, lout = self._views(labels, None, resliced)
+        _abi.check(self._lib.frog_wlabels_add(self._h, chain._h if chain is not None else None, src, lsrc, int(interpolation),
+                                              float(image_background), float(label_background), ov, lv), "frog_wlabels_add")
+        return (out, lout) if resliced else None
+
+    def finish(self):
+        """The number of distinct labels, after exactly n_images adds."""
+        n = C.c_uint32()
+        _abi.check(self._lib.frog_wlabels_finish(self._h, C.byref(n)), "frog_wlabels_finish")
+        self._n_labels = int(n.value)
+        return self._n_labels
+
+    def values(self):
+        """The distinct label values, int64 ascending."""
+        values = np.empty(self._n_labels or 0, np.int64)
+        _abi.check(self._lib.frog_wlabels_values(self._h, values.ctypes.data_as(C.POINTER(C.c_int64))), "frog_wlabels_values")
+        return values
+
+    def fused(self, dtype=None, fill_label=0):
+        """(labels, confidence): per voxel the label with the largest score (ties: the smallest value) as `dtype`, default
+        the first of uint8, uint16, int16, int32, uint32 that holds every label and `fill_label`; float32 share of the
+        voxel's total score that went to it.  Where no weight arrived: `fill_label`, confidence 0."""
+        if dtype is None:
+            dtype = fused_dtype(list(self.values()) + [int(fill_label)])
+            if dtype is None:
+                raise ValueError("no integer type of at most 32 bits holds every label value")
+        labels = np.empty(self.dims[::-1], np.dtype(dtype))
+        confidence = np.empty(self.dims[::-1], np.float32)
+        lv = _abi.volume_view(labels, tuple(self._grid.origin), tuple(self._grid.spacing))
+        _abi.check(self._lib.frog_wlabels_fused(self._h, int(fill_label), C.byref(lv), confidence.ctypes.data_as(_abi.c_float_p)),
+                   "frog_wlabels_fused")
+        return labels, confidence
+
+    def probability(self, value):
+        """float32 share of the voxel's total score that label `value` holds; 0 where no weight arrived."""
+        p = np.empty(self.dims[::-1], np.float32)
+        _abi.check(self._lib.frog_wlabels_probability(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), "frog_wlabels_probability")
+        return p
+
+
+def atlas_segment(target, images, label_maps, chains=None, target_chain=None, grid=None, radius=2, power=2, floor=2.0 ** -10,
+                  interpolation=1, image_backgrounds=None, label_background=0.0, fill_label=0, max_labels=0, device=0):
+    """Multi-atlas segmentation of `target` by locally weighted voting (bin/AtlasSegment).  `images`, `chains` and `grid` as
+    in average(); `label_maps`: one integer volume per image, with its own geometry; `target_chain`: None (the target is on
+    the grid) or the Chain from grid space to the target's; `image_backgrounds`: None (each volume's minimum, the target's
+    included), a number or one per image.  Returns (labels, confidence, values): the fused map in the grid's space, the
+    float32 share of each voxel's score that its label holds, and the distinct label values in ascending order."""
+    vols, grid = _group(images, chains, None, grid)
+    labels = [_as_volume(v) for v in label_maps]
+    if len(labels) != len(vols):
+        raise ValueError("one label map per image expected")
+    tgt = _as_volume(target)
+    if image_backgrounds is None:
+        image_backgrounds = [float(a.min()) for a, _, _ in vols]
+    elif np.ndim(image_backgrounds) == 0:
+        image_backgrounds = [float(image_backgrounds)] * len(vols)
+    acc = WeightedLabels(grid, len(vols), max_labels, radius, power, floor, device)
+    try:
+        acc.target(tgt, target_chain, interpolation, float(tgt[0].min()))
+        for k, v in enumerate(vols):
+            acc.add(v, labels[k], None if chains is None else chains[k], interpolation, image_backgrounds[k], label_background)
+        acc.finish()
+        fused, confidence = acc.fused(None, fill_label)
+        return fused, confidence, acc.values()
+    finally:
+        acc.close()

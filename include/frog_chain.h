@@ -270,6 +270,77 @@ int  frog_labels_fused(frog_labels *a, frog_volume *label, float *agreement);
 int  frog_labels_probability(frog_labels *a, int64_t value, float *p);
 void frog_labels_destroy(frog_labels *a);
 
+/* ---- locally weighted label fusion: a target image segmented from a registered group (an extension; Artaechevarria et al.,
+ * IEEE TMI 28(8), 2009: every atlas votes for its label with a weight that grows with its local similarity to the target) ------
+ * An accumulator of n_images atlases on `grid` (dims, origin, spacing; its dtype and data are ignored).  An atlas is an image
+ * and an integer label map that go through one chain; its vote at voxel v goes to the label it has there, weighted by the
+ * normalised cross-correlation between its resliced image and the resliced target over the patch of v:
+ * score[label][v], f32, one device thread per voxel in every plane, atlases in call order.  Every floating-point line below
+ * is one separately rounded operation; there is no floating-point atomic and the results are the same bits from run to run
+ * and however the work is cut into launches.
+ * radius 1..4: the patch is (2 radius + 1)^3 voxels; power 1..8; floor in [0, 1]: the least similarity an atlas is credited
+ * with.  max_labels (0: 1024, at most 65536) bounds the distinct label values.  Device memory: one f32 plane of 4 x the grid's
+ * voxels per distinct label value, two f32 staging planes of the same size (the target and the current atlas image), and
+ * the staging of the current image, label map and their resliced volumes.
+ * FROG_E_INVALID, before the device is touched: a NULL argument, an empty grid or one above 2^31 voxels, n_images == 0,
+ * max_labels > 65536, radius == 0 or > 4, power == 0 or > 8, floor outside [0, 1] or NaN. */
+typedef struct frog_wlabels frog_wlabels;
+int  frog_wlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels,
+                         uint32_t radius, uint32_t power, float floor, int device, frog_wlabels **out);
+/* The image to segment: exactly once, before the first add (a second call, or one after an add -> FROG_E_INVALID).  `source`
+ * has any of the eight types.  Per grid voxel v, t[v] = (float)r, r the voxel frog_chain_reslice(chain, source, out,
+ * interpolation, background) stores (the same device code, in the source's type, as in frog_cover_add), and validT[v] iff
+ * the position after the chain passes the reslice's inside test against the source (-0.5 <= c <= dims - 0.5 on every axis;
+ * NaN fails) and t[v] is finite.  chain == NULL: the source's dims must equal the grid's, every voxel is inside, and valid
+ * where t[v] is finite.  `resliced` (may be NULL; dims the grid's, dtype the source's) receives r for every voxel, valid or
+ * not (without a chain: the source), and is the only place `background` shows.  A chain on another device, bad geometry ->
+ * FROG_E_INVALID. */
+int  frog_wlabels_target(frog_wlabels *a, frog_chain *chain, const frog_volume *source,
+                         int interpolation, double background, frog_volume *resliced);
+/* One atlas.  The chain is evaluated once per voxel for both volumes.  `image` (any of the eight types) gives a[v] = (float)r
+ * and validA[v] exactly as the target's t[v] and validT[v].  `labels` (one of the six integer types; its own dims, origin and
+ * spacing) gives label[v], the voxel frog_chain_reslice(chain, labels, out, 0, label_background) stores (nearest neighbour)
+ * at the same position after the chain; the label background is a label like any other.  chain == NULL: both volumes have
+ * the grid's dims.  `resliced_image` and `resliced_labels` (each may be NULL; dims the grid's, dtype their source's) receive
+ * the two resliced volumes, as frog_chain_reslice gives them.
+ *   member[u] = validT[u] && validA[u]
+ *   patch(v)  = the grid voxels u with |u - v| <= radius on all three axes (voxels outside the grid do not exist) that
+ *               are members
+ *   six f64 sums, each from +0.0, over patch(v) with z ascending, then y, then x, T = (double)t[u], A = (double)a[u]:
+ *               n += 1;  st += T;  sa += A;  stt += T * T;  saa += A * A;  sta += T * A
+ *   cov = n * sta - st * sa;  vt = n * stt - st * st;  va = n * saa - sa * sa                      (f64)
+ *   if n >= 2 and vt > 0 and va > 0 and cov > 0:
+ *               q = (float)((cov * cov) / (vt * va));  c = sqrtf(q);  c = min(c, 1.0f) if c is finite
+ *   else        c = 0
+ *   c = max(c, floor)
+ *   w = c;  then power - 1 times  w = w * c                                                         (f32)
+ *   if member[v]:  score[label[v]][v] = score[label[v]][v] + w                                       (f32)
+ * A voxel that is no member gets no vote from this atlas.  With floor == 1 every weight is exactly 1: the majority vote over
+ * the atlases that cover the voxel together with the target.
+ * FROG_E_INVALID, before any device work: a NULL argument, a float label volume, a background that is not finite, an add
+ * before the target, more than n_images adds, a chain on another device, bad geometry.  An atlas whose label map (all grid
+ * voxels of it, members or not) would bring the number of distinct labels above max_labels is refused with FROG_E_INVALID
+ * (the message names the limit), a refused device allocation with FROG_E_NOMEM: either way the atlas leaves no vote and no
+ * label behind, the call does not count as one of the n_images, and another atlas may be added in its place. */
+int  frog_wlabels_add(frog_wlabels *a, frog_chain *chain, const frog_volume *image, const frog_volume *labels,
+                      int interpolation, double image_background, double label_background,
+                      frog_volume *resliced_image, frog_volume *resliced_labels);
+/* After exactly n_images adds (else FROG_E_INVALID): the number of distinct label values the atlases' resliced label maps
+ * hold, whether or not a vote reached them.  The four getters below are valid only after it (FROG_E_INVALID before). */
+int  frog_wlabels_finish(frog_wlabels *a, uint32_t *n_labels);
+int  frog_wlabels_values(frog_wlabels *a, int64_t *values);            /* ascending, signed */
+/* total[v] = the f32 sum of score[l][v] over the labels in ascending signed order of their values, from +0.0.  The fused
+ * label is the first value in that order whose score is strictly larger than every earlier one and > 0, stored as
+ * label->dtype (any of the six integer types; dims the grid's); confidence[v] = score_winner / total, one f32 division.
+ * Where total == 0 (no atlas covers the voxel together with the target, or every weight there is 0) the label is fill_label
+ * and the confidence 0.  Either output may be NULL, not both.  A table value or fill_label that does not fit label->dtype ->
+ * FROG_E_INVALID and nothing is written. */
+int  frog_wlabels_fused(frog_wlabels *a, int64_t fill_label, frog_volume *label, float *confidence);
+/* p[v] = score[value][v] / total[v], one f32 division; 0 where total == 0.  A value that is not in the table ->
+ * FROG_E_INVALID. */
+int  frog_wlabels_probability(frog_wlabels *a, int64_t value, float *p);
+void frog_wlabels_destroy(frog_wlabels *a);
+
 #ifdef __cplusplus
 }
 #endif
