@@ -53,13 +53,13 @@ def usable_cpus():
 
 def device_source_hash():
     """sha256 (first 16 hex digits) over the HIP sources of the registration kernels (everything under csrc/device
-    except the matcher, the transform chains and the collectives library), in name order: what a PMC measurement under
+    except the matcher, the transform chains with their rank kernels and the collectives library), in name order: what a PMC measurement under
     profiles/ is keyed on, so that bench.py can tell when the kernels have changed since."""
     import hashlib
     d = os.path.join(_HERE, "csrc", "device")
     h = hashlib.sha256()
     for name in sorted(os.listdir(d)):
-        if name.endswith((".hip", ".h")) and name not in ("comm.hip", "match.hip", "chain.hip"):
+        if name.endswith((".hip", ".h")) and name not in ("comm.hip", "match.hip", "chain.hip", "k_rank.hip.h"):
             h.update(name.encode())
             with open(os.path.join(d, name), "rb") as fh:
                 h.update(fh.read())
@@ -212,6 +212,9 @@ def grid_triplet(origin, spacing, dims):
     return (C.c_double * 3)(*origin), (C.c_double * 3)(*spacing), (C.c_uint32 * 3)(*dims)
 
 
+FROG_RANK_MAX_IMAGES = 4096         # include/frog_chain.h: the capacity of frog_rank's sort kernels
+
+
 class FrogScoreSums(C.Structure):
     """frog_score_sums (include/frog_chain.h)."""
     _fields_ = [("n", C.c_uint64), ("n_nonfinite", C.c_uint64), ("sx", C.c_double), ("sy", C.c_double), ("sxx", C.c_double),
@@ -295,6 +298,12 @@ HIP_SYMBOLS = {
                                    C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_float, C.POINTER(FrogScoreSums),
                                    C.POINTER(C.c_uint64)]),
     "frog_cover_destroy": (None, [C.c_void_p]),
+    "frog_rank_planes": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
+    "frog_rank_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "frog_rank_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double]),
+    "frog_rank_finish": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_double), c_float_p, c_float_p,
+                                   C.POINTER(C.c_uint16)]),
+    "frog_rank_destroy": (None, [C.c_void_p]),
     "frog_labels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_labels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
     "frog_labels_finish": (C.c_int, [C.c_void_p, c_u32_p]),

@@ -1042,6 +1042,8 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
     p[idx] = sum != 0.0f ? score / sum : 0.0f;
 }
 
+#include "k_rank.hip.h"
+
 } // namespace
 
 struct frog_chain {
@@ -1066,13 +1068,24 @@ struct frog_average : frog_group {
     frog::DevBuf<float> d_avg, d_sq;
 };
 
+// an accumulator whose adds take a mask (frog_cover, frog_rank)
+struct frog_masked : frog_group {
+    frog::DevBuf<unsigned char> d_mask;             // staging of the current u8 mask, grown on demand
+    std::vector<unsigned char> h_mask;              // the mask as value != 0, before its upload
+};
+
 // running mean, squared deviations and count of the images that cover each voxel of one grid
-struct frog_cover : frog_group {
+struct frog_cover : frog_masked {
     uint32_t added = 0;
     frog::DevBuf<float> d_mean, d_m2;
     frog::DevBuf<uint16_t> d_count;
-    frog::DevBuf<unsigned char> d_mask;             // staging of the current u8 mask, grown on demand
-    std::vector<unsigned char> h_mask;              // the mask as value != 0, before its upload
+};
+
+// one plane of sort keys per added image over a window of z-planes of one grid
+struct frog_rank : frog_masked {
+    uint32_t n_images = 0, added = 0;
+    size_t first = 0, window = 0;                   // the window's first voxel in the grid, and its voxels
+    frog::DevBuf<uint32_t> d_keys;                  // n_images planes of `window` keys, in the order of the adds
 };
 
 // vote counts of a group's label maps on one grid
@@ -1359,9 +1372,9 @@ int average_add_typed(frog_average *a, frog_chain *c, const frog_volume *src, in
     return return_resliced<S>("frog_average_add", a, c, src, resliced, e);
 }
 
-// cover's part of the staging step: the mask of an add or a score, which cover_mask left as bytes in a->h_mask, on the
-// device; a null pointer without one
-int cover_stage_mask(const char *where, frog_cover *a, const frog_volume *mask, const uint8_t **d_mask)
+// the masked accumulators' part of the staging step: the mask of an add or a score, which cover_mask left as bytes in
+// a->h_mask, on the device; a null pointer without one
+int cover_stage_mask(const char *where, frog_masked *a, const frog_volume *mask, const uint8_t **d_mask)
 {
     *d_mask = nullptr;
     if (!mask) return FROG_OK;
@@ -1440,7 +1453,7 @@ int cover_score_typed(frog_cover *a, frog_chain *c, const frog_volume *src, cons
 }
 
 // the mask of an add or a score as bytes, value != 0, in a->h_mask
-void cover_mask(frog_cover *a, const frog_volume *mask)
+void cover_mask(frog_masked *a, const frog_volume *mask)
 {
     with_integer_voxel_type(mask->dtype, [&](auto m) {
         const size_t n = voxel_count(mask);
@@ -1451,8 +1464,8 @@ void cover_mask(frog_cover *a, const frog_volume *mask)
     });
 }
 
-// what frog_cover_add and frog_cover_score refuse alike: add_inputs, then what concerns the mask
-int cover_inputs(const char *where, const frog_cover *a, const frog_chain *c, const frog_volume *src, const frog_volume *mask,
+// what frog_cover_add, frog_cover_score and frog_rank_add refuse alike: add_inputs, then what concerns the mask
+int cover_inputs(const char *where, const frog_masked *a, const frog_chain *c, const frog_volume *src, const frog_volume *mask,
                  const frog_volume *resliced)
 {
     if (int rc = add_inputs(where, a, c, src, resliced)) return rc;
@@ -1723,6 +1736,59 @@ void group_destroy(A *a)
     if (!a) return;
     (void)hipSetDevice(a->device);
     delete a;
+}
+
+// frog_rank_add for a source of type S: cover_add_typed with the key store, over the window
+template <class S>
+int rank_add_typed(frog_rank *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
+{
+    ResliceGrid g;
+    const uint8_t *d_mask;
+    if (int rc = stage_source<S>("frog_rank_add", a, src, false, interpolation, background, &g)) return rc;
+    if (int rc = cover_stage_mask("frog_rank_add", a, mask, &d_mask)) return rc;
+    const MaskGrid mg = mask_grid(mask);
+    const S *d_src = (const S *)a->d_src.p;
+    uint32_t *plane = a->d_keys.p + (size_t)a->added * a->window;
+    const hipError_t e = chunked_launch(a->window, [&](unsigned blocks, size_t base) {
+        if (c)
+            rank_reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg, plane);
+        else
+            rank_identity_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, d_src, d_mask, plane);
+    });
+    return return_resliced<S>("frog_rank_add", a, c, src, nullptr, e);
+}
+
+// The finish kernels over the window: the register tier for up to RANK_REG_MAX planes, one work-item per voxel; above it the
+// LDS tier, one block per tile of RANK_LDS_KEYS / P voxels.  P is the smallest of the padded sizes that holds the planes.
+hipError_t rank_finish_launch(const frog_rank *a, const RankFinish &f)
+{
+    const uint32_t *keys = a->d_keys.p;
+    auto reg = [&](auto kernel) {
+        return chunked_launch(f.window, [&](unsigned blocks, size_t base) { kernel<<<blocks, LAUNCH_BLOCK>>>(base, keys, f); });
+    };
+    auto lds = [&](auto kernel, size_t padded) {
+        const size_t per_tile = RANK_LDS_KEYS / padded, tiles = (f.window + per_tile - 1) / per_tile;
+        return chunked_launch(tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) { kernel<<<blocks, LAUNCH_BLOCK>>>(base, keys, f); });
+    };
+    if (f.n <= 8) return reg(rank_finish_reg_kernel<8>);
+    if (f.n <= 16) return reg(rank_finish_reg_kernel<16>);
+    if (f.n <= 32) return reg(rank_finish_reg_kernel<32>);
+    if (f.n <= RANK_REG_MAX) return reg(rank_finish_reg_kernel<64>);
+    if (f.n <= 128) return lds(rank_finish_lds_kernel<128>, 128);
+    if (f.n <= 256) return lds(rank_finish_lds_kernel<256>, 256);
+    if (f.n <= 512) return lds(rank_finish_lds_kernel<512>, 512);
+    if (f.n <= 1024) return lds(rank_finish_lds_kernel<1024>, 1024);
+    if (f.n <= 2048) return lds(rank_finish_lds_kernel<2048>, 2048);
+    return lds(rank_finish_lds_kernel<4096>, 4096);
+}
+
+// what frog_rank_planes and frog_rank_create refuse alike without asking for a device
+int rank_arguments(const char *where, const frog_volume *grid, uint32_t n_images, const void *out, size_t *total)
+{
+    if (int rc = group_arguments(where, grid, out, total)) return rc;
+    if (!n_images || n_images > FROG_RANK_MAX_IMAGES)
+        return fail(FROG_E_INVALID, std::string(where) + ": 1 to " + std::to_string(FROG_RANK_MAX_IMAGES) + " images");
+    return FROG_OK;
 }
 
 } // namespace
@@ -2013,6 +2079,85 @@ int frog_cover_finish(frog_cover *a, uint32_t min_count, float fill, float *mean
 }
 
 void frog_cover_destroy(frog_cover *a) { group_destroy(a); }
+
+int frog_rank_planes(const frog_volume *grid, uint32_t n_images, int device, uint32_t *planes)
+{
+    size_t total;
+    if (int rc = rank_arguments("frog_rank_planes", grid, n_images, planes, &total)) return rc;
+    if (int rc = select_device(device)) return rc;
+    size_t free_bytes = 0, device_bytes = 0;
+    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
+    const size_t plane_bytes = (size_t)grid->dims[0] * grid->dims[1] * sizeof(uint32_t) * n_images;
+    const size_t fit = free_bytes / 2 / plane_bytes;
+    if (!fit) return fail(FROG_E_INVALID, "frog_rank_planes: not one plane of the grid fits half of the free device memory");
+    *planes = (uint32_t)std::min<size_t>(fit, grid->dims[2]);
+    return FROG_OK;
+}
+
+int frog_rank_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_planes, uint32_t n_images, int device, frog_rank **out)
+{
+    size_t total;
+    if (int rc = rank_arguments("frog_rank_create", grid, n_images, out, &total)) return rc;
+    if (!n_planes || first_plane >= grid->dims[2] || n_planes > grid->dims[2] - first_plane)
+        return fail(FROG_E_INVALID, "frog_rank_create: the window lies outside the grid or is empty");
+    std::unique_ptr<frog_rank> a;
+    if (int rc = group_new(grid, total, device, a)) return rc;
+    const size_t plane = (size_t)grid->dims[0] * grid->dims[1];
+    a->n_images = n_images;
+    a->first = plane * first_plane;
+    a->window = plane * n_planes;
+    KCHECK(a->d_keys.alloc((size_t)n_images * a->window));
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_rank_add(frog_rank *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
+{
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_rank_add");
+    if (a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_rank_add: more volumes than the accumulator was created for");
+    if (int rc = cover_inputs("frog_rank_add", a, c, src, mask, nullptr)) return rc;
+    if (mask) cover_mask(a, mask);
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_voxel_type(src->dtype, [&](auto s) { return rank_add_typed<decltype(s)>(a, c, src, mask, interpolation, background); });
+    if (rc == FROG_OK) a->added++;
+    return rc;
+}
+
+int frog_rank_finish(frog_rank *a, uint32_t min_count, float fill, uint32_t n_q, const double *q, float *quantiles, float *mad, uint16_t *count)
+{
+    if (!a || n_q > RANK_MAX_Q || (n_q && !q)) return fail(FROG_E_INVALID, "bad arguments to frog_rank_finish");
+    if (!min_count) return fail(FROG_E_INVALID, "frog_rank_finish: min_count must be at least 1");
+    for (uint32_t j = 0; j < n_q; j++)
+        if (!(q[j] >= 0.0 && q[j] <= 1.0)) return fail(FROG_E_INVALID, "frog_rank_finish: a probability lies in [0, 1]");
+    if (!quantiles) n_q = 0;
+    if (!n_q && !mad && !count) return fail(FROG_E_INVALID, "frog_rank_finish: no output asked for");
+    if (!a->added) return fail(FROG_E_INVALID, "frog_rank_finish: before the first frog_rank_add");
+    KCHECK(hipSetDevice(a->device));
+    frog::DevBuf<float> d_q, d_mad;
+    frog::DevBuf<uint16_t> d_count;
+    if (n_q) KCHECK(d_q.alloc((size_t)n_q * a->window));
+    if (mad) KCHECK(d_mad.alloc(a->window));
+    if (count) KCHECK(d_count.alloc(a->window));
+    RankFinish f{};
+    f.window = a->window;
+    f.n = a->added;
+    f.min_count = min_count;
+    f.fill = fill;
+    f.n_q = n_q;
+    f.sort = n_q || mad;
+    for (uint32_t j = 0; j < n_q; j++) f.q[j] = q[j];
+    f.quantiles = d_q.p;
+    f.mad = d_mad.p;
+    f.count = d_count.p;
+    hipError_t e = rank_finish_launch(a, f);
+    if (e == hipSuccess && n_q) e = hipMemcpy(quantiles, d_q.p, (size_t)n_q * a->window * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && mad) e = hipMemcpy(mad, d_mad.p, a->window * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count) e = hipMemcpy(count, d_count.p, a->window * sizeof(uint16_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_rank_finish", e);
+    return FROG_OK;
+}
+
+void frog_rank_destroy(frog_rank *a) { group_destroy(a); }
 
 int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_labels **out)
 {

@@ -3,6 +3,7 @@
 // without N + 2 HIP runtime starts.
 //   AverageImage bbox.json spacing v_0 ... v_{N-1} [-td transformsDir] [-o outDir] [-i interpolation] [-b background]
 //                [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]] [-q 1 [-qb bins] [-qr lo hi]]
+//                [-r 1 [-rq q1,q2,...] [-rp planes]]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid); image i is resliced through the inverse of <transformsDir>/<i>.json
 // (default "transforms"; -j and sidecar forms) exactly as `VolumeTransform v_i dummy.mhd -t transforms/i.json` does it
 // (same device code; background = the image's minimum unless -b, linear unless -i 0), converted to its own type and added
@@ -25,6 +26,15 @@
 // nan.  -qb: bins per axis of the joint histogram behind mi and nmi (2..64, default 64).  -qr lo hi: its value range, by
 // default the smallest finite value of the mean over the voxels that minCount images cover and the float after the largest;
 // the range used is printed.  The average's files and the first pass are the same with and without -q 1.
+// -r 1 (with -c 1; the robust atlas): after the average is written, and after the -q 1 pass if there is one, the images and
+// masks are streamed again, once per slab of z-planes, and every image's value is kept per voxel (frog_rank_add) under the
+// validity rule of -c 1; median.nii.gz and mad.nii.gz (FLOAT32) are then the per-voxel median and the raw median absolute
+// deviation (x 1.4826 for a normal stdev) over the covering images whose value is not NaN.  -rq: up to 15 probabilities in
+// [0, 1], comma-separated; each gives quantile_<text as typed>.nii.gz (linear interpolation between the neighbouring order
+// statistics).  -mc and -f apply as they do to the mean (the MAD is 0 where the mean is the fill).  A slab is as many planes
+// as frog_rank_planes allows (half of the free device memory at 4 bytes per image and voxel), or -rp planes if that is
+// fewer; the slab count is printed and changes no bit of the files.  -rq or -rp without -r 1 is an error; every other file
+// is the same with and without -r 1.
 #include "group_tool.h"
 #include "volume_stream.h"
 
@@ -58,6 +68,23 @@ std::string csv_double(double v)
     return buf;
 }
 
+// -rq's list: up to 15 comma-separated probabilities in [0, 1], each kept as typed for its file name
+void parse_quantiles(const std::string &list, std::vector<std::string> &texts, std::vector<double> &values)
+{
+    for (size_t at = 0; at <= list.size();) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string text = list.substr(at, comma - at);
+        char *end = nullptr;
+        const double q = std::strtod(text.c_str(), &end);
+        if (text.empty() || *end || !(q >= 0.0 && q <= 1.0))
+            die("-rq takes comma-separated probabilities in [0, 1], not '" + text + "'");
+        texts.push_back(text);
+        values.push_back(q);
+        at = comma + 1;
+    }
+    if (values.size() > 15) die("-rq takes at most 15 probabilities");
+}
+
 } // namespace
 
 int main(int argc, char *argv[])
@@ -65,13 +92,15 @@ int main(int argc, char *argv[])
     PhaseTimes times;
     std::vector<std::string> volumes;
     std::string transformsDir = "transforms", outDir = ".", maskList;
-    int interpolation = 1, device = 0, writeTransformed = 0, coverage = 0, quality = 0;
-    long minCount = 1, qualityBins = 64;
+    int interpolation = 1, device = 0, writeTransformed = 0, coverage = 0, quality = 0, robust = 0;
+    long minCount = 1, qualityBins = 64, robustPlanes = 0;
     float fill = 0, qualityLo = 0, qualityHi = 0;
     bool qualityOption = false, qualityRange = false;       // -qb or -qr was given; -qr was given
     bool coverageOption = false;                            // -ml, -mc or -f was given
+    bool robustListOption = false, robustPlanesOption = false;  // -rq was given; -rp was given
+    std::string robustList;
     BackgroundLevel background;
-    int a = positional_arguments(argc, argv, 3, { "-td", "-o", "-i", "-b", "-wt", "-dev", "-c", "-ml", "-mc", "-f", "-q", "-qb", "-qr" }, volumes);
+    int a = positional_arguments(argc, argv, 3, { "-td", "-o", "-i", "-b", "-wt", "-dev", "-c", "-ml", "-mc", "-f", "-q", "-qb", "-qr", "-r", "-rq", "-rp" }, volumes);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
         if (std::strcmp(key, "-td") == 0) transformsDir = value;
@@ -92,11 +121,15 @@ int main(int argc, char *argv[])
             qualityOption = qualityRange = true;
             a++;
         }
+        else if (std::strcmp(key, "-r") == 0) robust = atoi(value);
+        else if (std::strcmp(key, "-rq") == 0) { robustList = value; robustListOption = true; }
+        else if (std::strcmp(key, "-rp") == 0) { robustPlanes = atol(value); robustPlanesOption = true; }
         else die(std::string("unknown option ") + key);
     }
     if (argc < 4 || volumes.empty()) {
         std::cout << "Usage : AverageImage bbox.json spacing image_0 ... image_N-1 [-td transformsDir] [-o outDir] [-i interpolation] "
-                     "[-b background] [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]] [-q 1 [-qb bins] [-qr lo hi]]" << std::endl;
+                     "[-b background] [-wt 1] [-dev n] [-c 1 [-ml masks.txt] [-mc minCount] [-f fill]] [-q 1 [-qb bins] [-qr lo hi]] "
+                     "[-r 1 [-rq q1,q2,...] [-rp planes]]" << std::endl;
         return 1;
     }
     const size_t n = volumes.size();
@@ -107,6 +140,13 @@ int main(int argc, char *argv[])
     if (qualityBins < 2 || qualityBins > 64) die("-qb takes 2 to 64 bins");
     if (qualityRange && !(std::isfinite(qualityLo) && std::isfinite(qualityHi) && qualityHi > qualityLo && std::isfinite(qualityHi - qualityLo)))
         die("-qr takes two finite values lo < hi");
+    if (robust == 1 && coverage != 1) die("-r 1 ranks the images under the coverage rule: it needs -c 1");
+    if ((robustListOption || robustPlanesOption) && robust != 1) die("-rq and -rp need -r 1");
+    if (robustPlanesOption && robustPlanes < 1) die("-rp takes a number of planes, at least 1");
+    if (robust == 1 && n > FROG_RANK_MAX_IMAGES) die("-r 1 takes at most " + std::to_string(FROG_RANK_MAX_IMAGES) + " images");
+    std::vector<std::string> quantileTexts;
+    std::vector<double> probabilities{ 0.5 };               // the median first, then -rq's
+    if (robustListOption) parse_quantiles(robustList, quantileTexts, probabilities);
     if (coverage == 1 && n > 65535) die("-c 1 takes at most 65535 images (16-bit counts)");
     std::vector<std::string> masks;
     if (!maskList.empty()) {
@@ -163,7 +203,7 @@ int main(int argc, char *argv[])
         times.device_s += seconds(t0);
         stream.release(i);
         if (maskStream) maskStream->release(i);
-        if (quality != 1) {                                 // the second pass evaluates the chain again
+        if (quality != 1 && robust != 1) {                  // a later pass evaluates the chain again
             frog_chain_destroy(chains[i]);
             chains[i] = nullptr;
         }
@@ -232,8 +272,10 @@ int main(int argc, char *argv[])
                 die(volumes[i] + ": " + frog_last_error());
             again.release(i);
             if (maskAgain) maskAgain->release(i);
-            frog_chain_destroy(chains[i]);
-            chains[i] = nullptr;
+            if (robust != 1) {
+                frog_chain_destroy(chains[i]);
+                chains[i] = nullptr;
+            }
         }
         std::vector<double> finite;
         for (const auto &m : metrics) if (std::isfinite(m.ncc)) finite.push_back(m.ncc);
@@ -258,10 +300,71 @@ int main(int argc, char *argv[])
         quality_s = seconds(t0);
     }
     frog_cover_destroy(cover);
+
+    // ---- -r 1: median, MAD and quantile images, the files streamed once more per slab of z-planes
+    double robust_s = 0;
+    if (robust == 1) {
+        t0 = clk::now();
+        uint32_t planes = 0;
+        if (frog_rank_planes(&grid, (uint32_t)n, device, &planes)) die(frog_last_error());
+        if (robustPlanesOption && (uint64_t)robustPlanes < planes) planes = (uint32_t)robustPlanes;
+        const uint32_t depth = grid.dims[2], slabs = (depth + planes - 1) / planes;
+        std::cout << "robust : " << slabs << (slabs == 1 ? " slab of " : " slabs of ") << planes << " planes, " << probabilities.size()
+                  << " probabilities" << std::endl;
+        const size_t n_q = probabilities.size(), plane = (size_t)grid.dims[0] * grid.dims[1];
+        std::vector<float> values(n_q * total), mad(total), slabValues;
+        for (uint32_t first = 0; first < depth; first += planes) {
+            const uint32_t count_planes = std::min(planes, depth - first);
+            const size_t slabVoxels = plane * count_planes;
+            frog_rank *rank = nullptr;
+            if (frog_rank_create(&grid, first, count_planes, (uint32_t)n, device, &rank)) die(frog_last_error());
+            frog::VolumeStream again(volumes, threads, window);
+            std::unique_ptr<frog::VolumeStream> maskAgain(masks.empty() ? nullptr : new frog::VolumeStream(masks, threads, window));
+            const bool last = first + count_planes >= depth;
+            for (size_t i = 0; i < n; i++) {
+                frog::VolumeStream::Item &it = again.get(i, nullptr);
+                if (!it.file) die("cannot read volume " + volumes[i]);
+                const frog_volume *mask = nullptr;
+                if (maskAgain) {
+                    frog::VolumeStream::Item &m = maskAgain->get(i, nullptr);
+                    if (!m.file) die("cannot read mask " + masks[i]);
+                    mask = &m.view;
+                }
+                if (frog_rank_add(rank, chains[i], &it.view, mask, interpolation, background.of(it.lo))) die(volumes[i] + ": " + frog_last_error());
+                again.release(i);
+                if (maskAgain) maskAgain->release(i);
+                if (last) {
+                    frog_chain_destroy(chains[i]);
+                    chains[i] = nullptr;
+                }
+            }
+            slabValues.resize(n_q * slabVoxels);
+            if (frog_rank_finish(rank, (uint32_t)minCount, fill, (uint32_t)n_q, probabilities.data(), slabValues.data(),
+                                 mad.data() + plane * first, nullptr)) die(frog_last_error());
+            for (size_t j = 0; j < n_q; j++)
+                std::memcpy(values.data() + j * total + plane * first, slabValues.data() + j * slabVoxels, slabVoxels * sizeof(float));
+            frog_rank_destroy(rank);
+        }
+        grid.dtype = FROG_V_F32;
+        auto write = [&](const std::string &name, float *data) {
+            grid.data = data;
+            const std::string path = outDir + "/" + name;
+            if (frog_volume_write(path.c_str(), &grid)) die("cannot write " + path);
+        };
+        write("median.nii.gz", values.data());
+        write("mad.nii.gz", mad.data());
+        for (size_t j = 1; j < n_q; j++) write("quantile_" + quantileTexts[j - 1] + ".nii.gz", values.data() + j * total);
+        robust_s = seconds(t0);
+    }
     times.print(stream.read_seconds() + (maskStream ? maskStream->read_seconds() : 0.0), stream.threads() + (maskStream ? maskStream->threads() : 0));
     if (quality == 1) {
         char line[64];
         std::snprintf(line, sizeof line, "quality : %.3f s", quality_s);
+        std::cout << line << std::endl;
+    }
+    if (robust == 1) {
+        char line[64];
+        std::snprintf(line, sizeof line, "robust : %.3f s", robust_s);
         std::cout << line << std::endl;
     }
     return 0;

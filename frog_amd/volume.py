@@ -286,6 +286,77 @@ def group_quality(volumes, chains=None, masks=None, grid=None, interpolation=1, 
     return rows
 
 
+class RankImages(_Accumulator):
+    """frog_rank (include/frog_chain.h): every added image's value per voxel of a window of `grid` = (dims(x, y, z), origin,
+    spacing), then per-voxel order statistics over the images that take part: quantile images, the MAD and the count.
+    `window` = (first z-plane, planes), default the whole grid; `n_images` is the most adds it will take."""
+
+    _NAME = "rank"
+
+    def __init__(self, grid, n_images, window=None, device=0):
+        first, planes = (0, int(grid[0][2])) if window is None else (int(window[0]), int(window[1]))
+        super().__init__(grid, first, planes, int(n_images), int(device))
+        self.window = (first, planes)
+        self.shape = (planes,) + self.dims[1::-1]
+
+    def add(self, volume, chain=None, mask=None, interpolation=1, background=0.0):
+        """Keeps `volume` where CoverAverage.add with the same arguments would count it and its value is not NaN."""
+        _, src, mv, _, _ = self._views(volume, mask)
+        _abi.check(self._lib.frog_rank_add(self._h, chain._h if chain is not None else None, src, mv, int(interpolation),
+                                           float(background)), "frog_rank_add")
+
+    def finish(self, min_count=1, fill=0.0, quantiles=(0.5,), mad=True, count=True):
+        """(values, mad, count) over the window: `values` float32 of shape (len(quantiles),) + shape, one image per
+        probability (linear interpolation between the two neighbouring order statistics); `mad` the raw median absolute
+        deviation, float32, or None; `count` uint16, the images that took part, or None.  Where fewer than min_count did,
+        the values are `fill` and the MAD 0.  May be called again, and after further adds."""
+        q = np.ascontiguousarray(quantiles, np.float64).ravel()
+        values = np.empty((len(q),) + self.shape, np.float32)
+        m = np.empty(self.shape, np.float32) if mad else None
+        c = np.empty(self.shape, np.uint16) if count else None
+        _abi.check(self._lib.frog_rank_finish(self._h, int(min_count), float(fill), len(q), q.ctypes.data_as(C.POINTER(C.c_double)),
+                                              values.ctypes.data_as(_abi.c_float_p) if len(q) else None,
+                                              m.ctypes.data_as(_abi.c_float_p) if mad else None,
+                                              c.ctypes.data_as(C.POINTER(C.c_uint16)) if count else None), "frog_rank_finish")
+        return values, m, c
+
+
+def rank_planes(grid, n_images, device=0):
+    """The most z-planes of `grid` a RankImages window for n_images may hold on the device now (frog_rank_planes)."""
+    dims, origin, spacing = grid
+    g = _abi.volume_view(None, origin, spacing, tuple(int(d) for d in dims))
+    planes = C.c_uint32()
+    _abi.check(_abi.hip_lib().frog_rank_planes(C.byref(g), int(n_images), int(device), C.byref(planes)), "frog_rank_planes")
+    return planes.value
+
+
+def group_median(volumes, chains=None, masks=None, grid=None, quantiles=(), interpolation=1, min_count=1, fill=0.0, max_planes=None,
+                 device=0):
+    """The robust atlas of a registered group (bin/AverageImage -c 1 -r 1): per grid voxel the median, the raw MAD (x 1.4826
+    for a normal stdev) and the count of the images that cover it, and one image per probability in `quantiles`.  Arguments as
+    in cover_average(); the device holds slabs of rank_planes() z-planes (at most max_planes) and the images are added once
+    per slab, which changes no bit.  Returns (median float32, mad float32, count uint16, {q: float32 image})."""
+    vols, grid = _group(volumes, chains, masks, grid)
+    qs = [float(q) for q in quantiles]
+    dims = tuple(int(d) for d in grid[0])
+    planes = rank_planes(grid, len(vols), device)
+    if max_planes is not None:
+        planes = max(1, min(planes, int(max_planes)))
+    values = np.empty((1 + len(qs),) + dims[::-1], np.float32)
+    mad = np.empty(dims[::-1], np.float32)
+    count = np.empty(dims[::-1], np.uint16)
+    for first in range(0, dims[2], planes):
+        n = min(planes, dims[2] - first)
+        acc = RankImages(grid, len(vols), (first, n), device)
+        try:
+            for k, v in enumerate(vols):
+                acc.add(v, None if chains is None else chains[k], None if masks is None else masks[k], interpolation)
+            values[:, first:first + n], mad[first:first + n], count[first:first + n] = acc.finish(min_count, fill, [0.5] + qs)
+        finally:
+            acc.close()
+    return values[0], mad, count, {q: values[1 + j] for j, q in enumerate(qs)}
+
+
 FUSED_DTYPES = ("uint8", "uint16", "int16", "int32", "uint32")
 
 

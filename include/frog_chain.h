@@ -232,6 +232,57 @@ int  frog_cover_score(frog_cover *a, frog_chain *chain, const frog_volume *sourc
                       double background, uint32_t min_count, int leave_one_out, uint32_t bins, float lo, float hi,
                       frog_score_sums *sums, uint64_t *histogram);
 
+/* ---- median, MAD and quantile images of a registered group (an extension: order statistics across the images) -----------------
+ * The moments above stream; an order statistic does not: this accumulator keeps every added image's value per voxel, then
+ * sorts per voxel.  It holds the z-planes [first_plane, first_plane + n_planes) of `grid` (dims, origin, spacing; its dtype
+ * and data are ignored): the WINDOW, n_planes * dims[1] * dims[0] voxels, x fastest.  A voxel's position is computed from
+ * its index in the whole grid, with the device code of frog_cover_add (the window is not a sub-grid with a shifted origin,
+ * which would round differently), so windows that partition the grid give, bit for bit, what one whole-grid window gives.
+ * The device holds 4 bytes per image and window voxel; n_images x window voxels may exceed 2^32.
+ *
+ * frog_rank_planes: the largest n_planes the device would accept for this grid and n_images: half of the free device memory
+ * at the time of the call / (4 bytes x n_images x dims[0] x dims[1]), at most dims[2]; FROG_E_INVALID when not one plane fits.
+ *
+ * What an add keeps.  Add number i (0-based, in call order) fills plane i of the window with one u32 per voxel:
+ *   x   = (float)r, r the voxel frog_chain_reslice(chain, source, out, interpolation, background) stores there, in the
+ *         source's type, as in frog_cover_add;
+ *   key = ~u where the sign bit of u = bits(x) is set, else u ^ 0x80000000: unsigned order of the keys is
+ *         -inf < ... < -0 < +0 < ... < +inf;
+ *   the entry TAKES PART iff the voxel is valid by frog_cover_add's rule (with a chain the inside test against the source,
+ *   then the mask at the same position; with chain == NULL equal dims and the mask's own voxel) and x is not NaN; every other
+ *   entry holds 0xFFFFFFFF, the key of a NaN, which no participating value has and which sorts last.
+ * The chain is evaluated once per voxel and add.  More than n_images adds are refused.
+ *
+ * What finish returns, per window voxel, after any number of adds >= 1 (more adds may follow, and finish may be called again).
+ * k is the number of participating entries and a[0 .. k-1] their values in ascending key order.
+ *   count = k: frog_cover's count minus the valid NaNs.
+ *   Where k < min_count every quantile is `fill` and mad is 0.  Otherwise, for each of the n_q probabilities q, in f64 with one
+ *   rounded operation per step and no contraction:
+ *       h = q * (double)(k - 1);  lo = floor(h);  f = h - lo;  hi = min(lo + 1, k - 1)
+ *       value(q) = a[lo]                                                        if f == 0 or a[lo] == a[hi] (so -0 == +0)
+ *                = (float)((double)a[lo] + f * ((double)a[hi] - (double)a[lo]))  otherwise
+ *   so equal neighbours never give inf - inf.  Neighbours -inf and +inf do; a NaN result is stored as 0x7FC00000.
+ *   quantiles: n_q window-sized planes, plane j for q[j].
+ *   mad: m = value(0.5) as the f32 it is stored as.  m not finite: mad = NaN (0x7FC00000).  Else d_i = |a[i] - m| in f32 (one
+ *   rounded subtraction, then the absolute value), and mad = value(0.5) of the sorted d by the same rule.  It is the raw
+ *   median absolute deviation: multiply by 1.4826 for a consistent estimate of a normal stdev.
+ * Order statistics are exact: the result does not depend on the sorting method, on scheduling or on how the work is cut into
+ * launches or windows.  n_q is 0..16 with every q in [0, 1] (NaN refused); any output may be NULL, not all of them (n_q == 0 or
+ * quantiles == NULL: mad or count).  Host buffers, window-sized, x fastest.
+ * FROG_RANK_MAX_IMAGES is the capacity of the sort kernels (one voxel's keys padded to a power of two in registers up to 64
+ * images, in LDS above), not of the 16-bit counts.
+ * FROG_E_INVALID, before the device is touched: a NULL argument, an empty grid or one above 2^31 voxels, a window outside the
+ * grid or n_planes == 0, n_images == 0 or > FROG_RANK_MAX_IMAGES; in add a float mask, bad geometry, a chain on another
+ * device, the (n_images + 1)th add; in finish min_count == 0, n_q > 16, a q outside [0, 1], no add yet. */
+#define FROG_RANK_MAX_IMAGES 4096
+typedef struct frog_rank frog_rank;
+int  frog_rank_planes(const frog_volume *grid, uint32_t n_images, int device, uint32_t *planes);
+int  frog_rank_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_planes, uint32_t n_images, int device, frog_rank **out);
+int  frog_rank_add(frog_rank *a, frog_chain *chain, const frog_volume *source, const frog_volume *mask, int interpolation, double background);
+int  frog_rank_finish(frog_rank *a, uint32_t min_count, float fill, uint32_t n_q, const double *q,
+                      float *quantiles, float *mad, uint16_t *count);
+void frog_rank_destroy(frog_rank *a);
+
 /* ---- majority-vote fusion of a registered group's label maps (an extension: the reference stops at N x VolumeTransform -i 0) --
  * An accumulator of n_images label volumes on `grid` (dims, origin, spacing; its dtype and data are ignored).  Per voxel v
  * and label value l it counts the images that carry l at v: count[l][v], 16-bit, one device thread per voxel, no atomics on
