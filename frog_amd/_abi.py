@@ -311,6 +311,16 @@ HIP_SYMBOLS = {
     "frog_labels_fused": (C.c_int, [C.c_void_p, C.POINTER(FrogVolume), c_float_p]),
     "frog_labels_probability": (C.c_int, [C.c_void_p, C.c_int64, c_float_p]),
     "frog_labels_destroy": (None, [C.c_void_p]),
+    "frog_staple_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "frog_staple_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
+    "frog_staple_finish": (C.c_int, [C.c_void_p, c_u32_p]),
+    "frog_staple_values": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "frog_staple_solve": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_int, c_u32_p, c_double_p,
+                                    C.POINTER(C.c_uint64)]),
+    "frog_staple_fused": (C.c_int, [C.c_void_p, C.POINTER(FrogVolume), c_float_p]),
+    "frog_staple_probability": (C.c_int, [C.c_void_p, C.c_int64, c_float_p]),
+    "frog_staple_performance": (C.c_int, [C.c_void_p, c_double_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), c_double_p]),
+    "frog_staple_destroy": (None, [C.c_void_p]),
     "frog_wlabels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_int,
                                       C.POINTER(C.c_void_p)]),
     "frog_wlabels_target": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_int, C.c_double, C.POINTER(FrogVolume)]),

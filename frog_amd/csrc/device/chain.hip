@@ -1043,6 +1043,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 }
 
 #include "k_rank.hip.h"
+#include "k_staple.hip.h"
 
 } // namespace
 
@@ -1124,6 +1125,27 @@ struct frog_wlabels : frog_group {
     std::vector<uint32_t> dense;                    // table position -> dense index
     frog::DevBuf<float *> d_sorted_planes;
     frog::DevBuf<long long> d_sorted_values;
+};
+
+// the dense label index of every image at every voxel of one grid, and the EM state of frog_staple_solve
+struct frog_staple : frog_group {
+    uint32_t n_images = 0, added = 0, max_labels = 0;
+    bool finished = false, solved = false;
+    LabelMap map{};                                 // as in frog_labels
+    frog::DevBuf<long long> d_keys, d_values;
+    frog::DevBuf<uint32_t> d_index, d_state;
+    std::vector<long long> known;                   // dense index of the adds -> value
+    frog::DevBuf<uint8_t> d_D;                      // n_images planes: before finish the adds' indices, after it D[i][v]
+    // after finish
+    std::vector<long long> values;                  // ascending
+    frog::DevBuf<long long> d_sorted_values;
+    frog::DevBuf<uint8_t> d_active;
+    frog::DevBuf<uint32_t> d_q;                     // L planes
+    frog::DevBuf<double> d_theta, d_prior;
+    frog::DevBuf<unsigned long long> d_S, d_T, d_word;      // d_word: c[l] (L words), then the change maximum
+    // after solve: what frog_staple_performance returns
+    std::vector<double> theta, prior;
+    std::vector<uint64_t> sums, totals;
 };
 
 namespace {
@@ -1500,8 +1522,8 @@ hipError_t labels_reset_map(A *a)
     return e;
 }
 
-// The empty device map of a new accumulator (A: frog_labels or frog_wlabels) for a->max_labels labels, and its table of
-// plane pointers: at least 16 slots, at least two per label.
+// The empty device map of a new accumulator (A: frog_labels, frog_wlabels or frog_staple) for a->max_labels labels: at
+// least 16 slots, at least two per label.
 template <class A>
 int labels_new_map(A *a)
 {
@@ -1512,7 +1534,6 @@ int labels_new_map(A *a)
     KCHECK(a->d_index.alloc(slots));
     KCHECK(a->d_values.alloc(a->max_labels));
     KCHECK(a->d_state.alloc(2));
-    KCHECK(a->d_planes.alloc(a->max_labels));
     a->map = LabelMap{ a->d_keys.p, a->d_index.p, a->d_values.p, a->d_state.p, (uint32_t)(slots - 1), 64 - bits, a->max_labels };
     KCHECK(labels_reset_map(a));
     return FROG_OK;
@@ -1788,6 +1809,106 @@ int rank_arguments(const char *where, const frog_volume *grid, uint32_t n_images
     if (int rc = group_arguments(where, grid, out, total)) return rc;
     if (!n_images || n_images > FROG_RANK_MAX_IMAGES)
         return fail(FROG_E_INVALID, std::string(where) + ": 1 to " + std::to_string(FROG_RANK_MAX_IMAGES) + " images");
+    return FROG_OK;
+}
+
+// frog_staple_add for a source of type S: labels_add_typed with the index plane in place of the vote.  The plane of the
+// image is written only after the volume's labels are accepted, so a refused volume leaves nothing behind.
+template <class S>
+int staple_add_typed(frog_staple *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
+{
+    ResliceGrid g;
+    if (int rc = stage_source<S>("frog_staple_add", a, src, c != nullptr, 0, background, &g)) return rc;
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = (S *)a->d_out.p;
+    const S *d_labels = c ? d_out : d_src;
+    uint32_t state[2] = { 0, 0 };
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            labels_collect_kernel<S, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->total, d_out, a->map);
+        else
+            labels_collect_kernel<S, false><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, a->total, nullptr, a->map);
+    });
+    if (e == hipSuccess) e = hipMemcpy(state, a->d_state.p, sizeof state, hipMemcpyDeviceToHost);
+    auto refuse = [&](int rc) { (void)labels_reset_map(a); return rc; };
+    if (e != hipSuccess) return refuse(hip_fail("frog_staple_add", e));
+    if (state[1] || state[0] > a->max_labels)
+        return refuse(fail(FROG_E_INVALID, "frog_staple_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
+    const size_t n_known = a->known.size(), n_now = state[0];
+    std::vector<long long> fresh(n_now - n_known);
+    if (!fresh.empty()) {
+        e = hipMemcpy(fresh.data(), a->d_values.p + n_known, fresh.size() * sizeof(long long), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return refuse(hip_fail("frog_staple_add", e));
+    }
+    uint8_t *plane = a->d_D.p + (size_t)a->added * a->total;
+    e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        staple_index_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_labels, a->total, a->map, plane);
+    });
+    const int rc = return_resliced<S>("frog_staple_add", a, c, src, resliced, e);
+    if (rc != FROG_OK) return refuse(rc);
+    a->known.insert(a->known.end(), fresh.begin(), fresh.end());
+    return FROG_OK;
+}
+
+template <class T>
+int staple_fused_typed(frog_staple *a, frog_volume *label, float *confidence)
+{
+    if (label && !labels_fit<T>(a)) return fail(FROG_E_INVALID, "frog_staple_fused: a label value does not fit the requested type");
+    frog::DevBuf<T> d_label;
+    frog::DevBuf<float> d_confidence;
+    if (label) KCHECK(d_label.alloc(a->total));
+    if (confidence) KCHECK(d_confidence.alloc(a->total));
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        staple_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_q.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
+                                                         d_label.p, d_confidence.p);
+    });
+    if (e == hipSuccess && label) e = hipMemcpy(label->data, d_label.p, a->total * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && confidence) e = hipMemcpy(confidence, d_confidence.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_staple_fused", e);
+    return FROG_OK;
+}
+
+// one E-step over the grid: the smallest register tile that holds the labels, the largest tiled above it
+hipError_t staple_estep_launch(const frog_staple *a)
+{
+    const uint32_t L = (uint32_t)a->values.size();
+    auto run = [&](auto kernel) {
+        return chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+            kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_D.p, a->total, a->n_images, L, a->d_theta.p, a->d_prior.p, a->d_active.p, a->d_q.p);
+        });
+    };
+    if (L <= 4) return run(staple_estep_kernel<4>);
+    if (L <= 8) return run(staple_estep_kernel<8>);
+    if (L <= 16) return run(staple_estep_kernel<16>);
+    return run(staple_estep_kernel<(int)STAPLE_TILE_MAX>);
+}
+
+// STAPLE_MSTEP_UNIFORM=0 at build time: every wave of the M-step takes the per-lane path (the A/B of DESIGN 20)
+#ifndef STAPLE_MSTEP_UNIFORM
+#define STAPLE_MSTEP_UNIFORM 1
+#endif
+
+// one M-step: S zeroed and summed, T, then theta and *change
+int staple_mstep(frog_staple *a, double *change)
+{
+    const uint32_t L = (uint32_t)a->values.size();
+    const size_t entries = (size_t)a->n_images * L * L;
+    unsigned long long *d_change = a->d_word.p + L;
+    const StapleTiles t = staple_tiles(a->n_images, L, a->total);
+    KCHECK(hipMemset(a->d_S.p, 0, entries * sizeof(unsigned long long)));
+    KCHECK(hipMemset(d_change, 0, sizeof(unsigned long long)));
+    KCHECK(chunked_launch((size_t)t.tiles * t.per_tile * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
+        staple_mstep_kernel<STAPLE_MSTEP_UNIFORM != 0><<<blocks, LAUNCH_BLOCK>>>(base, a->d_D.p, a->total, t, a->d_active.p, a->d_q.p, a->d_S.p);
+    }));
+    KCHECK(chunked_launch(L, [&](unsigned blocks, size_t base) {
+        staple_totals_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_S.p, L, a->d_T.p);
+    }));
+    KCHECK(chunked_launch(entries, [&](unsigned blocks, size_t base) {
+        staple_theta_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_S.p, a->d_T.p, L, entries, a->d_theta.p, d_change);
+    }));
+    unsigned long long bits = 0;
+    KCHECK(hipMemcpy(&bits, d_change, sizeof bits, hipMemcpyDeviceToHost));
+    std::memcpy(change, &bits, sizeof bits);
     return FROG_OK;
 }
 
@@ -2170,6 +2291,7 @@ int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_
     a->n_images = n_images;
     a->max_labels = max_labels ? max_labels : 1024;
     if (int rc = labels_new_map(a.get())) return rc;
+    KCHECK(a->d_planes.alloc(a->max_labels));
     *out = a.release();
     return FROG_OK;
 }
@@ -2265,6 +2387,174 @@ int frog_labels_probability(frog_labels *a, int64_t value, float *p)
 
 void frog_labels_destroy(frog_labels *a) { group_destroy(a); }
 
+int frog_staple_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_staple **out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_staple_create", grid, out, &total)) return rc;
+    if (!n_images || n_images > 4096) return fail(FROG_E_INVALID, "frog_staple_create: 1 to 4096 images");
+    if (max_labels > FROG_STAPLE_MAX_LABELS) return fail(FROG_E_INVALID, "frog_staple_create: max_labels above 256 (one byte per image and voxel)");
+    std::unique_ptr<frog_staple> a;
+    if (int rc = group_new(grid, total, device, a)) return rc;
+    a->n_images = n_images;
+    a->max_labels = max_labels ? max_labels : FROG_STAPLE_MAX_LABELS;
+    KCHECK(a->d_D.alloc((size_t)n_images * total));
+    if (int rc = labels_new_map(a.get())) return rc;
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_staple_add(frog_staple *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
+{
+    if (!a || !src || !src->data) return fail(FROG_E_INVALID, "bad arguments to frog_staple_add");
+    if (!integer_voxel_type(src->dtype)) return fail(FROG_E_INVALID, "frog_staple_add: a label volume has an integer type");
+    if (!std::isfinite(background)) return fail(FROG_E_INVALID, "frog_staple_add: background is not finite");
+    if (a->finished || a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_staple_add: more volumes than n_images");
+    if (int rc = add_inputs("frog_staple_add", a, c, src, resliced)) return rc;
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_integer_voxel_type(src->dtype, [&](auto s) { return staple_add_typed<decltype(s)>(a, c, src, background, resliced); });
+    if (rc == FROG_OK) a->added++;
+    return rc;
+}
+
+int frog_staple_finish(frog_staple *a, uint32_t *n_labels)
+{
+    if (!a || !n_labels) return fail(FROG_E_INVALID, "bad arguments to frog_staple_finish");
+    if (a->added != a->n_images) return fail(FROG_E_INVALID, "frog_staple_finish: fewer volumes added than n_images");
+    if (a->finished) { *n_labels = (uint32_t)a->values.size(); return FROG_OK; }
+    KCHECK(hipSetDevice(a->device));
+    const size_t L = a->known.size(), entries = (size_t)a->n_images * L * L;
+    std::vector<uint32_t> order(L);
+    for (size_t i = 0; i < L; i++) order[i] = (uint32_t)i;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return a->known[x] < a->known[y]; });
+    StapleLut lut{};
+    std::vector<long long> values(L);
+    for (size_t l = 0; l < L; l++) { lut.to[order[l]] = (uint8_t)l; values[l] = a->known[order[l]]; }
+    KCHECK(a->d_sorted_values.alloc(L));
+    KCHECK(a->d_active.alloc(a->total));
+    KCHECK(a->d_q.alloc(L * a->total));
+    KCHECK(a->d_theta.alloc(entries));
+    KCHECK(a->d_S.alloc(entries));
+    KCHECK(a->d_T.alloc(L));
+    KCHECK(a->d_prior.alloc(L));
+    KCHECK(a->d_word.alloc(L + 1));
+    KCHECK(hipMemcpy(a->d_sorted_values.p, values.data(), L * sizeof(long long), hipMemcpyHostToDevice));
+    const size_t count = (size_t)a->n_images * a->total;
+    KCHECK(chunked_launch(count, [&](unsigned blocks, size_t base) {
+        staple_renumber_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_D.p, count, lut);
+    }));
+    KCHECK(hipStreamSynchronize(0));
+    a->values = values;
+    a->finished = true;
+    *n_labels = (uint32_t)L;
+    return FROG_OK;
+}
+
+int frog_staple_values(frog_staple *a, int64_t *values)
+{
+    if (!a || !values) return fail(FROG_E_INVALID, "bad arguments to frog_staple_values");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_staple_values: before frog_staple_finish");
+    for (size_t l = 0; l < a->values.size(); l++) values[l] = a->values[l];
+    return FROG_OK;
+}
+
+int frog_staple_solve(frog_staple *a, double p0, double tol, uint32_t max_iter, int restrict_to_disputed,
+                      uint32_t *iterations, double *change, uint64_t *active_voxels)
+{
+    if (!a || !iterations || !change || !active_voxels) return fail(FROG_E_INVALID, "bad arguments to frog_staple_solve");
+    if (!(p0 > 0.0 && p0 < 1.0)) return fail(FROG_E_INVALID, "frog_staple_solve: p0 inside (0, 1)");
+    if (!(tol >= 0.0)) return fail(FROG_E_INVALID, "frog_staple_solve: a tolerance that is not negative");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_staple_solve: before frog_staple_finish");
+    KCHECK(hipSetDevice(a->device));
+    const uint32_t n = a->n_images, L = (uint32_t)a->values.size();
+    const size_t entries = (size_t)n * L * L;
+    a->solved = false;
+    std::vector<unsigned long long> c(L);
+    KCHECK(hipMemset(a->d_word.p, 0, L * sizeof(unsigned long long)));
+    KCHECK(chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        staple_active_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_D.p, a->total, n, L, restrict_to_disputed != 0, a->d_active.p, a->d_q.p, a->d_word.p);
+    }));
+    KCHECK(hipMemcpy(c.data(), a->d_word.p, L * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    unsigned long long entries_active = 0;
+    for (const unsigned long long x : c) entries_active += x;
+    const unsigned long long A = entries_active / n;
+    a->prior.assign(L, 0.0);
+    a->theta.assign(entries, 0.0);
+    a->sums.assign(entries, 0);
+    a->totals.assign(L, 0);
+    const double off = L > 1 ? (1.0 - p0) / (double)(L - 1) : 0.0;
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t lp = 0; lp < L; lp++)
+            for (uint32_t l = 0; l < L; l++) a->theta[((size_t)i * L + lp) * L + l] = lp == l ? p0 : off;
+    uint32_t it = 0;
+    double ch = INFINITY;
+    if (A) {
+        for (uint32_t l = 0; l < L; l++) a->prior[l] = (double)c[l] / (double)((unsigned long long)n * A);
+        KCHECK(hipMemcpy(a->d_prior.p, a->prior.data(), L * sizeof(double), hipMemcpyHostToDevice));
+        KCHECK(hipMemcpy(a->d_theta.p, a->theta.data(), entries * sizeof(double), hipMemcpyHostToDevice));
+        for (;;) {
+            KCHECK(staple_estep_launch(a));
+            if (it == max_iter) break;
+            if (int rc = staple_mstep(a, &ch)) return rc;
+            it++;
+            if (ch < tol) { KCHECK(staple_estep_launch(a)); break; }
+        }
+        KCHECK(hipMemcpy(a->theta.data(), a->d_theta.p, entries * sizeof(double), hipMemcpyDeviceToHost));
+        if (it) {
+            KCHECK(hipMemcpy(a->sums.data(), a->d_S.p, entries * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            KCHECK(hipMemcpy(a->totals.data(), a->d_T.p, L * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        }
+    }
+    KCHECK(hipStreamSynchronize(0));
+    a->solved = true;
+    *iterations = it;
+    *change = ch;
+    *active_voxels = A;
+    return FROG_OK;
+}
+
+int frog_staple_fused(frog_staple *a, frog_volume *label, float *confidence)
+{
+    if (!a || (!label && !confidence) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_staple_fused");
+    if (!a->solved) return fail(FROG_E_INVALID, "frog_staple_fused: before frog_staple_solve");
+    if (label) {
+        if (!integer_voxel_type(label->dtype)) return fail(FROG_E_INVALID, "frog_staple_fused: the fused map has an integer type");
+        if (!grid_sized(a, label)) return fail(FROG_E_INVALID, "frog_staple_fused: the fused map is not grid-sized");
+    }
+    KCHECK(hipSetDevice(a->device));
+    return with_integer_voxel_type(label ? label->dtype : FROG_V_I32, [&](auto t) { return staple_fused_typed<decltype(t)>(a, label, confidence); });
+}
+
+int frog_staple_probability(frog_staple *a, int64_t value, float *p)
+{
+    if (!a || !p) return fail(FROG_E_INVALID, "bad arguments to frog_staple_probability");
+    if (!a->solved) return fail(FROG_E_INVALID, "frog_staple_probability: before frog_staple_solve");
+    const auto it = std::lower_bound(a->values.begin(), a->values.end(), (long long)value);
+    if (it == a->values.end() || *it != (long long)value) return fail(FROG_E_INVALID, "frog_staple_probability: no such label");
+    KCHECK(hipSetDevice(a->device));
+    const uint32_t *plane = a->d_q.p + (size_t)(it - a->values.begin()) * a->total;
+    frog::DevBuf<float> d_p;
+    KCHECK(d_p.alloc(a->total));
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        staple_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, plane, a->total, d_p.p);
+    });
+    if (e == hipSuccess) e = hipMemcpy(p, d_p.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_staple_probability", e);
+    return FROG_OK;
+}
+
+int frog_staple_performance(frog_staple *a, double *theta, uint64_t *sums, uint64_t *totals, double *prior)
+{
+    if (!a || (!theta && !sums && !totals && !prior)) return fail(FROG_E_INVALID, "bad arguments to frog_staple_performance");
+    if (!a->solved) return fail(FROG_E_INVALID, "frog_staple_performance: before frog_staple_solve");
+    if (theta) std::copy(a->theta.begin(), a->theta.end(), theta);
+    if (sums) std::copy(a->sums.begin(), a->sums.end(), sums);
+    if (totals) std::copy(a->totals.begin(), a->totals.end(), totals);
+    if (prior) std::copy(a->prior.begin(), a->prior.end(), prior);
+    return FROG_OK;
+}
+
+void frog_staple_destroy(frog_staple *a) { group_destroy(a); }
+
 int frog_wlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, uint32_t radius, uint32_t power, float floor,
                         int device, frog_wlabels **out)
 {
@@ -2285,6 +2575,7 @@ int frog_wlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max
     KCHECK(a->d_target.alloc(total));
     KCHECK(a->d_atlas.alloc(total));
     if (int rc = labels_new_map(a.get())) return rc;
+    KCHECK(a->d_planes.alloc(a->max_labels));
     *out = a.release();
     return FROG_OK;
 }

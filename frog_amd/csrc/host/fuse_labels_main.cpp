@@ -1,7 +1,7 @@
 // FuseLabels: majority-vote fusion of a registered group's label maps in one process (the reference has no counterpart: it
 // stops at one `VolumeTransform -i 0` per image and leaves the N resliced label volumes to a script).
 //   FuseLabels bbox.json spacing labels_0 ... labels_N-1 [-td transformsDir] [-o outDir] [-b background] [-ml maxLabels]
-//              [-p 1] [-wt 1] [-dev n]
+//              [-p 1] [-wt 1] [-dev n] [-s 1 [-sp p0] [-st tol] [-si maxIter] [-sr 0|1]]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid); label map i goes through the inverse of <transformsDir>/<i>.json
 // (default "transforms") with nearest-neighbour interpolation exactly as `VolumeTransform labels_i dummy.mhd -t
 // transforms/i.json -i 0 -b <background>` does it (same device code; background 0 unless -b) and votes on the device
@@ -14,11 +14,26 @@
 //                       (include/frog_chain.h; nan for N = 1)
 //   -p 1                probability_<value>.nii.gz per label: f32 share of the images that carry it
 //   -wt 1               transformedLabels<i>.nii.gz, the file VolumeTransform -i 0 would write
-// Every transform and volume header is checked before anything is written; a float label file is an error.  Volumes are
+//   -s 1                STAPLE beside the vote (frog_staple, include/frog_chain.h: an EM estimate that weights every image's
+//                       vote by its estimated confusion matrix; at most 256 labels and 4096 images).  The resliced label
+//                       map of every image goes from frog_labels_add to frog_staple_add: one chain evaluation per image.
+//                       -sp: the starting diagonal of the confusion matrices (0.99); -st: the EM stops when no entry
+//                       changes by more (1e-6); -si: the most iterations (50); -sr 1: only the voxels on which the images
+//                       disagree take part.  It adds
+//     staple.nii.gz             per voxel the most probable label, typed as labels.nii.gz
+//     staple_confidence.nii.gz  its f32 probability
+//     staple.csv                label,prior,voxels,volume_mm3: the prior of the EM, the voxels of staple.nii.gz, their volume
+//     performance.csv           image,file,accuracy,accuracy_robust_z,sensitivity_<value>...: accuracy = sum_l S[i][l][l] /
+//                               sum_l T[l] (u64 sums, one f64 division), its robust z across the group by quality.csv's rule
+//                               ((a - median) / (1.4826 MAD), 0 where the MAD is 0), and theta[i][l][l] per label
+//     -p 1                      staple_probability_<value>.nii.gz per label
+//                       and a line "staple : <iterations> iterations, change <c>, <A> active voxels".
+// Every option, transform and volume header is checked before anything is written; a float label file is an error.  Volumes are
 // read and inflated on host threads ahead of the device (volume_stream.h).
 #include "group_tool.h"
 #include "volume_stream.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -27,15 +42,28 @@
 #include <string>
 #include <vector>
 
+namespace {
+
+// the median of a non-empty list: the middle value, or the mean of the middle two (as quality.csv's)
+double median(std::vector<double> v)
+{
+    std::sort(v.begin(), v.end());
+    const size_t n = v.size();
+    return n % 2 ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0;
+}
+
+} // namespace
+
 int main(int argc, char *argv[])
 {
     PhaseTimes times;
     std::vector<std::string> volumes;
     std::string transformsDir = "transforms", outDir = ".";
-    int device = 0, writeTransformed = 0, writeProbabilities = 0;
-    long maxLabels = 0;
-    double background = 0;
-    int a = positional_arguments(argc, argv, 3, { "-td", "-o", "-b", "-ml", "-p", "-wt", "-dev" }, volumes);
+    int device = 0, writeTransformed = 0, writeProbabilities = 0, staple = 0, stapleRestrict = 0;
+    long maxLabels = 0, stapleIterations = 50;
+    double background = 0, stapleP0 = 0.99, stapleTol = 1e-6;
+    bool stapleOption = false;                              // one of -sp, -st, -si, -sr was given
+    int a = positional_arguments(argc, argv, 3, { "-td", "-o", "-b", "-ml", "-p", "-wt", "-dev", "-s", "-sp", "-st", "-si", "-sr" }, volumes);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
         if (std::strcmp(key, "-td") == 0) transformsDir = value;
@@ -45,16 +73,30 @@ int main(int argc, char *argv[])
         else if (std::strcmp(key, "-p") == 0) writeProbabilities = atoi(value);
         else if (std::strcmp(key, "-wt") == 0) writeTransformed = atoi(value);
         else if (std::strcmp(key, "-dev") == 0) device = atoi(value);
+        else if (std::strcmp(key, "-s") == 0) staple = atoi(value);
+        else if (std::strcmp(key, "-sp") == 0) { stapleP0 = atof(value); stapleOption = true; }
+        else if (std::strcmp(key, "-st") == 0) { stapleTol = atof(value); stapleOption = true; }
+        else if (std::strcmp(key, "-si") == 0) { stapleIterations = atol(value); stapleOption = true; }
+        else if (std::strcmp(key, "-sr") == 0) { stapleRestrict = atoi(value); stapleOption = true; }
         else die(std::string("unknown option ") + key);
     }
     if (argc < 4 || volumes.empty()) {
         std::cout << "Usage : FuseLabels bbox.json spacing labels_0 ... labels_N-1 [-td transformsDir] [-o outDir] [-b background] "
-                     "[-ml maxLabels] [-p 1] [-wt 1] [-dev n]" << std::endl;
+                     "[-ml maxLabels] [-p 1] [-wt 1] [-dev n] [-s 1 [-sp p0] [-st tol] [-si maxIter] [-sr 0|1]]" << std::endl;
         return 1;
     }
     const size_t n = volumes.size();
     if (maxLabels < 0 || maxLabels > 65536) die("-ml : 1 to 65536 labels");
     if (n > 65535) die("at most 65535 label volumes");
+    if (stapleOption && staple != 1) die("-sp, -st, -si and -sr need -s 1");
+    if (staple == 1) {
+        if (n > 4096) die("-s 1 takes at most 4096 label volumes");
+        if (maxLabels > FROG_STAPLE_MAX_LABELS) die("-s 1 takes at most " + std::to_string(FROG_STAPLE_MAX_LABELS) + " labels (-ml)");
+        if (!(stapleP0 > 0.0 && stapleP0 < 1.0)) die("-sp : a probability inside (0, 1)");
+        if (!(stapleTol >= 0.0)) die("-st : a tolerance that is not negative");
+        if (stapleIterations < 0 || stapleIterations > 1000000) die("-si : 0 to 1000000 iterations");
+        if (stapleRestrict != 0 && stapleRestrict != 1) die("-sr : 0 or 1");
+    }
 
     // ---- everything is checked before the first output: the grid, every transform, every volume header
     frog_volume grid;
@@ -77,6 +119,8 @@ int main(int argc, char *argv[])
     std::vector<frog_chain *> chains = create_chains(inverse, device);
     frog_labels *acc = nullptr;
     if (frog_labels_create(&grid, (uint32_t)n, (uint32_t)maxLabels, device, &acc)) die(frog_last_error());
+    frog_staple *em = nullptr;
+    if (staple == 1 && frog_staple_create(&grid, (uint32_t)n, (uint32_t)maxLabels, device, &em)) die(frog_last_error());
     times.setup_s = seconds(t0);
 
     const size_t total = (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2];
@@ -86,14 +130,15 @@ int main(int argc, char *argv[])
         frog::VolumeStream::Item &it = stream.get(i, &waited);
         times.waited_s += waited;
         if (!it.file) die("cannot read volume " + volumes[i]);
-        frog_volume *out = resliced.stage(writeTransformed, grid, it.view.dtype);
+        frog_volume *out = resliced.stage(writeTransformed || em, grid, it.view.dtype);
         t0 = clk::now();
         if (frog_labels_add(acc, chains[i], &it.view, background, out)) die(volumes[i] + ": " + frog_last_error());
+        if (em && frog_staple_add(em, nullptr, out, background, nullptr)) die(volumes[i] + ": " + frog_last_error());
         times.device_s += seconds(t0);
         stream.release(i);
         frog_chain_destroy(chains[i]);
         chains[i] = nullptr;
-        if (out) {
+        if (out && writeTransformed) {
             t0 = clk::now();
             resliced.write(outDir, "transformedLabels", i);
             times.write_s += seconds(t0);
@@ -146,6 +191,92 @@ int main(int argc, char *argv[])
     }
     frog_labels_destroy(acc);
     std::cout << n_labels << " labels" << std::endl;
+    if (em) {
+        t0 = clk::now();
+        uint32_t L = 0, iterations = 0;
+        double change = 0;
+        uint64_t active = 0;
+        if (frog_staple_finish(em, &L) || frog_staple_solve(em, stapleP0, stapleTol, (uint32_t)stapleIterations, stapleRestrict, &iterations, &change, &active))
+            die(frog_last_error());
+        std::vector<int64_t> em_values(L);
+        std::vector<double> theta((size_t)n * L * L), prior(L);
+        std::vector<uint64_t> sums((size_t)n * L * L), totals(L);
+        if (frog_staple_values(em, em_values.data()) || frog_staple_performance(em, theta.data(), sums.data(), totals.data(), prior.data())
+            || frog_staple_fused(em, &label, share.data()))                      // the values are the vote's: the same type holds them
+            die(frog_last_error());
+        times.device_s += seconds(t0);
+
+        t0 = clk::now();
+        const std::string staple_path = outDir + "/staple.nii.gz", confidence_path = outDir + "/staple_confidence.nii.gz";
+        if (frog_volume_write(staple_path.c_str(), &label)) die("cannot write " + staple_path);
+        if (frog_volume_write(confidence_path.c_str(), &f32)) die("cannot write " + confidence_path);
+        // the voxels of every label in staple.nii.gz
+        std::vector<uint64_t> fused_voxels(L, 0);
+        for (size_t v = 0; v < total; v++) {
+            int64_t value = 0;
+            switch (dtype) {
+            case FROG_V_U8: value = ((const uint8_t *)fused.data())[v]; break;
+            case FROG_V_U16: value = ((const uint16_t *)fused.data())[v]; break;
+            case FROG_V_I16: value = ((const int16_t *)fused.data())[v]; break;
+            case FROG_V_I32: value = ((const int32_t *)fused.data())[v]; break;
+            default: value = ((const uint32_t *)fused.data())[v]; break;
+            }
+            fused_voxels[std::lower_bound(em_values.begin(), em_values.end(), value) - em_values.begin()]++;
+        }
+        const std::string staple_csv = outDir + "/staple.csv", performance_csv = outDir + "/performance.csv";
+        csv = std::fopen(staple_csv.c_str(), "w");
+        if (!csv) die("cannot write " + staple_csv);
+        std::fprintf(csv, "label,prior,voxels,volume_mm3\n");
+        for (uint32_t l = 0; l < L; l++)
+            std::fprintf(csv, "%lld,%.17g,%llu,%.17g\n", (long long)em_values[l], prior[l], (unsigned long long)fused_voxels[l],
+                         (double)fused_voxels[l] * voxel_mm3);
+        if (std::fclose(csv) != 0) die("cannot write " + staple_csv);
+        uint64_t all = 0;
+        for (const uint64_t x : totals) all += x;
+        std::vector<double> accuracy(n);
+        for (size_t i = 0; i < n; i++) {
+            uint64_t diagonal = 0;
+            for (uint32_t l = 0; l < L; l++) diagonal += sums[(i * L + l) * L + l];
+            accuracy[i] = (double)diagonal / (double)all;                       // nan where no M-step ran
+        }
+        std::vector<double> finite;
+        for (const double x : accuracy) if (std::isfinite(x)) finite.push_back(x);
+        double mid = 0, mad = 0;
+        if (!finite.empty()) {
+            mid = median(finite);
+            for (double &x : finite) x = std::fabs(x - mid);
+            mad = median(finite);
+        }
+        csv = std::fopen(performance_csv.c_str(), "w");
+        if (!csv) die("cannot write " + performance_csv);
+        std::fprintf(csv, "image,file,accuracy,accuracy_robust_z");
+        for (uint32_t l = 0; l < L; l++) std::fprintf(csv, ",sensitivity_%lld", (long long)em_values[l]);
+        std::fprintf(csv, "\n");
+        for (size_t i = 0; i < n; i++) {
+            const double z = !std::isfinite(accuracy[i]) ? NAN : (mad > 0 ? (accuracy[i] - mid) / (1.4826 * mad) : 0.0);
+            std::fprintf(csv, "%zu,%s,", i, volumes[i].c_str());
+            if (std::isnan(accuracy[i])) std::fprintf(csv, "nan,nan"); else std::fprintf(csv, "%.17g,%.17g", accuracy[i], z);
+            for (uint32_t l = 0; l < L; l++) std::fprintf(csv, ",%.17g", theta[(i * L + l) * L + l]);
+            std::fprintf(csv, "\n");
+        }
+        if (std::fclose(csv) != 0) die("cannot write " + performance_csv);
+        times.write_s += seconds(t0);
+        if (writeProbabilities) {
+            for (uint32_t l = 0; l < L; l++) {
+                t0 = clk::now();
+                if (frog_staple_probability(em, em_values[l], share.data())) die(frog_last_error());
+                times.device_s += seconds(t0);
+                t0 = clk::now();
+                const std::string path = outDir + "/staple_probability_" + std::to_string(em_values[l]) + ".nii.gz";
+                if (frog_volume_write(path.c_str(), &f32)) die("cannot write " + path);
+                times.write_s += seconds(t0);
+            }
+        }
+        frog_staple_destroy(em);
+        char line[160];
+        std::snprintf(line, sizeof line, "staple : %u iterations, change %.17g, %llu active voxels", iterations, change, (unsigned long long)active);
+        std::cout << line << std::endl;
+    }
     times.print(stream.read_seconds(), stream.threads());
     return 0;
 }

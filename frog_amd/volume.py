@@ -455,6 +455,109 @@ def fuse_labels(volumes, chains=None, grid=None, background=0.0, max_labels=0, d
         acc.close()
 
 
+class Staple(_Accumulator):
+    """frog_staple (include/frog_chain.h): n_images label maps added one by one on `grid` = (dims(x, y, z), origin, spacing),
+    then multi-label STAPLE: an EM consensus that weights every image's vote by its estimated confusion matrix, and those
+    matrices.  At most 256 distinct labels and 4096 images."""
+
+    _NAME = "staple"
+
+    def __init__(self, grid, n_images, max_labels=0, device=0):
+        self.n_images = int(n_images)
+        self._n_labels = None
+        super().__init__(grid, self.n_images, int(max_labels), int(device))
+
+    def add(self, volume, chain=None, background=0.0, resliced=False):
+        """As Labels.add: the integer label map `volume`, through `chain` with nearest-neighbour interpolation."""
+        _, src, _, ov, out = self._views(volume, None, resliced)
+        _abi.check(self._lib.frog_staple_add(self._h, chain._h if chain is not None else None, src, float(background), ov),
+                   "frog_staple_add")
+        return out
+
+    def finish(self):
+        """The number of distinct labels, after exactly n_images adds."""
+        n = C.c_uint32()
+        _abi.check(self._lib.frog_staple_finish(self._h, C.byref(n)), "frog_staple_finish")
+        self._n_labels = int(n.value)
+        return self._n_labels
+
+    def values(self):
+        """The distinct label values, int64 ascending."""
+        values = np.empty(self._n_labels or 0, np.int64)
+        _abi.check(self._lib.frog_staple_values(self._h, values.ctypes.data_as(C.POINTER(C.c_int64))), "frog_staple_values")
+        return values
+
+    def solve(self, p0=0.99, tol=1e-6, max_iter=50, restrict=False):
+        """Runs the EM from theta = p0 on the diagonal until the largest change of a theta entry is below `tol` or max_iter
+        M-steps ran; restrict=True leaves the voxels at which all images agree out of it.  May be called again.  Returns
+        (iterations, change, active_voxels)."""
+        p0, tol, max_iter = float(p0), float(tol), int(max_iter)
+        if not 0 <= max_iter < 2 ** 32:
+            raise ValueError("max_iter from 0 to 2^32 - 1")
+        it, change, active = C.c_uint32(), C.c_double(), C.c_uint64()
+        _abi.check(self._lib.frog_staple_solve(self._h, p0, tol, max_iter, int(bool(restrict)), C.byref(it), C.byref(change),
+                                               C.byref(active)), "frog_staple_solve")
+        return int(it.value), float(change.value), int(active.value)
+
+    def fused(self, dtype=None):
+        """(labels, confidence): per voxel the label with the largest probability (ties: the smallest value) as `dtype`,
+        default the first of uint8, uint16, int16, int32, uint32 that holds every label; its float32 probability."""
+        if dtype is None:
+            dtype = fused_dtype(self.values())
+            if dtype is None:
+                raise ValueError("no integer type of at most 32 bits holds every label value")
+        labels = np.empty(self.dims[::-1], np.dtype(dtype))
+        confidence = np.empty(self.dims[::-1], np.float32)
+        lv = _abi.volume_view(labels, tuple(self._grid.origin), tuple(self._grid.spacing))
+        _abi.check(self._lib.frog_staple_fused(self._h, C.byref(lv), confidence.ctypes.data_as(_abi.c_float_p)), "frog_staple_fused")
+        return labels, confidence
+
+    def probability(self, value):
+        """float32 probability that the truth is label `value`, per voxel."""
+        p = np.empty(self.dims[::-1], np.float32)
+        _abi.check(self._lib.frog_staple_probability(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), "frog_staple_probability")
+        return p
+
+    def performance(self):
+        """(theta, sums, totals, prior): theta[i, l', l] = P(image i shows values[l'] | the truth is values[l]), float64; the
+        uint64 sums[i, l', l] and totals[l] of the last M-step, whose quotient theta is; the float64 prior[l]."""
+        n, L = self.n_images, self._n_labels or 0
+        theta, sums = np.empty((n, L, L), np.float64), np.empty((n, L, L), np.uint64)
+        totals, prior = np.empty(L, np.uint64), np.empty(L, np.float64)
+        _abi.check(self._lib.frog_staple_performance(self._h, theta.ctypes.data_as(_abi.c_double_p), sums.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                     totals.ctypes.data_as(C.POINTER(C.c_uint64)), prior.ctypes.data_as(_abi.c_double_p)),
+                   "frog_staple_performance")
+        return theta, sums, totals, prior
+
+
+def staple_accuracy(sums, totals):
+    """Per image sum_l S[i][l][l] / sum_l T[l]: u64 sums, one float64 division (performance.csv's accuracy)."""
+    sums, totals = np.asarray(sums, np.uint64), np.asarray(totals, np.uint64)
+    diagonal = np.trace(sums, axis1=1, axis2=2, dtype=np.uint64)
+    return diagonal.astype(np.float64) / np.float64(totals.sum(dtype=np.uint64))
+
+
+def staple_labels(volumes, chains=None, grid=None, background=0.0, p0=0.99, tol=1e-6, max_iter=50, restrict=False, max_labels=0,
+                  device=0):
+    """STAPLE fusion of a group's label maps on the device (bin/FuseLabels -s 1).  `volumes`, `chains` and `grid` as in
+    average(); every volume has an integer type.  Returns a dict: labels, confidence, values, theta, sums, totals, prior
+    (Staple.performance), accuracy (staple_accuracy), iterations, change, active_voxels."""
+    vols, grid = _group(volumes, chains, None, grid)
+    acc = Staple(grid, len(vols), max_labels, device)
+    try:
+        for k, v in enumerate(vols):
+            acc.add(v, None if chains is None else chains[k], background)
+        acc.finish()
+        iterations, change, active = acc.solve(p0, tol, max_iter, restrict)
+        labels, confidence = acc.fused()
+        theta, sums, totals, prior = acc.performance()
+        return {"labels": labels, "confidence": confidence, "values": acc.values(), "theta": theta, "sums": sums, "totals": totals,
+                "prior": prior, "accuracy": staple_accuracy(sums, totals), "iterations": iterations, "change": change,
+                "active_voxels": active}
+    finally:
+        acc.close()
+
+
 class WeightedLabels(_Accumulator):
     """frog_wlabels (include/frog_chain.h): locally weighted label fusion.  The target image first, then n_images atlases
     (image + label map through one chain) on `grid` = (dims(x, y, z), origin, spacing); every atlas votes for its label with

@@ -321,6 +321,64 @@ int  frog_labels_fused(frog_labels *a, frog_volume *label, float *agreement);
 int  frog_labels_probability(frog_labels *a, int64_t value, float *p);
 void frog_labels_destroy(frog_labels *a);
 
+/* ---- STAPLE label fusion: an EM consensus and every image's performance (an extension; Warfield, Zou, Wells, IEEE TMI
+ * 23(7), 2004, multi-label form) --------------------------------------------------------------------------------------------
+ * An accumulator of n_images label volumes on `grid` (dims, origin, spacing; its dtype and data are ignored).  It keeps the
+ * label of image i at voxel v as a one-byte dense index D[i][v]; after finish index l stands for the l-th distinct value in
+ * ascending signed order, D[i][v] in [0, L).  solve estimates theta[i][l'][l] = P(image i shows l' | the truth is l) and
+ * q[v][l], the probability that the truth at v is l, as a u32 in units of 2^-30.  Every floating-point line below is one
+ * separately rounded f64 operation (no contraction, no log or exp), every sum is an exact u64 sum, and there is no
+ * floating-point atomic: what leaves the library is the same bits from run to run and however the work is cut into launches.
+ * Constants: FLOOR = 2^-24, ONE = 2^30, K = 16.  n = n_images, V = the grid's voxels.
+ *   Active voxels: all, or with restrict_to_disputed only those at which not all n images carry the same label; A is their
+ *     number.  An inactive voxel has q = ONE for its unanimous label and 0 for the others, and enters no sum below.
+ *   Prior:  prior[l] = (double)c[l] / (double)(n A), c[l] the u64 number of (image, active voxel) entries that carry l.
+ *   Start:  theta[i][l'][l] = p0 where l' == l, else (1.0 - p0) / (double)(L - 1).
+ *   E-step, per active voxel and label l:
+ *     1. m = prior[l]; e = 0
+ *     2. for i ascending: m = m * max(theta[i][D[i][v]][l], FLOOR)
+ *     3. after every factor with i % K == K - 1, and after the last one: (m, k) = frexp(m); e += k
+ *     4. emax = the largest e over the labels with m > 0
+ *     5. p[l] = ldexp(m, e - emax), which is 0 where m == 0
+ *     6. s = the sum of p[l] over l ascending, from +0.0
+ *     7. q[v][l] = (uint32)rint((p[l] / s) * 2^30), round half to even
+ *   M-step: T[l] = sum over the active v of q[v][l]; S[i][l'][l] = sum of q[v][l] over the active v with D[i][v] == l'; both
+ *     u64.  theta[i][l'][l] = (double)S[i][l'][l] / (double)T[l]; the previous value stays where T[l] == 0.
+ *   Loop:  it = 0.  Repeat: E-step; stop if it == max_iter; M-step; change = the largest |theta_new - theta_old|; it += 1;
+ *     if change < tol, one more E-step with the final theta, and stop.  *change is +inf when no M-step ran.  With A == 0
+ *     nothing runs: 0 iterations, prior 0, theta as started.
+ * Device memory: n V bytes (D) + V bytes (the active mask) + 4 L V bytes (q, which is stored, not recomputed: the M-step and
+ * the getters read what the last E-step wrote) + 16 n L^2 bytes (theta and S) + the staging of one source volume and, with a
+ * chain, of its resliced copy.  There are no slabs: the EM couples all voxels.
+ * FROG_E_INVALID, before the device is touched: a NULL argument, an empty grid or one above 2^31 voxels, n_images == 0 or
+ * > 4096, max_labels > FROG_STAPLE_MAX_LABELS (0: 256); everything frog_labels_add refuses (a float volume, a background
+ * that is not finite, bad geometry, a chain on another device, the (n_images + 1)th add); p0 outside (0, 1) or NaN, tol
+ * negative or NaN; a solve before finish, a getter before solve.  A refused device allocation is FROG_E_NOMEM. */
+#define FROG_STAPLE_MAX_LABELS 256
+typedef struct frog_staple frog_staple;
+int  frog_staple_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_staple **out);
+/* frog_labels_add's rules: one of the six integer types; chain == NULL: already on the grid; chain != NULL: nearest-neighbour
+ * reslicing through the same device code, `resliced` (may be NULL) receives that volume; the background is a label like any
+ * other.  A volume that would bring the distinct labels above max_labels is refused with FROG_E_INVALID and leaves nothing
+ * behind: the call does not count and another volume may be added in its place. */
+int  frog_staple_add(frog_staple *a, frog_chain *chain, const frog_volume *source, double background, frog_volume *resliced);
+/* After exactly n_images adds (else FROG_E_INVALID): renumbers D and returns L, the number of distinct labels. */
+int  frog_staple_finish(frog_staple *a, uint32_t *n_labels);
+int  frog_staple_values(frog_staple *a, int64_t *values);                    /* ascending, signed */
+/* The loop above; may be called again with other arguments, each call starts afresh. */
+int  frog_staple_solve(frog_staple *a, double p0, double tol, uint32_t max_iter, int restrict_to_disputed,
+                       uint32_t *iterations, double *change, uint64_t *active_voxels);
+/* Per voxel the first label in ascending order with the strictly largest q, stored as label->dtype (any of the six integer
+ * types; dims the grid's); confidence[v] = (float)((double)q_winner * 2^-30).  Either output may be NULL, not both.  A value
+ * that does not fit label->dtype -> FROG_E_INVALID and nothing is written. */
+int  frog_staple_fused(frog_staple *a, frog_volume *label, float *confidence);
+/* p[v] = (float)((double)q[v][value] * 2^-30); a value that no image carries -> FROG_E_INVALID. */
+int  frog_staple_probability(frog_staple *a, int64_t value, float *p);
+/* theta and sums: n L L entries each, entry (i L + l') L + l; totals and prior: L each.  sums and totals are those of the
+ * last M-step that ran (zeros if none did).  Any may be NULL, not all. */
+int  frog_staple_performance(frog_staple *a, double *theta, uint64_t *sums, uint64_t *totals, double *prior);
+void frog_staple_destroy(frog_staple *a);
+
 /* ---- locally weighted label fusion: a target image segmented from a registered group (an extension; Artaechevarria et al.,
  * IEEE TMI 28(8), 2009: every atlas votes for its label with a weight that grows with its local similarity to the target) ------
  * An accumulator of n_images atlases on `grid` (dims, origin, spacing; its dtype and data are ignored).  An atlas is an image
