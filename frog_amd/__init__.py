@@ -6,3 +6,4 @@ is the thin Python layer tests, bench.py and the multi-process launcher use.
 from .pairs import Pairs            # noqa: F401
 from .image_group import ImageGroup  # noqa: F401
 from .volume import Staple, staple_labels  # noqa: F401
+from .volume import SurfaceDistances, distance_map, surface_distances, surface_metrics  # noqa: F401

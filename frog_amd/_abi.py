@@ -221,6 +221,15 @@ class FrogScoreSums(C.Structure):
                 ("syy", C.c_double), ("sxy", C.c_double), ("sad", C.c_double)]
 
 
+FROG_SURFACE_MAX_LABELS = 256      # include/frog_chain.h: the most values a frog_surface measures
+
+
+class FrogSurfaceRow(C.Structure):
+    """frog_surface_row (include/frog_chain.h)."""
+    _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("sum_ab", C.c_uint64), ("sum_ba", C.c_uint64),
+                ("max_ab", C.c_uint32), ("max_ba", C.c_uint32), ("pct_ab", C.c_uint32), ("pct_ba", C.c_uint32)]
+
+
 class FrogScoreMetrics(C.Structure):
     """frog_score_metrics (include/frog_host.h)."""
     _fields_ = [("ncc", C.c_double), ("mean_abs_diff", C.c_double), ("rmse", C.c_double), ("mi", C.c_double), ("nmi", C.c_double)]
@@ -331,6 +340,11 @@ HIP_SYMBOLS = {
     "frog_wlabels_fused": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(FrogVolume), c_float_p]),
     "frog_wlabels_probability": (C.c_int, [C.c_void_p, C.c_int64, c_float_p]),
     "frog_wlabels_destroy": (None, [C.c_void_p]),
+    "frog_distance_map": (C.c_int, [C.POINTER(FrogVolume), C.c_int64, C.c_int, C.c_int, c_u32_p]),
+    "frog_surface_create": (C.c_int, [C.POINTER(FrogVolume), C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.c_int,
+                                      C.POINTER(C.c_void_p)]),
+    "frog_surface_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogSurfaceRow)]),
+    "frog_surface_destroy": (None, [C.c_void_p]),
     "frog_match_options_default": (None, [C.POINTER(FrogMatchOptions)]),
     "frog_matcher_create": (C.c_int, [C.POINTER(FrogKeypoints), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_matcher_destroy": (None, [C.c_void_p]),

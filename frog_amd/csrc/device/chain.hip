@@ -1044,6 +1044,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 
 #include "k_rank.hip.h"
 #include "k_staple.hip.h"
+#include "k_edt.hip.h"
 
 } // namespace
 
@@ -1146,6 +1147,21 @@ struct frog_staple : frog_group {
     // after solve: what frog_staple_performance returns
     std::vector<double> theta, prior;
     std::vector<uint64_t> sums, totals;
+};
+
+// the reference's distance maps, and what an add needs of the reference and of the current image
+struct frog_surface : frog_group {
+    uint32_t percentile = 95;
+    std::vector<long long> values;                  // ascending
+    frog::DevBuf<long long> d_values;
+    frog::DevBuf<uint16_t> d_ref_idx, d_idx;        // dense label index of the reference / of the current image
+    frog::DevBuf<uint8_t> d_ref_surf, d_surf;       // their surface masks
+    frog::DevBuf<uint32_t> d_maps;                  // D_B: one grid-sized map per value
+    std::vector<uint32_t> ref_bounds;               // per value EDT_BOUND_WORDS words: the box of B and n_b
+    frog::DevBuf<uint32_t> d_bounds, d_any, d_largest;
+    frog::DevBuf<unsigned long long> d_sum, d_count;
+    frog::DevBuf<double> d_g1, d_g2;                // the passes' planes, grown to the largest box
+    frog::DevBuf<uint2> d_list;
 };
 
 namespace {
@@ -1909,6 +1925,227 @@ int staple_mstep(frog_staple *a, double *change)
     unsigned long long bits = 0;
     KCHECK(hipMemcpy(&bits, d_change, sizeof bits, hipMemcpyDeviceToHost));
     std::memcpy(change, &bits, sizeof bits);
+    return FROG_OK;
+}
+
+// ---- the distance transform and the surface distances (k_edt.hip.h) ----------------------------------------------------------
+
+bool edt_spacing(const frog_volume *v)
+{
+    for (int k = 0; k < 3; k++)
+        if (!(v->spacing[k] > 0.0) || !std::isfinite(v->spacing[k])) return false;
+    return true;
+}
+
+// the box lo .. hi (inclusive) of the grid
+EdtBox edt_box(const frog_volume &grid, const uint32_t lo[3], const uint32_t hi[3])
+{
+    EdtBox b;
+    b.x0 = lo[0]; b.y0 = lo[1]; b.z0 = lo[2];
+    b.nx = hi[0] - lo[0] + 1; b.ny = hi[1] - lo[1] + 1; b.nz = hi[2] - lo[2] + 1;
+    b.gx = grid.dims[0]; b.gy = grid.dims[1];
+    b.sx = grid.spacing[0]; b.sy = grid.spacing[1]; b.sz = grid.spacing[2];
+    return b;
+}
+
+EdtBox edt_whole(const frog_volume &grid)
+{
+    const uint32_t lo[3] = { 0, 0, 0 }, hi[3] = { grid.dims[0] - 1, grid.dims[1] - 1, grid.dims[2] - 1 };
+    return edt_box(grid, lo, hi);
+}
+
+size_t edt_box_voxels(const EdtBox &b) { return (size_t)b.nx * b.ny * b.nz; }
+
+// The x and y passes over box b for the features idx == l (surface_only: and surf): g2 holds the result, `any` the planes with
+// a feature.  g1 and g2 grow to the box; `any` holds the grid's planes + 1 words.
+hipError_t edt_xy(const EdtBox &b, const uint16_t *idx, const uint8_t *surf, uint32_t l, int surface_only, frog::DevBuf<double> &g1,
+                  frog::DevBuf<double> &g2, uint32_t *any)
+{
+    const size_t count = edt_box_voxels(b), lines = (size_t)b.ny * b.nz;
+    hipError_t e = g1.alloc(count);
+    if (e == hipSuccess) e = g2.alloc(count);
+    if (e == hipSuccess) e = hipMemsetAsync(any, 0, ((size_t)b.nz + 1) * sizeof(uint32_t), 0);
+    if (e == hipSuccess) e = chunked_launch(lines * 64, [&](unsigned blocks, size_t base) {
+        edt_x_kernel<<<blocks, LAUNCH_BLOCK>>>(base, b, idx, surf, l, surface_only, g1.p, any);
+    });
+    if (e == hipSuccess) e = chunked_launch(count, [&](unsigned blocks, size_t base) {
+        edt_y_kernel<<<blocks, LAUNCH_BLOCK>>>(base, b, g1.p, g2.p, any);
+    });
+    return e;
+}
+
+// The transform over box b as stored distances, out indexed by the box.
+hipError_t edt_map(const EdtBox &b, const uint16_t *idx, const uint8_t *surf, uint32_t l, int surface_only, frog::DevBuf<double> &g1,
+                   frog::DevBuf<double> &g2, uint32_t *any, uint32_t *out)
+{
+    hipError_t e = edt_xy(b, idx, surf, l, surface_only, g1, g2, any);
+    if (e == hipSuccess) e = chunked_launch(edt_box_voxels(b), [&](unsigned blocks, size_t base) {
+        edt_z_kernel<<<blocks, LAUNCH_BLOCK>>>(base, b, g2.p, any, out);
+    });
+    return e;
+}
+
+// idx and surf of a label volume of S on the grid (device pointers)
+template <class S>
+hipError_t edt_surface(const frog_volume &grid, size_t total, const S *d_labels, const long long *d_values, uint32_t n, uint16_t *idx, uint8_t *surf)
+{
+    return chunked_launch(total, [&](unsigned blocks, size_t base) {
+        edt_surface_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_labels, grid.dims[0], grid.dims[1], grid.dims[2], d_values, n, idx, surf);
+    });
+}
+
+// per value the box of its set and the number of its surface voxels, to the host
+hipError_t edt_bounds(const frog_volume &grid, size_t total, const uint16_t *idx, const uint8_t *surf, uint32_t n, uint32_t *d_bounds,
+                      std::vector<uint32_t> &bounds)
+{
+    bounds.assign((size_t)n * EDT_BOUND_WORDS, 0u);
+    for (uint32_t l = 0; l < n; l++)
+        for (int k = 0; k < 3; k++) bounds[(size_t)l * EDT_BOUND_WORDS + k] = 0xFFFFFFFFu;
+    hipError_t e = hipMemcpy(d_bounds, bounds.data(), bounds.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = chunked_launch(total, [&](unsigned blocks, size_t base) {
+        edt_bounds_kernel<<<blocks, LAUNCH_BLOCK>>>(base, idx, surf, grid.dims[0], grid.dims[1], total, d_bounds);
+    });
+    if (e == hipSuccess) e = hipMemcpy(bounds.data(), d_bounds, bounds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    return e;
+}
+
+template <class S>
+int distance_map_typed(const frog_volume *labels, size_t total, long long value, int mode, uint32_t *out)
+{
+    frog::DevBuf<S> d_labels;
+    frog::DevBuf<long long> d_value;
+    frog::DevBuf<uint16_t> d_idx;
+    frog::DevBuf<uint8_t> d_surf;
+    frog::DevBuf<double> g1, g2;
+    frog::DevBuf<uint32_t> d_any, d_out;
+    KCHECK(d_labels.alloc(total));
+    KCHECK(d_value.alloc(1));
+    KCHECK(d_idx.alloc(total));
+    KCHECK(d_surf.alloc(total));
+    KCHECK(d_any.alloc((size_t)labels->dims[2] + 1));
+    KCHECK(d_out.alloc(total));
+    hipError_t e = hipMemcpy(d_labels.p, labels->data, total * sizeof(S), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_value.p, &value, sizeof value, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = edt_surface<S>(*labels, total, d_labels.p, d_value.p, 1, d_idx.p, d_surf.p);
+    if (e == hipSuccess) e = edt_map(edt_whole(*labels), d_idx.p, d_surf.p, 0, mode, g1, g2, d_any.p, d_out.p);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out.p, total * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_distance_map", e);
+    return FROG_OK;
+}
+
+// frog_surface_create for a reference of type S: idx, surf, the boxes and one whole-grid map per value
+template <class S>
+int surface_create_typed(frog_surface *a, const frog_volume *reference)
+{
+    const uint32_t n = (uint32_t)a->values.size();
+    KCHECK(a->d_src.alloc(a->total * sizeof(S)));
+    KCHECK(a->d_values.alloc(n));
+    KCHECK(a->d_ref_idx.alloc(a->total));
+    KCHECK(a->d_ref_surf.alloc(a->total));
+    KCHECK(a->d_idx.alloc(a->total));
+    KCHECK(a->d_surf.alloc(a->total));
+    KCHECK(a->d_maps.alloc((size_t)n * a->total));
+    KCHECK(a->d_bounds.alloc((size_t)n * EDT_BOUND_WORDS));
+    KCHECK(a->d_any.alloc((size_t)a->grid.dims[2] + 1));
+    KCHECK(a->d_largest.alloc(2 * (size_t)n));
+    KCHECK(a->d_sum.alloc(2 * (size_t)n));
+    KCHECK(a->d_count.alloc(1));
+    hipError_t e = hipMemcpy(a->d_src.p, reference->data, a->total * sizeof(S), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(a->d_values.p, a->values.data(), n * sizeof(long long), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = edt_surface<S>(a->grid, a->total, (const S *)a->d_src.p, a->d_values.p, n, a->d_ref_idx.p, a->d_ref_surf.p);
+    if (e == hipSuccess) e = edt_bounds(a->grid, a->total, a->d_ref_idx.p, a->d_ref_surf.p, n, a->d_bounds.p, a->ref_bounds);
+    const EdtBox whole = edt_whole(a->grid);
+    for (uint32_t l = 0; l < n && e == hipSuccess; l++) {
+        uint32_t *map = a->d_maps.p + (size_t)l * a->total;
+        if (!a->ref_bounds[(size_t)l * EDT_BOUND_WORDS + 6]) e = hipMemsetAsync(map, 0xFF, a->total * sizeof(uint32_t), 0);
+        else e = edt_map(whole, a->d_ref_idx.p, a->d_ref_surf.p, l, 1, a->d_g1, a->d_g2, a->d_any.p, map);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return hip_fail("frog_surface_create", e);
+    return FROG_OK;
+}
+
+// the k-th smallest (1-based) of a non-empty list
+uint32_t edt_kth(std::vector<uint32_t> &d, uint64_t k)
+{
+    std::nth_element(d.begin(), d.begin() + (k - 1), d.end());
+    return d[k - 1];
+}
+
+// frog_surface_add for a source of type S
+template <class S>
+int surface_add_typed(frog_surface *a, frog_chain *c, const frog_volume *src, double background, frog_surface_row *rows)
+{
+    const char *where = "frog_surface_add";
+    ResliceGrid g;
+    if (int rc = stage_source<S>(where, a, src, c != nullptr, 0, background, &g)) return rc;
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = (S *)a->d_out.p;
+    const S *d_labels = c ? d_out : d_src;
+    const uint32_t n = (uint32_t)a->values.size();
+    hipError_t e = hipSuccess;
+    if (c) e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, d_out);
+    });
+    if (e == hipSuccess) e = edt_surface<S>(a->grid, a->total, d_labels, a->d_values.p, n, a->d_idx.p, a->d_surf.p);
+    std::vector<uint32_t> bounds;
+    if (e == hipSuccess) e = edt_bounds(a->grid, a->total, a->d_idx.p, a->d_surf.p, n, a->d_bounds.p, bounds);
+    if (e != hipSuccess) return hip_fail(where, e);
+    auto n_a = [&](uint32_t l) { return (uint64_t)bounds[(size_t)l * EDT_BOUND_WORDS + 6]; };
+    auto n_b = [&](uint32_t l) { return (uint64_t)a->ref_bounds[(size_t)l * EDT_BOUND_WORDS + 6]; };
+    size_t capacity = 0;
+    for (uint32_t l = 0; l < n; l++) capacity += n_a(l) + (n_a(l) ? n_b(l) : 0);
+    KCHECK(a->d_list.alloc(capacity));
+    const EdtList list{ a->d_list.p, a->d_count.p };
+    e = hipMemsetAsync(a->d_sum.p, 0, 2 * (size_t)n * sizeof(unsigned long long), 0);
+    if (e == hipSuccess) e = hipMemsetAsync(a->d_largest.p, 0, 2 * (size_t)n * sizeof(uint32_t), 0);
+    if (e == hipSuccess) e = hipMemsetAsync(a->d_count.p, 0, sizeof(unsigned long long), 0);
+    if (e == hipSuccess) e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        edt_read_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_idx.p, a->d_surf.p, a->total, a->d_maps.p, a->d_sum.p, a->d_largest.p, list);
+    });
+    for (uint32_t l = 0; l < n && e == hipSuccess; l++) {
+        if (!n_a(l) || !n_b(l)) continue;
+        const uint32_t *pa = &bounds[(size_t)l * EDT_BOUND_WORDS], *pb = &a->ref_bounds[(size_t)l * EDT_BOUND_WORDS];
+        uint32_t lo[3], hi[3];
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(pa[k], pb[k]); hi[k] = std::max(pa[3 + k], pb[3 + k]); }
+        const EdtBox b = edt_box(a->grid, lo, hi);
+        e = edt_xy(b, a->d_idx.p, a->d_surf.p, l, 1, a->d_g1, a->d_g2, a->d_any.p);
+        if (e == hipSuccess) e = chunked_launch(edt_box_voxels(b), [&](unsigned blocks, size_t base) {
+            edt_z_collect_kernel<<<blocks, LAUNCH_BLOCK>>>(base, b, a->d_g2.p, a->d_ref_idx.p, a->d_ref_surf.p, l, n + l, a->d_sum.p + n,
+                                                          a->d_largest.p + n, list);
+        });
+    }
+    std::vector<unsigned long long> sum(2 * (size_t)n);
+    std::vector<uint32_t> largest(2 * (size_t)n);
+    unsigned long long count = 0;
+    if (e == hipSuccess) e = hipMemcpy(sum.data(), a->d_sum.p, sum.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(largest.data(), a->d_largest.p, largest.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(&count, a->d_count.p, sizeof count, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count != capacity) return fail(FROG_E_HIP, std::string(where) + ": the distance list is incomplete");
+    std::vector<uint2> entries(capacity);
+    if (e == hipSuccess && capacity) e = hipMemcpy(entries.data(), a->d_list.p, capacity * sizeof(uint2), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(where, e);
+    // the percentile: an order statistic of each key's distances, whatever order the list has them in
+    std::vector<std::vector<uint32_t>> by_key(2 * (size_t)n);
+    for (uint32_t l = 0; l < n; l++) {
+        if (!n_a(l) || !n_b(l)) continue;
+        by_key[l].reserve(n_a(l));
+        by_key[n + l].reserve(n_b(l));
+    }
+    for (const uint2 &x : entries)
+        if (n_b(x.x % n)) by_key[x.x].push_back(x.y);
+    for (uint32_t l = 0; l < n; l++) {
+        frog_surface_row &r = rows[l];
+        r.n_a = n_a(l); r.n_b = n_b(l);
+        r.sum_ab = r.sum_ba = 0;
+        r.max_ab = r.max_ba = r.pct_ab = r.pct_ba = 0xFFFFFFFFu;
+        if (!r.n_a || !r.n_b) continue;
+        if (by_key[l].size() != r.n_a || by_key[n + l].size() != r.n_b) return fail(FROG_E_HIP, std::string(where) + ": the distance list is incomplete");
+        r.sum_ab = sum[l]; r.sum_ba = sum[n + l];
+        r.max_ab = largest[l]; r.max_ba = largest[n + l];
+        r.pct_ab = edt_kth(by_key[l], ((uint64_t)a->percentile * r.n_a + 99) / 100);
+        r.pct_ba = edt_kth(by_key[n + l], ((uint64_t)a->percentile * r.n_b + 99) / 100);
+    }
     return FROG_OK;
 }
 
@@ -2676,5 +2913,51 @@ int frog_wlabels_probability(frog_wlabels *a, int64_t value, float *p)
 }
 
 void frog_wlabels_destroy(frog_wlabels *a) { group_destroy(a); }
+
+int frog_distance_map(const frog_volume *labels, int64_t value, int mode, int device, uint32_t *out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_distance_map", labels, out, &total)) return rc;
+    if (!labels->data) return fail(FROG_E_INVALID, "bad arguments to frog_distance_map");
+    if (!integer_voxel_type(labels->dtype)) return fail(FROG_E_INVALID, "frog_distance_map: a label volume has an integer type");
+    if (mode != 0 && mode != 1) return fail(FROG_E_INVALID, "frog_distance_map: mode 0 (the set) or 1 (its surface)");
+    if (!edt_spacing(labels)) return fail(FROG_E_INVALID, "frog_distance_map: the spacing must be positive and finite");
+    if (int rc = select_device(device)) return rc;
+    return with_integer_voxel_type(labels->dtype, [&](auto s) { return distance_map_typed<decltype(s)>(labels, total, (long long)value, mode, out); });
+}
+
+int frog_surface_create(const frog_volume *reference, const int64_t *values, uint32_t n_values, uint32_t percentile, int device,
+                        frog_surface **out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_surface_create", reference, out, &total)) return rc;
+    if (!values || !reference->data) return fail(FROG_E_INVALID, "bad arguments to frog_surface_create");
+    if (!integer_voxel_type(reference->dtype)) return fail(FROG_E_INVALID, "frog_surface_create: a label volume has an integer type");
+    if (!edt_spacing(reference)) return fail(FROG_E_INVALID, "frog_surface_create: the spacing must be positive and finite");
+    if (!n_values || n_values > FROG_SURFACE_MAX_LABELS)
+        return fail(FROG_E_INVALID, "frog_surface_create: 1 to " + std::to_string(FROG_SURFACE_MAX_LABELS) + " measured values");
+    for (uint32_t l = 1; l < n_values; l++)
+        if (values[l] <= values[l - 1]) return fail(FROG_E_INVALID, "frog_surface_create: the values must be strictly ascending");
+    if (percentile < 1 || percentile > 100) return fail(FROG_E_INVALID, "frog_surface_create: a percentile from 1 to 100");
+    std::unique_ptr<frog_surface> a;
+    if (int rc = group_new(reference, total, device, a)) return rc;
+    a->percentile = percentile;
+    a->values.assign(values, values + n_values);
+    if (int rc = with_integer_voxel_type(reference->dtype, [&](auto s) { return surface_create_typed<decltype(s)>(a.get(), reference); })) return rc;
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_surface_add(frog_surface *a, frog_chain *c, const frog_volume *src, double background, frog_surface_row *rows)
+{
+    if (!a || !src || !src->data || !rows) return fail(FROG_E_INVALID, "bad arguments to frog_surface_add");
+    if (!integer_voxel_type(src->dtype)) return fail(FROG_E_INVALID, "frog_surface_add: a label volume has an integer type");
+    if (!std::isfinite(background)) return fail(FROG_E_INVALID, "frog_surface_add: background is not finite");
+    if (int rc = add_inputs("frog_surface_add", a, c, src, nullptr)) return rc;
+    KCHECK(hipSetDevice(a->device));
+    return with_integer_voxel_type(src->dtype, [&](auto s) { return surface_add_typed<decltype(s)>(a, c, src, background, rows); });
+}
+
+void frog_surface_destroy(frog_surface *a) { group_destroy(a); }
 
 }

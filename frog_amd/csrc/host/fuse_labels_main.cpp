@@ -1,7 +1,7 @@
 // FuseLabels: majority-vote fusion of a registered group's label maps in one process (the reference has no counterpart: it
 // stops at one `VolumeTransform -i 0` per image and leaves the N resliced label volumes to a script).
 //   FuseLabels bbox.json spacing labels_0 ... labels_N-1 [-td transformsDir] [-o outDir] [-b background] [-ml maxLabels]
-//              [-p 1] [-wt 1] [-dev n] [-s 1 [-sp p0] [-st tol] [-si maxIter] [-sr 0|1]]
+//              [-p 1] [-wt 1] [-dev n] [-s 1 [-sp p0] [-st tol] [-si maxIter] [-sr 0|1]] [-d 1 [-dp percentile] [-dr 0|1]]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid); label map i goes through the inverse of <transformsDir>/<i>.json
 // (default "transforms") with nearest-neighbour interpolation exactly as `VolumeTransform labels_i dummy.mhd -t
 // transforms/i.json -i 0 -b <background>` does it (same device code; background 0 unless -b) and votes on the device
@@ -28,6 +28,19 @@
 //                               ((a - median) / (1.4826 MAD), 0 where the MAD is 0), and theta[i][l][l] per label
 //     -p 1                      staple_probability_<value>.nii.gz per label
 //                       and a line "staple : <iterations> iterations, change <c>, <A> active voxels".
+//   -d 1                surface distances of every image to the consensus (frog_surface, include/frog_chain.h: an exact
+//                       Euclidean distance transform on the device), after everything above is written.  The consensus is
+//                       labels.nii.gz (-dr 0) or staple.nii.gz (-dr 1, which needs -s 1); every value of the table except the
+//                       background (-b) is measured, at most 256.  The label maps are streamed a second time through
+//                       re-created chains.  -dp: the percentile p, 1 to 100 (95).  It adds, every floating-point column
+//                       printed with %.17g and in the unit of the spacing:
+//     surface.csv               image,file,label,surface_voxels,reference_surface_voxels,hausdorff,hausdorff_<p>,assd: one row
+//                               per image and label; nan where the label has no surface in the image or in the consensus
+//     surface_images.csv        image,file,labels_measured,mean_assd,mean_assd_robust_z,max_hausdorff: over the labels with
+//                               both surfaces; the robust z as performance.csv's, nan for an image with nothing measured
+//     surface_labels.csv        label,images_measured,mean_assd,max_hausdorff,mean_hausdorff_<p>: over the images
+//                       A mean is the sum in ascending order of the labels (of the images) from +0.0, over their number.
+//                       And a line "surface : <seconds> s" after the phase times.
 // Every option, transform and volume header is checked before anything is written; a float label file is an error.  Volumes are
 // read and inflated on host threads ahead of the device (volume_stream.h).
 #include "group_tool.h"
@@ -52,6 +65,38 @@ double median(std::vector<double> v)
     return n % 2 ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0;
 }
 
+// What a reader sees of a row, by the three lines of include/frog_chain.h; all nan when either surface is empty.
+struct SurfaceMetrics {
+    double hausdorff = NAN, hausdorff_p = NAN, assd = NAN;
+};
+
+SurfaceMetrics surface_metrics(const frog_surface_row &r)
+{
+    SurfaceMetrics m;
+    if (!r.n_a || !r.n_b) return m;
+    m.hausdorff = (double)std::max(r.max_ab, r.max_ba) * 0x1p-16;
+    m.hausdorff_p = (double)std::max(r.pct_ab, r.pct_ba) * 0x1p-16;
+    m.assd = ((double)(r.sum_ab + r.sum_ba) / (double)(r.n_a + r.n_b)) * 0x1p-16;
+    return m;
+}
+
+// %.17g, and nan without a sign
+std::string g17(double v)
+{
+    if (std::isnan(v)) return "nan";
+    char text[40];
+    std::snprintf(text, sizeof text, "%.17g", v);
+    return text;
+}
+
+// the sum of the values one by one from +0.0 over their number; nan for none
+double mean_in_order(const std::vector<double> &v)
+{
+    double total = 0.0;
+    for (const double x : v) total = total + x;
+    return v.empty() ? NAN : total / (double)v.size();
+}
+
 } // namespace
 
 int main(int argc, char *argv[])
@@ -59,11 +104,12 @@ int main(int argc, char *argv[])
     PhaseTimes times;
     std::vector<std::string> volumes;
     std::string transformsDir = "transforms", outDir = ".";
-    int device = 0, writeTransformed = 0, writeProbabilities = 0, staple = 0, stapleRestrict = 0;
-    long maxLabels = 0, stapleIterations = 50;
+    int device = 0, writeTransformed = 0, writeProbabilities = 0, staple = 0, stapleRestrict = 0, surface = 0, surfaceReference = 0;
+    long maxLabels = 0, stapleIterations = 50, surfacePercentile = 95;
     double background = 0, stapleP0 = 0.99, stapleTol = 1e-6;
     bool stapleOption = false;                              // one of -sp, -st, -si, -sr was given
-    int a = positional_arguments(argc, argv, 3, { "-td", "-o", "-b", "-ml", "-p", "-wt", "-dev", "-s", "-sp", "-st", "-si", "-sr" }, volumes);
+    bool surfaceOption = false;                             // one of -dp, -dr was given
+    int a = positional_arguments(argc, argv, 3, { "-td", "-o", "-b", "-ml", "-p", "-wt", "-dev", "-s", "-sp", "-st", "-si", "-sr", "-d", "-dp", "-dr" }, volumes);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
         if (std::strcmp(key, "-td") == 0) transformsDir = value;
@@ -78,11 +124,14 @@ int main(int argc, char *argv[])
         else if (std::strcmp(key, "-st") == 0) { stapleTol = atof(value); stapleOption = true; }
         else if (std::strcmp(key, "-si") == 0) { stapleIterations = atol(value); stapleOption = true; }
         else if (std::strcmp(key, "-sr") == 0) { stapleRestrict = atoi(value); stapleOption = true; }
+        else if (std::strcmp(key, "-d") == 0) surface = atoi(value);
+        else if (std::strcmp(key, "-dp") == 0) { surfacePercentile = atol(value); surfaceOption = true; }
+        else if (std::strcmp(key, "-dr") == 0) { surfaceReference = atoi(value); surfaceOption = true; }
         else die(std::string("unknown option ") + key);
     }
     if (argc < 4 || volumes.empty()) {
         std::cout << "Usage : FuseLabels bbox.json spacing labels_0 ... labels_N-1 [-td transformsDir] [-o outDir] [-b background] "
-                     "[-ml maxLabels] [-p 1] [-wt 1] [-dev n] [-s 1 [-sp p0] [-st tol] [-si maxIter] [-sr 0|1]]" << std::endl;
+                     "[-ml maxLabels] [-p 1] [-wt 1] [-dev n] [-s 1 [-sp p0] [-st tol] [-si maxIter] [-sr 0|1]] [-d 1 [-dp percentile] [-dr 0|1]]" << std::endl;
         return 1;
     }
     const size_t n = volumes.size();
@@ -96,6 +145,14 @@ int main(int argc, char *argv[])
         if (!(stapleTol >= 0.0)) die("-st : a tolerance that is not negative");
         if (stapleIterations < 0 || stapleIterations > 1000000) die("-si : 0 to 1000000 iterations");
         if (stapleRestrict != 0 && stapleRestrict != 1) die("-sr : 0 or 1");
+    }
+    if (surfaceOption && surface != 1) die("-dp and -dr need -d 1");
+    if (surface == 1) {
+        if (surfacePercentile < 1 || surfacePercentile > 100) die("-dp : a percentile from 1 to 100");
+        if (surfaceReference != 0 && surfaceReference != 1) die("-dr : 0 (the vote) or 1 (STAPLE)");
+        if (surfaceReference == 1 && staple != 1) die("-dr 1 measures against staple.nii.gz and needs -s 1");
+        // the table may hold the background beside the measured labels
+        if (maxLabels > FROG_SURFACE_MAX_LABELS + 1) die("-d 1 measures at most " + std::to_string(FROG_SURFACE_MAX_LABELS) + " labels (-ml)");
     }
 
     // ---- everything is checked before the first output: the grid, every transform, every volume header
@@ -191,6 +248,8 @@ int main(int argc, char *argv[])
     }
     frog_labels_destroy(acc);
     std::cout << n_labels << " labels" << std::endl;
+    std::vector<unsigned char> vote;                        // labels.nii.gz's voxels, where STAPLE is about to take their place
+    if (em && surface == 1 && surfaceReference == 0) vote = fused;
     if (em) {
         t0 = clk::now();
         uint32_t L = 0, iterations = 0;
@@ -277,6 +336,103 @@ int main(int argc, char *argv[])
         std::snprintf(line, sizeof line, "staple : %u iterations, change %.17g, %llu active voxels", iterations, change, (unsigned long long)active);
         std::cout << line << std::endl;
     }
+    // ---- -d 1: every image's surface distances to the consensus, the label maps streamed a second time
+    double surface_s = 0;
+    if (surface == 1) {
+        t0 = clk::now();
+        std::vector<int64_t> measured;
+        for (const int64_t v : values) if ((double)v != background) measured.push_back(v);
+        if (measured.empty()) die("-d 1 : the table holds no label besides the background");
+        if (measured.size() > FROG_SURFACE_MAX_LABELS) die("-d 1 measures at most " + std::to_string(FROG_SURFACE_MAX_LABELS) + " labels");
+        const size_t L = measured.size();
+        label.data = vote.empty() ? fused.data() : vote.data();
+        frog_surface *sd = nullptr;
+        if (frog_surface_create(&label, measured.data(), (uint32_t)L, (uint32_t)surfacePercentile, device, &sd)) die(frog_last_error());
+        chains = create_chains(inverse, device);
+        frog::VolumeStream again(volumes, threads, window);
+        std::vector<frog_surface_row> rows(n * L);
+        for (size_t i = 0; i < n; i++) {
+            frog::VolumeStream::Item &it = again.get(i, nullptr);
+            if (!it.file) die("cannot read volume " + volumes[i]);
+            if (frog_surface_add(sd, chains[i], &it.view, background, &rows[i * L])) die(volumes[i] + ": " + frog_last_error());
+            again.release(i);
+            frog_chain_destroy(chains[i]);
+            chains[i] = nullptr;
+        }
+        frog_surface_destroy(sd);
+
+        const std::string p = std::to_string(surfacePercentile);
+        const std::string rows_csv = outDir + "/surface.csv", images_csv = outDir + "/surface_images.csv", labels_csv = outDir + "/surface_labels.csv";
+        csv = std::fopen(rows_csv.c_str(), "w");
+        if (!csv) die("cannot write " + rows_csv);
+        std::fprintf(csv, "image,file,label,surface_voxels,reference_surface_voxels,hausdorff,hausdorff_%s,assd\n", p.c_str());
+        std::vector<SurfaceMetrics> metrics(n * L);
+        for (size_t i = 0; i < n; i++) {
+            for (size_t l = 0; l < L; l++) {
+                const frog_surface_row &r = rows[i * L + l];
+                const SurfaceMetrics &m = metrics[i * L + l] = surface_metrics(r);
+                std::fprintf(csv, "%zu,%s,%lld,%llu,%llu,%s,%s,%s\n", i, volumes[i].c_str(), (long long)measured[l], (unsigned long long)r.n_a,
+                             (unsigned long long)r.n_b, g17(m.hausdorff).c_str(), g17(m.hausdorff_p).c_str(), g17(m.assd).c_str());
+            }
+        }
+        if (std::fclose(csv) != 0) die("cannot write " + rows_csv);
+
+        std::vector<double> mean_assd(n), largest(n);
+        std::vector<size_t> labels_measured(n);
+        for (size_t i = 0; i < n; i++) {
+            std::vector<double> assd;
+            largest[i] = NAN;
+            for (size_t l = 0; l < L; l++) {
+                const SurfaceMetrics &m = metrics[i * L + l];
+                if (std::isnan(m.assd)) continue;
+                assd.push_back(m.assd);
+                if (std::isnan(largest[i]) || m.hausdorff > largest[i]) largest[i] = m.hausdorff;
+            }
+            labels_measured[i] = assd.size();
+            mean_assd[i] = mean_in_order(assd);
+        }
+        std::vector<double> finite;
+        for (const double x : mean_assd) if (std::isfinite(x)) finite.push_back(x);
+        double mid = 0, mad = 0;
+        if (!finite.empty()) {
+            mid = median(finite);
+            for (double &x : finite) x = std::fabs(x - mid);
+            mad = median(finite);
+        }
+        csv = std::fopen(images_csv.c_str(), "w");
+        if (!csv) die("cannot write " + images_csv);
+        std::fprintf(csv, "image,file,labels_measured,mean_assd,mean_assd_robust_z,max_hausdorff\n");
+        for (size_t i = 0; i < n; i++) {
+            const double z = !std::isfinite(mean_assd[i]) ? NAN : (mad > 0 ? (mean_assd[i] - mid) / (1.4826 * mad) : 0.0);
+            std::fprintf(csv, "%zu,%s,%zu,%s,%s,%s\n", i, volumes[i].c_str(), labels_measured[i], g17(mean_assd[i]).c_str(), g17(z).c_str(),
+                         g17(largest[i]).c_str());
+        }
+        if (std::fclose(csv) != 0) die("cannot write " + images_csv);
+
+        csv = std::fopen(labels_csv.c_str(), "w");
+        if (!csv) die("cannot write " + labels_csv);
+        std::fprintf(csv, "label,images_measured,mean_assd,max_hausdorff,mean_hausdorff_%s\n", p.c_str());
+        for (size_t l = 0; l < L; l++) {
+            std::vector<double> assd, hausdorff_p;
+            double top = NAN;
+            for (size_t i = 0; i < n; i++) {
+                const SurfaceMetrics &m = metrics[i * L + l];
+                if (std::isnan(m.assd)) continue;
+                assd.push_back(m.assd);
+                hausdorff_p.push_back(m.hausdorff_p);
+                if (std::isnan(top) || m.hausdorff > top) top = m.hausdorff;
+            }
+            std::fprintf(csv, "%lld,%zu,%s,%s,%s\n", (long long)measured[l], assd.size(), g17(mean_in_order(assd)).c_str(), g17(top).c_str(),
+                         g17(mean_in_order(hausdorff_p)).c_str());
+        }
+        if (std::fclose(csv) != 0) die("cannot write " + labels_csv);
+        surface_s = seconds(t0);
+    }
     times.print(stream.read_seconds(), stream.threads());
+    if (surface == 1) {
+        char line[64];
+        std::snprintf(line, sizeof line, "surface : %.3f s", surface_s);
+        std::cout << line << std::endl;
+    }
     return 0;
 }

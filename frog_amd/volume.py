@@ -651,3 +651,121 @@ def atlas_segment(target, images, label_maps, chains=None, target_chain=None, gr
         return fused, confidence, acc.values()
     finally:
         acc.close()
+
+
+SURFACE_ROW = np.dtype([("n_a", np.uint64), ("n_b", np.uint64), ("sum_ab", np.uint64), ("sum_ba", np.uint64),
+                        ("max_ab", np.uint32), ("max_ba", np.uint32), ("pct_ab", np.uint32), ("pct_ba", np.uint32)])
+assert SURFACE_ROW.itemsize == C.sizeof(_abi.FrogSurfaceRow)
+
+
+def distance_map(volume, value, spacing=(1.0, 1.0, 1.0), mode=0, device=0):
+    """The exact Euclidean distance transform of an integer label map on the device (frog_distance_map,
+    include/frog_chain.h): per voxel of `volume`[z, y, x] the distance to the set {volume == value} (mode 0) or to that set's
+    surface voxels (mode 1) at `spacing`(x, y, z), as uint32 fixed point in units of 2^-16; 0xFFFFFFFF where the set is
+    empty."""
+    a = np.ascontiguousarray(volume)
+    v = _abi.volume_view(a, (0.0, 0.0, 0.0), tuple(float(s) for s in spacing))
+    out = np.empty(a.shape, np.uint32)
+    _abi.check(_abi.hip_lib().frog_distance_map(C.byref(v), int(value), int(mode), int(device), out.ctypes.data_as(_abi.c_u32_p)),
+               "frog_distance_map")
+    return out
+
+
+class SurfaceDistances(_Accumulator):
+    """frog_surface (include/frog_chain.h): the surface distances of label maps to `reference`[z, y, x] for the label
+    `values` (strictly ascending).  `grid_or_spacing`: the reference's spacing(x, y, z) (origin 0), or its grid (dims(x, y, z),
+    origin, spacing).  The distance maps of the reference are computed once, here."""
+
+    _NAME = "surface"
+
+    def __init__(self, reference, values, grid_or_spacing=(1.0, 1.0, 1.0), percentile=95, device=0):
+        self._h = None
+        ref = np.ascontiguousarray(reference)
+        if ref.ndim != 3:
+            raise ValueError("a 3-D reference label map expected")
+        if np.ndim(grid_or_spacing[0]) == 0:
+            origin, spacing = (0.0, 0.0, 0.0), tuple(float(s) for s in grid_or_spacing)
+        else:
+            dims, origin, spacing = grid_or_spacing
+            if tuple(int(d) for d in dims) != ref.shape[::-1]:
+                raise ValueError("the reference's shape differs from the grid's dims")
+        if not 0 <= int(percentile) < 2 ** 32:
+            raise ValueError("a percentile from 1 to 100")
+        self._lib = _abi.hip_lib()
+        self.dims = ref.shape[::-1]
+        self.values = np.ascontiguousarray(values, np.int64).ravel()
+        self.percentile = int(percentile)
+        self._grid = _abi.volume_view(None, origin, spacing, self.dims)
+        view = _abi.volume_view(ref, origin, spacing)
+        h = C.c_void_p()
+        _abi.check(self._lib.frog_surface_create(C.byref(view), self.values.ctypes.data_as(C.POINTER(C.c_int64)), len(self.values),
+                                                 self.percentile, int(device), C.byref(h)), "frog_surface_create")
+        self._h = h
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, volume, chain=None, background=0.0):
+        """One image's rows, a SURFACE_ROW array with an entry per value.  `volume` as in Labels.add: an integer label map
+        ((voxels, origin, spacing), or an array already on the grid when chain is None), through `chain` with
+        nearest-neighbour interpolation.  Adds are independent of each other."""
+        _, src, _, _, _ = self._views(volume)
+        rows = np.zeros(len(self.values), SURFACE_ROW)
+        _abi.check(self._lib.frog_surface_add(self._h, chain._h if chain is not None else None, src, float(background),
+                                              rows.ctypes.data_as(C.POINTER(_abi.FrogSurfaceRow))), "frog_surface_add")
+        return rows
+
+
+def surface_metrics(rows):
+    """(hausdorff, hausdorff_p, assd) of SURFACE_ROW rows, float64 in the spacing's unit, by the three lines of
+    include/frog_chain.h: max(max_ab, max_ba) * 2^-16, max(pct_ab, pct_ba) * 2^-16 and
+    ((sum_ab + sum_ba) / (n_a + n_b)) * 2^-16; NaN where either surface is empty."""
+    rows = np.asarray(rows)
+    empty = (rows["n_a"] == 0) | (rows["n_b"] == 0)
+    scale = 2.0 ** -16
+    hausdorff = np.maximum(rows["max_ab"], rows["max_ba"]).astype(np.float64) * scale
+    hausdorff_p = np.maximum(rows["pct_ab"], rows["pct_ba"]).astype(np.float64) * scale
+    count = np.where(empty, np.uint64(1), rows["n_a"] + rows["n_b"])
+    assd = ((rows["sum_ab"] + rows["sum_ba"]).astype(np.float64) / count.astype(np.float64)) * scale
+    for m in (hausdorff, hausdorff_p, assd):
+        m[empty] = np.nan
+    return hausdorff, hausdorff_p, assd
+
+
+def _mean_in_order(values):
+    """The sum of `values` one by one from +0.0, over their number (surface_images.csv and surface_labels.csv form their
+    means this way); NaN for none."""
+    total = 0.0
+    for v in values:
+        total = total + float(v)
+    return total / len(values) if len(values) else float("nan")
+
+
+def surface_distances(volumes, reference, values=None, chains=None, grid=None, background=0.0, percentile=95, device=0):
+    """The surface distances of a group's label maps to a consensus (bin/FuseLabels -d 1).  `volumes`, `chains` and `grid` as
+    in fuse_labels(); `reference`[z, y, x] is an integer label map on the grid; `values`: the labels to measure, default every
+    value of the reference except `background`.  Returns a dict: values; rows (SURFACE_ROW, images x values); hausdorff,
+    hausdorff_p, assd (surface_metrics of the rows); per image labels_measured, mean_assd, mean_assd_robust_z (robust_z) and
+    max_hausdorff over the labels with both surfaces; per label images_measured, label_mean_assd, label_max_hausdorff and
+    label_mean_hausdorff_p over the images.  Means are sums in ascending order from +0.0 over the count."""
+    vols, grid = _group(volumes, chains, None, grid)
+    ref = np.ascontiguousarray(reference)
+    if values is None:
+        values = [int(v) for v in np.unique(ref) if float(v) != float(background)]
+    with SurfaceDistances(ref, values, grid, percentile, device) as acc:
+        rows = np.stack([acc.add(v, None if chains is None else chains[k], background) for k, v in enumerate(vols)])
+    hausdorff, hausdorff_p, assd = surface_metrics(rows)
+    measured = ~np.isnan(assd)
+    nan = float("nan")
+    out = {"values": np.ascontiguousarray(values, np.int64), "rows": rows, "hausdorff": hausdorff, "hausdorff_p": hausdorff_p, "assd": assd,
+           "labels_measured": measured.sum(1), "images_measured": measured.sum(0),
+           "mean_assd": np.array([_mean_in_order(a[m]) for a, m in zip(assd, measured)]),
+           "max_hausdorff": np.array([h[m].max() if m.any() else nan for h, m in zip(hausdorff, measured)]),
+           "label_mean_assd": np.array([_mean_in_order(a[m]) for a, m in zip(assd.T, measured.T)]),
+           "label_max_hausdorff": np.array([h[m].max() if m.any() else nan for h, m in zip(hausdorff.T, measured.T)]),
+           "label_mean_hausdorff_p": np.array([_mean_in_order(h[m]) for h, m in zip(hausdorff_p.T, measured.T)])}
+    out["mean_assd_robust_z"] = robust_z(out["mean_assd"])
+    return out

@@ -450,6 +450,67 @@ int  frog_wlabels_fused(frog_wlabels *a, int64_t fill_label, frog_volume *label,
 int  frog_wlabels_probability(frog_wlabels *a, int64_t value, float *p);
 void frog_wlabels_destroy(frog_wlabels *a);
 
+/* ---- surface distances between label maps: an exact Euclidean distance transform (an extension; the reference has no
+ * counterpart) ---------------------------------------------------------------------------------------------------------------
+ * How far apart are the boundaries of a structure in two label maps, in the spacing's unit: the Hausdorff distance, a
+ * percentile of it and the average symmetric surface distance.  Every line below is one separately rounded f64 operation or an
+ * integer operation (no contraction), every sum, maximum and order statistic is integer arithmetic: what leaves the library is
+ * the same bits from run to run and however the work is cut into launches.
+ *   Surface.  For a label map m on a grid and a value l, A = {v : m[v] == l}.  A voxel of A is a SURFACE VOXEL if at least one
+ *     of its six face neighbours is not in A; a neighbour outside the grid counts as not in A.
+ *   Distance transform of a voxel set F (the features) at spacing (sx, sy, sz):
+ *     g1[x,y,z] = min over q of ( F[q,y,z] ? ((double)(x - q) * sx)^2 : +inf )
+ *     g2[x,y,z] = min over q of ( g1[x,q,z] + ((double)(y - q) * sy)^2 )
+ *     g3[x,y,z] = min over q of ( g2[x,y,q] + ((double)(z - q) * sz)^2 )
+ *     d * d is one multiplication, the + one addition.  The minimum of f64 values does not depend on the order it is taken in,
+ *     so every method that returns the true minimum of these expressions returns these bits.
+ *   Stored distance: unsigned 32-bit fixed point in units of 2^-16 of the spacing's unit,
+ *     u = (g3 == +inf) ? 0xFFFFFFFF : min(0xFFFFFFFE, (uint64)llrint(sqrt(g3) * 65536.0))
+ *     with the correctly rounded f64 square root and rounding to nearest even.  0xFFFFFFFF: there is no feature.
+ *   Per image and measured value: A the image's set and S_A its surface voxels, B the reference's set and S_B its surface
+ *     voxels, D_B the transform with F = S_B and D_A the one with F = S_A.
+ *       n_a = |S_A|;  n_b = |S_B|
+ *       sum_ab = sum over v in S_A of D_B[v];  sum_ba = sum over v in S_B of D_A[v]                       (u64)
+ *       max_ab, max_ba: the largest of those distances                                                    (u32)
+ *       pct_ab = the k-th smallest of {D_B[v] : v in S_A}, k = (p * n_a + 99) / 100 (1-based, integer division); pct_ba likewise
+ *       with D_A, S_B and n_b.  p = 100 is the maximum.
+ *     If n_a == 0 or n_b == 0 both sums are 0 and the four distances are 0xFFFFFFFF.
+ *   What users read is formed from the row on the host, here and nowhere else:
+ *       hausdorff   = (double)max(max_ab, max_ba) * 2^-16
+ *       hausdorff_p = (double)max(pct_ab, pct_ba) * 2^-16
+ *       assd        = ((double)(sum_ab + sum_ba) / (double)(n_a + n_b)) * 2^-16
+ *     all three NaN when n_a == 0 or n_b == 0.
+ * Device memory of an accumulator on V voxels with n measured values: 4 n V bytes (one map D_B per value), 6 V bytes (the
+ * reference's and the current image's dense label index and surface mask), two f64 planes of the largest bounding box of an
+ * image's and the reference's set of one value (at most 16 V bytes), 8 bytes per surface voxel of the image and the reference,
+ * and the staging of one source volume and of its resliced copy.
+ * FROG_E_INVALID, before the device is touched: a NULL argument, a float volume, an empty grid or one above 2^31 voxels, a
+ * spacing that is not positive and finite, n_values == 0 or > FROG_SURFACE_MAX_LABELS, values that are not strictly ascending,
+ * a percentile outside 1..100, a mode other than 0 or 1; in add a background that is not finite, a chain on another device, a
+ * source without a chain whose dims differ from the grid's.  A refused device allocation is FROG_E_NOMEM: a failed create leaves
+ * nothing allocated, a failed add leaves the accumulator as it was. */
+#define FROG_SURFACE_MAX_LABELS 256
+/* out[v] = the stored distance from voxel v to the set {labels == value} (mode 0) or to that set's surface voxels (mode 1), at
+ * labels->spacing.  `labels` has one of the six integer types; host arrays, out has one uint32 per voxel, x fastest. */
+int  frog_distance_map(const frog_volume *labels, int64_t value, int mode, int device, uint32_t *out);
+
+typedef struct frog_surface_row {
+    uint64_t n_a, n_b, sum_ab, sum_ba;
+    uint32_t max_ab, max_ba, pct_ab, pct_ba;
+} frog_surface_row;
+typedef struct frog_surface frog_surface;
+/* `reference`: an integer label volume with host data; its dims, origin and spacing are the grid.  `values`: the n_values
+ * measured label values, strictly ascending (signed).  The maps D_B of all values are computed here. */
+int  frog_surface_create(const frog_volume *reference, const int64_t *values, uint32_t n_values, uint32_t percentile,
+                         int device, frog_surface **out);
+/* One image against the reference.  The image's label at a grid voxel is taken exactly as frog_labels_add takes it: with a
+ * chain the voxel frog_chain_reslice(chain, source, out, 0, background) stores there (the same device code), with
+ * chain == NULL the source's own voxel (its dims must equal the grid's).  A label of the image that is not in `values` is
+ * measured nowhere; it still ends its neighbours' sets, so it makes surface.  rows[j] is the row of values[j].  The call keeps
+ * nothing of the image: adds are independent of each other and of their order. */
+int  frog_surface_add(frog_surface *a, frog_chain *chain, const frog_volume *source, double background, frog_surface_row *rows);
+void frog_surface_destroy(frog_surface *a);
+
 #ifdef __cplusplus
 }
 #endif
