@@ -340,6 +340,17 @@ HIP_SYMBOLS = {
     "frog_wlabels_fused": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(FrogVolume), c_float_p]),
     "frog_wlabels_probability": (C.c_int, [C.c_void_p, C.c_int64, c_float_p]),
     "frog_wlabels_destroy": (None, [C.c_void_p]),
+    "frog_jlabels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_int,
+                                      C.POINTER(C.c_void_p)]),
+    "frog_jlabels_target": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_int, C.c_double, C.POINTER(FrogVolume)]),
+    "frog_jlabels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double,
+                                   C.c_double, C.POINTER(FrogVolume), C.POINTER(FrogVolume)]),
+    "frog_jlabels_finish": (C.c_int, [C.c_void_p, c_u32_p]),
+    "frog_jlabels_values": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "frog_jlabels_fused": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(FrogVolume), c_float_p]),
+    "frog_jlabels_probability": (C.c_int, [C.c_void_p, C.c_int64, c_float_p]),
+    "frog_jlabels_weight": (C.c_int, [C.c_void_p, C.c_uint32, c_float_p]),
+    "frog_jlabels_destroy": (None, [C.c_void_p]),
     "frog_distance_map": (C.c_int, [C.POINTER(FrogVolume), C.c_int64, C.c_int, C.c_int, c_u32_p]),
     "frog_surface_create": (C.c_int, [C.POINTER(FrogVolume), C.POINTER(C.c_int64), C.c_uint32, C.c_uint32, C.c_int,
                                       C.POINTER(C.c_void_p)]),

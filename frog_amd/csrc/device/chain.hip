@@ -1045,6 +1045,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 #include "k_rank.hip.h"
 #include "k_staple.hip.h"
 #include "k_edt.hip.h"
+#include "k_joint.hip.h"
 
 } // namespace
 
@@ -1126,6 +1127,17 @@ struct frog_wlabels : frog_group {
     std::vector<uint32_t> dense;                    // table position -> dense index
     frog::DevBuf<float *> d_sorted_planes;
     frog::DevBuf<long long> d_sorted_values;
+};
+
+// joint label fusion: frog_wlabels' target plane, label map and score planes, and what the adds leave for finish
+struct frog_jlabels : frog_wlabels {
+    uint32_t beta = 0;
+    double alpha = 0;
+    frog::DevBuf<float> d_atlases, d_weights;       // n_images planes each; d_weights only with keep_weights
+    std::deque<frog::DevBuf<unsigned char>> label_maps;     // the added atlases' label maps on the grid, in their own types
+    std::vector<int> ltypes;
+    frog::DevBuf<const void *> d_label_maps;
+    frog::DevBuf<int> d_ltypes;
 };
 
 // the dense label index of every image at every voxel of one grid, and the EM state of frog_staple_solve
@@ -1651,10 +1663,11 @@ WlabelsTiles wlabels_tiles(const frog_wlabels *a)
 }
 
 template <class S>
-int wlabels_target_typed(frog_wlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+int wlabels_target_typed(const char *where, frog_wlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background,
+                         frog_volume *resliced)
 {
     ResliceGrid g;
-    if (int rc = stage_source<S>("frog_wlabels_target", a, src, c && resliced, interpolation, background, &g)) return rc;
+    if (int rc = stage_source<S>(where, a, src, c && resliced, interpolation, background, &g)) return rc;
     const S *d_src = (const S *)a->d_src.p;
     S *d_out = resliced ? (S *)a->d_out.p : nullptr;
     const hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
@@ -1665,7 +1678,7 @@ int wlabels_target_typed(frog_wlabels *a, frog_chain *c, const frog_volume *src,
             wlabels_collect_kernel<S, false, false><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, nullptr, 0, g, a->total, a->d_target.p,
                                                                               nullptr, nullptr, a->map);
     });
-    return return_resliced<S>("frog_wlabels_target", a, c, src, resliced, e);
+    return return_resliced<S>(where, a, c, src, resliced, e);
 }
 
 // S: the image's type; the label map's is a run-time argument of the kernels
@@ -1720,6 +1733,92 @@ int wlabels_add_typed(frog_wlabels *a, frog_chain *c, const frog_volume *image, 
         else std::memcpy(resliced_labels->data, labels->data, a->total * label_bytes);
     }
     return return_resliced<S>("frog_wlabels_add", a, c, image, resliced_image, e);
+}
+
+// An add of frog_jlabels: phase 1 of wlabels_add_typed into the atlas' own plane and label map, which stay for finish.
+template <class S>
+int jlabels_add_typed(frog_jlabels *a, frog_chain *c, const frog_volume *image, const frog_volume *labels, int interpolation,
+                      double image_background, double label_background, frog_volume *resliced_image, frog_volume *resliced_labels)
+{
+    ResliceGrid g;
+    if (int rc = stage_source<S>("frog_jlabels_add", a, image, c && resliced_image, interpolation, image_background, &g)) return rc;
+    const size_t label_bytes = frog_volume_voxel_bytes(labels->dtype), n_labels_src = voxel_count(labels);
+    frog::DevBuf<unsigned char> on_grid;
+    KCHECK(on_grid.alloc(a->total * label_bytes));
+    if (c) KCHECK(a->d_lsrc.alloc(n_labels_src * label_bytes));
+    unsigned char *const d_lsrc = c ? a->d_lsrc.p : on_grid.p;             // without a chain the map is on the grid as it is
+    KCHECK(hipMemcpy(d_lsrc, labels->data, n_labels_src * label_bytes, hipMemcpyHostToDevice));
+    const ResliceGrid lg = reslice_grid(labels, &a->grid, 0, label_background);
+    const int ltype = labels->dtype;
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = resliced_image ? (S *)a->d_out.p : nullptr;
+    float *const plane = a->d_atlases.p + (size_t)a->added * a->total;
+    uint32_t state[2] = { 0, 0 };
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            wlabels_collect_kernel<S, true, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, d_lsrc, ltype, lg,
+                                                                            a->total, plane, d_out, on_grid.p, a->map);
+        else
+            wlabels_collect_kernel<S, false, true><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, d_lsrc, ltype, lg, a->total, plane,
+                                                                             nullptr, nullptr, a->map);
+    });
+    if (e == hipSuccess) e = hipMemcpy(state, a->d_state.p, sizeof state, hipMemcpyDeviceToHost);
+    // as in labels_add_typed: from here on the map may hold values without a plane, and every failure takes them back
+    auto refuse = [&](int rc) { (void)labels_reset_map(a); return rc; };
+    if (e != hipSuccess) return refuse(hip_fail("frog_jlabels_add", e));
+    if (state[1] || state[0] > a->max_labels)
+        return refuse(fail(FROG_E_INVALID, "frog_jlabels_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
+    e = labels_grow_planes<float>(a->total, state[0], a->d_values.p, a->known, a->planes, a->d_planes.p);
+    if (e != hipSuccess) return refuse(hip_fail("frog_jlabels_add", e));
+    if (resliced_labels) {
+        if (c) e = hipMemcpy(resliced_labels->data, on_grid.p, a->total * label_bytes, hipMemcpyDeviceToHost);
+        else std::memcpy(resliced_labels->data, labels->data, a->total * label_bytes);
+    }
+    const int rc = return_resliced<S>("frog_jlabels_add", a, c, image, resliced_image, e);
+    if (rc != FROG_OK) return rc;
+    a->label_maps.emplace_back();
+    a->label_maps.back().swap(on_grid);
+    a->ltypes.push_back(ltype);
+    return FROG_OK;
+}
+
+// finish of frog_jlabels: the solve and the votes of every voxel (k_joint.hip.h)
+int jlabels_solve(frog_jlabels *a)
+{
+    const int n = (int)a->n_images, radius = (int)a->radius;
+    std::vector<const void *> maps;
+    for (const auto &m : a->label_maps) maps.push_back(m.p);
+    KCHECK(a->d_label_maps.alloc(maps.size()));
+    KCHECK(a->d_ltypes.alloc(maps.size()));
+    KCHECK(hipMemcpy(a->d_label_maps.p, maps.data(), maps.size() * sizeof(const void *), hipMemcpyHostToDevice));
+    KCHECK(hipMemcpy(a->d_ltypes.p, a->ltypes.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (a->d_weights.p) KCHECK(hipMemset(a->d_weights.p, 0, (size_t)n * a->total * sizeof(float)));
+    JointArgs j{};
+    j.target = a->d_target.p; j.atlases = a->d_atlases.p; j.labels = a->d_label_maps.p; j.ltypes = a->d_ltypes.p;
+    j.weights = a->d_weights.p; j.planes = a->d_planes.p; j.n_planes = (uint32_t)a->known.size(); j.map = a->map;
+    j.total = a->total;
+    j.nx = a->grid.dims[0]; j.ny = a->grid.dims[1]; j.nz = a->grid.dims[2];
+    j.runs = (j.nx + JL_RUN - 1) / JL_RUN;
+    j.tiles = (size_t)j.runs * j.ny * j.nz;
+    j.n = n; j.radius = radius; j.beta = (int)a->beta; j.alpha = a->alpha;
+    // lanes per voxel and pairs per lane: the smallest that hold the n (n + 1) / 2 pairs and the n + 1 planes of the statistics
+    const int pairs = n * (n + 1) / 2;
+    const int lanes = n <= 10 ? 32 : 64, ppl = pairs <= 128 ? 2 : pairs <= 256 ? 4 : pairs <= 384 ? 6 : 9;
+    const size_t scratch = (size_t)(64 / lanes) * joint_group_doubles(n, radius) * sizeof(double);
+    const size_t staged = scratch + joint_staged_floats(n, radius) * sizeof(float);
+    j.staged = staged <= JL_LDS_BUDGET;
+    const size_t lds = j.staged ? staged : scratch;
+    // one block of 64 threads per tile: the work-items are the tiles times LAUNCH_BLOCK, so a launch chunk never splits a tile
+    hipError_t e = chunked_launch(j.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
+        if (lanes == 32) jlabels_solve_kernel<32, 2><<<blocks, 64, lds>>>(base, j);
+        else if (ppl == 2) jlabels_solve_kernel<64, 2><<<blocks, 64, lds>>>(base, j);
+        else if (ppl == 4) jlabels_solve_kernel<64, 4><<<blocks, 64, lds>>>(base, j);
+        else if (ppl == 6) jlabels_solve_kernel<64, 6><<<blocks, 64, lds>>>(base, j);
+        else jlabels_solve_kernel<64, 9><<<blocks, 64, lds>>>(base, j);
+    });
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail("frog_jlabels_finish", e);
+    return FROG_OK;
 }
 
 template <class T>
@@ -2823,7 +2922,7 @@ int frog_wlabels_target(frog_wlabels *a, frog_chain *c, const frog_volume *src, 
     if (a->has_target) return fail(FROG_E_INVALID, "frog_wlabels_target: the target is given once, before the first add");
     if (int rc = add_inputs("frog_wlabels_target", a, c, src, resliced)) return rc;
     KCHECK(hipSetDevice(a->device));
-    const int rc = with_voxel_type(src->dtype, [&](auto s) { return wlabels_target_typed<decltype(s)>(a, c, src, interpolation, background, resliced); });
+    const int rc = with_voxel_type(src->dtype, [&](auto s) { return wlabels_target_typed<decltype(s)>("frog_wlabels_target", a, c, src, interpolation, background, resliced); });
     if (rc == FROG_OK) a->has_target = true;
     return rc;
 }
@@ -2913,6 +3012,109 @@ int frog_wlabels_probability(frog_wlabels *a, int64_t value, float *p)
 }
 
 void frog_wlabels_destroy(frog_wlabels *a) { group_destroy(a); }
+
+int frog_jlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, uint32_t radius, uint32_t beta, double alpha,
+                        int keep_weights, int device, frog_jlabels **out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_jlabels_create", grid, out, &total)) return rc;
+    if (!n_images || n_images > (uint32_t)JL_MAX_N) return fail(FROG_E_INVALID, "frog_jlabels_create: 1 to 32 images");
+    if (max_labels > 65536) return fail(FROG_E_INVALID, "frog_jlabels_create: max_labels above 65536");
+    if (radius < 1 || radius > 3) return fail(FROG_E_INVALID, "frog_jlabels_create: a radius from 1 to 3");
+    if (beta < 1 || beta > 4) return fail(FROG_E_INVALID, "frog_jlabels_create: a beta from 1 to 4");
+    if (!(std::isfinite(alpha) && alpha > 0.0)) return fail(FROG_E_INVALID, "frog_jlabels_create: a finite alpha above 0");
+    std::unique_ptr<frog_jlabels> a;
+    if (int rc = group_new(grid, total, device, a)) return rc;
+    a->n_images = n_images;
+    a->max_labels = max_labels ? max_labels : 1024;
+    a->radius = radius;
+    a->beta = beta;
+    a->alpha = alpha;
+    KCHECK(a->d_target.alloc(total));
+    KCHECK(a->d_atlases.alloc((size_t)n_images * total));
+    if (keep_weights) KCHECK(a->d_weights.alloc((size_t)n_images * total));
+    if (int rc = labels_new_map(a.get())) return rc;
+    KCHECK(a->d_planes.alloc(a->max_labels));
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_jlabels_target(frog_jlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+{
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_target");
+    if (a->has_target) return fail(FROG_E_INVALID, "frog_jlabels_target: the target is given once, before the first add");
+    if (int rc = add_inputs("frog_jlabels_target", a, c, src, resliced)) return rc;
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_voxel_type(src->dtype, [&](auto s) {
+        return wlabels_target_typed<decltype(s)>("frog_jlabels_target", a, c, src, interpolation, background, resliced);
+    });
+    if (rc == FROG_OK) a->has_target = true;
+    return rc;
+}
+
+int frog_jlabels_add(frog_jlabels *a, frog_chain *c, const frog_volume *image, const frog_volume *labels, int interpolation,
+                     double image_background, double label_background, frog_volume *resliced_image, frog_volume *resliced_labels)
+{
+    if (!a || !image || !image->data || !frog_volume_voxel_bytes(image->dtype) || !labels || !labels->data)
+        return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_add");
+    if (!integer_voxel_type(labels->dtype)) return fail(FROG_E_INVALID, "frog_jlabels_add: a label volume has an integer type");
+    if (!std::isfinite(image_background) || !std::isfinite(label_background)) return fail(FROG_E_INVALID, "frog_jlabels_add: background is not finite");
+    if (!a->has_target) return fail(FROG_E_INVALID, "frog_jlabels_add: before frog_jlabels_target");
+    if (a->finished || a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_jlabels_add: more atlases than n_images");
+    if (int rc = add_inputs("frog_jlabels_add", a, c, image, resliced_image)) return rc;
+    if (int rc = add_inputs("frog_jlabels_add", a, c, labels, resliced_labels)) return rc;
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_voxel_type(image->dtype, [&](auto s) {
+        return jlabels_add_typed<decltype(s)>(a, c, image, labels, interpolation, image_background, label_background, resliced_image, resliced_labels);
+    });
+    if (rc == FROG_OK) a->added++;
+    return rc;
+}
+
+int frog_jlabels_finish(frog_jlabels *a, uint32_t *n_labels)
+{
+    if (!a || !n_labels) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_finish");
+    if (a->added != a->n_images) return fail(FROG_E_INVALID, "frog_jlabels_finish: fewer atlases added than n_images");
+    if (!a->finished) {
+        KCHECK(hipSetDevice(a->device));
+        if (int rc = jlabels_solve(a)) return rc;
+    }
+    return frog_wlabels_finish(a, n_labels);        // the table, as for frog_wlabels' scores
+}
+
+int frog_jlabels_values(frog_jlabels *a, int64_t *values)
+{
+    if (!a || !values) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_values");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_jlabels_values: before frog_jlabels_finish");
+    return frog_wlabels_values(a, values);
+}
+
+int frog_jlabels_fused(frog_jlabels *a, int64_t fill_label, frog_volume *label, float *confidence)
+{
+    if (!a || (!label && !confidence) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_fused");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_jlabels_fused: before frog_jlabels_finish");
+    return frog_wlabels_fused(a, fill_label, label, confidence);
+}
+
+int frog_jlabels_probability(frog_jlabels *a, int64_t value, float *p)
+{
+    if (!a || !p) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_probability");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_jlabels_probability: before frog_jlabels_finish");
+    return frog_wlabels_probability(a, value, p);
+}
+
+int frog_jlabels_weight(frog_jlabels *a, uint32_t image_index, float *w)
+{
+    if (!a || !w) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_weight");
+    if (!a->d_weights.p) return fail(FROG_E_INVALID, "frog_jlabels_weight: the accumulator was created without keep_weights");
+    if (!a->finished) return fail(FROG_E_INVALID, "frog_jlabels_weight: before frog_jlabels_finish");
+    if (image_index >= a->n_images) return fail(FROG_E_INVALID, "frog_jlabels_weight: no such image");
+    KCHECK(hipSetDevice(a->device));
+    KCHECK(hipMemcpy(w, a->d_weights.p + (size_t)image_index * a->total, a->total * sizeof(float), hipMemcpyDeviceToHost));
+    return FROG_OK;
+}
+
+void frog_jlabels_destroy(frog_jlabels *a) { group_destroy(a); }
 
 int frog_distance_map(const frog_volume *labels, int64_t value, int mode, int device, uint32_t *out)
 {

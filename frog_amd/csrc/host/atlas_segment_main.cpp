@@ -1,8 +1,9 @@
 // AtlasSegment: multi-atlas segmentation of a target image from a registered group by locally weighted voting (no counterpart
-// in the reference; Artaechevarria et al., IEEE TMI 28(8), 2009).
+// in the reference; Artaechevarria et al., IEEE TMI 28(8), 2009) or, with -j 1, by joint label fusion (Wang et al., IEEE PAMI
+// 35(3), 2013).
 //   AtlasSegment bbox.json spacing target image_0 ... image_N-1 -ll labels.txt [-td transformsDir] [-tt target.json] [-o outDir]
 //                [-r radius] [-pw power] [-fl floor] [-i interpolation] [-b imageBackground] [-bl labelBackground] [-f fillLabel]
-//                [-ml maxLabels] [-p 1] [-wt 1] [-dev n]
+//                [-ml maxLabels] [-p 1] [-wt 1] [-dev n] [-j 1 [-ja alpha] [-jb beta] [-jw 1]]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid).  Atlas i is image_i and line i of labels.txt (one label file per line,
 // N lines, the list format of AverageImage -ml); both go through the inverse of <transformsDir>/<i>.json (default
 // "transforms"), the image exactly as `VolumeTransform image_i dummy.mhd -t transforms/i.json` reslices it (background = its
@@ -20,6 +21,12 @@
 //   -p 1                  probability_<value>.nii.gz per label: f32 share of the voxel's score
 //   -wt 1                 transformedTarget.nii.gz, transformed<i>.nii.gz and transformedLabels<i>.nii.gz, the files
 //                         VolumeTransform would write
+//   -j 1                  joint label fusion (frog_jlabels) in place of the weighted vote: at most 32 atlases, -r 1..3; the
+//                         weights of a voxel solve the system of the atlases' pairwise patch differences from the target,
+//                         raised elementwise to -jb (1..4, default 2) with -ja (> 0, default 0.1) on the diagonal; they sum to 1
+//                         and may be negative, so a confidence can exceed 1.  -pw and -fl do not apply and are an error.  The
+//                         files keep their names and formats.
+//   -jw 1                 with -j 1: weight_<i>.nii.gz per atlas, its f32 weight per voxel
 // The segmentation is in the group's space: `VolumeTransform segmentation.nii.gz target -t target.json -i 0` brings it to the
 // subject.  Every transform and volume header is checked before anything is written; a float label file is an error.
 #include "group_tool.h"
@@ -39,7 +46,7 @@ namespace {
 const char *USAGE =
     "Usage : AtlasSegment bbox.json spacing target image_0 ... image_N-1 -ll labels.txt [-td transformsDir] [-tt target.json] [-o outDir] "
     "[-r radius=2] [-pw power=2] [-fl floor=0.0009765625] [-i 1] [-b imageBackground] [-bl labelBackground] [-f fillLabel] [-ml maxLabels] "
-    "[-p 1] [-wt 1] [-dev n]\n"
+    "[-p 1] [-wt 1] [-dev n] [-j 1 [-ja alpha=0.1] [-jb beta=2] [-jw 1]]\n"
     "The segmentation is in the group's space: VolumeTransform segmentation.nii.gz target -t target.json -i 0 brings it to the subject.";
 
 // the voxel of an integer volume as a 64-bit value
@@ -62,13 +69,15 @@ int main(int argc, char *argv[])
     PhaseTimes times;
     std::vector<std::string> positional, labelFiles;
     std::string transformsDir = "transforms", outDir = ".", labelList, targetTransform;
-    int device = 0, writeTransformed = 0, writeProbabilities = 0, interpolation = 1;
-    long radius = 2, power = 2, maxLabels = 0;
+    int device = 0, writeTransformed = 0, writeProbabilities = 0, interpolation = 1, joint = 0, writeWeights = 0;
+    bool votingOption = false, jointOption = false;         // -pw or -fl given; -ja, -jb or -jw given
+    long radius = 2, power = 2, maxLabels = 0, beta = 2;
+    double alpha = 0.1;
     long long fillLabel = 0;
     float floor = 0.0009765625f;
     double labelBackground = 0;
     BackgroundLevel background;
-    int a = positional_arguments(argc, argv, 3, { "-ll", "-td", "-tt", "-o", "-r", "-pw", "-fl", "-i", "-b", "-bl", "-f", "-ml", "-p", "-wt", "-dev" }, positional);
+    int a = positional_arguments(argc, argv, 3, { "-ll", "-td", "-tt", "-o", "-r", "-pw", "-fl", "-i", "-b", "-bl", "-f", "-ml", "-p", "-wt", "-dev", "-j", "-ja", "-jb", "-jw" }, positional);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
         if (std::strcmp(key, "-ll") == 0) labelList = value;
@@ -76,8 +85,12 @@ int main(int argc, char *argv[])
         else if (std::strcmp(key, "-tt") == 0) targetTransform = value;
         else if (std::strcmp(key, "-o") == 0) outDir = value;
         else if (std::strcmp(key, "-r") == 0) radius = atol(value);
-        else if (std::strcmp(key, "-pw") == 0) power = atol(value);
-        else if (std::strcmp(key, "-fl") == 0) floor = (float)atof(value);
+        else if (std::strcmp(key, "-pw") == 0) { power = atol(value); votingOption = true; }
+        else if (std::strcmp(key, "-fl") == 0) { floor = (float)atof(value); votingOption = true; }
+        else if (std::strcmp(key, "-j") == 0) joint = atoi(value);
+        else if (std::strcmp(key, "-ja") == 0) { alpha = atof(value); jointOption = true; }
+        else if (std::strcmp(key, "-jb") == 0) { beta = atol(value); jointOption = true; }
+        else if (std::strcmp(key, "-jw") == 0) { writeWeights = atoi(value); jointOption = true; }
         else if (std::strcmp(key, "-i") == 0) interpolation = atoi(value);
         else if (std::strcmp(key, "-b") == 0) background.parse(value);
         else if (std::strcmp(key, "-bl") == 0) labelBackground = (float)atof(value);  // a float, as VolumeTransform parses -b
@@ -95,6 +108,15 @@ int main(int argc, char *argv[])
     const std::string target = positional[0];
     const std::vector<std::string> images(positional.begin() + 1, positional.end());
     const size_t n = images.size();
+    if (joint) {
+        if (votingOption) die("-pw and -fl belong to the weighted vote: they do not go with -j 1");
+        if (n > 32) die("-j 1 : at most 32 atlases");
+        if (radius < 1 || radius > 3) die("-r : a radius from 1 to 3 with -j 1");
+        if (beta < 1 || beta > 4) die("-jb : a beta from 1 to 4");
+        if (!(std::isfinite(alpha) && alpha > 0)) die("-ja : a finite alpha above 0");
+    } else if (jointOption) {
+        die("-ja, -jb and -jw belong to joint label fusion: they need -j 1");
+    }
     if (radius < 1 || radius > 4) die("-r : a radius from 1 to 4");
     if (power < 1 || power > 8) die("-pw : a power from 1 to 8");
     if (!(floor >= 0.0f && floor <= 1.0f)) die("-fl : a floor in [0, 1]");
@@ -131,8 +153,12 @@ int main(int argc, char *argv[])
     std::vector<frog_chain *> chains = create_chains(inverse, device);
     frog_chain *targetChain = nullptr;                       // no -tt: a chain without links, the identity
     if (frog_chain_create(targetTransforms.links.data(), (uint32_t)targetTransforms.links.size(), device, &targetChain)) die(target + ": " + frog_last_error());
+    // one of the two accumulators; after create their calls take the same arguments
     frog_wlabels *acc = nullptr;
-    if (frog_wlabels_create(&grid, (uint32_t)n, (uint32_t)maxLabels, (uint32_t)radius, (uint32_t)power, floor, device, &acc)) die(frog_last_error());
+    frog_jlabels *jacc = nullptr;
+    if (joint ? frog_jlabels_create(&grid, (uint32_t)n, (uint32_t)maxLabels, (uint32_t)radius, (uint32_t)beta, alpha, writeWeights, device, &jacc)
+              : frog_wlabels_create(&grid, (uint32_t)n, (uint32_t)maxLabels, (uint32_t)radius, (uint32_t)power, floor, device, &acc))
+        die(frog_last_error());
     times.setup_s = seconds(t0);
 
     const size_t total = (size_t)grid.dims[0] * grid.dims[1] * grid.dims[2];
@@ -144,7 +170,9 @@ int main(int argc, char *argv[])
         if (!it.file) die("cannot read volume " + target);
         frog_volume *out = resliced.stage(writeTransformed, grid, it.view.dtype);
         t0 = clk::now();
-        if (frog_wlabels_target(acc, targetChain, &it.view, interpolation, background.of(it.lo), out)) die(target + ": " + frog_last_error());
+        if (joint ? frog_jlabels_target(jacc, targetChain, &it.view, interpolation, background.of(it.lo), out)
+                  : frog_wlabels_target(acc, targetChain, &it.view, interpolation, background.of(it.lo), out))
+            die(target + ": " + frog_last_error());
         times.device_s += seconds(t0);
         targetStream.release(0);
         frog_chain_destroy(targetChain);
@@ -166,7 +194,8 @@ int main(int argc, char *argv[])
         frog_volume *out = resliced.stage(writeTransformed, grid, it.view.dtype);
         frog_volume *lout = reslicedLabels.stage(writeTransformed, grid, lt.view.dtype);
         t0 = clk::now();
-        if (frog_wlabels_add(acc, chains[i], &it.view, &lt.view, interpolation, background.of(it.lo), labelBackground, out, lout))
+        if (joint ? frog_jlabels_add(jacc, chains[i], &it.view, &lt.view, interpolation, background.of(it.lo), labelBackground, out, lout)
+                  : frog_wlabels_add(acc, chains[i], &it.view, &lt.view, interpolation, background.of(it.lo), labelBackground, out, lout))
             die(images[i] + ", " + labelFiles[i] + ": " + frog_last_error());
         times.device_s += seconds(t0);
         stream.release(i);
@@ -182,9 +211,9 @@ int main(int argc, char *argv[])
     }
     t0 = clk::now();
     uint32_t n_labels = 0;
-    if (frog_wlabels_finish(acc, &n_labels)) die(frog_last_error());
+    if (joint ? frog_jlabels_finish(jacc, &n_labels) : frog_wlabels_finish(acc, &n_labels)) die(frog_last_error());
     std::vector<int64_t> values(n_labels);
-    if (frog_wlabels_values(acc, values.data())) die(frog_last_error());
+    if (joint ? frog_jlabels_values(jacc, values.data()) : frog_wlabels_values(acc, values.data())) die(frog_last_error());
     std::vector<int64_t> range = values;                     // the segmentation's type holds the fill label too
     range.insert(std::lower_bound(range.begin(), range.end(), (int64_t)fillLabel), (int64_t)fillLabel);
     const int dtype = fused_type(range);
@@ -194,7 +223,7 @@ int main(int argc, char *argv[])
     frog_volume label = grid;
     label.dtype = dtype;
     label.data = fused.data();
-    if (frog_wlabels_fused(acc, fillLabel, &label, share.data())) die(frog_last_error());
+    if (joint ? frog_jlabels_fused(jacc, fillLabel, &label, share.data()) : frog_wlabels_fused(acc, fillLabel, &label, share.data())) die(frog_last_error());
     times.device_s += seconds(t0);
 
     t0 = clk::now();
@@ -217,7 +246,7 @@ int main(int argc, char *argv[])
     if (writeProbabilities) {
         for (uint32_t l = 0; l < n_labels; l++) {
             t0 = clk::now();
-            if (frog_wlabels_probability(acc, values[l], share.data())) die(frog_last_error());
+            if (joint ? frog_jlabels_probability(jacc, values[l], share.data()) : frog_wlabels_probability(acc, values[l], share.data())) die(frog_last_error());
             times.device_s += seconds(t0);
             t0 = clk::now();
             const std::string path = outDir + "/probability_" + std::to_string(values[l]) + ".nii.gz";
@@ -225,7 +254,17 @@ int main(int argc, char *argv[])
             times.write_s += seconds(t0);
         }
     }
+    for (size_t i = 0; joint && writeWeights && i < n; i++) {
+        t0 = clk::now();
+        if (frog_jlabels_weight(jacc, (uint32_t)i, share.data())) die(frog_last_error());
+        times.device_s += seconds(t0);
+        t0 = clk::now();
+        const std::string path = outDir + "/weight_" + std::to_string(i) + ".nii.gz";
+        if (frog_volume_write(path.c_str(), &f32)) die("cannot write " + path);
+        times.write_s += seconds(t0);
+    }
     frog_wlabels_destroy(acc);
+    frog_jlabels_destroy(jacc);
     std::cout << n_labels << " labels" << std::endl;
     times.print(stream.read_seconds() + labelStream.read_seconds() + targetStream.read_seconds(), stream.threads() + labelStream.threads() + 1);
     return 0;

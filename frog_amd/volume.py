@@ -571,13 +571,16 @@ class WeightedLabels(_Accumulator):
         self._n_labels = None
         super().__init__(grid, self.n_images, int(max_labels), int(radius), int(power), float(floor), int(device))
 
+    def _call(self, name):
+        return getattr(self._lib, f"frog_{self._NAME}_{name}")
+
     def target(self, volume, chain=None, interpolation=1, background=0.0, resliced=False):
         """The image to segment ((voxels, origin, spacing) or an array already on the grid when chain is None), once, before
         the first add; with a chain (frog_amd.chain.Chain, grid space -> volume space) it is resliced as Chain.reslice does.
         resliced=True returns that volume (source dtype, shape dims[::-1])."""
         _, src, _, ov, out = self._views(volume, None, resliced)
-        _abi.check(self._lib.frog_wlabels_target(self._h, chain._h if chain is not None else None, src, int(interpolation),
-                                                 float(background), ov), "frog_wlabels_target")
+        _abi.check(self._call("target")(self._h, chain._h if chain is not None else None, src, int(interpolation), float(background), ov),
+                   f"frog_{self._NAME}_target")
         return out
 
     def add(self, image, labels, chain=None, interpolation=1, image_background=0.0, label_background=0.0, resliced=False):
@@ -586,21 +589,21 @@ class WeightedLabels(_Accumulator):
         Chain.reslice gives them (the labels with nearest-neighbour interpolation)."""
         _, src, _, ov, out = self._views(image, None, resliced)
         _, lsrc, _, lv, lout = self._views(labels, None, resliced)
-        _abi.check(self._lib.frog_wlabels_add(self._h, chain._h if chain is not None else None, src, lsrc, int(interpolation),
-                                              float(image_background), float(label_background), ov, lv), "frog_wlabels_add")
+        _abi.check(self._call("add")(self._h, chain._h if chain is not None else None, src, lsrc, int(interpolation),
+                                     float(image_background), float(label_background), ov, lv), f"frog_{self._NAME}_add")
         return (out, lout) if resliced else None
 
     def finish(self):
         """The number of distinct labels, after exactly n_images adds."""
         n = C.c_uint32()
-        _abi.check(self._lib.frog_wlabels_finish(self._h, C.byref(n)), "frog_wlabels_finish")
+        _abi.check(self._call("finish")(self._h, C.byref(n)), f"frog_{self._NAME}_finish")
         self._n_labels = int(n.value)
         return self._n_labels
 
     def values(self):
         """The distinct label values, int64 ascending."""
         values = np.empty(self._n_labels or 0, np.int64)
-        _abi.check(self._lib.frog_wlabels_values(self._h, values.ctypes.data_as(C.POINTER(C.c_int64))), "frog_wlabels_values")
+        _abi.check(self._call("values")(self._h, values.ctypes.data_as(C.POINTER(C.c_int64))), f"frog_{self._NAME}_values")
         return values
 
     def fused(self, dtype=None, fill_label=0):
@@ -614,15 +617,36 @@ class WeightedLabels(_Accumulator):
         labels = np.empty(self.dims[::-1], np.dtype(dtype))
         confidence = np.empty(self.dims[::-1], np.float32)
         lv = _abi.volume_view(labels, tuple(self._grid.origin), tuple(self._grid.spacing))
-        _abi.check(self._lib.frog_wlabels_fused(self._h, int(fill_label), C.byref(lv), confidence.ctypes.data_as(_abi.c_float_p)),
-                   "frog_wlabels_fused")
+        _abi.check(self._call("fused")(self._h, int(fill_label), C.byref(lv), confidence.ctypes.data_as(_abi.c_float_p)),
+                   f"frog_{self._NAME}_fused")
         return labels, confidence
 
     def probability(self, value):
         """float32 share of the voxel's total score that label `value` holds; 0 where no weight arrived."""
         p = np.empty(self.dims[::-1], np.float32)
-        _abi.check(self._lib.frog_wlabels_probability(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), "frog_wlabels_probability")
+        _abi.check(self._call("probability")(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), f"frog_{self._NAME}_probability")
         return p
+
+
+class JointLabels(WeightedLabels):
+    """frog_jlabels (include/frog_chain.h): joint label fusion (Wang et al., PAMI 2013).  The calls of WeightedLabels; an add
+    only collects, and finish() solves, per voxel, the n x n system of the atlases' pairwise patch differences from the target
+    (raised elementwise to `beta`, `alpha` on the diagonal) for the weights of the vote, which sum to 1 and may be negative.
+    At most 32 atlases, radius 1..3.  keep_weights=True keeps every atlas' weight plane for weight()."""
+
+    _NAME = "jlabels"
+
+    def __init__(self, grid, n_images, max_labels=0, radius=2, beta=2, alpha=0.1, keep_weights=False, device=0):
+        self.n_images = int(n_images)
+        self._n_labels = None
+        _Accumulator.__init__(self, grid, self.n_images, int(max_labels), int(radius), int(beta), float(alpha), int(bool(keep_weights)),
+                              int(device))
+
+    def weight(self, image_index):
+        """float32 weight of atlas `image_index` (in call order) per voxel, 0 where it is not active; after finish()."""
+        w = np.empty(self.dims[::-1], np.float32)
+        _abi.check(self._lib.frog_jlabels_weight(self._h, int(image_index), w.ctypes.data_as(_abi.c_float_p)), "frog_jlabels_weight")
+        return w
 
 
 def atlas_segment(target, images, label_maps, chains=None, target_chain=None, grid=None, radius=2, power=2, floor=2.0 ** -10,
@@ -632,6 +656,26 @@ def atlas_segment(target, images, label_maps, chains=None, target_chain=None, gr
     the grid) or the Chain from grid space to the target's; `image_backgrounds`: None (each volume's minimum, the target's
     included), a number or one per image.  Returns (labels, confidence, values): the fused map in the grid's space, the
     float32 share of each voxel's score that its label holds, and the distinct label values in ascending order."""
+    acc_of = lambda grid, n: WeightedLabels(grid, n, max_labels, radius, power, floor, device)
+    return _segment(acc_of, target, images, label_maps, chains, target_chain, grid, interpolation, image_backgrounds, label_background,
+                    fill_label)[:3]
+
+
+def joint_atlas_segment(target, images, label_maps, chains=None, target_chain=None, grid=None, radius=2, beta=2, alpha=0.1,
+                        interpolation=1, image_backgrounds=None, label_background=0.0, fill_label=0, max_labels=0, keep_weights=False,
+                        device=0):
+    """atlas_segment() by joint label fusion (bin/AtlasSegment -j 1; JointLabels): the same arguments with `beta` and `alpha`
+    in place of `power` and `floor`, at most 32 atlases, radius 1..3.  Returns (labels, confidence, values), and with
+    keep_weights a fourth item: the float32 weight plane of every atlas."""
+    acc_of = lambda grid, n: JointLabels(grid, n, max_labels, radius, beta, alpha, keep_weights, device)
+    out = _segment(acc_of, target, images, label_maps, chains, target_chain, grid, interpolation, image_backgrounds, label_background,
+                   fill_label, keep_weights)
+    return out if keep_weights else out[:3]
+
+
+def _segment(acc_of, target, images, label_maps, chains, target_chain, grid, interpolation, image_backgrounds, label_background, fill_label,
+             weights=False):
+    """What atlas_segment() and joint_atlas_segment() share: the target, the adds, finish and the fused map."""
     vols, grid = _group(images, chains, None, grid)
     labels = [_as_volume(v) for v in label_maps]
     if len(labels) != len(vols):
@@ -641,14 +685,14 @@ def atlas_segment(target, images, label_maps, chains=None, target_chain=None, gr
         image_backgrounds = [float(a.min()) for a, _, _ in vols]
     elif np.ndim(image_backgrounds) == 0:
         image_backgrounds = [float(image_backgrounds)] * len(vols)
-    acc = WeightedLabels(grid, len(vols), max_labels, radius, power, floor, device)
+    acc = acc_of(grid, len(vols))
     try:
         acc.target(tgt, target_chain, interpolation, float(tgt[0].min()))
         for k, v in enumerate(vols):
             acc.add(v, labels[k], None if chains is None else chains[k], interpolation, image_backgrounds[k], label_background)
         acc.finish()
         fused, confidence = acc.fused(None, fill_label)
-        return fused, confidence, acc.values()
+        return fused, confidence, acc.values(), [acc.weight(k) for k in range(len(vols))] if weights else None
     finally:
         acc.close()
 

@@ -450,6 +450,70 @@ int  frog_wlabels_fused(frog_wlabels *a, int64_t fill_label, frog_volume *label,
 int  frog_wlabels_probability(frog_wlabels *a, int64_t value, float *p);
 void frog_wlabels_destroy(frog_wlabels *a);
 
+/* ---- joint label fusion (an extension; Wang, Suh, Das, Pluta, Craige, Yushkevich, IEEE PAMI 35(3), 2013: the atlases' weights
+ * at a voxel minimise the expected error of the combined vote given how the atlases' errors correlate over the patch, so
+ * atlases that are wrong in the same way share one vote) ------------------------------------------------------------------------
+ * An accumulator of n_images <= 32 atlases on `grid`, as frog_wlabels.  An add only collects: the atlas' f32 plane (NaN where
+ * not valid) and its resliced label map stay on the device until frog_jlabels_finish, which solves one n x n system per voxel
+ * and votes.  Every floating-point line below is one separately rounded f64 operation unless marked; there is no
+ * floating-point atomic and the results are the same bits from run to run and however the work is cut into launches.
+ * radius 1..3: the patch is (2 radius + 1)^3 voxels; beta 1..4, an integer, the elementwise power of the Gram matrix (which
+ * stays positive semidefinite: Schur product theorem); alpha > 0, finite, added to the diagonal; max_labels as frog_wlabels.
+ * Device memory, V the grid's voxels: n_images x (4 V for the image plane + V x the label type's bytes for its label map,
+ * allocated by the add) + 4 V for the target + 4 V per distinct label value; with keep_weights n_images x 4 V more; and the
+ * staging of the current image, label map and resliced image.  There is no cutting into slabs: a grid whose planes do not
+ * fit is refused with FROG_E_NOMEM by the call that allocates.
+ * FROG_E_INVALID, before the device is touched: everything frog_wlabels_create refuses for grid, n_images and max_labels,
+ * n_images > 32, radius == 0 or > 3, beta == 0 or > 4, alpha not finite or <= 0. */
+typedef struct frog_jlabels frog_jlabels;
+int  frog_jlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, uint32_t radius, uint32_t beta,
+                         double alpha, int keep_weights, int device, frog_jlabels **out);
+/* Exactly frog_wlabels_target: t[v] and validT[v]. */
+int  frog_jlabels_target(frog_jlabels *a, frog_chain *chain, const frog_volume *source,
+                         int interpolation, double background, frog_volume *resliced);
+/* Exactly frog_wlabels_add's arguments, a_i[v], validA_i[v], label_i[v], resliced volumes, refusals and the take-back of a
+ * refused atlas; no vote yet. */
+int  frog_jlabels_add(frog_jlabels *a, frog_chain *chain, const frog_volume *image, const frog_volume *labels,
+                      int interpolation, double image_background, double label_background,
+                      frog_volume *resliced_image, frog_volume *resliced_labels);
+/* After exactly n_images adds (else FROG_E_INVALID): solves and votes, then returns the number of distinct label values as
+ * frog_wlabels_finish.  At grid voxel v, patch(v) = the grid voxels u with |u - v| <= radius on all three axes (voxels
+ * outside the grid do not exist), walked with z ascending, then y, then x:
+ *   Patch statistics, for X = t and for X = every a_i, over the u of patch(v) where X is valid, each sum from +0.0:
+ *               x = (double)X[u];  n = n + 1;  s = s + x;  xx = x * x;  ss = ss + xx
+ *               nss = n * ss;  s2 = s * s;  num = nss - s2;  nn = n * n;  var = num / nn;  mean = s / n
+ *               if n >= 2 and var > 0:  sd = sqrt(var);  inv = 1 / sd        else  inv = 0
+ *   Differences, where validT[u] and validA_i[u]:
+ *               ac = (double)a_i[u] - mean_i;  ah = ac * inv_i;  tc = (double)t[u] - mean_t;  th = tc * inv_t
+ *               e = ah - th;  d_i(u) = fabs(e)                               elsewhere  d_i(u) = +0.0
+ *   Gram matrix, for j <= i, each entry from +0.0, over patch(v) in the stated order:
+ *               p = d_i(u) * d_j(u);  M[i][j] = M[i][j] + p
+ *   Power:      K[i][j] = M[i][j];  then beta - 1 times  K[i][j] = K[i][j] * M[i][j];  then  K[i][i] = K[i][i] + alpha
+ *   Active set: atlas i is active at v iff validT[v] && validA_i[v].  The system is K restricted to the active atlases in call
+ *               order; an atlas that is not active has weight 0 and no vote; no active atlas, or a target that is not valid
+ *               at v: no score is written at v.
+ *   K w = 1 by LDL^T without pivoting (loops ascending unless said otherwise):
+ *     for j:    D_j = K_jj;  for k < j:  q = L_jk * L_jk;  m = q * D_k;  D_j = D_j - m
+ *               for i > j:   x = K_ij;  for k < j:  q = L_ik * L_jk;  m = q * D_k;  x = x - m;   then  L_ij = x / D_j
+ *     forward:  z_i = 1;  for k < i:  m = L_ik * z_k;  z_i = z_i - m
+ *     diagonal: y_i = z_i / D_i
+ *     backward, i descending:  w_i = y_i;  for k > i ascending:  m = L_ki * w_k;  w_i = w_i - m
+ *     normalise: S = +0.0;  for i:  S = S + w_i;   then  w_i = w_i / S;  the weight of atlas i at v is (float)w_i
+ *   Votes, in call order over the active atlases:  score[label_i[v]][v] = score[label_i[v]][v] + (float)w_i          (f32)
+ * Weights may be negative: that is the method, and how it cancels an error the atlases share.  They are neither clamped nor
+ * renormalised.  The four getters below are valid only after finish (FROG_E_INVALID before). */
+int  frog_jlabels_finish(frog_jlabels *a, uint32_t *n_labels);
+int  frog_jlabels_values(frog_jlabels *a, int64_t *values);            /* ascending, signed */
+/* Exactly frog_wlabels_fused on these scores: total in ascending label order, the winner the first strictly larger score
+ * that is > 0, confidence = winner / total, fill_label and 0 where total == 0.  Where other labels' scores are negative the
+ * total is smaller than the winner's score and the confidence exceeds 1. */
+int  frog_jlabels_fused(frog_jlabels *a, int64_t fill_label, frog_volume *label, float *confidence);
+int  frog_jlabels_probability(frog_jlabels *a, int64_t value, float *p);       /* as frog_wlabels_probability */
+/* w[v] = the weight of atlas image_index (in call order) at v, 0 where it is not active.  Without keep_weights, before
+ * finish, or image_index >= n_images -> FROG_E_INVALID. */
+int  frog_jlabels_weight(frog_jlabels *a, uint32_t image_index, float *w);
+void frog_jlabels_destroy(frog_jlabels *a);
+
 /* ---- surface distances between label maps: an exact Euclidean distance transform (an extension; the reference has no
  * counterpart) ---------------------------------------------------------------------------------------------------------------
  * How far apart are the boundaries of a structure in two label maps, in the spacing's unit: the Hausdorff distance, a
