@@ -213,6 +213,7 @@ def grid_triplet(origin, spacing, dims):
 
 
 FROG_RANK_MAX_IMAGES = 4096         # include/frog_chain.h: the capacity of frog_rank's sort kernels
+FROG_GLM_MAX_IMAGES, FROG_GLM_MAX_COLUMNS, FROG_GLM_MAX_CONTRASTS = 4096, 8, 8     # include/frog_chain.h: frog_glm's limits
 
 
 class FrogScoreSums(C.Structure):
@@ -313,6 +314,18 @@ HIP_SYMBOLS = {
     "frog_rank_finish": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.POINTER(C.c_double), c_float_p, c_float_p,
                                    C.POINTER(C.c_uint16)]),
     "frog_rank_destroy": (None, [C.c_void_p]),
+    "frog_glm_planes": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
+    "frog_glm_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, c_double_p, C.c_int,
+                                  C.POINTER(C.c_void_p)]),
+    "frog_glm_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double]),
+    "frog_glm_add_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int]),
+    "frog_glm_plane": (C.c_int, [C.c_void_p, C.c_uint32, c_float_p]),
+    "frog_glm_finish": (C.c_int, [C.c_void_p, C.c_uint32, c_double_p, C.c_uint32, C.c_double, C.POINTER(C.c_uint8), C.c_float,
+                                  c_float_p, c_float_p, c_float_p, C.POINTER(C.c_uint16)]),
+    "frog_glm_permute": (C.c_int, [C.c_void_p, C.c_uint32, c_double_p, C.c_uint32, C.c_double, C.POINTER(C.c_uint8), C.c_uint32,
+                                   C.c_uint32, c_u32_p, C.POINTER(C.c_int8), c_float_p, c_float_p]),
+    "frog_glm_draw": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, c_u32_p, C.POINTER(C.c_int8)]),
+    "frog_glm_destroy": (None, [C.c_void_p]),
     "frog_labels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_labels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
     "frog_labels_finish": (C.c_int, [C.c_void_p, c_u32_p]),

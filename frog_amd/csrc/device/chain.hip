@@ -1046,6 +1046,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 #include "k_staple.hip.h"
 #include "k_edt.hip.h"
 #include "k_joint.hip.h"
+#include "k_glm.hip.h"
 
 } // namespace
 
@@ -1089,6 +1090,15 @@ struct frog_rank : frog_masked {
     uint32_t n_images = 0, added = 0;
     size_t first = 0, window = 0;                   // the window's first voxel in the grid, and its voxels
     frog::DevBuf<uint32_t> d_keys;                  // n_images planes of `window` keys, in the order of the adds
+};
+
+// one plane of f32 values per added image over a window of z-planes of one grid, and the design of the linear model
+struct frog_glm : frog_masked {
+    uint32_t n_images = 0, added = 0, p = 0;
+    size_t first = 0, window = 0;                   // as in frog_rank
+    std::vector<double> design;                     // n_images x p
+    frog::DevBuf<float> d_vals;                     // n_images planes of `window` values, in the order of the adds
+    frog::DevBuf<double> d_design, d_table;         // d_table: the design rows of one launch's permutations, grown on demand
 };
 
 // vote counts of a group's label maps on one grid
@@ -1927,6 +1937,103 @@ int rank_arguments(const char *where, const frog_volume *grid, uint32_t n_images
     return FROG_OK;
 }
 
+// frog_glm_add for a source of type S: rank_add_typed with the float store
+template <class S>
+int glm_add_typed(frog_glm *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
+{
+    ResliceGrid g;
+    const uint8_t *d_mask;
+    if (int rc = stage_source<S>("frog_glm_add", a, src, false, interpolation, background, &g)) return rc;
+    if (int rc = cover_stage_mask("frog_glm_add", a, mask, &d_mask)) return rc;
+    const MaskGrid mg = mask_grid(mask);
+    const S *d_src = (const S *)a->d_src.p;
+    float *plane = a->d_vals.p + (size_t)a->added * a->window;
+    const hipError_t e = chunked_launch(a->window, [&](unsigned blocks, size_t base) {
+        if (c)
+            glm_reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg, plane);
+        else
+            glm_identity_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, d_src, d_mask, plane);
+    });
+    return return_resliced<S>("frog_glm_add", a, c, src, nullptr, e);
+}
+
+// what frog_glm_finish and frog_glm_permute refuse alike, before the device is touched
+int glm_fit_arguments(const char *where, const frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor)
+{
+    const std::string w = std::string(where) + ": ";
+    if (!a || n_contrasts > FROG_GLM_MAX_CONTRASTS || (n_contrasts && !contrasts)) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (a->added != a->n_images) return fail(FROG_E_INVALID, w + "fewer volumes added than n_images");
+    if (!min_count) return fail(FROG_E_INVALID, w + "min_count must be at least 1");
+    if (!(sigma_floor >= 0.0)) return fail(FROG_E_INVALID, w + "sigma_floor must not be negative");
+    for (size_t e = 0; e < (size_t)n_contrasts * a->p; e++)
+        if (!std::isfinite(contrasts[e])) return fail(FROG_E_INVALID, w + "a contrast entry is not finite");
+    return FROG_OK;
+}
+
+// The fit kernel over the window for the n_perms permutations whose rows d_table holds: instantiated on the number of columns
+// and on whether the values of a voxel stay in LDS.
+hipError_t glm_fit_launch(const frog_glm *a, const GlmArgs &f)
+{
+    const bool lds = a->n_images <= GLM_LDS_MAX;
+    const size_t bytes = (f.extrema ? (size_t)f.n_perms * f.n_contrasts * 2 * sizeof(uint32_t) : 0) + (lds ? (size_t)a->n_images * 256 * sizeof(float) : 0);
+    auto go = [&](auto kernel) {
+        // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
+        return chunked_launch(f.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
+            kernel<<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f);
+        });
+    };
+    switch (a->p * 2 + (lds ? 1 : 0)) {
+    case 2: return go(glm_fit_kernel<1, false>);
+    case 3: return go(glm_fit_kernel<1, true>);
+    case 4: return go(glm_fit_kernel<2, false>);
+    case 5: return go(glm_fit_kernel<2, true>);
+    case 6: return go(glm_fit_kernel<3, false>);
+    case 7: return go(glm_fit_kernel<3, true>);
+    case 8: return go(glm_fit_kernel<4, false>);
+    case 9: return go(glm_fit_kernel<4, true>);
+    case 10: return go(glm_fit_kernel<5, false>);
+    case 11: return go(glm_fit_kernel<5, true>);
+    case 12: return go(glm_fit_kernel<6, false>);
+    case 13: return go(glm_fit_kernel<6, true>);
+    case 14: return go(glm_fit_kernel<7, false>);
+    case 15: return go(glm_fit_kernel<7, true>);
+    case 16: return go(glm_fit_kernel<8, false>);
+    default: return go(glm_fit_kernel<8, true>);
+    }
+}
+
+// the design rows of n_perms permutations (perm and sign on the device; both null: the design as it is) into a->d_table
+hipError_t glm_table_launch(frog_glm *a, const uint32_t *d_perm, const int8_t *d_sign, uint32_t columns, uint32_t n_perms)
+{
+    const size_t total = (size_t)n_perms * a->n_images;
+    hipError_t e = a->d_table.alloc(total * glm_row_doubles(a->p));
+    if (e != hipSuccess) return e;
+    return chunked_launch(total, [&](unsigned blocks, size_t base) {
+        glm_table_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_design.p, d_perm, d_sign, a->n_images, a->p, columns, total, a->d_table.p);
+    });
+}
+
+// the arguments of a launch that finish and permute fill alike; region (window-sized, may be null) goes to d_region
+int glm_fit_args(const char *where, frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                 const uint8_t *region, frog::DevBuf<uint8_t> &d_region, GlmArgs *f)
+{
+    *f = GlmArgs{};
+    f->window = a->window;
+    f->tiles = (a->window + GLM_TILE - 1) / GLM_TILE;
+    f->n = a->n_images;
+    f->need = std::max(min_count, a->p + 1u);
+    f->n_contrasts = n_contrasts;
+    f->sigma_floor = sigma_floor;
+    for (size_t e = 0; e < (size_t)n_contrasts * a->p; e++) f->contrasts[e] = contrasts[e];
+    if (region) {
+        KCHECK(d_region.alloc(a->window));
+        const hipError_t e = hipMemcpy(d_region.p, region, a->window, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(where, e);
+        f->region = d_region.p;
+    }
+    return FROG_OK;
+}
+
 // frog_staple_add for a source of type S: labels_add_typed with the index plane in place of the vote.  The plane of the
 // image is written only after the volume's labels are accepted, so a refused volume leaves nothing behind.
 template <class S>
@@ -2615,6 +2722,195 @@ int frog_rank_finish(frog_rank *a, uint32_t min_count, float fill, uint32_t n_q,
 }
 
 void frog_rank_destroy(frog_rank *a) { group_destroy(a); }
+
+int frog_glm_planes(const frog_volume *grid, uint32_t n_images, int device, uint32_t *planes)
+{
+    if (n_images > FROG_GLM_MAX_IMAGES) return fail(FROG_E_INVALID, "frog_glm_planes: 1 to " + std::to_string(FROG_GLM_MAX_IMAGES) + " images");
+    return frog_rank_planes(grid, n_images, device, planes);       // the same four bytes per image and voxel
+}
+
+int frog_glm_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_planes, uint32_t n_images, uint32_t n_columns,
+                    const double *design, int device, frog_glm **out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_glm_create", grid, out, &total)) return rc;
+    if (!design) return fail(FROG_E_INVALID, "bad arguments to frog_glm_create");
+    if (!n_images || n_images > FROG_GLM_MAX_IMAGES) return fail(FROG_E_INVALID, "frog_glm_create: 1 to " + std::to_string(FROG_GLM_MAX_IMAGES) + " images");
+    if (!n_columns || n_columns > FROG_GLM_MAX_COLUMNS) return fail(FROG_E_INVALID, "frog_glm_create: 1 to " + std::to_string(FROG_GLM_MAX_COLUMNS) + " columns");
+    if (n_images <= n_columns) return fail(FROG_E_INVALID, "frog_glm_create: more images than columns are needed");
+    for (size_t e = 0; e < (size_t)n_images * n_columns; e++)
+        if (!std::isfinite(design[e])) return fail(FROG_E_INVALID, "frog_glm_create: a design entry is not finite");
+    if (!n_planes || first_plane >= grid->dims[2] || n_planes > grid->dims[2] - first_plane)
+        return fail(FROG_E_INVALID, "frog_glm_create: the window lies outside the grid or is empty");
+    std::unique_ptr<frog_glm> a;
+    if (int rc = group_new(grid, total, device, a)) return rc;
+    const size_t plane = (size_t)grid->dims[0] * grid->dims[1];
+    a->n_images = n_images;
+    a->p = n_columns;
+    a->first = plane * first_plane;
+    a->window = plane * n_planes;
+    a->design.assign(design, design + (size_t)n_images * n_columns);
+    KCHECK(a->d_vals.alloc((size_t)n_images * a->window));
+    KCHECK(a->d_design.alloc(a->design.size()));
+    KCHECK(hipMemcpy(a->d_design.p, a->design.data(), a->design.size() * sizeof(double), hipMemcpyHostToDevice));
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_glm_add(frog_glm *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
+{
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_glm_add");
+    if (a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_glm_add: more volumes than the accumulator was created for");
+    if (int rc = cover_inputs("frog_glm_add", a, c, src, mask, nullptr)) return rc;
+    if (mask) cover_mask(a, mask);
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_voxel_type(src->dtype, [&](auto s) { return glm_add_typed<decltype(s)>(a, c, src, mask, interpolation, background); });
+    if (rc == FROG_OK) a->added++;
+    return rc;
+}
+
+int frog_glm_add_jacobian(frog_glm *a, frog_chain *c, const frog_volume *support, const frog_volume *mask, int log_mode)
+{
+    if (!a || !c) return fail(FROG_E_INVALID, "bad arguments to frog_glm_add_jacobian");
+    if (a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: more volumes than the accumulator was created for");
+    if (c->device != a->device) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: chain and accumulator on different devices");
+    if (support && (!voxel_count(support) || !chain_samples(support))) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: bad support geometry");
+    if (mask) {
+        if (!mask->data) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: a mask without voxels");
+        if (!integer_voxel_type(mask->dtype)) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: a mask has an integer type");
+        if (!voxel_count(mask) || !chain_samples(mask)) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: bad mask geometry");
+        cover_mask(a, mask);
+    }
+    KCHECK(hipSetDevice(a->device));
+    const uint8_t *d_mask;
+    if (int rc = cover_stage_mask("frog_glm_add_jacobian", a, mask, &d_mask)) return rc;
+    const MaskGrid mg = mask_grid(mask), sg = mask_grid(support);
+    const NodeGrid out = node_grid(a->grid.origin, a->grid.spacing, a->grid.dims);
+    float *plane = a->d_vals.p + (size_t)a->added * a->window;
+    hipError_t e = chunked_launch(a->window, [&](unsigned blocks, size_t base) {
+        glm_jacobian_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), out, support != nullptr, sg,
+                                                      d_mask, mg, log_mode != 0, plane);
+    });
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return hip_fail("frog_glm_add_jacobian", e);
+    a->added++;
+    return FROG_OK;
+}
+
+int frog_glm_plane(frog_glm *a, uint32_t image_index, float *values)
+{
+    if (!a || !values) return fail(FROG_E_INVALID, "bad arguments to frog_glm_plane");
+    if (image_index >= a->added) return fail(FROG_E_INVALID, "frog_glm_plane: that image has not been added");
+    KCHECK(hipSetDevice(a->device));
+    KCHECK(hipMemcpy(values, a->d_vals.p + (size_t)image_index * a->window, a->window * sizeof(float), hipMemcpyDeviceToHost));
+    return FROG_OK;
+}
+
+int frog_glm_finish(frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                    const uint8_t *region, float fill, float *beta, float *sigma, float *t, uint16_t *count)
+{
+    if (int rc = glm_fit_arguments("frog_glm_finish", a, n_contrasts, contrasts, min_count, sigma_floor)) return rc;
+    if (!t || !n_contrasts) { t = nullptr; n_contrasts = 0; }
+    if (!beta && !sigma && !t && !count) return fail(FROG_E_INVALID, "frog_glm_finish: no output asked for");
+    KCHECK(hipSetDevice(a->device));
+    frog::DevBuf<float> d_beta, d_sigma, d_t;
+    frog::DevBuf<uint16_t> d_count;
+    frog::DevBuf<uint8_t> d_region;
+    if (beta) KCHECK(d_beta.alloc((size_t)a->p * a->window));
+    if (sigma) KCHECK(d_sigma.alloc(a->window));
+    if (t) KCHECK(d_t.alloc((size_t)n_contrasts * a->window));
+    if (count) KCHECK(d_count.alloc(a->window));
+    GlmArgs f;
+    if (int rc = glm_fit_args("frog_glm_finish", a, n_contrasts, contrasts, min_count, sigma_floor, region, d_region, &f)) return rc;
+    f.n_perms = 1;
+    f.fill = fill;
+    f.beta = d_beta.p;
+    f.sigma = d_sigma.p;
+    f.t = d_t.p;
+    f.count = d_count.p;
+    hipError_t e = glm_table_launch(a, nullptr, nullptr, 0, 1);
+    if (e == hipSuccess) e = glm_fit_launch(a, f);
+    if (e == hipSuccess && beta) e = hipMemcpy(beta, d_beta.p, (size_t)a->p * a->window * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && sigma) e = hipMemcpy(sigma, d_sigma.p, a->window * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && t) e = hipMemcpy(t, d_t.p, (size_t)n_contrasts * a->window * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && count) e = hipMemcpy(count, d_count.p, a->window * sizeof(uint16_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_glm_finish", e);
+    return FROG_OK;
+}
+
+int frog_glm_permute(frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                     const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
+                     float *max_t, float *min_t)
+{
+    if (int rc = glm_fit_arguments("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor)) return rc;
+    if (!n_contrasts || !n_perms || !perm || (!max_t && !min_t)) return fail(FROG_E_INVALID, "bad arguments to frog_glm_permute");
+    if (!columns || (columns >> a->p)) return fail(FROG_E_INVALID, "frog_glm_permute: columns names at least one column, and none past the design's");
+    const size_t entries = (size_t)n_perms * a->n_images;
+    for (size_t e = 0; e < entries; e++) {
+        if (perm[e] >= a->n_images) return fail(FROG_E_INVALID, "frog_glm_permute: a perm entry is not an image index");
+        if (sign && sign[e] != 1 && sign[e] != -1) return fail(FROG_E_INVALID, "frog_glm_permute: a sign is +1 or -1");
+    }
+    KCHECK(hipSetDevice(a->device));
+    const size_t n_ext = (size_t)n_perms * n_contrasts * 2;
+    frog::DevBuf<uint32_t> d_perm, d_ext;
+    frog::DevBuf<int8_t> d_sign;
+    frog::DevBuf<uint8_t> d_region;
+    KCHECK(d_perm.alloc(entries));
+    KCHECK(d_ext.alloc(n_ext));
+    if (sign) KCHECK(d_sign.alloc(entries));
+    std::vector<uint32_t> ext(n_ext);
+    for (size_t e = 0; e < n_ext; e++) ext[e] = (e & 1) ? GLM_KEY_POS_INF : GLM_KEY_NEG_INF;
+    GlmArgs f;
+    if (int rc = glm_fit_args("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor, region, d_region, &f)) return rc;
+    hipError_t e = hipMemcpy(d_perm.p, perm, entries * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && sign) e = hipMemcpy(d_sign.p, sign, entries, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_ext.p, ext.data(), n_ext * sizeof(uint32_t), hipMemcpyHostToDevice);
+    // the permutations in launches of at most GLM_BATCH whose design rows fit GLM_TABLE_BYTES
+    const size_t per_perm = (size_t)a->n_images * glm_row_doubles(a->p) * sizeof(double);
+    const uint32_t batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(GLM_BATCH, GLM_TABLE_BYTES / per_perm));
+    for (uint32_t k0 = 0; k0 < n_perms && e == hipSuccess; k0 += batch) {
+        const uint32_t nb = std::min(batch, n_perms - k0);
+        const size_t at = (size_t)k0 * a->n_images;
+        e = glm_table_launch(a, d_perm.p + at, sign ? d_sign.p + at : nullptr, columns, nb);
+        f.n_perms = nb;
+        f.extrema = d_ext.p + (size_t)k0 * n_contrasts * 2;
+        if (e == hipSuccess) e = glm_fit_launch(a, f);
+    }
+    if (e == hipSuccess) e = hipMemcpy(ext.data(), d_ext.p, n_ext * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_glm_permute", e);
+    for (size_t e2 = 0; e2 < n_ext / 2; e2++) {
+        const uint32_t hi = ext[2 * e2], lo = ext[2 * e2 + 1];
+        const uint32_t bits_hi = (hi & 0x80000000u) ? (hi ^ 0x80000000u) : ~hi, bits_lo = (lo & 0x80000000u) ? (lo ^ 0x80000000u) : ~lo;
+        if (max_t) std::memcpy(max_t + e2, &bits_hi, sizeof(float));
+        if (min_t) std::memcpy(min_t + e2, &bits_lo, sizeof(float));
+    }
+    return FROG_OK;
+}
+
+int frog_glm_draw(uint32_t n, uint32_t n_perms, uint64_t seed, int shuffle, int flip, uint32_t *perm, int8_t *sign)
+{
+    if (!perm || (flip && !sign)) return fail(FROG_E_INVALID, "bad arguments to frog_glm_draw");
+    if (!n || n > FROG_GLM_MAX_IMAGES || !n_perms) return fail(FROG_E_INVALID, "frog_glm_draw: 1 to " + std::to_string(FROG_GLM_MAX_IMAGES) + " images and at least one permutation");
+    uint64_t s = seed;
+    auto next = [&s]() {
+        s += 0x9E3779B97F4A7C15ull;
+        uint64_t z = s;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return z ^ (z >> 31);
+    };
+    for (uint32_t k = 0; k < n_perms; k++) {
+        uint32_t *row = perm + (size_t)k * n;
+        int8_t *sg = sign ? sign + (size_t)k * n : nullptr;
+        for (uint32_t i = 0; i < n; i++) row[i] = i;
+        if (k && shuffle)
+            for (uint32_t i = n - 1; i >= 1; i--) std::swap(row[i], row[next() % (i + 1)]);
+        for (uint32_t i = 0; sg && i < n; i++) sg[i] = k && flip && (next() >> 63) ? -1 : 1;
+    }
+    return FROG_OK;
+}
+
+void frog_glm_destroy(frog_glm *a) { group_destroy(a); }
 
 int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_labels **out)
 {

@@ -357,6 +357,192 @@ def group_median(volumes, chains=None, masks=None, grid=None, quantiles=(), inte
     return values[0], mad, count, {q: values[1 + j] for j, q in enumerate(qs)}
 
 
+class GroupGLM(_Accumulator):
+    """frog_glm (include/frog_chain.h): every added image's value per voxel of a window of `grid`, then per voxel the linear
+    model of those values on `design` (n_images x n_columns, row i belongs to add number i) over the images that take part
+    there: coefficients, residual stdev, one t per contrast, and the extrema of t under permutations of the design.
+    `window` = (first z-plane, planes), default the whole grid."""
+
+    _NAME = "glm"
+
+    def __init__(self, grid, design, window=None, device=0):
+        X = np.ascontiguousarray(design, np.float64)
+        if X.ndim != 2:
+            raise ValueError("design: one row per image, one column per regressor")
+        first, planes = (0, int(grid[0][2])) if window is None else (int(window[0]), int(window[1]))
+        super().__init__(grid, first, planes, X.shape[0], X.shape[1], X.ctypes.data_as(_abi.c_double_p), int(device))
+        self.design = X
+        self.window = (first, planes)
+        self.shape = (planes,) + self.dims[1::-1]
+
+    def add(self, volume, chain=None, mask=None, interpolation=1, background=0.0):
+        """Keeps `volume` where CoverAverage.add with the same arguments would count it and its value is finite."""
+        _, src, mv, _, _ = self._views(volume, mask)
+        _abi.check(self._lib.frog_glm_add(self._h, chain._h if chain is not None else None, src, mv, int(interpolation),
+                                          float(background)), "frog_glm_add")
+
+    def add_jacobian(self, chain, support=None, mask=None, log=True):
+        """Keeps the Jacobian determinant of `chain` at every window voxel (what Chain.sample gives there), or with `log` its
+        logarithm where it is positive.  `support` = (dims(x, y, z), origin, spacing): the voxel counts only where the chain
+        takes it inside that geometry; `mask` as in add."""
+        sv = None
+        if support is not None:
+            dims, origin, spacing = support
+            sv = C.byref(_abi.volume_view(None, tuple(float(v) for v in origin), tuple(float(v) for v in spacing), tuple(int(d) for d in dims)))
+        mv = self._views(mask)[1] if mask is not None else None
+        _abi.check(self._lib.frog_glm_add_jacobian(self._h, chain._h if chain is not None else None, sv, mv, int(bool(log))),
+                   "frog_glm_add_jacobian")
+
+    def plane(self, image_index):
+        """What add number image_index stored over the window: float32, NaN (0x7FC00000) where it does not take part."""
+        out = np.empty(self.shape, np.float32)
+        _abi.check(self._lib.frog_glm_plane(self._h, int(image_index), out.ctypes.data_as(_abi.c_float_p)), "frog_glm_plane")
+        return out
+
+    def _fit_arguments(self, contrasts, region):
+        c = np.ascontiguousarray(contrasts, np.float64).reshape(-1, self.design.shape[1])
+        r = None if region is None else np.ascontiguousarray(np.asarray(region) != 0, np.uint8)
+        if r is not None and r.shape != self.shape:
+            raise ValueError("region: one value per window voxel")
+        return c, r, None if r is None else r.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def finish(self, contrasts, min_count=1, sigma_floor=0.0, region=None, fill=0.0):
+        """(beta, sigma, t, count) over the window: beta float32 (n_columns,) + shape, sigma float32, t float32 (n_contrasts,)
+        + shape, count uint16.  Voxels that are not fit hold `fill` in beta, sigma and t; a fit voxel whose residual stdev is
+        <= sigma_floor has t = NaN."""
+        c, _r, rp = self._fit_arguments(contrasts, region)
+        beta = np.empty((self.design.shape[1],) + self.shape, np.float32)
+        sigma = np.empty(self.shape, np.float32)
+        t = np.empty((len(c),) + self.shape, np.float32)
+        count = np.empty(self.shape, np.uint16)
+        _abi.check(self._lib.frog_glm_finish(self._h, len(c), c.ctypes.data_as(_abi.c_double_p), int(min_count), float(sigma_floor), rp,
+                                             float(fill), beta.ctypes.data_as(_abi.c_float_p), sigma.ctypes.data_as(_abi.c_float_p),
+                                             t.ctypes.data_as(_abi.c_float_p) if len(c) else None,
+                                             count.ctypes.data_as(C.POINTER(C.c_uint16))), "frog_glm_finish")
+        return beta, sigma, t, count
+
+    def permute(self, contrasts, perm, sign=None, columns=None, min_count=1, sigma_floor=0.0, region=None):
+        """(max_t, min_t), float32 (n_perms, n_contrasts): the extrema of each contrast's t over the window's fit voxels under
+        every row of `perm` (n_perms x n_images image indices) and `sign` (+-1, or None).  `columns`: the design columns that
+        move, an iterable of indices or a bit mask; default all."""
+        c, _r, rp = self._fit_arguments(contrasts, region)
+        pm = np.ascontiguousarray(perm, np.uint32).reshape(-1, self.design.shape[0])
+        sg = None if sign is None else np.ascontiguousarray(sign, np.int8).reshape(pm.shape)
+        p = self.design.shape[1]
+        bits = (1 << p) - 1 if columns is None else (int(columns) if np.isscalar(columns) else sum(1 << int(j) for j in set(columns)))
+        hi = np.empty((len(pm), len(c)), np.float32)
+        lo = np.empty((len(pm), len(c)), np.float32)
+        _abi.check(self._lib.frog_glm_permute(self._h, len(c), c.ctypes.data_as(_abi.c_double_p), int(min_count), float(sigma_floor), rp,
+                                              bits, len(pm), pm.ctypes.data_as(_abi.c_u32_p),
+                                              None if sg is None else sg.ctypes.data_as(C.POINTER(C.c_int8)),
+                                              hi.ctypes.data_as(_abi.c_float_p), lo.ctypes.data_as(_abi.c_float_p)), "frog_glm_permute")
+        return hi, lo
+
+
+def glm_planes(grid, n_images, device=0):
+    """The most z-planes of `grid` a GroupGLM window for n_images may hold on the device now (frog_glm_planes)."""
+    dims, origin, spacing = grid
+    g = _abi.volume_view(None, origin, spacing, tuple(int(d) for d in dims))
+    planes = C.c_uint32()
+    _abi.check(_abi.hip_lib().frog_glm_planes(C.byref(g), int(n_images), int(device), C.byref(planes)), "frog_glm_planes")
+    return planes.value
+
+
+def glm_draw(n, n_perms, seed=0, shuffle=True, flip=False):
+    """(perm uint32, sign int8), both (n_perms, n): frog_glm_draw's permutations and signs.  Row 0 is the identity with every
+    sign +1.  Host code: no device is needed."""
+    perm = np.empty((int(n_perms), int(n)), np.uint32)
+    sign = np.empty((int(n_perms), int(n)), np.int8)
+    _abi.check(_abi.hip_lib().frog_glm_draw(int(n), int(n_perms), int(seed) & (2 ** 64 - 1), int(bool(shuffle)), int(bool(flip)),
+                                            perm.ctypes.data_as(_abi.c_u32_p), sign.ctypes.data_as(C.POINTER(C.c_int8))), "frog_glm_draw")
+    return perm, sign
+
+
+def _float_keys(x):
+    """frog_rank's keys of float32 values: their unsigned order is -inf < ... < -0 < +0 < ... < +inf."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    return np.where(u >> 31 != 0, ~u, u ^ np.uint32(0x80000000))
+
+
+def fwe_p(t, max_t, min_t=None, fit=None):
+    """The family-wise corrected p-map of one contrast: p[v] = (float32)((1 + #{k >= 1: max_t[k] >= t[v]}) / (double)n_perms),
+    max_t the n_perms maxima over the whole grid with row 0 the unpermuted design.  With min_t the two-sided form: max(max_t,
+    -min_t) against |t|.  Voxels outside `fit`, and NaN voxels, get 1."""
+    t = np.asarray(t, np.float32)
+    hi = np.asarray(max_t, np.float32)
+    if min_t is not None:
+        hi, t = np.maximum(hi, -np.asarray(min_t, np.float32)), np.abs(t)
+    null = np.sort(hi[1:])
+    beyond = len(null) - np.searchsorted(null, t, side="left")
+    p = ((1 + beyond).astype(np.float64) / np.float64(len(hi))).astype(np.float32)
+    bad = np.isnan(t) if fit is None else (np.isnan(t) | ~np.asarray(fit, bool))
+    return np.where(bad, np.float32(1), p)
+
+
+def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=None, value="logjacobian", supports=None, interpolation=1,
+              min_count=1, sigma_floor=0.0, region=None, fill=0.0, n_perms=0, seed=0, columns=None, flip=False, two_sided=False,
+              max_planes=None, device=0):
+    """The per-voxel linear model of a registered group (bin/GroupStats).  value "logjacobian" or "jacobian": image i is the
+    (log) Jacobian determinant of chains[i] on `grid`, counted where the chain lands inside supports[i] (a geometry, optional)
+    and masks[i]; value "images": volumes[i] resliced as in cover_average().  With n_perms > 0 the columns `columns` (default
+    those with a non-zero entry in any contrast) are permuted (and with `flip` sign-flipped) n_perms - 1 times by glm_draw(seed),
+    row 0 being the design itself.  The device holds slabs of glm_planes() z-planes (at most max_planes); the slabs' extrema are
+    combined with max and min, which changes no bit.  Returns a dict: beta, sigma, t, count, fit (bool: the voxel was fit), and
+    with permutations max_t, min_t (n_perms, n_contrasts) and p (n_contrasts,) + shape from fwe_p()."""
+    X = np.ascontiguousarray(design, np.float64)
+    c = np.ascontiguousarray(contrasts, np.float64).reshape(-1, X.shape[1])
+    n = X.shape[0]
+    images = value == "images"
+    if value not in ("logjacobian", "jacobian", "images"):
+        raise ValueError("value: logjacobian, jacobian or images")
+    if images:
+        vols, grid = _group(volumes, chains, masks, grid)
+        if len(vols) != n:
+            raise ValueError("one design row per volume expected")
+    elif chains is None or len(chains) != n or grid is None:
+        raise ValueError("a grid and one chain per design row expected")
+    dims = tuple(int(d) for d in grid[0])
+    shape = dims[::-1]
+    reg = None if region is None else np.asarray(region) != 0
+    planes = glm_planes(grid, n, device)
+    if max_planes is not None:
+        planes = max(1, min(planes, int(max_planes)))
+    if columns is None:
+        columns = [j for j in range(X.shape[1]) if (c[:, j] != 0).any()]
+    out = dict(beta=np.empty((X.shape[1],) + shape, np.float32), sigma=np.empty(shape, np.float32), t=np.empty((len(c),) + shape, np.float32),
+               count=np.empty(shape, np.uint16))
+    perm, sign = glm_draw(n, n_perms, seed, True, flip) if n_perms else (None, None)
+    hi = lo = None
+    for first in range(0, dims[2], planes):
+        m = min(planes, dims[2] - first)
+        acc = GroupGLM(grid, X, (first, m), device)
+        try:
+            for k in range(n):
+                mask = None if masks is None else masks[k]
+                if images:
+                    acc.add(vols[k], None if chains is None else chains[k], mask, interpolation)
+                else:
+                    acc.add_jacobian(chains[k], None if supports is None else supports[k], mask, value == "logjacobian")
+            r = None if reg is None else reg[first:first + m]
+            b, s, t, k = acc.finish(c, min_count, sigma_floor, r, fill)
+            marked = acc.finish(c, min_count, sigma_floor, r, -1.0)[1]      # a residual stdev is never -1: the unfit voxels
+            sl = slice(first, first + m)
+            out["beta"][:, sl], out["sigma"][sl], out["t"][:, sl], out["count"][sl] = b, s, t, k
+            out.setdefault("fit", np.empty(shape, bool))[sl] = marked != -1
+            if n_perms:
+                h, l = acc.permute(c, perm, sign if flip else None, columns, min_count, sigma_floor, r)
+                if hi is None:
+                    hi, lo = h, l
+                else:
+                    hi, lo = np.where(_float_keys(h) > _float_keys(hi), h, hi), np.where(_float_keys(l) < _float_keys(lo), l, lo)
+        finally:
+            acc.close()
+    if n_perms:
+        out["max_t"], out["min_t"] = hi, lo
+        out["p"] = np.stack([fwe_p(out["t"][j], hi[:, j], lo[:, j] if two_sided else None, out["fit"]) for j in range(len(c))])
+    return out
+
+
 FUSED_DTYPES = ("uint8", "uint16", "int16", "int32", "uint32")
 
 

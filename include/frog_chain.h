@@ -575,6 +575,98 @@ int  frog_surface_create(const frog_volume *reference, const int64_t *values, ui
 int  frog_surface_add(frog_surface *a, frog_chain *chain, const frog_volume *source, double background, frog_surface_row *rows);
 void frog_surface_destroy(frog_surface *a);
 
+/* ---- a per-voxel linear model over the group and its permutation test (an extension: tensor-based morphometry; the reference
+ * has no counterpart) ------------------------------------------------------------------------------------------------------------
+ * Where do the images of a registered group differ from each other: per grid voxel the model y_i = sum_j X_ij beta_j + e_i over
+ * the images i that take part there, y_i the image's value (its resliced intensity, or the Jacobian determinant of its chain or
+ * its logarithm), X the n_images x n_columns design (row i belongs to add number i), one t statistic per contrast, and the
+ * maximum and minimum of each t over the voxels under permutations of the design, from which family-wise corrected p-values are
+ * formed (Nichols and Holmes, Human Brain Mapping 15, 2002).
+ * The accumulator holds the z-planes [first_plane, first_plane + n_planes) of `grid`, the WINDOW, exactly as frog_rank does: a
+ * voxel's position is computed from its index in the whole grid, so windows that partition the grid give, bit for bit, what one
+ * whole-grid window gives.  The device holds one f32 per image and window voxel; the bits 0x7FC00000 (a NaN) mean "does not take
+ * part".  frog_glm_planes is frog_rank_planes.
+ *
+ * What an add keeps.  Add number i fills plane i of the window.
+ *   frog_glm_add: x and the voxel's validity exactly as frog_rank_add takes them; the entry takes part iff the voxel is valid
+ *     and x is finite.
+ *   frog_glm_add_jacobian: det is the f64 value frog_chain_sample(chain, grid ...) stores for that node (the same device code).
+ *     The voxel is valid iff its position after the chain passes frog_cover_add's inside test against `support` (a frog_volume
+ *     of which only dims, origin and spacing are read; NULL: valid everywhere) and then frog_cover_add's mask rule at the same
+ *     position (mask may be NULL).  The chain is evaluated once.  log_mode 0: x = (float)det.  log_mode 1: x = (float)log(det)
+ *     where det > 0; elsewhere the entry does not take part, so a folded voxel is excluded.  The device's f64 log is not
+ *     correctly rounded (1 ulp, HIP's math table): that line alone is not stated to the bit.  Everything below is stated on the
+ *     stored plane, which frog_glm_plane returns.  A chain is required.
+ *   frog_glm_plane: what add number image_index stored, window-sized, 0x7FC00000 where the entry does not take part.
+ *
+ * frog_glm_finish and frog_glm_permute require exactly n_images adds.  Per window voxel, every floating-point line below is one
+ * separately rounded f64 operation (no contraction), loops ascending unless said otherwise.  p = n_columns.
+ *   Design rows X'.  In finish X'_i = X_i.  In permutation k of permute, for the columns j whose bit is set in `columns`:
+ *       X'_ij = (double)sign[k][i] * X[perm[k][i]][j]                     (one multiplication; sign == NULL: 1.0)
+ *     and X'_ij = X_ij for every other column (Draper-Stoneman; with all bits set the rows move: Manly; with perm the identity
+ *     it is sign flipping, the one-sample test).  perm and sign are n_perms x n_images, row k permutation k.
+ *   Participating set.  S = the images whose entry takes part, in add order; k = |S|.  The voxel is UNFIT if `region` (u8,
+ *     window-sized, may be NULL) is 0 there or k < max(min_count, p + 1).
+ *   Normal equations, over S in add order, each sum from +0.0:
+ *       for c <= r:  m = X'_ir * X'_ic;  A_rc = A_rc + m
+ *       y = (double)value_i;  for r:  m = X'_ir * y;  b_r = b_r + m
+ *   LDL^T with frog_jlabels_finish's loops:
+ *       for j:    D_j = A_jj;  for k < j:  q = L_jk * L_jk;  m = q * D_k;  D_j = D_j - m
+ *                 for i > j:   x = A_ij;  for k < j:  q = L_ik * L_jk;  m = q * D_k;  x = x - m;   then  L_ij = x / D_j
+ *       forward:  z_i = b_i;  for k < i:  m = L_ik * z_k;  z_i = z_i - m
+ *       diagonal: y_i = z_i / D_i
+ *       backward, i descending:  beta_i = y_i;  for k > i ascending:  m = L_ki * beta_k;  beta_i = beta_i - m
+ *     The voxel is UNFIT unless for every j  A_jj > 0  and  D_j > lim_j,  lim_j = 2^-40 * A_jj: a covering set that leaves one
+ *     group empty, or has fewer distinct covariate values than columns, drops out instead of dividing by rounding noise.
+ *   Residuals, over S in add order, rss from +0.0:
+ *       f = +0.0;  for j:  m = X'_ij * beta_j;  f = f + m;      r = y - f;  q = r * r;  rss = rss + q
+ *       s2 = rss / (double)(k - p);  sd = sqrt(s2)                                                  correctly rounded
+ *   Per contrast c (p doubles, row c of `contrasts`):  u = the solution of A u = c with the same factor and the same three loops;
+ *       v = +0.0;  for j:  m = c_j * u_j;  v = v + m;        e = +0.0;  for j:  m = c_j * beta_j;  e = e + m
+ *       den = s2 * v;  den = sqrt(den);  g = e / den;  t = (float)g
+ *     Where sd <= sigma_floor (the default 0 catches an exact fit) or t is not finite (a NaN, or a quotient beyond f32):
+ *     t = 0x7FC00000.  So t is finite or that one NaN, never +-inf.
+ *   finish, window-sized host buffers, any may be NULL, not all: beta (p planes, (float)beta_j), sigma ((float)sd), t (n_contrasts
+ *     planes; NULL or n_contrasts == 0: none), count (k, always the raw count).  Unfit voxels get `fill` in beta, sigma and t.
+ *   permute: max_t[k * n_contrasts + c] and min_t[...] (either may be NULL, not both) are the largest and smallest t of contrast c
+ *     over the window's voxels that are fit under permutation k and whose t is not the NaN; -inf and +inf where there is none.  A
+ *     voxel may be fit under one permutation and unfit under another.  The order of floats used is that of frog_rank's keys
+ *     (-0 < +0).  Extrema are exact: the result does not depend on scheduling, on how n_perms is cut into calls or launches, or
+ *     on windows (combine windows with max and min).  No floating-point atomic is used.
+ *
+ * frog_glm_draw (host code, no device): permutations and signs from splitmix64,
+ *       next():  s += 0x9E3779B97F4A7C15;  z = s;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *                return z ^ z >> 31                                              (u64 arithmetic; s starts at seed)
+ *   Row 0 is the identity with every sign +1 and consumes no draw.  For k >= 1 in turn: perm[k] starts as the identity; with
+ *   shuffle != 0, for i = n - 1 down to 1:  j = next() % (i + 1);  swap perm[k][i] and perm[k][j]  (Fisher-Yates; the modulo bias
+ *   is below n / 2^64 < 2^-52); then with flip != 0, for i ascending:  sign[k][i] = (next() >> 63) ? -1 : +1;  without flip +1.
+ *   sign may be NULL when flip == 0.
+ *
+ * FROG_E_INVALID, before the device is touched: a NULL argument that is not marked optional, everything frog_rank_create refuses
+ * for the grid and the window, n_images == 0 or > FROG_GLM_MAX_IMAGES, n_columns == 0 or > FROG_GLM_MAX_COLUMNS,
+ * n_images <= n_columns, a design entry that is not finite; in the adds what frog_rank_add refuses, a NULL chain or a support
+ * or mask the chain cannot sample in add_jacobian, the (n_images + 1)th add; in plane an image_index not yet added; in finish
+ * and permute fewer than n_images adds, min_count == 0, n_contrasts > FROG_GLM_MAX_CONTRASTS, a contrast entry that is not
+ * finite, a sigma_floor that is negative or NaN, no output; in permute n_contrasts == 0, n_perms == 0, a perm entry >= n_images,
+ * a sign other than +-1, columns == 0 or with a bit >= n_columns; in draw n == 0 or > FROG_GLM_MAX_IMAGES, n_perms == 0. */
+#define FROG_GLM_MAX_IMAGES 4096
+#define FROG_GLM_MAX_COLUMNS 8
+#define FROG_GLM_MAX_CONTRASTS 8
+typedef struct frog_glm frog_glm;
+int  frog_glm_planes(const frog_volume *grid, uint32_t n_images, int device, uint32_t *planes);
+int  frog_glm_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_planes, uint32_t n_images, uint32_t n_columns,
+                     const double *design, int device, frog_glm **out);
+int  frog_glm_add(frog_glm *a, frog_chain *chain, const frog_volume *source, const frog_volume *mask, int interpolation, double background);
+int  frog_glm_add_jacobian(frog_glm *a, frog_chain *chain, const frog_volume *support, const frog_volume *mask, int log_mode);
+int  frog_glm_plane(frog_glm *a, uint32_t image_index, float *values);
+int  frog_glm_finish(frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                     const uint8_t *region, float fill, float *beta, float *sigma, float *t, uint16_t *count);
+int  frog_glm_permute(frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                      const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
+                      float *max_t, float *min_t);
+int  frog_glm_draw(uint32_t n, uint32_t n_perms, uint64_t seed, int shuffle, int flip, uint32_t *perm, int8_t *sign);
+void frog_glm_destroy(frog_glm *a);
+
 #ifdef __cplusplus
 }
 #endif
