@@ -1072,7 +1072,7 @@ struct frog_average : frog_group {
     frog::DevBuf<float> d_avg, d_sq;
 };
 
-// an accumulator whose adds take a mask (frog_cover, frog_rank)
+// an accumulator whose adds take a mask (frog_cover, frog_rank, frog_glm)
 struct frog_masked : frog_group {
     frog::DevBuf<unsigned char> d_mask;             // staging of the current u8 mask, grown on demand
     std::vector<unsigned char> h_mask;              // the mask as value != 0, before its upload
@@ -1085,58 +1085,63 @@ struct frog_cover : frog_masked {
     frog::DevBuf<uint16_t> d_count;
 };
 
-// one plane of sort keys per added image over a window of z-planes of one grid
-struct frog_rank : frog_masked {
+// an accumulator that stores one plane per added image over a window of z-planes of one grid (frog_rank, frog_glm)
+struct frog_windowed : frog_masked {
     uint32_t n_images = 0, added = 0;
     size_t first = 0, window = 0;                   // the window's first voxel in the grid, and its voxels
+};
+
+// one plane of sort keys per added image
+struct frog_rank : frog_windowed {
     frog::DevBuf<uint32_t> d_keys;                  // n_images planes of `window` keys, in the order of the adds
 };
 
-// one plane of f32 values per added image over a window of z-planes of one grid, and the design of the linear model
-struct frog_glm : frog_masked {
-    uint32_t n_images = 0, added = 0, p = 0;
-    size_t first = 0, window = 0;                   // as in frog_rank
+// one plane of f32 values per added image, and the design of the linear model
+struct frog_glm : frog_windowed {
+    uint32_t p = 0;
     std::vector<double> design;                     // n_images x p
     frog::DevBuf<float> d_vals;                     // n_images planes of `window` values, in the order of the adds
     frog::DevBuf<double> d_design, d_table;         // d_table: the design rows of one launch's permutations, grown on demand
 };
 
-// vote counts of a group's label maps on one grid
-struct frog_labels : frog_group {
-    uint32_t n_images = 0, added = 0, max_labels = 0;
+// The label table of frog_labels, frog_wlabels (and through it frog_jlabels) and frog_staple: the device hash map in which
+// the adds' collect kernels number the label values they meet, the values that are accepted so far, and after finish the
+// sorted table.  The labels_* functions below work on it.
+struct LabelTable {
+    uint32_t max_labels = 0;
     bool finished = false;
-    LabelMap map{};                                 // device pointers into the five buffers below
+    LabelMap map{};                                 // device pointers into the four buffers below
     frog::DevBuf<long long> d_keys, d_values;
     frog::DevBuf<uint32_t> d_index, d_state;
-    std::vector<long long> known;                   // dense index -> value: the labels that have a plane
-    std::deque<frog::DevBuf<uint16_t>> planes;      // one per known label; growth never copies counts
-    frog::DevBuf<uint16_t *> d_planes;              // dense index -> plane
-    // after finish: the table in ascending order of the values (labels without a vote dropped)
+    std::vector<long long> known;                   // dense index -> value: the labels of the accepted volumes
+    // after finish: the table in ascending order of the values
     std::vector<long long> values;
-    std::vector<uint32_t> dense;                    // table position -> dense index
-    std::vector<uint64_t> voxels, pairs;
-    frog::DevBuf<uint16_t *> d_sorted_planes;
     frog::DevBuf<long long> d_sorted_values;
 };
 
+// vote counts of a group's label maps on one grid
+struct frog_labels : frog_group, LabelTable {
+    uint32_t n_images = 0, added = 0;
+    std::deque<frog::DevBuf<uint16_t>> planes;      // one per known label; growth never copies counts
+    frog::DevBuf<uint16_t *> d_planes;              // dense index -> plane
+    // after finish (labels without a vote dropped from the table)
+    std::vector<uint32_t> dense;                    // table position -> dense index
+    std::vector<uint64_t> voxels, pairs;
+    frog::DevBuf<uint16_t *> d_sorted_planes;
+};
+
 // weighted votes of a group of atlases for a target image on one grid
-struct frog_wlabels : frog_group {
-    uint32_t n_images = 0, added = 0, max_labels = 0, radius = 0, power = 0;
+struct frog_wlabels : frog_group, LabelTable {
+    uint32_t n_images = 0, added = 0, radius = 0, power = 0;
     float floor = 0;
-    bool has_target = false, finished = false;
-    LabelMap map{};                                 // as in frog_labels
-    frog::DevBuf<long long> d_keys, d_values;
-    frog::DevBuf<uint32_t> d_index, d_state;
-    std::vector<long long> known;                   // dense index -> value: the labels that have a plane
+    bool has_target = false;
     std::deque<frog::DevBuf<float>> planes;         // one f32 score plane per known label
     frog::DevBuf<float *> d_planes;                 // dense index -> plane
     frog::DevBuf<float> d_target, d_atlas;          // t and a on the grid, NaN where not valid
     frog::DevBuf<unsigned char> d_lsrc, d_lout;     // staging of the current label map / resliced label map
-    // after finish: the table in ascending order of the values
-    std::vector<long long> values;
+    // after finish
     std::vector<uint32_t> dense;                    // table position -> dense index
     frog::DevBuf<float *> d_sorted_planes;
-    frog::DevBuf<long long> d_sorted_values;
 };
 
 // joint label fusion: frog_wlabels' target plane, label map and score planes, and what the adds leave for finish
@@ -1151,17 +1156,11 @@ struct frog_jlabels : frog_wlabels {
 };
 
 // the dense label index of every image at every voxel of one grid, and the EM state of frog_staple_solve
-struct frog_staple : frog_group {
-    uint32_t n_images = 0, added = 0, max_labels = 0;
-    bool finished = false, solved = false;
-    LabelMap map{};                                 // as in frog_labels
-    frog::DevBuf<long long> d_keys, d_values;
-    frog::DevBuf<uint32_t> d_index, d_state;
-    std::vector<long long> known;                   // dense index of the adds -> value
+struct frog_staple : frog_group, LabelTable {
+    uint32_t n_images = 0, added = 0;
+    bool solved = false;
     frog::DevBuf<uint8_t> d_D;                      // n_images planes: before finish the adds' indices, after it D[i][v]
     // after finish
-    std::vector<long long> values;                  // ascending
-    frog::DevBuf<long long> d_sorted_values;
     frog::DevBuf<uint8_t> d_active;
     frog::DevBuf<uint32_t> d_q;                     // L planes
     frog::DevBuf<double> d_theta, d_prior;
@@ -1400,15 +1399,22 @@ int stage_source(const char *where, frog_group *a, const frog_volume *src, bool 
     return FROG_OK;
 }
 
-// The return step of an add, after launches that ended with `e`: the resliced volume where one is asked for (what the chain
-// kernel stored in a->d_out; without a chain the source itself), then the stream drained.
+// A volume an add hands back on the grid, after launches that ended with `e`, where one is asked for: the `bytes` the chain
+// kernel stored at d_on_grid; without a chain the source itself.
+hipError_t copy_resliced(const frog_chain *c, const frog_volume *src, frog_volume *resliced, const void *d_on_grid, size_t bytes, hipError_t e)
+{
+    if (e == hipSuccess && resliced) {
+        if (c) e = hipMemcpy(resliced->data, d_on_grid, bytes, hipMemcpyDeviceToHost);
+        else std::memcpy(resliced->data, src->data, bytes);
+    }
+    return e;
+}
+
+// The return step of an add, after launches that ended with `e`: the resliced volume (in a->d_out), then the stream drained.
 template <class S>
 int return_resliced(const char *where, frog_group *a, const frog_chain *c, const frog_volume *src, frog_volume *resliced, hipError_t e)
 {
-    if (e == hipSuccess && resliced) {
-        if (c) e = hipMemcpy(resliced->data, a->d_out.p, a->total * sizeof(S), hipMemcpyDeviceToHost);
-        else std::memcpy(resliced->data, src->data, a->total * sizeof(S));
-    }
+    e = copy_resliced(c, src, resliced, a->d_out.p, a->total * sizeof(S), e);
     if (e == hipSuccess) e = hipStreamSynchronize(0);
     if (e != hipSuccess) return hip_fail(where, e);
     return FROG_OK;
@@ -1539,55 +1545,79 @@ int cover_inputs(const char *where, const frog_masked *a, const frog_chain *c, c
     return FROG_OK;
 }
 
+// ---- the label table (LabelTable) of frog_labels, frog_staple, frog_wlabels and frog_jlabels ---------------------------------
+
 // The device map rebuilt from the known labels alone (at creation: empty): how a refused volume's inserts are taken back.
-// A: frog_labels or frog_wlabels.
-template <class A>
-hipError_t labels_reset_map(A *a)
+hipError_t labels_reset_map(LabelTable *t)
 {
-    const size_t slots = (size_t)a->map.mask + 1;
+    const size_t slots = (size_t)t->map.mask + 1;
     std::vector<long long> keys(slots, LABEL_EMPTY);
     std::vector<uint32_t> index(slots, 0);
-    for (size_t i = 0; i < a->known.size(); i++) {
-        uint32_t slot = label_slot(a->known[i], a->map.shift);
-        while (keys[slot] != LABEL_EMPTY) slot = (slot + 1) & a->map.mask;            // load <= 1/2: a free slot exists
-        keys[slot] = a->known[i];
+    for (size_t i = 0; i < t->known.size(); i++) {
+        uint32_t slot = label_slot(t->known[i], t->map.shift);
+        while (keys[slot] != LABEL_EMPTY) slot = (slot + 1) & t->map.mask;            // load <= 1/2: a free slot exists
+        keys[slot] = t->known[i];
         index[slot] = (uint32_t)i;
     }
-    const uint32_t state[2] = { (uint32_t)a->known.size(), 0 };
-    hipError_t e = hipMemcpy(a->d_keys.p, keys.data(), slots * sizeof(long long), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(a->d_index.p, index.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(a->d_state.p, state, sizeof state, hipMemcpyHostToDevice);
+    const uint32_t state[2] = { (uint32_t)t->known.size(), 0 };
+    hipError_t e = hipMemcpy(t->d_keys.p, keys.data(), slots * sizeof(long long), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_index.p, index.data(), slots * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(t->d_state.p, state, sizeof state, hipMemcpyHostToDevice);
     return e;
 }
 
-// The empty device map of a new accumulator (A: frog_labels, frog_wlabels or frog_staple) for a->max_labels labels: at
-// least 16 slots, at least two per label.
-template <class A>
-int labels_new_map(A *a)
+// The empty device map of a new accumulator for max_labels labels: at least 16 slots, at least two per label.
+int labels_new_map(LabelTable *t, uint32_t max_labels)
 {
+    t->max_labels = max_labels;
     int bits = 4;
-    while (((size_t)1 << bits) < 2 * (size_t)a->max_labels) bits++;
+    while (((size_t)1 << bits) < 2 * (size_t)max_labels) bits++;
     const size_t slots = (size_t)1 << bits;
-    KCHECK(a->d_keys.alloc(slots));
-    KCHECK(a->d_index.alloc(slots));
-    KCHECK(a->d_values.alloc(a->max_labels));
-    KCHECK(a->d_state.alloc(2));
-    a->map = LabelMap{ a->d_keys.p, a->d_index.p, a->d_values.p, a->d_state.p, (uint32_t)(slots - 1), 64 - bits, a->max_labels };
-    KCHECK(labels_reset_map(a));
+    KCHECK(t->d_keys.alloc(slots));
+    KCHECK(t->d_index.alloc(slots));
+    KCHECK(t->d_values.alloc(max_labels));
+    KCHECK(t->d_state.alloc(2));
+    t->map = LabelMap{ t->d_keys.p, t->d_index.p, t->d_values.p, t->d_state.p, (uint32_t)(slots - 1), 64 - bits, max_labels };
+    KCHECK(labels_reset_map(t));
     return FROG_OK;
 }
 
-// The planes of the labels an add has found beyond the n_known that had one: their values from the device map, a zeroed
-// plane of P each, the pointers behind d_planes.  On a failure the new planes are gone again and `known` is as it was.
-template <class P>
-hipError_t labels_grow_planes(size_t total, size_t n_now, const long long *d_values, std::vector<long long> &known,
-                              std::deque<frog::DevBuf<P>> &planes, P **d_planes)
+// After an add's collect the map may hold values that `known` does not: every failure from there on takes them back, so
+// the volume leaves no label behind.
+int labels_refuse(LabelTable *t, int rc) { (void)labels_reset_map(t); return rc; }
+
+// What follows the collect launches of `where`, which ended with `e`: the map's state read, and a volume refused whose
+// labels do not fit the table.  *n_now: the labels the map holds now, the known ones first.
+int labels_collected(const char *where, LabelTable *t, hipError_t e, size_t *n_now)
 {
-    const size_t n_known = known.size();
-    if (n_now <= n_known) return hipSuccess;
-    std::vector<long long> fresh(n_now - n_known);
+    uint32_t state[2] = { 0, 0 };
+    if (e == hipSuccess) e = hipMemcpy(state, t->d_state.p, sizeof state, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return labels_refuse(t, hip_fail(where, e));
+    if (state[1] || state[0] > t->max_labels)
+        return labels_refuse(t, fail(FROG_E_INVALID, std::string(where) + ": more than max_labels = " + std::to_string(t->max_labels) + " distinct labels"));
+    *n_now = state[0];
+    return FROG_OK;
+}
+
+// the values of the labels the map holds beyond the known ones, in the order of their dense indices
+hipError_t labels_fresh_values(const LabelTable *t, size_t n_now, std::vector<long long> &fresh)
+{
+    const size_t n_known = t->known.size();
+    fresh.resize(n_now - n_known);
+    if (fresh.empty()) return hipSuccess;
+    return hipMemcpy(fresh.data(), t->d_values.p + n_known, fresh.size() * sizeof(long long), hipMemcpyDeviceToHost);
+}
+
+// The planes of the labels an add has found beyond those that had one: a zeroed plane of P each, the pointers behind
+// d_planes, and then the labels known.  On a failure the new planes are gone again and `known` is as it was.
+template <class P>
+hipError_t labels_grow_planes(LabelTable *t, size_t total, size_t n_now, std::deque<frog::DevBuf<P>> &planes, P **d_planes)
+{
+    const size_t n_known = t->known.size();
+    std::vector<long long> fresh;
     std::vector<P *> pointers;
-    hipError_t e = hipMemcpy(fresh.data(), d_values + n_known, fresh.size() * sizeof(long long), hipMemcpyDeviceToHost);
+    hipError_t e = labels_fresh_values(t, n_now, fresh);
+    if (fresh.empty()) return e;
     for (size_t i = 0; i < fresh.size() && e == hipSuccess; i++) {
         planes.emplace_back();
         e = planes.back().alloc(total);
@@ -1600,65 +1630,153 @@ hipError_t labels_grow_planes(size_t total, size_t n_now, const long long *d_val
         while (planes.size() > n_known) planes.pop_back();
         return e;
     }
-    known.insert(known.end(), fresh.begin(), fresh.end());
+    t->known.insert(t->known.end(), fresh.begin(), fresh.end());
     return hipSuccess;
+}
+
+// The table of a finish: `order`, the dense indices of the labels that enter it, sorted by their values; those values in
+// t->values and on the device.
+int labels_sort(LabelTable *t, std::vector<uint32_t> &order)
+{
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return t->known[x] < t->known[y]; });
+    t->values.clear();
+    for (const uint32_t i : order) t->values.push_back(t->known[i]);
+    KCHECK(t->d_sorted_values.alloc(order.size()));
+    KCHECK(hipMemcpy(t->d_sorted_values.p, t->values.data(), order.size() * sizeof(long long), hipMemcpyHostToDevice));
+    return FROG_OK;
+}
+
+// every known label in the order of the adds: what a finish that drops none hands to labels_sort
+std::vector<uint32_t> labels_all(const LabelTable *t)
+{
+    std::vector<uint32_t> order(t->known.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+    return order;
+}
+
+// the planes of a sorted table's labels behind d_sorted_planes
+template <class P>
+int labels_sort_planes(const std::vector<uint32_t> &order, std::deque<frog::DevBuf<P>> &planes, frog::DevBuf<P *> &d_sorted_planes)
+{
+    std::vector<P *> sorted_planes;
+    for (const uint32_t i : order) sorted_planes.push_back(planes[i].p);
+    KCHECK(d_sorted_planes.alloc(order.size()));
+    KCHECK(hipMemcpy(d_sorted_planes.p, sorted_planes.data(), order.size() * sizeof(P *), hipMemcpyHostToDevice));
+    return FROG_OK;
+}
+
+// *l: the position of `value` in the sorted table; `where`: `tail` if it is not there
+int labels_find(const char *where, const char *tail, const LabelTable *t, int64_t value, size_t *l)
+{
+    const auto it = std::lower_bound(t->values.begin(), t->values.end(), (long long)value);
+    if (it == t->values.end() || *it != (long long)value) return fail(FROG_E_INVALID, std::string(where) + ": " + tail);
+    *l = (size_t)(it - t->values.begin());
+    return FROG_OK;
+}
+
+// every value of the table is a T
+template <class T>
+bool labels_fit(const LabelTable *t)
+{
+    for (const long long v : t->values)
+        if (v < (long long)std::numeric_limits<T>::lowest() || v > (long long)std::numeric_limits<T>::max()) return false;
+    return true;
+}
+
+// How every getter of a label accumulator opens: `given`, its arguments are all there; `ready`, the accumulator is past
+// the call `after`, from which on the getter has something to give.
+int labels_getter(const char *where, bool given, bool ready, const char *after)
+{
+    if (!given) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (!ready) return fail(FROG_E_INVALID, std::string(where) + ": before " + after);
+    return FROG_OK;
+}
+
+// what the frog_*_values entry points give: the sorted table
+int labels_values(const char *where, const LabelTable *t, const char *after, int64_t *values)
+{
+    if (int rc = labels_getter(where, t && values, t && t->finished, after)) return rc;
+    for (size_t l = 0; l < t->values.size(); l++) values[l] = t->values[l];
+    return FROG_OK;
+}
+
+// What the frog_*_fused entry points refuse alike, in this order, before the accumulator's device is made current: missing
+// arguments, an accumulator that is not `ready` (past `after`), a fused map of a type that is no integer's or not grid-sized.
+int fused_arguments(const char *where, const frog_group *a, bool ready, const char *after, const frog_volume *label, const float *second)
+{
+    const std::string w = std::string(where) + ": ";
+    if (int rc = labels_getter(where, a && (label || second) && (!label || label->data), ready, after)) return rc;
+    if (label) {
+        if (!integer_voxel_type(label->dtype)) return fail(FROG_E_INVALID, w + "the fused map has an integer type");
+        if (!grid_sized(a, label)) return fail(FROG_E_INVALID, w + "the fused map is not grid-sized");
+    }
+    KCHECK(hipSetDevice(a->device));
+    return FROG_OK;
+}
+
+// A fused output of type T: the fused map and its f32 companion (agreement or confidence), each only where asked for, on the
+// device; launch(blocks, base, d_label, d_second) for the chunks of the grid; the copies back.
+template <class T, class Launch>
+int fused_output(const char *where, const frog_group *a, frog_volume *label, float *second, Launch launch)
+{
+    frog::DevBuf<T> d_label;
+    frog::DevBuf<float> d_second;
+    if (label) KCHECK(d_label.alloc(a->total));
+    if (second) KCHECK(d_second.alloc(a->total));
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) { launch(blocks, base, d_label.p, d_second.p); });
+    if (e == hipSuccess && label) e = hipMemcpy(label->data, d_label.p, a->total * sizeof(T), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && second) e = hipMemcpy(second, d_second.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(where, e);
+    return FROG_OK;
+}
+
+// A probability output: the accumulator's device made current, one f32 plane of the grid on it, launch(blocks, base, d_p) for
+// the chunks of the grid, the copy back.
+template <class Launch>
+int probability_output(const char *where, const frog_group *a, float *p, Launch launch)
+{
+    KCHECK(hipSetDevice(a->device));
+    frog::DevBuf<float> d_p;
+    KCHECK(d_p.alloc(a->total));
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) { launch(blocks, base, d_p.p); });
+    if (e == hipSuccess) e = hipMemcpy(p, d_p.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(where, e);
+    return FROG_OK;
+}
+
+// The collect step of frog_labels_add and frog_staple_add for a source of type S: the source staged and its labels -- with a
+// chain the resliced ones, which the kernel leaves in a->d_out -- numbered in the table's map.  *d_labels: those labels on the
+// grid; *n_now as labels_collected gives it.
+template <class S>
+int labels_collect(const char *where, frog_group *a, LabelTable *t, frog_chain *c, const frog_volume *src, double background,
+                   const S **d_labels, size_t *n_now)
+{
+    ResliceGrid g;
+    if (int rc = stage_source<S>(where, a, src, c != nullptr, 0, background, &g)) return rc;
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = (S *)a->d_out.p;                     // with a chain the votes are read from the resliced labels
+    *d_labels = c ? d_out : d_src;
+    const hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            labels_collect_kernel<S, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->total, d_out, t->map);
+        else
+            labels_collect_kernel<S, false><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, a->total, nullptr, t->map);
+    });
+    return labels_collected(where, t, e, n_now);
 }
 
 template <class S>
 int labels_add_typed(frog_labels *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
 {
-    ResliceGrid g;
-    if (int rc = stage_source<S>("frog_labels_add", a, src, c != nullptr, 0, background, &g)) return rc;
-    const S *d_src = (const S *)a->d_src.p;
-    S *d_out = (S *)a->d_out.p;                     // with a chain the votes are read from the resliced labels
-    const S *d_labels = c ? d_out : d_src;
-    uint32_t state[2] = { 0, 0 };
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        if (c)
-            labels_collect_kernel<S, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->total, d_out, a->map);
-        else
-            labels_collect_kernel<S, false><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, a->total, nullptr, a->map);
-    });
-    if (e == hipSuccess) e = hipMemcpy(state, a->d_state.p, sizeof state, hipMemcpyDeviceToHost);
-    // from here on the map may hold values without a plane: every failure takes them back, so the volume leaves no vote
-    auto refuse = [&](int rc) { (void)labels_reset_map(a); return rc; };
-    if (e != hipSuccess) return refuse(hip_fail("frog_labels_add", e));
-    if (state[1] || state[0] > a->max_labels)
-        return refuse(fail(FROG_E_INVALID, "frog_labels_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
-    const size_t n_now = state[0];
-    e = labels_grow_planes<uint16_t>(a->total, n_now, a->d_values.p, a->known, a->planes, a->d_planes.p);
-    if (e != hipSuccess) return refuse(hip_fail("frog_labels_add", e));
+    const S *d_labels;
+    size_t n_now;
+    if (int rc = labels_collect<S>("frog_labels_add", a, a, c, src, background, &d_labels, &n_now)) return rc;
+    hipError_t e = labels_grow_planes<uint16_t>(a, a->total, n_now, a->planes, a->d_planes.p);
+    if (e != hipSuccess) return labels_refuse(a, hip_fail("frog_labels_add", e));
     e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
         labels_vote_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_labels, a->total, a->map, a->d_planes.p, (uint32_t)n_now);
     });
     return return_resliced<S>("frog_labels_add", a, c, src, resliced, e);
-}
-
-// every value of the table is a T
-template <class T, class A>
-bool labels_fit(const A *a)
-{
-    for (const long long v : a->values)
-        if (v < (long long)std::numeric_limits<T>::lowest() || v > (long long)std::numeric_limits<T>::max()) return false;
-    return true;
-}
-
-template <class T>
-int labels_fused_typed(frog_labels *a, frog_volume *label, float *agreement)
-{
-    if (label && !labels_fit<T>(a)) return fail(FROG_E_INVALID, "frog_labels_fused: a label value does not fit the requested type");
-    frog::DevBuf<T> d_label;
-    frog::DevBuf<float> d_agreement;
-    if (label) KCHECK(d_label.alloc(a->total));
-    if (agreement) KCHECK(d_agreement.alloc(a->total));
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        labels_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
-                                                         (float)a->n_images, d_label.p, d_agreement.p);
-    });
-    if (e == hipSuccess && label) e = hipMemcpy(label->data, d_label.p, a->total * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && agreement) e = hipMemcpy(agreement, d_agreement.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("frog_labels_fused", e);
-    return FROG_OK;
 }
 
 // the tiles of wlabels_vote_kernel over the accumulator's grid
@@ -1691,7 +1809,33 @@ int wlabels_target_typed(const char *where, frog_wlabels *a, frog_chain *c, cons
     return return_resliced<S>(where, a, c, src, resliced, e);
 }
 
-// S: the image's type; the label map's is a run-time argument of the kernels
+// The collect step of frog_wlabels_add and frog_jlabels_add for an image of type S (the label map's type is a run-time
+// argument of the kernels), after the caller has staged the image (g) and its label map (at d_lsrc): the atlas on the grid
+// into `plane`, with a chain its label map on the grid into d_on_grid and, if `want_image`, the image into a->d_out; the
+// labels numbered in the table's map, and a score plane for every new one.
+template <class S>
+int wlabels_collect(const char *where, frog_wlabels *a, frog_chain *c, const ResliceGrid &g, const frog_volume *labels, double label_background,
+                    const void *d_lsrc, bool want_image, float *plane, void *d_on_grid)
+{
+    const ResliceGrid lg = reslice_grid(labels, &a->grid, 0, label_background);
+    const int ltype = labels->dtype;
+    const S *d_src = (const S *)a->d_src.p;
+    S *d_out = want_image ? (S *)a->d_out.p : nullptr;
+    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
+        if (c)
+            wlabels_collect_kernel<S, true, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, d_lsrc, ltype, lg,
+                                                                            a->total, plane, d_out, d_on_grid, a->map);
+        else
+            wlabels_collect_kernel<S, false, true><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, d_lsrc, ltype, lg, a->total, plane,
+                                                                             nullptr, nullptr, a->map);
+    });
+    size_t n_now;
+    if (int rc = labels_collected(where, a, e, &n_now)) return rc;
+    e = labels_grow_planes<float>(a, a->total, n_now, a->planes, a->d_planes.p);
+    if (e != hipSuccess) return labels_refuse(a, hip_fail(where, e));
+    return FROG_OK;
+}
+
 template <class S>
 int wlabels_add_typed(frog_wlabels *a, frog_chain *c, const frog_volume *image, const frog_volume *labels, int interpolation,
                       double image_background, double label_background, frog_volume *resliced_image, frog_volume *resliced_labels)
@@ -1702,34 +1846,17 @@ int wlabels_add_typed(frog_wlabels *a, frog_chain *c, const frog_volume *image, 
     KCHECK(a->d_lsrc.alloc(n_labels_src * label_bytes));
     if (c) KCHECK(a->d_lout.alloc(a->total * label_bytes));
     KCHECK(hipMemcpy(a->d_lsrc.p, labels->data, n_labels_src * label_bytes, hipMemcpyHostToDevice));
-    const ResliceGrid lg = reslice_grid(labels, &a->grid, 0, label_background);
-    const int ltype = labels->dtype;
-    const S *d_src = (const S *)a->d_src.p;
-    S *d_out = resliced_image ? (S *)a->d_out.p : nullptr;
+    if (int rc = wlabels_collect<S>("frog_wlabels_add", a, c, g, labels, label_background, a->d_lsrc.p, resliced_image != nullptr, a->d_atlas.p,
+                                    a->d_lout.p))
+        return rc;
     const void *d_labels = c ? a->d_lout.p : a->d_lsrc.p;      // with a chain the votes are read from the resliced labels
-    uint32_t state[2] = { 0, 0 };
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        if (c)
-            wlabels_collect_kernel<S, true, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->d_lsrc.p, ltype, lg,
-                                                                            a->total, a->d_atlas.p, d_out, a->d_lout.p, a->map);
-        else
-            wlabels_collect_kernel<S, false, true><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, a->d_lsrc.p, ltype, lg, a->total,
-                                                                             a->d_atlas.p, nullptr, nullptr, a->map);
-    });
-    if (e == hipSuccess) e = hipMemcpy(state, a->d_state.p, sizeof state, hipMemcpyDeviceToHost);
-    // as in labels_add_typed: from here on the map may hold values without a plane, and every failure takes them back
-    auto refuse = [&](int rc) { (void)labels_reset_map(a); return rc; };
-    if (e != hipSuccess) return refuse(hip_fail("frog_wlabels_add", e));
-    if (state[1] || state[0] > a->max_labels)
-        return refuse(fail(FROG_E_INVALID, "frog_wlabels_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
-    const size_t n_now = state[0];
-    e = labels_grow_planes<float>(a->total, n_now, a->d_values.p, a->known, a->planes, a->d_planes.p);
-    if (e != hipSuccess) return refuse(hip_fail("frog_wlabels_add", e));
+    const int ltype = labels->dtype;
+    const uint32_t n_now = (uint32_t)a->known.size();
     const WlabelsTiles w = wlabels_tiles(a);
     // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
-    e = chunked_launch(w.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
+    hipError_t e = chunked_launch(w.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
 #define WLABELS_VOTE(R) wlabels_vote_kernel<R><<<blocks, LAUNCH_BLOCK>>>(base, a->d_target.p, a->d_atlas.p, d_labels, ltype, w, a->power, a->floor, \
-                                                                        a->map, a->d_planes.p, (uint32_t)n_now)
+                                                                        a->map, a->d_planes.p, n_now)
         switch (a->radius) {
         case 1: WLABELS_VOTE(1); break;
         case 2: WLABELS_VOTE(2); break;
@@ -1738,14 +1865,11 @@ int wlabels_add_typed(frog_wlabels *a, frog_chain *c, const frog_volume *image, 
         }
 #undef WLABELS_VOTE
     });
-    if (e == hipSuccess && resliced_labels) {
-        if (c) e = hipMemcpy(resliced_labels->data, a->d_lout.p, a->total * label_bytes, hipMemcpyDeviceToHost);
-        else std::memcpy(resliced_labels->data, labels->data, a->total * label_bytes);
-    }
+    e = copy_resliced(c, labels, resliced_labels, a->d_lout.p, a->total * label_bytes, e);
     return return_resliced<S>("frog_wlabels_add", a, c, image, resliced_image, e);
 }
 
-// An add of frog_jlabels: phase 1 of wlabels_add_typed into the atlas' own plane and label map, which stay for finish.
+// An add of frog_jlabels: the collect step into the atlas' own plane and label map, which stay for finish.
 template <class S>
 int jlabels_add_typed(frog_jlabels *a, frog_chain *c, const frog_volume *image, const frog_volume *labels, int interpolation,
                       double image_background, double label_background, frog_volume *resliced_image, frog_volume *resliced_labels)
@@ -1758,37 +1882,15 @@ int jlabels_add_typed(frog_jlabels *a, frog_chain *c, const frog_volume *image, 
     if (c) KCHECK(a->d_lsrc.alloc(n_labels_src * label_bytes));
     unsigned char *const d_lsrc = c ? a->d_lsrc.p : on_grid.p;             // without a chain the map is on the grid as it is
     KCHECK(hipMemcpy(d_lsrc, labels->data, n_labels_src * label_bytes, hipMemcpyHostToDevice));
-    const ResliceGrid lg = reslice_grid(labels, &a->grid, 0, label_background);
-    const int ltype = labels->dtype;
-    const S *d_src = (const S *)a->d_src.p;
-    S *d_out = resliced_image ? (S *)a->d_out.p : nullptr;
     float *const plane = a->d_atlases.p + (size_t)a->added * a->total;
-    uint32_t state[2] = { 0, 0 };
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        if (c)
-            wlabels_collect_kernel<S, true, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, d_lsrc, ltype, lg,
-                                                                            a->total, plane, d_out, on_grid.p, a->map);
-        else
-            wlabels_collect_kernel<S, false, true><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, d_lsrc, ltype, lg, a->total, plane,
-                                                                             nullptr, nullptr, a->map);
-    });
-    if (e == hipSuccess) e = hipMemcpy(state, a->d_state.p, sizeof state, hipMemcpyDeviceToHost);
-    // as in labels_add_typed: from here on the map may hold values without a plane, and every failure takes them back
-    auto refuse = [&](int rc) { (void)labels_reset_map(a); return rc; };
-    if (e != hipSuccess) return refuse(hip_fail("frog_jlabels_add", e));
-    if (state[1] || state[0] > a->max_labels)
-        return refuse(fail(FROG_E_INVALID, "frog_jlabels_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
-    e = labels_grow_planes<float>(a->total, state[0], a->d_values.p, a->known, a->planes, a->d_planes.p);
-    if (e != hipSuccess) return refuse(hip_fail("frog_jlabels_add", e));
-    if (resliced_labels) {
-        if (c) e = hipMemcpy(resliced_labels->data, on_grid.p, a->total * label_bytes, hipMemcpyDeviceToHost);
-        else std::memcpy(resliced_labels->data, labels->data, a->total * label_bytes);
-    }
+    if (int rc = wlabels_collect<S>("frog_jlabels_add", a, c, g, labels, label_background, d_lsrc, resliced_image != nullptr, plane, on_grid.p))
+        return rc;
+    const hipError_t e = copy_resliced(c, labels, resliced_labels, on_grid.p, a->total * label_bytes, hipSuccess);
     const int rc = return_resliced<S>("frog_jlabels_add", a, c, image, resliced_image, e);
     if (rc != FROG_OK) return rc;
     a->label_maps.emplace_back();
     a->label_maps.back().swap(on_grid);
-    a->ltypes.push_back(ltype);
+    a->ltypes.push_back(labels->dtype);
     return FROG_OK;
 }
 
@@ -1831,25 +1933,6 @@ int jlabels_solve(frog_jlabels *a)
     return FROG_OK;
 }
 
-template <class T>
-int wlabels_fused_typed(frog_wlabels *a, long long fill, frog_volume *label, float *confidence)
-{
-    if (label && (!labels_fit<T>(a) || fill < (long long)std::numeric_limits<T>::lowest() || fill > (long long)std::numeric_limits<T>::max()))
-        return fail(FROG_E_INVALID, "frog_wlabels_fused: a label value or the fill label does not fit the requested type");
-    frog::DevBuf<T> d_label;
-    frog::DevBuf<float> d_confidence;
-    if (label) KCHECK(d_label.alloc(a->total));
-    if (confidence) KCHECK(d_confidence.alloc(a->total));
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        wlabels_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
-                                                          (T)fill, d_label.p, d_confidence.p);
-    });
-    if (e == hipSuccess && label) e = hipMemcpy(label->data, d_label.p, a->total * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && confidence) e = hipMemcpy(confidence, d_confidence.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("frog_wlabels_fused", e);
-    return FROG_OK;
-}
-
 // The opening of every accumulator's create: what it refuses without asking for a device, and the grid's voxels.  The
 // accumulator's own argument checks follow, then group_new.
 int group_arguments(const char *where, const frog_volume *grid, const void *out, size_t *total)
@@ -1884,24 +1967,59 @@ void group_destroy(A *a)
     delete a;
 }
 
-// frog_rank_add for a source of type S: cover_add_typed with the key store, over the window
-template <class S>
-int rank_add_typed(frog_rank *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
+// ---- the windowed plane store (frog_windowed) of frog_rank and frog_glm ------------------------------------------------------
+
+// A new accumulator A with the window of n_planes z-planes from first_plane on, after the create's own argument checks.
+template <class A>
+int windowed_new(const char *where, const frog_volume *grid, size_t total, uint32_t first_plane, uint32_t n_planes, uint32_t n_images, int device,
+                 std::unique_ptr<A> &a)
+{
+    if (!n_planes || first_plane >= grid->dims[2] || n_planes > grid->dims[2] - first_plane)
+        return fail(FROG_E_INVALID, std::string(where) + ": the window lies outside the grid or is empty");
+    if (int rc = group_new(grid, total, device, a)) return rc;
+    const size_t plane = (size_t)grid->dims[0] * grid->dims[1];
+    a->n_images = n_images;
+    a->first = plane * first_plane;
+    a->window = plane * n_planes;
+    return FROG_OK;
+}
+
+// An add for a source of type S: cover_add_typed with the store of Entry (RankEntry: a key, GlmEntry: an f32) in place of the
+// update, over the window, into the image's plane.
+template <class S, class Entry>
+int windowed_add_typed(const char *where, frog_windowed *a, typename Entry::type *plane, frog_chain *c, const frog_volume *src,
+                       const frog_volume *mask, int interpolation, double background)
 {
     ResliceGrid g;
     const uint8_t *d_mask;
-    if (int rc = stage_source<S>("frog_rank_add", a, src, false, interpolation, background, &g)) return rc;
-    if (int rc = cover_stage_mask("frog_rank_add", a, mask, &d_mask)) return rc;
+    if (int rc = stage_source<S>(where, a, src, false, interpolation, background, &g)) return rc;
+    if (int rc = cover_stage_mask(where, a, mask, &d_mask)) return rc;
     const MaskGrid mg = mask_grid(mask);
     const S *d_src = (const S *)a->d_src.p;
-    uint32_t *plane = a->d_keys.p + (size_t)a->added * a->window;
     const hipError_t e = chunked_launch(a->window, [&](unsigned blocks, size_t base) {
         if (c)
-            rank_reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg, plane);
+            window_reslice_kernel<S, Entry><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg, plane);
         else
-            rank_identity_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, d_src, d_mask, plane);
+            window_identity_kernel<S, Entry><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, d_src, d_mask, plane);
     });
-    return return_resliced<S>("frog_rank_add", a, c, src, nullptr, e);
+    return return_resliced<S>(where, a, c, src, nullptr, e);
+}
+
+// frog_rank_add and frog_glm_add: `planes` is the accumulator's store, n_images planes of the window (null with a null a)
+template <class Entry>
+int windowed_add(const char *where, frog_windowed *a, typename Entry::type *planes, frog_chain *c, const frog_volume *src, const frog_volume *mask,
+                 int interpolation, double background)
+{
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (a->added >= a->n_images) return fail(FROG_E_INVALID, std::string(where) + ": more volumes than the accumulator was created for");
+    if (int rc = cover_inputs(where, a, c, src, mask, nullptr)) return rc;
+    if (mask) cover_mask(a, mask);
+    KCHECK(hipSetDevice(a->device));
+    const int rc = with_voxel_type(src->dtype, [&](auto s) {
+        return windowed_add_typed<decltype(s), Entry>(where, a, planes + (size_t)a->added * a->window, c, src, mask, interpolation, background);
+    });
+    if (rc == FROG_OK) a->added++;
+    return rc;
 }
 
 // The finish kernels over the window: the register tier for up to RANK_REG_MAX planes, one work-item per voxel; above it the
@@ -1935,26 +2053,6 @@ int rank_arguments(const char *where, const frog_volume *grid, uint32_t n_images
     if (!n_images || n_images > FROG_RANK_MAX_IMAGES)
         return fail(FROG_E_INVALID, std::string(where) + ": 1 to " + std::to_string(FROG_RANK_MAX_IMAGES) + " images");
     return FROG_OK;
-}
-
-// frog_glm_add for a source of type S: rank_add_typed with the float store
-template <class S>
-int glm_add_typed(frog_glm *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
-{
-    ResliceGrid g;
-    const uint8_t *d_mask;
-    if (int rc = stage_source<S>("frog_glm_add", a, src, false, interpolation, background, &g)) return rc;
-    if (int rc = cover_stage_mask("frog_glm_add", a, mask, &d_mask)) return rc;
-    const MaskGrid mg = mask_grid(mask);
-    const S *d_src = (const S *)a->d_src.p;
-    float *plane = a->d_vals.p + (size_t)a->added * a->window;
-    const hipError_t e = chunked_launch(a->window, [&](unsigned blocks, size_t base) {
-        if (c)
-            glm_reslice_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg, plane);
-        else
-            glm_identity_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, d_src, d_mask, plane);
-    });
-    return return_resliced<S>("frog_glm_add", a, c, src, nullptr, e);
 }
 
 // what frog_glm_finish and frog_glm_permute refuse alike, before the device is touched
@@ -2035,58 +2133,24 @@ int glm_fit_args(const char *where, frog_glm *a, uint32_t n_contrasts, const dou
 }
 
 // frog_staple_add for a source of type S: labels_add_typed with the index plane in place of the vote.  The plane of the
-// image is written only after the volume's labels are accepted, so a refused volume leaves nothing behind.
+// image is written, and its labels become known, only after the volume's labels are accepted and its plane is complete, so a
+// refused volume leaves nothing behind.
 template <class S>
 int staple_add_typed(frog_staple *a, frog_chain *c, const frog_volume *src, double background, frog_volume *resliced)
 {
-    ResliceGrid g;
-    if (int rc = stage_source<S>("frog_staple_add", a, src, c != nullptr, 0, background, &g)) return rc;
-    const S *d_src = (const S *)a->d_src.p;
-    S *d_out = (S *)a->d_out.p;
-    const S *d_labels = c ? d_out : d_src;
-    uint32_t state[2] = { 0, 0 };
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        if (c)
-            labels_collect_kernel<S, true><<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_src, g, a->total, d_out, a->map);
-        else
-            labels_collect_kernel<S, false><<<blocks, LAUNCH_BLOCK>>>(base, nullptr, 0, d_src, g, a->total, nullptr, a->map);
-    });
-    if (e == hipSuccess) e = hipMemcpy(state, a->d_state.p, sizeof state, hipMemcpyDeviceToHost);
-    auto refuse = [&](int rc) { (void)labels_reset_map(a); return rc; };
-    if (e != hipSuccess) return refuse(hip_fail("frog_staple_add", e));
-    if (state[1] || state[0] > a->max_labels)
-        return refuse(fail(FROG_E_INVALID, "frog_staple_add: more than max_labels = " + std::to_string(a->max_labels) + " distinct labels"));
-    const size_t n_known = a->known.size(), n_now = state[0];
-    std::vector<long long> fresh(n_now - n_known);
-    if (!fresh.empty()) {
-        e = hipMemcpy(fresh.data(), a->d_values.p + n_known, fresh.size() * sizeof(long long), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return refuse(hip_fail("frog_staple_add", e));
-    }
+    const S *d_labels;
+    size_t n_now;
+    if (int rc = labels_collect<S>("frog_staple_add", a, a, c, src, background, &d_labels, &n_now)) return rc;
+    std::vector<long long> fresh;
+    hipError_t e = labels_fresh_values(a, n_now, fresh);
+    if (e != hipSuccess) return labels_refuse(a, hip_fail("frog_staple_add", e));
     uint8_t *plane = a->d_D.p + (size_t)a->added * a->total;
     e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
         staple_index_kernel<S><<<blocks, LAUNCH_BLOCK>>>(base, d_labels, a->total, a->map, plane);
     });
     const int rc = return_resliced<S>("frog_staple_add", a, c, src, resliced, e);
-    if (rc != FROG_OK) return refuse(rc);
+    if (rc != FROG_OK) return labels_refuse(a, rc);
     a->known.insert(a->known.end(), fresh.begin(), fresh.end());
-    return FROG_OK;
-}
-
-template <class T>
-int staple_fused_typed(frog_staple *a, frog_volume *label, float *confidence)
-{
-    if (label && !labels_fit<T>(a)) return fail(FROG_E_INVALID, "frog_staple_fused: a label value does not fit the requested type");
-    frog::DevBuf<T> d_label;
-    frog::DevBuf<float> d_confidence;
-    if (label) KCHECK(d_label.alloc(a->total));
-    if (confidence) KCHECK(d_confidence.alloc(a->total));
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        staple_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_q.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
-                                                         d_label.p, d_confidence.p);
-    });
-    if (e == hipSuccess && label) e = hipMemcpy(label->data, d_label.p, a->total * sizeof(T), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && confidence) e = hipMemcpy(confidence, d_confidence.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("frog_staple_fused", e);
     return FROG_OK;
 }
 
@@ -2662,14 +2726,8 @@ int frog_rank_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_p
 {
     size_t total;
     if (int rc = rank_arguments("frog_rank_create", grid, n_images, out, &total)) return rc;
-    if (!n_planes || first_plane >= grid->dims[2] || n_planes > grid->dims[2] - first_plane)
-        return fail(FROG_E_INVALID, "frog_rank_create: the window lies outside the grid or is empty");
     std::unique_ptr<frog_rank> a;
-    if (int rc = group_new(grid, total, device, a)) return rc;
-    const size_t plane = (size_t)grid->dims[0] * grid->dims[1];
-    a->n_images = n_images;
-    a->first = plane * first_plane;
-    a->window = plane * n_planes;
+    if (int rc = windowed_new("frog_rank_create", grid, total, first_plane, n_planes, n_images, device, a)) return rc;
     KCHECK(a->d_keys.alloc((size_t)n_images * a->window));
     *out = a.release();
     return FROG_OK;
@@ -2677,14 +2735,7 @@ int frog_rank_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_p
 
 int frog_rank_add(frog_rank *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
 {
-    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_rank_add");
-    if (a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_rank_add: more volumes than the accumulator was created for");
-    if (int rc = cover_inputs("frog_rank_add", a, c, src, mask, nullptr)) return rc;
-    if (mask) cover_mask(a, mask);
-    KCHECK(hipSetDevice(a->device));
-    const int rc = with_voxel_type(src->dtype, [&](auto s) { return rank_add_typed<decltype(s)>(a, c, src, mask, interpolation, background); });
-    if (rc == FROG_OK) a->added++;
-    return rc;
+    return windowed_add<RankEntry>("frog_rank_add", a, a ? a->d_keys.p : nullptr, c, src, mask, interpolation, background);
 }
 
 int frog_rank_finish(frog_rank *a, uint32_t min_count, float fill, uint32_t n_q, const double *q, float *quantiles, float *mad, uint16_t *count)
@@ -2740,15 +2791,9 @@ int frog_glm_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_pl
     if (n_images <= n_columns) return fail(FROG_E_INVALID, "frog_glm_create: more images than columns are needed");
     for (size_t e = 0; e < (size_t)n_images * n_columns; e++)
         if (!std::isfinite(design[e])) return fail(FROG_E_INVALID, "frog_glm_create: a design entry is not finite");
-    if (!n_planes || first_plane >= grid->dims[2] || n_planes > grid->dims[2] - first_plane)
-        return fail(FROG_E_INVALID, "frog_glm_create: the window lies outside the grid or is empty");
     std::unique_ptr<frog_glm> a;
-    if (int rc = group_new(grid, total, device, a)) return rc;
-    const size_t plane = (size_t)grid->dims[0] * grid->dims[1];
-    a->n_images = n_images;
+    if (int rc = windowed_new("frog_glm_create", grid, total, first_plane, n_planes, n_images, device, a)) return rc;
     a->p = n_columns;
-    a->first = plane * first_plane;
-    a->window = plane * n_planes;
     a->design.assign(design, design + (size_t)n_images * n_columns);
     KCHECK(a->d_vals.alloc((size_t)n_images * a->window));
     KCHECK(a->d_design.alloc(a->design.size()));
@@ -2759,14 +2804,7 @@ int frog_glm_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_pl
 
 int frog_glm_add(frog_glm *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
 {
-    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_glm_add");
-    if (a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_glm_add: more volumes than the accumulator was created for");
-    if (int rc = cover_inputs("frog_glm_add", a, c, src, mask, nullptr)) return rc;
-    if (mask) cover_mask(a, mask);
-    KCHECK(hipSetDevice(a->device));
-    const int rc = with_voxel_type(src->dtype, [&](auto s) { return glm_add_typed<decltype(s)>(a, c, src, mask, interpolation, background); });
-    if (rc == FROG_OK) a->added++;
-    return rc;
+    return windowed_add<GlmEntry>("frog_glm_add", a, a ? a->d_vals.p : nullptr, c, src, mask, interpolation, background);
 }
 
 int frog_glm_add_jacobian(frog_glm *a, frog_chain *c, const frog_volume *support, const frog_volume *mask, int log_mode)
@@ -2921,8 +2959,7 @@ int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_
     std::unique_ptr<frog_labels> a;
     if (int rc = group_new(grid, total, device, a)) return rc;
     a->n_images = n_images;
-    a->max_labels = max_labels ? max_labels : 1024;
-    if (int rc = labels_new_map(a.get())) return rc;
+    if (int rc = labels_new_map(a.get(), max_labels ? max_labels : 1024)) return rc;
     KCHECK(a->d_planes.alloc(a->max_labels));
     *out = a.release();
     return FROG_OK;
@@ -2958,22 +2995,16 @@ int frog_labels_finish(frog_labels *a, uint32_t *n_labels)
     });
     if (e == hipSuccess) e = hipMemcpy(sums.data(), d_sums.p, sums.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail("frog_labels_finish", e);
-    std::vector<uint32_t> order;
+    std::vector<uint32_t> order;                    // the labels without a vote do not enter the table
     for (size_t i = 0; i < n_planes; i++) if (sums[LABEL_SUM_STRIDE * i]) order.push_back((uint32_t)i);
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return a->known[x] < a->known[y]; });
-    std::vector<uint16_t *> sorted_planes;
-    a->values.clear(); a->voxels.clear(); a->pairs.clear();
+    if (int rc = labels_sort(a, order)) return rc;
+    if (int rc = labels_sort_planes(order, a->planes, a->d_sorted_planes)) return rc;
+    a->voxels.clear(); a->pairs.clear();
     for (const uint32_t i : order) {
-        a->values.push_back(a->known[i]);
         a->voxels.push_back(sums[LABEL_SUM_STRIDE * i]);
         a->pairs.push_back(sums[LABEL_SUM_STRIDE * i + 1]);
-        sorted_planes.push_back(a->planes[i].p);
     }
     a->dense = order;
-    KCHECK(a->d_sorted_planes.alloc(order.size()));
-    KCHECK(a->d_sorted_values.alloc(order.size()));
-    KCHECK(hipMemcpy(a->d_sorted_planes.p, sorted_planes.data(), order.size() * sizeof(uint16_t *), hipMemcpyHostToDevice));
-    KCHECK(hipMemcpy(a->d_sorted_values.p, a->values.data(), order.size() * sizeof(long long), hipMemcpyHostToDevice));
     a->finished = true;
     *n_labels = (uint32_t)order.size();
     return FROG_OK;
@@ -2989,32 +3020,26 @@ int frog_labels_table(frog_labels *a, int64_t *values, uint64_t *voxels, uint64_
 
 int frog_labels_fused(frog_labels *a, frog_volume *label, float *agreement)
 {
-    if (!a || (!label && !agreement) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_labels_fused");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_labels_fused: before frog_labels_finish");
-    if (label) {
-        if (!integer_voxel_type(label->dtype)) return fail(FROG_E_INVALID, "frog_labels_fused: the fused map has an integer type");
-        if (!grid_sized(a, label)) return fail(FROG_E_INVALID, "frog_labels_fused: the fused map is not grid-sized");
-    }
-    KCHECK(hipSetDevice(a->device));
-    return with_integer_voxel_type(label ? label->dtype : FROG_V_I32, [&](auto t) { return labels_fused_typed<decltype(t)>(a, label, agreement); });
+    if (int rc = fused_arguments("frog_labels_fused", a, a && a->finished, "frog_labels_finish", label, agreement)) return rc;
+    return with_integer_voxel_type(label ? label->dtype : FROG_V_I32, [&](auto t) {
+        using T = decltype(t);
+        if (label && !labels_fit<T>(a)) return fail(FROG_E_INVALID, "frog_labels_fused: a label value does not fit the requested type");
+        return fused_output<T>("frog_labels_fused", a, label, agreement, [&](unsigned blocks, size_t base, T *d_label, float *d_agreement) {
+            labels_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
+                                                             (float)a->n_images, d_label, d_agreement);
+        });
+    });
 }
 
 int frog_labels_probability(frog_labels *a, int64_t value, float *p)
 {
-    if (!a || !p) return fail(FROG_E_INVALID, "bad arguments to frog_labels_probability");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_labels_probability: before frog_labels_finish");
-    const auto it = std::lower_bound(a->values.begin(), a->values.end(), (long long)value);
-    if (it == a->values.end() || *it != (long long)value) return fail(FROG_E_INVALID, "frog_labels_probability: no such label in the table");
-    KCHECK(hipSetDevice(a->device));
-    const uint16_t *plane = a->planes[a->dense[it - a->values.begin()]].p;
-    frog::DevBuf<float> d_p;
-    KCHECK(d_p.alloc(a->total));
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        labels_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, plane, a->total, (float)a->n_images, d_p.p);
+    size_t l;
+    if (int rc = labels_getter("frog_labels_probability", a && p, a && a->finished, "frog_labels_finish")) return rc;
+    if (int rc = labels_find("frog_labels_probability", "no such label in the table", a, value, &l)) return rc;
+    const uint16_t *plane = a->planes[a->dense[l]].p;
+    return probability_output("frog_labels_probability", a, p, [&](unsigned blocks, size_t base, float *d_p) {
+        labels_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, plane, a->total, (float)a->n_images, d_p);
     });
-    if (e == hipSuccess) e = hipMemcpy(p, d_p.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("frog_labels_probability", e);
-    return FROG_OK;
 }
 
 void frog_labels_destroy(frog_labels *a) { group_destroy(a); }
@@ -3028,9 +3053,8 @@ int frog_staple_create(const frog_volume *grid, uint32_t n_images, uint32_t max_
     std::unique_ptr<frog_staple> a;
     if (int rc = group_new(grid, total, device, a)) return rc;
     a->n_images = n_images;
-    a->max_labels = max_labels ? max_labels : FROG_STAPLE_MAX_LABELS;
     KCHECK(a->d_D.alloc((size_t)n_images * total));
-    if (int rc = labels_new_map(a.get())) return rc;
+    if (int rc = labels_new_map(a.get(), max_labels ? max_labels : FROG_STAPLE_MAX_LABELS)) return rc;
     *out = a.release();
     return FROG_OK;
 }
@@ -3055,13 +3079,10 @@ int frog_staple_finish(frog_staple *a, uint32_t *n_labels)
     if (a->finished) { *n_labels = (uint32_t)a->values.size(); return FROG_OK; }
     KCHECK(hipSetDevice(a->device));
     const size_t L = a->known.size(), entries = (size_t)a->n_images * L * L;
-    std::vector<uint32_t> order(L);
-    for (size_t i = 0; i < L; i++) order[i] = (uint32_t)i;
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return a->known[x] < a->known[y]; });
+    std::vector<uint32_t> order = labels_all(a);
+    if (int rc = labels_sort(a, order)) return rc;
     StapleLut lut{};
-    std::vector<long long> values(L);
-    for (size_t l = 0; l < L; l++) { lut.to[order[l]] = (uint8_t)l; values[l] = a->known[order[l]]; }
-    KCHECK(a->d_sorted_values.alloc(L));
+    for (size_t l = 0; l < L; l++) lut.to[order[l]] = (uint8_t)l;
     KCHECK(a->d_active.alloc(a->total));
     KCHECK(a->d_q.alloc(L * a->total));
     KCHECK(a->d_theta.alloc(entries));
@@ -3069,25 +3090,17 @@ int frog_staple_finish(frog_staple *a, uint32_t *n_labels)
     KCHECK(a->d_T.alloc(L));
     KCHECK(a->d_prior.alloc(L));
     KCHECK(a->d_word.alloc(L + 1));
-    KCHECK(hipMemcpy(a->d_sorted_values.p, values.data(), L * sizeof(long long), hipMemcpyHostToDevice));
     const size_t count = (size_t)a->n_images * a->total;
     KCHECK(chunked_launch(count, [&](unsigned blocks, size_t base) {
         staple_renumber_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_D.p, count, lut);
     }));
     KCHECK(hipStreamSynchronize(0));
-    a->values = values;
     a->finished = true;
     *n_labels = (uint32_t)L;
     return FROG_OK;
 }
 
-int frog_staple_values(frog_staple *a, int64_t *values)
-{
-    if (!a || !values) return fail(FROG_E_INVALID, "bad arguments to frog_staple_values");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_staple_values: before frog_staple_finish");
-    for (size_t l = 0; l < a->values.size(); l++) values[l] = a->values[l];
-    return FROG_OK;
-}
+int frog_staple_values(frog_staple *a, int64_t *values) { return labels_values("frog_staple_values", a, "frog_staple_finish", values); }
 
 int frog_staple_solve(frog_staple *a, double p0, double tol, uint32_t max_iter, int restrict_to_disputed,
                       uint32_t *iterations, double *change, uint64_t *active_voxels)
@@ -3146,32 +3159,26 @@ int frog_staple_solve(frog_staple *a, double p0, double tol, uint32_t max_iter, 
 
 int frog_staple_fused(frog_staple *a, frog_volume *label, float *confidence)
 {
-    if (!a || (!label && !confidence) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_staple_fused");
-    if (!a->solved) return fail(FROG_E_INVALID, "frog_staple_fused: before frog_staple_solve");
-    if (label) {
-        if (!integer_voxel_type(label->dtype)) return fail(FROG_E_INVALID, "frog_staple_fused: the fused map has an integer type");
-        if (!grid_sized(a, label)) return fail(FROG_E_INVALID, "frog_staple_fused: the fused map is not grid-sized");
-    }
-    KCHECK(hipSetDevice(a->device));
-    return with_integer_voxel_type(label ? label->dtype : FROG_V_I32, [&](auto t) { return staple_fused_typed<decltype(t)>(a, label, confidence); });
+    if (int rc = fused_arguments("frog_staple_fused", a, a && a->solved, "frog_staple_solve", label, confidence)) return rc;
+    return with_integer_voxel_type(label ? label->dtype : FROG_V_I32, [&](auto t) {
+        using T = decltype(t);
+        if (label && !labels_fit<T>(a)) return fail(FROG_E_INVALID, "frog_staple_fused: a label value does not fit the requested type");
+        return fused_output<T>("frog_staple_fused", a, label, confidence, [&](unsigned blocks, size_t base, T *d_label, float *d_confidence) {
+            staple_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_q.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
+                                                             d_label, d_confidence);
+        });
+    });
 }
 
 int frog_staple_probability(frog_staple *a, int64_t value, float *p)
 {
-    if (!a || !p) return fail(FROG_E_INVALID, "bad arguments to frog_staple_probability");
-    if (!a->solved) return fail(FROG_E_INVALID, "frog_staple_probability: before frog_staple_solve");
-    const auto it = std::lower_bound(a->values.begin(), a->values.end(), (long long)value);
-    if (it == a->values.end() || *it != (long long)value) return fail(FROG_E_INVALID, "frog_staple_probability: no such label");
-    KCHECK(hipSetDevice(a->device));
-    const uint32_t *plane = a->d_q.p + (size_t)(it - a->values.begin()) * a->total;
-    frog::DevBuf<float> d_p;
-    KCHECK(d_p.alloc(a->total));
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        staple_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, plane, a->total, d_p.p);
+    size_t l;
+    if (int rc = labels_getter("frog_staple_probability", a && p, a && a->solved, "frog_staple_solve")) return rc;
+    if (int rc = labels_find("frog_staple_probability", "no such label", a, value, &l)) return rc;
+    const uint32_t *plane = a->d_q.p + l * a->total;
+    return probability_output("frog_staple_probability", a, p, [&](unsigned blocks, size_t base, float *d_p) {
+        staple_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, plane, a->total, d_p);
     });
-    if (e == hipSuccess) e = hipMemcpy(p, d_p.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("frog_staple_probability", e);
-    return FROG_OK;
 }
 
 int frog_staple_performance(frog_staple *a, double *theta, uint64_t *sums, uint64_t *totals, double *prior)
@@ -3200,27 +3207,33 @@ int frog_wlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max
     std::unique_ptr<frog_wlabels> a;
     if (int rc = group_new(grid, total, device, a)) return rc;
     a->n_images = n_images;
-    a->max_labels = max_labels ? max_labels : 1024;
     a->radius = radius;
     a->power = power;
     a->floor = floor;
     KCHECK(a->d_target.alloc(total));
     KCHECK(a->d_atlas.alloc(total));
-    if (int rc = labels_new_map(a.get())) return rc;
+    if (int rc = labels_new_map(a.get(), max_labels ? max_labels : 1024)) return rc;
     KCHECK(a->d_planes.alloc(a->max_labels));
     *out = a.release();
     return FROG_OK;
 }
 
-int frog_wlabels_target(frog_wlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+// frog_wlabels_target and frog_jlabels_target under their names
+static int wlabels_target(const char *where, frog_wlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background,
+                          frog_volume *resliced)
 {
-    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_target");
-    if (a->has_target) return fail(FROG_E_INVALID, "frog_wlabels_target: the target is given once, before the first add");
-    if (int rc = add_inputs("frog_wlabels_target", a, c, src, resliced)) return rc;
+    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (a->has_target) return fail(FROG_E_INVALID, std::string(where) + ": the target is given once, before the first add");
+    if (int rc = add_inputs(where, a, c, src, resliced)) return rc;
     KCHECK(hipSetDevice(a->device));
-    const int rc = with_voxel_type(src->dtype, [&](auto s) { return wlabels_target_typed<decltype(s)>("frog_wlabels_target", a, c, src, interpolation, background, resliced); });
+    const int rc = with_voxel_type(src->dtype, [&](auto s) { return wlabels_target_typed<decltype(s)>(where, a, c, src, interpolation, background, resliced); });
     if (rc == FROG_OK) a->has_target = true;
     return rc;
+}
+
+int frog_wlabels_target(frog_wlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
+{
+    return wlabels_target("frog_wlabels_target", a, c, src, interpolation, background, resliced);
 }
 
 int frog_wlabels_add(frog_wlabels *a, frog_chain *c, const frog_volume *image, const frog_volume *labels, int interpolation,
@@ -3248,63 +3261,40 @@ int frog_wlabels_finish(frog_wlabels *a, uint32_t *n_labels)
     if (a->added != a->n_images) return fail(FROG_E_INVALID, "frog_wlabels_finish: fewer atlases added than n_images");
     if (a->finished) { *n_labels = (uint32_t)a->values.size(); return FROG_OK; }
     KCHECK(hipSetDevice(a->device));
-    std::vector<uint32_t> order(a->known.size());
-    for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return a->known[x] < a->known[y]; });
-    std::vector<float *> sorted_planes;
-    a->values.clear();
-    for (const uint32_t i : order) {
-        a->values.push_back(a->known[i]);
-        sorted_planes.push_back(a->planes[i].p);
-    }
+    std::vector<uint32_t> order = labels_all(a);
+    if (int rc = labels_sort(a, order)) return rc;
+    if (int rc = labels_sort_planes(order, a->planes, a->d_sorted_planes)) return rc;
     a->dense = order;
-    KCHECK(a->d_sorted_planes.alloc(order.size()));
-    KCHECK(a->d_sorted_values.alloc(order.size()));
-    KCHECK(hipMemcpy(a->d_sorted_planes.p, sorted_planes.data(), order.size() * sizeof(float *), hipMemcpyHostToDevice));
-    KCHECK(hipMemcpy(a->d_sorted_values.p, a->values.data(), order.size() * sizeof(long long), hipMemcpyHostToDevice));
     a->finished = true;
     *n_labels = (uint32_t)order.size();
     return FROG_OK;
 }
 
-int frog_wlabels_values(frog_wlabels *a, int64_t *values)
-{
-    if (!a || !values) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_values");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_wlabels_values: before frog_wlabels_finish");
-    for (size_t l = 0; l < a->values.size(); l++) values[l] = a->values[l];
-    return FROG_OK;
-}
+int frog_wlabels_values(frog_wlabels *a, int64_t *values) { return labels_values("frog_wlabels_values", a, "frog_wlabels_finish", values); }
 
 int frog_wlabels_fused(frog_wlabels *a, int64_t fill_label, frog_volume *label, float *confidence)
 {
-    if (!a || (!label && !confidence) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_fused");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_wlabels_fused: before frog_wlabels_finish");
-    if (label) {
-        if (!integer_voxel_type(label->dtype)) return fail(FROG_E_INVALID, "frog_wlabels_fused: the fused map has an integer type");
-        if (!grid_sized(a, label)) return fail(FROG_E_INVALID, "frog_wlabels_fused: the fused map is not grid-sized");
-    }
-    KCHECK(hipSetDevice(a->device));
+    if (int rc = fused_arguments("frog_wlabels_fused", a, a && a->finished, "frog_wlabels_finish", label, confidence)) return rc;
+    const long long fill = label ? (long long)fill_label : 0;
     return with_integer_voxel_type(label ? label->dtype : FROG_V_I32, [&](auto t) {
-        return wlabels_fused_typed<decltype(t)>(a, label ? (long long)fill_label : 0, label, confidence);
+        using T = decltype(t);
+        if (label && (!labels_fit<T>(a) || fill < (long long)std::numeric_limits<T>::lowest() || fill > (long long)std::numeric_limits<T>::max()))
+            return fail(FROG_E_INVALID, "frog_wlabels_fused: a label value or the fill label does not fit the requested type");
+        return fused_output<T>("frog_wlabels_fused", a, label, confidence, [&](unsigned blocks, size_t base, T *d_label, float *d_confidence) {
+            wlabels_fused_kernel<T><<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, a->d_sorted_values.p, (uint32_t)a->values.size(), a->total,
+                                                              (T)fill, d_label, d_confidence);
+        });
     });
 }
 
 int frog_wlabels_probability(frog_wlabels *a, int64_t value, float *p)
 {
-    if (!a || !p) return fail(FROG_E_INVALID, "bad arguments to frog_wlabels_probability");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_wlabels_probability: before frog_wlabels_finish");
-    const auto it = std::lower_bound(a->values.begin(), a->values.end(), (long long)value);
-    if (it == a->values.end() || *it != (long long)value) return fail(FROG_E_INVALID, "frog_wlabels_probability: no such label in the table");
-    KCHECK(hipSetDevice(a->device));
-    frog::DevBuf<float> d_p;
-    KCHECK(d_p.alloc(a->total));
-    hipError_t e = chunked_launch(a->total, [&](unsigned blocks, size_t base) {
-        wlabels_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, (uint32_t)a->values.size(), (uint32_t)(it - a->values.begin()),
-                                                             a->total, d_p.p);
+    size_t l;
+    if (int rc = labels_getter("frog_wlabels_probability", a && p, a && a->finished, "frog_wlabels_finish")) return rc;
+    if (int rc = labels_find("frog_wlabels_probability", "no such label in the table", a, value, &l)) return rc;
+    return probability_output("frog_wlabels_probability", a, p, [&](unsigned blocks, size_t base, float *d_p) {
+        wlabels_probability_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_sorted_planes.p, (uint32_t)a->values.size(), (uint32_t)l, a->total, d_p);
     });
-    if (e == hipSuccess) e = hipMemcpy(p, d_p.p, a->total * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("frog_wlabels_probability", e);
-    return FROG_OK;
 }
 
 void frog_wlabels_destroy(frog_wlabels *a) { group_destroy(a); }
@@ -3322,14 +3312,13 @@ int frog_jlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max
     std::unique_ptr<frog_jlabels> a;
     if (int rc = group_new(grid, total, device, a)) return rc;
     a->n_images = n_images;
-    a->max_labels = max_labels ? max_labels : 1024;
     a->radius = radius;
     a->beta = beta;
     a->alpha = alpha;
     KCHECK(a->d_target.alloc(total));
     KCHECK(a->d_atlases.alloc((size_t)n_images * total));
     if (keep_weights) KCHECK(a->d_weights.alloc((size_t)n_images * total));
-    if (int rc = labels_new_map(a.get())) return rc;
+    if (int rc = labels_new_map(a.get(), max_labels ? max_labels : 1024)) return rc;
     KCHECK(a->d_planes.alloc(a->max_labels));
     *out = a.release();
     return FROG_OK;
@@ -3337,15 +3326,7 @@ int frog_jlabels_create(const frog_volume *grid, uint32_t n_images, uint32_t max
 
 int frog_jlabels_target(frog_jlabels *a, frog_chain *c, const frog_volume *src, int interpolation, double background, frog_volume *resliced)
 {
-    if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_target");
-    if (a->has_target) return fail(FROG_E_INVALID, "frog_jlabels_target: the target is given once, before the first add");
-    if (int rc = add_inputs("frog_jlabels_target", a, c, src, resliced)) return rc;
-    KCHECK(hipSetDevice(a->device));
-    const int rc = with_voxel_type(src->dtype, [&](auto s) {
-        return wlabels_target_typed<decltype(s)>("frog_jlabels_target", a, c, src, interpolation, background, resliced);
-    });
-    if (rc == FROG_OK) a->has_target = true;
-    return rc;
+    return wlabels_target("frog_jlabels_target", a, c, src, interpolation, background, resliced);
 }
 
 int frog_jlabels_add(frog_jlabels *a, frog_chain *c, const frog_volume *image, const frog_volume *labels, int interpolation,
@@ -3378,24 +3359,20 @@ int frog_jlabels_finish(frog_jlabels *a, uint32_t *n_labels)
     return frog_wlabels_finish(a, n_labels);        // the table, as for frog_wlabels' scores
 }
 
-int frog_jlabels_values(frog_jlabels *a, int64_t *values)
-{
-    if (!a || !values) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_values");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_jlabels_values: before frog_jlabels_finish");
-    return frog_wlabels_values(a, values);
-}
+int frog_jlabels_values(frog_jlabels *a, int64_t *values) { return labels_values("frog_jlabels_values", a, "frog_jlabels_finish", values); }
 
+// frog_jlabels_fused and frog_jlabels_probability answer for their arguments and for finish under their own names; the rest
+// is frog_wlabels', under its name
 int frog_jlabels_fused(frog_jlabels *a, int64_t fill_label, frog_volume *label, float *confidence)
 {
-    if (!a || (!label && !confidence) || (label && !label->data)) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_fused");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_jlabels_fused: before frog_jlabels_finish");
+    if (int rc = labels_getter("frog_jlabels_fused", a && (label || confidence) && (!label || label->data), a && a->finished, "frog_jlabels_finish"))
+        return rc;
     return frog_wlabels_fused(a, fill_label, label, confidence);
 }
 
 int frog_jlabels_probability(frog_jlabels *a, int64_t value, float *p)
 {
-    if (!a || !p) return fail(FROG_E_INVALID, "bad arguments to frog_jlabels_probability");
-    if (!a->finished) return fail(FROG_E_INVALID, "frog_jlabels_probability: before frog_jlabels_finish");
+    if (int rc = labels_getter("frog_jlabels_probability", a && p, a && a->finished, "frog_jlabels_finish")) return rc;
     return frog_wlabels_probability(a, value, p);
 }
 

@@ -38,33 +38,11 @@ __device__ __forceinline__ float glm_entry(bool valid, float x)
     return valid && x - x == 0.0f ? x : __uint_as_float(GLM_NAN_BITS);
 }
 
-// rank_reslice_kernel with the float store
-template <class S>
-__global__ __launch_bounds__(256) void glm_reslice_kernel(size_t base, size_t first, size_t window, const DevLink *links, int n_links,
-                                                          const S *__restrict__ src, const ResliceGrid g, const uint8_t *__restrict__ mask,
-                                                          const MaskGrid mg, float *__restrict__ plane)
-{
-    const size_t w = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= window) return;
-    const size_t idx = first + w;
-    double p[3], c[3];
-    reslice_position(links, n_links, g.out, idx, p);
-    bool valid = voxel_coordinates(p, g.so, g.ss, g.sx, g.sy, g.sz, c);
-    const S r = reslice_sample<S>(src, g, c, valid);
-    if (valid && mask) valid = mask_covers(p, mask, mg);
-    plane[w] = glm_entry(valid, (float)r);
-}
-
-// rank_identity_kernel with the float store
-template <class S>
-__global__ __launch_bounds__(256) void glm_identity_kernel(size_t base, size_t first, size_t window, const S *__restrict__ src,
-                                                           const uint8_t *__restrict__ mask, float *__restrict__ plane)
-{
-    const size_t w = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= window) return;
-    const size_t idx = first + w;
-    plane[w] = glm_entry(!mask || mask[idx] != 0, (float)src[idx]);
-}
+// window_reslice_kernel and window_identity_kernel (k_rank.hip.h) with the float store
+struct GlmEntry {
+    using type = float;
+    static __device__ __forceinline__ type of(bool valid, float x) { return glm_entry(valid, x); }
+};
 
 // The determinant chain_sample_kernel stores for the node (grid_node, chain_point<true>, det3), and the validity of
 // cover_reslice_kernel at the position the same evaluation of the chain gives: inside `support` (where there is one), then

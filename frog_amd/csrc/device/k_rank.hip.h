@@ -41,12 +41,19 @@ __device__ __forceinline__ uint32_t rank_entry(bool valid, float x)
     return valid && x == x ? rank_key(x) : RANK_SENTINEL;
 }
 
-// cover_reslice_kernel with the key store in place of cover_update: window voxel w is voxel `first + w` of the whole grid,
-// and its position is computed from that index, so a window gives what the whole grid gives there
-template <class S>
-__global__ __launch_bounds__(256) void rank_reslice_kernel(size_t base, size_t first, size_t window, const DevLink *links, int n_links,
-                                                           const S *__restrict__ src, const ResliceGrid g, const uint8_t *__restrict__ mask,
-                                                           const MaskGrid mg, uint32_t *__restrict__ plane)
+// The collect kernels of the accumulators that keep a plane per image over a window (frog_rank and frog_glm, k_glm.hip.h)
+// store Entry::of(valid, x) as an Entry::type: this one the key.
+struct RankEntry {
+    using type = uint32_t;
+    static __device__ __forceinline__ type of(bool valid, float x) { return rank_entry(valid, x); }
+};
+
+// cover_reslice_kernel with the store of Entry in place of cover_update: window voxel w is voxel `first + w` of the whole
+// grid, and its position is computed from that index, so a window gives what the whole grid gives there
+template <class S, class Entry>
+__global__ __launch_bounds__(256) void window_reslice_kernel(size_t base, size_t first, size_t window, const DevLink *links, int n_links,
+                                                             const S *__restrict__ src, const ResliceGrid g, const uint8_t *__restrict__ mask,
+                                                             const MaskGrid mg, typename Entry::type *__restrict__ plane)
 {
     const size_t w = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= window) return;
@@ -56,18 +63,18 @@ __global__ __launch_bounds__(256) void rank_reslice_kernel(size_t base, size_t f
     bool valid = voxel_coordinates(p, g.so, g.ss, g.sx, g.sy, g.sz, c);
     const S r = reslice_sample<S>(src, g, c, valid);
     if (valid && mask) valid = mask_covers(p, mask, mg);
-    plane[w] = rank_entry(valid, (float)r);
+    plane[w] = Entry::of(valid, (float)r);
 }
 
 // a source (and a mask) already on the grid: every voxel is inside
-template <class S>
-__global__ __launch_bounds__(256) void rank_identity_kernel(size_t base, size_t first, size_t window, const S *__restrict__ src,
-                                                            const uint8_t *__restrict__ mask, uint32_t *__restrict__ plane)
+template <class S, class Entry>
+__global__ __launch_bounds__(256) void window_identity_kernel(size_t base, size_t first, size_t window, const S *__restrict__ src,
+                                                              const uint8_t *__restrict__ mask, typename Entry::type *__restrict__ plane)
 {
     const size_t w = base + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= window) return;
     const size_t idx = first + w;
-    plane[w] = rank_entry(!mask || mask[idx] != 0, (float)src[idx]);
+    plane[w] = Entry::of(!mask || mask[idx] != 0, (float)src[idx]);
 }
 
 // the arguments of a finish that both tiers take by value

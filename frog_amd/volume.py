@@ -557,16 +557,62 @@ def fused_dtype(values):
     return None
 
 
-class Labels(_Accumulator):
+class _LabelAccumulator(_Accumulator):
+    """What Labels, Staple, WeightedLabels and JointLabels share: n_images adds, finish() and the outputs over the sorted
+    table of label values, each the library's frog_<_NAME>_<call>."""
+
+    def __init__(self, grid, n_images, *create_args):
+        self.n_images = int(n_images)
+        self._n_labels = None
+        super().__init__(grid, self.n_images, *create_args)
+
+    def _call(self, name):
+        return getattr(self._lib, f"frog_{self._NAME}_{name}")
+
+    def finish(self):
+        """The number of distinct labels, after exactly n_images adds."""
+        n = C.c_uint32()
+        _abi.check(self._call("finish")(self._h, C.byref(n)), f"frog_{self._NAME}_finish")
+        self._n_labels = int(n.value)
+        return self._n_labels
+
+    def values(self):
+        """The distinct label values, int64 ascending."""
+        values = np.empty(self._n_labels or 0, np.int64)
+        _abi.check(self._call("values")(self._h, values.ctypes.data_as(C.POINTER(C.c_int64))), f"frog_{self._NAME}_values")
+        return values
+
+    def fused(self, dtype=None, fill_label=None):
+        """(labels, second): the fused map as `dtype`, default the first of uint8, uint16, int16, int32, uint32 that holds
+        every label (and `fill_label`, which only the accumulators that have one pass on), and its float32 companion."""
+        fill = () if fill_label is None else (int(fill_label),)
+        if dtype is None:
+            dtype = fused_dtype(list(self.values()) + list(fill))
+            if dtype is None:
+                raise ValueError("no integer type of at most 32 bits holds every label value")
+        labels = np.empty(self.dims[::-1], np.dtype(dtype))
+        second = np.empty(self.dims[::-1], np.float32)
+        lv = _abi.volume_view(labels, tuple(self._grid.origin), tuple(self._grid.spacing))
+        _abi.check(self._call("fused")(self._h, *fill, C.byref(lv), second.ctypes.data_as(_abi.c_float_p)), f"frog_{self._NAME}_fused")
+        return labels, second
+
+    def probability(self, value):
+        """float32 per voxel, for label `value`: of Labels the share of the images that carry it; of Staple the probability
+        that the truth is it; of WeightedLabels and JointLabels the share of the voxel's total score that it holds, 0 where
+        no weight arrived."""
+        p = np.empty(self.dims[::-1], np.float32)
+        _abi.check(self._call("probability")(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), f"frog_{self._NAME}_probability")
+        return p
+
+
+class Labels(_LabelAccumulator):
     """frog_labels (include/frog_chain.h): n_images label maps added one by one on `grid` = (dims(x, y, z), origin, spacing),
     then the majority vote, its agreement, per-label probabilities and the table of vote sums."""
 
     _NAME = "labels"
 
     def __init__(self, grid, n_images, max_labels=0, device=0):
-        self.n_images = int(n_images)
-        self._n_labels = None
-        super().__init__(grid, self.n_images, int(max_labels), int(device))
+        super().__init__(grid, n_images, int(max_labels), int(device))
 
     def add(self, volume, chain=None, background=0.0, resliced=False):
         """Adds the integer label map `volume` ((voxels, origin, spacing) or an array already on the grid when chain is
@@ -577,12 +623,9 @@ class Labels(_Accumulator):
                    "frog_labels_add")
         return out
 
-    def finish(self):
-        """The number of distinct labels, after exactly n_images adds."""
-        n = C.c_uint32()
-        _abi.check(self._lib.frog_labels_finish(self._h, C.byref(n)), "frog_labels_finish")
-        self._n_labels = int(n.value)
-        return self._n_labels
+    def values(self):
+        """The distinct label values, int64 ascending: the first column of table()."""
+        return self.table()[0]
 
     def table(self):
         """(values int64 ascending, voxels uint64, pairs uint64): per label the votes summed over the voxels and the image
@@ -597,21 +640,7 @@ class Labels(_Accumulator):
     def fused(self, dtype=None):
         """(labels, agreement): the majority label per voxel (ties: the smallest value) as `dtype`, default the first of
         uint8, uint16, int16, int32, uint32 that holds every label; float32 share of the images that voted for it."""
-        if dtype is None:
-            dtype = fused_dtype(self.table()[0])
-            if dtype is None:
-                raise ValueError("no integer type of at most 32 bits holds every label value")
-        labels = np.empty(self.dims[::-1], np.dtype(dtype))
-        agreement = np.empty(self.dims[::-1], np.float32)
-        lv = _abi.volume_view(labels, tuple(self._grid.origin), tuple(self._grid.spacing))
-        _abi.check(self._lib.frog_labels_fused(self._h, C.byref(lv), agreement.ctypes.data_as(_abi.c_float_p)), "frog_labels_fused")
-        return labels, agreement
-
-    def probability(self, value):
-        """float32 share of the images that carry label `value`, per voxel."""
-        p = np.empty(self.dims[::-1], np.float32)
-        _abi.check(self._lib.frog_labels_probability(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), "frog_labels_probability")
-        return p
+        return super().fused(dtype)
 
 
 def group_dice(voxels, pairs, n_images):
@@ -641,7 +670,7 @@ def fuse_labels(volumes, chains=None, grid=None, background=0.0, max_labels=0, d
         acc.close()
 
 
-class Staple(_Accumulator):
+class Staple(_LabelAccumulator):
     """frog_staple (include/frog_chain.h): n_images label maps added one by one on `grid` = (dims(x, y, z), origin, spacing),
     then multi-label STAPLE: an EM consensus that weights every image's vote by its estimated confusion matrix, and those
     matrices.  At most 256 distinct labels and 4096 images."""
@@ -649,9 +678,7 @@ class Staple(_Accumulator):
     _NAME = "staple"
 
     def __init__(self, grid, n_images, max_labels=0, device=0):
-        self.n_images = int(n_images)
-        self._n_labels = None
-        super().__init__(grid, self.n_images, int(max_labels), int(device))
+        super().__init__(grid, n_images, int(max_labels), int(device))
 
     def add(self, volume, chain=None, background=0.0, resliced=False):
         """As Labels.add: the integer label map `volume`, through `chain` with nearest-neighbour interpolation."""
@@ -659,19 +686,6 @@ class Staple(_Accumulator):
         _abi.check(self._lib.frog_staple_add(self._h, chain._h if chain is not None else None, src, float(background), ov),
                    "frog_staple_add")
         return out
-
-    def finish(self):
-        """The number of distinct labels, after exactly n_images adds."""
-        n = C.c_uint32()
-        _abi.check(self._lib.frog_staple_finish(self._h, C.byref(n)), "frog_staple_finish")
-        self._n_labels = int(n.value)
-        return self._n_labels
-
-    def values(self):
-        """The distinct label values, int64 ascending."""
-        values = np.empty(self._n_labels or 0, np.int64)
-        _abi.check(self._lib.frog_staple_values(self._h, values.ctypes.data_as(C.POINTER(C.c_int64))), "frog_staple_values")
-        return values
 
     def solve(self, p0=0.99, tol=1e-6, max_iter=50, restrict=False):
         """Runs the EM from theta = p0 on the diagonal until the largest change of a theta entry is below `tol` or max_iter
@@ -688,21 +702,7 @@ class Staple(_Accumulator):
     def fused(self, dtype=None):
         """(labels, confidence): per voxel the label with the largest probability (ties: the smallest value) as `dtype`,
         default the first of uint8, uint16, int16, int32, uint32 that holds every label; its float32 probability."""
-        if dtype is None:
-            dtype = fused_dtype(self.values())
-            if dtype is None:
-                raise ValueError("no integer type of at most 32 bits holds every label value")
-        labels = np.empty(self.dims[::-1], np.dtype(dtype))
-        confidence = np.empty(self.dims[::-1], np.float32)
-        lv = _abi.volume_view(labels, tuple(self._grid.origin), tuple(self._grid.spacing))
-        _abi.check(self._lib.frog_staple_fused(self._h, C.byref(lv), confidence.ctypes.data_as(_abi.c_float_p)), "frog_staple_fused")
-        return labels, confidence
-
-    def probability(self, value):
-        """float32 probability that the truth is label `value`, per voxel."""
-        p = np.empty(self.dims[::-1], np.float32)
-        _abi.check(self._lib.frog_staple_probability(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), "frog_staple_probability")
-        return p
+        return super().fused(dtype)
 
     def performance(self):
         """(theta, sums, totals, prior): theta[i, l', l] = P(image i shows values[l'] | the truth is values[l]), float64; the
@@ -744,7 +744,7 @@ def staple_labels(volumes, chains=None, grid=None, background=0.0, p0=0.99, tol=
         acc.close()
 
 
-class WeightedLabels(_Accumulator):
+class WeightedLabels(_LabelAccumulator):
     """frog_wlabels (include/frog_chain.h): locally weighted label fusion.  The target image first, then n_images atlases
     (image + label map through one chain) on `grid` = (dims(x, y, z), origin, spacing); every atlas votes for its label with
     the local normalised cross-correlation between its image and the target over a (2 radius + 1)^3 patch, raised to
@@ -753,12 +753,7 @@ class WeightedLabels(_Accumulator):
     _NAME = "wlabels"
 
     def __init__(self, grid, n_images, max_labels=0, radius=2, power=2, floor=2.0 ** -10, device=0):
-        self.n_images = int(n_images)
-        self._n_labels = None
-        super().__init__(grid, self.n_images, int(max_labels), int(radius), int(power), float(floor), int(device))
-
-    def _call(self, name):
-        return getattr(self._lib, f"frog_{self._NAME}_{name}")
+        super().__init__(grid, n_images, int(max_labels), int(radius), int(power), float(floor), int(device))
 
     def target(self, volume, chain=None, interpolation=1, background=0.0, resliced=False):
         """The image to segment ((voxels, origin, spacing) or an array already on the grid when chain is None), once, before
@@ -779,39 +774,11 @@ class WeightedLabels(_Accumulator):
                                      float(image_background), float(label_background), ov, lv), f"frog_{self._NAME}_add")
         return (out, lout) if resliced else None
 
-    def finish(self):
-        """The number of distinct labels, after exactly n_images adds."""
-        n = C.c_uint32()
-        _abi.check(self._call("finish")(self._h, C.byref(n)), f"frog_{self._NAME}_finish")
-        self._n_labels = int(n.value)
-        return self._n_labels
-
-    def values(self):
-        """The distinct label values, int64 ascending."""
-        values = np.empty(self._n_labels or 0, np.int64)
-        _abi.check(self._call("values")(self._h, values.ctypes.data_as(C.POINTER(C.c_int64))), f"frog_{self._NAME}_values")
-        return values
-
     def fused(self, dtype=None, fill_label=0):
         """(labels, confidence): per voxel the label with the largest score (ties: the smallest value) as `dtype`, default
         the first of uint8, uint16, int16, int32, uint32 that holds every label and `fill_label`; float32 share of the
         voxel's total score that went to it.  Where no weight arrived: `fill_label`, confidence 0."""
-        if dtype is None:
-            dtype = fused_dtype(list(self.values()) + [int(fill_label)])
-            if dtype is None:
-                raise ValueError("no integer type of at most 32 bits holds every label value")
-        labels = np.empty(self.dims[::-1], np.dtype(dtype))
-        confidence = np.empty(self.dims[::-1], np.float32)
-        lv = _abi.volume_view(labels, tuple(self._grid.origin), tuple(self._grid.spacing))
-        _abi.check(self._call("fused")(self._h, int(fill_label), C.byref(lv), confidence.ctypes.data_as(_abi.c_float_p)),
-                   f"frog_{self._NAME}_fused")
-        return labels, confidence
-
-    def probability(self, value):
-        """float32 share of the voxel's total score that label `value` holds; 0 where no weight arrived."""
-        p = np.empty(self.dims[::-1], np.float32)
-        _abi.check(self._call("probability")(self._h, int(value), p.ctypes.data_as(_abi.c_float_p)), f"frog_{self._NAME}_probability")
-        return p
+        return super().fused(dtype, fill_label)
 
 
 class JointLabels(WeightedLabels):
@@ -823,10 +790,8 @@ class JointLabels(WeightedLabels):
     _NAME = "jlabels"
 
     def __init__(self, grid, n_images, max_labels=0, radius=2, beta=2, alpha=0.1, keep_weights=False, device=0):
-        self.n_images = int(n_images)
-        self._n_labels = None
-        _Accumulator.__init__(self, grid, self.n_images, int(max_labels), int(radius), int(beta), float(alpha), int(bool(keep_weights)),
-                              int(device))
+        _LabelAccumulator.__init__(self, grid, n_images, int(max_labels), int(radius), int(beta), float(alpha), int(bool(keep_weights)),
+                                   int(device))
 
     def weight(self, image_index):
         """float32 weight of atlas `image_index` (in call order) per voxel, 0 where it is not active; after finish()."""
