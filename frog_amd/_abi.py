@@ -326,6 +326,15 @@ HIP_SYMBOLS = {
                                    C.c_uint32, c_u32_p, C.POINTER(C.c_int8), c_float_p, c_float_p]),
     "frog_glm_draw": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int, c_u32_p, C.POINTER(C.c_int8)]),
     "frog_glm_destroy": (None, [C.c_void_p]),
+    "frog_components": (C.c_int, [C.POINTER(FrogVolume), C.c_int, C.c_int, c_u32_p, c_u32_p, C.POINTER(C.c_uint64)]),
+    "frog_clusters_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_int, C.c_int,
+                                       C.POINTER(C.c_void_p)]),
+    "frog_glm_permute_clusters": (C.c_int, [C.c_void_p, C.c_uint32, c_double_p, C.c_uint32, C.c_double, C.POINTER(C.c_uint8), C.c_uint32,
+                                            C.c_uint32, c_u32_p, C.POINTER(C.c_int8), C.c_uint32, C.c_void_p, c_float_p, c_float_p]),
+    "frog_clusters_finish": (C.c_int, [C.c_void_p, c_u32_p]),
+    "frog_clusters_mask": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]),
+    "frog_clusters_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, c_u32_p, c_u32_p]),
+    "frog_clusters_destroy": (None, [C.c_void_p]),
     "frog_labels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_labels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
     "frog_labels_finish": (C.c_int, [C.c_void_p, c_u32_p]),

@@ -1047,6 +1047,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 #include "k_edt.hip.h"
 #include "k_joint.hip.h"
 #include "k_glm.hip.h"
+#include "k_ccl.hip.h"
 
 } // namespace
 
@@ -1102,6 +1103,18 @@ struct frog_glm : frog_windowed {
     std::vector<double> design;                     // n_images x p
     frog::DevBuf<float> d_vals;                     // n_images planes of `window` values, in the order of the adds
     frog::DevBuf<double> d_design, d_table;         // d_table: the design rows of one launch's permutations, grown on demand
+};
+
+// the supra-threshold voxels of every permutation, contrast and side of a permutation test on one grid, as bit masks, and the
+// workspace that labels their connected components
+struct frog_clusters : frog_group {
+    uint32_t n_perms = 0, n_contrasts = 0, sides = 1;
+    float threshold = 0;
+    CclGrid ccl{};
+    size_t slots = 0;                               // n_perms * n_contrasts * sides masks of ccl.words words
+    uint32_t batch = 0;                             // the masks one launch labels: the workspace holds that many
+    frog::DevBuf<uint32_t> d_bits, d_parent, d_extent, d_stats;
+    std::vector<uint8_t> received;                  // [perm * nz + z]: the plane has been written for the permutation's slots
 };
 
 // The label table of frog_labels, frog_wlabels (and through it frog_jlabels) and frog_staple: the device hash map in which
@@ -2069,34 +2082,38 @@ int glm_fit_arguments(const char *where, const frog_glm *a, uint32_t n_contrasts
 }
 
 // The fit kernel over the window for the n_perms permutations whose rows d_table holds: instantiated on the number of columns
-// and on whether the values of a voxel stay in LDS.
-hipError_t glm_fit_launch(const frog_glm *a, const GlmArgs &f)
+// and on whether the values of a voxel stay in LDS.  With a sink, the kernel that also stores the bits.
+template <int P, bool LDS>
+hipError_t glm_fit_go(const frog_glm *a, const GlmArgs &f, const GlmSink *sink, size_t bytes)
+{
+    // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
+    return chunked_launch(f.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
+        if (sink) glm_fit_kernel<P, LDS, GlmSink><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f, *sink);
+        else glm_fit_kernel<P, LDS><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f);
+    });
+}
+
+hipError_t glm_fit_launch(const frog_glm *a, const GlmArgs &f, const GlmSink *sink = nullptr)
 {
     const bool lds = a->n_images <= GLM_LDS_MAX;
     const size_t bytes = (f.extrema ? (size_t)f.n_perms * f.n_contrasts * 2 * sizeof(uint32_t) : 0) + (lds ? (size_t)a->n_images * 256 * sizeof(float) : 0);
-    auto go = [&](auto kernel) {
-        // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
-        return chunked_launch(f.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
-            kernel<<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f);
-        });
-    };
     switch (a->p * 2 + (lds ? 1 : 0)) {
-    case 2: return go(glm_fit_kernel<1, false>);
-    case 3: return go(glm_fit_kernel<1, true>);
-    case 4: return go(glm_fit_kernel<2, false>);
-    case 5: return go(glm_fit_kernel<2, true>);
-    case 6: return go(glm_fit_kernel<3, false>);
-    case 7: return go(glm_fit_kernel<3, true>);
-    case 8: return go(glm_fit_kernel<4, false>);
-    case 9: return go(glm_fit_kernel<4, true>);
-    case 10: return go(glm_fit_kernel<5, false>);
-    case 11: return go(glm_fit_kernel<5, true>);
-    case 12: return go(glm_fit_kernel<6, false>);
-    case 13: return go(glm_fit_kernel<6, true>);
-    case 14: return go(glm_fit_kernel<7, false>);
-    case 15: return go(glm_fit_kernel<7, true>);
-    case 16: return go(glm_fit_kernel<8, false>);
-    default: return go(glm_fit_kernel<8, true>);
+    case 2: return glm_fit_go<1, false>(a, f, sink, bytes);
+    case 3: return glm_fit_go<1, true>(a, f, sink, bytes);
+    case 4: return glm_fit_go<2, false>(a, f, sink, bytes);
+    case 5: return glm_fit_go<2, true>(a, f, sink, bytes);
+    case 6: return glm_fit_go<3, false>(a, f, sink, bytes);
+    case 7: return glm_fit_go<3, true>(a, f, sink, bytes);
+    case 8: return glm_fit_go<4, false>(a, f, sink, bytes);
+    case 9: return glm_fit_go<4, true>(a, f, sink, bytes);
+    case 10: return glm_fit_go<5, false>(a, f, sink, bytes);
+    case 11: return glm_fit_go<5, true>(a, f, sink, bytes);
+    case 12: return glm_fit_go<6, false>(a, f, sink, bytes);
+    case 13: return glm_fit_go<6, true>(a, f, sink, bytes);
+    case 14: return glm_fit_go<7, false>(a, f, sink, bytes);
+    case 15: return glm_fit_go<7, true>(a, f, sink, bytes);
+    case 16: return glm_fit_go<8, false>(a, f, sink, bytes);
+    default: return glm_fit_go<8, true>(a, f, sink, bytes);
     }
 }
 
@@ -2130,6 +2147,149 @@ int glm_fit_args(const char *where, frog_glm *a, uint32_t n_contrasts, const dou
         f->region = d_region.p;
     }
     return FROG_OK;
+}
+
+// frog_glm_permute (sink null) and frog_glm_permute_clusters: the validation, the table batches and the launches, which with
+// a sink store the bits of row k in the sink's permutation first_perm + k
+int glm_permute(const char *where, frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign, uint32_t first_perm,
+                frog_clusters *sink, float *max_t, float *min_t)
+{
+    const std::string w = std::string(where) + ": ";
+    if (int rc = glm_fit_arguments(where, a, n_contrasts, contrasts, min_count, sigma_floor)) return rc;
+    if (!n_contrasts || !n_perms || !perm || (!sink && !max_t && !min_t)) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (!columns || (columns >> a->p)) return fail(FROG_E_INVALID, w + "columns names at least one column, and none past the design's");
+    const size_t entries = (size_t)n_perms * a->n_images;
+    for (size_t e = 0; e < entries; e++) {
+        if (perm[e] >= a->n_images) return fail(FROG_E_INVALID, w + "a perm entry is not an image index");
+        if (sign && sign[e] != 1 && sign[e] != -1) return fail(FROG_E_INVALID, w + "a sign is +1 or -1");
+    }
+    const size_t plane = (size_t)a->grid.dims[0] * a->grid.dims[1];
+    const uint32_t z0 = (uint32_t)(a->first / plane), nz = (uint32_t)(a->window / plane), depth = a->grid.dims[2];
+    if (sink) {
+        if (sink->device != a->device) return fail(FROG_E_INVALID, w + "sink and accumulator on different devices");
+        for (int k = 0; k < 3; k++)
+            if (sink->grid.dims[k] != a->grid.dims[k]) return fail(FROG_E_INVALID, w + "the sink's grid is not the accumulator's");
+        if (n_contrasts != sink->n_contrasts) return fail(FROG_E_INVALID, w + "the sink was created for another number of contrasts");
+        if (first_perm > sink->n_perms || n_perms > sink->n_perms - first_perm) return fail(FROG_E_INVALID, w + "permutations beyond the sink's");
+        for (uint32_t k = 0; k < n_perms; k++)
+            for (uint32_t z = 0; z < nz; z++)
+                if (sink->received[(size_t)(first_perm + k) * depth + z0 + z])
+                    return fail(FROG_E_STATE, w + "plane " + std::to_string(z0 + z) + " of permutation " + std::to_string(first_perm + k) + " has been written before");
+    }
+    KCHECK(hipSetDevice(a->device));
+    const size_t n_ext = (size_t)n_perms * n_contrasts * 2;
+    frog::DevBuf<uint32_t> d_perm, d_ext;
+    frog::DevBuf<int8_t> d_sign;
+    frog::DevBuf<uint8_t> d_region;
+    KCHECK(d_perm.alloc(entries));
+    KCHECK(d_ext.alloc(n_ext));
+    if (sign) KCHECK(d_sign.alloc(entries));
+    std::vector<uint32_t> ext(n_ext);
+    for (size_t e = 0; e < n_ext; e++) ext[e] = (e & 1) ? GLM_KEY_POS_INF : GLM_KEY_NEG_INF;
+    GlmArgs f;
+    if (int rc = glm_fit_args(where, a, n_contrasts, contrasts, min_count, sigma_floor, region, d_region, &f)) return rc;
+    hipError_t e = hipMemcpy(d_perm.p, perm, entries * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && sign) e = hipMemcpy(d_sign.p, sign, entries, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_ext.p, ext.data(), n_ext * sizeof(uint32_t), hipMemcpyHostToDevice);
+    // the permutations in launches of at most GLM_BATCH whose design rows fit GLM_TABLE_BYTES
+    const size_t per_perm = (size_t)a->n_images * glm_row_doubles(a->p) * sizeof(double);
+    const uint32_t batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(GLM_BATCH, GLM_TABLE_BYTES / per_perm));
+    for (uint32_t k0 = 0; k0 < n_perms && e == hipSuccess; k0 += batch) {
+        const uint32_t nb = std::min(batch, n_perms - k0);
+        const size_t at = (size_t)k0 * a->n_images;
+        e = glm_table_launch(a, d_perm.p + at, sign ? d_sign.p + at : nullptr, columns, nb);
+        f.n_perms = nb;
+        f.extrema = d_ext.p + (size_t)k0 * n_contrasts * 2;
+        const GlmSink to = sink ? GlmSink{ sink->d_bits.p, sink->ccl.words, a->first, first_perm + k0, sink->sides, sink->threshold } : GlmSink{};
+        if (e == hipSuccess) e = glm_fit_launch(a, f, sink ? &to : nullptr);
+    }
+    if (e == hipSuccess) e = hipMemcpy(ext.data(), d_ext.p, n_ext * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(where, e);
+    for (uint32_t k = 0; sink && k < n_perms; k++) std::fill_n(sink->received.begin() + (size_t)(first_perm + k) * depth + z0, nz, (uint8_t)1);
+    for (size_t e2 = 0; e2 < n_ext / 2; e2++) {
+        const uint32_t hi = ext[2 * e2], lo = ext[2 * e2 + 1];
+        const uint32_t bits_hi = (hi & 0x80000000u) ? (hi ^ 0x80000000u) : ~hi, bits_lo = (lo & 0x80000000u) ? (lo ^ 0x80000000u) : ~lo;
+        if (max_t) std::memcpy(max_t + e2, &bits_hi, sizeof(float));
+        if (min_t) std::memcpy(min_t + e2, &bits_lo, sizeof(float));
+    }
+    return FROG_OK;
+}
+
+// ---- connected components (k_ccl.hip.h) ---------------------------------------------------------------------------------------
+
+// the largest |dx| + |dy| + |dz| of a neighbour at connectivity 6, 18 or 26; 0 for anything else
+uint32_t ccl_order(int connectivity) { return connectivity == 6 ? 1u : connectivity == 18 ? 2u : connectivity == 26 ? 3u : 0u; }
+
+CclGrid ccl_grid(const frog_volume *grid, size_t total, int connectivity)
+{
+    return CclGrid{ grid->dims[0], grid->dims[1], grid->dims[2], ccl_order(connectivity), (total + 31) / 32, total };
+}
+
+// The components of n_masks <= the workspace's masks, `words` apart from d_masks on: parents and extents at the set voxels of
+// the workspace, and with d_stats (2 words per mask, zero) the components' number and the largest extent.
+hipError_t ccl_label(const CclGrid &g, const uint32_t *d_masks, uint32_t n_masks, uint32_t *d_parent, uint32_t *d_extent, uint32_t *d_stats)
+{
+    hipError_t e = chunked_launch(g.words, [&](unsigned blocks, size_t base) {
+        ccl_init_kernel<<<dim3(blocks, n_masks), LAUNCH_BLOCK>>>(base, d_masks, g, d_parent, d_extent);
+    });
+    if (e == hipSuccess) e = chunked_launch(g.words, [&](unsigned blocks, size_t base) {
+        ccl_link_kernel<<<dim3(blocks, n_masks), LAUNCH_BLOCK>>>(base, d_masks, g, d_parent);
+    });
+    if (e == hipSuccess) e = chunked_launch(g.words, [&](unsigned blocks, size_t base) {
+        ccl_count_kernel<<<dim3(blocks, n_masks), LAUNCH_BLOCK>>>(base, d_masks, g, d_parent, d_extent);
+    });
+    if (e == hipSuccess && d_stats) e = chunked_launch(g.words, [&](unsigned blocks, size_t base) {
+        ccl_stats_kernel<<<dim3(blocks, n_masks), LAUNCH_BLOCK>>>(base, d_masks, g, d_parent, d_extent, d_stats);
+    });
+    return e;
+}
+
+// One labelled mask as labels 1..K in ascending order of root, into the host array: the device writes root + 1, and since a
+// root is the smallest index of its component, one ascending host pass numbers a root when it meets it and copies the
+// number to the members that follow.  Returns K through n.
+hipError_t ccl_labels_out(const CclGrid &g, const uint32_t *d_mask, const uint32_t *d_parent, uint32_t *labels, uint32_t *n)
+{
+    frog::DevBuf<uint32_t> d_out;
+    hipError_t e = d_out.alloc(g.total);
+    if (e == hipSuccess) e = chunked_launch(g.total, [&](unsigned blocks, size_t base) {
+        ccl_roots_kernel<<<blocks, LAUNCH_BLOCK>>>(base, d_mask, g.total, d_parent, d_out.p);
+    });
+    if (e == hipSuccess) e = hipMemcpy(labels, d_out.p, g.total * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    uint32_t k = 0;
+    for (size_t v = 0; v < g.total; v++) {
+        if (!labels[v]) continue;
+        const size_t root = labels[v] - 1;
+        labels[v] = root == v ? ++k : labels[root];
+    }
+    *n = k;
+    return hipSuccess;
+}
+
+// what frog_clusters_mask and frog_clusters_labels refuse alike; the slot's index through `slot`
+int clusters_slot(const char *where, const frog_clusters *s, uint32_t perm, uint32_t contrast, int side, const void *out, size_t *slot)
+{
+    if (!s || !out) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (perm >= s->n_perms || contrast >= s->n_contrasts || side < 0 || (uint32_t)side >= s->sides)
+        return fail(FROG_E_INVALID, std::string(where) + ": no such permutation, contrast or side in the sink");
+    *slot = ((size_t)perm * s->n_contrasts + contrast) * s->sides + (uint32_t)side;
+    return FROG_OK;
+}
+
+// whether every z-plane of permutations [first, first + count) has been written
+bool clusters_complete(const frog_clusters *s, uint32_t first, uint32_t count)
+{
+    const size_t depth = s->grid.dims[2];
+    return std::find(s->received.begin() + first * depth, s->received.begin() + ((size_t)first + count) * depth, (uint8_t)0)
+           == s->received.begin() + ((size_t)first + count) * depth;
+}
+
+template <class S>
+void ccl_pack(const S *voxels, size_t total, std::vector<uint32_t> &words)
+{
+    for (size_t v = 0; v < total; v++)
+        if (voxels[v] != 0) words[v >> 5] |= 1u << (v & 31);
 }
 
 // frog_staple_add for a source of type S: labels_add_typed with the index plane in place of the vote.  The plane of the
@@ -2880,49 +3040,7 @@ int frog_glm_permute(frog_glm *a, uint32_t n_contrasts, const double *contrasts,
                      const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
                      float *max_t, float *min_t)
 {
-    if (int rc = glm_fit_arguments("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor)) return rc;
-    if (!n_contrasts || !n_perms || !perm || (!max_t && !min_t)) return fail(FROG_E_INVALID, "bad arguments to frog_glm_permute");
-    if (!columns || (columns >> a->p)) return fail(FROG_E_INVALID, "frog_glm_permute: columns names at least one column, and none past the design's");
-    const size_t entries = (size_t)n_perms * a->n_images;
-    for (size_t e = 0; e < entries; e++) {
-        if (perm[e] >= a->n_images) return fail(FROG_E_INVALID, "frog_glm_permute: a perm entry is not an image index");
-        if (sign && sign[e] != 1 && sign[e] != -1) return fail(FROG_E_INVALID, "frog_glm_permute: a sign is +1 or -1");
-    }
-    KCHECK(hipSetDevice(a->device));
-    const size_t n_ext = (size_t)n_perms * n_contrasts * 2;
-    frog::DevBuf<uint32_t> d_perm, d_ext;
-    frog::DevBuf<int8_t> d_sign;
-    frog::DevBuf<uint8_t> d_region;
-    KCHECK(d_perm.alloc(entries));
-    KCHECK(d_ext.alloc(n_ext));
-    if (sign) KCHECK(d_sign.alloc(entries));
-    std::vector<uint32_t> ext(n_ext);
-    for (size_t e = 0; e < n_ext; e++) ext[e] = (e & 1) ? GLM_KEY_POS_INF : GLM_KEY_NEG_INF;
-    GlmArgs f;
-    if (int rc = glm_fit_args("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor, region, d_region, &f)) return rc;
-    hipError_t e = hipMemcpy(d_perm.p, perm, entries * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && sign) e = hipMemcpy(d_sign.p, sign, entries, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_ext.p, ext.data(), n_ext * sizeof(uint32_t), hipMemcpyHostToDevice);
-    // the permutations in launches of at most GLM_BATCH whose design rows fit GLM_TABLE_BYTES
-    const size_t per_perm = (size_t)a->n_images * glm_row_doubles(a->p) * sizeof(double);
-    const uint32_t batch = (uint32_t)std::max<size_t>(1, std::min<size_t>(GLM_BATCH, GLM_TABLE_BYTES / per_perm));
-    for (uint32_t k0 = 0; k0 < n_perms && e == hipSuccess; k0 += batch) {
-        const uint32_t nb = std::min(batch, n_perms - k0);
-        const size_t at = (size_t)k0 * a->n_images;
-        e = glm_table_launch(a, d_perm.p + at, sign ? d_sign.p + at : nullptr, columns, nb);
-        f.n_perms = nb;
-        f.extrema = d_ext.p + (size_t)k0 * n_contrasts * 2;
-        if (e == hipSuccess) e = glm_fit_launch(a, f);
-    }
-    if (e == hipSuccess) e = hipMemcpy(ext.data(), d_ext.p, n_ext * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("frog_glm_permute", e);
-    for (size_t e2 = 0; e2 < n_ext / 2; e2++) {
-        const uint32_t hi = ext[2 * e2], lo = ext[2 * e2 + 1];
-        const uint32_t bits_hi = (hi & 0x80000000u) ? (hi ^ 0x80000000u) : ~hi, bits_lo = (lo & 0x80000000u) ? (lo ^ 0x80000000u) : ~lo;
-        if (max_t) std::memcpy(max_t + e2, &bits_hi, sizeof(float));
-        if (min_t) std::memcpy(min_t + e2, &bits_lo, sizeof(float));
-    }
-    return FROG_OK;
+    return glm_permute("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, 0, nullptr, max_t, min_t);
 }
 
 int frog_glm_draw(uint32_t n, uint32_t n_perms, uint64_t seed, int shuffle, int flip, uint32_t *perm, int8_t *sign)
@@ -2949,6 +3067,128 @@ int frog_glm_draw(uint32_t n, uint32_t n_perms, uint64_t seed, int shuffle, int 
 }
 
 void frog_glm_destroy(frog_glm *a) { group_destroy(a); }
+
+int frog_components(const frog_volume *mask, int connectivity, int device, uint32_t *labels, uint32_t *n_components, uint64_t *largest)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_components", mask, mask, &total)) return rc;
+    if (!labels && !n_components && !largest) return fail(FROG_E_INVALID, "frog_components: no output asked for");
+    if (!mask->data) return fail(FROG_E_INVALID, "frog_components: a mask without voxels");
+    if (!integer_voxel_type(mask->dtype)) return fail(FROG_E_INVALID, "frog_components: a mask has an integer type");
+    if (!ccl_order(connectivity)) return fail(FROG_E_INVALID, "frog_components: connectivity 6, 18 or 26");
+    const CclGrid g = ccl_grid(mask, total, connectivity);
+    std::vector<uint32_t> words(g.words, 0u);
+    with_integer_voxel_type(mask->dtype, [&](auto s) { ccl_pack((const decltype(s) *)mask->data, total, words); return FROG_OK; });
+    if (int rc = select_device(device)) return rc;
+    frog::DevBuf<uint32_t> d_bits, d_parent, d_extent, d_stats;
+    KCHECK(d_bits.alloc(g.words));
+    KCHECK(d_parent.alloc(total));
+    KCHECK(d_extent.alloc(total));
+    KCHECK(d_stats.alloc(2));
+    uint32_t stats[2] = { 0, 0 }, n = 0;
+    hipError_t e = hipMemcpy(d_bits.p, words.data(), g.words * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_stats.p, 0, sizeof stats);
+    if (e == hipSuccess) e = ccl_label(g, d_bits.p, 1, d_parent.p, d_extent.p, d_stats.p);
+    if (e == hipSuccess) e = hipMemcpy(stats, d_stats.p, sizeof stats, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && labels) e = ccl_labels_out(g, d_bits.p, d_parent.p, labels, &n);
+    if (e != hipSuccess) return hip_fail("frog_components", e);
+    if (n_components) *n_components = stats[0];
+    if (largest) *largest = stats[1];
+    return FROG_OK;
+}
+
+int frog_clusters_create(const frog_volume *grid, uint32_t n_perms, uint32_t n_contrasts, int two_sided, float threshold, int connectivity,
+                         int device, frog_clusters **out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_clusters_create", grid, out, &total)) return rc;
+    if (!n_perms || !n_contrasts) return fail(FROG_E_INVALID, "frog_clusters_create: at least one permutation and one contrast");
+    if (n_contrasts > FROG_GLM_MAX_CONTRASTS) return fail(FROG_E_INVALID, "frog_clusters_create: at most " + std::to_string(FROG_GLM_MAX_CONTRASTS) + " contrasts");
+    if (!(threshold >= 0.0f) || !std::isfinite(threshold)) return fail(FROG_E_INVALID, "frog_clusters_create: the threshold must be finite and not negative");
+    if (!ccl_order(connectivity)) return fail(FROG_E_INVALID, "frog_clusters_create: connectivity 6, 18 or 26");
+    std::unique_ptr<frog_clusters> s;
+    if (int rc = group_new(grid, total, device, s)) return rc;
+    s->n_perms = n_perms;
+    s->n_contrasts = n_contrasts;
+    s->sides = two_sided ? 2u : 1u;
+    s->threshold = threshold;
+    s->ccl = ccl_grid(grid, total, connectivity);
+    s->slots = (size_t)n_perms * n_contrasts * s->sides;
+    // the masks, and a workspace of two words per voxel for as many masks of a launch as fit, up to CCL_BATCH
+    size_t free_bytes = 0, device_bytes = 0;
+    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
+    const size_t mask_bytes = s->slots * s->ccl.words * sizeof(uint32_t) + s->slots * 2 * sizeof(uint32_t), work_bytes = total * 2 * sizeof(uint32_t);
+    if (mask_bytes + work_bytes > free_bytes)
+        return fail(FROG_E_NOMEM, "frog_clusters_create: " + std::to_string(s->slots) + " masks and the workspace need " + std::to_string(mask_bytes + work_bytes) +
+                                  " bytes of device memory, " + std::to_string(free_bytes) + " are free");
+    s->batch = (uint32_t)std::min<size_t>(std::min<size_t>(s->slots, CCL_BATCH), std::max<size_t>(1, (free_bytes - mask_bytes) / 2 / work_bytes));
+    KCHECK(s->d_bits.alloc(s->slots * s->ccl.words));
+    KCHECK(s->d_stats.alloc(s->slots * 2));
+    KCHECK(s->d_parent.alloc((size_t)s->batch * total));
+    KCHECK(s->d_extent.alloc((size_t)s->batch * total));
+    KCHECK(hipMemset(s->d_bits.p, 0, s->d_bits.bytes()));
+    s->received.assign((size_t)n_perms * grid->dims[2], 0);
+    *out = s.release();
+    return FROG_OK;
+}
+
+int frog_glm_permute_clusters(frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                              const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
+                              uint32_t first_perm, frog_clusters *sink, float *max_t, float *min_t)
+{
+    if (!sink) return fail(FROG_E_INVALID, "bad arguments to frog_glm_permute_clusters");
+    return glm_permute("frog_glm_permute_clusters", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, first_perm,
+                       sink, max_t, min_t);
+}
+
+int frog_clusters_finish(frog_clusters *s, uint32_t *max_extent)
+{
+    if (!s || !max_extent) return fail(FROG_E_INVALID, "bad arguments to frog_clusters_finish");
+    if (!clusters_complete(s, 0, s->n_perms)) return fail(FROG_E_STATE, "frog_clusters_finish: a permutation has not received every plane of the grid");
+    KCHECK(hipSetDevice(s->device));
+    hipError_t e = hipMemset(s->d_stats.p, 0, s->d_stats.bytes());
+    for (size_t at = 0; at < s->slots && e == hipSuccess; at += s->batch)
+        e = ccl_label(s->ccl, s->d_bits.p + at * s->ccl.words, (uint32_t)std::min<size_t>(s->batch, s->slots - at), s->d_parent.p, s->d_extent.p,
+                      s->d_stats.p + 2 * at);
+    std::vector<uint32_t> stats(s->slots * 2);
+    if (e == hipSuccess) e = hipMemcpy(stats.data(), s->d_stats.p, s->d_stats.bytes(), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_clusters_finish", e);
+    for (size_t k = 0; k < s->slots; k++) max_extent[k] = stats[2 * k + 1];
+    return FROG_OK;
+}
+
+int frog_clusters_mask(frog_clusters *s, uint32_t perm, uint32_t contrast, int side, uint8_t *mask)
+{
+    size_t slot;
+    if (int rc = clusters_slot("frog_clusters_mask", s, perm, contrast, side, mask, &slot)) return rc;
+    KCHECK(hipSetDevice(s->device));
+    frog::DevBuf<uint8_t> d_out;
+    KCHECK(d_out.alloc(s->total));
+    const uint32_t *d_mask = s->d_bits.p + slot * s->ccl.words;
+    hipError_t e = chunked_launch(s->total, [&](unsigned blocks, size_t base) {
+        ccl_bytes_kernel<<<blocks, LAUNCH_BLOCK>>>(base, d_mask, s->total, d_out.p);
+    });
+    if (e == hipSuccess) e = hipMemcpy(mask, d_out.p, s->total, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_clusters_mask", e);
+    return FROG_OK;
+}
+
+int frog_clusters_labels(frog_clusters *s, uint32_t perm, uint32_t contrast, int side, uint32_t *labels, uint32_t *n_components)
+{
+    size_t slot;
+    if (int rc = clusters_slot("frog_clusters_labels", s, perm, contrast, side, labels, &slot)) return rc;
+    if (!clusters_complete(s, perm, 1)) return fail(FROG_E_STATE, "frog_clusters_labels: the permutation has not received every plane of the grid");
+    KCHECK(hipSetDevice(s->device));
+    const uint32_t *d_mask = s->d_bits.p + slot * s->ccl.words;
+    uint32_t n = 0;
+    hipError_t e = ccl_label(s->ccl, d_mask, 1, s->d_parent.p, s->d_extent.p, nullptr);
+    if (e == hipSuccess) e = ccl_labels_out(s->ccl, d_mask, s->d_parent.p, labels, &n);
+    if (e != hipSuccess) return hip_fail("frog_clusters_labels", e);
+    if (n_components) *n_components = n;
+    return FROG_OK;
+}
+
+void frog_clusters_destroy(frog_clusters *s) { group_destroy(s); }
 
 int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_labels **out)
 {

@@ -20,6 +20,10 @@
 // keys are exact and do not depend on the order they are taken in.  Per permutation and contrast: a wave's reduction by
 // DPP moves, one LDS atomic per wave, and at the end of the tile one integer global atomic per block.  No floating-point
 // atomic anywhere.
+//
+// Sink.  frog_glm_permute_clusters instantiates the fit kernel with a GlmSink: the voxels that count towards an extremum and
+// lie beyond the cluster-forming threshold get their bit set in the masks of a frog_clusters (k_ccl.hip.h), a ballot per
+// wavefront, contrast and side and an integer atomicOr where it is not zero.  Without one the kernel is what it was.
 #pragma once
 
 constexpr uint32_t GLM_NAN_BITS = 0x7FC00000u;
@@ -272,10 +276,39 @@ __device__ __forceinline__ uint32_t glm_wave_extreme(uint32_t v)
     return v;
 }
 
+// where glm_fit_kernel sets the bits of the supra-threshold voxels: the masks of a frog_clusters (k_ccl.hip.h states
+// their layout), slot (permutation, contrast, side) at bits + slot * words
+struct GlmSink {
+    uint32_t *bits;
+    size_t words;
+    size_t first;                                   // the window's first voxel in the grid
+    uint32_t perm0;                                 // the sink's permutation of the launch's first
+    uint32_t sides;
+    float threshold;
+};
+__device__ __forceinline__ const GlmSink &glm_the_sink(const GlmSink &sink) { return sink; }
+
+// The bits of the wavefront's 64 consecutive voxels, the first at grid index g0, into `mask`: the ballot shifted to g0's place
+// in its word spans up to three words, which lanes 0 to 2 OR in where they are not zero.  A word past the mask's end would
+// hold bits of voxels past the grid's, which are never on.  Every lane of the wavefront must be active.
+__device__ __forceinline__ void glm_sink_store(uint32_t *mask, size_t g0, bool on)
+{
+    const unsigned long long m = __ballot(on);
+    if (!m) return;
+    const uint32_t lane = threadIdx.x & 63u, shift = (uint32_t)(g0 & 31u);
+    const unsigned long long low = m << shift;
+    const uint32_t word = lane == 0u ? (uint32_t)low : lane == 1u ? (uint32_t)(low >> 32) : (shift ? (uint32_t)(m >> (64u - shift)) : 0u);
+    if (lane < 3u && word) atomicOr(mask + (g0 >> 5) + lane, word);
+}
+
 // One block per tile; blockIdx counts tiles from base / 256 (the launch's work-items are the tiles padded to whole blocks).
 // Dynamic LDS: 2 n_perms n_contrasts keys where extrema are wanted, then with LDS 256 n floats.
-template <int P, bool LDS>
-__global__ __launch_bounds__(256) void glm_fit_kernel(size_t base, const float *__restrict__ vals, const double *__restrict__ table, const GlmArgs a)
+// Sink is empty (finish and frog_glm_permute: the kernel takes no further argument) or one GlmSink (frog_glm_permute_clusters),
+// with which the kernel also sets the bit of every voxel that counts towards an extremum and lies beyond the threshold, in the
+// sink's mask of its permutation, contrast and side, at the voxel's index in the whole grid.
+template <int P, bool LDS, class... Sink>
+__global__ __launch_bounds__(256) void glm_fit_kernel(size_t base, const float *__restrict__ vals, const double *__restrict__ table, const GlmArgs a,
+                                                      const Sink... sink)
 {
     extern __shared__ uint32_t glm_mem[];
     constexpr int ROW = P + P * (P + 1) / 2;
@@ -338,6 +371,14 @@ __global__ __launch_bounds__(256) void glm_fit_kernel(size_t base, const float *
                 if ((tid & 63u) == 63u) {
                     atomicMax(&ext[(kk * C + c) * 2u], hi);
                     atomicMin(&ext[(kk * C + c) * 2u + 1u], lo);
+                }
+                if constexpr (sizeof...(Sink) != 0) {
+                    // f32 comparisons on the t the extrema are taken over; side 0 above the threshold, side 1 below its negative
+                    const GlmSink &to = glm_the_sink(sink...);
+                    uint32_t *const mask = to.bits + ((size_t)(to.perm0 + kk) * C + c) * to.sides * to.words;
+                    const size_t g0 = to.first + w0 + (tid & ~63u);
+                    glm_sink_store(mask, g0, counts && t > to.threshold);
+                    if (to.sides == 2u) glm_sink_store(mask + to.words, g0, counts && t < -to.threshold);
                 }
             }
         }

@@ -3,7 +3,7 @@
 // over all voxels (frog_glm, include/frog_chain.h, which states the arithmetic).
 //   GroupStats bbox.json spacing design.csv [-c contrasts.csv] [-td transformsDir] [-o outDir] [-v jacobian|logjacobian|images]
 //              [-vl volumes.txt] [-ml masks.txt] [-m regionMask] [-mc minCount] [-sf sigmaFloor] [-f fill] [-np nPerms]
-//              [-ps seed] [-pc columns] [-pf 1] [-two 1] [-rp planes] [-dev n]
+//              [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-rp planes] [-dev n]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid).  design.csv has one row per image and one column per regressor,
 // numbers separated by commas or blanks, after an optional header line; row i belongs to <transformsDir>/<i>.json (default
 // "transforms"), which is inverted as AverageImage inverts it.  -c: one contrast per row, as many numbers as the design has
@@ -22,6 +22,15 @@
 // fwe_p_<c>.nii.gz = (float)((1 + #{k >= 1 : max_t[k][c] >= t}) / (double)nPerms), 1 where the voxel is unfit or t is NaN;
 // -two 1 compares |t| with max(max_t, -min_t).  maxt.csv: permutation,contrast,max,min as %.9g.  threshold_p05 is the largest
 // null maximum a t must exceed for p < 0.05 (inf where no count of exceedances gives that), voxels_p05 the voxels that do.
+// -ct threshold (needs -np): the cluster-extent test (frog_clusters).  The voxels with t > threshold, and with -two 1 also
+// those with t < -threshold, form clusters at connectivity -cc (default 26: faces, edges and corners; needs -ct); a cluster's
+// p is (float)((1 + #{k >= 1 : extent[k][c] >= its voxels}) / (double)nPerms), extent[k][c] the largest cluster under
+// permutation k, with -two 1 the larger of the two sides'.  clusters_<c>.nii.gz (INT32): the observed map's clusters 1..K in
+// ascending order of their smallest voxel index, the negative side's after the positive side's.  cluster_p_<c>.nii.gz
+// (FLOAT32): the p of the voxel's cluster, 1 elsewhere.  clusters.csv: contrast,cluster,sign,voxels,peak_t,peak_x,peak_y,
+// peak_z,p_fwe, the peak the largest |t| of the cluster, the smallest index among equals.  maxextent.csv:
+// permutation,contrast,extent.  One sink on the device holds every permutation's masks for the whole grid, so a cluster that
+// crosses slabs is one cluster; if it does not fit, the tool says how many bytes it needs and stops before the first output.
 // The device holds slabs of frog_glm_planes z-planes, or -rp planes if that is fewer; the slab count is printed and changes no
 // bit of any file.  Every input is checked before anything is written.
 #include "group_tool.h"
@@ -95,13 +104,13 @@ int main(int argc, char *argv[])
     PhaseTimes times;
     std::vector<std::string> positional;
     std::string transformsDir = "transforms", outDir = ".", contrastsPath, valueName = "logjacobian", volumeList, maskList, regionPath, columnList;
-    int device = 0, flips = 0, twoSided = 0;
+    int device = 0, flips = 0, twoSided = 0, connectivity = 26;
     long minCount = 1, nPerms = 0, planesOption = 0;
     unsigned long long seed = 0;
-    double sigmaFloor = 0;
+    double sigmaFloor = 0, clusterThreshold = 0;
     float fill = 0;
-    bool planesGiven = false, permOption = false;
-    int a = positional_arguments(argc, argv, 1, { "-c", "-td", "-o", "-v", "-vl", "-ml", "-m", "-mc", "-sf", "-f", "-np", "-ps", "-pc", "-pf", "-two", "-rp", "-dev" },
+    bool planesGiven = false, permOption = false, clusterTest = false, connectivityGiven = false;
+    int a = positional_arguments(argc, argv, 1, { "-c", "-td", "-o", "-v", "-vl", "-ml", "-m", "-mc", "-sf", "-f", "-np", "-ps", "-pc", "-pf", "-two", "-ct", "-cc", "-rp", "-dev" },
                                  positional);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
@@ -120,6 +129,8 @@ int main(int argc, char *argv[])
         else if (std::strcmp(key, "-pc") == 0) { columnList = value; permOption = true; }
         else if (std::strcmp(key, "-pf") == 0) { flips = atoi(value); permOption = true; }
         else if (std::strcmp(key, "-two") == 0) { twoSided = atoi(value); permOption = true; }
+        else if (std::strcmp(key, "-ct") == 0) { clusterThreshold = atof(value); clusterTest = true; }
+        else if (std::strcmp(key, "-cc") == 0) { connectivity = atoi(value); connectivityGiven = true; }
         else if (std::strcmp(key, "-rp") == 0) { planesOption = atol(value); planesGiven = true; }
         else if (std::strcmp(key, "-dev") == 0) device = atoi(value);
         else die(std::string("unknown option ") + key);
@@ -127,7 +138,7 @@ int main(int argc, char *argv[])
     if (positional.size() != 3) {
         std::cout << "Usage : GroupStats bbox.json spacing design.csv [-c contrasts.csv] [-td transformsDir] [-o outDir] "
                      "[-v jacobian|logjacobian|images] [-vl volumes.txt] [-ml masks.txt] [-m regionMask] [-mc minCount] [-sf sigmaFloor] "
-                     "[-f fill] [-np nPerms] [-ps seed] [-pc columns] [-pf 1] [-two 1] [-rp planes] [-dev n]" << std::endl;
+                     "[-f fill] [-np nPerms] [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-rp planes] [-dev n]" << std::endl;
         return 1;
     }
 
@@ -139,6 +150,10 @@ int main(int argc, char *argv[])
     if (!(sigmaFloor >= 0.0)) die("-sf takes a stdev that is not negative");
     if (nPerms < 0 || nPerms == 1 || nPerms > 1000000) die("-np takes 2 to 1000000 permutations (the first is the design itself)");
     if (permOption && nPerms == 0) die("-ps, -pc, -pf and -two need -np");
+    if ((clusterTest || connectivityGiven) && nPerms == 0) die("-ct and -cc need -np");
+    if (connectivityGiven && !clusterTest) die("-cc needs -ct");
+    if (clusterTest && (!(clusterThreshold >= 0.0) || !std::isfinite((float)clusterThreshold))) die("-ct takes a threshold that is finite and not negative");
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26) die("-cc takes 6, 18 or 26");
     if (planesGiven && planesOption < 1) die("-rp takes a number of planes, at least 1");
     const auto design = read_table(positional[2], "the design");
     const size_t n = design.size(), p = design[0].size();
@@ -226,6 +241,9 @@ int main(int argc, char *argv[])
         }
         frog_volume_free(f);
     }
+    frog_clusters *sink = nullptr;
+    if (clusterTest && frog_clusters_create(&grid, (uint32_t)nPerms, (uint32_t)n_c, twoSided == 1, (float)clusterThreshold, connectivity, device, &sink))
+        die(frog_last_error());
     begin_output(outDir, n, "images", grid);
 
     auto t0 = clk::now();
@@ -300,8 +318,11 @@ int main(int argc, char *argv[])
         for (size_t j = 0; j < p; j++) std::memcpy(beta.data() + j * total + at, slabBeta.data() + j * slabVoxels, slabVoxels * sizeof(float));
         for (size_t c = 0; c < n_c; c++) std::memcpy(t.data() + c * total + at, slabT.data() + c * slabVoxels, slabVoxels * sizeof(float));
         if (nPerms) {
-            if (frog_glm_permute(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, columns, (uint32_t)nPerms, perm.data(),
-                                 flips == 1 ? sign.data() : nullptr, slabMax.data(), slabMin.data())) die(frog_last_error());
+            const int8_t *signs = flips == 1 ? sign.data() : nullptr;
+            if (sink ? frog_glm_permute_clusters(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, columns, (uint32_t)nPerms,
+                                                 perm.data(), signs, 0, sink, slabMax.data(), slabMin.data())
+                     : frog_glm_permute(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, columns, (uint32_t)nPerms, perm.data(),
+                                        signs, slabMax.data(), slabMin.data())) die(frog_last_error());
             for (size_t e = 0; e < maxT.size(); e++) {
                 if (float_key(slabMax[e]) > float_key(maxT[e])) maxT[e] = slabMax[e];
                 if (float_key(slabMin[e]) < float_key(minT[e])) minT[e] = slabMin[e];
@@ -311,6 +332,27 @@ int main(int argc, char *argv[])
         frog_glm_destroy(glm);
     }
     for (frog_chain *c : chains) frog_chain_destroy(c);
+    // the cluster-extent test: every slot's largest extent, and the observed map's labels, the negative side's after the positive's
+    const uint32_t sides = twoSided == 1 ? 2 : 1;
+    std::vector<uint32_t> slotExtent, clusterLabels, sideLabels;
+    std::vector<std::vector<int>> clusterSign(n_c);
+    if (sink) {
+        t0 = clk::now();
+        slotExtent.resize((size_t)nPerms * n_c * sides);
+        if (frog_clusters_finish(sink, slotExtent.data())) die(frog_last_error());
+        clusterLabels.assign(n_c * total, 0);
+        sideLabels.resize(total);
+        for (size_t c = 0; c < n_c; c++)
+            for (uint32_t side = 0; side < sides; side++) {
+                uint32_t found = 0;
+                if (frog_clusters_labels(sink, 0, (uint32_t)c, (int)side, sideLabels.data(), &found)) die(frog_last_error());
+                const uint32_t before = (uint32_t)clusterSign[c].size();
+                for (size_t v = 0; v < total; v++) if (sideLabels[v]) clusterLabels[c * total + v] = sideLabels[v] + before;
+                clusterSign[c].resize(before + found, side ? -1 : 1);
+            }
+        times.device_s += seconds(t0);
+        frog_clusters_destroy(sink);
+    }
 
     // ---- the files
     t0 = clk::now();
@@ -356,6 +398,47 @@ int main(int argc, char *argv[])
             }
             write("fwe_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
         }
+    }
+    if (clusterTest) {
+        std::ofstream csv(outDir + "/maxextent.csv"), table(outDir + "/clusters.csv");
+        csv << "permutation,contrast,extent\n";
+        table << "contrast,cluster,sign,voxels,peak_t,peak_x,peak_y,peak_z,p_fwe\n";
+        auto nullExtent = [&](long k, size_t c) {
+            const uint32_t *e = slotExtent.data() + ((size_t)k * n_c + c) * sides;
+            return sides == 2 ? std::max(e[0], e[1]) : e[0];
+        };
+        for (long k = 0; k < nPerms; k++)
+            for (size_t c = 0; c < n_c; c++) csv << k << "," << c << "," << nullExtent(k, c) << "\n";
+        csv.close();
+        if (!csv) die("cannot write " + outDir + "/maxextent.csv");
+        std::vector<float> pmap(total);
+        std::vector<uint32_t> null((size_t)nPerms - 1);
+        for (size_t c = 0; c < n_c; c++) {
+            const size_t found = clusterSign[c].size();
+            const uint32_t *labels = clusterLabels.data() + c * total;
+            std::vector<uint64_t> voxels(found + 1, 0);
+            std::vector<size_t> peak(found + 1, total);
+            for (size_t v = 0; v < total; v++) {
+                const uint32_t l = labels[v];
+                if (!l) continue;
+                voxels[l]++;
+                if (peak[l] == total || std::fabs(t[c * total + v]) > std::fabs(t[c * total + peak[l]])) peak[l] = v;
+            }
+            for (long k = 1; k < nPerms; k++) null[k - 1] = nullExtent(k, c);
+            std::sort(null.begin(), null.end());
+            std::vector<float> pOf(found + 1, 1.0f);
+            for (size_t l = 1; l <= found; l++) {
+                const size_t reach = null.end() - std::lower_bound(null.begin(), null.end(), (uint32_t)voxels[l]);
+                pOf[l] = (float)((double)(1 + reach) / (double)nPerms);
+                table << c << "," << l << "," << clusterSign[c][l - 1] << "," << voxels[l] << "," << csv_float(t[c * total + peak[l]]) << "," << peak[l] % grid.dims[0]
+                      << "," << (peak[l] / grid.dims[0]) % grid.dims[1] << "," << peak[l] / plane << "," << csv_float(pOf[l]) << "\n";
+            }
+            for (size_t v = 0; v < total; v++) pmap[v] = pOf[labels[v]];
+            write("clusters_" + std::to_string(c) + ".nii.gz", FROG_V_I32, clusterLabels.data() + c * total);
+            write("cluster_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
+        }
+        table.close();
+        if (!table) die("cannot write " + outDir + "/clusters.csv");
     }
     {
         std::ofstream csv(outDir + "/glm.csv");

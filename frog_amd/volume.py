@@ -425,6 +425,14 @@ class GroupGLM(_Accumulator):
         """(max_t, min_t), float32 (n_perms, n_contrasts): the extrema of each contrast's t over the window's fit voxels under
         every row of `perm` (n_perms x n_images image indices) and `sign` (+-1, or None).  `columns`: the design columns that
         move, an iterable of indices or a bit mask; default all."""
+        return self._permute(None, 0, contrasts, perm, sign, columns, min_count, sigma_floor, region)
+
+    def permute_clusters(self, sink, contrasts, perm, sign=None, columns=None, min_count=1, sigma_floor=0.0, region=None, first_perm=0):
+        """permute(), which also sets in the ClusterSink `sink`, for row k in the slots of its permutation first_perm + k, the
+        bit of every window voxel whose t counts towards the extrema and lies beyond the sink's threshold."""
+        return self._permute(sink, first_perm, contrasts, perm, sign, columns, min_count, sigma_floor, region)
+
+    def _permute(self, sink, first_perm, contrasts, perm, sign, columns, min_count, sigma_floor, region):
         c, _r, rp = self._fit_arguments(contrasts, region)
         pm = np.ascontiguousarray(perm, np.uint32).reshape(-1, self.design.shape[0])
         sg = None if sign is None else np.ascontiguousarray(sign, np.int8).reshape(pm.shape)
@@ -432,11 +440,71 @@ class GroupGLM(_Accumulator):
         bits = (1 << p) - 1 if columns is None else (int(columns) if np.isscalar(columns) else sum(1 << int(j) for j in set(columns)))
         hi = np.empty((len(pm), len(c)), np.float32)
         lo = np.empty((len(pm), len(c)), np.float32)
-        _abi.check(self._lib.frog_glm_permute(self._h, len(c), c.ctypes.data_as(_abi.c_double_p), int(min_count), float(sigma_floor), rp,
-                                              bits, len(pm), pm.ctypes.data_as(_abi.c_u32_p),
-                                              None if sg is None else sg.ctypes.data_as(C.POINTER(C.c_int8)),
-                                              hi.ctypes.data_as(_abi.c_float_p), lo.ctypes.data_as(_abi.c_float_p)), "frog_glm_permute")
+        shared = (self._h, len(c), c.ctypes.data_as(_abi.c_double_p), int(min_count), float(sigma_floor), rp, bits, len(pm),
+                  pm.ctypes.data_as(_abi.c_u32_p), None if sg is None else sg.ctypes.data_as(C.POINTER(C.c_int8)))
+        out = (hi.ctypes.data_as(_abi.c_float_p), lo.ctypes.data_as(_abi.c_float_p))
+        if sink is None:
+            _abi.check(self._lib.frog_glm_permute(*shared, *out), "frog_glm_permute")
+        else:
+            _abi.check(self._lib.frog_glm_permute_clusters(*shared, int(first_perm), sink._h, *out), "frog_glm_permute_clusters")
         return hi, lo
+
+
+class ClusterSink(_Accumulator):
+    """frog_clusters (include/frog_chain.h): on the device, for the whole `grid`, one bit mask per slot (permutation, contrast,
+    side) of the voxels whose t lies beyond `threshold` (side 0: t > threshold; with two_sided side 1: t < -threshold), which
+    GroupGLM.permute_clusters fills window by window, and the connected components of each mask at `connectivity`."""
+
+    _NAME = "clusters"
+
+    def __init__(self, grid, n_perms, n_contrasts, threshold, two_sided=False, connectivity=26, device=0):
+        super().__init__(grid, int(n_perms), int(n_contrasts), int(bool(two_sided)), float(threshold), int(connectivity), int(device))
+        self.n_perms, self.n_contrasts, self.sides = int(n_perms), int(n_contrasts), 2 if two_sided else 1
+        self.shape = self.dims[::-1]
+
+    def finish(self):
+        """The largest extent of every slot's mask, uint32 (n_perms, n_contrasts, sides); 0 where no voxel is set."""
+        out = np.empty((self.n_perms, self.n_contrasts, self.sides), np.uint32)
+        _abi.check(self._lib.frog_clusters_finish(self._h, out.ctypes.data_as(_abi.c_u32_p)), "frog_clusters_finish")
+        return out
+
+    def mask(self, perm, contrast, side=0):
+        """One slot's mask, bool on the grid."""
+        out = np.empty(self.shape, np.uint8)
+        _abi.check(self._lib.frog_clusters_mask(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(C.POINTER(C.c_uint8))),
+                   "frog_clusters_mask")
+        return out != 0
+
+    def labels(self, perm, contrast, side=0):
+        """(labels uint32 on the grid, n): one slot's components numbered 1..n in ascending order of their smallest voxel index."""
+        out = np.empty(self.shape, np.uint32)
+        n = C.c_uint32()
+        _abi.check(self._lib.frog_clusters_labels(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(_abi.c_u32_p), C.byref(n)),
+                   "frog_clusters_labels")
+        return out, n.value
+
+
+def components(mask, connectivity=26, device=0, largest=False):
+    """(labels, n) of the non-zero voxels of the integer array mask[z, y, x] (frog_components): labels uint32, 1..n in ascending
+    order of each component's smallest voxel index (scipy.ndimage.label's numbering), 0 elsewhere.  connectivity 6 (faces), 18
+    (faces and edges) or 26.  With `largest` also the largest component's voxels: (labels, n, largest)."""
+    a = np.ascontiguousarray(mask)
+    if a.dtype == bool:
+        a = a.view(np.uint8)
+    v = _abi.volume_view(a, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+    out = np.empty(a.shape, np.uint32)
+    n, big = C.c_uint32(), C.c_uint64()
+    _abi.check(_abi.hip_lib().frog_components(C.byref(v), int(connectivity), int(device), out.ctypes.data_as(_abi.c_u32_p), C.byref(n), C.byref(big)),
+               "frog_components")
+    return (out, n.value, big.value) if largest else (out, n.value)
+
+
+def cluster_p(extent, max_extent):
+    """The family-wise corrected p of clusters of `extent` voxels: (float32)((1 + #{k >= 1: max_extent[k] >= extent}) /
+    (double)n_perms), max_extent the n_perms largest null extents with row 0 the unpermuted design."""
+    null = np.sort(np.asarray(max_extent, np.int64)[1:])
+    beyond = len(null) - np.searchsorted(null, np.asarray(extent, np.int64), side="left")
+    return ((1 + beyond).astype(np.float64) / np.float64(len(null) + 1)).astype(np.float32)
 
 
 def glm_planes(grid, n_images, device=0):
@@ -481,14 +549,20 @@ def fwe_p(t, max_t, min_t=None, fit=None):
 
 def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=None, value="logjacobian", supports=None, interpolation=1,
               min_count=1, sigma_floor=0.0, region=None, fill=0.0, n_perms=0, seed=0, columns=None, flip=False, two_sided=False,
-              max_planes=None, device=0):
+              max_planes=None, device=0, cluster_threshold=None, connectivity=26):
     """The per-voxel linear model of a registered group (bin/GroupStats).  value "logjacobian" or "jacobian": image i is the
     (log) Jacobian determinant of chains[i] on `grid`, counted where the chain lands inside supports[i] (a geometry, optional)
     and masks[i]; value "images": volumes[i] resliced as in cover_average().  With n_perms > 0 the columns `columns` (default
     those with a non-zero entry in any contrast) are permuted (and with `flip` sign-flipped) n_perms - 1 times by glm_draw(seed),
     row 0 being the design itself.  The device holds slabs of glm_planes() z-planes (at most max_planes); the slabs' extrema are
     combined with max and min, which changes no bit.  Returns a dict: beta, sigma, t, count, fit (bool: the voxel was fit), and
-    with permutations max_t, min_t (n_perms, n_contrasts) and p (n_contrasts,) + shape from fwe_p()."""
+    with permutations max_t, min_t (n_perms, n_contrasts) and p (n_contrasts,) + shape from fwe_p().
+    With cluster_threshold and permutations also the cluster-extent test at `connectivity`: one ClusterSink for the whole grid,
+    filled by every slab.  max_extent uint32 (n_perms, n_contrasts): the largest cluster of t > cluster_threshold under each
+    permutation, with two_sided the larger of that and the largest cluster of t < -cluster_threshold.  clusters int32
+    (n_contrasts,) + shape: the observed map's clusters 1..K, with two_sided the negative side's numbered after the positive
+    side's.  cluster_extent: per contrast the K extents, uint32.  cluster_p float32 (n_contrasts,) + shape: cluster_p() of the
+    voxel's cluster against max_extent, 1 outside every cluster."""
     X = np.ascontiguousarray(design, np.float64)
     c = np.ascontiguousarray(contrasts, np.float64).reshape(-1, X.shape[1])
     n = X.shape[0]
@@ -513,6 +587,7 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
                count=np.empty(shape, np.uint16))
     perm, sign = glm_draw(n, n_perms, seed, True, flip) if n_perms else (None, None)
     hi = lo = None
+    sink = ClusterSink(grid, n_perms, len(c), cluster_threshold, two_sided, connectivity, device) if n_perms and cluster_threshold is not None else None
     for first in range(0, dims[2], planes):
         m = min(planes, dims[2] - first)
         acc = GroupGLM(grid, X, (first, m), device)
@@ -530,7 +605,7 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
             out["beta"][:, sl], out["sigma"][sl], out["t"][:, sl], out["count"][sl] = b, s, t, k
             out.setdefault("fit", np.empty(shape, bool))[sl] = marked != -1
             if n_perms:
-                h, l = acc.permute(c, perm, sign if flip else None, columns, min_count, sigma_floor, r)
+                h, l = acc._permute(sink, 0, c, perm, sign if flip else None, columns, min_count, sigma_floor, r)
                 if hi is None:
                     hi, lo = h, l
                 else:
@@ -540,6 +615,22 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
     if n_perms:
         out["max_t"], out["min_t"] = hi, lo
         out["p"] = np.stack([fwe_p(out["t"][j], hi[:, j], lo[:, j] if two_sided else None, out["fit"]) for j in range(len(c))])
+    if sink is not None:
+        try:
+            out["max_extent"] = sink.finish().max(axis=2)
+            out["clusters"], out["cluster_extent"], out["cluster_p"] = np.zeros((len(c),) + shape, np.int32), [], np.ones((len(c),) + shape, np.float32)
+            for j in range(len(c)):
+                k = 0
+                for side in range(sink.sides):
+                    labels, n = sink.labels(0, j, side)
+                    out["clusters"][j][labels != 0] = labels[labels != 0].astype(np.int32) + k
+                    k += n
+                extent = np.bincount(out["clusters"][j].reshape(-1), minlength=k + 1)[1:].astype(np.uint32)
+                out["cluster_extent"].append(extent)
+                p = np.concatenate([np.ones(1, np.float32), cluster_p(extent, out["max_extent"][:, j])])
+                out["cluster_p"][j] = p[out["clusters"][j]]
+        finally:
+            sink.close()
     return out
 
 

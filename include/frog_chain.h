@@ -667,6 +667,57 @@ int  frog_glm_permute(frog_glm *a, uint32_t n_contrasts, const double *contrasts
 int  frog_glm_draw(uint32_t n, uint32_t n_perms, uint64_t seed, int shuffle, int flip, uint32_t *perm, int8_t *sign);
 void frog_glm_destroy(frog_glm *a);
 
+/* ---- connected components and the cluster-extent test (an extension; the reference has no counterpart) --------------------------
+ * A MASK is a set of voxels of a 3-D grid, x fastest.  Two set voxels are neighbours at connectivity 6 when they share a face
+ * (|dx| + |dy| + |dz| == 1), at 18 when they share a face or an edge (max(|dx|, |dy|, |dz|) == 1 and the sum <= 2), at 26 when
+ * max(|dx|, |dy|, |dz|) == 1; a COMPONENT is a class of the transitive closure.  The last voxel of a row and the first of the
+ * next are no neighbours: adjacency is of coordinates, not of indices.
+ *   root(v)   = the smallest linear index x + nx * (y + ny * z) of v's component
+ *   extent    = the number of voxels of a component
+ *   label(v)  = 1 + #{roots below root(v)} at a set voxel, 0 elsewhere: 1..K in ascending order of root
+ * Every result is an integer and exact: it does not depend on scheduling (integer atomic minimum, sum and maximum only).
+ *
+ * frog_components: the mask is the non-zero voxels of an integer volume with host data.  labels (u32, grid-sized),
+ * n_components (K) and largest (the largest extent, 0 for an empty mask) may each be NULL, not all.
+ *
+ * frog_clusters, the SINK of a permutation test: on the device, for the whole grid, one bit mask per SLOT (permutation,
+ * contrast, side), slot = (perm * n_contrasts + contrast) * sides + side, sides = 2 with two_sided and 1 without, all empty
+ * at first.  Side 0 is the positive side, side 1 the negative.
+ *   frog_glm_permute_clusters does what frog_glm_permute does with the same arguments; max_t and min_t (either or both may be
+ *     NULL here) are bit for bit frog_glm_permute's.  For row k of the call and contrast c it also sets, in the slots of
+ *     permutation first_perm + k, the bit of every window voxel at the voxel's index in the whole grid, where the voxel is
+ *     fit under that permutation and its t is not the NaN -- the voxels the extrema are taken over -- and
+ *         side 0:  t > threshold            side 1:  t < -threshold          (f32 comparisons on that t)
+ *     Windows that partition the grid fill one mask between them, so a cluster that crosses a window boundary is one
+ *     cluster.  The sink counts the z-planes each permutation has received: a plane written twice is FROG_E_STATE (nothing
+ *     is computed then).
+ *   frog_clusters_finish: max_extent[slot] = the largest extent of the slot's mask at the sink's connectivity, 0 for an empty
+ *     mask.  FROG_E_STATE unless every permutation has received every plane of the grid.
+ *   frog_clusters_mask: one slot as bytes (0 or 1), grid-sized.
+ *   frog_clusters_labels: one slot's labels as frog_components gives them (n_components may be NULL).  FROG_E_STATE unless the
+ *     permutation has received every plane.
+ * Device memory: slots * ceil(voxels / 32) words for the masks, and 8 bytes per voxel for each of the masks that are labelled
+ * in one launch (at most 64, fewer where memory is short).  FROG_E_NOMEM, with the bytes needed and the bytes free in the
+ * message, when the masks and the workspace of one mask do not fit.
+ *
+ * FROG_E_INVALID, before the device is touched: a NULL argument that is not marked optional, a grid that is empty or above 2^31
+ * voxels, a connectivity other than 6, 18 or 26, a threshold that is negative or not finite, n_perms == 0, n_contrasts == 0 or
+ * > FROG_GLM_MAX_CONTRASTS, a float mask volume or one without data, everything frog_glm_permute refuses, a sink whose grid
+ * dims, device or n_contrasts differ from the accumulator's and the call's, first_perm + n_perms beyond the sink's n_perms,
+ * a permutation, contrast or side that the sink does not have. */
+int  frog_components(const frog_volume *mask, int connectivity, int device, uint32_t *labels, uint32_t *n_components, uint64_t *largest);
+
+typedef struct frog_clusters frog_clusters;
+int  frog_clusters_create(const frog_volume *grid, uint32_t n_perms, uint32_t n_contrasts, int two_sided, float threshold,
+                          int connectivity, int device, frog_clusters **out);
+int  frog_glm_permute_clusters(frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                               const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
+                               uint32_t first_perm, frog_clusters *sink, float *max_t, float *min_t);
+int  frog_clusters_finish(frog_clusters *s, uint32_t *max_extent);
+int  frog_clusters_mask(frog_clusters *s, uint32_t perm, uint32_t contrast, int side, uint8_t *mask);
+int  frog_clusters_labels(frog_clusters *s, uint32_t perm, uint32_t contrast, int side, uint32_t *labels, uint32_t *n_components);
+void frog_clusters_destroy(frog_clusters *s);
+
 #ifdef __cplusplus
 }
 #endif
