@@ -335,6 +335,15 @@ HIP_SYMBOLS = {
     "frog_clusters_mask": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]),
     "frog_clusters_labels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, c_u32_p, c_u32_p]),
     "frog_clusters_destroy": (None, [C.c_void_p]),
+    "frog_tfce_volume": (C.c_int, [C.POINTER(FrogVolume), C.c_int, C.c_float, C.c_double, C.c_double, C.c_int, C.c_int, c_float_p, c_float_p]),
+    "frog_tfce_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_double, C.c_double, C.c_int, C.c_int,
+                                   C.POINTER(C.c_void_p)]),
+    "frog_glm_permute_tfce": (C.c_int, [C.c_void_p, C.c_uint32, c_double_p, C.c_uint32, C.c_double, C.POINTER(C.c_uint8), C.c_uint32,
+                                        C.c_uint32, c_u32_p, C.POINTER(C.c_int8), C.c_uint32, C.c_void_p, c_float_p, c_float_p]),
+    "frog_tfce_finish": (C.c_int, [C.c_void_p, c_float_p]),
+    "frog_tfce_levels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]),
+    "frog_tfce_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, c_float_p]),
+    "frog_tfce_destroy": (None, [C.c_void_p]),
     "frog_labels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_labels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
     "frog_labels_finish": (C.c_int, [C.c_void_p, c_u32_p]),

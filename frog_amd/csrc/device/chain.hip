@@ -1048,6 +1048,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 #include "k_joint.hip.h"
 #include "k_glm.hip.h"
 #include "k_ccl.hip.h"
+#include "k_tfce.hip.h"
 
 } // namespace
 
@@ -1105,16 +1106,40 @@ struct frog_glm : frog_windowed {
     frog::DevBuf<double> d_design, d_table;         // d_table: the design rows of one launch's permutations, grown on demand
 };
 
-// the supra-threshold voxels of every permutation, contrast and side of a permutation test on one grid, as bit masks, and the
-// workspace that labels their connected components
-struct frog_clusters : frog_group {
+// what the sinks of a permutation test hold alike (frog_clusters, frog_tfce): one slot per permutation, contrast and side for
+// the whole grid, and which planes of it each permutation has received
+struct frog_sink : frog_group {
     uint32_t n_perms = 0, n_contrasts = 0, sides = 1;
-    float threshold = 0;
     CclGrid ccl{};
-    size_t slots = 0;                               // n_perms * n_contrasts * sides masks of ccl.words words
-    uint32_t batch = 0;                             // the masks one launch labels: the workspace holds that many
-    frog::DevBuf<uint32_t> d_bits, d_parent, d_extent, d_stats;
+    size_t slots = 0;                               // n_perms * n_contrasts * sides
+    uint32_t batch = 0;                             // the slots one launch labels: the workspace holds that many
     std::vector<uint8_t> received;                  // [perm * nz + z]: the plane has been written for the permutation's slots
+};
+
+// the supra-threshold voxels of every permutation, contrast and side of a permutation test on one grid, as bit masks of
+// ccl.words words, and the workspace that labels their connected components
+struct frog_clusters : frog_sink {
+    float threshold = 0;
+    frog::DevBuf<uint32_t> d_bits, d_parent, d_extent, d_stats;
+};
+
+// the levels of every permutation, contrast and side of a permutation test on one grid, one byte per voxel and `stride`
+// bytes per slot (k_tfce.hip.h), and the workspace that enhances a batch of them
+struct TfceWork {
+    frog::DevBuf<uint32_t> d_bits, d_parent, d_extent;      // of `batch` slots: k_ccl.hip.h's masks and workspace
+    frog::DevBuf<double> d_acc;                             // of `batch` slots: one sum per voxel
+};
+struct TfceParams {
+    float dh = 0;
+    bool root = true;                               // E == 0.5
+    double weight[256] = {};                        // w_k; weight[0] is not used
+};
+struct frog_tfce : frog_sink {
+    TfceParams par;
+    size_t stride = 0;
+    frog::DevBuf<uint8_t> d_levels;
+    frog::DevBuf<uint32_t> d_top, d_best;           // per slot: the highest level, the bits of the largest tfce
+    TfceWork work;
 };
 
 // The label table of frog_labels, frog_wlabels (and through it frog_jlabels) and frog_staple: the device hash map in which
@@ -2082,18 +2107,25 @@ int glm_fit_arguments(const char *where, const frog_glm *a, uint32_t n_contrasts
 }
 
 // The fit kernel over the window for the n_perms permutations whose rows d_table holds: instantiated on the number of columns
-// and on whether the values of a voxel stay in LDS.  With a sink, the kernel that also stores the bits.
+// and on whether the values of a voxel stay in LDS.  With a sink, the kernel that also stores the bits or the levels.
+struct GlmSinks {
+    const GlmSink *bits = nullptr;
+    const GlmLevelSink *levels = nullptr;           // at most one of the two
+};
+
 template <int P, bool LDS>
-hipError_t glm_fit_go(const frog_glm *a, const GlmArgs &f, const GlmSink *sink, size_t bytes)
+hipError_t glm_fit_go(const frog_glm *a, const GlmArgs &f, const GlmSinks &to, size_t bytes)
 {
+    const GlmSink *const sink = to.bits;
     // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
     return chunked_launch(f.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
         if (sink) glm_fit_kernel<P, LDS, GlmSink><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f, *sink);
+        else if (to.levels) glm_fit_kernel<P, LDS, GlmLevelSink><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f, *to.levels);
         else glm_fit_kernel<P, LDS><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f);
     });
 }
 
-hipError_t glm_fit_launch(const frog_glm *a, const GlmArgs &f, const GlmSink *sink = nullptr)
+hipError_t glm_fit_launch(const frog_glm *a, const GlmArgs &f, const GlmSinks &sink = GlmSinks{})
 {
     const bool lds = a->n_images <= GLM_LDS_MAX;
     const size_t bytes = (f.extrema ? (size_t)f.n_perms * f.n_contrasts * 2 * sizeof(uint32_t) : 0) + (lds ? (size_t)a->n_images * 256 * sizeof(float) : 0);
@@ -2149,12 +2181,13 @@ int glm_fit_args(const char *where, frog_glm *a, uint32_t n_contrasts, const dou
     return FROG_OK;
 }
 
-// frog_glm_permute (sink null) and frog_glm_permute_clusters: the validation, the table batches and the launches, which with
-// a sink store the bits of row k in the sink's permutation first_perm + k
+// frog_glm_permute (no sink), frog_glm_permute_clusters and frog_glm_permute_tfce (one sink): the validation, the table batches
+// and the launches, which with a sink store the bits or the levels of row k in the sink's permutation first_perm + k
 int glm_permute(const char *where, frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
                 const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign, uint32_t first_perm,
-                frog_clusters *sink, float *max_t, float *min_t)
+                frog_clusters *clusters, frog_tfce *tfce, float *max_t, float *min_t)
 {
+    frog_sink *const sink = clusters ? static_cast<frog_sink *>(clusters) : tfce;
     const std::string w = std::string(where) + ": ";
     if (int rc = glm_fit_arguments(where, a, n_contrasts, contrasts, min_count, sigma_floor)) return rc;
     if (!n_contrasts || !n_perms || !perm || (!sink && !max_t && !min_t)) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
@@ -2201,8 +2234,9 @@ int glm_permute(const char *where, frog_glm *a, uint32_t n_contrasts, const doub
         e = glm_table_launch(a, d_perm.p + at, sign ? d_sign.p + at : nullptr, columns, nb);
         f.n_perms = nb;
         f.extrema = d_ext.p + (size_t)k0 * n_contrasts * 2;
-        const GlmSink to = sink ? GlmSink{ sink->d_bits.p, sink->ccl.words, a->first, first_perm + k0, sink->sides, sink->threshold } : GlmSink{};
-        if (e == hipSuccess) e = glm_fit_launch(a, f, sink ? &to : nullptr);
+        const GlmSink bits = clusters ? GlmSink{ clusters->d_bits.p, clusters->ccl.words, a->first, first_perm + k0, clusters->sides, clusters->threshold } : GlmSink{};
+        const GlmLevelSink levels = tfce ? GlmLevelSink{ tfce->d_levels.p, tfce->stride, a->first, first_perm + k0, tfce->sides, tfce->par.dh } : GlmLevelSink{};
+        if (e == hipSuccess) e = glm_fit_launch(a, f, GlmSinks{ clusters ? &bits : nullptr, tfce ? &levels : nullptr });
     }
     if (e == hipSuccess) e = hipMemcpy(ext.data(), d_ext.p, n_ext * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(where, e);
@@ -2267,8 +2301,8 @@ hipError_t ccl_labels_out(const CclGrid &g, const uint32_t *d_mask, const uint32
     return hipSuccess;
 }
 
-// what frog_clusters_mask and frog_clusters_labels refuse alike; the slot's index through `slot`
-int clusters_slot(const char *where, const frog_clusters *s, uint32_t perm, uint32_t contrast, int side, const void *out, size_t *slot)
+// what frog_clusters_mask, frog_clusters_labels, frog_tfce_levels and frog_tfce_map refuse alike; the slot's index through `slot`
+int clusters_slot(const char *where, const frog_sink *s, uint32_t perm, uint32_t contrast, int side, const void *out, size_t *slot)
 {
     if (!s || !out) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
     if (perm >= s->n_perms || contrast >= s->n_contrasts || side < 0 || (uint32_t)side >= s->sides)
@@ -2278,11 +2312,78 @@ int clusters_slot(const char *where, const frog_clusters *s, uint32_t perm, uint
 }
 
 // whether every z-plane of permutations [first, first + count) has been written
-bool clusters_complete(const frog_clusters *s, uint32_t first, uint32_t count)
+bool clusters_complete(const frog_sink *s, uint32_t first, uint32_t count)
 {
     const size_t depth = s->grid.dims[2];
     return std::find(s->received.begin() + first * depth, s->received.begin() + ((size_t)first + count) * depth, (uint8_t)0)
            == s->received.begin() + ((size_t)first + count) * depth;
+}
+
+// ---- threshold-free cluster enhancement (k_tfce.hip.h) ---------------------------------------------------------------------------
+
+// what frog_tfce_create and frog_tfce_volume refuse alike, and the level weights w_k as the header states them
+int tfce_params(const char *where, float dh, double E, double H, int connectivity, TfceParams *par)
+{
+    const std::string w = std::string(where) + ": ";
+    if (!(dh > 0.0f) || !std::isfinite(dh)) return fail(FROG_E_INVALID, w + "dh must be finite and above 0");
+    if (E != 0.5 && E != 1.0) return fail(FROG_E_INVALID, w + "E is 0.5 or 1");
+    if (H != 1.0 && H != 2.0) return fail(FROG_E_INVALID, w + "H is 1 or 2");
+    if (!ccl_order(connectivity)) return fail(FROG_E_INVALID, w + "connectivity 6, 18 or 26");
+    par->dh = dh;
+    par->root = E == 0.5;
+    for (int k = 1; k <= 255; k++) {
+        const double h = (double)k * (double)dh;
+        const double hh = H == 2.0 ? h * h : h;
+        par->weight[k] = hh * (double)dh;
+    }
+    return FROG_OK;
+}
+
+size_t tfce_stride(const CclGrid &g) { return g.words * 32; }
+
+// device bytes of one slot's workspace: parent, extent, the f64 sum, the bit mask
+size_t tfce_work_bytes(const CclGrid &g) { return g.total * (2 * sizeof(uint32_t) + sizeof(double)) + g.words * sizeof(uint32_t); }
+
+hipError_t tfce_work_alloc(TfceWork &work, const CclGrid &g, size_t n)
+{
+    hipError_t e = work.d_bits.alloc(n * g.words);
+    if (e == hipSuccess) e = work.d_parent.alloc(n * g.total);
+    if (e == hipSuccess) e = work.d_extent.alloc(n * g.total);
+    if (e == hipSuccess) e = work.d_acc.alloc(n * g.total);
+    return e;
+}
+
+// The enhancement of the n slots whose levels lie `stride` apart from d_levels on, n at most the workspace's slots: d_top[slot]
+// their highest levels, d_best[slot] the bits of their largest tfce, and with d_map (n == 1) the map.  The one device routine
+// of frog_tfce_finish, frog_tfce_map and frog_tfce_volume.
+hipError_t tfce_enhance(const CclGrid &g, const TfceParams &par, const uint8_t *d_levels, size_t stride, uint32_t n, TfceWork &work,
+                        uint32_t *d_top, float *d_map, uint32_t *d_best)
+{
+    std::vector<uint32_t> top(n);
+    hipError_t e = hipMemset(d_top, 0, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(d_best, 0, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = chunked_launch(g.words, [&](unsigned blocks, size_t base) {
+        tfce_top_kernel<<<dim3(blocks, n), LAUNCH_BLOCK>>>(base, d_levels, stride, g.words, d_top);
+    });
+    if (e == hipSuccess) e = hipMemcpy(top.data(), d_top, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemset(work.d_acc.p, 0, (size_t)n * g.total * sizeof(double));
+    const uint32_t highest = e == hipSuccess ? *std::max_element(top.begin(), top.end()) : 0u;
+    for (uint32_t k = highest; k >= 1 && e == hipSuccess; k--) {
+        e = chunked_launch(g.words, [&](unsigned blocks, size_t base) {
+            tfce_mask_kernel<<<dim3(blocks, n), LAUNCH_BLOCK>>>(base, d_levels, stride, g.words, d_top, k, work.d_bits.p);
+        });
+        if (e == hipSuccess) e = ccl_label(g, work.d_bits.p, n, work.d_parent.p, work.d_extent.p, nullptr);
+        if (e == hipSuccess) e = chunked_launch(g.words, [&](unsigned blocks, size_t base) {
+            if (par.root)
+                tfce_accumulate_kernel<true><<<dim3(blocks, n), LAUNCH_BLOCK>>>(base, work.d_bits.p, g, work.d_parent.p, work.d_extent.p, par.weight[k], work.d_acc.p);
+            else
+                tfce_accumulate_kernel<false><<<dim3(blocks, n), LAUNCH_BLOCK>>>(base, work.d_bits.p, g, work.d_parent.p, work.d_extent.p, par.weight[k], work.d_acc.p);
+        });
+    }
+    if (e == hipSuccess) e = chunked_launch(g.total, [&](unsigned blocks, size_t base) {
+        tfce_round_kernel<<<dim3(blocks, n), LAUNCH_BLOCK>>>(base, work.d_acc.p, g.total, d_map, d_best);
+    });
+    return e;
 }
 
 template <class S>
@@ -3040,7 +3141,7 @@ int frog_glm_permute(frog_glm *a, uint32_t n_contrasts, const double *contrasts,
                      const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
                      float *max_t, float *min_t)
 {
-    return glm_permute("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, 0, nullptr, max_t, min_t);
+    return glm_permute("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, 0, nullptr, nullptr, max_t, min_t);
 }
 
 int frog_glm_draw(uint32_t n, uint32_t n_perms, uint64_t seed, int shuffle, int flip, uint32_t *perm, int8_t *sign)
@@ -3138,7 +3239,7 @@ int frog_glm_permute_clusters(frog_glm *a, uint32_t n_contrasts, const double *c
 {
     if (!sink) return fail(FROG_E_INVALID, "bad arguments to frog_glm_permute_clusters");
     return glm_permute("frog_glm_permute_clusters", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, first_perm,
-                       sink, max_t, min_t);
+                       sink, nullptr, max_t, min_t);
 }
 
 int frog_clusters_finish(frog_clusters *s, uint32_t *max_extent)
@@ -3189,6 +3290,126 @@ int frog_clusters_labels(frog_clusters *s, uint32_t perm, uint32_t contrast, int
 }
 
 void frog_clusters_destroy(frog_clusters *s) { group_destroy(s); }
+
+int frog_tfce_create(const frog_volume *grid, uint32_t n_perms, uint32_t n_contrasts, int two_sided, float dh, double E, double H,
+                     int connectivity, int device, frog_tfce **out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_tfce_create", grid, out, &total)) return rc;
+    if (!n_perms || !n_contrasts) return fail(FROG_E_INVALID, "frog_tfce_create: at least one permutation and one contrast");
+    if (n_contrasts > FROG_GLM_MAX_CONTRASTS) return fail(FROG_E_INVALID, "frog_tfce_create: at most " + std::to_string(FROG_GLM_MAX_CONTRASTS) + " contrasts");
+    TfceParams par;
+    if (int rc = tfce_params("frog_tfce_create", dh, E, H, connectivity, &par)) return rc;
+    std::unique_ptr<frog_tfce> s;
+    if (int rc = group_new(grid, total, device, s)) return rc;
+    s->n_perms = n_perms;
+    s->n_contrasts = n_contrasts;
+    s->sides = two_sided ? 2u : 1u;
+    s->par = par;
+    s->ccl = ccl_grid(grid, total, connectivity);
+    s->stride = tfce_stride(s->ccl);
+    s->slots = (size_t)n_perms * n_contrasts * s->sides;
+    // the levels, and the workspace for as many slots of a launch as fit, up to CCL_BATCH
+    size_t free_bytes = 0, device_bytes = 0;
+    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
+    const size_t per_slot = s->stride + 2 * sizeof(uint32_t), work_bytes = tfce_work_bytes(s->ccl);
+    const bool countable = s->slots <= (std::numeric_limits<size_t>::max() - work_bytes) / per_slot;
+    const size_t level_bytes = countable ? s->slots * per_slot : 0;
+    if (!countable || level_bytes + work_bytes > free_bytes)
+        return fail(FROG_E_NOMEM, "frog_tfce_create: " + std::to_string(s->slots) + " level maps and the workspace need " +
+                                  (countable ? std::to_string(level_bytes + work_bytes) : std::string("more than 2^64")) + " bytes of device memory, " +
+                                  std::to_string(free_bytes) + " are free");
+    s->batch = (uint32_t)std::min<size_t>(std::min<size_t>(s->slots, CCL_BATCH), std::max<size_t>(1, (free_bytes - level_bytes) / 2 / work_bytes));
+    KCHECK(s->d_levels.alloc(s->slots * s->stride));
+    KCHECK(s->d_top.alloc(s->slots));
+    KCHECK(s->d_best.alloc(s->slots));
+    KCHECK(tfce_work_alloc(s->work, s->ccl, s->batch));
+    KCHECK(hipMemset(s->d_levels.p, 0, s->d_levels.bytes()));
+    s->received.assign((size_t)n_perms * grid->dims[2], 0);
+    *out = s.release();
+    return FROG_OK;
+}
+
+int frog_glm_permute_tfce(frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                          const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
+                          uint32_t first_perm, frog_tfce *sink, float *max_t, float *min_t)
+{
+    if (!sink) return fail(FROG_E_INVALID, "bad arguments to frog_glm_permute_tfce");
+    return glm_permute("frog_glm_permute_tfce", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, first_perm,
+                       nullptr, sink, max_t, min_t);
+}
+
+int frog_tfce_finish(frog_tfce *s, float *max_tfce)
+{
+    if (!s || !max_tfce) return fail(FROG_E_INVALID, "bad arguments to frog_tfce_finish");
+    if (!clusters_complete(s, 0, s->n_perms)) return fail(FROG_E_STATE, "frog_tfce_finish: a permutation has not received every plane of the grid");
+    KCHECK(hipSetDevice(s->device));
+    hipError_t e = hipSuccess;
+    for (size_t at = 0; at < s->slots && e == hipSuccess; at += s->batch)
+        e = tfce_enhance(s->ccl, s->par, s->d_levels.p + at * s->stride, s->stride, (uint32_t)std::min<size_t>(s->batch, s->slots - at), s->work,
+                         s->d_top.p + at, nullptr, s->d_best.p + at);
+    if (e == hipSuccess) e = hipMemcpy(max_tfce, s->d_best.p, s->slots * sizeof(float), hipMemcpyDeviceToHost);    // the bits of f32 values
+    if (e != hipSuccess) return hip_fail("frog_tfce_finish", e);
+    return FROG_OK;
+}
+
+int frog_tfce_levels(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, uint8_t *levels)
+{
+    size_t slot;
+    if (int rc = clusters_slot("frog_tfce_levels", s, perm, contrast, side, levels, &slot)) return rc;
+    KCHECK(hipSetDevice(s->device));
+    KCHECK(hipMemcpy(levels, s->d_levels.p + slot * s->stride, s->total, hipMemcpyDeviceToHost));
+    return FROG_OK;
+}
+
+int frog_tfce_map(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, float *tfce)
+{
+    size_t slot;
+    if (int rc = clusters_slot("frog_tfce_map", s, perm, contrast, side, tfce, &slot)) return rc;
+    if (!clusters_complete(s, perm, 1)) return fail(FROG_E_STATE, "frog_tfce_map: the permutation has not received every plane of the grid");
+    KCHECK(hipSetDevice(s->device));
+    frog::DevBuf<float> d_map;
+    KCHECK(d_map.alloc(s->total));
+    hipError_t e = tfce_enhance(s->ccl, s->par, s->d_levels.p + slot * s->stride, s->stride, 1, s->work, s->d_top.p + slot, d_map.p, s->d_best.p + slot);
+    if (e == hipSuccess) e = hipMemcpy(tfce, d_map.p, s->total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_tfce_map", e);
+    return FROG_OK;
+}
+
+void frog_tfce_destroy(frog_tfce *s) { group_destroy(s); }
+
+int frog_tfce_volume(const frog_volume *stat, int side, float dh, double E, double H, int connectivity, int device, float *tfce, float *max)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_tfce_volume", stat, stat, &total)) return rc;
+    if (!tfce && !max) return fail(FROG_E_INVALID, "frog_tfce_volume: no output asked for");
+    if (!stat->data) return fail(FROG_E_INVALID, "frog_tfce_volume: a volume without voxels");
+    if (stat->dtype != FROG_V_F32) return fail(FROG_E_INVALID, "frog_tfce_volume: the volume has type FROG_V_F32");
+    if (side != 0 && side != 1) return fail(FROG_E_INVALID, "frog_tfce_volume: side 0 or 1");
+    TfceParams par;
+    if (int rc = tfce_params("frog_tfce_volume", dh, E, H, connectivity, &par)) return rc;
+    const CclGrid g = ccl_grid(stat, total, connectivity);
+    if (int rc = select_device(device)) return rc;
+    frog::DevBuf<float> d_stat, d_map;
+    frog::DevBuf<uint8_t> d_levels;
+    frog::DevBuf<uint32_t> d_slot;                  // the highest level, the bits of the largest tfce
+    TfceWork work;
+    KCHECK(d_stat.alloc(total));
+    KCHECK(d_map.alloc(total));
+    KCHECK(d_levels.alloc(tfce_stride(g)));
+    KCHECK(d_slot.alloc(2));
+    KCHECK(tfce_work_alloc(work, g, 1));
+    hipError_t e = hipMemcpy(d_stat.p, stat->data, total * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_levels.p, 0, d_levels.bytes());
+    if (e == hipSuccess) e = chunked_launch(total, [&](unsigned blocks, size_t base) {
+        tfce_levels_kernel<<<blocks, LAUNCH_BLOCK>>>(base, d_stat.p, total, (uint32_t)side, dh, d_levels.p);
+    });
+    if (e == hipSuccess) e = tfce_enhance(g, par, d_levels.p, tfce_stride(g), 1, work, d_slot.p, d_map.p, d_slot.p + 1);
+    if (e == hipSuccess && tfce) e = hipMemcpy(tfce, d_map.p, total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && max) e = hipMemcpy(max, d_slot.p + 1, sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_tfce_volume", e);
+    return FROG_OK;
+}
 
 int frog_labels_create(const frog_volume *grid, uint32_t n_images, uint32_t max_labels, int device, frog_labels **out)
 {

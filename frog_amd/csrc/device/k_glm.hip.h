@@ -288,6 +288,27 @@ struct GlmSink {
 };
 __device__ __forceinline__ const GlmSink &glm_the_sink(const GlmSink &sink) { return sink; }
 
+// where glm_fit_kernel stores the levels of the voxels: the level maps of a frog_tfce (k_tfce.hip.h states their layout and
+// the level of a statistic, glm_level below restates it), slot (permutation, contrast, side) at levels + slot * stride
+struct GlmLevelSink {
+    uint8_t *levels;
+    size_t stride;
+    size_t first;                                   // the window's first voxel in the grid
+    uint32_t perm0;                                 // the sink's permutation of the launch's first
+    uint32_t sides;
+    float dh;
+};
+__device__ __forceinline__ const GlmLevelSink &glm_the_sink(const GlmLevelSink &sink) { return sink; }
+
+// trunc(s / dh) saturated at 255 for s = t (side 0) or -t (side 1), 0 where s is not positive: one f64 division
+__device__ __forceinline__ uint8_t glm_level(float t, uint32_t side, float dh)
+{
+    const float s = side ? -t : t;
+    if (!(s > 0.0f)) return 0;
+    const double q = (double)s / (double)dh;
+    return q >= 255.0 ? (uint8_t)255 : (uint8_t)q;
+}
+
 // The bits of the wavefront's 64 consecutive voxels, the first at grid index g0, into `mask`: the ballot shifted to g0's place
 // in its word spans up to three words, which lanes 0 to 2 OR in where they are not zero.  A word past the mask's end would
 // hold bits of voxels past the grid's, which are never on.  Every lane of the wavefront must be active.
@@ -305,7 +326,8 @@ __device__ __forceinline__ void glm_sink_store(uint32_t *mask, size_t g0, bool o
 // Dynamic LDS: 2 n_perms n_contrasts keys where extrema are wanted, then with LDS 256 n floats.
 // Sink is empty (finish and frog_glm_permute: the kernel takes no further argument) or one GlmSink (frog_glm_permute_clusters),
 // with which the kernel also sets the bit of every voxel that counts towards an extremum and lies beyond the threshold, in the
-// sink's mask of its permutation, contrast and side, at the voxel's index in the whole grid.
+// sink's mask of its permutation, contrast and side, at the voxel's index in the whole grid; or one GlmLevelSink
+// (frog_glm_permute_tfce), with which it stores there, one byte per voxel, that voxel's level on each side instead.
 template <int P, bool LDS, class... Sink>
 __global__ __launch_bounds__(256) void glm_fit_kernel(size_t base, const float *__restrict__ vals, const double *__restrict__ table, const GlmArgs a,
                                                       const Sink... sink)
@@ -372,13 +394,22 @@ __global__ __launch_bounds__(256) void glm_fit_kernel(size_t base, const float *
                     atomicMax(&ext[(kk * C + c) * 2u], hi);
                     atomicMin(&ext[(kk * C + c) * 2u + 1u], lo);
                 }
-                if constexpr (sizeof...(Sink) != 0) {
+                if constexpr ((std::is_same_v<Sink, GlmSink> || ...)) {
                     // f32 comparisons on the t the extrema are taken over; side 0 above the threshold, side 1 below its negative
                     const GlmSink &to = glm_the_sink(sink...);
                     uint32_t *const mask = to.bits + ((size_t)(to.perm0 + kk) * C + c) * to.sides * to.words;
                     const size_t g0 = to.first + w0 + (tid & ~63u);
                     glm_sink_store(mask, g0, counts && t > to.threshold);
                     if (to.sides == 2u) glm_sink_store(mask + to.words, g0, counts && t < -to.threshold);
+                }
+                if constexpr ((std::is_same_v<Sink, GlmLevelSink> || ...)) {
+                    // every window voxel's own byte: its level where it counts, 0 where it does not
+                    const GlmLevelSink &to = glm_the_sink(sink...);
+                    uint8_t *const level = to.levels + ((size_t)(to.perm0 + kk) * C + c) * to.sides * to.stride + to.first + w;
+                    if (live) {
+                        level[0] = counts ? glm_level(t, 0u, to.dh) : (uint8_t)0;
+                        if (to.sides == 2u) level[to.stride] = counts ? glm_level(t, 1u, to.dh) : (uint8_t)0;
+                    }
                 }
             }
         }

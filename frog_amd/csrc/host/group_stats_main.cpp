@@ -3,7 +3,8 @@
 // over all voxels (frog_glm, include/frog_chain.h, which states the arithmetic).
 //   GroupStats bbox.json spacing design.csv [-c contrasts.csv] [-td transformsDir] [-o outDir] [-v jacobian|logjacobian|images]
 //              [-vl volumes.txt] [-ml masks.txt] [-m regionMask] [-mc minCount] [-sf sigmaFloor] [-f fill] [-np nPerms]
-//              [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-rp planes] [-dev n]
+//              [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-tf 1] [-tfd dh] [-tfe 0.5|1] [-tfh 1|2]
+//              [-rp planes] [-dev n]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid).  design.csv has one row per image and one column per regressor,
 // numbers separated by commas or blanks, after an optional header line; row i belongs to <transformsDir>/<i>.json (default
 // "transforms"), which is inverted as AverageImage inverts it.  -c: one contrast per row, as many numbers as the design has
@@ -23,7 +24,7 @@
 // -two 1 compares |t| with max(max_t, -min_t).  maxt.csv: permutation,contrast,max,min as %.9g.  threshold_p05 is the largest
 // null maximum a t must exceed for p < 0.05 (inf where no count of exceedances gives that), voxels_p05 the voxels that do.
 // -ct threshold (needs -np): the cluster-extent test (frog_clusters).  The voxels with t > threshold, and with -two 1 also
-// those with t < -threshold, form clusters at connectivity -cc (default 26: faces, edges and corners; needs -ct); a cluster's
+// those with t < -threshold, form clusters at connectivity -cc (default 26: faces, edges and corners; needs -ct or -tf); a cluster's
 // p is (float)((1 + #{k >= 1 : extent[k][c] >= its voxels}) / (double)nPerms), extent[k][c] the largest cluster under
 // permutation k, with -two 1 the larger of the two sides'.  clusters_<c>.nii.gz (INT32): the observed map's clusters 1..K in
 // ascending order of their smallest voxel index, the negative side's after the positive side's.  cluster_p_<c>.nii.gz
@@ -31,6 +32,15 @@
 // peak_z,p_fwe, the peak the largest |t| of the cluster, the smallest index among equals.  maxextent.csv:
 // permutation,contrast,extent.  One sink on the device holds every permutation's masks for the whole grid, so a cluster that
 // crosses slabs is one cluster; if it does not fit, the tool says how many bytes it needs and stops before the first output.
+// -tf 1 (needs -np): threshold-free cluster enhancement (frog_tfce), which needs no cluster-forming threshold.  A voxel's t
+// becomes the sum, over the levels k * dh (-tfd, default 0.1) up to its own, of extent^E * height^H * dh, extent the voxels of
+// its cluster at that level at connectivity -cc, E = -tfe (0.5 or 1, default 0.5), H = -tfh (1 or 2, default 2); a t beyond
+// 255 * dh counts as 255 * dh.  tfce_<c>.nii.gz (FLOAT32): the observed enhanced map, with -two 1 the negative side's values
+// negated.  tfce_p_<c>.nii.gz = (float)((1 + #{k >= 1 : max_tfce[k][c] >= |tfce|}) / (double)nPerms), 1 where tfce is 0,
+// max_tfce[k][c] the largest enhanced value under permutation k, with -two 1 the larger of the two sides'.  maxtfce.csv:
+// permutation,contrast,max_tfce.  tfce.csv: contrast,peak_tfce,peak_x,peak_y,peak_z,threshold_p05,voxels_p05, as in glm.csv.
+// One sink on the device holds every permutation's levels for the whole grid, one byte per voxel; if it does not fit, the tool
+// says how many bytes it needs and stops before the first output.  -tf and -ct may be given together.
 // The device holds slabs of frog_glm_planes z-planes, or -rp planes if that is fewer; the slab count is printed and changes no
 // bit of any file.  Every input is checked before anything is written.
 #include "group_tool.h"
@@ -107,10 +117,11 @@ int main(int argc, char *argv[])
     int device = 0, flips = 0, twoSided = 0, connectivity = 26;
     long minCount = 1, nPerms = 0, planesOption = 0;
     unsigned long long seed = 0;
-    double sigmaFloor = 0, clusterThreshold = 0;
+    double sigmaFloor = 0, clusterThreshold = 0, tfceStep = 0.1, tfceE = 0.5, tfceH = 2;
     float fill = 0;
-    bool planesGiven = false, permOption = false, clusterTest = false, connectivityGiven = false;
-    int a = positional_arguments(argc, argv, 1, { "-c", "-td", "-o", "-v", "-vl", "-ml", "-m", "-mc", "-sf", "-f", "-np", "-ps", "-pc", "-pf", "-two", "-ct", "-cc", "-rp", "-dev" },
+    bool planesGiven = false, permOption = false, clusterTest = false, connectivityGiven = false, tfceOption = false;
+    int tfceTest = 0;
+    int a = positional_arguments(argc, argv, 1, { "-c", "-td", "-o", "-v", "-vl", "-ml", "-m", "-mc", "-sf", "-f", "-np", "-ps", "-pc", "-pf", "-two", "-ct", "-cc", "-tf", "-tfd", "-tfe", "-tfh", "-rp", "-dev" },
                                  positional);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
@@ -131,6 +142,10 @@ int main(int argc, char *argv[])
         else if (std::strcmp(key, "-two") == 0) { twoSided = atoi(value); permOption = true; }
         else if (std::strcmp(key, "-ct") == 0) { clusterThreshold = atof(value); clusterTest = true; }
         else if (std::strcmp(key, "-cc") == 0) { connectivity = atoi(value); connectivityGiven = true; }
+        else if (std::strcmp(key, "-tf") == 0) tfceTest = atoi(value);
+        else if (std::strcmp(key, "-tfd") == 0) { tfceStep = atof(value); tfceOption = true; }
+        else if (std::strcmp(key, "-tfe") == 0) { tfceE = atof(value); tfceOption = true; }
+        else if (std::strcmp(key, "-tfh") == 0) { tfceH = atof(value); tfceOption = true; }
         else if (std::strcmp(key, "-rp") == 0) { planesOption = atol(value); planesGiven = true; }
         else if (std::strcmp(key, "-dev") == 0) device = atoi(value);
         else die(std::string("unknown option ") + key);
@@ -138,7 +153,9 @@ int main(int argc, char *argv[])
     if (positional.size() != 3) {
         std::cout << "Usage : GroupStats bbox.json spacing design.csv [-c contrasts.csv] [-td transformsDir] [-o outDir] "
                      "[-v jacobian|logjacobian|images] [-vl volumes.txt] [-ml masks.txt] [-m regionMask] [-mc minCount] [-sf sigmaFloor] "
-                     "[-f fill] [-np nPerms] [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-rp planes] [-dev n]" << std::endl;
+                     "[-f fill] [-np nPerms] [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-tf 1] [-tfd dh] [-tfe 0.5|1] [-tfh 1|2] "
+                     "[-rp planes] [-dev n]\n-tf 1: threshold-free cluster enhancement in steps of dh (default 0.1); a statistic beyond 255 * dh "
+                     "saturates there" << std::endl;
         return 1;
     }
 
@@ -151,7 +168,13 @@ int main(int argc, char *argv[])
     if (nPerms < 0 || nPerms == 1 || nPerms > 1000000) die("-np takes 2 to 1000000 permutations (the first is the design itself)");
     if (permOption && nPerms == 0) die("-ps, -pc, -pf and -two need -np");
     if ((clusterTest || connectivityGiven) && nPerms == 0) die("-ct and -cc need -np");
-    if (connectivityGiven && !clusterTest) die("-cc needs -ct");
+    if (tfceTest != 0 && tfceTest != 1) die("-tf takes 1 (or 0)");
+    if ((tfceTest || tfceOption) && nPerms == 0) die("-tf, -tfd, -tfe and -tfh need -np");
+    if (tfceOption && !tfceTest) die("-tfd, -tfe and -tfh need -tf 1");
+    if (connectivityGiven && !clusterTest && !tfceTest) die("-cc needs -ct or -tf 1");
+    if (tfceTest && (!((float)tfceStep > 0.0f) || !std::isfinite((float)tfceStep))) die("-tfd takes a step that is finite and above 0");
+    if (tfceTest && tfceE != 0.5 && tfceE != 1.0) die("-tfe takes 0.5 or 1");
+    if (tfceTest && tfceH != 1.0 && tfceH != 2.0) die("-tfh takes 1 or 2");
     if (clusterTest && (!(clusterThreshold >= 0.0) || !std::isfinite((float)clusterThreshold))) die("-ct takes a threshold that is finite and not negative");
     if (connectivity != 6 && connectivity != 18 && connectivity != 26) die("-cc takes 6, 18 or 26");
     if (planesGiven && planesOption < 1) die("-rp takes a number of planes, at least 1");
@@ -244,6 +267,9 @@ int main(int argc, char *argv[])
     frog_clusters *sink = nullptr;
     if (clusterTest && frog_clusters_create(&grid, (uint32_t)nPerms, (uint32_t)n_c, twoSided == 1, (float)clusterThreshold, connectivity, device, &sink))
         die(frog_last_error());
+    frog_tfce *enhance = nullptr;
+    if (tfceTest && frog_tfce_create(&grid, (uint32_t)nPerms, (uint32_t)n_c, twoSided == 1, (float)tfceStep, tfceE, tfceH, connectivity, device, &enhance))
+        die(frog_last_error());
     begin_output(outDir, n, "images", grid);
 
     auto t0 = clk::now();
@@ -323,6 +349,9 @@ int main(int argc, char *argv[])
                                                  perm.data(), signs, 0, sink, slabMax.data(), slabMin.data())
                      : frog_glm_permute(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, columns, (uint32_t)nPerms, perm.data(),
                                         signs, slabMax.data(), slabMin.data())) die(frog_last_error());
+            // the same adds fill the second sink; the extrema are the same bits and are taken once
+            if (enhance && frog_glm_permute_tfce(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, columns, (uint32_t)nPerms,
+                                                 perm.data(), signs, 0, enhance, nullptr, nullptr)) die(frog_last_error());
             for (size_t e = 0; e < maxT.size(); e++) {
                 if (float_key(slabMax[e]) > float_key(maxT[e])) maxT[e] = slabMax[e];
                 if (float_key(slabMin[e]) < float_key(minT[e])) minT[e] = slabMin[e];
@@ -352,6 +381,24 @@ int main(int argc, char *argv[])
             }
         times.device_s += seconds(t0);
         frog_clusters_destroy(sink);
+    }
+    // threshold-free cluster enhancement: every slot's largest value, and the observed maps, the negative side's negated
+    std::vector<float> slotTfce, tfceMap, sideMap;
+    if (enhance) {
+        t0 = clk::now();
+        slotTfce.resize((size_t)nPerms * n_c * sides);
+        if (frog_tfce_finish(enhance, slotTfce.data())) die(frog_last_error());
+        tfceMap.resize(n_c * total);
+        sideMap.resize(total);
+        for (size_t c = 0; c < n_c; c++) {
+            if (frog_tfce_map(enhance, 0, (uint32_t)c, 0, tfceMap.data() + c * total)) die(frog_last_error());
+            if (sides == 2) {
+                if (frog_tfce_map(enhance, 0, (uint32_t)c, 1, sideMap.data())) die(frog_last_error());
+                for (size_t v = 0; v < total; v++) tfceMap[c * total + v] -= sideMap[v];       // a voxel has at most one side
+            }
+        }
+        times.device_s += seconds(t0);
+        frog_tfce_destroy(enhance);
     }
 
     // ---- the files
@@ -439,6 +486,49 @@ int main(int argc, char *argv[])
         }
         table.close();
         if (!table) die("cannot write " + outDir + "/clusters.csv");
+    }
+    if (tfceTest) {
+        std::ofstream csv(outDir + "/maxtfce.csv"), table(outDir + "/tfce.csv");
+        csv << "permutation,contrast,max_tfce\n";
+        table << "contrast,peak_tfce,peak_x,peak_y,peak_z,threshold_p05,voxels_p05\n";
+        auto nullTfce = [&](long k, size_t c) {
+            const float *e = slotTfce.data() + ((size_t)k * n_c + c) * sides;
+            return sides == 2 ? std::max(e[0], e[1]) : e[0];
+        };
+        for (long k = 0; k < nPerms; k++)
+            for (size_t c = 0; c < n_c; c++) csv << k << "," << c << "," << csv_float(nullTfce(k, c)) << "\n";
+        csv.close();
+        if (!csv) die("cannot write " + outDir + "/maxtfce.csv");
+        std::vector<float> pmap(total), null((size_t)nPerms - 1);
+        for (size_t c = 0; c < n_c; c++) {
+            for (long k = 1; k < nPerms; k++) null[k - 1] = nullTfce(k, c);
+            std::sort(null.begin(), null.end());
+            // maxt.csv's rule: the largest null maximum a value must exceed for p < 0.05
+            const long allowed = (nPerms - 1) / 20 - 1;
+            const double limit = allowed < 0 ? INFINITY : (allowed >= (long)null.size() ? -INFINITY : (double)null[null.size() - 1 - allowed]);
+            const float *map = tfceMap.data() + c * total;
+            uint64_t past = 0;
+            size_t peak = total;
+            for (size_t v = 0; v < total; v++) {
+                const float value = std::fabs(map[v]);
+                float pv = 1.0f;
+                if (value != 0.0f) {
+                    const size_t exceed = null.end() - std::lower_bound(null.begin(), null.end(), value);
+                    pv = (float)((double)(1 + exceed) / (double)nPerms);
+                    if (20 * (1 + (long)exceed) < nPerms) past++;
+                    if (peak == total || value > std::fabs(map[peak])) peak = v;
+                }
+                pmap[v] = pv;
+            }
+            table << c << ",";
+            if (peak < total) table << csv_float(map[peak]) << "," << peak % grid.dims[0] << "," << (peak / grid.dims[0]) % grid.dims[1] << "," << peak / plane;
+            else table << "nan,,,";
+            table << "," << csv_float((float)limit) << "," << past << "\n";
+            write("tfce_" + std::to_string(c) + ".nii.gz", FROG_V_F32, tfceMap.data() + c * total);
+            write("tfce_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
+        }
+        table.close();
+        if (!table) die("cannot write " + outDir + "/tfce.csv");
     }
     {
         std::ofstream csv(outDir + "/glm.csv");

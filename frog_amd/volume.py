@@ -432,6 +432,11 @@ class GroupGLM(_Accumulator):
         bit of every window voxel whose t counts towards the extrema and lies beyond the sink's threshold."""
         return self._permute(sink, first_perm, contrasts, perm, sign, columns, min_count, sigma_floor, region)
 
+    def permute_tfce(self, sink, contrasts, perm, sign=None, columns=None, min_count=1, sigma_floor=0.0, region=None, first_perm=0):
+        """permute(), which also stores in the TfceSink `sink`, for row k in the slots of its permutation first_perm + k, the
+        level of every window voxel whose t counts towards the extrema, and 0 for the window's other voxels."""
+        return self._permute(sink, first_perm, contrasts, perm, sign, columns, min_count, sigma_floor, region)
+
     def _permute(self, sink, first_perm, contrasts, perm, sign, columns, min_count, sigma_floor, region):
         c, _r, rp = self._fit_arguments(contrasts, region)
         pm = np.ascontiguousarray(perm, np.uint32).reshape(-1, self.design.shape[0])
@@ -446,7 +451,8 @@ class GroupGLM(_Accumulator):
         if sink is None:
             _abi.check(self._lib.frog_glm_permute(*shared, *out), "frog_glm_permute")
         else:
-            _abi.check(self._lib.frog_glm_permute_clusters(*shared, int(first_perm), sink._h, *out), "frog_glm_permute_clusters")
+            where = f"frog_glm_permute_{sink._NAME}"
+            _abi.check(getattr(self._lib, where)(*shared, int(first_perm), sink._h, *out), where)
         return hi, lo
 
 
@@ -482,6 +488,61 @@ class ClusterSink(_Accumulator):
         _abi.check(self._lib.frog_clusters_labels(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(_abi.c_u32_p), C.byref(n)),
                    "frog_clusters_labels")
         return out, n.value
+
+
+class TfceSink(_Accumulator):
+    """frog_tfce (include/frog_chain.h): on the device, for the whole `grid`, one u8 level per voxel and slot (permutation,
+    contrast, side) -- trunc(t / dh) on side 0 and, with two_sided, trunc(-t / dh) on side 1, saturated at 255 -- which
+    GroupGLM.permute_tfce fills window by window, and the threshold-free cluster enhancement of each slot with the exponents
+    `e` (0.5 or 1, of the extent) and `h` (1 or 2, of the height) at `connectivity`."""
+
+    _NAME = "tfce"
+
+    def __init__(self, grid, n_perms, n_contrasts, dh=0.1, e=0.5, h=2, two_sided=False, connectivity=26, device=0):
+        super().__init__(grid, int(n_perms), int(n_contrasts), int(bool(two_sided)), float(dh), float(e), float(h), int(connectivity), int(device))
+        self.n_perms, self.n_contrasts, self.sides = int(n_perms), int(n_contrasts), 2 if two_sided else 1
+        self.shape = self.dims[::-1]
+
+    def finish(self):
+        """The largest tfce of every slot, float32 (n_perms, n_contrasts, sides); 0 where no voxel has a positive level."""
+        out = np.empty((self.n_perms, self.n_contrasts, self.sides), np.float32)
+        _abi.check(self._lib.frog_tfce_finish(self._h, out.ctypes.data_as(_abi.c_float_p)), "frog_tfce_finish")
+        return out
+
+    def levels(self, perm, contrast, side=0):
+        """One slot's levels, uint8 on the grid."""
+        out = np.empty(self.shape, np.uint8)
+        _abi.check(self._lib.frog_tfce_levels(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(C.POINTER(C.c_uint8))),
+                   "frog_tfce_levels")
+        return out
+
+    def map(self, perm, contrast, side=0):
+        """One slot's enhanced map, float32 on the grid."""
+        out = np.empty(self.shape, np.float32)
+        _abi.check(self._lib.frog_tfce_map(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(_abi.c_float_p)), "frog_tfce_map")
+        return out
+
+
+def tfce(stat, dh=0.1, e=0.5, h=2, connectivity=26, side=0, device=0):
+    """(tfce float32 on the grid, its maximum) of the float32 array stat[z, y, x] (frog_tfce_volume): the threshold-free
+    cluster enhancement of stat (side 0) or of -stat (side 1) in steps of dh, saturated at 255 * dh."""
+    a = np.ascontiguousarray(stat)
+    v = _abi.volume_view(a, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+    out = np.empty(a.shape, np.float32)
+    top = C.c_float()
+    _abi.check(_abi.hip_lib().frog_tfce_volume(C.byref(v), int(side), float(dh), float(e), float(h), int(connectivity), int(device),
+                                               out.ctypes.data_as(_abi.c_float_p), C.byref(top)), "frog_tfce_volume")
+    return out, np.float32(top.value)
+
+
+def tfce_p(tfce, null):
+    """The family-wise corrected p of enhanced values: (float32)((1 + #{k >= 1: null[k] >= tfce}) / (double)n_perms), null the
+    n_perms largest enhanced values with row 0 the unpermuted design; 1 where tfce == 0.  Signed maps go by magnitude."""
+    t = np.abs(np.asarray(tfce, np.float32))
+    ranked = np.sort(np.asarray(null, np.float32)[1:])
+    beyond = len(ranked) - np.searchsorted(ranked, t, side="left")
+    p = ((1 + beyond).astype(np.float64) / np.float64(len(ranked) + 1)).astype(np.float32)
+    return np.where(t == 0, np.float32(1), p)
 
 
 def components(mask, connectivity=26, device=0, largest=False):
@@ -549,7 +610,7 @@ def fwe_p(t, max_t, min_t=None, fit=None):
 
 def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=None, value="logjacobian", supports=None, interpolation=1,
               min_count=1, sigma_floor=0.0, region=None, fill=0.0, n_perms=0, seed=0, columns=None, flip=False, two_sided=False,
-              max_planes=None, device=0, cluster_threshold=None, connectivity=26):
+              max_planes=None, device=0, cluster_threshold=None, connectivity=26, tfce=False):
     """The per-voxel linear model of a registered group (bin/GroupStats).  value "logjacobian" or "jacobian": image i is the
     (log) Jacobian determinant of chains[i] on `grid`, counted where the chain lands inside supports[i] (a geometry, optional)
     and masks[i]; value "images": volumes[i] resliced as in cover_average().  With n_perms > 0 the columns `columns` (default
@@ -562,7 +623,12 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
     permutation, with two_sided the larger of that and the largest cluster of t < -cluster_threshold.  clusters int32
     (n_contrasts,) + shape: the observed map's clusters 1..K, with two_sided the negative side's numbered after the positive
     side's.  cluster_extent: per contrast the K extents, uint32.  cluster_p float32 (n_contrasts,) + shape: cluster_p() of the
-    voxel's cluster against max_extent, 1 outside every cluster."""
+    voxel's cluster against max_extent, 1 outside every cluster.
+    With tfce (True, or a dict of dh, e, h, connectivity in place of 0.1, 0.5, 2 and `connectivity`) and permutations also
+    threshold-free cluster enhancement: one TfceSink for the whole grid, filled by every slab with a permute call of its own.
+    max_tfce float32 (n_perms, n_contrasts): the largest enhanced value under each permutation, with two_sided the larger of
+    the two sides'.  tfce float32 (n_contrasts,) + shape: the observed enhanced map, with two_sided +tfce of the positive side
+    and -tfce of the negative.  tfce_p float32: tfce_p() of the map against max_tfce."""
     X = np.ascontiguousarray(design, np.float64)
     c = np.ascontiguousarray(contrasts, np.float64).reshape(-1, X.shape[1])
     n = X.shape[0]
@@ -588,6 +654,11 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
     perm, sign = glm_draw(n, n_perms, seed, True, flip) if n_perms else (None, None)
     hi = lo = None
     sink = ClusterSink(grid, n_perms, len(c), cluster_threshold, two_sided, connectivity, device) if n_perms and cluster_threshold is not None else None
+    enhance = None
+    if n_perms and tfce:
+        opt = dict(dh=0.1, e=0.5, h=2, connectivity=connectivity)
+        opt.update(tfce if isinstance(tfce, dict) else {})
+        enhance = TfceSink(grid, n_perms, len(c), opt["dh"], opt["e"], opt["h"], two_sided, opt["connectivity"], device)
     for first in range(0, dims[2], planes):
         m = min(planes, dims[2] - first)
         acc = GroupGLM(grid, X, (first, m), device)
@@ -606,6 +677,8 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
             out.setdefault("fit", np.empty(shape, bool))[sl] = marked != -1
             if n_perms:
                 h, l = acc._permute(sink, 0, c, perm, sign if flip else None, columns, min_count, sigma_floor, r)
+                if enhance is not None:
+                    acc._permute(enhance, 0, c, perm, sign if flip else None, columns, min_count, sigma_floor, r)
                 if hi is None:
                     hi, lo = h, l
                 else:
@@ -631,6 +704,15 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
                 out["cluster_p"][j] = p[out["clusters"][j]]
         finally:
             sink.close()
+    if enhance is not None:
+        try:
+            out["max_tfce"] = enhance.finish().max(axis=2)
+            out["tfce"] = np.stack([enhance.map(0, j, 0) for j in range(len(c))])
+            if two_sided:
+                out["tfce"] -= np.stack([enhance.map(0, j, 1) for j in range(len(c))])      # a voxel has at most one side
+            out["tfce_p"] = np.stack([tfce_p(out["tfce"][j], out["max_tfce"][:, j]) for j in range(len(c))])
+        finally:
+            enhance.close()
     return out
 
 

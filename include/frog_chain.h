@@ -718,6 +718,64 @@ int  frog_clusters_mask(frog_clusters *s, uint32_t perm, uint32_t contrast, int 
 int  frog_clusters_labels(frog_clusters *s, uint32_t perm, uint32_t contrast, int side, uint32_t *labels, uint32_t *n_components);
 void frog_clusters_destroy(frog_clusters *s);
 
+/* ---- threshold-free cluster enhancement, TFCE (an extension; Smith and Nichols, NeuroImage 44, 2009) ---------------------------
+ * Parameters: dh (f32, finite, > 0), E (0.5 or 1), H (1 or 2), connectivity (6, 18 or 26).  Components and extents are those
+ * of the section above.
+ *
+ * LEVEL of a statistic t (f32) on a side:
+ *   s = t on side 0, s = -t on side 1
+ *   L = 0                                         where t is the NaN or s <= 0
+ *   q = (double)s / (double)dh                    one f64 division, correctly rounded
+ *   L = q >= 255 ? 255 : (uint8_t)q               truncation; a statistic beyond 255 * dh SATURATES at level 255
+ *
+ * ENHANCEMENT of a level map:
+ *   M_k    = { v : L(v) >= k },  e_k(v) = the extent of v's component of M_k
+ *   h_k    = (double)k * (double)dh
+ *   w_k    = (H == 2 ? h_k * h_k : h_k) * (double)dh          separately rounded f64 products
+ *   g(e)   = E == 0.5 ? sqrt((double)e) : (double)e            the correctly rounded f64 square root
+ *   acc    = +0.0;  for k = L(v) down to 1:  m = g(e_k(v)) * w_k;  acc = acc + m       (f64, in this order, no FMA)
+ *   tfce(v) = (float)acc, which is 0 where L(v) == 0
+ * No floating-point atomic is used: a voxel's sum is its own, and a maximum over voxels is an integer maximum on the bits of
+ * non-negative f32 values.  Every result is the same from run to run.
+ *
+ * frog_tfce_volume: the enhancement of one side (0 or 1) of any FROG_V_F32 volume with host data; tfce (f32, grid-sized) and
+ * max (the largest tfce, 0 where every level is 0) may each be NULL, not both.
+ *
+ * frog_tfce, the SINK of a permutation test: on the device, for the whole grid, one u8 level per voxel and SLOT,
+ * slot = (perm * n_contrasts + contrast) * sides + side as for frog_clusters, all zero at first.
+ *   frog_glm_permute_tfce does what frog_glm_permute does with the same arguments; max_t and min_t (either or both may be NULL
+ *     here) are bit for bit frog_glm_permute's.  For row k of the call and contrast c it also stores, in the slots of
+ *     permutation first_perm + k, at the voxel's index in the whole grid, the level of every window voxel that is fit under
+ *     that permutation and whose t is not the NaN -- the voxels the extrema are taken over -- and 0 for the window's other
+ *     voxels.  Windows that partition the grid fill one level map between them.  The sink counts the z-planes each
+ *     permutation has received: a plane written twice is FROG_E_STATE (nothing is computed or written then).
+ *   frog_tfce_finish: max_tfce[slot] = the largest tfce(v) of the slot, 0 for a slot without a positive level.  FROG_E_STATE
+ *     unless every permutation has received every plane of the grid.
+ *   frog_tfce_levels: one slot's levels, grid-sized.
+ *   frog_tfce_map: one slot's tfce, grid-sized.  FROG_E_STATE unless the permutation has received every plane.
+ * Device memory: slots * (voxels rounded up to a multiple of 32) bytes for the levels, and 16 bytes per voxel plus a bit mask
+ * for each of the slots that are enhanced in one launch (at most 64, fewer where memory is short).  FROG_E_NOMEM, with the
+ * bytes needed and the bytes free in the message, when the levels and the workspace of one slot do not fit.
+ *
+ * FROG_E_INVALID, before the device is touched: a NULL argument that is not marked optional, a grid that is empty or above 2^31
+ * voxels, dh that is not finite or not above 0, E other than 0.5 or 1, H other than 1 or 2, a connectivity other than 6, 18 or
+ * 26, n_perms == 0, n_contrasts == 0 or > FROG_GLM_MAX_CONTRASTS, a side other than 0 or 1, a volume that is not FROG_V_F32 or
+ * has no data, everything frog_glm_permute refuses, a sink whose grid dims, device or n_contrasts differ from the
+ * accumulator's and the call's, first_perm + n_perms beyond the sink's n_perms, a permutation, contrast or side that the sink
+ * does not have. */
+int  frog_tfce_volume(const frog_volume *stat, int side, float dh, double E, double H, int connectivity, int device, float *tfce, float *max);
+
+typedef struct frog_tfce frog_tfce;
+int  frog_tfce_create(const frog_volume *grid, uint32_t n_perms, uint32_t n_contrasts, int two_sided, float dh, double E, double H,
+                      int connectivity, int device, frog_tfce **out);
+int  frog_glm_permute_tfce(frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
+                           const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
+                           uint32_t first_perm, frog_tfce *sink, float *max_t, float *min_t);
+int  frog_tfce_finish(frog_tfce *s, float *max_tfce);
+int  frog_tfce_levels(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, uint8_t *levels);
+int  frog_tfce_map(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, float *tfce);
+void frog_tfce_destroy(frog_tfce *s);
+
 #ifdef __cplusplus
 }
 #endif

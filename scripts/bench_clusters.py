@@ -108,8 +108,8 @@ def noise(args, perm):
     return out
 
 
-def tool(clusters):
-    """bin/GroupStats on bench_glm's files with 100 permutations: its phase lines."""
+def tool(clusters, extra=()):
+    """bin/GroupStats on bench_glm's files with 100 permutations (and the options `extra`): its phase lines."""
     import re
     import shutil
     import tempfile
@@ -135,7 +135,7 @@ def tool(clusters):
             fh.write("0,1,0\n")
         t0 = time.perf_counter()
         r = subprocess.run([os.path.join(ROOT, "bin", "GroupStats"), "bbox.json", repr(GRID[2][0]), "design.csv", "-c", "contrasts.csv", "-o", "out",
-                            "-np", "100"] + (["-ct", repr(THRESHOLD), "-cc", str(CONNECTIVITY)] if clusters else []),
+                            "-np", "100"] + (["-ct", repr(THRESHOLD), "-cc", str(CONNECTIVITY)] if clusters else []) + list(extra),
                            cwd=d, capture_output=True, text=True, timeout=900)
         wall = time.perf_counter() - t0
         if r.returncode != 0:
