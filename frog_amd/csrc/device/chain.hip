@@ -1049,6 +1049,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 #include "k_glm.hip.h"
 #include "k_ccl.hip.h"
 #include "k_tfce.hip.h"
+#include "k_smooth.hip.h"
 
 } // namespace
 
@@ -1098,12 +1099,29 @@ struct frog_rank : frog_windowed {
     frog::DevBuf<uint32_t> d_keys;                  // n_images planes of `window` keys, in the order of the adds
 };
 
+// The taps of the three axes, and the scratch of the passes over a RANGE of whole planes (k_smooth.hip.h): the f32 values the
+// x pass reads, and what the x and the y pass store.
+struct SmoothWork {
+    SmoothTaps taps[3];
+    frog::DevBuf<float> d_raw;
+    frog::DevBuf<double2> d_x, d_y;
+};
+constexpr size_t SMOOTH_VOXEL_BYTES = sizeof(float) + 2 * sizeof(double2);
+
+// frog_glm_smooth's: the range an add evaluates, the window extended by the z radius and clipped at the grid's ends
+struct SmoothPlan {
+    bool on = false;
+    size_t first = 0, count = 0;                    // the range's first voxel in the grid, and its voxels
+    SmoothWork work;
+};
+
 // one plane of f32 values per added image, and the design of the linear model
 struct frog_glm : frog_windowed {
     uint32_t p = 0;
     std::vector<double> design;                     // n_images x p
     frog::DevBuf<float> d_vals;                     // n_images planes of `window` values, in the order of the adds
     frog::DevBuf<double> d_design, d_table;         // d_table: the design rows of one launch's permutations, grown on demand
+    SmoothPlan smooth;                              // frog_glm_smooth's; off at first
 };
 
 // what the sinks of a permutation test hold alike (frog_clusters, frog_tfce): one slot per permutation, contrast and side for
@@ -2025,8 +2043,8 @@ int windowed_new(const char *where, const frog_volume *grid, size_t total, uint3
 // An add for a source of type S: cover_add_typed with the store of Entry (RankEntry: a key, GlmEntry: an f32) in place of the
 // update, over the window, into the image's plane.
 template <class S, class Entry>
-int windowed_add_typed(const char *where, frog_windowed *a, typename Entry::type *plane, frog_chain *c, const frog_volume *src,
-                       const frog_volume *mask, int interpolation, double background)
+int windowed_add_typed(const char *where, frog_windowed *a, size_t first, size_t window, typename Entry::type *plane, frog_chain *c,
+                       const frog_volume *src, const frog_volume *mask, int interpolation, double background)
 {
     ResliceGrid g;
     const uint8_t *d_mask;
@@ -2034,19 +2052,21 @@ int windowed_add_typed(const char *where, frog_windowed *a, typename Entry::type
     if (int rc = cover_stage_mask(where, a, mask, &d_mask)) return rc;
     const MaskGrid mg = mask_grid(mask);
     const S *d_src = (const S *)a->d_src.p;
-    const hipError_t e = chunked_launch(a->window, [&](unsigned blocks, size_t base) {
+    const hipError_t e = chunked_launch(window, [&](unsigned blocks, size_t base) {
         if (c)
-            window_reslice_kernel<S, Entry><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg, plane);
+            window_reslice_kernel<S, Entry><<<blocks, LAUNCH_BLOCK>>>(base, first, window, c->d_links.p, (int)c->h_links.size(), d_src, g, d_mask, mg, plane);
         else
-            window_identity_kernel<S, Entry><<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, d_src, d_mask, plane);
+            window_identity_kernel<S, Entry><<<blocks, LAUNCH_BLOCK>>>(base, first, window, d_src, d_mask, plane);
     });
     return return_resliced<S>(where, a, c, src, nullptr, e);
 }
 
-// frog_rank_add and frog_glm_add: `planes` is the accumulator's store, n_images planes of the window (null with a null a)
+// frog_rank_add and frog_glm_add: `planes` is the accumulator's store, n_images planes of the window (null with a null a).
+// With `range` the same kernels store the `range_count` voxels of the grid from `range_first` on there instead, and the add is
+// not counted: the caller has more to do (frog_glm_add with smoothing).
 template <class Entry>
 int windowed_add(const char *where, frog_windowed *a, typename Entry::type *planes, frog_chain *c, const frog_volume *src, const frog_volume *mask,
-                 int interpolation, double background)
+                 int interpolation, double background, typename Entry::type *range = nullptr, size_t range_first = 0, size_t range_count = 0)
 {
     if (!a || !src || !src->data || !frog_volume_voxel_bytes(src->dtype)) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
     if (a->added >= a->n_images) return fail(FROG_E_INVALID, std::string(where) + ": more volumes than the accumulator was created for");
@@ -2054,9 +2074,11 @@ int windowed_add(const char *where, frog_windowed *a, typename Entry::type *plan
     if (mask) cover_mask(a, mask);
     KCHECK(hipSetDevice(a->device));
     const int rc = with_voxel_type(src->dtype, [&](auto s) {
-        return windowed_add_typed<decltype(s), Entry>(where, a, planes + (size_t)a->added * a->window, c, src, mask, interpolation, background);
+        if (range) return windowed_add_typed<decltype(s), Entry>(where, a, range_first, range_count, range, c, src, mask, interpolation, background);
+        return windowed_add_typed<decltype(s), Entry>(where, a, a->first, a->window, planes + (size_t)a->added * a->window, c, src, mask, interpolation,
+                                                      background);
     });
-    if (rc == FROG_OK) a->added++;
+    if (rc == FROG_OK && !range) a->added++;
     return rc;
 }
 
@@ -2091,6 +2113,77 @@ int rank_arguments(const char *where, const frog_volume *grid, uint32_t n_images
     if (!n_images || n_images > FROG_RANK_MAX_IMAGES)
         return fail(FROG_E_INVALID, std::string(where) + ": 1 to " + std::to_string(FROG_RANK_MAX_IMAGES) + " images");
     return FROG_OK;
+}
+
+// ---- the coverage-aware Gaussian (k_smooth.hip.h) of frog_smooth_volume and frog_glm_smooth ------------------------------------
+
+// The taps of the three axes of `grid`, as frog_smooth_taps gives them; sigma == 0: radius 0 and w_0 = 1 on every axis.
+int smooth_taps3(const char *where, const frog_volume *grid, double sigma, SmoothTaps taps[3])
+{
+    if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(FROG_E_INVALID, std::string(where) + ": sigma is finite and not negative");
+    if (!voxel_count(grid)) return fail(FROG_E_INVALID, "empty grid");
+    for (int k = 0; k < 3; k++) {
+        taps[k] = SmoothTaps{};
+        taps[k].w[0] = 1.0;
+        if (sigma == 0.0) continue;
+        if (int rc = frog_smooth_taps(sigma, grid->spacing[k], &taps[k].radius, taps[k].w)) return rc;      // with its message
+    }
+    return FROG_OK;
+}
+
+// the free bytes of the current device, as frog_glm_smooth and frog_glm_smooth_planes count them
+// (test hook: FROG_CHAIN_FREE_MAX=n, at most n of them count; read at every call)
+hipError_t smooth_free_bytes(size_t *free_bytes)
+{
+    size_t device_bytes = 0;
+    const hipError_t e = hipMemGetInfo(free_bytes, &device_bytes);
+    const char *s = getenv("FROG_CHAIN_FREE_MAX");
+    const long long cap = s ? atoll(s) : 0;
+    if (e == hipSuccess && cap > 0) *free_bytes = std::min(*free_bytes, (size_t)cap);
+    return e;
+}
+
+hipError_t smooth_work_alloc(SmoothWork &w, size_t count)
+{
+    hipError_t e = w.d_raw.alloc(count);
+    if (e == hipSuccess) e = w.d_x.alloc(count);
+    if (e == hipSuccess) e = w.d_y.alloc(count);
+    return e;
+}
+
+// The three passes over the `count` voxels in w.d_raw, whole planes of `grid` (with the flags d_take of the same voxels, or
+// null); d_out receives the `window` voxels from `offset` on.
+hipError_t smooth_passes(const frog_volume &grid, SmoothWork &w, const uint8_t *d_take, size_t count, size_t offset, size_t window, float *d_out)
+{
+    const uint32_t nx = grid.dims[0], ny = grid.dims[1];
+    hipError_t e = chunked_launch(count, [&](unsigned blocks, size_t base) {
+        smooth_x_kernel<<<blocks, LAUNCH_BLOCK>>>(base, count, nx, w.d_raw.p, d_take, w.taps[0], w.d_x.p);
+    });
+    if (e == hipSuccess) e = chunked_launch(count, [&](unsigned blocks, size_t base) {
+        smooth_y_kernel<<<blocks, LAUNCH_BLOCK>>>(base, count, nx, ny, w.d_x.p, w.taps[1], w.d_y.p);
+    });
+    if (e == hipSuccess) e = chunked_launch(window, [&](unsigned blocks, size_t base) {
+        smooth_z_kernel<<<blocks, LAUNCH_BLOCK>>>(base, window, offset, count, (size_t)nx * ny, w.d_raw.p, d_take, w.d_y.p, w.taps[2], d_out);
+    });
+    return e;
+}
+
+// the second half of a smoothed add: the raw map of the range is in the scratch
+int glm_smooth_store(const char *where, frog_glm *a)
+{
+    SmoothPlan &s = a->smooth;
+    hipError_t e = smooth_passes(a->grid, s.work, nullptr, s.count, a->first - s.first, a->window, a->d_vals.p + (size_t)a->added * a->window);
+    if (e == hipSuccess) e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return hip_fail(where, e);
+    a->added++;
+    return FROG_OK;
+}
+
+// the planes [*first, *first + *count) a window's smoothed add evaluates
+void smooth_range(uint32_t depth, uint32_t first_plane, uint32_t n_planes, uint32_t radius, uint32_t *first, uint32_t *count)
+{
+    *first = first_plane > radius ? first_plane - radius : 0;
+    *count = (uint32_t)std::min<uint64_t>((uint64_t)first_plane + n_planes + radius, depth) - *first;
 }
 
 // what frog_glm_finish and frog_glm_permute refuse alike, before the device is touched
@@ -3065,7 +3158,10 @@ int frog_glm_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_pl
 
 int frog_glm_add(frog_glm *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
 {
-    return windowed_add<GlmEntry>("frog_glm_add", a, a ? a->d_vals.p : nullptr, c, src, mask, interpolation, background);
+    if (!a || !a->smooth.on) return windowed_add<GlmEntry>("frog_glm_add", a, a ? a->d_vals.p : nullptr, c, src, mask, interpolation, background);
+    const SmoothPlan &s = a->smooth;
+    if (int rc = windowed_add<GlmEntry>("frog_glm_add", a, a->d_vals.p, c, src, mask, interpolation, background, s.work.d_raw.p, s.first, s.count)) return rc;
+    return glm_smooth_store("frog_glm_add", a);
 }
 
 int frog_glm_add_jacobian(frog_glm *a, frog_chain *c, const frog_volume *support, const frog_volume *mask, int log_mode)
@@ -3085,11 +3181,18 @@ int frog_glm_add_jacobian(frog_glm *a, frog_chain *c, const frog_volume *support
     if (int rc = cover_stage_mask("frog_glm_add_jacobian", a, mask, &d_mask)) return rc;
     const MaskGrid mg = mask_grid(mask), sg = mask_grid(support);
     const NodeGrid out = node_grid(a->grid.origin, a->grid.spacing, a->grid.dims);
-    float *plane = a->d_vals.p + (size_t)a->added * a->window;
-    hipError_t e = chunked_launch(a->window, [&](unsigned blocks, size_t base) {
-        glm_jacobian_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), out, support != nullptr, sg,
+    // with smoothing the same kernel on the larger range, into the scratch
+    const SmoothPlan &s = a->smooth;
+    const size_t first = s.on ? s.first : a->first, window = s.on ? s.count : a->window;
+    float *plane = s.on ? s.work.d_raw.p : a->d_vals.p + (size_t)a->added * a->window;
+    hipError_t e = chunked_launch(window, [&](unsigned blocks, size_t base) {
+        glm_jacobian_kernel<<<blocks, LAUNCH_BLOCK>>>(base, first, window, c->d_links.p, (int)c->h_links.size(), out, support != nullptr, sg,
                                                       d_mask, mg, log_mode != 0, plane);
     });
+    if (s.on) {
+        if (e != hipSuccess) return hip_fail("frog_glm_add_jacobian", e);
+        return glm_smooth_store("frog_glm_add_jacobian", a);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(0);
     if (e != hipSuccess) return hip_fail("frog_glm_add_jacobian", e);
     a->added++;
@@ -3408,6 +3511,104 @@ int frog_tfce_volume(const frog_volume *stat, int side, float dh, double E, doub
     if (e == hipSuccess && tfce) e = hipMemcpy(tfce, d_map.p, total * sizeof(float), hipMemcpyDeviceToHost);
     if (e == hipSuccess && max) e = hipMemcpy(max, d_slot.p + 1, sizeof(float), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail("frog_tfce_volume", e);
+    return FROG_OK;
+}
+
+int frog_smooth_taps(double sigma_mm, double spacing, uint32_t *radius, double *taps)
+{
+    if (!radius) return fail(FROG_E_INVALID, "bad arguments to frog_smooth_taps");
+    if (!(sigma_mm > 0.0) || !std::isfinite(sigma_mm)) return fail(FROG_E_INVALID, "frog_smooth_taps: sigma is finite and above 0");
+    if (!(spacing > 0.0) || !std::isfinite(spacing)) return fail(FROG_E_INVALID, "frog_smooth_taps: the spacing is finite and above 0");
+    volatile double q = 3.0 * sigma_mm;             // volatile: every line is rounded to f64 on its own, whatever the host compiler contracts
+    q = q / spacing;
+    const double r = std::ceil(q);
+    if (!(r <= (double)FROG_SMOOTH_MAX_RADIUS))
+        return fail(FROG_E_INVALID, "frog_smooth_taps: a radius of " + std::to_string(r) + " voxels, above " + std::to_string(FROG_SMOOTH_MAX_RADIUS));
+    *radius = (uint32_t)r;
+    if (!taps) return FROG_OK;
+    volatile double den = 2.0 * sigma_mm;
+    den = den * sigma_mm;
+    for (uint32_t d = 0; d <= *radius; d++) {
+        volatile double x = (double)d * spacing;
+        x = x * x;
+        x = x / den;
+        taps[d] = std::exp(-x);
+    }
+    return FROG_OK;
+}
+
+int frog_smooth_volume(const frog_volume *volume, const uint8_t *take, double sigma_mm, int device, float *out)
+{
+    size_t total;
+    if (int rc = group_arguments("frog_smooth_volume", volume, out, &total)) return rc;
+    if (!volume->data) return fail(FROG_E_INVALID, "frog_smooth_volume: a volume without voxels");
+    if (volume->dtype != FROG_V_F32) return fail(FROG_E_INVALID, "frog_smooth_volume: the volume has type FROG_V_F32");
+    SmoothWork work;
+    if (int rc = smooth_taps3("frog_smooth_volume", volume, sigma_mm, work.taps)) return rc;
+    if (int rc = select_device(device)) return rc;
+    frog::DevBuf<uint8_t> d_take;
+    frog::DevBuf<float> d_out;
+    KCHECK(smooth_work_alloc(work, total));
+    KCHECK(d_out.alloc(total));
+    if (take) KCHECK(d_take.alloc(total));
+    hipError_t e = hipMemcpy(work.d_raw.p, volume->data, total * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && take) e = hipMemcpy(d_take.p, take, total, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = smooth_passes(*volume, work, d_take.p, total, 0, total, d_out.p);
+    if (e == hipSuccess) e = hipMemcpy(out, d_out.p, total * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_smooth_volume", e);
+    return FROG_OK;
+}
+
+int frog_glm_smooth(frog_glm *a, double sigma_mm)
+{
+    if (!a) return fail(FROG_E_INVALID, "bad arguments to frog_glm_smooth");
+    SmoothTaps taps[3];
+    if (int rc = smooth_taps3("frog_glm_smooth", &a->grid, sigma_mm, taps)) return rc;
+    if (a->added) return fail(FROG_E_STATE, "frog_glm_smooth: after the first add");
+    KCHECK(hipSetDevice(a->device));
+    SmoothPlan &s = a->smooth;
+    s.on = false;
+    s.work.d_raw.release();
+    s.work.d_x.release();
+    s.work.d_y.release();
+    if (sigma_mm == 0.0) return FROG_OK;
+    const size_t plane = (size_t)a->grid.dims[0] * a->grid.dims[1];
+    uint32_t first, count;
+    smooth_range(a->grid.dims[2], (uint32_t)(a->first / plane), (uint32_t)(a->window / plane), taps[2].radius, &first, &count);
+    const size_t voxels = plane * count, need = voxels * SMOOTH_VOXEL_BYTES;
+    size_t free_bytes = 0;
+    KCHECK(smooth_free_bytes(&free_bytes));
+    if (need > free_bytes)
+        return fail(FROG_E_NOMEM, "frog_glm_smooth: the scratch of " + std::to_string(count) + " planes needs " + std::to_string(need) +
+                                      " bytes of device memory, " + std::to_string(free_bytes) + " are free");
+    KCHECK(smooth_work_alloc(s.work, voxels));
+    for (int k = 0; k < 3; k++) s.work.taps[k] = taps[k];
+    s.first = plane * first;
+    s.count = voxels;
+    s.on = true;
+    return FROG_OK;
+}
+
+int frog_glm_smooth_planes(const frog_volume *grid, uint32_t n_images, double sigma_mm, int device, uint32_t *planes)
+{
+    if (!grid || !planes) return fail(FROG_E_INVALID, "bad arguments to frog_glm_smooth_planes");
+    SmoothTaps taps[3];
+    if (int rc = smooth_taps3("frog_glm_smooth_planes", grid, sigma_mm, taps)) return rc;
+    uint32_t fit = 0;
+    if (int rc = frog_glm_planes(grid, n_images, device, &fit)) return rc;
+    if (sigma_mm == 0.0) { *planes = fit; return FROG_OK; }
+    size_t free_bytes = 0;
+    KCHECK(smooth_free_bytes(&free_bytes));
+    const size_t plane = (size_t)grid->dims[0] * grid->dims[1], depth = grid->dims[2], halo = 2 * (size_t)taps[2].radius;
+    auto bytes = [&](size_t p) { return plane * (p * sizeof(float) * n_images + std::min(p + halo, depth) * SMOOTH_VOXEL_BYTES); };
+    // bytes() grows with p: the largest p that fits, by bisection
+    size_t lo = 0, hi = fit;
+    while (lo < hi) {
+        const size_t mid = lo + (hi - lo + 1) / 2;
+        if (bytes(mid) <= free_bytes / 2) lo = mid; else hi = mid - 1;
+    }
+    if (!lo) return fail(FROG_E_INVALID, "frog_glm_smooth_planes: not one plane of the grid and the scratch of its halo fit half of the free device memory");
+    *planes = (uint32_t)lo;
     return FROG_OK;
 }
 

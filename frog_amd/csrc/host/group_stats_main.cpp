@@ -4,7 +4,7 @@
 //   GroupStats bbox.json spacing design.csv [-c contrasts.csv] [-td transformsDir] [-o outDir] [-v jacobian|logjacobian|images]
 //              [-vl volumes.txt] [-ml masks.txt] [-m regionMask] [-mc minCount] [-sf sigmaFloor] [-f fill] [-np nPerms]
 //              [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-tf 1] [-tfd dh] [-tfe 0.5|1] [-tfh 1|2]
-//              [-rp planes] [-dev n]
+//              [-s fwhm_mm] [-rp planes] [-dev n]
 // The grid is DummyVolumeGenerator's (frog_bbox_grid).  design.csv has one row per image and one column per regressor,
 // numbers separated by commas or blanks, after an optional header line; row i belongs to <transformsDir>/<i>.json (default
 // "transforms"), which is inverted as AverageImage inverts it.  -c: one contrast per row, as many numbers as the design has
@@ -41,6 +41,11 @@
 // permutation,contrast,max_tfce.  tfce.csv: contrast,peak_tfce,peak_x,peak_y,peak_z,threshold_p05,voxels_p05, as in glm.csv.
 // One sink on the device holds every permutation's levels for the whole grid, one byte per voxel; if it does not fit, the tool
 // says how many bytes it needs and stops before the first output.  -tf and -ct may be given together.
+// -s fwhm_mm: every image's map is smoothed before the fit by the coverage-aware Gaussian of frog_glm_smooth, sigma = fwhm /
+// 2.3548200450309493 (FROG_SMOOTH_FWHM): a normalised convolution over the voxels at which the image takes part, so count.nii.gz
+// does not change and no background enters an image's rim.  A radius (3 sigma, in voxels) above 64 is refused.  -s 0, the
+// default, changes no byte of any file.  The slabs are then those of frog_glm_smooth_planes, which leave room for the scratch
+// of a slab's halo, and the line "stats :" names the FWHM, sigma and the three radii.
 // The device holds slabs of frog_glm_planes z-planes, or -rp planes if that is fewer; the slab count is printed and changes no
 // bit of any file.  Every input is checked before anything is written.
 #include "group_tool.h"
@@ -117,11 +122,12 @@ int main(int argc, char *argv[])
     int device = 0, flips = 0, twoSided = 0, connectivity = 26;
     long minCount = 1, nPerms = 0, planesOption = 0;
     unsigned long long seed = 0;
-    double sigmaFloor = 0, clusterThreshold = 0, tfceStep = 0.1, tfceE = 0.5, tfceH = 2;
+    double sigmaFloor = 0, clusterThreshold = 0, tfceStep = 0.1, tfceE = 0.5, tfceH = 2, fwhm = 0;
+    std::string fwhmText = "0";
     float fill = 0;
     bool planesGiven = false, permOption = false, clusterTest = false, connectivityGiven = false, tfceOption = false;
     int tfceTest = 0;
-    int a = positional_arguments(argc, argv, 1, { "-c", "-td", "-o", "-v", "-vl", "-ml", "-m", "-mc", "-sf", "-f", "-np", "-ps", "-pc", "-pf", "-two", "-ct", "-cc", "-tf", "-tfd", "-tfe", "-tfh", "-rp", "-dev" },
+    int a = positional_arguments(argc, argv, 1, { "-c", "-td", "-o", "-v", "-vl", "-ml", "-m", "-mc", "-sf", "-f", "-np", "-ps", "-pc", "-pf", "-two", "-ct", "-cc", "-tf", "-tfd", "-tfe", "-tfh", "-s", "-rp", "-dev" },
                                  positional);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
@@ -146,6 +152,7 @@ int main(int argc, char *argv[])
         else if (std::strcmp(key, "-tfd") == 0) { tfceStep = atof(value); tfceOption = true; }
         else if (std::strcmp(key, "-tfe") == 0) { tfceE = atof(value); tfceOption = true; }
         else if (std::strcmp(key, "-tfh") == 0) { tfceH = atof(value); tfceOption = true; }
+        else if (std::strcmp(key, "-s") == 0) fwhmText = value;
         else if (std::strcmp(key, "-rp") == 0) { planesOption = atol(value); planesGiven = true; }
         else if (std::strcmp(key, "-dev") == 0) device = atoi(value);
         else die(std::string("unknown option ") + key);
@@ -154,7 +161,7 @@ int main(int argc, char *argv[])
         std::cout << "Usage : GroupStats bbox.json spacing design.csv [-c contrasts.csv] [-td transformsDir] [-o outDir] "
                      "[-v jacobian|logjacobian|images] [-vl volumes.txt] [-ml masks.txt] [-m regionMask] [-mc minCount] [-sf sigmaFloor] "
                      "[-f fill] [-np nPerms] [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-tf 1] [-tfd dh] [-tfe 0.5|1] [-tfh 1|2] "
-                     "[-rp planes] [-dev n]\n-tf 1: threshold-free cluster enhancement in steps of dh (default 0.1); a statistic beyond 255 * dh "
+                     "[-s fwhm_mm] [-rp planes] [-dev n]\n-tf 1: threshold-free cluster enhancement in steps of dh (default 0.1); a statistic beyond 255 * dh "
                      "saturates there" << std::endl;
         return 1;
     }
@@ -178,6 +185,12 @@ int main(int argc, char *argv[])
     if (clusterTest && (!(clusterThreshold >= 0.0) || !std::isfinite((float)clusterThreshold))) die("-ct takes a threshold that is finite and not negative");
     if (connectivity != 6 && connectivity != 18 && connectivity != 26) die("-cc takes 6, 18 or 26");
     if (planesGiven && planesOption < 1) die("-rp takes a number of planes, at least 1");
+    {
+        char *end = nullptr;
+        fwhm = std::strtod(fwhmText.c_str(), &end);
+        if (fwhmText.empty() || *end || !(fwhm >= 0.0) || !std::isfinite(fwhm)) die("-s takes a FWHM in mm that is finite and not negative, not '" + fwhmText + "'");
+    }
+    const double smoothSigma = fwhm / FROG_SMOOTH_FWHM;
     const auto design = read_table(positional[2], "the design");
     const size_t n = design.size(), p = design[0].size();
     if (n > FROG_GLM_MAX_IMAGES) die("at most " + std::to_string(FROG_GLM_MAX_IMAGES) + " images");
@@ -230,6 +243,9 @@ int main(int argc, char *argv[])
     frog_volume grid;
     if (frog_bbox_grid(positional[0].c_str(), atof(positional[1].c_str()), &grid))
         die("cannot read a bounding box from " + positional[0] + " (or spacing " + positional[1] + " is not positive)");
+    uint32_t radius[3] = { 0, 0, 0 };
+    for (int k = 0; k < 3 && smoothSigma > 0.0; k++)
+        if (frog_smooth_taps(smoothSigma, grid.spacing[k], &radius[k], nullptr)) die("-s " + fwhmText + ": " + frog_last_error());
     ChainArguments transforms;
     const auto inverse = inverse_transforms(transforms, transformsDir, n);
     std::vector<frog_volume> supports(volumes.size());
@@ -275,11 +291,15 @@ int main(int argc, char *argv[])
     auto t0 = clk::now();
     std::vector<frog_chain *> chains = create_chains(inverse, device);
     uint32_t planes = 0;
-    if (frog_glm_planes(&grid, (uint32_t)n, device, &planes)) die(frog_last_error());
+    if (smoothSigma > 0.0 ? frog_glm_smooth_planes(&grid, (uint32_t)n, smoothSigma, device, &planes) : frog_glm_planes(&grid, (uint32_t)n, device, &planes))
+        die(frog_last_error());
     if (planesGiven && (uint64_t)planesOption < planes) planes = (uint32_t)planesOption;
     const uint32_t depth = grid.dims[2], slabs = (depth + planes - 1) / planes;
     std::cout << "stats : " << slabs << (slabs == 1 ? " slab of " : " slabs of ") << planes << " planes, " << p << " columns, " << n_c << " contrasts, "
-              << nPerms << " permutations" << std::endl;
+              << nPerms << " permutations";
+    if (smoothSigma > 0.0)
+        std::cout << ", smoothed: FWHM " << fwhm << " mm, sigma " << smoothSigma << " mm, radii " << radius[0] << " " << radius[1] << " " << radius[2] << " voxels";
+    std::cout << std::endl;
     std::vector<uint32_t> perm;
     std::vector<int8_t> sign;
     if (nPerms) {
@@ -303,6 +323,7 @@ int main(int argc, char *argv[])
         frog_glm *glm = nullptr;
         t0 = clk::now();
         if (frog_glm_create(&grid, first, count_planes, (uint32_t)n, (uint32_t)p, X.data(), device, &glm)) die(frog_last_error());
+        if (smoothSigma > 0.0 && frog_glm_smooth(glm, smoothSigma)) die(frog_last_error());
         times.device_s += seconds(t0);
         std::unique_ptr<frog::VolumeStream> stream(images ? new frog::VolumeStream(volumes, threads, window) : nullptr);
         std::unique_ptr<frog::VolumeStream> maskStream(masks.empty() ? nullptr : new frog::VolumeStream(masks, threads, window));

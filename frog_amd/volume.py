@@ -365,7 +365,7 @@ class GroupGLM(_Accumulator):
 
     _NAME = "glm"
 
-    def __init__(self, grid, design, window=None, device=0):
+    def __init__(self, grid, design, window=None, device=0, smooth=0.0):
         X = np.ascontiguousarray(design, np.float64)
         if X.ndim != 2:
             raise ValueError("design: one row per image, one column per regressor")
@@ -374,6 +374,17 @@ class GroupGLM(_Accumulator):
         self.design = X
         self.window = (first, planes)
         self.shape = (planes,) + self.dims[1::-1]
+        if smooth:
+            try:
+                self.smooth(smooth)
+            except Exception:
+                self.close()
+                raise
+
+    def smooth(self, sigma):
+        """Before the first add: every add from now on stores its map smoothed by the coverage-aware Gaussian of `sigma` mm
+        (smooth_volume() of the whole-grid map, of which the window's part is kept); 0 turns it off (frog_glm_smooth)."""
+        _abi.check(self._lib.frog_glm_smooth(self._h, float(sigma)), "frog_glm_smooth")
 
     def add(self, volume, chain=None, mask=None, interpolation=1, background=0.0):
         """Keeps `volume` where CoverAverage.add with the same arguments would count it and its value is finite."""
@@ -568,13 +579,48 @@ def cluster_p(extent, max_extent):
     return ((1 + beyond).astype(np.float64) / np.float64(len(null) + 1)).astype(np.float32)
 
 
-def glm_planes(grid, n_images, device=0):
-    """The most z-planes of `grid` a GroupGLM window for n_images may hold on the device now (frog_glm_planes)."""
+def glm_planes(grid, n_images, device=0, smooth=0.0):
+    """The most z-planes of `grid` a GroupGLM window for n_images may hold on the device now (frog_glm_planes); with `smooth`
+    (sigma in mm) together with the scratch of the window's halo (frog_glm_smooth_planes)."""
     dims, origin, spacing = grid
     g = _abi.volume_view(None, origin, spacing, tuple(int(d) for d in dims))
     planes = C.c_uint32()
-    _abi.check(_abi.hip_lib().frog_glm_planes(C.byref(g), int(n_images), int(device), C.byref(planes)), "frog_glm_planes")
+    if smooth:
+        _abi.check(_abi.hip_lib().frog_glm_smooth_planes(C.byref(g), int(n_images), float(smooth), int(device), C.byref(planes)),
+                   "frog_glm_smooth_planes")
+    else:
+        _abi.check(_abi.hip_lib().frog_glm_planes(C.byref(g), int(n_images), int(device), C.byref(planes)), "frog_glm_planes")
     return planes.value
+
+
+SMOOTH_FWHM = _abi.FROG_SMOOTH_FWHM         # fwhm = SMOOTH_FWHM * sigma (2 sqrt(2 ln 2))
+
+
+def smooth_taps(sigma, spacing):
+    """(radius, taps float64 (radius + 1,)) of one axis of the Gaussian of `sigma` mm at `spacing` mm (frog_smooth_taps):
+    radius = ceil(3 sigma / spacing), taps[d] = exp(-(d spacing)^2 / (2 sigma^2)), taps[0] == 1.  Host code: no device is
+    needed.  The device uses exactly these doubles."""
+    radius = C.c_uint32()
+    taps = np.zeros(_abi.FROG_SMOOTH_MAX_RADIUS + 1, np.float64)
+    _abi.check(_abi.hip_lib().frog_smooth_taps(float(sigma), float(spacing), C.byref(radius), taps.ctypes.data_as(_abi.c_double_p)),
+               "frog_smooth_taps")
+    return radius.value, taps[:radius.value + 1].copy()
+
+
+def smooth_volume(volume, sigma, take=None, spacing=(1.0, 1.0, 1.0), device=0):
+    """The float32 array volume[z, y, x] smoothed by the coverage-aware Gaussian of `sigma` mm (frog_smooth_volume): the
+    normalised convolution over the voxels that take part -- those with a finite value and, with `take`, a non-zero flag --
+    with `spacing` = (x, y, z) in mm.  float32; NaN (0x7FC00000) where the voxel does not take part.  fwhm = SMOOTH_FWHM *
+    sigma."""
+    a = np.ascontiguousarray(volume)
+    v = _abi.volume_view(a, (0.0, 0.0, 0.0), tuple(float(s) for s in spacing))
+    flags = None if take is None else np.ascontiguousarray(np.asarray(take) != 0, np.uint8)
+    if flags is not None and flags.shape != a.shape:
+        raise ValueError("take: one flag per voxel")
+    out = np.empty(a.shape, np.float32)
+    _abi.check(_abi.hip_lib().frog_smooth_volume(C.byref(v), None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_uint8)), float(sigma),
+                                                 int(device), out.ctypes.data_as(_abi.c_float_p)), "frog_smooth_volume")
+    return out
 
 
 def glm_draw(n, n_perms, seed=0, shuffle=True, flip=False):
@@ -610,7 +656,7 @@ def fwe_p(t, max_t, min_t=None, fit=None):
 
 def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=None, value="logjacobian", supports=None, interpolation=1,
               min_count=1, sigma_floor=0.0, region=None, fill=0.0, n_perms=0, seed=0, columns=None, flip=False, two_sided=False,
-              max_planes=None, device=0, cluster_threshold=None, connectivity=26, tfce=False):
+              max_planes=None, device=0, cluster_threshold=None, connectivity=26, tfce=False, smooth=0.0):
     """The per-voxel linear model of a registered group (bin/GroupStats).  value "logjacobian" or "jacobian": image i is the
     (log) Jacobian determinant of chains[i] on `grid`, counted where the chain lands inside supports[i] (a geometry, optional)
     and masks[i]; value "images": volumes[i] resliced as in cover_average().  With n_perms > 0 the columns `columns` (default
@@ -628,7 +674,10 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
     threshold-free cluster enhancement: one TfceSink for the whole grid, filled by every slab with a permute call of its own.
     max_tfce float32 (n_perms, n_contrasts): the largest enhanced value under each permutation, with two_sided the larger of
     the two sides'.  tfce float32 (n_contrasts,) + shape: the observed enhanced map, with two_sided +tfce of the positive side
-    and -tfce of the negative.  tfce_p float32: tfce_p() of the map against max_tfce."""
+    and -tfce of the negative.  tfce_p float32: tfce_p() of the map against max_tfce.
+    With smooth (sigma in mm; fwhm = SMOOTH_FWHM * sigma = 2.3548... * sigma) every image's map is smoothed before the fit by
+    the coverage-aware Gaussian of smooth_volume(), over the voxels at which the image takes part; the slabs are then those of
+    glm_planes(smooth=...), which leave room for the scratch of a slab's halo, and still change no bit."""
     X = np.ascontiguousarray(design, np.float64)
     c = np.ascontiguousarray(contrasts, np.float64).reshape(-1, X.shape[1])
     n = X.shape[0]
@@ -644,7 +693,7 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
     dims = tuple(int(d) for d in grid[0])
     shape = dims[::-1]
     reg = None if region is None else np.asarray(region) != 0
-    planes = glm_planes(grid, n, device)
+    planes = glm_planes(grid, n, device, smooth)
     if max_planes is not None:
         planes = max(1, min(planes, int(max_planes)))
     if columns is None:
@@ -661,7 +710,7 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
         enhance = TfceSink(grid, n_perms, len(c), opt["dh"], opt["e"], opt["h"], two_sided, opt["connectivity"], device)
     for first in range(0, dims[2], planes):
         m = min(planes, dims[2] - first)
-        acc = GroupGLM(grid, X, (first, m), device)
+        acc = GroupGLM(grid, X, (first, m), device, smooth)
         try:
             for k in range(n):
                 mask = None if masks is None else masks[k]

@@ -776,6 +776,64 @@ int  frog_tfce_levels(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, 
 int  frog_tfce_map(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, float *tfce);
 void frog_tfce_destroy(frog_tfce *s);
 
+/* ---- smoothing the maps before the fit: a coverage-aware Gaussian (an extension; the reference has no counterpart) --------------
+ * A normalised convolution over the voxels that take part (Knutsson and Westin, CVPR 1993): the background of an image's field
+ * of view is not pulled into its rim, and the set of voxels that take part does not change.  sigma is in mm and isotropic; each
+ * axis has its own spacing, so the radii and the taps differ per axis.  fwhm = FROG_SMOOTH_FWHM * sigma.
+ *
+ * frog_smooth_taps (host code, no device): the radius and the taps w_0 .. w_R of one axis with spacing s.  Every line is one
+ * rounded f64 operation, exp is the host libm's:
+ *       q = 3.0 * sigma;  q = q / s;  R = (uint32_t)ceil(q)
+ *       den = 2.0 * sigma;  den = den * sigma
+ *       for d = 0 .. R:  x = (double)d * s;  x = x * x;  x = x / den;  w_d = exp(-x)
+ *   w_0 is exactly 1: the quotient below normalises, not the taps.  taps (FROG_SMOOTH_MAX_RADIUS + 1 doubles, of which R + 1 are
+ *   written) may be NULL.  The taps are DATA: the device code uses exactly the doubles this function returns, uploaded as they
+ *   are, so nothing below depends on any exp being correctly rounded.
+ *
+ * A SMOOTHED VOLUME, of f32 values x with a per-voxel "takes part".  Two f64 fields start per voxel as
+ *       num = takes part ? (double)x : +0.0          den = takes part ? 1.0 : +0.0
+ *   Three passes follow, along x, then y, then z, each applied to both fields with the axis's R and taps.  Per voxel v and field:
+ *       acc = +0.0;  for d = -R .. +R ascending:  m = w_|d| * in(v + d * e_axis);  acc = acc + m
+ *   where a neighbour outside the grid contributes the term +0.0.  Every line is one rounded f64 operation, no contraction; a
+ *   pass reads the f64 values the pass before it gave, never rounded to f32.  No sum is ever -0.0 (it starts from +0.0, and
+ *   round-to-nearest gives +0.0 for x + (-x)), so a term of +0.0 changes no bit: the sums carry the bits of the loop over the
+ *   neighbours inside the grid alone, and a voxel that does not take part counts exactly as one outside the grid.
+ *       result = (float)(num / den)     where the voxel itself takes part: one correctly rounded division; den >= 1 there,
+ *                                       because w_0 == 1 and every term is >= +0.0
+ *       result = 0x7FC00000             where it does not
+ *   Smoothing never changes which voxels take part: counts and coverage stay as they are.  A voxel that takes part and has no
+ *   participating neighbour within the radii keeps its value exactly (num = x, den = 1; a -0.0 comes back as +0.0).  No floating-point atomic is used and
+ *   no result depends on scheduling, on how a launch is cut, or on windows.
+ *
+ * frog_smooth_volume: any FROG_V_F32 volume with host data, smoothed on `device` with the volume's own spacing; out is f32,
+ *   grid-sized.  take (u8, grid-sized) may be NULL: then a voxel takes part iff its value is finite; with take iff its flag is
+ *   non-zero and its value is finite.  sigma_mm == 0: every radius is 0, so a voxel that takes part keeps its value.
+ *
+ * frog_glm_smooth: legal only before the first add (FROG_E_STATE after one); sigma_mm == 0 turns smoothing off, which is how an
+ *   accumulator starts.  Afterwards every frog_glm_add and frog_glm_add_jacobian stores the smoothed value in place of the raw
+ *   one: the RAW MAP of add i is what the same call without smoothing would store at every voxel of the WHOLE grid, a voxel
+ *   takes part iff its raw entry is not 0x7FC00000, the map is smoothed as above with the grid's spacing, and the window's part
+ *   is kept.  So windows that partition the grid still give, bit for bit, what one whole-grid window gives, and everything
+ *   stated on the stored plane above -- frog_glm_plane, finish, the three permute calls and their sinks -- holds as it stands.
+ *   The add evaluates the raw map on the window extended by R_z planes on each side, clipped at the grid's ends, with the same
+ *   device code on a larger range: a halo costs extra evaluations only where the grid is cut into windows.
+ *   Device memory: 36 bytes per voxel of that extended range, allocated by frog_glm_smooth.  FROG_E_NOMEM, with the bytes needed
+ *   and the bytes free in the message, when it does not fit; the accumulator then stays unsmoothed.
+ * frog_glm_smooth_planes: frog_glm_planes with the scratch of the halo counted: the most planes p such that the n_images planes
+ *   of p z-planes and 36 bytes per voxel of min(p + 2 R_z, dims[2]) planes fit half of the free device memory; sigma_mm == 0
+ *   gives frog_glm_planes' answer.
+ *
+ * FROG_E_INVALID, before the device is touched: a NULL argument that is not marked optional, a sigma that is negative or not
+ * finite (in frog_smooth_taps also 0), a spacing that is not finite or not above 0, a radius above
+ * FROG_SMOOTH_MAX_RADIUS along any axis, a volume that is not FROG_V_F32, has no data, is empty or above 2^31 voxels,
+ * everything frog_glm_planes refuses. */
+#define FROG_SMOOTH_MAX_RADIUS 64
+#define FROG_SMOOTH_FWHM 2.3548200450309493         /* 2 sqrt(2 ln 2): sigma = fwhm / FROG_SMOOTH_FWHM */
+int  frog_smooth_taps(double sigma_mm, double spacing, uint32_t *radius, double *taps);
+int  frog_smooth_volume(const frog_volume *volume, const uint8_t *take, double sigma_mm, int device, float *out);
+int  frog_glm_smooth(frog_glm *a, double sigma_mm);
+int  frog_glm_smooth_planes(const frog_volume *grid, uint32_t n_images, double sigma_mm, int device, uint32_t *planes);
+
 #ifdef __cplusplus
 }
 #endif
