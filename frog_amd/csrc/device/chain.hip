@@ -1124,6 +1124,13 @@ struct frog_glm : frog_windowed {
     SmoothPlan smooth;                              // frog_glm_smooth's; off at first
 };
 
+// what glm_fit_kernel stores besides the extrema: nothing, the bits of a frog_clusters or the levels of a frog_tfce
+struct GlmStore {
+    enum Kind { NONE, BITS, LEVELS } kind = NONE;
+    GlmSink bits{};
+    GlmLevelSink levels{};
+};
+
 // what the sinks of a permutation test hold alike (frog_clusters, frog_tfce): one slot per permutation, contrast and side for
 // the whole grid, and which planes of it each permutation has received
 struct frog_sink : frog_group {
@@ -1132,12 +1139,12 @@ struct frog_sink : frog_group {
     size_t slots = 0;                               // n_perms * n_contrasts * sides
     uint32_t batch = 0;                             // the slots one launch labels: the workspace holds that many
     std::vector<uint8_t> received;                  // [perm * nz + z]: the plane has been written for the permutation's slots
+    GlmStore store;                                 // the sink as the fit kernel sees it; `first` and `perm0` are a launch's
 };
 
 // the supra-threshold voxels of every permutation, contrast and side of a permutation test on one grid, as bit masks of
 // ccl.words words, and the workspace that labels their connected components
 struct frog_clusters : frog_sink {
-    float threshold = 0;
     frog::DevBuf<uint32_t> d_bits, d_parent, d_extent, d_stats;
 };
 
@@ -2200,25 +2207,19 @@ int glm_fit_arguments(const char *where, const frog_glm *a, uint32_t n_contrasts
 }
 
 // The fit kernel over the window for the n_perms permutations whose rows d_table holds: instantiated on the number of columns
-// and on whether the values of a voxel stay in LDS.  With a sink, the kernel that also stores the bits or the levels.
-struct GlmSinks {
-    const GlmSink *bits = nullptr;
-    const GlmLevelSink *levels = nullptr;           // at most one of the two
-};
-
+// and on whether the values of a voxel stay in LDS.  With a sink's store, the kernel that also stores the bits or the levels.
 template <int P, bool LDS>
-hipError_t glm_fit_go(const frog_glm *a, const GlmArgs &f, const GlmSinks &to, size_t bytes)
+hipError_t glm_fit_go(const frog_glm *a, const GlmArgs &f, const GlmStore &to, size_t bytes)
 {
-    const GlmSink *const sink = to.bits;
     // one block per tile: the work-items are the tiles padded to whole blocks, so a launch chunk never splits a tile
     return chunked_launch(f.tiles * LAUNCH_BLOCK, [&](unsigned blocks, size_t base) {
-        if (sink) glm_fit_kernel<P, LDS, GlmSink><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f, *sink);
-        else if (to.levels) glm_fit_kernel<P, LDS, GlmLevelSink><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f, *to.levels);
+        if (to.kind == GlmStore::BITS) glm_fit_kernel<P, LDS, GlmSink><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f, to.bits);
+        else if (to.kind == GlmStore::LEVELS) glm_fit_kernel<P, LDS, GlmLevelSink><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f, to.levels);
         else glm_fit_kernel<P, LDS><<<blocks, LAUNCH_BLOCK, bytes>>>(base, a->d_vals.p, a->d_table.p, f);
     });
 }
 
-hipError_t glm_fit_launch(const frog_glm *a, const GlmArgs &f, const GlmSinks &sink = GlmSinks{})
+hipError_t glm_fit_launch(const frog_glm *a, const GlmArgs &f, const GlmStore &sink = GlmStore{})
 {
     const bool lds = a->n_images <= GLM_LDS_MAX;
     const size_t bytes = (f.extrema ? (size_t)f.n_perms * f.n_contrasts * 2 * sizeof(uint32_t) : 0) + (lds ? (size_t)a->n_images * 256 * sizeof(float) : 0);
@@ -2278,9 +2279,8 @@ int glm_fit_args(const char *where, frog_glm *a, uint32_t n_contrasts, const dou
 // and the launches, which with a sink store the bits or the levels of row k in the sink's permutation first_perm + k
 int glm_permute(const char *where, frog_glm *a, uint32_t n_contrasts, const double *contrasts, uint32_t min_count, double sigma_floor,
                 const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign, uint32_t first_perm,
-                frog_clusters *clusters, frog_tfce *tfce, float *max_t, float *min_t)
+                frog_sink *sink, float *max_t, float *min_t)
 {
-    frog_sink *const sink = clusters ? static_cast<frog_sink *>(clusters) : tfce;
     const std::string w = std::string(where) + ": ";
     if (int rc = glm_fit_arguments(where, a, n_contrasts, contrasts, min_count, sigma_floor)) return rc;
     if (!n_contrasts || !n_perms || !perm || (!sink && !max_t && !min_t)) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
@@ -2315,6 +2315,8 @@ int glm_permute(const char *where, frog_glm *a, uint32_t n_contrasts, const doub
     for (size_t e = 0; e < n_ext; e++) ext[e] = (e & 1) ? GLM_KEY_POS_INF : GLM_KEY_NEG_INF;
     GlmArgs f;
     if (int rc = glm_fit_args(where, a, n_contrasts, contrasts, min_count, sigma_floor, region, d_region, &f)) return rc;
+    GlmStore to = sink ? sink->store : GlmStore{};  // what the sink wants stored, at this window
+    to.bits.first = to.levels.first = a->first;
     hipError_t e = hipMemcpy(d_perm.p, perm, entries * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && sign) e = hipMemcpy(d_sign.p, sign, entries, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_ext.p, ext.data(), n_ext * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -2327,9 +2329,8 @@ int glm_permute(const char *where, frog_glm *a, uint32_t n_contrasts, const doub
         e = glm_table_launch(a, d_perm.p + at, sign ? d_sign.p + at : nullptr, columns, nb);
         f.n_perms = nb;
         f.extrema = d_ext.p + (size_t)k0 * n_contrasts * 2;
-        const GlmSink bits = clusters ? GlmSink{ clusters->d_bits.p, clusters->ccl.words, a->first, first_perm + k0, clusters->sides, clusters->threshold } : GlmSink{};
-        const GlmLevelSink levels = tfce ? GlmLevelSink{ tfce->d_levels.p, tfce->stride, a->first, first_perm + k0, tfce->sides, tfce->par.dh } : GlmLevelSink{};
-        if (e == hipSuccess) e = glm_fit_launch(a, f, GlmSinks{ clusters ? &bits : nullptr, tfce ? &levels : nullptr });
+        to.bits.perm0 = to.levels.perm0 = first_perm + k0;
+        if (e == hipSuccess) e = glm_fit_launch(a, f, to);
     }
     if (e == hipSuccess) e = hipMemcpy(ext.data(), d_ext.p, n_ext * sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(where, e);
@@ -2394,22 +2395,72 @@ hipError_t ccl_labels_out(const CclGrid &g, const uint32_t *d_mask, const uint32
     return hipSuccess;
 }
 
-// what frog_clusters_mask, frog_clusters_labels, frog_tfce_levels and frog_tfce_map refuse alike; the slot's index through `slot`
-int clusters_slot(const char *where, const frog_sink *s, uint32_t perm, uint32_t contrast, int side, const void *out, size_t *slot)
-{
-    if (!s || !out) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
-    if (perm >= s->n_perms || contrast >= s->n_contrasts || side < 0 || (uint32_t)side >= s->sides)
-        return fail(FROG_E_INVALID, std::string(where) + ": no such permutation, contrast or side in the sink");
-    *slot = ((size_t)perm * s->n_contrasts + contrast) * s->sides + (uint32_t)side;
-    return FROG_OK;
-}
-
 // whether every z-plane of permutations [first, first + count) has been written
-bool clusters_complete(const frog_sink *s, uint32_t first, uint32_t count)
+bool sink_complete(const frog_sink *s, uint32_t first, uint32_t count)
 {
     const size_t depth = s->grid.dims[2];
     return std::find(s->received.begin() + first * depth, s->received.begin() + ((size_t)first + count) * depth, (uint8_t)0)
            == s->received.begin() + ((size_t)first + count) * depth;
+}
+
+// how a slot's read-out begins: the refusals (with `complete`, also of a permutation that lacks planes), the slot's index, the device
+int sink_slot(const char *where, const frog_sink *s, uint32_t perm, uint32_t contrast, int side, const void *out, bool complete, size_t *slot)
+{
+    if (!s || !out) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (perm >= s->n_perms || contrast >= s->n_contrasts || side < 0 || (uint32_t)side >= s->sides)
+        return fail(FROG_E_INVALID, std::string(where) + ": no such permutation, contrast or side in the sink");
+    if (complete && !sink_complete(s, perm, 1)) return fail(FROG_E_STATE, std::string(where) + ": the permutation has not received every plane of the grid");
+    *slot = ((size_t)perm * s->n_contrasts + contrast) * s->sides + (uint32_t)side;
+    KCHECK(hipSetDevice(s->device));
+    return FROG_OK;
+}
+
+// The frame of frog_clusters_create and frog_tfce_create: the refusals, the sink's own() after the shared ones; the new sink
+// with frog_sink's fields; the memory budget from sizes(ccl) = (device bytes a slot keeps, bytes of one slot's workspace), which
+// holds `batch` slots: as many as fit half of what the slots leave free.  Bytes beyond size_t are refused like bytes beyond the device.
+template <class S, class Own, class Sizes>
+int sink_new(const char *where, const char *noun, const frog_volume *grid, uint32_t n_perms, uint32_t n_contrasts, int two_sided, int connectivity,
+             int device, S **out, Own own, Sizes sizes, std::unique_ptr<S> &s)
+{
+    const std::string w = std::string(where) + ": ";
+    size_t total, free_bytes = 0, device_bytes = 0;
+    if (int rc = group_arguments(where, grid, out, &total)) return rc;
+    if (!n_perms || !n_contrasts) return fail(FROG_E_INVALID, w + "at least one permutation and one contrast");
+    if (n_contrasts > FROG_GLM_MAX_CONTRASTS) return fail(FROG_E_INVALID, w + "at most " + std::to_string(FROG_GLM_MAX_CONTRASTS) + " contrasts");
+    if (int rc = own()) return rc;
+    if (!ccl_order(connectivity)) return fail(FROG_E_INVALID, w + "connectivity 6, 18 or 26");
+    if (int rc = group_new(grid, total, device, s)) return rc;
+    s->n_perms = n_perms;
+    s->n_contrasts = n_contrasts;
+    s->sides = two_sided ? 2u : 1u;
+    s->ccl = ccl_grid(grid, total, connectivity);
+    s->slots = (size_t)n_perms * n_contrasts * s->sides;
+    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
+    const auto [per_slot, work_bytes] = sizes(s->ccl);
+    const bool countable = s->slots <= (std::numeric_limits<size_t>::max() - work_bytes) / per_slot;
+    const size_t slot_bytes = countable ? s->slots * per_slot : 0;
+    if (!countable || slot_bytes + work_bytes > free_bytes)
+        return fail(FROG_E_NOMEM, w + std::to_string(s->slots) + " " + noun + " and the workspace need " +
+                                  (countable ? std::to_string(slot_bytes + work_bytes) : std::string("more than 2^64")) + " bytes of device memory, " +
+                                  std::to_string(free_bytes) + " are free");
+    s->batch = (uint32_t)std::min<size_t>(std::min<size_t>(s->slots, CCL_BATCH), std::max<size_t>(1, (free_bytes - slot_bytes) / 2 / work_bytes));
+    s->received.assign((size_t)n_perms * grid->dims[2], 0);
+    return FROG_OK;
+}
+
+// The frame of frog_clusters_finish and frog_tfce_finish: every permutation must be complete; then each(at, n) for the slots
+// [at, at + n) of every batch, and copy_out() once.
+template <class Each, class Out>
+int sink_finish(const char *where, frog_sink *s, const void *out, Each each, Out copy_out)
+{
+    if (!s || !out) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (!sink_complete(s, 0, s->n_perms)) return fail(FROG_E_STATE, std::string(where) + ": a permutation has not received every plane of the grid");
+    KCHECK(hipSetDevice(s->device));
+    hipError_t e = hipSuccess;
+    for (size_t at = 0; at < s->slots && e == hipSuccess; at += s->batch) e = each(at, (uint32_t)std::min<size_t>(s->batch, s->slots - at));
+    if (e == hipSuccess) e = copy_out();
+    if (e != hipSuccess) return hip_fail(where, e);
+    return FROG_OK;
 }
 
 // ---- threshold-free cluster enhancement (k_tfce.hip.h) ---------------------------------------------------------------------------
@@ -3244,7 +3295,7 @@ int frog_glm_permute(frog_glm *a, uint32_t n_contrasts, const double *contrasts,
                      const uint8_t *region, uint32_t columns, uint32_t n_perms, const uint32_t *perm, const int8_t *sign,
                      float *max_t, float *min_t)
 {
-    return glm_permute("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, 0, nullptr, nullptr, max_t, min_t);
+    return glm_permute("frog_glm_permute", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, 0, nullptr, max_t, min_t);
 }
 
 int frog_glm_draw(uint32_t n, uint32_t n_perms, uint64_t seed, int shuffle, int flip, uint32_t *perm, int8_t *sign)
@@ -3304,34 +3355,19 @@ int frog_components(const frog_volume *mask, int connectivity, int device, uint3
 int frog_clusters_create(const frog_volume *grid, uint32_t n_perms, uint32_t n_contrasts, int two_sided, float threshold, int connectivity,
                          int device, frog_clusters **out)
 {
-    size_t total;
-    if (int rc = group_arguments("frog_clusters_create", grid, out, &total)) return rc;
-    if (!n_perms || !n_contrasts) return fail(FROG_E_INVALID, "frog_clusters_create: at least one permutation and one contrast");
-    if (n_contrasts > FROG_GLM_MAX_CONTRASTS) return fail(FROG_E_INVALID, "frog_clusters_create: at most " + std::to_string(FROG_GLM_MAX_CONTRASTS) + " contrasts");
-    if (!(threshold >= 0.0f) || !std::isfinite(threshold)) return fail(FROG_E_INVALID, "frog_clusters_create: the threshold must be finite and not negative");
-    if (!ccl_order(connectivity)) return fail(FROG_E_INVALID, "frog_clusters_create: connectivity 6, 18 or 26");
     std::unique_ptr<frog_clusters> s;
-    if (int rc = group_new(grid, total, device, s)) return rc;
-    s->n_perms = n_perms;
-    s->n_contrasts = n_contrasts;
-    s->sides = two_sided ? 2u : 1u;
-    s->threshold = threshold;
-    s->ccl = ccl_grid(grid, total, connectivity);
-    s->slots = (size_t)n_perms * n_contrasts * s->sides;
-    // the masks, and a workspace of two words per voxel for as many masks of a launch as fit, up to CCL_BATCH
-    size_t free_bytes = 0, device_bytes = 0;
-    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
-    const size_t mask_bytes = s->slots * s->ccl.words * sizeof(uint32_t) + s->slots * 2 * sizeof(uint32_t), work_bytes = total * 2 * sizeof(uint32_t);
-    if (mask_bytes + work_bytes > free_bytes)
-        return fail(FROG_E_NOMEM, "frog_clusters_create: " + std::to_string(s->slots) + " masks and the workspace need " + std::to_string(mask_bytes + work_bytes) +
-                                  " bytes of device memory, " + std::to_string(free_bytes) + " are free");
-    s->batch = (uint32_t)std::min<size_t>(std::min<size_t>(s->slots, CCL_BATCH), std::max<size_t>(1, (free_bytes - mask_bytes) / 2 / work_bytes));
+    // a slot keeps its mask and two words of statistics; a slot's workspace is two words per voxel
+    if (int rc = sink_new("frog_clusters_create", "masks", grid, n_perms, n_contrasts, two_sided, connectivity, device, out, [&]() {
+            const bool good = threshold >= 0.0f && std::isfinite(threshold);
+            return good ? (int)FROG_OK : fail(FROG_E_INVALID, "frog_clusters_create: the threshold must be finite and not negative");
+        }, [](const CclGrid &g) { return std::make_pair(g.words * sizeof(uint32_t) + 2 * sizeof(uint32_t), g.total * 2 * sizeof(uint32_t)); }, s)) return rc;
     KCHECK(s->d_bits.alloc(s->slots * s->ccl.words));
     KCHECK(s->d_stats.alloc(s->slots * 2));
-    KCHECK(s->d_parent.alloc((size_t)s->batch * total));
-    KCHECK(s->d_extent.alloc((size_t)s->batch * total));
+    KCHECK(s->d_parent.alloc((size_t)s->batch * s->total));
+    KCHECK(s->d_extent.alloc((size_t)s->batch * s->total));
     KCHECK(hipMemset(s->d_bits.p, 0, s->d_bits.bytes()));
-    s->received.assign((size_t)n_perms * grid->dims[2], 0);
+    s->store.kind = GlmStore::BITS;
+    s->store.bits = GlmSink{ s->d_bits.p, s->ccl.words, 0, 0, s->sides, threshold };
     *out = s.release();
     return FROG_OK;
 }
@@ -3341,22 +3377,16 @@ int frog_glm_permute_clusters(frog_glm *a, uint32_t n_contrasts, const double *c
                               uint32_t first_perm, frog_clusters *sink, float *max_t, float *min_t)
 {
     if (!sink) return fail(FROG_E_INVALID, "bad arguments to frog_glm_permute_clusters");
-    return glm_permute("frog_glm_permute_clusters", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, first_perm,
-                       sink, nullptr, max_t, min_t);
+    return glm_permute("frog_glm_permute_clusters", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, first_perm, sink, max_t, min_t);
 }
 
 int frog_clusters_finish(frog_clusters *s, uint32_t *max_extent)
 {
-    if (!s || !max_extent) return fail(FROG_E_INVALID, "bad arguments to frog_clusters_finish");
-    if (!clusters_complete(s, 0, s->n_perms)) return fail(FROG_E_STATE, "frog_clusters_finish: a permutation has not received every plane of the grid");
-    KCHECK(hipSetDevice(s->device));
-    hipError_t e = hipMemset(s->d_stats.p, 0, s->d_stats.bytes());
-    for (size_t at = 0; at < s->slots && e == hipSuccess; at += s->batch)
-        e = ccl_label(s->ccl, s->d_bits.p + at * s->ccl.words, (uint32_t)std::min<size_t>(s->batch, s->slots - at), s->d_parent.p, s->d_extent.p,
-                      s->d_stats.p + 2 * at);
-    std::vector<uint32_t> stats(s->slots * 2);
-    if (e == hipSuccess) e = hipMemcpy(stats.data(), s->d_stats.p, s->d_stats.bytes(), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail("frog_clusters_finish", e);
+    std::vector<uint32_t> stats(s ? s->slots * 2 : 0);
+    if (int rc = sink_finish("frog_clusters_finish", s, max_extent, [&](size_t at, uint32_t n) {
+            const hipError_t e = hipMemset(s->d_stats.p + 2 * at, 0, 2 * n * sizeof(uint32_t));
+            return e != hipSuccess ? e : ccl_label(s->ccl, s->d_bits.p + at * s->ccl.words, n, s->d_parent.p, s->d_extent.p, s->d_stats.p + 2 * at);
+        }, [&]() { return hipMemcpy(stats.data(), s->d_stats.p, s->d_stats.bytes(), hipMemcpyDeviceToHost); })) return rc;
     for (size_t k = 0; k < s->slots; k++) max_extent[k] = stats[2 * k + 1];
     return FROG_OK;
 }
@@ -3364,8 +3394,7 @@ int frog_clusters_finish(frog_clusters *s, uint32_t *max_extent)
 int frog_clusters_mask(frog_clusters *s, uint32_t perm, uint32_t contrast, int side, uint8_t *mask)
 {
     size_t slot;
-    if (int rc = clusters_slot("frog_clusters_mask", s, perm, contrast, side, mask, &slot)) return rc;
-    KCHECK(hipSetDevice(s->device));
+    if (int rc = sink_slot("frog_clusters_mask", s, perm, contrast, side, mask, false, &slot)) return rc;
     frog::DevBuf<uint8_t> d_out;
     KCHECK(d_out.alloc(s->total));
     const uint32_t *d_mask = s->d_bits.p + slot * s->ccl.words;
@@ -3380,9 +3409,7 @@ int frog_clusters_mask(frog_clusters *s, uint32_t perm, uint32_t contrast, int s
 int frog_clusters_labels(frog_clusters *s, uint32_t perm, uint32_t contrast, int side, uint32_t *labels, uint32_t *n_components)
 {
     size_t slot;
-    if (int rc = clusters_slot("frog_clusters_labels", s, perm, contrast, side, labels, &slot)) return rc;
-    if (!clusters_complete(s, perm, 1)) return fail(FROG_E_STATE, "frog_clusters_labels: the permutation has not received every plane of the grid");
-    KCHECK(hipSetDevice(s->device));
+    if (int rc = sink_slot("frog_clusters_labels", s, perm, contrast, side, labels, true, &slot)) return rc;
     const uint32_t *d_mask = s->d_bits.p + slot * s->ccl.words;
     uint32_t n = 0;
     hipError_t e = ccl_label(s->ccl, d_mask, 1, s->d_parent.p, s->d_extent.p, nullptr);
@@ -3397,38 +3424,21 @@ void frog_clusters_destroy(frog_clusters *s) { group_destroy(s); }
 int frog_tfce_create(const frog_volume *grid, uint32_t n_perms, uint32_t n_contrasts, int two_sided, float dh, double E, double H,
                      int connectivity, int device, frog_tfce **out)
 {
-    size_t total;
-    if (int rc = group_arguments("frog_tfce_create", grid, out, &total)) return rc;
-    if (!n_perms || !n_contrasts) return fail(FROG_E_INVALID, "frog_tfce_create: at least one permutation and one contrast");
-    if (n_contrasts > FROG_GLM_MAX_CONTRASTS) return fail(FROG_E_INVALID, "frog_tfce_create: at most " + std::to_string(FROG_GLM_MAX_CONTRASTS) + " contrasts");
     TfceParams par;
-    if (int rc = tfce_params("frog_tfce_create", dh, E, H, connectivity, &par)) return rc;
     std::unique_ptr<frog_tfce> s;
-    if (int rc = group_new(grid, total, device, s)) return rc;
-    s->n_perms = n_perms;
-    s->n_contrasts = n_contrasts;
-    s->sides = two_sided ? 2u : 1u;
+    // a slot keeps its levels, its highest level and its largest tfce
+    if (int rc = sink_new("frog_tfce_create", "level maps", grid, n_perms, n_contrasts, two_sided, connectivity, device, out,
+                          [&]() { return tfce_params("frog_tfce_create", dh, E, H, connectivity, &par); },
+                          [](const CclGrid &g) { return std::make_pair(tfce_stride(g) + 2 * sizeof(uint32_t), tfce_work_bytes(g)); }, s)) return rc;
     s->par = par;
-    s->ccl = ccl_grid(grid, total, connectivity);
     s->stride = tfce_stride(s->ccl);
-    s->slots = (size_t)n_perms * n_contrasts * s->sides;
-    // the levels, and the workspace for as many slots of a launch as fit, up to CCL_BATCH
-    size_t free_bytes = 0, device_bytes = 0;
-    KCHECK(hipMemGetInfo(&free_bytes, &device_bytes));
-    const size_t per_slot = s->stride + 2 * sizeof(uint32_t), work_bytes = tfce_work_bytes(s->ccl);
-    const bool countable = s->slots <= (std::numeric_limits<size_t>::max() - work_bytes) / per_slot;
-    const size_t level_bytes = countable ? s->slots * per_slot : 0;
-    if (!countable || level_bytes + work_bytes > free_bytes)
-        return fail(FROG_E_NOMEM, "frog_tfce_create: " + std::to_string(s->slots) + " level maps and the workspace need " +
-                                  (countable ? std::to_string(level_bytes + work_bytes) : std::string("more than 2^64")) + " bytes of device memory, " +
-                                  std::to_string(free_bytes) + " are free");
-    s->batch = (uint32_t)std::min<size_t>(std::min<size_t>(s->slots, CCL_BATCH), std::max<size_t>(1, (free_bytes - level_bytes) / 2 / work_bytes));
     KCHECK(s->d_levels.alloc(s->slots * s->stride));
     KCHECK(s->d_top.alloc(s->slots));
     KCHECK(s->d_best.alloc(s->slots));
     KCHECK(tfce_work_alloc(s->work, s->ccl, s->batch));
     KCHECK(hipMemset(s->d_levels.p, 0, s->d_levels.bytes()));
-    s->received.assign((size_t)n_perms * grid->dims[2], 0);
+    s->store.kind = GlmStore::LEVELS;
+    s->store.levels = GlmLevelSink{ s->d_levels.p, s->stride, 0, 0, s->sides, par.dh };
     *out = s.release();
     return FROG_OK;
 }
@@ -3438,29 +3448,20 @@ int frog_glm_permute_tfce(frog_glm *a, uint32_t n_contrasts, const double *contr
                           uint32_t first_perm, frog_tfce *sink, float *max_t, float *min_t)
 {
     if (!sink) return fail(FROG_E_INVALID, "bad arguments to frog_glm_permute_tfce");
-    return glm_permute("frog_glm_permute_tfce", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, first_perm,
-                       nullptr, sink, max_t, min_t);
+    return glm_permute("frog_glm_permute_tfce", a, n_contrasts, contrasts, min_count, sigma_floor, region, columns, n_perms, perm, sign, first_perm, sink, max_t, min_t);
 }
 
 int frog_tfce_finish(frog_tfce *s, float *max_tfce)
 {
-    if (!s || !max_tfce) return fail(FROG_E_INVALID, "bad arguments to frog_tfce_finish");
-    if (!clusters_complete(s, 0, s->n_perms)) return fail(FROG_E_STATE, "frog_tfce_finish: a permutation has not received every plane of the grid");
-    KCHECK(hipSetDevice(s->device));
-    hipError_t e = hipSuccess;
-    for (size_t at = 0; at < s->slots && e == hipSuccess; at += s->batch)
-        e = tfce_enhance(s->ccl, s->par, s->d_levels.p + at * s->stride, s->stride, (uint32_t)std::min<size_t>(s->batch, s->slots - at), s->work,
-                         s->d_top.p + at, nullptr, s->d_best.p + at);
-    if (e == hipSuccess) e = hipMemcpy(max_tfce, s->d_best.p, s->slots * sizeof(float), hipMemcpyDeviceToHost);    // the bits of f32 values
-    if (e != hipSuccess) return hip_fail("frog_tfce_finish", e);
-    return FROG_OK;
+    return sink_finish("frog_tfce_finish", s, max_tfce, [&](size_t at, uint32_t n) {
+        return tfce_enhance(s->ccl, s->par, s->d_levels.p + at * s->stride, s->stride, n, s->work, s->d_top.p + at, nullptr, s->d_best.p + at);
+    }, [&]() { return hipMemcpy(max_tfce, s->d_best.p, s->slots * sizeof(float), hipMemcpyDeviceToHost); });   // the bits of f32 values
 }
 
 int frog_tfce_levels(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, uint8_t *levels)
 {
     size_t slot;
-    if (int rc = clusters_slot("frog_tfce_levels", s, perm, contrast, side, levels, &slot)) return rc;
-    KCHECK(hipSetDevice(s->device));
+    if (int rc = sink_slot("frog_tfce_levels", s, perm, contrast, side, levels, false, &slot)) return rc;
     KCHECK(hipMemcpy(levels, s->d_levels.p + slot * s->stride, s->total, hipMemcpyDeviceToHost));
     return FROG_OK;
 }
@@ -3468,9 +3469,7 @@ int frog_tfce_levels(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, u
 int frog_tfce_map(frog_tfce *s, uint32_t perm, uint32_t contrast, int side, float *tfce)
 {
     size_t slot;
-    if (int rc = clusters_slot("frog_tfce_map", s, perm, contrast, side, tfce, &slot)) return rc;
-    if (!clusters_complete(s, perm, 1)) return fail(FROG_E_STATE, "frog_tfce_map: the permutation has not received every plane of the grid");
-    KCHECK(hipSetDevice(s->device));
+    if (int rc = sink_slot("frog_tfce_map", s, perm, contrast, side, tfce, true, &slot)) return rc;
     frog::DevBuf<float> d_map;
     KCHECK(d_map.alloc(s->total));
     hipError_t e = tfce_enhance(s->ccl, s->par, s->d_levels.p + slot * s->stride, s->stride, 1, s->work, s->d_top.p + slot, d_map.p, s->d_best.p + slot);

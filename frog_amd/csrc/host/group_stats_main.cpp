@@ -49,6 +49,7 @@
 // The device holds slabs of frog_glm_planes z-planes, or -rp planes if that is fewer; the slab count is printed and changes no
 // bit of any file.  Every input is checked before anything is written.
 #include "group_tool.h"
+#include "inference.h"
 #include "volume_stream.h"
 
 #include <algorithm>
@@ -63,6 +64,8 @@
 #include <vector>
 
 namespace {
+
+using frog::csv_float;
 
 // The numeric rows of a CSV: fields separated by commas, semicolons or blanks.  A first line with a field that is not a
 // number is a header and is dropped; any later one is an error.  Every row has the first row's length.
@@ -104,104 +107,120 @@ uint32_t float_key(float x)
     return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u);
 }
 
-std::string csv_float(float v)
-{
-    if (std::isnan(v)) return "nan";
-    char buf[40];
-    std::snprintf(buf, sizeof buf, "%.9g", (double)v);
-    return buf;
-}
+// ---- the options -----------------------------------------------------------------------------------------------------------------
 
-} // namespace
-
-int main(int argc, char *argv[])
-{
-    PhaseTimes times;
+// the command line as it was given, before any check
+struct Options {
     std::vector<std::string> positional;
     std::string transformsDir = "transforms", outDir = ".", contrastsPath, valueName = "logjacobian", volumeList, maskList, regionPath, columnList;
-    int device = 0, flips = 0, twoSided = 0, connectivity = 26;
+    std::string fwhmText = "0";
+    int device = 0, flips = 0, twoSided = 0, connectivity = 26, tfceTest = 0;
     long minCount = 1, nPerms = 0, planesOption = 0;
     unsigned long long seed = 0;
-    double sigmaFloor = 0, clusterThreshold = 0, tfceStep = 0.1, tfceE = 0.5, tfceH = 2, fwhm = 0;
-    std::string fwhmText = "0";
+    double sigmaFloor = 0, clusterThreshold = 0, tfceStep = 0.1, tfceE = 0.5, tfceH = 2;
     float fill = 0;
     bool planesGiven = false, permOption = false, clusterTest = false, connectivityGiven = false, tfceOption = false;
-    int tfceTest = 0;
+
+    uint32_t sides() const { return twoSided == 1 ? 2 : 1; }
+};
+
+Options parse_options(int argc, char *argv[])
+{
+    Options o;
     int a = positional_arguments(argc, argv, 1, { "-c", "-td", "-o", "-v", "-vl", "-ml", "-m", "-mc", "-sf", "-f", "-np", "-ps", "-pc", "-pf", "-two", "-ct", "-cc", "-tf", "-tfd", "-tfe", "-tfh", "-s", "-rp", "-dev" },
-                                 positional);
+                                 o.positional);
     for (; a < argc; a += 2) {
         const char *key = argv[a], *value = a + 1 < argc ? argv[a + 1] : "";
-        if (std::strcmp(key, "-c") == 0) contrastsPath = value;
-        else if (std::strcmp(key, "-td") == 0) transformsDir = value;
-        else if (std::strcmp(key, "-o") == 0) outDir = value;
-        else if (std::strcmp(key, "-v") == 0) valueName = value;
-        else if (std::strcmp(key, "-vl") == 0) volumeList = value;
-        else if (std::strcmp(key, "-ml") == 0) maskList = value;
-        else if (std::strcmp(key, "-m") == 0) regionPath = value;
-        else if (std::strcmp(key, "-mc") == 0) minCount = atol(value);
-        else if (std::strcmp(key, "-sf") == 0) sigmaFloor = atof(value);
-        else if (std::strcmp(key, "-f") == 0) fill = (float)atof(value);
-        else if (std::strcmp(key, "-np") == 0) nPerms = atol(value);
-        else if (std::strcmp(key, "-ps") == 0) { seed = std::strtoull(value, nullptr, 10); permOption = true; }
-        else if (std::strcmp(key, "-pc") == 0) { columnList = value; permOption = true; }
-        else if (std::strcmp(key, "-pf") == 0) { flips = atoi(value); permOption = true; }
-        else if (std::strcmp(key, "-two") == 0) { twoSided = atoi(value); permOption = true; }
-        else if (std::strcmp(key, "-ct") == 0) { clusterThreshold = atof(value); clusterTest = true; }
-        else if (std::strcmp(key, "-cc") == 0) { connectivity = atoi(value); connectivityGiven = true; }
-        else if (std::strcmp(key, "-tf") == 0) tfceTest = atoi(value);
-        else if (std::strcmp(key, "-tfd") == 0) { tfceStep = atof(value); tfceOption = true; }
-        else if (std::strcmp(key, "-tfe") == 0) { tfceE = atof(value); tfceOption = true; }
-        else if (std::strcmp(key, "-tfh") == 0) { tfceH = atof(value); tfceOption = true; }
-        else if (std::strcmp(key, "-s") == 0) fwhmText = value;
-        else if (std::strcmp(key, "-rp") == 0) { planesOption = atol(value); planesGiven = true; }
-        else if (std::strcmp(key, "-dev") == 0) device = atoi(value);
+        if (std::strcmp(key, "-c") == 0) o.contrastsPath = value;
+        else if (std::strcmp(key, "-td") == 0) o.transformsDir = value;
+        else if (std::strcmp(key, "-o") == 0) o.outDir = value;
+        else if (std::strcmp(key, "-v") == 0) o.valueName = value;
+        else if (std::strcmp(key, "-vl") == 0) o.volumeList = value;
+        else if (std::strcmp(key, "-ml") == 0) o.maskList = value;
+        else if (std::strcmp(key, "-m") == 0) o.regionPath = value;
+        else if (std::strcmp(key, "-mc") == 0) o.minCount = atol(value);
+        else if (std::strcmp(key, "-sf") == 0) o.sigmaFloor = atof(value);
+        else if (std::strcmp(key, "-f") == 0) o.fill = (float)atof(value);
+        else if (std::strcmp(key, "-np") == 0) o.nPerms = atol(value);
+        else if (std::strcmp(key, "-ps") == 0) { o.seed = std::strtoull(value, nullptr, 10); o.permOption = true; }
+        else if (std::strcmp(key, "-pc") == 0) { o.columnList = value; o.permOption = true; }
+        else if (std::strcmp(key, "-pf") == 0) { o.flips = atoi(value); o.permOption = true; }
+        else if (std::strcmp(key, "-two") == 0) { o.twoSided = atoi(value); o.permOption = true; }
+        else if (std::strcmp(key, "-ct") == 0) { o.clusterThreshold = atof(value); o.clusterTest = true; }
+        else if (std::strcmp(key, "-cc") == 0) { o.connectivity = atoi(value); o.connectivityGiven = true; }
+        else if (std::strcmp(key, "-tf") == 0) o.tfceTest = atoi(value);
+        else if (std::strcmp(key, "-tfd") == 0) { o.tfceStep = atof(value); o.tfceOption = true; }
+        else if (std::strcmp(key, "-tfe") == 0) { o.tfceE = atof(value); o.tfceOption = true; }
+        else if (std::strcmp(key, "-tfh") == 0) { o.tfceH = atof(value); o.tfceOption = true; }
+        else if (std::strcmp(key, "-s") == 0) o.fwhmText = value;
+        else if (std::strcmp(key, "-rp") == 0) { o.planesOption = atol(value); o.planesGiven = true; }
+        else if (std::strcmp(key, "-dev") == 0) o.device = atoi(value);
         else die(std::string("unknown option ") + key);
     }
-    if (positional.size() != 3) {
-        std::cout << "Usage : GroupStats bbox.json spacing design.csv [-c contrasts.csv] [-td transformsDir] [-o outDir] "
-                     "[-v jacobian|logjacobian|images] [-vl volumes.txt] [-ml masks.txt] [-m regionMask] [-mc minCount] [-sf sigmaFloor] "
-                     "[-f fill] [-np nPerms] [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-tf 1] [-tfd dh] [-tfe 0.5|1] [-tfh 1|2] "
-                     "[-s fwhm_mm] [-rp planes] [-dev n]\n-tf 1: threshold-free cluster enhancement in steps of dh (default 0.1); a statistic beyond 255 * dh "
-                     "saturates there" << std::endl;
-        return 1;
-    }
+    return o;
+}
 
-    // ---- everything is checked before the first output
-    const bool images = valueName == "images", logMode = valueName == "logjacobian";
-    if (!images && !logMode && valueName != "jacobian") die("-v takes jacobian, logjacobian or images, not '" + valueName + "'");
-    if (images && volumeList.empty()) die("-v images needs the volumes: -vl volumes.txt");
-    if (minCount < 1 || minCount > 65535) die("-mc takes a count from 1 to 65535");
-    if (!(sigmaFloor >= 0.0)) die("-sf takes a stdev that is not negative");
-    if (nPerms < 0 || nPerms == 1 || nPerms > 1000000) die("-np takes 2 to 1000000 permutations (the first is the design itself)");
-    if (permOption && nPerms == 0) die("-ps, -pc, -pf and -two need -np");
-    if ((clusterTest || connectivityGiven) && nPerms == 0) die("-ct and -cc need -np");
-    if (tfceTest != 0 && tfceTest != 1) die("-tf takes 1 (or 0)");
-    if ((tfceTest || tfceOption) && nPerms == 0) die("-tf, -tfd, -tfe and -tfh need -np");
-    if (tfceOption && !tfceTest) die("-tfd, -tfe and -tfh need -tf 1");
-    if (connectivityGiven && !clusterTest && !tfceTest) die("-cc needs -ct or -tf 1");
-    if (tfceTest && (!((float)tfceStep > 0.0f) || !std::isfinite((float)tfceStep))) die("-tfd takes a step that is finite and above 0");
-    if (tfceTest && tfceE != 0.5 && tfceE != 1.0) die("-tfe takes 0.5 or 1");
-    if (tfceTest && tfceH != 1.0 && tfceH != 2.0) die("-tfh takes 1 or 2");
-    if (clusterTest && (!(clusterThreshold >= 0.0) || !std::isfinite((float)clusterThreshold))) die("-ct takes a threshold that is finite and not negative");
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26) die("-cc takes 6, 18 or 26");
-    if (planesGiven && planesOption < 1) die("-rp takes a number of planes, at least 1");
-    {
-        char *end = nullptr;
-        fwhm = std::strtod(fwhmText.c_str(), &end);
-        if (fwhmText.empty() || *end || !(fwhm >= 0.0) || !std::isfinite(fwhm)) die("-s takes a FWHM in mm that is finite and not negative, not '" + fwhmText + "'");
-    }
-    const double smoothSigma = fwhm / FROG_SMOOTH_FWHM;
-    const auto design = read_table(positional[2], "the design");
-    const size_t n = design.size(), p = design[0].size();
+// ---- the checks: everything is checked before the first output ---------------------------------------------------------------------
+
+// what the checks load and work out: the model, the grid, and what each image is read from
+struct Inputs {
+    bool images = false, logMode = false;
+    double fwhm = 0, smoothSigma = 0;
+    size_t n = 0, p = 0, n_c = 0;                   // images, design columns, contrasts
+    std::vector<double> X, contrasts;
+    uint32_t columns = 0;                           // the columns the permutations move, as bits
+    std::vector<std::string> volumes, masks;
+    frog_volume grid;
+    size_t plane = 0, total = 0;
+    uint32_t radius[3] = { 0, 0, 0 };
+    ChainArguments transforms;
+    std::vector<std::vector<frog_chain_link>> inverse;
+    std::vector<frog_volume> supports;
+    std::vector<uint8_t> region;
+};
+
+// the options by themselves
+void check_options(const Options &o, Inputs &in)
+{
+    in.images = o.valueName == "images";
+    in.logMode = o.valueName == "logjacobian";
+    if (!in.images && !in.logMode && o.valueName != "jacobian") die("-v takes jacobian, logjacobian or images, not '" + o.valueName + "'");
+    if (in.images && o.volumeList.empty()) die("-v images needs the volumes: -vl volumes.txt");
+    if (o.minCount < 1 || o.minCount > 65535) die("-mc takes a count from 1 to 65535");
+    if (!(o.sigmaFloor >= 0.0)) die("-sf takes a stdev that is not negative");
+    if (o.nPerms < 0 || o.nPerms == 1 || o.nPerms > 1000000) die("-np takes 2 to 1000000 permutations (the first is the design itself)");
+    if (o.permOption && o.nPerms == 0) die("-ps, -pc, -pf and -two need -np");
+    if ((o.clusterTest || o.connectivityGiven) && o.nPerms == 0) die("-ct and -cc need -np");
+    if (o.tfceTest != 0 && o.tfceTest != 1) die("-tf takes 1 (or 0)");
+    if ((o.tfceTest || o.tfceOption) && o.nPerms == 0) die("-tf, -tfd, -tfe and -tfh need -np");
+    if (o.tfceOption && !o.tfceTest) die("-tfd, -tfe and -tfh need -tf 1");
+    if (o.connectivityGiven && !o.clusterTest && !o.tfceTest) die("-cc needs -ct or -tf 1");
+    if (o.tfceTest && (!((float)o.tfceStep > 0.0f) || !std::isfinite((float)o.tfceStep))) die("-tfd takes a step that is finite and above 0");
+    if (o.tfceTest && o.tfceE != 0.5 && o.tfceE != 1.0) die("-tfe takes 0.5 or 1");
+    if (o.tfceTest && o.tfceH != 1.0 && o.tfceH != 2.0) die("-tfh takes 1 or 2");
+    if (o.clusterTest && (!(o.clusterThreshold >= 0.0) || !std::isfinite((float)o.clusterThreshold))) die("-ct takes a threshold that is finite and not negative");
+    if (o.connectivity != 6 && o.connectivity != 18 && o.connectivity != 26) die("-cc takes 6, 18 or 26");
+    if (o.planesGiven && o.planesOption < 1) die("-rp takes a number of planes, at least 1");
+    char *end = nullptr;
+    in.fwhm = std::strtod(o.fwhmText.c_str(), &end);
+    if (o.fwhmText.empty() || *end || !(in.fwhm >= 0.0) || !std::isfinite(in.fwhm)) die("-s takes a FWHM in mm that is finite and not negative, not '" + o.fwhmText + "'");
+    in.smoothSigma = in.fwhm / FROG_SMOOTH_FWHM;
+}
+
+// the design, the contrasts and the columns that move
+void load_model(const Options &o, Inputs &in)
+{
+    const auto design = read_table(o.positional[2], "the design");
+    const size_t n = in.n = design.size(), p = in.p = design[0].size();
     if (n > FROG_GLM_MAX_IMAGES) die("at most " + std::to_string(FROG_GLM_MAX_IMAGES) + " images");
     if (p > FROG_GLM_MAX_COLUMNS) die("at most " + std::to_string(FROG_GLM_MAX_COLUMNS) + " design columns");
     if (n <= p) die("the design needs more rows than columns");
-    std::vector<double> X(n * p);
+    std::vector<double> &X = in.X, &contrasts = in.contrasts;
+    X.resize(n * p);
     for (size_t i = 0; i < n; i++) std::copy(design[i].begin(), design[i].end(), X.begin() + i * p);
-    std::vector<double> contrasts;
-    if (!contrastsPath.empty()) {
-        const auto rows = read_table(contrastsPath, "the contrasts");
-        if (rows[0].size() != p) die(contrastsPath + " has " + std::to_string(rows[0].size()) + " columns for a design of " + std::to_string(p));
+    if (!o.contrastsPath.empty()) {
+        const auto rows = read_table(o.contrastsPath, "the contrasts");
+        if (rows[0].size() != p) die(o.contrastsPath + " has " + std::to_string(rows[0].size()) + " columns for a design of " + std::to_string(p));
         for (const auto &r : rows) contrasts.insert(contrasts.end(), r.begin(), r.end());
     } else {
         for (size_t j = 0; j < p; j++) {
@@ -213,366 +232,487 @@ int main(int argc, char *argv[])
         }
         if (contrasts.empty()) die("every design column is constant: give the contrasts with -c");
     }
-    const size_t n_c = contrasts.size() / p;
+    const size_t n_c = in.n_c = contrasts.size() / p;
     if (n_c > FROG_GLM_MAX_CONTRASTS) die("at most " + std::to_string(FROG_GLM_MAX_CONTRASTS) + " contrasts");
-    uint32_t columns = 0;
-    if (!columnList.empty()) {
-        for (size_t at = 0; at <= columnList.size();) {
-            const size_t comma = std::min(columnList.find(',', at), columnList.size());
-            const std::string text = columnList.substr(at, comma - at);
+    if (!o.columnList.empty()) {
+        for (size_t at = 0; at <= o.columnList.size();) {
+            const size_t comma = std::min(o.columnList.find(',', at), o.columnList.size());
+            const std::string text = o.columnList.substr(at, comma - at);
             char *end = nullptr;
             const long j = std::strtol(text.c_str(), &end, 10);
             if (text.empty() || *end || j < 0 || j >= (long)p) die("-pc takes comma-separated column indices below " + std::to_string(p) + ", not '" + text + "'");
-            columns |= 1u << j;
+            in.columns |= 1u << j;
             at = comma + 1;
         }
     } else {
         for (size_t c = 0; c < n_c; c++)
-            for (size_t j = 0; j < p; j++) if (contrasts[c * p + j] != 0.0) columns |= 1u << j;
+            for (size_t j = 0; j < p; j++) if (contrasts[c * p + j] != 0.0) in.columns |= 1u << j;
     }
-    if (nPerms && !columns) die("no column to permute: every contrast is zero");
-    std::vector<std::string> volumes, masks;
-    if (!volumeList.empty()) {
-        if (!read_list(volumeList, volumes)) die("cannot read the volume list " + volumeList);
-        if (volumes.size() != n) die(volumeList + " holds " + std::to_string(volumes.size()) + " volumes for " + std::to_string(n) + " design rows");
+    if (o.nPerms && !in.columns) die("no column to permute: every contrast is zero");
+}
+
+// the -m volume as one flag per grid voxel
+void load_region(const std::string &regionPath, Inputs &in)
+{
+    int status = 0;
+    frog_volume_file *f = frog_volume_read(regionPath.c_str(), &status);
+    if (!f) die("cannot read the region mask " + regionPath);
+    frog_volume v;
+    frog_volume_view(f, &v);
+    if (v.dims[0] != in.grid.dims[0] || v.dims[1] != in.grid.dims[1] || v.dims[2] != in.grid.dims[2]) die(regionPath + " is not on the grid");
+    if (v.dtype == FROG_V_F32 || v.dtype == FROG_V_F64) die(regionPath + " is a float volume: masks have an integer type");
+    in.region.resize(in.total);
+    const size_t bytes = frog_volume_voxel_bytes(v.dtype);
+    const unsigned char *data = (const unsigned char *)v.data;
+    for (size_t i = 0; i < in.total; i++) {
+        bool on = false;
+        for (size_t b = 0; b < bytes; b++) on = on || data[i * bytes + b] != 0;
+        in.region[i] = on;
     }
-    if (!maskList.empty()) {
-        if (!read_list(maskList, masks)) die("cannot read the mask list " + maskList);
-        if (masks.size() != n) die(maskList + " holds " + std::to_string(masks.size()) + " masks for " + std::to_string(n) + " design rows");
+    frog_volume_free(f);
+}
+
+// the lists, the grid, the transforms, and the header of every volume and mask
+void load_images(const Options &o, Inputs &in)
+{
+    const size_t n = in.n;
+    if (!o.volumeList.empty()) {
+        if (!read_list(o.volumeList, in.volumes)) die("cannot read the volume list " + o.volumeList);
+        if (in.volumes.size() != n) die(o.volumeList + " holds " + std::to_string(in.volumes.size()) + " volumes for " + std::to_string(n) + " design rows");
     }
-    frog_volume grid;
-    if (frog_bbox_grid(positional[0].c_str(), atof(positional[1].c_str()), &grid))
-        die("cannot read a bounding box from " + positional[0] + " (or spacing " + positional[1] + " is not positive)");
-    uint32_t radius[3] = { 0, 0, 0 };
-    for (int k = 0; k < 3 && smoothSigma > 0.0; k++)
-        if (frog_smooth_taps(smoothSigma, grid.spacing[k], &radius[k], nullptr)) die("-s " + fwhmText + ": " + frog_last_error());
-    ChainArguments transforms;
-    const auto inverse = inverse_transforms(transforms, transformsDir, n);
-    std::vector<frog_volume> supports(volumes.size());
-    for (size_t i = 0; i < volumes.size(); i++) {
-        if (!peek_header(volumes[i]).ok) die("cannot read volume " + volumes[i]);
-        supports[i] = frog_volume{};
-        if (!images && frog_volume_geometry(volumes[i].c_str(), supports[i].dims, supports[i].spacing, supports[i].origin))
-            die("cannot read the geometry of " + volumes[i]);
+    if (!o.maskList.empty()) {
+        if (!read_list(o.maskList, in.masks)) die("cannot read the mask list " + o.maskList);
+        if (in.masks.size() != n) die(o.maskList + " holds " + std::to_string(in.masks.size()) + " masks for " + std::to_string(n) + " design rows");
     }
-    for (const auto &m : masks) {
+    if (frog_bbox_grid(o.positional[0].c_str(), atof(o.positional[1].c_str()), &in.grid))
+        die("cannot read a bounding box from " + o.positional[0] + " (or spacing " + o.positional[1] + " is not positive)");
+    for (int k = 0; k < 3 && in.smoothSigma > 0.0; k++)
+        if (frog_smooth_taps(in.smoothSigma, in.grid.spacing[k], &in.radius[k], nullptr)) die("-s " + o.fwhmText + ": " + frog_last_error());
+    in.inverse = inverse_transforms(in.transforms, o.transformsDir, n);
+    in.supports.resize(in.volumes.size());
+    for (size_t i = 0; i < in.volumes.size(); i++) {
+        if (!peek_header(in.volumes[i]).ok) die("cannot read volume " + in.volumes[i]);
+        in.supports[i] = frog_volume{};
+        if (!in.images && frog_volume_geometry(in.volumes[i].c_str(), in.supports[i].dims, in.supports[i].spacing, in.supports[i].origin))
+            die("cannot read the geometry of " + in.volumes[i]);
+    }
+    for (const auto &m : in.masks) {
         const VolumeHeader h = peek_header(m);
         if (!h.ok) die("cannot read mask " + m);
         if (h.is_float) die(m + " is a float volume: masks have an integer type");
     }
-    const size_t plane = (size_t)grid.dims[0] * grid.dims[1], total = plane * grid.dims[2];
-    std::vector<uint8_t> region;
-    if (!regionPath.empty()) {
-        int status = 0;
-        frog_volume_file *f = frog_volume_read(regionPath.c_str(), &status);
-        if (!f) die("cannot read the region mask " + regionPath);
-        frog_volume v;
-        frog_volume_view(f, &v);
-        if (v.dims[0] != grid.dims[0] || v.dims[1] != grid.dims[1] || v.dims[2] != grid.dims[2]) die(regionPath + " is not on the grid");
-        if (v.dtype == FROG_V_F32 || v.dtype == FROG_V_F64) die(regionPath + " is a float volume: masks have an integer type");
-        region.resize(total);
-        const size_t bytes = frog_volume_voxel_bytes(v.dtype);
-        const unsigned char *data = (const unsigned char *)v.data;
-        for (size_t i = 0; i < total; i++) {
-            bool on = false;
-            for (size_t b = 0; b < bytes; b++) on = on || data[i * bytes + b] != 0;
-            region[i] = on;
-        }
-        frog_volume_free(f);
-    }
-    frog_clusters *sink = nullptr;
-    if (clusterTest && frog_clusters_create(&grid, (uint32_t)nPerms, (uint32_t)n_c, twoSided == 1, (float)clusterThreshold, connectivity, device, &sink))
-        die(frog_last_error());
-    frog_tfce *enhance = nullptr;
-    if (tfceTest && frog_tfce_create(&grid, (uint32_t)nPerms, (uint32_t)n_c, twoSided == 1, (float)tfceStep, tfceE, tfceH, connectivity, device, &enhance))
-        die(frog_last_error());
-    begin_output(outDir, n, "images", grid);
+    in.plane = (size_t)in.grid.dims[0] * in.grid.dims[1];
+    in.total = in.plane * in.grid.dims[2];
+    if (!o.regionPath.empty()) load_region(o.regionPath, in);
+}
 
-    auto t0 = clk::now();
-    std::vector<frog_chain *> chains = create_chains(inverse, device);
+// ---- the fit ---------------------------------------------------------------------------------------------------------------------
+
+// what the slabs share: one chain per image, the planes of a slab, and the permutations' rows
+struct Plan {
+    std::vector<frog_chain *> chains;
     uint32_t planes = 0;
-    if (smoothSigma > 0.0 ? frog_glm_smooth_planes(&grid, (uint32_t)n, smoothSigma, device, &planes) : frog_glm_planes(&grid, (uint32_t)n, device, &planes))
-        die(frog_last_error());
-    if (planesGiven && (uint64_t)planesOption < planes) planes = (uint32_t)planesOption;
-    const uint32_t depth = grid.dims[2], slabs = (depth + planes - 1) / planes;
-    std::cout << "stats : " << slabs << (slabs == 1 ? " slab of " : " slabs of ") << planes << " planes, " << p << " columns, " << n_c << " contrasts, "
-              << nPerms << " permutations";
-    if (smoothSigma > 0.0)
-        std::cout << ", smoothed: FWHM " << fwhm << " mm, sigma " << smoothSigma << " mm, radii " << radius[0] << " " << radius[1] << " " << radius[2] << " voxels";
-    std::cout << std::endl;
     std::vector<uint32_t> perm;
     std::vector<int8_t> sign;
-    if (nPerms) {
-        perm.resize((size_t)nPerms * n);
-        sign.resize((size_t)nPerms * n);
-        if (frog_glm_draw((uint32_t)n, (uint32_t)nPerms, seed, 1, flips == 1, perm.data(), sign.data())) die(frog_last_error());
-    }
-    times.setup_s = seconds(t0);
+};
 
+void set_up(const Options &o, const Inputs &in, Plan &plan)
+{
+    plan.chains = create_chains(in.inverse, o.device);
+    uint32_t &planes = plan.planes;
+    if (in.smoothSigma > 0.0 ? frog_glm_smooth_planes(&in.grid, (uint32_t)in.n, in.smoothSigma, o.device, &planes) : frog_glm_planes(&in.grid, (uint32_t)in.n, o.device, &planes))
+        die(frog_last_error());
+    if (o.planesGiven && (uint64_t)o.planesOption < planes) planes = (uint32_t)o.planesOption;
+    const uint32_t slabs = (in.grid.dims[2] + planes - 1) / planes;
+    std::cout << "stats : " << slabs << (slabs == 1 ? " slab of " : " slabs of ") << planes << " planes, " << in.p << " columns, " << in.n_c << " contrasts, "
+              << o.nPerms << " permutations";
+    if (in.smoothSigma > 0.0)
+        std::cout << ", smoothed: FWHM " << in.fwhm << " mm, sigma " << in.smoothSigma << " mm, radii " << in.radius[0] << " " << in.radius[1] << " " << in.radius[2] << " voxels";
+    std::cout << std::endl;
+    if (o.nPerms) {
+        plan.perm.resize((size_t)o.nPerms * in.n);
+        plan.sign.resize((size_t)o.nPerms * in.n);
+        if (frog_glm_draw((uint32_t)in.n, (uint32_t)o.nPerms, o.seed, 1, o.flips == 1, plan.perm.data(), plan.sign.data())) die(frog_last_error());
+    }
+}
+
+// the maps over the whole grid, and the permutations' extrema over it ([permutation * n_c + contrast])
+struct Fit {
+    std::vector<float> beta, sigma, marker, t, maxT, minT;     // marker: -1 where the voxel was not fit
+    std::vector<uint16_t> count;
+    double read_s = 0;
     int threads = 1;
     size_t window = 1;
-    frog::volume_stream_shape(n, &threads, &window);
-    if (!masks.empty()) threads = std::max(1, threads / 2);
-    std::vector<float> beta(p * total), sigma(total), marker(total), t(n_c * total), slabBeta, slabT;
-    std::vector<uint16_t> count(total);
-    std::vector<float> maxT((size_t)nPerms * n_c, -INFINITY), minT((size_t)nPerms * n_c, INFINITY), slabMax(maxT.size()), slabMin(minT.size());
-    double read_s = 0;
-    for (uint32_t first = 0; first < depth; first += planes) {
-        const uint32_t count_planes = std::min(planes, depth - first);
+};
+
+// every image's map into one slab's accumulator, in the order of the design's rows
+void add_images(const Inputs &in, const Plan &plan, frog_glm *glm, Fit &fit, PhaseTimes &times)
+{
+    std::unique_ptr<frog::VolumeStream> stream(in.images ? new frog::VolumeStream(in.volumes, fit.threads, fit.window) : nullptr);
+    std::unique_ptr<frog::VolumeStream> maskStream(in.masks.empty() ? nullptr : new frog::VolumeStream(in.masks, fit.threads, fit.window));
+    for (size_t i = 0; i < in.n; i++) {
+        double waited = 0;
+        const frog_volume *mask = nullptr;
+        if (maskStream) {
+            frog::VolumeStream::Item &m = maskStream->get(i, &waited);
+            times.waited_s += waited;
+            if (!m.file) die("cannot read mask " + in.masks[i]);
+            mask = &m.view;
+        }
+        if (in.images) {
+            frog::VolumeStream::Item &it = stream->get(i, &waited);
+            times.waited_s += waited;
+            if (!it.file) die("cannot read volume " + in.volumes[i]);
+            const auto t0 = clk::now();
+            if (frog_glm_add(glm, plan.chains[i], &it.view, mask, 1, 0.0)) die(in.volumes[i] + ": " + frog_last_error());
+            times.device_s += seconds(t0);
+            stream->release(i);
+        } else {
+            const auto t0 = clk::now();
+            if (frog_glm_add_jacobian(glm, plan.chains[i], in.supports.empty() ? nullptr : &in.supports[i], mask, in.logMode))
+                die("transform " + std::to_string(i) + ": " + frog_last_error());
+            times.device_s += seconds(t0);
+        }
+        if (maskStream) maskStream->release(i);
+    }
+    if (stream) fit.read_s += stream->read_seconds();
+    if (maskStream) fit.read_s += maskStream->read_seconds();
+}
+
+// One slab's permutations: its extrema into the grid's, and its bits and levels into the sinks.  Each sink takes a pass of
+// its own; the extrema are the same bits in both and are taken once.
+void permute_slab(const Options &o, const Inputs &in, const Plan &plan, frog_glm *glm, const uint8_t *slabRegion, frog_clusters *sink, frog_tfce *enhance,
+                  Fit &fit, std::vector<float> &slabMax, std::vector<float> &slabMin)
+{
+    const uint32_t n_c = (uint32_t)in.n_c, minCount = (uint32_t)o.minCount, nPerms = (uint32_t)o.nPerms;
+    const int8_t *signs = o.flips == 1 ? plan.sign.data() : nullptr;
+    if (sink ? frog_glm_permute_clusters(glm, n_c, in.contrasts.data(), minCount, o.sigmaFloor, slabRegion, in.columns, nPerms, plan.perm.data(), signs, 0, sink,
+                                         slabMax.data(), slabMin.data())
+             : frog_glm_permute(glm, n_c, in.contrasts.data(), minCount, o.sigmaFloor, slabRegion, in.columns, nPerms, plan.perm.data(), signs, slabMax.data(),
+                                slabMin.data())) die(frog_last_error());
+    if (enhance && frog_glm_permute_tfce(glm, n_c, in.contrasts.data(), minCount, o.sigmaFloor, slabRegion, in.columns, nPerms, plan.perm.data(), signs, 0, enhance,
+                                         nullptr, nullptr)) die(frog_last_error());
+    for (size_t e = 0; e < fit.maxT.size(); e++) {
+        if (float_key(slabMax[e]) > float_key(fit.maxT[e])) fit.maxT[e] = slabMax[e];
+        if (float_key(slabMin[e]) < float_key(fit.minT[e])) fit.minT[e] = slabMin[e];
+    }
+}
+
+// the slab loop: per slab an accumulator, every image's map, the fit, and the permutations
+void fit_slabs(const Options &o, const Inputs &in, const Plan &plan, frog_clusters *sink, frog_tfce *enhance, Fit &fit, PhaseTimes &times)
+{
+    const size_t n = in.n, p = in.p, n_c = in.n_c, plane = in.plane, total = in.total;
+    frog::volume_stream_shape(n, &fit.threads, &fit.window);
+    if (!in.masks.empty()) fit.threads = std::max(1, fit.threads / 2);
+    fit.beta.resize(p * total);
+    fit.sigma.resize(total);
+    fit.marker.resize(total);
+    fit.t.resize(n_c * total);
+    fit.count.resize(total);
+    fit.maxT.assign((size_t)o.nPerms * n_c, -INFINITY);
+    fit.minT.assign((size_t)o.nPerms * n_c, INFINITY);
+    std::vector<float> slabBeta, slabT, slabMax(fit.maxT.size()), slabMin(fit.minT.size());
+    const uint32_t depth = in.grid.dims[2], minCount = (uint32_t)o.minCount;
+    for (uint32_t first = 0; first < depth; first += plan.planes) {
+        const uint32_t count_planes = std::min(plan.planes, depth - first);
         const size_t slabVoxels = plane * count_planes, at = plane * first;
         frog_glm *glm = nullptr;
-        t0 = clk::now();
-        if (frog_glm_create(&grid, first, count_planes, (uint32_t)n, (uint32_t)p, X.data(), device, &glm)) die(frog_last_error());
-        if (smoothSigma > 0.0 && frog_glm_smooth(glm, smoothSigma)) die(frog_last_error());
+        auto t0 = clk::now();
+        if (frog_glm_create(&in.grid, first, count_planes, (uint32_t)n, (uint32_t)p, in.X.data(), o.device, &glm)) die(frog_last_error());
+        if (in.smoothSigma > 0.0 && frog_glm_smooth(glm, in.smoothSigma)) die(frog_last_error());
         times.device_s += seconds(t0);
-        std::unique_ptr<frog::VolumeStream> stream(images ? new frog::VolumeStream(volumes, threads, window) : nullptr);
-        std::unique_ptr<frog::VolumeStream> maskStream(masks.empty() ? nullptr : new frog::VolumeStream(masks, threads, window));
-        for (size_t i = 0; i < n; i++) {
-            double waited = 0;
-            const frog_volume *mask = nullptr;
-            if (maskStream) {
-                frog::VolumeStream::Item &m = maskStream->get(i, &waited);
-                times.waited_s += waited;
-                if (!m.file) die("cannot read mask " + masks[i]);
-                mask = &m.view;
-            }
-            if (images) {
-                frog::VolumeStream::Item &it = stream->get(i, &waited);
-                times.waited_s += waited;
-                if (!it.file) die("cannot read volume " + volumes[i]);
-                t0 = clk::now();
-                if (frog_glm_add(glm, chains[i], &it.view, mask, 1, 0.0)) die(volumes[i] + ": " + frog_last_error());
-                times.device_s += seconds(t0);
-                stream->release(i);
-            } else {
-                t0 = clk::now();
-                if (frog_glm_add_jacobian(glm, chains[i], supports.empty() ? nullptr : &supports[i], mask, logMode))
-                    die("transform " + std::to_string(i) + ": " + frog_last_error());
-                times.device_s += seconds(t0);
-            }
-            if (maskStream) maskStream->release(i);
-        }
-        if (stream) read_s += stream->read_seconds();
-        if (maskStream) read_s += maskStream->read_seconds();
+        add_images(in, plan, glm, fit, times);
         t0 = clk::now();
-        const uint8_t *slabRegion = region.empty() ? nullptr : region.data() + at;
+        const uint8_t *slabRegion = in.region.empty() ? nullptr : in.region.data() + at;
         slabBeta.resize(p * slabVoxels);
         slabT.resize(n_c * slabVoxels);
-        if (frog_glm_finish(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, fill, slabBeta.data(), sigma.data() + at,
-                            slabT.data(), count.data() + at)) die(frog_last_error());
+        if (frog_glm_finish(glm, (uint32_t)n_c, in.contrasts.data(), minCount, o.sigmaFloor, slabRegion, o.fill, slabBeta.data(), fit.sigma.data() + at, slabT.data(),
+                            fit.count.data() + at)) die(frog_last_error());
         // a residual stdev is never -1: the voxels that were not fit
-        if (frog_glm_finish(glm, 0, nullptr, (uint32_t)minCount, sigmaFloor, slabRegion, -1.0f, nullptr, marker.data() + at, nullptr, nullptr)) die(frog_last_error());
-        for (size_t j = 0; j < p; j++) std::memcpy(beta.data() + j * total + at, slabBeta.data() + j * slabVoxels, slabVoxels * sizeof(float));
-        for (size_t c = 0; c < n_c; c++) std::memcpy(t.data() + c * total + at, slabT.data() + c * slabVoxels, slabVoxels * sizeof(float));
-        if (nPerms) {
-            const int8_t *signs = flips == 1 ? sign.data() : nullptr;
-            if (sink ? frog_glm_permute_clusters(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, columns, (uint32_t)nPerms,
-                                                 perm.data(), signs, 0, sink, slabMax.data(), slabMin.data())
-                     : frog_glm_permute(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, columns, (uint32_t)nPerms, perm.data(),
-                                        signs, slabMax.data(), slabMin.data())) die(frog_last_error());
-            // the same adds fill the second sink; the extrema are the same bits and are taken once
-            if (enhance && frog_glm_permute_tfce(glm, (uint32_t)n_c, contrasts.data(), (uint32_t)minCount, sigmaFloor, slabRegion, columns, (uint32_t)nPerms,
-                                                 perm.data(), signs, 0, enhance, nullptr, nullptr)) die(frog_last_error());
-            for (size_t e = 0; e < maxT.size(); e++) {
-                if (float_key(slabMax[e]) > float_key(maxT[e])) maxT[e] = slabMax[e];
-                if (float_key(slabMin[e]) < float_key(minT[e])) minT[e] = slabMin[e];
-            }
-        }
+        if (frog_glm_finish(glm, 0, nullptr, minCount, o.sigmaFloor, slabRegion, -1.0f, nullptr, fit.marker.data() + at, nullptr, nullptr)) die(frog_last_error());
+        for (size_t j = 0; j < p; j++) std::memcpy(fit.beta.data() + j * total + at, slabBeta.data() + j * slabVoxels, slabVoxels * sizeof(float));
+        for (size_t c = 0; c < n_c; c++) std::memcpy(fit.t.data() + c * total + at, slabT.data() + c * slabVoxels, slabVoxels * sizeof(float));
+        if (o.nPerms) permute_slab(o, in, plan, glm, slabRegion, sink, enhance, fit, slabMax, slabMin);
         times.device_s += seconds(t0);
         frog_glm_destroy(glm);
     }
-    for (frog_chain *c : chains) frog_chain_destroy(c);
-    // the cluster-extent test: every slot's largest extent, and the observed map's labels, the negative side's after the positive's
-    const uint32_t sides = twoSided == 1 ? 2 : 1;
-    std::vector<uint32_t> slotExtent, clusterLabels, sideLabels;
-    std::vector<std::vector<int>> clusterSign(n_c);
-    if (sink) {
-        t0 = clk::now();
-        slotExtent.resize((size_t)nPerms * n_c * sides);
-        if (frog_clusters_finish(sink, slotExtent.data())) die(frog_last_error());
-        clusterLabels.assign(n_c * total, 0);
-        sideLabels.resize(total);
-        for (size_t c = 0; c < n_c; c++)
-            for (uint32_t side = 0; side < sides; side++) {
-                uint32_t found = 0;
-                if (frog_clusters_labels(sink, 0, (uint32_t)c, (int)side, sideLabels.data(), &found)) die(frog_last_error());
-                const uint32_t before = (uint32_t)clusterSign[c].size();
-                for (size_t v = 0; v < total; v++) if (sideLabels[v]) clusterLabels[c * total + v] = sideLabels[v] + before;
-                clusterSign[c].resize(before + found, side ? -1 : 1);
-            }
-        times.device_s += seconds(t0);
-        frog_clusters_destroy(sink);
-    }
-    // threshold-free cluster enhancement: every slot's largest value, and the observed maps, the negative side's negated
-    std::vector<float> slotTfce, tfceMap, sideMap;
-    if (enhance) {
-        t0 = clk::now();
-        slotTfce.resize((size_t)nPerms * n_c * sides);
-        if (frog_tfce_finish(enhance, slotTfce.data())) die(frog_last_error());
-        tfceMap.resize(n_c * total);
-        sideMap.resize(total);
-        for (size_t c = 0; c < n_c; c++) {
-            if (frog_tfce_map(enhance, 0, (uint32_t)c, 0, tfceMap.data() + c * total)) die(frog_last_error());
-            if (sides == 2) {
-                if (frog_tfce_map(enhance, 0, (uint32_t)c, 1, sideMap.data())) die(frog_last_error());
-                for (size_t v = 0; v < total; v++) tfceMap[c * total + v] -= sideMap[v];       // a voxel has at most one side
-            }
+    for (frog_chain *c : plan.chains) frog_chain_destroy(c);
+}
+
+// ---- the sinks' read-outs ----------------------------------------------------------------------------------------------------------
+
+// the cluster-extent test: every slot's largest extent, and the observed map's labels, the negative side's after the positive's
+struct Clusters {
+    std::vector<uint32_t> extent, labels;           // [(permutation * n_c + contrast) * sides + side], [contrast * total + voxel]
+    std::vector<std::vector<int>> sign;             // per contrast: +1 or -1 of cluster l at [l - 1]
+};
+
+void read_clusters(frog_clusters *sink, const Options &o, const Inputs &in, Clusters &got, PhaseTimes &times)
+{
+    const auto t0 = clk::now();
+    const uint32_t sides = o.sides();
+    got.extent.resize((size_t)o.nPerms * in.n_c * sides);
+    if (frog_clusters_finish(sink, got.extent.data())) die(frog_last_error());
+    got.labels.assign(in.n_c * in.total, 0);
+    got.sign.resize(in.n_c);
+    std::vector<uint32_t> sideLabels(in.total);
+    for (size_t c = 0; c < in.n_c; c++)
+        for (uint32_t side = 0; side < sides; side++) {
+            uint32_t found = 0;
+            if (frog_clusters_labels(sink, 0, (uint32_t)c, (int)side, sideLabels.data(), &found)) die(frog_last_error());
+            const uint32_t before = (uint32_t)got.sign[c].size();
+            for (size_t v = 0; v < in.total; v++) if (sideLabels[v]) got.labels[c * in.total + v] = sideLabels[v] + before;
+            got.sign[c].resize(before + found, side ? -1 : 1);
         }
-        times.device_s += seconds(t0);
-        frog_tfce_destroy(enhance);
+    times.device_s += seconds(t0);
+    frog_clusters_destroy(sink);
+}
+
+// threshold-free cluster enhancement: every slot's largest value, and the observed maps, the negative side's negated
+struct Enhanced {
+    std::vector<float> max, map;                    // [(permutation * n_c + contrast) * sides + side], [contrast * total + voxel]
+};
+
+void read_tfce(frog_tfce *enhance, const Options &o, const Inputs &in, Enhanced &got, PhaseTimes &times)
+{
+    const auto t0 = clk::now();
+    const uint32_t sides = o.sides();
+    got.max.resize((size_t)o.nPerms * in.n_c * sides);
+    if (frog_tfce_finish(enhance, got.max.data())) die(frog_last_error());
+    got.map.resize(in.n_c * in.total);
+    std::vector<float> sideMap(in.total);
+    for (size_t c = 0; c < in.n_c; c++) {
+        if (frog_tfce_map(enhance, 0, (uint32_t)c, 0, got.map.data() + c * in.total)) die(frog_last_error());
+        if (sides == 2) {
+            if (frog_tfce_map(enhance, 0, (uint32_t)c, 1, sideMap.data())) die(frog_last_error());
+            for (size_t v = 0; v < in.total; v++) got.map[c * in.total + v] -= sideMap[v];     // a voxel has at most one side
+        }
     }
+    times.device_s += seconds(t0);
+    frog_tfce_destroy(enhance);
+}
+
+// ---- the files -------------------------------------------------------------------------------------------------------------------
+
+struct Output {
+    std::string dir;
+    frog_volume grid;
+
+    std::string path(const std::string &name) const { return dir + "/" + name; }
+    void volume(const std::string &name, int dtype, void *data)
+    {
+        grid.dtype = dtype;
+        grid.data = data;
+        if (frog_volume_write(path(name).c_str(), &grid)) die("cannot write " + path(name));
+    }
+    void close(std::ofstream &csv, const std::string &name) const
+    {
+        if (!frog::csv_close(csv)) die("cannot write " + path(name));
+    }
+};
+
+// the null distribution of contrast c: of(k) under the permutations k = 1..nPerms-1
+template <class T, class Of>
+frog::NullDistribution<T> null_of(long nPerms, Of of)
+{
+    std::vector<T> null((size_t)nPerms - 1);
+    for (long k = 1; k < nPerms; k++) null[k - 1] = of(k);
+    return frog::NullDistribution<T>(std::move(null));
+}
+
+void write_maps(Output &out, const Inputs &in, Fit &fit)
+{
+    for (size_t j = 0; j < in.p; j++) out.volume("beta_" + std::to_string(j) + ".nii.gz", FROG_V_F32, fit.beta.data() + j * in.total);
+    out.volume("sigma.nii.gz", FROG_V_F32, fit.sigma.data());
+    out.volume("count.nii.gz", FROG_V_U16, fit.count.data());
+    for (size_t c = 0; c < in.n_c; c++) out.volume("t_" + std::to_string(c) + ".nii.gz", FROG_V_F32, fit.t.data() + c * in.total);
+}
+
+// glm.csv's last two columns, per contrast: NaN and 0 without permutations
+struct Verdicts {
+    std::vector<double> threshold;
+    std::vector<uint64_t> beyond;
+};
+
+// maxt.csv and fwe_p_<c>
+void write_fwe(Output &out, const Options &o, const Inputs &in, const Fit &fit, Verdicts &verdicts)
+{
+    const size_t n_c = in.n_c, total = in.total;
+    const long nPerms = o.nPerms;
+    std::ofstream csv(out.path("maxt.csv"));
+    csv << "permutation,contrast,max,min\n";
+    for (long k = 0; k < nPerms; k++)
+        for (size_t c = 0; c < n_c; c++) csv << k << "," << c << "," << csv_float(fit.maxT[k * n_c + c]) << "," << csv_float(fit.minT[k * n_c + c]) << "\n";
+    out.close(csv, "maxt.csv");
+    std::vector<float> pmap(total);
+    for (size_t c = 0; c < n_c; c++) {
+        const auto null = null_of<float>(nPerms, [&](long k) {
+            const float row[2] = { fit.maxT[k * n_c + c], -fit.minT[k * n_c + c] };
+            return frog::sides_max(row, o.sides());
+        });
+        verdicts.threshold[c] = null.threshold_p05();
+        for (size_t v = 0; v < total; v++) {
+            float value = fit.t[c * total + v];
+            if (o.twoSided == 1) value = std::fabs(value);
+            pmap[v] = 1.0f;
+            if (fit.marker[v] == -1.0f || std::isnan(value)) continue;
+            const auto verdict = null.test(value);
+            pmap[v] = verdict.p;
+            if (verdict.significant) verdicts.beyond[c]++;
+        }
+        out.volume("fwe_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
+    }
+}
+
+// maxextent.csv, clusters.csv, clusters_<c> and cluster_p_<c>
+void write_clusters(Output &out, const Options &o, const Inputs &in, const Fit &fit, Clusters &got)
+{
+    const size_t n_c = in.n_c, total = in.total;
+    const long nPerms = o.nPerms;
+    std::ofstream csv(out.path("maxextent.csv")), table(out.path("clusters.csv"));
+    csv << "permutation,contrast,extent\n";
+    table << "contrast,cluster,sign,voxels,peak_t,peak_x,peak_y,peak_z,p_fwe\n";
+    auto nullExtent = [&](long k, size_t c) { return frog::sides_max(got.extent.data() + ((size_t)k * n_c + c) * o.sides(), o.sides()); };
+    for (long k = 0; k < nPerms; k++)
+        for (size_t c = 0; c < n_c; c++) csv << k << "," << c << "," << nullExtent(k, c) << "\n";
+    out.close(csv, "maxextent.csv");
+    std::vector<float> pmap(total);
+    for (size_t c = 0; c < n_c; c++) {
+        const size_t found = got.sign[c].size();
+        const uint32_t *labels = got.labels.data() + c * total;
+        const float *t = fit.t.data() + c * total;
+        std::vector<uint64_t> voxels(found + 1, 0);
+        std::vector<size_t> peak(found + 1, total);
+        for (size_t v = 0; v < total; v++) {
+            const uint32_t l = labels[v];
+            if (!l) continue;
+            voxels[l]++;
+            if (peak[l] == total || std::fabs(t[v]) > std::fabs(t[peak[l]])) peak[l] = v;
+        }
+        const auto null = null_of<uint32_t>(nPerms, [&](long k) { return nullExtent(k, c); });
+        std::vector<float> pOf(found + 1, 1.0f);
+        for (size_t l = 1; l <= found; l++) {
+            pOf[l] = null.p((uint32_t)voxels[l]);
+            table << c << "," << l << "," << got.sign[c][l - 1] << "," << voxels[l] << ",";
+            frog::write_peak(table, t, peak[l], in.grid.dims);
+            table << "," << csv_float(pOf[l]) << "\n";
+        }
+        for (size_t v = 0; v < total; v++) pmap[v] = pOf[labels[v]];
+        out.volume("clusters_" + std::to_string(c) + ".nii.gz", FROG_V_I32, got.labels.data() + c * total);
+        out.volume("cluster_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
+    }
+    out.close(table, "clusters.csv");
+}
+
+// maxtfce.csv, tfce.csv, tfce_<c> and tfce_p_<c>
+void write_tfce(Output &out, const Options &o, const Inputs &in, Enhanced &got)
+{
+    const size_t n_c = in.n_c, total = in.total;
+    const long nPerms = o.nPerms;
+    std::ofstream csv(out.path("maxtfce.csv")), table(out.path("tfce.csv"));
+    csv << "permutation,contrast,max_tfce\n";
+    table << "contrast,peak_tfce,peak_x,peak_y,peak_z,threshold_p05,voxels_p05\n";
+    auto nullTfce = [&](long k, size_t c) { return frog::sides_max(got.max.data() + ((size_t)k * n_c + c) * o.sides(), o.sides()); };
+    for (long k = 0; k < nPerms; k++)
+        for (size_t c = 0; c < n_c; c++) csv << k << "," << c << "," << csv_float(nullTfce(k, c)) << "\n";
+    out.close(csv, "maxtfce.csv");
+    std::vector<float> pmap(total);
+    for (size_t c = 0; c < n_c; c++) {
+        const auto null = null_of<float>(nPerms, [&](long k) { return nullTfce(k, c); });
+        const float *map = got.map.data() + c * total;
+        uint64_t past = 0;
+        size_t peak = total;
+        for (size_t v = 0; v < total; v++) {
+            const float value = std::fabs(map[v]);
+            pmap[v] = 1.0f;
+            if (value == 0.0f) continue;
+            const auto verdict = null.test(value);
+            pmap[v] = verdict.p;
+            if (verdict.significant) past++;
+            if (peak == total || value > std::fabs(map[peak])) peak = v;
+        }
+        table << c << ",";
+        frog::write_peak(table, map, peak, in.grid.dims);
+        table << "," << csv_float((float)null.threshold_p05()) << "," << past << "\n";
+        out.volume("tfce_" + std::to_string(c) + ".nii.gz", FROG_V_F32, got.map.data() + c * total);
+        out.volume("tfce_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
+    }
+    out.close(table, "tfce.csv");
+}
+
+void write_glm_csv(const Output &out, const Options &o, const Inputs &in, const Fit &fit, const Verdicts &verdicts)
+{
+    const size_t total = in.total;
+    std::ofstream csv(out.path("glm.csv"));
+    csv << "contrast,fit_voxels,peak_t,peak_x,peak_y,peak_z,threshold_p05,voxels_p05\n";
+    for (size_t c = 0; c < in.n_c; c++) {
+        const float *t = fit.t.data() + c * total;
+        uint64_t fitted = 0;
+        size_t peak = total;
+        for (size_t v = 0; v < total; v++) {
+            const float value = t[v];
+            if (fit.marker[v] == -1.0f || std::isnan(value)) continue;
+            fitted++;
+            const float best = peak < total ? t[peak] : 0.0f;
+            if (peak == total || (o.twoSided == 1 ? std::fabs(value) > std::fabs(best) : value > best)) peak = v;
+        }
+        csv << c << "," << fitted << ",";
+        frog::write_peak(csv, t, peak, in.grid.dims);
+        csv << "," << csv_float((float)verdicts.threshold[c]) << "," << verdicts.beyond[c] << "\n";
+    }
+    out.close(csv, "glm.csv");
+}
+
+} // namespace
+
+int main(int argc, char *argv[])
+{
+    PhaseTimes times;
+    const Options o = parse_options(argc, argv);
+    if (o.positional.size() != 3) {
+        std::cout << "Usage : GroupStats bbox.json spacing design.csv [-c contrasts.csv] [-td transformsDir] [-o outDir] "
+                     "[-v jacobian|logjacobian|images] [-vl volumes.txt] [-ml masks.txt] [-m regionMask] [-mc minCount] [-sf sigmaFloor] "
+                     "[-f fill] [-np nPerms] [-ps seed] [-pc columns] [-pf 1] [-two 1] [-ct threshold] [-cc 6|18|26] [-tf 1] [-tfd dh] [-tfe 0.5|1] [-tfh 1|2] "
+                     "[-s fwhm_mm] [-rp planes] [-dev n]\n-tf 1: threshold-free cluster enhancement in steps of dh (default 0.1); a statistic beyond 255 * dh "
+                     "saturates there" << std::endl;
+        return 1;
+    }
+
+    // ---- everything is checked before the first output: the options, the inputs, and that the sinks fit the device
+    Inputs in;
+    check_options(o, in);
+    load_model(o, in);
+    load_images(o, in);
+    frog_clusters *sink = nullptr;
+    if (o.clusterTest && frog_clusters_create(&in.grid, (uint32_t)o.nPerms, (uint32_t)in.n_c, o.twoSided == 1, (float)o.clusterThreshold, o.connectivity, o.device, &sink))
+        die(frog_last_error());
+    frog_tfce *enhance = nullptr;
+    if (o.tfceTest && frog_tfce_create(&in.grid, (uint32_t)o.nPerms, (uint32_t)in.n_c, o.twoSided == 1, (float)o.tfceStep, o.tfceE, o.tfceH, o.connectivity, o.device, &enhance))
+        die(frog_last_error());
+    begin_output(o.outDir, in.n, "images", in.grid);
+
+    // ---- the device's work: the slabs, then each sink's read-out
+    auto t0 = clk::now();
+    Plan plan;
+    set_up(o, in, plan);
+    times.setup_s = seconds(t0);
+    Fit fit;
+    fit_slabs(o, in, plan, sink, enhance, fit, times);
+    Clusters clusters;
+    Enhanced enhanced;
+    if (sink) read_clusters(sink, o, in, clusters, times);
+    if (enhance) read_tfce(enhance, o, in, enhanced, times);
 
     // ---- the files
     t0 = clk::now();
-    auto write = [&](const std::string &name, int dtype, void *data) {
-        grid.dtype = dtype;
-        grid.data = data;
-        const std::string path = outDir + "/" + name;
-        if (frog_volume_write(path.c_str(), &grid)) die("cannot write " + path);
-    };
-    for (size_t j = 0; j < p; j++) write("beta_" + std::to_string(j) + ".nii.gz", FROG_V_F32, beta.data() + j * total);
-    write("sigma.nii.gz", FROG_V_F32, sigma.data());
-    write("count.nii.gz", FROG_V_U16, count.data());
-    for (size_t c = 0; c < n_c; c++) write("t_" + std::to_string(c) + ".nii.gz", FROG_V_F32, t.data() + c * total);
-    std::vector<double> threshold(n_c, NAN);
-    std::vector<uint64_t> beyond(n_c, 0);
-    if (nPerms) {
-        std::ofstream csv(outDir + "/maxt.csv");
-        csv << "permutation,contrast,max,min\n";
-        for (long k = 0; k < nPerms; k++)
-            for (size_t c = 0; c < n_c; c++) csv << k << "," << c << "," << csv_float(maxT[k * n_c + c]) << "," << csv_float(minT[k * n_c + c]) << "\n";
-        csv.close();
-        if (!csv) die("cannot write " + outDir + "/maxt.csv");
-        std::vector<float> pmap(total), null((size_t)nPerms - 1);
-        for (size_t c = 0; c < n_c; c++) {
-            for (long k = 1; k < nPerms; k++) {
-                const float hi = maxT[k * n_c + c], lo = -minT[k * n_c + c];
-                null[k - 1] = twoSided == 1 && lo > hi ? lo : hi;
-            }
-            std::sort(null.begin(), null.end());
-            // p < 0.05 iff 20 (1 + exceedances) < nPerms: the largest such count, and the null maximum a t must exceed for it
-            const long allowed = (nPerms - 1) / 20 - 1;         // exceedances allowed; < 0: none gives p < 0.05
-            threshold[c] = allowed < 0 ? INFINITY : (allowed >= (long)null.size() ? -INFINITY : (double)null[null.size() - 1 - allowed]);
-            for (size_t v = 0; v < total; v++) {
-                float value = t[c * total + v];
-                if (twoSided == 1) value = std::fabs(value);
-                float pv = 1.0f;
-                if (marker[v] != -1.0f && !std::isnan(value)) {
-                    const size_t exceed = null.end() - std::lower_bound(null.begin(), null.end(), value);
-                    pv = (float)((double)(1 + exceed) / (double)nPerms);
-                    if (20 * (1 + (long)exceed) < nPerms) beyond[c]++;
-                }
-                pmap[v] = pv;
-            }
-            write("fwe_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
-        }
-    }
-    if (clusterTest) {
-        std::ofstream csv(outDir + "/maxextent.csv"), table(outDir + "/clusters.csv");
-        csv << "permutation,contrast,extent\n";
-        table << "contrast,cluster,sign,voxels,peak_t,peak_x,peak_y,peak_z,p_fwe\n";
-        auto nullExtent = [&](long k, size_t c) {
-            const uint32_t *e = slotExtent.data() + ((size_t)k * n_c + c) * sides;
-            return sides == 2 ? std::max(e[0], e[1]) : e[0];
-        };
-        for (long k = 0; k < nPerms; k++)
-            for (size_t c = 0; c < n_c; c++) csv << k << "," << c << "," << nullExtent(k, c) << "\n";
-        csv.close();
-        if (!csv) die("cannot write " + outDir + "/maxextent.csv");
-        std::vector<float> pmap(total);
-        std::vector<uint32_t> null((size_t)nPerms - 1);
-        for (size_t c = 0; c < n_c; c++) {
-            const size_t found = clusterSign[c].size();
-            const uint32_t *labels = clusterLabels.data() + c * total;
-            std::vector<uint64_t> voxels(found + 1, 0);
-            std::vector<size_t> peak(found + 1, total);
-            for (size_t v = 0; v < total; v++) {
-                const uint32_t l = labels[v];
-                if (!l) continue;
-                voxels[l]++;
-                if (peak[l] == total || std::fabs(t[c * total + v]) > std::fabs(t[c * total + peak[l]])) peak[l] = v;
-            }
-            for (long k = 1; k < nPerms; k++) null[k - 1] = nullExtent(k, c);
-            std::sort(null.begin(), null.end());
-            std::vector<float> pOf(found + 1, 1.0f);
-            for (size_t l = 1; l <= found; l++) {
-                const size_t reach = null.end() - std::lower_bound(null.begin(), null.end(), (uint32_t)voxels[l]);
-                pOf[l] = (float)((double)(1 + reach) / (double)nPerms);
-                table << c << "," << l << "," << clusterSign[c][l - 1] << "," << voxels[l] << "," << csv_float(t[c * total + peak[l]]) << "," << peak[l] % grid.dims[0]
-                      << "," << (peak[l] / grid.dims[0]) % grid.dims[1] << "," << peak[l] / plane << "," << csv_float(pOf[l]) << "\n";
-            }
-            for (size_t v = 0; v < total; v++) pmap[v] = pOf[labels[v]];
-            write("clusters_" + std::to_string(c) + ".nii.gz", FROG_V_I32, clusterLabels.data() + c * total);
-            write("cluster_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
-        }
-        table.close();
-        if (!table) die("cannot write " + outDir + "/clusters.csv");
-    }
-    if (tfceTest) {
-        std::ofstream csv(outDir + "/maxtfce.csv"), table(outDir + "/tfce.csv");
-        csv << "permutation,contrast,max_tfce\n";
-        table << "contrast,peak_tfce,peak_x,peak_y,peak_z,threshold_p05,voxels_p05\n";
-        auto nullTfce = [&](long k, size_t c) {
-            const float *e = slotTfce.data() + ((size_t)k * n_c + c) * sides;
-            return sides == 2 ? std::max(e[0], e[1]) : e[0];
-        };
-        for (long k = 0; k < nPerms; k++)
-            for (size_t c = 0; c < n_c; c++) csv << k << "," << c << "," << csv_float(nullTfce(k, c)) << "\n";
-        csv.close();
-        if (!csv) die("cannot write " + outDir + "/maxtfce.csv");
-        std::vector<float> pmap(total), null((size_t)nPerms - 1);
-        for (size_t c = 0; c < n_c; c++) {
-            for (long k = 1; k < nPerms; k++) null[k - 1] = nullTfce(k, c);
-            std::sort(null.begin(), null.end());
-            // maxt.csv's rule: the largest null maximum a value must exceed for p < 0.05
-            const long allowed = (nPerms - 1) / 20 - 1;
-            const double limit = allowed < 0 ? INFINITY : (allowed >= (long)null.size() ? -INFINITY : (double)null[null.size() - 1 - allowed]);
-            const float *map = tfceMap.data() + c * total;
-            uint64_t past = 0;
-            size_t peak = total;
-            for (size_t v = 0; v < total; v++) {
-                const float value = std::fabs(map[v]);
-                float pv = 1.0f;
-                if (value != 0.0f) {
-                    const size_t exceed = null.end() - std::lower_bound(null.begin(), null.end(), value);
-                    pv = (float)((double)(1 + exceed) / (double)nPerms);
-                    if (20 * (1 + (long)exceed) < nPerms) past++;
-                    if (peak == total || value > std::fabs(map[peak])) peak = v;
-                }
-                pmap[v] = pv;
-            }
-            table << c << ",";
-            if (peak < total) table << csv_float(map[peak]) << "," << peak % grid.dims[0] << "," << (peak / grid.dims[0]) % grid.dims[1] << "," << peak / plane;
-            else table << "nan,,,";
-            table << "," << csv_float((float)limit) << "," << past << "\n";
-            write("tfce_" + std::to_string(c) + ".nii.gz", FROG_V_F32, tfceMap.data() + c * total);
-            write("tfce_p_" + std::to_string(c) + ".nii.gz", FROG_V_F32, pmap.data());
-        }
-        table.close();
-        if (!table) die("cannot write " + outDir + "/tfce.csv");
-    }
-    {
-        std::ofstream csv(outDir + "/glm.csv");
-        csv << "contrast,fit_voxels,peak_t,peak_x,peak_y,peak_z,threshold_p05,voxels_p05\n";
-        for (size_t c = 0; c < n_c; c++) {
-            uint64_t fit = 0;
-            size_t peak = total;
-            for (size_t v = 0; v < total; v++) {
-                const float value = t[c * total + v];
-                if (marker[v] == -1.0f || std::isnan(value)) continue;
-                fit++;
-                const float best = peak < total ? t[c * total + peak] : 0.0f;
-                if (peak == total || (twoSided == 1 ? std::fabs(value) > std::fabs(best) : value > best)) peak = v;
-            }
-            csv << c << "," << fit << ",";
-            if (peak < total) csv << csv_float(t[c * total + peak]) << "," << peak % grid.dims[0] << "," << (peak / grid.dims[0]) % grid.dims[1] << "," << peak / plane;
-            else csv << "nan,,,";
-            csv << "," << (std::isnan(threshold[c]) ? std::string("nan") : csv_float((float)threshold[c])) << "," << beyond[c] << "\n";
-        }
-        csv.close();
-        if (!csv) die("cannot write " + outDir + "/glm.csv");
-    }
+    Output out{ o.outDir, in.grid };
+    Verdicts verdicts{ std::vector<double>(in.n_c, NAN), std::vector<uint64_t>(in.n_c, 0) };
+    write_maps(out, in, fit);
+    if (o.nPerms) write_fwe(out, o, in, fit, verdicts);
+    if (o.clusterTest) write_clusters(out, o, in, fit, clusters);
+    if (o.tfceTest) write_tfce(out, o, in, enhanced);
+    write_glm_csv(out, o, in, fit, verdicts);
     times.write_s += seconds(t0);
-    times.print(read_s, images || !masks.empty() ? threads : 0);
+    times.print(fit.read_s, in.images || !in.masks.empty() ? fit.threads : 0);
     return 0;
 }

@@ -467,7 +467,32 @@ class GroupGLM(_Accumulator):
         return hi, lo
 
 
-class ClusterSink(_Accumulator):
+class _PermutationSink(_Accumulator):
+    """What ClusterSink and TfceSink share: the slots (n_perms, n_contrasts, sides) for the whole grid of `shape`, which every
+    create takes first, the per-slot value of finish() and a slot's outputs on the grid."""
+
+    def __init__(self, grid, n_perms, n_contrasts, two_sided, *create_args):
+        super().__init__(grid, int(n_perms), int(n_contrasts), int(bool(two_sided)), *create_args)
+        self.n_perms, self.n_contrasts, self.sides = int(n_perms), int(n_contrasts), 2 if two_sided else 1
+        self.shape = self.dims[::-1]
+
+    def _output(self, name, shape, dtype, *slot, extra=()):
+        """The new array that frog_<_NAME>_<name>(handle, *slot, the array, *extra) fills."""
+        out = np.empty(shape, dtype)
+        where = f"frog_{self._NAME}_{name}"
+        pointer = out.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(out.dtype)))
+        _abi.check(getattr(self._lib, where)(self._h, *slot, pointer, *extra), where)
+        return out
+
+    def _finish(self, dtype):
+        return self._output("finish", (self.n_perms, self.n_contrasts, self.sides), dtype)
+
+    def _slot(self, name, dtype, perm, contrast, side, *extra):
+        """One slot's output `name` on the grid; `extra`: the byref arguments the library's function takes after it."""
+        return self._output(name, self.shape, dtype, int(perm), int(contrast), int(side), extra=extra)
+
+
+class ClusterSink(_PermutationSink):
     """frog_clusters (include/frog_chain.h): on the device, for the whole `grid`, one bit mask per slot (permutation, contrast,
     side) of the voxels whose t lies beyond `threshold` (side 0: t > threshold; with two_sided side 1: t < -threshold), which
     GroupGLM.permute_clusters fills window by window, and the connected components of each mask at `connectivity`."""
@@ -475,33 +500,23 @@ class ClusterSink(_Accumulator):
     _NAME = "clusters"
 
     def __init__(self, grid, n_perms, n_contrasts, threshold, two_sided=False, connectivity=26, device=0):
-        super().__init__(grid, int(n_perms), int(n_contrasts), int(bool(two_sided)), float(threshold), int(connectivity), int(device))
-        self.n_perms, self.n_contrasts, self.sides = int(n_perms), int(n_contrasts), 2 if two_sided else 1
-        self.shape = self.dims[::-1]
+        super().__init__(grid, n_perms, n_contrasts, two_sided, float(threshold), int(connectivity), int(device))
 
     def finish(self):
         """The largest extent of every slot's mask, uint32 (n_perms, n_contrasts, sides); 0 where no voxel is set."""
-        out = np.empty((self.n_perms, self.n_contrasts, self.sides), np.uint32)
-        _abi.check(self._lib.frog_clusters_finish(self._h, out.ctypes.data_as(_abi.c_u32_p)), "frog_clusters_finish")
-        return out
+        return self._finish(np.uint32)
 
     def mask(self, perm, contrast, side=0):
         """One slot's mask, bool on the grid."""
-        out = np.empty(self.shape, np.uint8)
-        _abi.check(self._lib.frog_clusters_mask(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(C.POINTER(C.c_uint8))),
-                   "frog_clusters_mask")
-        return out != 0
+        return self._slot("mask", np.uint8, perm, contrast, side) != 0
 
     def labels(self, perm, contrast, side=0):
         """(labels uint32 on the grid, n): one slot's components numbered 1..n in ascending order of their smallest voxel index."""
-        out = np.empty(self.shape, np.uint32)
         n = C.c_uint32()
-        _abi.check(self._lib.frog_clusters_labels(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(_abi.c_u32_p), C.byref(n)),
-                   "frog_clusters_labels")
-        return out, n.value
+        return self._slot("labels", np.uint32, perm, contrast, side, C.byref(n)), n.value
 
 
-class TfceSink(_Accumulator):
+class TfceSink(_PermutationSink):
     """frog_tfce (include/frog_chain.h): on the device, for the whole `grid`, one u8 level per voxel and slot (permutation,
     contrast, side) -- trunc(t / dh) on side 0 and, with two_sided, trunc(-t / dh) on side 1, saturated at 255 -- which
     GroupGLM.permute_tfce fills window by window, and the threshold-free cluster enhancement of each slot with the exponents
@@ -510,28 +525,28 @@ class TfceSink(_Accumulator):
     _NAME = "tfce"
 
     def __init__(self, grid, n_perms, n_contrasts, dh=0.1, e=0.5, h=2, two_sided=False, connectivity=26, device=0):
-        super().__init__(grid, int(n_perms), int(n_contrasts), int(bool(two_sided)), float(dh), float(e), float(h), int(connectivity), int(device))
-        self.n_perms, self.n_contrasts, self.sides = int(n_perms), int(n_contrasts), 2 if two_sided else 1
-        self.shape = self.dims[::-1]
+        super().__init__(grid, n_perms, n_contrasts, two_sided, float(dh), float(e), float(h), int(connectivity), int(device))
 
     def finish(self):
         """The largest tfce of every slot, float32 (n_perms, n_contrasts, sides); 0 where no voxel has a positive level."""
-        out = np.empty((self.n_perms, self.n_contrasts, self.sides), np.float32)
-        _abi.check(self._lib.frog_tfce_finish(self._h, out.ctypes.data_as(_abi.c_float_p)), "frog_tfce_finish")
-        return out
+        return self._finish(np.float32)
 
     def levels(self, perm, contrast, side=0):
         """One slot's levels, uint8 on the grid."""
-        out = np.empty(self.shape, np.uint8)
-        _abi.check(self._lib.frog_tfce_levels(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(C.POINTER(C.c_uint8))),
-                   "frog_tfce_levels")
-        return out
+        return self._slot("levels", np.uint8, perm, contrast, side)
 
     def map(self, perm, contrast, side=0):
         """One slot's enhanced map, float32 on the grid."""
-        out = np.empty(self.shape, np.float32)
-        _abi.check(self._lib.frog_tfce_map(self._h, int(perm), int(contrast), int(side), out.ctypes.data_as(_abi.c_float_p)), "frog_tfce_map")
-        return out
+        return self._slot("map", np.float32, perm, contrast, side)
+
+
+def _null_p(values, null, dtype):
+    """The family-wise corrected p of `values` against one contrast's null row: (float32)((1 + #{k >= 1: null[k] >= value}) /
+    (double)n_perms).  null[0] belongs to the unpermuted design and is no part of the null; the sort and the comparisons are
+    made in `dtype`."""
+    ranked = np.sort(np.asarray(null, dtype)[1:])
+    beyond = len(ranked) - np.searchsorted(ranked, np.asarray(values, dtype), side="left")
+    return ((1 + beyond).astype(np.float64) / np.float64(len(ranked) + 1)).astype(np.float32)
 
 
 def tfce(stat, dh=0.1, e=0.5, h=2, connectivity=26, side=0, device=0):
@@ -550,10 +565,7 @@ def tfce_p(tfce, null):
     """The family-wise corrected p of enhanced values: (float32)((1 + #{k >= 1: null[k] >= tfce}) / (double)n_perms), null the
     n_perms largest enhanced values with row 0 the unpermuted design; 1 where tfce == 0.  Signed maps go by magnitude."""
     t = np.abs(np.asarray(tfce, np.float32))
-    ranked = np.sort(np.asarray(null, np.float32)[1:])
-    beyond = len(ranked) - np.searchsorted(ranked, t, side="left")
-    p = ((1 + beyond).astype(np.float64) / np.float64(len(ranked) + 1)).astype(np.float32)
-    return np.where(t == 0, np.float32(1), p)
+    return np.where(t == 0, np.float32(1), _null_p(t, null, np.float32))
 
 
 def components(mask, connectivity=26, device=0, largest=False):
@@ -574,9 +586,7 @@ def components(mask, connectivity=26, device=0, largest=False):
 def cluster_p(extent, max_extent):
     """The family-wise corrected p of clusters of `extent` voxels: (float32)((1 + #{k >= 1: max_extent[k] >= extent}) /
     (double)n_perms), max_extent the n_perms largest null extents with row 0 the unpermuted design."""
-    null = np.sort(np.asarray(max_extent, np.int64)[1:])
-    beyond = len(null) - np.searchsorted(null, np.asarray(extent, np.int64), side="left")
-    return ((1 + beyond).astype(np.float64) / np.float64(len(null) + 1)).astype(np.float32)
+    return _null_p(extent, max_extent, np.int64)
 
 
 def glm_planes(grid, n_images, device=0, smooth=0.0):
@@ -647,11 +657,8 @@ def fwe_p(t, max_t, min_t=None, fit=None):
     hi = np.asarray(max_t, np.float32)
     if min_t is not None:
         hi, t = np.maximum(hi, -np.asarray(min_t, np.float32)), np.abs(t)
-    null = np.sort(hi[1:])
-    beyond = len(null) - np.searchsorted(null, t, side="left")
-    p = ((1 + beyond).astype(np.float64) / np.float64(len(hi))).astype(np.float32)
     bad = np.isnan(t) if fit is None else (np.isnan(t) | ~np.asarray(fit, bool))
-    return np.where(bad, np.float32(1), p)
+    return np.where(bad, np.float32(1), _null_p(t, hi, np.float32))
 
 
 def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=None, value="logjacobian", supports=None, interpolation=1,
@@ -699,70 +706,97 @@ def group_glm(design, contrasts, volumes=None, chains=None, masks=None, grid=Non
     if columns is None:
         columns = [j for j in range(X.shape[1]) if (c[:, j] != 0).any()]
     out = dict(beta=np.empty((X.shape[1],) + shape, np.float32), sigma=np.empty(shape, np.float32), t=np.empty((len(c),) + shape, np.float32),
-               count=np.empty(shape, np.uint16))
-    perm, sign = glm_draw(n, n_perms, seed, True, flip) if n_perms else (None, None)
-    hi = lo = None
+               count=np.empty(shape, np.uint16), fit=np.empty(shape, bool))
+    draws = glm_draw(n, n_perms, seed, True, flip) if n_perms else None
     sink = ClusterSink(grid, n_perms, len(c), cluster_threshold, two_sided, connectivity, device) if n_perms and cluster_threshold is not None else None
     enhance = None
     if n_perms and tfce:
         opt = dict(dh=0.1, e=0.5, h=2, connectivity=connectivity)
         opt.update(tfce if isinstance(tfce, dict) else {})
         enhance = TfceSink(grid, n_perms, len(c), opt["dh"], opt["e"], opt["h"], two_sided, opt["connectivity"], device)
-    for first in range(0, dims[2], planes):
-        m = min(planes, dims[2] - first)
+
+    def add(acc, k):
+        mask = None if masks is None else masks[k]
+        if images:
+            acc.add(vols[k], None if chains is None else chains[k], mask, interpolation)
+        else:
+            acc.add_jacobian(chains[k], None if supports is None else supports[k], mask, value == "logjacobian")
+
+    moves = (draws[0], draws[1] if flip else None, columns) if n_perms else None
+    hi, lo = _glm_slabs(out, grid, X, c, planes, add, reg, (min_count, sigma_floor, fill), device, smooth, moves, sink, enhance)
+    if n_perms:
+        out["max_t"], out["min_t"] = hi, lo
+        out["p"] = np.stack([fwe_p(out["t"][j], hi[:, j], lo[:, j] if two_sided else None, out["fit"]) for j in range(len(c))])
+    if sink is not None:
+        try:
+            _read_clusters(sink, out)
+        finally:
+            sink.close()
+    if enhance is not None:
+        try:
+            _read_tfce(enhance, out)
+        finally:
+            enhance.close()
+    return out
+
+
+def _glm_slabs(out, grid, X, c, planes, add, region, fit, device, smooth, moves, sink, enhance):
+    """group_glm()'s slab loop: per slab a GroupGLM, add(acc, k) for every design row, the fit with `fit` = (min_count, sigma_floor,
+    fill) into `out`, and with `moves` = (perm, sign, columns) one permute call for the extrema, which fills `sink` if there is
+    one, and one more that fills `enhance`.  Returns (max_t, min_t) over the grid, (None, None) without permutations."""
+    min_count, sigma_floor, fill = fit
+    depth = int(grid[0][2])
+    hi = lo = None
+    for first in range(0, depth, planes):
+        m = min(planes, depth - first)
         acc = GroupGLM(grid, X, (first, m), device, smooth)
         try:
-            for k in range(n):
-                mask = None if masks is None else masks[k]
-                if images:
-                    acc.add(vols[k], None if chains is None else chains[k], mask, interpolation)
-                else:
-                    acc.add_jacobian(chains[k], None if supports is None else supports[k], mask, value == "logjacobian")
-            r = None if reg is None else reg[first:first + m]
+            for k in range(len(X)):
+                add(acc, k)
+            r = None if region is None else region[first:first + m]
             b, s, t, k = acc.finish(c, min_count, sigma_floor, r, fill)
             marked = acc.finish(c, min_count, sigma_floor, r, -1.0)[1]      # a residual stdev is never -1: the unfit voxels
             sl = slice(first, first + m)
-            out["beta"][:, sl], out["sigma"][sl], out["t"][:, sl], out["count"][sl] = b, s, t, k
-            out.setdefault("fit", np.empty(shape, bool))[sl] = marked != -1
-            if n_perms:
-                h, l = acc._permute(sink, 0, c, perm, sign if flip else None, columns, min_count, sigma_floor, r)
+            out["beta"][:, sl], out["sigma"][sl], out["t"][:, sl], out["count"][sl], out["fit"][sl] = b, s, t, k, marked != -1
+            if moves is not None:
+                perm, sign, columns = moves
+                h, l = acc._permute(sink, 0, c, perm, sign, columns, min_count, sigma_floor, r)
                 if enhance is not None:
-                    acc._permute(enhance, 0, c, perm, sign if flip else None, columns, min_count, sigma_floor, r)
+                    acc._permute(enhance, 0, c, perm, sign, columns, min_count, sigma_floor, r)
                 if hi is None:
                     hi, lo = h, l
                 else:
                     hi, lo = np.where(_float_keys(h) > _float_keys(hi), h, hi), np.where(_float_keys(l) < _float_keys(lo), l, lo)
         finally:
             acc.close()
-    if n_perms:
-        out["max_t"], out["min_t"] = hi, lo
-        out["p"] = np.stack([fwe_p(out["t"][j], hi[:, j], lo[:, j] if two_sided else None, out["fit"]) for j in range(len(c))])
-    if sink is not None:
-        try:
-            out["max_extent"] = sink.finish().max(axis=2)
-            out["clusters"], out["cluster_extent"], out["cluster_p"] = np.zeros((len(c),) + shape, np.int32), [], np.ones((len(c),) + shape, np.float32)
-            for j in range(len(c)):
-                k = 0
-                for side in range(sink.sides):
-                    labels, n = sink.labels(0, j, side)
-                    out["clusters"][j][labels != 0] = labels[labels != 0].astype(np.int32) + k
-                    k += n
-                extent = np.bincount(out["clusters"][j].reshape(-1), minlength=k + 1)[1:].astype(np.uint32)
-                out["cluster_extent"].append(extent)
-                p = np.concatenate([np.ones(1, np.float32), cluster_p(extent, out["max_extent"][:, j])])
-                out["cluster_p"][j] = p[out["clusters"][j]]
-        finally:
-            sink.close()
-    if enhance is not None:
-        try:
-            out["max_tfce"] = enhance.finish().max(axis=2)
-            out["tfce"] = np.stack([enhance.map(0, j, 0) for j in range(len(c))])
-            if two_sided:
-                out["tfce"] -= np.stack([enhance.map(0, j, 1) for j in range(len(c))])      # a voxel has at most one side
-            out["tfce_p"] = np.stack([tfce_p(out["tfce"][j], out["max_tfce"][:, j]) for j in range(len(c))])
-        finally:
-            enhance.close()
-    return out
+    return hi, lo
+
+
+def _read_clusters(sink, out):
+    """group_glm()'s max_extent, clusters, cluster_extent and cluster_p into `out`, from the ClusterSink every slab has filled."""
+    n_c, shape = sink.n_contrasts, sink.shape
+    out["max_extent"] = sink.finish().max(axis=2)
+    out["clusters"], out["cluster_extent"], out["cluster_p"] = np.zeros((n_c,) + shape, np.int32), [], np.ones((n_c,) + shape, np.float32)
+    for j in range(n_c):
+        k = 0
+        for side in range(sink.sides):
+            labels, n = sink.labels(0, j, side)
+            out["clusters"][j][labels != 0] = labels[labels != 0].astype(np.int32) + k
+            k += n
+        extent = np.bincount(out["clusters"][j].reshape(-1), minlength=k + 1)[1:].astype(np.uint32)
+        out["cluster_extent"].append(extent)
+        p = np.concatenate([np.ones(1, np.float32), cluster_p(extent, out["max_extent"][:, j])])
+        out["cluster_p"][j] = p[out["clusters"][j]]
+
+
+def _read_tfce(enhance, out):
+    """group_glm()'s max_tfce, tfce and tfce_p into `out`, from the TfceSink every slab has filled."""
+    n_c = enhance.n_contrasts
+    out["max_tfce"] = enhance.finish().max(axis=2)
+    out["tfce"] = np.stack([enhance.map(0, j, 0) for j in range(n_c)])
+    if enhance.sides == 2:
+        out["tfce"] -= np.stack([enhance.map(0, j, 1) for j in range(n_c)])      # a voxel has at most one side
+    out["tfce_p"] = np.stack([tfce_p(out["tfce"][j], out["max_tfce"][:, j]) for j in range(n_c)])
 
 
 FUSED_DTYPES = ("uint8", "uint16", "int16", "int32", "uint32")

@@ -298,6 +298,21 @@ def test_sink_state_and_refusals():
     one.close()
 
 
+def test_masks_whose_bytes_cannot_be_counted_are_refused():
+    """2^32 - 1 permutations of 8 contrasts and 2 sides on the largest grid a create accepts, 2^31 voxels: the masks' bytes do
+    not fit 64 bits, and a product that wrapped would ask for a few GB.  The request is refused from the sizes alone, before
+    anything is allocated."""
+    dims = (1 << 11, 1 << 10, 1 << 10)
+    voxels = dims[0] * dims[1] * dims[2]
+    slots, words = (2 ** 32 - 1) * 16, voxels // 32
+    assert voxels == 1 << 31 and slots * (words * 4 + 8) + voxels * 8 >= 2 ** 64 > slots * (words // 2 * 4 + 8) + voxels * 4
+    with pytest.raises(_abi.FrogError) as e:
+        ClusterSink((dims, SINK_GRID[1], SINK_GRID[2]), 2 ** 32 - 1, 8, T0, True, 26)
+    text = str(e.value)
+    assert e.value.code == _abi.FROG_E_NOMEM and str(slots) in text and "masks" in text and "more than 2^64" in text and "are free" in text, text
+    assert code_of(ClusterSink, ((dims[0] + 1,) + dims[1:], SINK_GRID[1], SINK_GRID[2]), 2 ** 32 - 1, 8, T0, True, 26) == _abi.FROG_E_INVALID
+
+
 # ---- 5. group_glm and the tool -------------------------------------------------------------------------------------------------
 
 def run(args, cwd, timeout=300):
