@@ -433,6 +433,10 @@ HIP_SYMBOLS = {
     "frog_test_cull_ranges": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "frog_test_cull_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "frog_test_em_refit": (C.c_int, [C.c_void_p, C.c_int]),
+    "frog_test_ransac_candidates": (C.c_int, [C.POINTER(FrogModel), C.c_uint32, C.POINTER(FrogRansacOptions), c_double_p,
+                                              C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "frog_test_ransac_census": (C.c_int, [C.c_void_p, C.POINTER(FrogModel), C.c_uint32, c_double_p, C.c_size_t, C.c_float,
+                                          c_u32_p]),
     "frog_test_inlier_probability": (C.c_int, [C.c_int, c_float_p, c_float_p, C.c_size_t, c_float_p, c_float_p]),
     "frog_test_inlier_weight_pair": (C.c_int, [C.c_int, c_float_p, c_float_p, C.c_float, c_float_p, C.c_size_t, c_float_p,
                                               C.POINTER(C.c_ubyte)]),

@@ -1583,26 +1583,33 @@ int frog_update_stats(frog_ctx *ctx)
 }
 
 // ---- RANSAC + RANSACBatch (imageGroup.cxx:629-804) -----------------------------------------
-int frog_ransac(frog_ctx *ctx, const frog_model *m, uint32_t image, const frog_ransac_options *o, int64_t *n_inliers)
+// Three pieces: the candidates (host), their census (one launch), the selection and refit (host).  The first two are also
+// reached through frog_test_ransac_candidates / frog_test_ransac_census, so that tests see every candidate's count.
+namespace {
+
+int ransac_check(const frog_ctx *ctx, const frog_model *m, uint32_t image)
 {
-    CTX_GUARD(ctx);
-    if (!m || !o) return fail(FROG_E_INVALID, "null argument");
     if (image < ctx->ib || image >= ctx->ie) return fail(FROG_E_INVALID, "image not owned by this context");
     if (m->n_images != ctx->nI || m->point_offset[ctx->nI] != ctx->P) return fail(FROG_E_INVALID, "model does not match the context");
     if (ctx->deformable) return fail(FROG_E_STATE, "RANSAC after deformable set-up");
-    if (o->iterations < 0 || o->batches < 1) return fail(FROG_E_INVALID, "bad RANSAC options");
-    hipStream_t s = ctx->stream;
-    const uint32_t pb = ctx->poff[image], nPoints = ctx->poff[image + 1] - pb;
-    const int perBatch = o->iterations / o->batches;                         // :636
-    const float maxDistance2 = (float)std::pow((double)o->inlier_distance, 2);   // :677,:730
-    auto xyz_of = [&](uint16_t img, uint32_t pt) { return m->xyz + 3 * ((size_t)m->point_offset[img] + pt); };
+    return FROG_OK;
+}
 
-    // candidates: 4 random correspondences each (:743-760).  A draw that lands on a point without
-    // links is repeated, so an image without any link would never return: refuse it.
+// candidates: 4 random correspondences each (:743-760), 12 doubles per candidate (rows 0..2);
+// usable = a defined rotation and a determinant inside [1/maxScale, maxScale]
+int ransac_candidates(const frog_model *m, uint32_t image, const frog_ransac_options *o, std::vector<double> &cand,
+                      std::vector<uint8_t> &usable)
+{
+    if (image >= m->n_images) return fail(FROG_E_INVALID, "no such image");
+    if (o->iterations < 0 || o->batches < 1) return fail(FROG_E_INVALID, "bad RANSAC options");
+    const uint32_t pb = m->point_offset[image], nPoints = m->point_offset[image + 1] - pb;
+    const int perBatch = o->iterations / o->batches;                         // :636
+    auto xyz_of = [&](uint16_t img, uint32_t pt) { return m->xyz + 3 * ((size_t)m->point_offset[img] + pt); };
+    // A draw that lands on a point without links is repeated, so an image without any link would never return: refuse it.
     if (nPoints == 0 || m->row_ptr[pb + nPoints] == m->row_ptr[pb]) return fail(FROG_E_INVALID, "image has no link");
     const uint32_t nCand = (uint32_t)perBatch * (uint32_t)o->batches;
-    std::vector<double> cand((size_t)nCand * 12);   // 12 doubles per candidate (rows 0..2)
-    std::vector<uint8_t> usable(nCand, 0);        // determinant inside [1/maxScale, maxScale] and a defined rotation
+    cand.assign((size_t)nCand * 12, 0.0);
+    usable.assign(nCand, 0);
     #pragma omp parallel for schedule(dynamic, 1) num_threads(host_threads())    // batches are independent streams, as upstream's threads (:639-647)
     for (int batch = 0; batch < o->batches; batch++) {
         std::mt19937 rng((uint32_t)(batch * 1000));
@@ -1629,22 +1636,82 @@ int frog_ransac(frog_ctx *ctx, const frog_model *m, uint32_t image, const frog_r
             std::memcpy(&cand[c * 12], M, 12 * sizeof(double));
         }
     }
-    std::vector<unsigned int> counts(nCand, 0u);
+    return FROG_OK;
+}
+
+inline float ransac_max_distance2(float inlier_distance) { return (float)std::pow((double)inlier_distance, 2); }   // :677,:730
+
+// counts[c] = half-links of the image that candidate c brings within the distance (:762-785), all candidates in one launch
+int ransac_census(frog_ctx *ctx, const frog_model *m, uint32_t image, const double *cand, uint32_t nCand, float inlier_distance,
+                  unsigned int *counts)
+{
+    if (!nCand) return FROG_OK;
+    hipStream_t s = ctx->stream;
+    const uint32_t pb = ctx->poff[image], nPoints = ctx->poff[image + 1] - pb;
     const uint32_t lpb = pb - ctx->own_pt_begin, lpe = lpb + nPoints;
     const uint64_t nLinks = m->row_ptr[pb + nPoints] - m->row_ptr[pb];
-    if (nCand) {
-        DevBuf<double> d_cand;
-        DevBuf<unsigned int> d_counts;
-        FROG_HIP_CHECK(d_cand.upload(cand, s));
-        FROG_HIP_CHECK(d_counts.alloc(nCand));
-        FROG_HIP_CHECK(hipMemsetAsync(d_counts.p, 0, d_counts.bytes(), s));
-        const unsigned blocks = div_up(nLinks, (size_t)256 * RANSAC_LINKS);
-        ransac_count_kernel<<<blocks, 256, 0, s>>>(ctx->pos.p, ctx->pos2.p, ctx->ref_rowptr.p, ctx->ref_link.p, ctx->new_of_old.p,
-                                                  lpb, lpe, d_cand.p, nCand, maxDistance2, d_counts.p);
-        FROG_HIP_CHECK(hipGetLastError());
-        FROG_HIP_CHECK(hipMemcpyAsync(counts.data(), d_counts.p, d_counts.bytes(), hipMemcpyDeviceToHost, s));
-        FROG_HIP_CHECK(hipStreamSynchronize(s));
-    }
+    if (!nLinks) return fail(FROG_E_INVALID, "image has no link");
+    DevBuf<double> d_cand;
+    DevBuf<unsigned int> d_counts;
+    FROG_HIP_CHECK(d_cand.alloc((size_t)nCand * 12));
+    FROG_HIP_CHECK(hipMemcpyAsync(d_cand.p, cand, d_cand.bytes(), hipMemcpyHostToDevice, s));
+    FROG_HIP_CHECK(d_counts.alloc(nCand));
+    FROG_HIP_CHECK(hipMemsetAsync(d_counts.p, 0, d_counts.bytes(), s));
+    const unsigned blocks = div_up(nLinks, (size_t)256 * RANSAC_LINKS);
+    ransac_count_kernel<<<blocks, 256, 0, s>>>(ctx->pos.p, ctx->pos2.p, ctx->ref_rowptr.p, ctx->ref_link.p, ctx->new_of_old.p,
+                                              lpb, lpe, d_cand.p, nCand, ransac_max_distance2(inlier_distance), d_counts.p);
+    FROG_HIP_CHECK(hipGetLastError());
+    FROG_HIP_CHECK(hipMemcpyAsync(counts, d_counts.p, d_counts.bytes(), hipMemcpyDeviceToHost, s));
+    FROG_HIP_CHECK(hipStreamSynchronize(s));
+    return FROG_OK;
+}
+
+} // namespace
+
+int frog_test_ransac_candidates(const frog_model *m, uint32_t image, const frog_ransac_options *o, double *cand12n,
+                                unsigned char *usable, size_t cap, size_t *n)
+{
+    if (!m || !o || !n) return fail(FROG_E_INVALID, "null argument");
+    std::vector<double> cand;
+    std::vector<uint8_t> ok;
+    const int rc = ransac_candidates(m, image, o, cand, ok);
+    if (rc) return rc;
+    *n = ok.size();
+    if (ok.size() > cap) return fail(FROG_E_INVALID, "more candidates than the caller has room for");
+    if (cand12n && !cand.empty()) std::memcpy(cand12n, cand.data(), cand.size() * sizeof(double));
+    if (usable && !ok.empty()) std::memcpy(usable, ok.data(), ok.size());
+    return FROG_OK;
+}
+
+int frog_test_ransac_census(frog_ctx *ctx, const frog_model *m, uint32_t image, const double *cand12n, size_t n,
+                            float inlier_distance, uint32_t *counts)
+{
+    CTX_GUARD(ctx);
+    if (!m || (n && (!cand12n || !counts))) return fail(FROG_E_INVALID, "null argument");
+    if (n > UINT32_MAX) return fail(FROG_E_INVALID, "too many candidates");
+    const int rc = ransac_check(ctx, m, image);
+    if (rc) return rc;
+    static_assert(sizeof(unsigned int) == sizeof(uint32_t), "counts are 32 bits wide");
+    return ransac_census(ctx, m, image, cand12n, (uint32_t)n, inlier_distance, reinterpret_cast<unsigned int *>(counts));
+}
+
+int frog_ransac(frog_ctx *ctx, const frog_model *m, uint32_t image, const frog_ransac_options *o, int64_t *n_inliers)
+{
+    CTX_GUARD(ctx);
+    if (!m || !o) return fail(FROG_E_INVALID, "null argument");
+    int rc = ransac_check(ctx, m, image);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    const uint32_t pb = ctx->poff[image], nPoints = ctx->poff[image + 1] - pb;
+    const float maxDistance2 = ransac_max_distance2(o->inlier_distance);
+    std::vector<double> cand;
+    std::vector<uint8_t> usable;
+    rc = ransac_candidates(m, image, o, cand, usable);
+    if (rc) return rc;
+    const int perBatch = o->iterations / o->batches;
+    std::vector<unsigned int> counts(usable.size(), 0u);
+    rc = ransac_census(ctx, m, image, cand.data(), (uint32_t)usable.size(), o->inlier_distance, counts.data());
+    if (rc) return rc;
     // best of each batch (first strictly larger count, :790-795), then best batch (:651-664; upstream takes the
     // batches in the order their threads finished -- here in batch order, so ties resolve the same way every run)
     long long maxNumberOfInliers = 0;
@@ -1669,7 +1736,7 @@ int frog_ransac(frog_ctx *ctx, const frog_model *m, uint32_t image, const frog_r
     }
     // refit on every half-link the best candidate brings within the distance (:666-700)
     std::vector<float> xyz2(3 * ctx->P);
-    int rc = download_points(ctx, ctx->pos2.p, xyz2.data());
+    rc = download_points(ctx, ctx->pos2.p, xyz2.data());
     if (rc) return rc;
     std::vector<const float *> srcs, tgts;
     for (uint32_t pt = 0; pt < nPoints; pt++) {

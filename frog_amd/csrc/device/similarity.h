@@ -52,12 +52,31 @@ inline void jacobi4(double a[4][4], double v[4][4])
     }
 }
 
+// The rotation counts as determined when the two largest eigenvalues l1 >= l2 of N are apart by
+// more than this fraction of |l1|.  In exact arithmetic collinear points (and coincident ones)
+// give l1 == l2; in f64 the Jacobi iteration leaves the two a few ulps apart, so an exact
+// comparison (upstream's, vtkLandmarkTransform) lets most such inputs through with whatever
+// rotation about the line rounding produced.  Measured through tests/similarity_driver.cpp
+// (tests/test_similarity.py, `python tests/test_similarity.py 100000`), f32 coordinates in
+// +-100, with and without an offset of 5000 on half of them, 100 000 four-point draws a kind:
+//   exactly degenerate draws (two distinct correspondences each twice; one three times plus
+//   another; four collinear points): largest (l1 - l2) / |l1| = 1.7e-15;
+//   generic draws:                  smallest (l1 - l2) / |l1| = 1.0e-3.
+// 2^-30 = 9.3e-10 is 2^19 above the first and 2^20 below the second; the rotation of a fit at the
+// threshold is good to 2^-52 / 2^-30 = 2^-22, a float's precision.
+// Deviation from upstream: VTK compares exactly and has a branch for collinear points behind that
+// test; with f64 Jacobi output it is as good as unreachable there too, and it is not restated here.
+constexpr double SIMILARITY_MIN_RELATIVE_GAP = 0x1p-30;
+
 // Fits target ~ s R source + t.  `point(i, a, b)` yields the i-th correspondence.
-// Returns false (and the identity) when the rotation is not determined (fewer than 3 points,
-// collinear points: the two largest eigenvalues coincide).  out: row-major 4x4.
-template <class Points> bool similarity_fit(size_t n, Points point, double out[16])
+// Returns false (and the identity) when the rotation is not determined: two points, collinear or
+// coincident sources or targets (the two largest eigenvalues within SIMILARITY_MIN_RELATIVE_GAP
+// of each other), non-finite input.  No points give the identity, one point a pure translation,
+// both true.  out: row-major 4x4.  top2, if given, receives l1 and l2 whenever N was formed.
+template <class Points> bool similarity_fit(size_t n, Points point, double out[16], double *top2 = nullptr)
 {
     for (int k = 0; k < 16; k++) out[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    if (top2) top2[0] = top2[1] = 0.0;
     if (n == 0) return true;                                     // vtkLandmarkTransform: identity for no points
     double ca[3] = { 0, 0, 0 }, cb[3] = { 0, 0, 0 }, a[3], b[3];
     for (size_t i = 0; i < n; i++) {
@@ -94,7 +113,9 @@ template <class Points> bool similarity_fit(size_t n, Points point, double out[1
     int best = 0, second = -1;
     for (int k = 1; k < 4; k++) if (N[k][k] > N[best][best]) best = k;
     for (int k = 0; k < 4; k++) if (k != best && (second < 0 || N[k][k] > N[second][second])) second = k;
-    if (n == 2 || N[best][best] == N[second][second]) return false;
+    const double l1 = N[best][best], l2 = N[second][second];
+    if (top2) { top2[0] = l1; top2[1] = l2; }
+    if (n == 2 || !(l1 - l2 > SIMILARITY_MIN_RELATIVE_GAP * std::fabs(l1))) return false;   // also NaN and 0 - 0
     const double w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];
     const double ww = w * w, wx = w * x, wy = w * y, wz = w * z, xx = x * x, yy = y * y, zz = z * z,
                  xy = x * y, xz = x * z, yz = y * z;

@@ -106,6 +106,16 @@ class ImageGroup:
         check(self._lib.frog_ransac(self._ctx, C.byref(self.pairs.model), image, C.byref(o), C.byref(n)), "frog_ransac")
         return n.value
 
+    def ransac_census(self, image, candidates, inlier_distance=50.0):
+        """The census of every candidate (n x 12 doubles, rows 0..2 of a matrix) over the half-links of `image`, by
+        frog_ransac's own launch -- frog_test_ransac_census."""
+        cand = np.ascontiguousarray(candidates, np.float64).reshape(-1, 12)
+        counts = np.zeros(len(cand), np.uint32)
+        check(self._lib.frog_test_ransac_census(self._ctx, C.byref(self.pairs.model), image, cand.ctypes.data_as(_abi.c_double_p),
+                                                len(cand), inlier_distance, counts.ctypes.data_as(_abi.c_u32_p)),
+              "frog_test_ransac_census")
+        return counts
+
     def setupDeformableTransforms(self, level):
         info = _abi.FrogGridInfo()
         check(self._lib.frog_deformable_setup(self._ctx, level, C.byref(info)), "frog_deformable_setup")
@@ -282,6 +292,17 @@ class ImageGroup:
         check(self._lib.frog_get_gradient(self._ctx, image, out.ctypes.data_as(_abi.c_float_p), 4 * n_cp),
               "frog_get_gradient")
         return out
+
+
+def ransac_candidates(pairs, image, iterations=5000, batches=8, inlier_distance=50.0, max_scale=10.0):
+    """(n x 12 candidate matrices, n usable flags) frog_ransac draws for these options -- frog_test_ransac_candidates."""
+    lib = _abi.hip_lib()
+    o = _abi.FrogRansacOptions(iterations, batches, inlier_distance, max_scale)
+    cap = max(iterations, 0)
+    cand, usable, n = np.zeros((cap, 12), np.float64), np.zeros(cap, np.uint8), C.c_size_t()
+    check(lib.frog_test_ransac_candidates(C.byref(pairs.model), image, C.byref(o), cand.ctypes.data_as(_abi.c_double_p),
+                                          usable.ctypes.data_as(C.POINTER(C.c_ubyte)), cap, C.byref(n)), "frog_test_ransac_candidates")
+    return cand[:n.value], usable[:n.value].astype(bool)
 
 
 def device_inlier_probability(em, d2, device=0):

@@ -91,7 +91,10 @@ int frog_linear_step(frog_ctx *ctx, double *E);
  * random (point, link) correspondences between the image's xyz and the partners' xyz, a
  * least-squares similarity transform through them (vtkLandmarkTransform, similarity mode), its
  * inlier count = half-links of the image with |T(xyz) - partner xyz2|^2 < inlier_distance^2.
- * Candidates whose |determinant| is outside [1/max_scale, max_scale] are skipped.  The best
+ * Candidates whose |determinant| is outside [1/max_scale, max_scale] are skipped, and so are
+ * candidates whose rotation is not determined: draws that are collinear or repeat a correspondence
+ * (the fit's two largest eigenvalues within 2^-30 relative, frog_amd/csrc/device/similarity.h;
+ * upstream compares them exactly, which f64 rounding defeats).  The best
  * candidate is refitted on all its inlier half-links and becomes the image's matrix
  * (frog_get_linear); *n_inliers = the best candidate's count (before the refit, as upstream
  * reports it).  All candidates are counted in one launch.  Upstream's `batches` is
@@ -305,6 +308,18 @@ int frog_test_cull_ranges(frog_ctx *ctx, uint64_t *ranges, uint64_t *with_electi
 /* test hook: steps (64 listed records, the lanes of one sweep step) of the current culling list, and how many of them hold
  * a point twice: a range counted by frog_test_cull_ranges' second output elects in exactly those steps */
 int frog_test_cull_steps(frog_ctx *ctx, uint64_t *listed_steps, uint64_t *steps_with_election);
+
+/* Test hooks: the first two pieces of frog_ransac by themselves (the third is the selection and the refit).
+ * frog_test_ransac_candidates (host only, no context): the candidates frog_ransac draws for (model, image, options), in batch
+ * order: rows 0..2 of each matrix (12 doubles, the identity where the fit was refused) into cand12n, and into usable whether
+ * the candidate may win (rotation determined, |determinant| inside the scale bounds).  *n = their number,
+ * (iterations / batches) * batches; FROG_E_INVALID when that exceeds cap (*n is set all the same).
+ * frog_test_ransac_census: counts[c] = the census of the caller's candidate c over the half-links of `image`, by the launch
+ * frog_ransac itself makes.  tests/test_gpu_ransac.py compares every count with tests/ransac_restate.py. */
+int frog_test_ransac_candidates(const frog_model *model, uint32_t image, const frog_ransac_options *options, double *cand12n,
+                                unsigned char *usable, size_t cap, size_t *n);
+int frog_test_ransac_census(frog_ctx *ctx, const frog_model *model, uint32_t image, const double *cand12n, size_t n,
+                            float inlier_distance, uint32_t *counts);
 
 /* Test hook: Stats::estimateDistribution (stats.cxx:14-70) again, on the samples the last refresh retained and from
  * the CURRENT (c1, c2, ratio) of every owned image (set them with frog_set_em first), with the term-by-term form of

@@ -95,8 +95,15 @@ struct Correspondences {
     void add(const float *s, const float *t) { source.push_back(s); target.push_back(t); }
 };
 
-// vtkLandmarkTransform::InternalUpdate, similarity mode.  Returns false where VTK takes its
-// collinear-points branch (not restated: such a candidate is skipped on both sides).
+// vtkLandmarkTransform::InternalUpdate, similarity mode.  Returns false where the rotation is not
+// determined (such a candidate is skipped on both sides).  Second documented deviation: VTK tests
+// `ew[0] == ew[1]` and has a branch for collinear points behind it; two f64 Jacobi outputs of a
+// collinear draw are a few ulps apart (1.7e-15 relative at most, where a generic draw is never
+// below 1e-3), so the exact test lets most of them through with an arbitrary rotation about the
+// line.  The rule here is the product's (frog_amd/csrc/device/similarity.h, where the measurement
+// is stated): undetermined unless ew[0] - ew[1] > 2^-30 |ew[0]|, which also refuses NaN and 0 - 0.
+constexpr double kMinRelativeGap = 0x1p-30;
+
 bool landmark_similarity(const Correspondences &c, double matrix[4][4])
 {
     const size_t N = c.source.size();
@@ -128,7 +135,7 @@ bool landmark_similarity(const Correspondences &c, double matrix[4][4])
     Nm[1][3] = Nm[3][1] = M[2][0] + M[0][2];
     Nm[2][3] = Nm[3][2] = M[1][2] + M[2][1];
     jacobi_n4(Nm, ew, ev);
-    if (ew[0] == ew[1] || N == 2) return false;
+    if (!(ew[0] - ew[1] > kMinRelativeGap * std::fabs(ew[0])) || N == 2) return false;
     const double w = ev[0][0], x = ev[1][0], y = ev[2][0], z = ev[3][0];
     const double ww = w * w, wx = w * x, wy = w * y, wz = w * z, xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z;
     matrix[0][0] = ww + xx - yy - zz; matrix[1][0] = 2.0 * (wz + xy); matrix[2][0] = 2.0 * (-wy + xz);

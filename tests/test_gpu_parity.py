@@ -519,6 +519,19 @@ def test_ransac_stage_matches_oracle(small_pairs):
     start(g3, ref3)
     assert g3.RANSAC(nf, iterations=3, batches=4, inlier_distance=80.0) == ref3.ransac(nf, iterations=3, batches=4, inlier_distance=80.0) == 0
     assert np.allclose(g3.matrix(nf), ref3.matrix(nf), rtol=1e-9, atol=1e-9)
+    # a sparsely linked image (5 linked points): a fifth of the draws are lines, which both sides refuse
+    from ransac_restate import sparse_group
+    sparse, _ = sparse_group()
+    g4 = ImageGroup(sparse, n_fixed_images=1)
+    ref4 = OracleGroup(sparse.model, _abi.FrogOptions.default(n_fixed_images=1))
+    ref4.setup_stats()
+    start(g4, ref4)
+    a = g4.RANSAC(1, iterations=400, batches=4, inlier_distance=2.0, max_scale=10.0)
+    assert a == ref4.ransac(1, iterations=400, batches=4, inlier_distance=2.0, max_scale=10.0) and a >= 5, "best census of the sparse image"
+    assert np.allclose(g4.matrix(1), ref4.matrix(1), rtol=1e-9, atol=1e-9), "refitted matrix of the sparse image"
+    m = g4.matrix(1)[:3, :3]
+    s = np.cbrt(np.linalg.det(m))
+    assert np.allclose(m @ m.T, s * s * np.eye(3), atol=1e-9)
     # degenerate requests are refused before any launch
     with pytest.raises(Exception):
         g2 = ImageGroup(small_pairs, n_fixed_images=nf)

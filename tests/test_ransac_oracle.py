@@ -3,7 +3,9 @@ known answer.  VTK's vtkLandmarkTransform is absent (parity unpinned): what can 
 similarity fit recovers a planted transform and that the census/selection rules hold."""
 import numpy as np
 
+import ransac_restate as rr
 from frog_amd import _abi
+from frog_amd.image_group import ransac_candidates
 from frog_amd.pairs import Pairs
 from oracle.oracle_api import OracleGroup
 
@@ -68,3 +70,24 @@ def test_scale_filter_and_batch_split():
     ref2 = prepared(pairs)
     assert ref2.ransac(1, iterations=3, batches=4, inlier_distance=1e-3) == 0
     assert np.array_equal(ref2.matrix(1), np.eye(4)) and not np.array_equal(before, np.eye(4))
+
+
+def test_sparsely_linked_image_skips_the_same_candidates_as_the_product():
+    """5 linked points (ransac_restate.sparse_group): about a fifth of the draws repeat correspondences until two distinct
+    ones or fewer are left, a line.  Both sides refuse those (relative eigenvalue gap, similarity.h), so the oracle's best
+    census is the selection rule's over the PRODUCT's candidates and flags with the restated counts, and its matrix is a
+    similarity close to the planted one.  With the exact comparison of before, each side kept most of such draws with a
+    rotation about the line of its own rounding."""
+    pairs, planted = rr.sparse_group()
+    ref = prepared(pairs)
+    cand, usable = ransac_candidates(pairs, 1, iterations=400, batches=4, inlier_distance=2.0, max_scale=10.0)
+    refused = (cand == np.eye(4)[:3].reshape(12)).all(axis=1)
+    assert len(cand) == 400 and refused.sum() >= 50 and not usable[refused].any()
+    owner, partner = rr.half_links(pairs, 1)
+    counts = rr.census(cand, ref.xyz(), ref.xyz2(), owner, partner, 2.0)
+    best, winner = rr.select(counts, usable, 4)
+    assert ref.ransac(1, iterations=400, batches=4, inlier_distance=2.0) == best == 6
+    m = ref.matrix(1)
+    s2 = np.trace(m[:3, :3] @ m[:3, :3].T) / 3
+    assert np.allclose(m[:3, :3] @ m[:3, :3].T, s2 * np.eye(3), rtol=0, atol=1e-12 * s2) and np.linalg.det(m[:3, :3]) > 0
+    assert np.abs(m[:3, :3] - planted[:3, :3]).max() < 0.05 and np.abs(m[:3, 3] - planted[:3, 3]).max() < 2.0
