@@ -432,6 +432,7 @@ HIP_SYMBOLS = {
     "frog_test_stray_points": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "frog_test_cull_ranges": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "frog_test_cull_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "frog_test_cull_readback": (C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_u32_p, c_float_p, c_u32_p]),
     "frog_test_em_refit": (C.c_int, [C.c_void_p, C.c_int]),
     "frog_test_ransac_candidates": (C.c_int, [C.POINTER(FrogModel), C.c_uint32, C.POINTER(FrogRansacOptions), c_double_p,
                                               C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -19,6 +19,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <limits>
 #include <new>
@@ -2833,6 +2834,29 @@ int frog_test_cull_steps(frog_ctx *ctx, uint64_t *listed_steps, uint64_t *steps_
         for (uint32_t v : h) *listed_steps += ((v & ~CULL_DUP_BIT) + 63u) / 64u;
         for (uint32_t v : bits) *steps_with_election += (uint64_t)__builtin_popcount(v);
     }
+    return FROG_OK;
+}
+
+int frog_test_cull_readback(frog_ctx *ctx, float *cut_now, float *cut_list, float *allow, uint32_t *state, float *disp_max, uint32_t *disp_n)
+{
+    CTX_GUARD(ctx);
+    if (!ctx->cut_now.p || !ctx->cut_list.p || !ctx->disp_part.p || !ctx->cull_state.p || !ctx->disp_allow.p)
+        return fail(FROG_E_STATE, "the context has no culling list (FROG_CULL=0, a threshold below 1e-3, or its buffers did not fit)");
+    hipStream_t s = ctx->stream;
+    const uint32_t n = (uint32_t)std::min<size_t>(ctx->disp_n, ctx->disp_part.n);
+    std::vector<uint32_t> part(disp_max ? n : 0);
+    if (cut_now) FROG_HIP_CHECK(hipMemcpyAsync(cut_now, ctx->cut_now.p, (size_t)ctx->nI * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (cut_list) FROG_HIP_CHECK(hipMemcpyAsync(cut_list, ctx->cut_list.p, (size_t)ctx->nI * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (allow) FROG_HIP_CHECK(hipMemcpyAsync(allow, ctx->disp_allow.p, sizeof(float), hipMemcpyDeviceToHost, s));
+    if (state) FROG_HIP_CHECK(hipMemcpyAsync(state, ctx->cull_state.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (!part.empty()) FROG_HIP_CHECK(hipMemcpyAsync(part.data(), ctx->disp_part.p, part.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    FROG_HIP_CHECK(hipStreamSynchronize(s));
+    if (disp_max) {
+        uint32_t m = 0;                         // f32 bits, as cull_validate_kernel takes the maximum (a NaN is above every number)
+        for (uint32_t v : part) m = std::max(m, v);
+        std::memcpy(disp_max, &m, sizeof m);
+    }
+    if (disp_n) *disp_n = n;
     return FROG_OK;
 }
 

@@ -26,9 +26,11 @@
 // The listed records keep their relative order and the skipped ones would have added nothing: the f32 per-point sums --
 // and with them lattices, coordinates, the census -- are bit-identical to the full sweep's.  The energy's two f64 sums are
 // accumulated per lane and then over the wavefront; compaction moves records to other lanes, so their association
-// changes: equal up to f64 re-association of f32 terms (identical bits in every run compared so far:
-// tests/test_gpu_round2.py compares whole runs with FROG_CULL=0 and 1, and with a zero skin that invalidates the list at
-// every step).  Nothing is approximated and no decision is cached: a listed link is evaluated from scratch each iteration.
+// changes: equal up to f64 re-association of f32 terms (identical bits under the default skin and a zero skin, whole runs in
+// tests/test_gpu_round2.py; one ulp of f64 seen under skins of a millimetre at alpha 0.3, where the energies are compared as
+// the f32 the reference records: tests/test_gpu_cull_certificate.py, which also takes the three parts apart -- what a cutoff
+// certifies, which links a list holds at the floats around the rule's edge, the check at the floats around the allowance).
+// Nothing is approximated and no decision is cached: a listed link is evaluated from scratch each iteration.
 #pragma once
 
 #include "ctx.h"
@@ -213,7 +215,9 @@ __global__ __launch_bounds__(256) void cull_build_kernel(const SweepArgs a, cons
             const float dx = pb[u].x - pa[u].x, dy = pb[u].y - pa[u].y, dz = pb[u].z - pa[u].z;
             const float d2 = dx * dx + dy * dy + dz * dz;
             const float cut = have[u] ? fminf(cutA, cut_list[imgB[u]]) : 0.f;
-            const bool keep = have[u] && !(d2 >= cut * cut);  // as the sweep's own list-writing form (k_links.hip.h BUILD)
+            // as the sweep's own list-writing form (k_links.hip.h BUILD); an infinite distance is listed like a NaN one: the
+            // weight there is inf * 0 = NaN in the general form, as in the reference, and the certificate speaks of finite d only
+            const bool keep = have[u] && !(d2 >= cut * cut && d2 < __builtin_inff());
             const unsigned long long m = __ballot(keep);
             const uint32_t to = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
             bool hit = false;

@@ -507,7 +507,9 @@ __global__ __launch_bounds__(FUSED ? 512 : 256, 1) void sweep_kernel(const Sweep
             // cull_build_kernel's criterion and compaction, on the distance this step has just formed (all 64 lanes are here:
             // `valid` = the lane holds a record of the range)
             const float cut = fminf(cutA, cut_s[img_of(rq)]);
-            const bool keep = valid && !(d2 >= cut * cut);  // a NaN distance is listed (the linear sweep's sums must see it, as the full sweep's do)
+            // a NaN distance is listed (the linear sweep's sums must see it, as the full sweep's do), and so is an infinite one:
+            // x1 = kq1 (inf * 0) is NaN there, not +0
+            const bool keep = valid && !(d2 >= cut * cut && d2 < __builtin_inff());
             const unsigned long long m = __ballot(keep);
             const uint32_t to = built + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
             bool hit = false;

@@ -278,6 +278,28 @@ class ImageGroup:
         check(self._lib.frog_test_cull_steps(self._ctx, C.byref(a), C.byref(b)), "frog_test_cull_steps")
         return a.value, b.value
 
+    def cull_readback(self):
+        """The culling list's certificate as it stands on the device -- frog_test_cull_readback: a dict of cut_now and cut_list
+        (f32 per image), allow, state (the flag a sweep reads), disp_max (the largest measured displacement, f32) and disp_n."""
+        n = self.n_images
+        now, lst = np.empty(n, np.float32), np.empty(n, np.float32)
+        allow, dmax = np.empty(1, np.float32), np.empty(1, np.float32)
+        state, dn = np.empty(1, np.uint32), np.empty(1, np.uint32)
+        check(self._lib.frog_test_cull_readback(self._ctx, now.ctypes.data_as(_abi.c_float_p), lst.ctypes.data_as(_abi.c_float_p),
+                                                allow.ctypes.data_as(_abi.c_float_p), state.ctypes.data_as(_abi.c_u32_p),
+                                                dmax.ctypes.data_as(_abi.c_float_p), dn.ctypes.data_as(_abi.c_u32_p)),
+              "frog_test_cull_readback")
+        return {"cut_now": now, "cut_list": lst, "allow": allow[0], "state": int(state[0]), "disp_max": dmax[0], "disp_n": int(dn[0])}
+
+    def set_em_rows(self, table):
+        """Every image's (c1, c2, ratio) at once (frog_set_em_rows), then published as a statistics refresh publishes them
+        (frog_stats_publish: weight constants and certified cutoffs)."""
+        t = np.zeros((self.n_images, 4), np.float32)
+        t[:, :3] = np.asarray(table, np.float32).reshape(self.n_images, 3)
+        check(self._lib.frog_set_em_rows(self._ctx, t.ctypes.data_as(_abi.c_float_p), 0, self.n_images), "frog_set_em_rows")
+        check(self._lib.frog_stats_publish(self._ctx), "frog_stats_publish")
+        self.synchronize()              # the copy reads `t`
+
     def stray_points(self):
         """Points the scatter found outside their brick since creation (frog_test_stray_points): 0 unless the sort is broken."""
         n = C.c_uint64()

@@ -308,6 +308,13 @@ int frog_test_cull_ranges(frog_ctx *ctx, uint64_t *ranges, uint64_t *with_electi
 /* test hook: steps (64 listed records, the lanes of one sweep step) of the current culling list, and how many of them hold
  * a point twice: a range counted by frog_test_cull_ranges' second output elects in exactly those steps */
 int frog_test_cull_steps(frog_ctx *ctx, uint64_t *listed_steps, uint64_t *steps_with_election);
+/* test hook: the culling list's certificate as it stands on the device (k_cull.hip.h), after the stream has drained: the
+ * per-image cutoffs of the current mixtures (cut_now[n_images]) and of the list (cut_list[n_images]), the displacement the
+ * list allows, the flag a sweep reads (1: walk every record), the largest of the per-block displacement maxima the last
+ * producer wrote (the f32 whose bits are that maximum; a NaN is above every number) and how many there are.  Any pointer
+ * may be null; launches nothing.  FROG_E_STATE when the context has no list. */
+int frog_test_cull_readback(frog_ctx *ctx, float *cut_now, float *cut_list, float *allow, uint32_t *state, float *disp_max,
+                            uint32_t *disp_n);
 
 /* Test hooks: the first two pieces of frog_ransac by themselves (the third is the selection and the refit).
  * frog_test_ransac_candidates (host only, no context): the candidates frog_ransac draws for (model, image, options), in batch

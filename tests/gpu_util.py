@@ -33,6 +33,21 @@ def relerr(a, b):
     return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30))
 
 
+def _run_schedule(pairs, monkeypatch, cull, skin=None, **opt):
+    monkeypatch.setenv("FROG_CULL", "1" if cull else "0")
+    if skin:
+        monkeypatch.setenv("FROG_CULL_SKIN", skin)
+    else:
+        monkeypatch.delenv("FROG_CULL_SKIN", raising=False)
+    g = ImageGroup(pairs, **opt)
+    g.linearIterations, g.deformableLevels, g.deformableIterations = 20, 3, 25
+    E = g.run()
+    lattices = [[g.grid(i, k)[1].copy() for k in range(g.num_grids())] for i in range(pairs.n_images)]
+    sums = g.point_sums().copy()
+    counts = [(c.inliers, c.outliers) for c in g.countInliers()]
+    return g, E, lattices, sums, counts, g.points()[1].copy()
+
+
 class Side:
     """The HIP path (ImageGroup) or the oracle (OracleGroup) as a side of frog_amd.schedule: the six verbs, and every other
     name the two groups share, are the group's own; the read-back accessors whose names or signatures differ are here."""

@@ -24,6 +24,11 @@ def test_device_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), n
     assert sorted(_abi.HIP_SYMBOLS) == names        # the ctypes table is complete, nothing undeclared
+    # the read-back of the culling list's certificate: a context, three f32 outputs, the flag, the largest displacement, its count
+    assert "frog_test_cull_readback" in names
+    restype, argtypes = _abi.HIP_SYMBOLS["frog_test_cull_readback"]
+    assert restype is C.c_int and argtypes == [C.c_void_p, _abi.c_float_p, _abi.c_float_p, _abi.c_float_p, _abi.c_u32_p,
+                                               _abi.c_float_p, _abi.c_u32_p]
 
 
 def test_host_library_exports_every_declared_symbol():

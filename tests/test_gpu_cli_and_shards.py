@@ -241,6 +241,20 @@ def test_ragged_ranks_with_a_zero_skin_list(tmp_path):
     assert relerr(three[0]["xyz2"], one["xyz2"]) < 1e-6
 
 
+def test_ragged_ranks_with_a_thin_skin_list(tmp_path):
+    """The same three ranks with a skin of one millimetre (FROG_CULL_SKIN=1.0,1.0): the list survives some steps and goes stale
+    at others, and which is decided from the displacement of every rank's rows against the snapshot -- the own rows' by the
+    transform, the others' while they are unpacked from the gathered slab (k_comm.hip.h unpack_slab_kernel with `snap`).  A
+    rank that missed another rank's motion would keep a list the one-rank run has given up."""
+    thin = {"FROG_CULL_SKIN": "1.0,1.0", "FROG_CULL_SKIN_LINEAR": "1.0,1.0"}
+    one = _launch(tmp_path, 1, "one7t", images=7)[0]
+    three = _launch(tmp_path, 3, "three7t", images=7, extra_env=thin)
+    assert three[0]["E"] == three[1]["E"] == three[2]["E"] and three[0]["grids"] == one["grids"]
+    assert np.max(np.abs(np.array(three[0]["E"]) - np.array(one["E"])) / np.array(one["E"])) < 1e-6
+    assert np.array_equal(np.array(three[0]["xyz2"]), np.array(three[2]["xyz2"]))
+    assert relerr(three[0]["xyz2"], one["xyz2"]) < 1e-6
+
+
 def test_cli_validation_landmarks(tmp_path):
     # -l <dir>: one file per image (sorted names), "name,x,y,z" lines with x and y inverted (-il 1 is
     # the default); landmarks become link-less points of their image (imageGroup.cxx:1161-1227), the

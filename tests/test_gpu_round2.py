@@ -12,7 +12,7 @@ from frog_amd import _abi, schedule
 from frog_amd.image_group import ImageGroup, device_inlier_probability, device_inlier_weight_pair
 from frog_amd.pairs import Pairs
 from oracle.oracle_api import OracleGroup, Stats, ref_lib
-from gpu_util import note, relerr
+from gpu_util import _run_schedule, note, relerr
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
@@ -288,21 +288,6 @@ def test_parity_sweep(case):
 
 
 # ---- certified outlier culling ---------------------------------------------------------------------------------
-
-def _run_schedule(pairs, monkeypatch, cull, skin=None, **opt):
-    monkeypatch.setenv("FROG_CULL", "1" if cull else "0")
-    if skin:
-        monkeypatch.setenv("FROG_CULL_SKIN", skin)
-    else:
-        monkeypatch.delenv("FROG_CULL_SKIN", raising=False)
-    g = ImageGroup(pairs, **opt)
-    g.linearIterations, g.deformableLevels, g.deformableIterations = 20, 3, 25
-    E = g.run()
-    lattices = [[g.grid(i, k)[1].copy() for k in range(g.num_grids())] for i in range(pairs.n_images)]
-    sums = g.point_sums().copy()
-    counts = [(c.inliers, c.outliers) for c in g.countInliers()]
-    return g, E, lattices, sums, counts, g.points()[1].copy()
-
 
 @pytest.mark.parametrize("opt", [{}, dict(inlier_threshold=0.2), dict(guarantee_diffeomorphism=0)])
 def test_culled_sweep_is_bit_identical_to_the_full_sweep(small_pairs, monkeypatch, opt):

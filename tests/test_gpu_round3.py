@@ -301,7 +301,7 @@ def _linear_run(pairs, n_it, **opt):
     return np.array(es), mats, g.points()[1].copy(), stats
 
 
-@pytest.mark.parametrize("skin", ["1.25,10", "1.0,0"])
+@pytest.mark.parametrize("skin", ["1.25,10", "1.0,0", "1.0,0.5"])     # the last: a list that goes stale every few steps, and is used in between
 def test_linear_stage_with_the_zero_weight_list_equals_the_full_sweep(monkeypatch, skin):
     """updateLinearTransforms has no threshold (imageGroup.cxx:1100-1117), but a half-link whose weight is exactly zero
     adds nothing to the 18 sums: the linear sweep walks a list that leaves out the half-links whose distance puts the
