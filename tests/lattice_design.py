@@ -30,6 +30,7 @@ RESERVED = 39.9                      # no other linked point has all three coord
 FLUSH = 2.0 ** -150                  # a term below this vanishes in any f32 accumulator
 U = 2.0 ** -24                       # unit round-off of f32
 TINY = 2.0 ** -149                   # smallest f32 denormal
+ALL_IMAGES = "all images"            # step(mean_over=...): the mean of the proposals over every image of the group
 
 
 class Lattice:
@@ -235,7 +236,7 @@ def _stencil(cell, frac, lat):
     return np.where(inside, node, -1).reshape(n, 64), w.reshape(n, 64)
 
 
-def step(lat, point_offset, xyz, sums, c_prev, alpha, touched_only=False):
+def step(lat, point_offset, xyz, sums, c_prev, alpha, touched_only=False, mean_over=ALL_IMAGES, first_image=0):
     """One deformable step of all images in f64 (imageGroup.cxx:299-432).
 
     xyz [P, 3]: the coordinates the scatter bins (Point::xyz); sums [P, 4]: per-point (sDisp, sWeight); c_prev: per image
@@ -249,11 +250,19 @@ def step(lat, point_offset, xyz, sums, c_prev, alpha, touched_only=False):
                 D = alpha (B_g + |g / gw| B_gw) / gw + 2 2^-24 |proposal|     the proposal's (first order; 0 where gw == 0),
                 D_i + mean_j D_j + 2^-24 (|proposal| + |mean|) + 2^-149       the coefficient's
       gw      [images, nodes] the weight sums;  terms [images, nodes] the n above
+
+    mean_over: the divisor of the sum of the proposals (ALL_IMAGES: the number of images, a context that owns the whole group; an
+    int: the group's image count, whatever part of the group the sum runs over), or None: no mean is removed, the form with
+    fixed images (imageGroup.cxx:398).  The coefficient is then the proposal itself -- (float)((double) v - 0.0) is v --, and
+    the terms the mean brings drop out of the bound:
+                D_i + 2^-24 |proposal| + 2^-149                                the coefficient's without a mean
+    first_image: the images below it take no part (the fixed images: every loop of the step starts behind them): they add nothing
+    to the sum, their rows of `new` are their previous coefficients, of `bound` 2^-149, of `gw` and `terms` zero.
     """
     n_img = len(point_offset) - 1
     per = []
     touched = []
-    for i in range(n_img):
+    for i in range(first_image, n_img):
         x = np.asarray(xyz[point_offset[i]:point_offset[i + 1]], np.float32)
         s = np.asarray(sums[point_offset[i]:point_offset[i + 1]], np.float32).astype(np.float64)
         live = s[:, 3] != 0                                 # imageGroup.cxx:299
@@ -272,7 +281,9 @@ def step(lat, point_offset, xyz, sums, c_prev, alpha, touched_only=False):
     nodes = np.unique(np.concatenate(touched)) if touched_only else np.arange(lat.n_cp)
     m = len(nodes)
     prop = np.empty((n_img, m, 3)); D = np.zeros((n_img, m, 3)); gw_all = np.zeros((n_img, m)); terms = np.zeros((n_img, m))
-    for i, (un, g, a, n) in enumerate(per):
+    for i in range(first_image):
+        prop[i] = np.asarray(c_prev[i], np.float32).astype(np.float64)[nodes]
+    for i, (un, g, a, n) in enumerate(per, start=first_image):
         at = np.searchsorted(nodes, un)
         G = np.zeros((m, 4)); A = np.zeros((m, 4)); N = np.zeros(m)
         G[at], A[at], N[at] = g, a, n
@@ -285,9 +296,16 @@ def step(lat, point_offset, xyz, sums, c_prev, alpha, touched_only=False):
         prop[i] = c + alpha * ratio
         D[i][move] = alpha * (B[move, :3] + np.abs(ratio[move]) * B[move, 3:4]) / gw[move, None] + 2 * U * np.abs(prop[i][move])
         gw_all[i], terms[i] = gw, N
-    mean = prop.mean(axis=0)
-    new = prop - mean
-    bound = D + D.mean(axis=0) + U * (np.abs(prop) + np.abs(mean)) + TINY
+    if mean_over is None:
+        new = prop.copy()
+        bound = D + U * np.abs(prop) + TINY
+    else:
+        divisor = n_img if mean_over is ALL_IMAGES else int(mean_over)
+        mean = prop[first_image:].sum(axis=0) / divisor         # (all images: prop.mean(axis=0), the same two operations)
+        new = prop - mean
+        bound = D + D[first_image:].sum(axis=0) / divisor + U * (np.abs(prop) + np.abs(mean)) + TINY
+    new[:first_image] = prop[:first_image]
+    bound[:first_image] = TINY
     return {"nodes": nodes, "new": new, "bound": bound, "gw": gw_all, "terms": terms}
 
 
