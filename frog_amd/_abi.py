@@ -215,6 +215,7 @@ def grid_triplet(origin, spacing, dims):
 FROG_RANK_MAX_IMAGES = 4096         # include/frog_chain.h: the capacity of frog_rank's sort kernels
 FROG_GLM_MAX_IMAGES, FROG_GLM_MAX_COLUMNS, FROG_GLM_MAX_CONTRASTS = 4096, 8, 8     # include/frog_chain.h: frog_glm's limits
 FROG_SMOOTH_MAX_RADIUS, FROG_SMOOTH_FWHM = 64, 2.3548200450309493                  # include/frog_chain.h: fwhm = FROG_SMOOTH_FWHM * sigma
+FROG_MODES_MAX_IMAGES, FROG_MODES_CHUNK = 512, 1024                                # include/frog_chain.h: frog_modes' limit and chunk
 
 
 class FrogScoreSums(C.Structure):
@@ -349,6 +350,16 @@ HIP_SYMBOLS = {
     "frog_smooth_volume": (C.c_int, [C.POINTER(FrogVolume), C.POINTER(C.c_uint8), C.c_double, C.c_int, c_float_p]),
     "frog_glm_smooth": (C.c_int, [C.c_void_p, C.c_double]),
     "frog_glm_smooth_planes": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_double, C.c_int, C.POINTER(C.c_uint32)]),
+    "frog_modes_planes": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
+    "frog_modes_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "frog_modes_add_displacement": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume)]),
+    "frog_modes_add_jacobian": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int]),
+    "frog_modes_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.POINTER(FrogVolume), C.c_int, C.c_double]),
+    "frog_modes_plane": (C.c_int, [C.c_void_p, C.c_uint32, c_float_p]),
+    "frog_modes_gram": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), c_double_p, C.POINTER(C.c_uint64)]),
+    "frog_modes_project": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, c_double_p, C.c_float, c_float_p, c_float_p]),
+    "frog_modes_eigen": (C.c_int, [C.c_uint32, c_double_p, C.c_double, c_double_p, c_double_p]),
+    "frog_modes_destroy": (None, [C.c_void_p]),
     "frog_labels_create": (C.c_int, [C.POINTER(FrogVolume), C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_labels_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogVolume)]),
     "frog_labels_finish": (C.c_int, [C.c_void_p, c_u32_p]),

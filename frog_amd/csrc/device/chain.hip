@@ -1050,6 +1050,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 #include "k_ccl.hip.h"
 #include "k_tfce.hip.h"
 #include "k_smooth.hip.h"
+#include "k_modes.hip.h"
 
 } // namespace
 
@@ -1122,6 +1123,12 @@ struct frog_glm : frog_windowed {
     frog::DevBuf<float> d_vals;                     // n_images planes of `window` values, in the order of the adds
     frog::DevBuf<double> d_design, d_table;         // d_table: the design rows of one launch's permutations, grown on demand
     SmoothPlan smooth;                              // frog_glm_smooth's; off at first
+};
+
+// n_components f32 per added image and window voxel, a voxel's components next to each other
+struct frog_modes : frog_windowed {
+    uint32_t components = 0;
+    frog::DevBuf<float> d_vals;                     // n_images planes of `window` x components values, in the order of the adds
 };
 
 // what glm_fit_kernel stores besides the extrema: nothing, the bits of a frog_clusters or the levels of a frog_tfce
@@ -2824,6 +2831,81 @@ int surface_add_typed(frog_surface *a, frog_chain *c, const frog_volume *src, do
     return FROG_OK;
 }
 
+// What frog_glm_add_jacobian and frog_modes' chain adds refuse alike, before the device is touched; a good mask is left in
+// a->h_mask.
+int chain_add_inputs(const char *where, frog_windowed *a, const frog_chain *c, const frog_volume *support, const frog_volume *mask)
+{
+    const std::string w = std::string(where) + ": ";
+    if (!a || !c) return fail(FROG_E_INVALID, std::string("bad arguments to ") + where);
+    if (a->added >= a->n_images) return fail(FROG_E_INVALID, w + "more volumes than the accumulator was created for");
+    if (c->device != a->device) return fail(FROG_E_INVALID, w + "chain and accumulator on different devices");
+    if (support && (!voxel_count(support) || !chain_samples(support))) return fail(FROG_E_INVALID, w + "bad support geometry");
+    if (mask) {
+        if (!mask->data) return fail(FROG_E_INVALID, w + "a mask without voxels");
+        if (!integer_voxel_type(mask->dtype)) return fail(FROG_E_INVALID, w + "a mask has an integer type");
+        if (!voxel_count(mask) || !chain_samples(mask)) return fail(FROG_E_INVALID, w + "bad mask geometry");
+        cover_mask(a, mask);
+    }
+    return FROG_OK;
+}
+
+// glm_jacobian_kernel over the `window` voxels of the grid from `first` on, into `plane`; the add is not counted
+int jacobian_launch(const char *where, frog_windowed *a, frog_chain *c, const frog_volume *support, const frog_volume *mask, int log_mode,
+                    size_t first, size_t window, float *plane)
+{
+    KCHECK(hipSetDevice(a->device));
+    const uint8_t *d_mask;
+    if (int rc = cover_stage_mask(where, a, mask, &d_mask)) return rc;
+    const MaskGrid mg = mask_grid(mask), sg = mask_grid(support);
+    const NodeGrid out = node_grid(a->grid.origin, a->grid.spacing, a->grid.dims);
+    const hipError_t e = chunked_launch(window, [&](unsigned blocks, size_t base) {
+        glm_jacobian_kernel<<<blocks, LAUNCH_BLOCK>>>(base, first, window, c->d_links.p, (int)c->h_links.size(), out, support != nullptr, sg,
+                                                      d_mask, mg, log_mode != 0, plane);
+    });
+    if (e != hipSuccess) return hip_fail(where, e);
+    return FROG_OK;
+}
+
+// the end of an add that launched on the null stream: wait, then count it
+int windowed_added(const char *where, frog_windowed *a)
+{
+    const hipError_t e = hipStreamSynchronize(0);
+    if (e != hipSuccess) return hip_fail(where, e);
+    a->added++;
+    return FROG_OK;
+}
+
+// ---- the principal modes of a group (k_modes.hip.h) ---------------------------------------------------------------------------
+
+constexpr size_t MODES_SCRATCH_BYTES = (size_t)256 << 20;      // what a batch of gram or project may take, beyond one plane's
+constexpr size_t MODES_BATCH_CHUNKS = (size_t)1 << 20;         // the most chunks of one launch: well inside a dispatch's 32-bit grid
+
+// what frog_modes_planes and frog_modes_create refuse alike without asking for a device
+int modes_arguments(const char *where, const frog_volume *grid, uint32_t n_images, uint32_t n_components, const void *out, size_t *total)
+{
+    if (int rc = group_arguments(where, grid, out, total)) return rc;
+    if (n_images < 2 || n_images > FROG_MODES_MAX_IMAGES)
+        return fail(FROG_E_INVALID, std::string(where) + ": 2 to " + std::to_string(FROG_MODES_MAX_IMAGES) + " images");
+    if (n_components != 1 && n_components != 3) return fail(FROG_E_INVALID, std::string(where) + ": 1 or 3 components");
+    return FROG_OK;
+}
+
+// what gram and project refuse alike; region (window-sized, may be null) goes to d_region
+int modes_ready(const char *where, const frog_modes *a)
+{
+    if (a->added != a->n_images) return fail(FROG_E_INVALID, std::string(where) + ": fewer volumes added than n_images");
+    return FROG_OK;
+}
+
+int modes_region(const char *where, const frog_modes *a, const uint8_t *region, frog::DevBuf<uint8_t> &d_region)
+{
+    if (!region) return FROG_OK;
+    KCHECK(d_region.alloc(a->window));
+    const hipError_t e = hipMemcpy(d_region.p, region, a->window, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(where, e);
+    return FROG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -3217,37 +3299,16 @@ int frog_glm_add(frog_glm *a, frog_chain *c, const frog_volume *src, const frog_
 
 int frog_glm_add_jacobian(frog_glm *a, frog_chain *c, const frog_volume *support, const frog_volume *mask, int log_mode)
 {
-    if (!a || !c) return fail(FROG_E_INVALID, "bad arguments to frog_glm_add_jacobian");
-    if (a->added >= a->n_images) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: more volumes than the accumulator was created for");
-    if (c->device != a->device) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: chain and accumulator on different devices");
-    if (support && (!voxel_count(support) || !chain_samples(support))) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: bad support geometry");
-    if (mask) {
-        if (!mask->data) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: a mask without voxels");
-        if (!integer_voxel_type(mask->dtype)) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: a mask has an integer type");
-        if (!voxel_count(mask) || !chain_samples(mask)) return fail(FROG_E_INVALID, "frog_glm_add_jacobian: bad mask geometry");
-        cover_mask(a, mask);
-    }
-    KCHECK(hipSetDevice(a->device));
-    const uint8_t *d_mask;
-    if (int rc = cover_stage_mask("frog_glm_add_jacobian", a, mask, &d_mask)) return rc;
-    const MaskGrid mg = mask_grid(mask), sg = mask_grid(support);
-    const NodeGrid out = node_grid(a->grid.origin, a->grid.spacing, a->grid.dims);
+    if (int rc = chain_add_inputs("frog_glm_add_jacobian", a, c, support, mask)) return rc;
     // with smoothing the same kernel on the larger range, into the scratch
     const SmoothPlan &s = a->smooth;
-    const size_t first = s.on ? s.first : a->first, window = s.on ? s.count : a->window;
-    float *plane = s.on ? s.work.d_raw.p : a->d_vals.p + (size_t)a->added * a->window;
-    hipError_t e = chunked_launch(window, [&](unsigned blocks, size_t base) {
-        glm_jacobian_kernel<<<blocks, LAUNCH_BLOCK>>>(base, first, window, c->d_links.p, (int)c->h_links.size(), out, support != nullptr, sg,
-                                                      d_mask, mg, log_mode != 0, plane);
-    });
     if (s.on) {
-        if (e != hipSuccess) return hip_fail("frog_glm_add_jacobian", e);
+        if (int rc = jacobian_launch("frog_glm_add_jacobian", a, c, support, mask, log_mode, s.first, s.count, s.work.d_raw.p)) return rc;
         return glm_smooth_store("frog_glm_add_jacobian", a);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(0);
-    if (e != hipSuccess) return hip_fail("frog_glm_add_jacobian", e);
-    a->added++;
-    return FROG_OK;
+    if (int rc = jacobian_launch("frog_glm_add_jacobian", a, c, support, mask, log_mode, a->first, a->window, a->d_vals.p + (size_t)a->added * a->window))
+        return rc;
+    return windowed_added("frog_glm_add_jacobian", a);
 }
 
 int frog_glm_plane(frog_glm *a, uint32_t image_index, float *values)
@@ -4095,5 +4156,224 @@ int frog_surface_add(frog_surface *a, frog_chain *c, const frog_volume *src, dou
 }
 
 void frog_surface_destroy(frog_surface *a) { group_destroy(a); }
+
+int frog_modes_planes(const frog_volume *grid, uint32_t n_images, uint32_t n_components, int device, uint32_t *planes)
+{
+    size_t total;
+    if (int rc = modes_arguments("frog_modes_planes", grid, n_images, n_components, planes, &total)) return rc;
+    return frog_rank_planes(grid, n_images * n_components, device, planes);        // four bytes per image, component and voxel
+}
+
+int frog_modes_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_planes, uint32_t n_images, uint32_t n_components,
+                      int device, frog_modes **out)
+{
+    size_t total;
+    if (int rc = modes_arguments("frog_modes_create", grid, n_images, n_components, out, &total)) return rc;
+    std::unique_ptr<frog_modes> a;
+    if (int rc = windowed_new("frog_modes_create", grid, total, first_plane, n_planes, n_images, device, a)) return rc;
+    a->components = n_components;
+    KCHECK(a->d_vals.alloc((size_t)n_images * a->window * n_components));
+    *out = a.release();
+    return FROG_OK;
+}
+
+int frog_modes_add_displacement(frog_modes *a, frog_chain *c, const frog_volume *support, const frog_volume *mask)
+{
+    if (a && a->components != 3) return fail(FROG_E_INVALID, "frog_modes_add_displacement: the accumulator holds one component");
+    if (int rc = chain_add_inputs("frog_modes_add_displacement", a, c, support, mask)) return rc;
+    KCHECK(hipSetDevice(a->device));
+    const uint8_t *d_mask;
+    if (int rc = cover_stage_mask("frog_modes_add_displacement", a, mask, &d_mask)) return rc;
+    const MaskGrid mg = mask_grid(mask), sg = mask_grid(support);
+    const NodeGrid out = node_grid(a->grid.origin, a->grid.spacing, a->grid.dims);
+    float *plane = a->d_vals.p + (size_t)a->added * a->window * 3;
+    const hipError_t e = chunked_launch(a->window, [&](unsigned blocks, size_t base) {
+        modes_displacement_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->first, a->window, c->d_links.p, (int)c->h_links.size(), out, support != nullptr, sg,
+                                                            d_mask, mg, plane);
+    });
+    if (e != hipSuccess) return hip_fail("frog_modes_add_displacement", e);
+    return windowed_added("frog_modes_add_displacement", a);
+}
+
+int frog_modes_add_jacobian(frog_modes *a, frog_chain *c, const frog_volume *support, const frog_volume *mask, int log_mode)
+{
+    if (a && a->components != 1) return fail(FROG_E_INVALID, "frog_modes_add_jacobian: the accumulator holds three components");
+    if (int rc = chain_add_inputs("frog_modes_add_jacobian", a, c, support, mask)) return rc;
+    if (int rc = jacobian_launch("frog_modes_add_jacobian", a, c, support, mask, log_mode, a->first, a->window, a->d_vals.p + (size_t)a->added * a->window))
+        return rc;
+    return windowed_added("frog_modes_add_jacobian", a);
+}
+
+int frog_modes_add(frog_modes *a, frog_chain *c, const frog_volume *src, const frog_volume *mask, int interpolation, double background)
+{
+    if (a && a->components != 1) return fail(FROG_E_INVALID, "frog_modes_add: the accumulator holds three components");
+    return windowed_add<GlmEntry>("frog_modes_add", a, a ? a->d_vals.p : nullptr, c, src, mask, interpolation, background);
+}
+
+int frog_modes_plane(frog_modes *a, uint32_t image_index, float *values)
+{
+    if (!a || !values) return fail(FROG_E_INVALID, "bad arguments to frog_modes_plane");
+    if (image_index >= a->added) return fail(FROG_E_INVALID, "frog_modes_plane: that image has not been added");
+    KCHECK(hipSetDevice(a->device));
+    const size_t stride = a->window * a->components;
+    KCHECK(hipMemcpy(values, a->d_vals.p + (size_t)image_index * stride, stride * sizeof(float), hipMemcpyDeviceToHost));
+    return FROG_OK;
+}
+
+int frog_modes_gram(frog_modes *a, const uint8_t *region, double *gram, uint64_t *n_support)
+{
+    if (!a || !gram || !n_support) return fail(FROG_E_INVALID, "bad arguments to frog_modes_gram");
+    if (int rc = modes_ready("frog_modes_gram", a)) return rc;
+    KCHECK(hipSetDevice(a->device));
+    const uint32_t n = a->n_images;
+    const size_t pairs = (size_t)n * (n + 1) / 2, tiles = (n + MODES_TILE - 1) / MODES_TILE;
+    const size_t stride = a->window * a->components;
+    const size_t plane_values = (size_t)a->grid.dims[0] * a->grid.dims[1] * a->components, planes = stride / plane_values;
+    const size_t chunks = (plane_values + FROG_MODES_CHUNK - 1) / FROG_MODES_CHUNK;
+    // a batch of whole planes: its means, its chunk sums and its plane sums
+    const size_t plane_bytes = (plane_values + chunks * pairs + pairs) * sizeof(double);
+    const size_t batch = std::max<size_t>(1, std::min({ planes, MODES_SCRATCH_BYTES / plane_bytes, MODES_BATCH_CHUNKS / chunks }));
+    frog::DevBuf<uint8_t> d_region;
+    frog::DevBuf<double> d_mean, d_scratch, d_sums, d_gram;
+    frog::DevBuf<unsigned long long> d_count;
+    if (int rc = modes_region("frog_modes_gram", a, region, d_region)) return rc;
+    KCHECK(d_mean.alloc(batch * plane_values));
+    KCHECK(d_scratch.alloc(batch * chunks * pairs));
+    KCHECK(d_sums.alloc(batch * pairs));
+    KCHECK(d_gram.alloc(pairs));
+    KCHECK(d_count.alloc(1));
+    KCHECK(hipMemcpy(d_gram.p, gram, pairs * sizeof(double), hipMemcpyHostToDevice));
+    KCHECK(hipMemset(d_count.p, 0, sizeof(unsigned long long)));
+    hipError_t e = hipSuccess;
+    for (size_t first = 0; first < planes && e == hipSuccess; first += batch) {
+        const size_t m = std::min(batch, planes - first), v0 = first * plane_values, count = m * plane_values;
+        e = chunked_launch(count, [&](unsigned blocks, size_t base) {
+            modes_mean_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_vals.p, stride, n, a->components, d_region.p, v0, count, d_mean.p, d_count.p);
+        });
+        if (e != hipSuccess) break;
+        modes_gram_kernel<<<dim3((unsigned)(m * chunks), (unsigned)(tiles * (tiles + 1) / 2)), LAUNCH_BLOCK>>>(
+            a->d_vals.p, stride, n, d_mean.p, v0, plane_values, (uint32_t)chunks, d_scratch.p);
+        e = hipGetLastError();
+        if (e != hipSuccess) break;
+        e = chunked_launch(m * pairs, [&](unsigned blocks, size_t base) {
+            modes_fold_chunks_kernel<<<blocks, LAUNCH_BLOCK>>>(base, m * pairs, pairs, (uint32_t)chunks, d_scratch.p, d_sums.p);
+        });
+        if (e != hipSuccess) break;
+        e = chunked_launch(pairs, [&](unsigned blocks, size_t base) {
+            modes_fold_planes_kernel<<<blocks, LAUNCH_BLOCK>>>(base, pairs, m, d_sums.p, d_gram.p);
+        });
+    }
+    unsigned long long support = 0;
+    if (e == hipSuccess) e = hipMemcpy(&support, d_count.p, sizeof support, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(gram, d_gram.p, pairs * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_modes_gram", e);
+    *n_support += support;
+    return FROG_OK;
+}
+
+int frog_modes_project(frog_modes *a, const uint8_t *region, uint32_t n_modes, const double *weights, float fill, float *mean, float *modes)
+{
+    if (!a || !weights || !modes) return fail(FROG_E_INVALID, "bad arguments to frog_modes_project");
+    if (int rc = modes_ready("frog_modes_project", a)) return rc;
+    if (!n_modes || n_modes > a->n_images) return fail(FROG_E_INVALID, "frog_modes_project: 1 to n_images modes");
+    for (size_t e = 0; e < (size_t)n_modes * a->n_images; e++)
+        if (!std::isfinite(weights[e])) return fail(FROG_E_INVALID, "frog_modes_project: a weight is not finite");
+    KCHECK(hipSetDevice(a->device));
+    const uint32_t n = a->n_images;
+    const size_t stride = a->window * a->components;
+    const size_t batch = std::min(stride, MODES_SCRATCH_BYTES / ((MODES_GROUP + 1) * sizeof(float)) / LAUNCH_BLOCK * LAUNCH_BLOCK);
+    frog::DevBuf<uint8_t> d_region;
+    frog::DevBuf<double> d_weights;
+    frog::DevBuf<float> d_mean, d_modes;
+    if (int rc = modes_region("frog_modes_project", a, region, d_region)) return rc;
+    KCHECK(d_weights.alloc((size_t)n_modes * n));
+    KCHECK(hipMemcpy(d_weights.p, weights, (size_t)n_modes * n * sizeof(double), hipMemcpyHostToDevice));
+    KCHECK(d_mean.alloc(batch));
+    KCHECK(d_modes.alloc(MODES_GROUP * batch));
+    hipError_t e = hipSuccess;
+    for (size_t v0 = 0; v0 < stride && e == hipSuccess; v0 += batch) {
+        const size_t count = std::min(batch, stride - v0);
+        for (uint32_t k0 = 0; k0 < n_modes && e == hipSuccess; k0 += MODES_GROUP) {
+            const uint32_t kn = std::min(MODES_GROUP, n_modes - k0);
+            float *d_m = mean && !k0 ? d_mean.p : nullptr;
+            e = chunked_launch(count, [&](unsigned blocks, size_t base) {
+                modes_project_kernel<<<blocks, LAUNCH_BLOCK>>>(base, a->d_vals.p, stride, n, a->components, d_region.p, v0, count, d_weights.p, k0, kn,
+                                                               fill, d_m, d_modes.p);
+            });
+            if (e == hipSuccess && d_m) e = hipMemcpy(mean + v0, d_mean.p, count * sizeof(float), hipMemcpyDeviceToHost);
+            for (uint32_t k = 0; k < kn && e == hipSuccess; k++)
+                e = hipMemcpy(modes + (size_t)(k0 + k) * stride + v0, d_modes.p + (size_t)k * count, count * sizeof(float), hipMemcpyDeviceToHost);
+        }
+    }
+    if (e != hipSuccess) return hip_fail("frog_modes_project", e);
+    return FROG_OK;
+}
+
+int frog_modes_eigen(uint32_t n, const double *gram, double divisor, double *values, double *vectors)
+{
+    if (!gram || !values || !vectors) return fail(FROG_E_INVALID, "bad arguments to frog_modes_eigen");
+    if (!n || n > FROG_MODES_MAX_IMAGES) return fail(FROG_E_INVALID, "frog_modes_eigen: 1 to " + std::to_string(FROG_MODES_MAX_IMAGES) + " images");
+    if (!(divisor > 0.0) || !std::isfinite(divisor)) return fail(FROG_E_INVALID, "frog_modes_eigen: the divisor must be above 0");
+    for (size_t e = 0; e < (size_t)n * (n + 1) / 2; e++)
+        if (!std::isfinite(gram[e])) return fail(FROG_E_INVALID, "frog_modes_eigen: a gram entry is not finite");
+    std::vector<double> G((size_t)n * n), E((size_t)n * n, 0.0);
+    double d = 0.0;
+    for (uint32_t i = 0; i < n; i++) {
+        E[(size_t)i * n + i] = 1.0;
+        for (uint32_t j = 0; j <= i; j++) {
+            const double g = gram[(size_t)i * (i + 1) / 2 + j] / divisor;
+            G[(size_t)i * n + j] = G[(size_t)j * n + i] = g;
+            d = std::max(d, std::fabs(g));
+        }
+    }
+    const double tol = std::ldexp(d, -60);
+    // (the off-diagonal norm falls quadratically: a dozen sweeps at most in practice; the bound only rules out an endless loop)
+    int sweeps = 0;
+    for (bool rotated = true; rotated;) {
+        if (++sweeps > 256) return fail(FROG_E_STATE, "frog_modes_eigen: no convergence");
+        rotated = false;
+        for (uint32_t p = 0; p + 1 < n; p++)
+            for (uint32_t q = p + 1; q < n; q++) {
+                const double apq = G[(size_t)p * n + q];
+                if (!(std::fabs(apq) > tol)) continue;
+                rotated = true;
+                const double theta = (G[(size_t)q * n + q] - G[(size_t)p * n + p]) / (2.0 * apq);
+                const double t = (theta < 0.0 ? -1.0 : 1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                G[(size_t)p * n + p] -= t * apq;
+                G[(size_t)q * n + q] += t * apq;
+                G[(size_t)p * n + q] = G[(size_t)q * n + p] = 0.0;
+                for (uint32_t k = 0; k < n; k++) {
+                    if (k != p && k != q) {
+                        const double gkp = G[(size_t)k * n + p], gkq = G[(size_t)k * n + q];
+                        G[(size_t)k * n + p] = G[(size_t)p * n + k] = c * gkp - s * gkq;
+                        G[(size_t)k * n + q] = G[(size_t)q * n + k] = s * gkp + c * gkq;
+                    }
+                    const double ekp = E[(size_t)k * n + p], ekq = E[(size_t)k * n + q];
+                    E[(size_t)k * n + p] = c * ekp - s * ekq;
+                    E[(size_t)k * n + q] = s * ekp + c * ekq;
+                }
+            }
+    }
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return G[(size_t)x * n + x] > G[(size_t)y * n + y]; });
+    for (uint32_t k = 0; k < n; k++) {
+        const uint32_t col = order[k];
+        values[k] = G[(size_t)col * n + col];
+        double norm = 0.0, largest = 0.0;
+        uint32_t at = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            const double v = E[(size_t)i * n + col];
+            norm += v * v;
+            if (std::fabs(v) > largest) { largest = std::fabs(v); at = i; }
+        }
+        const double scale = (E[(size_t)at * n + col] < 0.0 ? -1.0 : 1.0) / std::sqrt(norm);
+        for (uint32_t i = 0; i < n; i++) vectors[(size_t)k * n + i] = E[(size_t)i * n + col] * scale;
+    }
+    return FROG_OK;
+}
+
+void frog_modes_destroy(frog_modes *a) { group_destroy(a); }
 
 }

@@ -802,6 +802,274 @@ def _read_tfce(enhance, out):
 FUSED_DTYPES = ("uint8", "uint16", "int16", "int32", "uint32")
 
 
+class ModeImages(_Accumulator):
+    """frog_modes (include/frog_chain.h): `components` (3: displacements, 1: a scalar) float32 per added image and voxel of a
+    window of `grid`, then the Gram matrix of the centred images over the voxels every image covers, and the mean and the modes
+    that a set of weights gives.  `window` = (first z-plane, planes), default the whole grid."""
+
+    _NAME = "modes"
+
+    def __init__(self, grid, n_images, components=3, window=None, device=0):
+        first, planes = (0, int(grid[0][2])) if window is None else (int(window[0]), int(window[1]))
+        super().__init__(grid, first, planes, int(n_images), int(components), int(device))
+        self.n_images, self.components = int(n_images), int(components)
+        self.window = (first, planes)
+        self.shape = (planes,) + self.dims[1::-1]
+        self.value_shape = self.shape + ((3,) if self.components == 3 else ())
+
+    def _geometry(self, support):
+        if support is None:
+            return None
+        dims, origin, spacing = support
+        return C.byref(_abi.volume_view(None, tuple(float(v) for v in origin), tuple(float(v) for v in spacing), tuple(int(d) for d in dims)))
+
+    def add(self, volume, chain=None, mask=None, interpolation=1, background=0.0):
+        """One component: what GroupGLM.add stores."""
+        _, src, mv, _, _ = self._views(volume, mask)
+        _abi.check(self._lib.frog_modes_add(self._h, chain._h if chain is not None else None, src, mv, int(interpolation),
+                                            float(background)), "frog_modes_add")
+
+    def add_jacobian(self, chain, support=None, mask=None, log=True):
+        """One component: what GroupGLM.add_jacobian stores."""
+        mv = self._views(mask)[1] if mask is not None else None
+        _abi.check(self._lib.frog_modes_add_jacobian(self._h, chain._h if chain is not None else None, self._geometry(support), mv,
+                                                     int(bool(log))), "frog_modes_add_jacobian")
+
+    def add_displacement(self, chain, support=None, mask=None):
+        """Three components: the displacement of `chain` at every window voxel, what Chain.sample gives there as float32;
+        `support` and `mask` as in add_jacobian."""
+        mv = self._views(mask)[1] if mask is not None else None
+        _abi.check(self._lib.frog_modes_add_displacement(self._h, chain._h if chain is not None else None, self._geometry(support), mv),
+                   "frog_modes_add_displacement")
+
+    def plane(self, image_index):
+        """What add number image_index stored over the window: float32 shape (+ (3,)), NaN (0x7FC00000) where it takes no part."""
+        out = np.empty(self.value_shape, np.float32)
+        _abi.check(self._lib.frog_modes_plane(self._h, int(image_index), out.ctypes.data_as(_abi.c_float_p)), "frog_modes_plane")
+        return out
+
+    def _region(self, region):
+        r = None if region is None else np.ascontiguousarray(np.asarray(region) != 0, np.uint8)
+        if r is not None and r.shape != self.shape:
+            raise ValueError("region: one value per window voxel")
+        return r, None if r is None else r.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def gram(self, region=None, gram=None, n_support=0):
+        """(gram, n_support): the packed lower triangle, float64 (n (n + 1) / 2,), of the centred images' inner products over
+        the window's support, added onto `gram` (default zeros), and the support's voxels added to n_support.  Windows that
+        partition the grid give the whole grid's bits when they are taken in ascending order with gram passed on."""
+        n = self.n_images
+        g = np.zeros(n * (n + 1) // 2, np.float64) if gram is None else np.array(gram, np.float64).ravel()
+        if len(g) != n * (n + 1) // 2:
+            raise ValueError("gram: the packed lower triangle of n_images x n_images expected")
+        _r, rp = self._region(region)
+        count = C.c_uint64(int(n_support))
+        _abi.check(self._lib.frog_modes_gram(self._h, rp, g.ctypes.data_as(_abi.c_double_p), C.byref(count)), "frog_modes_gram")
+        return g, count.value
+
+    def project(self, weights, region=None, fill=0.0):
+        """(mean, modes): float32 of value shape and (n_modes,) + value shape; mode k is the sum over the images of weights[k, i]
+        times the centred image i.  `fill` outside the support."""
+        w = np.ascontiguousarray(weights, np.float64).reshape(-1, self.n_images)
+        _r, rp = self._region(region)
+        mean = np.empty(self.value_shape, np.float32)
+        modes = np.empty((len(w),) + self.value_shape, np.float32)
+        _abi.check(self._lib.frog_modes_project(self._h, rp, len(w), w.ctypes.data_as(_abi.c_double_p), float(fill),
+                                                mean.ctypes.data_as(_abi.c_float_p), modes.ctypes.data_as(_abi.c_float_p)), "frog_modes_project")
+        return mean, modes
+
+
+def modes_planes(grid, n_images, components=3, device=0):
+    """The most z-planes of `grid` a ModeImages window for n_images may hold on the device now (frog_modes_planes)."""
+    dims, origin, spacing = grid
+    g = _abi.volume_view(None, origin, spacing, tuple(int(d) for d in dims))
+    planes = C.c_uint32()
+    _abi.check(_abi.hip_lib().frog_modes_planes(C.byref(g), int(n_images), int(components), int(device), C.byref(planes)), "frog_modes_planes")
+    return planes.value
+
+
+def modes_eigen(gram, divisor=1.0):
+    """(values float64 (n,), vectors float64 (n, n)) of the symmetric matrix whose packed lower triangle is `gram`, divided by
+    `divisor` (frog_modes_eigen: cyclic Jacobi): values descend, row k of vectors is the unit eigenvector of values[k] with its
+    entry of largest magnitude positive.  Host code: no device is needed."""
+    g = np.ascontiguousarray(gram, np.float64).ravel()
+    n = int(round((np.sqrt(8 * len(g) + 1) - 1) / 2))
+    if n * (n + 1) // 2 != len(g):
+        raise ValueError("gram: a packed lower triangle expected")
+    values, vectors = np.empty(n, np.float64), np.empty((n, n), np.float64)
+    _abi.check(_abi.hip_lib().frog_modes_eigen(n, g.ctypes.data_as(_abi.c_double_p), float(divisor), values.ctypes.data_as(_abi.c_double_p),
+                                               vectors.ctypes.data_as(_abi.c_double_p)), "frog_modes_eigen")
+    return values, vectors
+
+
+def drop_linear(links):
+    """A chain's links without the linear ones: its deformable part (bin/GroupModes -nl 1)."""
+    from .chain import LINEAR
+    return [l for l in links if l.kind != LINEAR]
+
+
+def group_modes(chains=None, grid=None, value="displacement", volumes=None, masks=None, supports=None, region=None, n_modes=None,
+                fill=0.0, mode_sd=0.0, interpolation=1, max_planes=None, device=0):
+    """The principal modes of a registered group (bin/GroupModes): the statistical deformation model of Rueckert, Frangi and
+    Schnabel (2003).  value "displacement" (3 components): image i is the displacement of chains[i] on `grid` in mm;
+    "logjacobian", "jacobian" and "images" as in group_glm().  A voxel belongs to the SUPPORT where `region` (optional) is
+    non-zero and every image takes part.  n_modes: the modes kept, default min(n - 1, 8).
+    The device holds slabs of modes_planes() z-planes (at most max_planes).  With one slab the images are added once; with more
+    they are added twice, once for the Gram matrix (the slabs in ascending order, which the stated sums need) and, after the
+    eigen-solve on the host, once more for the projection.
+    Returns a dict: mean float32 value-shaped, modes float32 (n_modes,) + value shape in units per standard deviation (`fill`
+    outside the support in both), support uint8, n_support, gram (packed), eigenvalues and vectors (all n, of gram / (n - 1)),
+    rms, share, cumulative (n_modes,), scores float64 (n, n_modes) in standard deviations, distance (n,) = the norm of an image's
+    scores, distance_robust_z = robust_z(distance).  With mode_sd = s > 0 (displacement only) also mean_field and plus, minus
+    (n_modes,) + value shape, float32: mean and mean +- s * mode_k as displacement fields, 0 outside the support."""
+    kinds = ("displacement", "logjacobian", "jacobian", "images")
+    if value not in kinds:
+        raise ValueError("value: " + ", ".join(kinds))
+    images = value == "images"
+    if images:
+        vols, grid = _group(volumes, chains, masks, grid)
+        n = len(vols)
+    elif chains is None or grid is None:
+        raise ValueError("a grid and one chain per image expected")
+    else:
+        n = len(chains)
+    if n < 2:
+        raise ValueError("at least two images expected")
+    components = 3 if value == "displacement" else 1
+    if mode_sd and components != 3:
+        raise ValueError("mode_sd: displacement fields only")
+    keep = min(n - 1, 8) if n_modes is None else int(n_modes)
+    if not 1 <= keep <= n:
+        raise ValueError("n_modes: 1 to the number of images")
+    dims = tuple(int(d) for d in grid[0])
+    depth, shape = dims[2], dims[::-1]
+    value_shape = shape + ((3,) if components == 3 else ())
+    reg = None if region is None else np.asarray(region) != 0
+    planes = modes_planes(grid, n, components, device)
+    if max_planes is not None:
+        planes = max(1, min(planes, int(max_planes)))
+
+    def filled(first, m):
+        acc = ModeImages(grid, n, components, (first, m), device)
+        try:
+            for k in range(n):
+                mask = None if masks is None else masks[k]
+                support = None if supports is None else supports[k]
+                if images:
+                    acc.add(vols[k], None if chains is None else chains[k], mask, interpolation)
+                elif components == 3:
+                    acc.add_displacement(chains[k], support, mask)
+                else:
+                    acc.add_jacobian(chains[k], support, mask, value == "logjacobian")
+        except Exception:
+            acc.close()
+            raise
+        return acc
+
+    slabs = [(first, min(planes, depth - first)) for first in range(0, depth, planes)]
+    gram, n_support, kept = None, 0, None
+    for first, m in slabs:
+        acc = filled(first, m)
+        try:
+            gram, n_support = acc.gram(None if reg is None else reg[first:first + m], gram, n_support)
+        except Exception:
+            acc.close()
+            raise
+        if len(slabs) == 1:
+            kept = acc
+        else:
+            acc.close()
+    try:
+        if not n_support:
+            raise ValueError("the support is empty: no voxel is covered by every image")
+        values, vectors = modes_eigen(gram, n - 1)
+        root = float(np.sqrt(np.float64(n - 1)))
+        weights = vectors[:keep] / root
+        out = dict(mean=np.empty(value_shape, np.float32), modes=np.empty((keep,) + value_shape, np.float32), support=np.empty(shape, np.uint8))
+        for first, m in slabs:
+            acc = kept if kept is not None else filled(first, m)
+            try:
+                # a mean is never NaN inside the support: NaN as the fill marks the voxels outside it
+                mean, modes = acc.project(weights, None if reg is None else reg[first:first + m], np.nan)
+            finally:
+                if kept is None:
+                    acc.close()
+            inside = ~np.isnan(mean if components == 1 else mean[..., 0])
+            mean[~inside], modes[:, ~inside] = fill, fill
+            sl = slice(first, first + m)
+            out["mean"][sl], out["modes"][:, sl], out["support"][sl] = mean, modes, inside
+    finally:
+        if kept is not None:
+            kept.close()
+    trace = 0.0
+    for v in values:
+        trace = trace + float(v)
+    share = np.array([float(v) / trace if trace > 0 else 0.0 for v in values[:keep]], np.float64)
+    scores = root * vectors[:keep].T
+    distance = np.empty(n, np.float64)
+    for i in range(n):
+        s = 0.0
+        for k in range(keep):
+            s = s + float(scores[i, k]) * float(scores[i, k])
+        distance[i] = np.sqrt(s)
+    cumulative, c = np.empty(keep, np.float64), 0.0
+    for k in range(keep):
+        c = c + float(share[k])
+        cumulative[k] = c
+    per_value = float(n_support) * components
+    out.update(n_support=n_support, gram=gram, eigenvalues=values, vectors=vectors, share=share, cumulative=cumulative,
+               rms=np.array([np.sqrt(max(float(v), 0.0) / per_value) for v in values[:keep]], np.float64),
+               scores=scores, distance=distance, distance_robust_z=robust_z(distance))
+    if mode_sd:
+        inside = out["support"] != 0
+        step = np.float32(mode_sd) * out["modes"]
+        out["mean_field"] = np.where(inside[..., None], out["mean"], np.float32(0))
+        out["plus"] = np.where(inside[None, ..., None], out["mean"][None] + step, np.float32(0))
+        out["minus"] = np.where(inside[None, ..., None], out["mean"][None] - step, np.float32(0))
+    return out
+
+
+def write_group_modes(result, grid, out_dir, mode_sd=0.0):
+    """The files bin/GroupModes writes, from group_modes()'s dict: mean.nii.gz, mode_<k>.nii.gz, support.nii.gz, modes.csv and
+    scores.csv, and with mode_sd mean_field.nii.gz, mean.json and per mode mode_<k>_plus / _minus .nii.gz and .json."""
+    import os
+    dims, origin, spacing = grid
+    d, o, s = (C.c_uint32 * 3)(*[int(v) for v in dims]), (C.c_double * 3)(*[float(v) for v in origin]), (C.c_double * 3)(*[float(v) for v in spacing])
+
+    def field(name, a):
+        a = np.ascontiguousarray(a, np.float32)
+        path = os.path.join(str(out_dir), name)
+        rc = _abi.host_lib().frog_nifti_write(path.encode(), d, s, o, 3 if a.ndim == 4 else 1, a.ctypes.data_as(_abi.c_float_p))
+        if rc != 0:
+            raise IOError(f"cannot write {path}")
+
+    def transform(name, file):
+        with open(os.path.join(str(out_dir), name), "w") as f:
+            f.write('{"transforms": [{"type": "frogDisplacementField", "file": "%s"}]}\n' % file)
+
+    os.makedirs(str(out_dir), exist_ok=True)
+    keep = len(result["modes"])
+    field("mean.nii.gz", result["mean"])
+    for k in range(keep):
+        field(f"mode_{k}.nii.gz", result["modes"][k])
+    write_volume(os.path.join(str(out_dir), "support.nii.gz"), result["support"], origin, spacing)
+    with open(os.path.join(str(out_dir), "modes.csv"), "w") as f:
+        f.write("mode,eigenvalue,rms,share,cumulative\n")
+        for k in range(keep):
+            f.write("%d,%.17g,%.17g,%.17g,%.17g\n" % (k, result["eigenvalues"][k], result["rms"][k], result["share"][k], result["cumulative"][k]))
+    with open(os.path.join(str(out_dir), "scores.csv"), "w") as f:
+        f.write("image," + "".join(f"score_{k}," for k in range(keep)) + "distance,distance_robust_z\n")
+        for i in range(len(result["scores"])):
+            f.write("%d," % i + "".join("%.17g," % v for v in result["scores"][i]) + "%.17g,%.17g\n" % (result["distance"][i], result["distance_robust_z"][i]))
+    if mode_sd:
+        field("mean_field.nii.gz", result["mean_field"])
+        transform("mean.json", "mean_field.nii.gz")
+        for k in range(keep):
+            for side in ("plus", "minus"):
+                field(f"mode_{k}_{side}.nii.gz", result[side][k])
+                transform(f"mode_{k}_{side}.json", f"mode_{k}_{side}.nii.gz")
+
+
 def fused_dtype(values):
     """The type bin/FuseLabels gives labels.nii.gz: the first of uint8, uint16, int16, int32, uint32 that holds every label
     value; None if none does."""

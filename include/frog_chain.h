@@ -834,6 +834,91 @@ int  frog_smooth_volume(const frog_volume *volume, const uint8_t *take, double s
 int  frog_glm_smooth(frog_glm *a, double sigma_mm);
 int  frog_glm_smooth_planes(const frog_volume *grid, uint32_t n_images, double sigma_mm, int device, uint32_t *planes);
 
+/* ---- principal modes of a registered group: a statistical deformation model (an extension; Rueckert, Frangi and Schnabel, IEEE
+ * TMI 22(8), 2003: a principal component analysis of the images' deformation fields in the group's space) ----------------------
+ * How does the group vary as a whole: the mean of the images' values, a few modes (each a field of values per standard
+ * deviation), the share of the variance each explains, and per image a score on every mode.  A value is the displacement of the
+ * image's chain in mm (3 components), or one of frog_glm's three scalar kinds (1 component).
+ * The accumulator holds the z-planes [first_plane, first_plane + n_planes) of `grid`, the WINDOW, exactly as frog_glm does, and
+ * n_components (1 or 3) f32 per image and window voxel, component fastest; the bits 0x7FC00000 mean "does not take part".
+ * frog_modes_planes is frog_rank_planes' rule for n_images * n_components values per voxel.
+ *
+ * What an add keeps.  Add number i fills entry i of the window.
+ *   frog_modes_add_displacement (3 components): d is the f64 displacement frog_chain_sample(chain, grid ...) stores for that node
+ *     (the same device code), x_k = (float)d_k.  The voxel is valid exactly as in frog_glm_add_jacobian (support, then mask, at
+ *     the position the same evaluation of the chain gives); it takes part iff it is valid and all three x_k are finite, else all
+ *     three entries are 0x7FC00000.  A chain is required.
+ *   frog_modes_add_jacobian and frog_modes_add (1 component): bit for bit what frog_glm_add_jacobian and frog_glm_add store (the
+ *     same kernels).  There is no smoothing here.
+ *   frog_modes_plane: what add number image_index stored, window-sized, n_components floats per voxel.  Everything below is stated
+ *     on these planes.
+ *
+ * Every floating-point line below is one separately rounded f64 operation (no contraction), loops ascending.  n = n_images, x_i
+ * the stored f32 of image i at one voxel and component.
+ *   SUPPORT.  A window voxel is in the support iff `region` (u8, window-sized, may be NULL) is non-zero there and every image
+ *     takes part there: a principal component analysis needs complete rows.
+ *   Mean and centring, per support voxel and component:
+ *       s = +0.0;  for i:  s = s + (double)x_i;      m = s / (double)n;      c_i = (double)x_i - m
+ *     Outside the support c_i = +0.0 for every i.
+ *
+ * frog_modes_gram: gram is the packed lower triangle, entry (i, j), j <= i, at i (i + 1) / 2 + j, n (n + 1) / 2 doubles.  It is
+ *   READ AND UPDATED, and so is n_support (the number of support voxels is added to it).
+ *   The values of one z-plane in index order (x fastest, then y, component fastest of all) are cut into CHUNKS of FROG_MODES_CHUNK
+ *   consecutive values; the last chunk of a plane may be shorter.  Per pair j <= i:
+ *       chunk:   s = +0.0;  for the chunk's values ascending:  p = c_i * c_j;  s = s + p
+ *       plane:   t = +0.0;  for the plane's chunks ascending:  t = t + s_chunk
+ *       window:  for the window's planes ascending:  gram_ij = gram_ij + t_plane
+ *   So windows that partition the grid, taken in ASCENDING plane order with gram passed on from one to the next, give the bits of
+ *   one whole-grid window.  THE ORDER OF THE WINDOWS MATTERS HERE, and here only: every other result of this library is
+ *   independent of the order its windows are taken in.  No floating-point atomic is used, and no sum depends on scheduling.
+ *
+ * frog_modes_project: weights is n_modes x n_images, row k the weights w_k of mode k.  Per support voxel and component
+ *       mean = (float)m
+ *       mode_k:  s = +0.0;  for i:  p = w_ki * c_i;  s = s + p;      mode_k = (float)s
+ *   and `fill` outside the support.  mean (window-sized, n_components floats per voxel; may be NULL) and modes (n_modes such
+ *   fields, mode k first) are host buffers.  Windows are independent.
+ *
+ * frog_modes_eigen (host code, no device): the eigen-decomposition of the symmetric matrix G = gram / divisor (gram packed as
+ *   above, one division per entry) by the cyclic Jacobi method in f64.
+ *       d = the largest |G_ij|;  tol = 2^-60 * d
+ *       a SWEEP visits the pairs (p, q), p < q, p ascending and for each p q ascending.  A pair with |G_pq| <= tol is left as it
+ *       is.  Every other pair is ROTATED:
+ *           theta = (G_qq - G_pp) / (2 G_pq);  t = sgn(theta) / (|theta| + sqrt(theta^2 + 1))   (sgn(0) = +1)
+ *           c = 1 / sqrt(t^2 + 1);  s = t c
+ *           G_pp = G_pp - t G_pq;  G_qq = G_qq + t G_pq;  G_pq = G_qp = 0
+ *           for k other than p, q:  G_kp' = c G_kp - s G_kq;  G_kq' = s G_kp + c G_kq      (and their mirror images)
+ *           for k:                  E_kp' = c E_kp - s E_kq;  E_kq' = s E_kp + c E_kq      (E starts as the identity)
+ *       Sweeps are repeated until one rotates nothing.  The eigenvalues are then the diagonal, the eigenvectors the columns of E.
+ *   values[k] descend; ties keep index order (a stable sort).  vectors is n x n, row k the eigenvector of values[k]: unit length
+ *   (it is renormalised once at the end), and its entry of largest magnitude (the lowest index on ties) is positive.
+ *   What users read is formed from these on the host: with divisor = n - 1, weights w_ki = vectors[k][i] / sqrt(n - 1) give
+ *   modes per standard deviation, and b_ik = sqrt(n - 1) * vectors[k][i] is image i's score on mode k in standard deviations.
+ *
+ * Device memory: 4 * n_images * n_components bytes per window voxel, allocated by create; gram and project work through the
+ * window in batches whose scratch stays below 256 MiB (or one z-plane's, where that is more).
+ * Left out: voxels that some image does not cover (they are outside the support), more than FROG_MODES_MAX_IMAGES images,
+ * log-Euclidean and velocity-field statistics, leave-one-out generalisation and specificity.
+ *
+ * FROG_E_INVALID, before the device is touched: a NULL argument that is not marked optional, everything frog_glm_create refuses
+ * for the grid and the window, n_images < 2 or > FROG_MODES_MAX_IMAGES, n_components other than 1 or 3; in the adds what the
+ * frog_glm adds refuse, an add whose kind does not fit n_components, the (n_images + 1)th add; in plane an image_index not yet
+ * added; in gram and project fewer than n_images adds; in project n_modes == 0 or > n_images, a weight that is not finite; in
+ * eigen n == 0 or > FROG_MODES_MAX_IMAGES, a divisor that is not > 0 (or not finite), a gram entry that is not finite. */
+#define FROG_MODES_MAX_IMAGES 512
+#define FROG_MODES_CHUNK 1024
+typedef struct frog_modes frog_modes;
+int  frog_modes_planes(const frog_volume *grid, uint32_t n_images, uint32_t n_components, int device, uint32_t *planes);
+int  frog_modes_create(const frog_volume *grid, uint32_t first_plane, uint32_t n_planes, uint32_t n_images, uint32_t n_components,
+                       int device, frog_modes **out);
+int  frog_modes_add_displacement(frog_modes *a, frog_chain *chain, const frog_volume *support, const frog_volume *mask);
+int  frog_modes_add_jacobian(frog_modes *a, frog_chain *chain, const frog_volume *support, const frog_volume *mask, int log_mode);
+int  frog_modes_add(frog_modes *a, frog_chain *chain, const frog_volume *source, const frog_volume *mask, int interpolation, double background);
+int  frog_modes_plane(frog_modes *a, uint32_t image_index, float *values);
+int  frog_modes_gram(frog_modes *a, const uint8_t *region, double *gram, uint64_t *n_support);
+int  frog_modes_project(frog_modes *a, const uint8_t *region, uint32_t n_modes, const double *weights, float fill, float *mean, float *modes);
+int  frog_modes_eigen(uint32_t n, const double *gram, double divisor, double *values, double *vectors);
+void frog_modes_destroy(frog_modes *a);
+
 #ifdef __cplusplus
 }
 #endif
