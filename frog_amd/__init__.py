@@ -7,3 +7,4 @@ from .pairs import Pairs            # noqa: F401
 from .image_group import ImageGroup  # noqa: F401
 from .volume import Staple, staple_labels  # noqa: F401
 from .volume import SurfaceDistances, distance_map, surface_distances, surface_metrics  # noqa: F401
+from .mesh import isosurface, read_mesh, transform_points, write_mesh  # noqa: F401

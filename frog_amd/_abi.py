@@ -192,6 +192,14 @@ class FrogVolume(C.Structure):
                 ("dtype", C.c_int), ("data", C.c_void_p)]
 
 
+class FrogMesh(C.Structure):
+    """frog_mesh (include/frog_host.h)."""
+    _fields_ = [("n_points", C.c_uint32), ("xyz", c_float_p), ("n_faces", C.c_uint32), ("face_ptr", C.POINTER(C.c_uint32)),
+                ("face_idx", C.POINTER(C.c_uint32))]
+
+
+FROG_ISO_LEVEL, FROG_ISO_LABEL = 0, 1   # include/frog_chain.h
+
 FROG_V_DTYPES = ["uint8", "int8", "uint16", "int16", "uint32", "int32", "float32", "float64"]
 
 
@@ -403,6 +411,12 @@ HIP_SYMBOLS = {
                                       C.POINTER(C.c_void_p)]),
     "frog_surface_add": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogVolume), C.c_double, C.POINTER(FrogSurfaceRow)]),
     "frog_surface_destroy": (None, [C.c_void_p]),
+    "frog_isosurface_create": (C.c_int, [C.POINTER(FrogVolume), C.c_int, C.c_double, C.c_int64, C.c_int, C.POINTER(C.c_void_p),
+                                         c_u32_p, c_u32_p]),
+    "frog_isosurface_apply": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "frog_isosurface_get": (C.c_int, [C.c_void_p, c_float_p, c_u32_p]),
+    "frog_isosurface_destroy": (None, [C.c_void_p]),
+    "frog_chain_apply_f32": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t]),
     "frog_match_options_default": (None, [C.POINTER(FrogMatchOptions)]),
     "frog_matcher_create": (C.c_int, [C.POINTER(FrogKeypoints), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_matcher_destroy": (None, [C.c_void_p]),
@@ -496,6 +510,11 @@ HOST_SYMBOLS = {
     "frog_volume_geometry": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), c_double_p, c_double_p]),
     "frog_nifti_write": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32), c_double_p, c_double_p, C.c_uint32, c_float_p]),
     "frog_run_schedule": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(FrogSchedulePlan), C.POINTER(FrogScheduleResult)]),
+    "frog_mesh_read": (C.c_void_p, [C.c_char_p, C.POINTER(C.c_int)]),
+    "frog_mesh_view": (None, [C.c_void_p, C.POINTER(FrogMesh)]),
+    "frog_mesh_free": (None, [C.c_void_p]),
+    "frog_mesh_write": (C.c_int, [C.c_char_p, C.POINTER(FrogMesh)]),
+    "frog_mesh_last_error": (C.c_char_p, []),
 }
 
 # include/frog_comm.h (libfrog_comm.so: RCCL; loaded only by hosts that shard over GPUs from C)

@@ -5,6 +5,7 @@
 // A sampled displacement field (FROG_T_FIELD) is a link too: eight node reads and a trilinear blend per point, which is
 // what frog_chain_sample collapses a whole chain (Newton inverses included) into.
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 
 #include "frog_chain.h"
 #include "dev_buf.h"
@@ -1051,6 +1052,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 #include "k_tfce.hip.h"
 #include "k_smooth.hip.h"
 #include "k_modes.hip.h"
+#include "k_iso.hip.h"
 
 } // namespace
 
@@ -1253,6 +1255,14 @@ struct frog_surface : frog_group {
     frog::DevBuf<unsigned long long> d_sum, d_count;
     frog::DevBuf<double> d_g1, d_g2;                // the passes' planes, grown to the largest box
     frog::DevBuf<uint2> d_list;
+};
+
+// a triangle mesh on the device: what frog_isosurface_create extracted, where frog_isosurface_apply moves it
+struct frog_isosurface {
+    int device = 0;
+    uint32_t n_vertices = 0, n_triangles = 0;
+    frog::DevBuf<float> d_xyz;                      // 3 per vertex
+    frog::DevBuf<uint32_t> d_triangles;             // 3 per triangle
 };
 
 namespace {
@@ -2906,6 +2916,94 @@ int modes_region(const char *where, const frog_modes *a, const uint8_t *region, 
     return FROG_OK;
 }
 
+// the chain on n f32 points that lie on the chain's device (in and out may be the same array)
+hipError_t chain_apply_f32_device(frog_chain *c, const float *d_in, float *d_out, size_t n)
+{
+    return chunked_launch(n, [&](unsigned blocks, size_t base) {
+        chain_apply_f32_kernel<<<blocks, LAUNCH_BLOCK>>>(base, c->d_links.p, (int)c->h_links.size(), d_in, d_out, n);
+    });
+}
+
+// frog_isosurface_create refuses a result of ISO_RESULT_MAX or more vertices or triangles: the indices are 32-bit and a mesh
+// file's counts signed
+// (test hook: FROG_ISO_RESULT_MAX=n lowers the limit)
+uint64_t iso_result_max()
+{
+    static const uint64_t m = [] {
+        const uint64_t cap = (uint64_t)1 << 31;
+        const char *s = getenv("FROG_ISO_RESULT_MAX");
+        const long long v = s ? atoll(s) : 0;
+        return v > 0 ? std::min(cap, (uint64_t)v) : cap;
+    }();
+    return m;
+}
+
+// exclusive sums of the blocks' totals: d_sums[b] for block b, d_sums[blocks] the grand total (d_counts has blocks + 1 entries,
+// the last one zero)
+int iso_block_offsets(const frog::DevBuf<unsigned long long> &d_counts, frog::DevBuf<unsigned long long> &d_sums, size_t blocks,
+                      frog::DevBuf<unsigned char> &d_temp, uint64_t *grand)
+{
+    size_t bytes = 0;
+    KCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_counts.p, d_sums.p, blocks + 1));
+    KCHECK(d_temp.alloc(std::max<size_t>(bytes, 1)));
+    KCHECK(hipcub::DeviceScan::ExclusiveSum(d_temp.p, bytes, d_counts.p, d_sums.p, blocks + 1));
+    unsigned long long total = 0;
+    KCHECK(hipMemcpy(&total, d_sums.p + blocks, sizeof total, hipMemcpyDeviceToHost));
+    *grand = total;
+    return FROG_OK;
+}
+
+template <class S>
+int isosurface_typed(frog_isosurface *s, const frog_volume *v, size_t total, int mode, double level, long long value)
+{
+    IsoParams p;
+    p.g = node_grid(v->origin, v->spacing, v->dims);
+    p.mode = mode; p.level = level; p.value = value;
+    const size_t blocks = (total + ISO_BLOCK - 1) / ISO_BLOCK;
+    frog::DevBuf<S> d_vol;
+    frog::DevBuf<uint8_t> d_mask, d_config;
+    frog::DevBuf<unsigned long long> d_count_v, d_count_t, d_first_v, d_first_t;
+    frog::DevBuf<unsigned char> d_temp;
+    KCHECK(d_vol.alloc(total));
+    KCHECK(d_mask.alloc(total));
+    KCHECK(d_config.alloc(total));
+    KCHECK(d_count_v.alloc(blocks + 1));
+    KCHECK(d_count_t.alloc(blocks + 1));
+    KCHECK(d_first_v.alloc(blocks + 1));
+    KCHECK(d_first_t.alloc(blocks + 1));
+    KCHECK(hipMemcpy(d_vol.p, v->data, total * sizeof(S), hipMemcpyHostToDevice));
+    KCHECK(hipMemsetAsync(d_count_v.p + blocks, 0, sizeof(unsigned long long), 0));
+    KCHECK(hipMemsetAsync(d_count_t.p + blocks, 0, sizeof(unsigned long long), 0));
+    hipError_t e = chunked_launch(total, [&](unsigned n, size_t base) {
+        iso_classify_kernel<S><<<n, ISO_BLOCK>>>(base, d_vol.p, total, p, d_mask.p, d_config.p, d_count_v.p, d_count_t.p);
+    });
+    if (e != hipSuccess) return hip_fail("frog_isosurface_create: classify", e);
+    uint64_t n_v = 0, n_t = 0;
+    if (int rc = iso_block_offsets(d_count_v, d_first_v, blocks, d_temp, &n_v)) return rc;
+    if (int rc = iso_block_offsets(d_count_t, d_first_t, blocks, d_temp, &n_t)) return rc;
+    if (n_v >= iso_result_max() || n_t >= iso_result_max())
+        return fail(FROG_E_INVALID, "frog_isosurface_create: " + std::to_string(n_v) + " vertices and " + std::to_string(n_t) +
+                                        " triangles: a surface holds fewer than " + std::to_string(iso_result_max()) + " of each");
+    if (!n_v) return FROG_OK;
+    frog::DevBuf<uint32_t> d_vertex_offset;
+    KCHECK(d_vertex_offset.alloc(total));
+    KCHECK(s->d_xyz.alloc(3 * (size_t)n_v));
+    KCHECK(s->d_triangles.alloc(3 * (size_t)n_t));
+    e = chunked_launch(total, [&](unsigned n, size_t base) {
+        iso_vertices_kernel<S><<<n, ISO_BLOCK>>>(base, d_vol.p, total, p, d_mask.p, d_first_v.p, d_vertex_offset.p, s->d_xyz.p);
+    });
+    if (e == hipSuccess && n_t) {
+        e = chunked_launch(total, [&](unsigned n, size_t base) {
+            iso_triangles_kernel<<<n, ISO_BLOCK>>>(base, total, p.g, d_mask.p, d_config.p, d_first_t.p, d_vertex_offset.p, s->d_triangles.p);
+        });
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail("frog_isosurface_create: emit", e);
+    s->n_vertices = (uint32_t)n_v;
+    s->n_triangles = (uint32_t)n_t;
+    return FROG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -2977,6 +3075,75 @@ int frog_chain_apply(frog_chain *c, const double *in, double *out, size_t n)
     if (e == hipSuccess) e = hipMemcpy(out, d_out.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail("frog_chain_apply", e);
     return FROG_OK;
+}
+
+int frog_chain_apply_f32(frog_chain *c, const float *in, float *out, size_t n)
+{
+    if (!c || (n && (!in || !out))) return fail(FROG_E_INVALID, "bad arguments to frog_chain_apply_f32");
+    if (!n) return FROG_OK;
+    KCHECK(hipSetDevice(c->device));
+    frog::DevBuf<float> d_p;
+    KCHECK(d_p.alloc(3 * n));
+    hipError_t e = hipMemcpy(d_p.p, in, 3 * n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = chain_apply_f32_device(c, d_p.p, d_p.p, n);
+    if (e == hipSuccess) e = hipMemcpy(out, d_p.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail("frog_chain_apply_f32", e);
+    return FROG_OK;
+}
+
+int frog_isosurface_create(const frog_volume *volume, int mode, double level, int64_t value, int device,
+                           frog_isosurface **out, uint32_t *n_vertices, uint32_t *n_triangles)
+{
+    if (!volume || !volume->data || !out || !n_vertices || !n_triangles) return fail(FROG_E_INVALID, "bad arguments to frog_isosurface_create");
+    if (mode != FROG_ISO_LEVEL && mode != FROG_ISO_LABEL) return fail(FROG_E_INVALID, "frog_isosurface_create: mode FROG_ISO_LEVEL or FROG_ISO_LABEL");
+    if (!frog_volume_voxel_bytes(volume->dtype)) return fail(FROG_E_INVALID, "frog_isosurface_create: unknown scalar type");
+    if (mode == FROG_ISO_LABEL && !integer_voxel_type(volume->dtype))
+        return fail(FROG_E_INVALID, "frog_isosurface_create: a label volume has an integer type");
+    if (mode == FROG_ISO_LEVEL && std::isnan(level)) return fail(FROG_E_INVALID, "frog_isosurface_create: the level is NaN");
+    const uint64_t slice = (uint64_t)volume->dims[0] * volume->dims[1];         // < 2^64
+    if (slice > ((uint64_t)1 << 31) || slice * volume->dims[2] > ((uint64_t)1 << 31))
+        return fail(FROG_E_INVALID, "frog_isosurface_create: more than 2^31 nodes");
+    if (int rc = select_device(device)) return rc;
+    std::unique_ptr<frog_isosurface> s(new (std::nothrow) frog_isosurface);
+    if (!s) return fail(FROG_E_NOMEM, "out of host memory");
+    s->device = device;
+    if (volume->dims[0] >= 2 && volume->dims[1] >= 2 && volume->dims[2] >= 2) {
+        const size_t total = voxel_count(volume);
+        if (int rc = with_voxel_type(volume->dtype, [&](auto t) { return isosurface_typed<decltype(t)>(s.get(), volume, total, mode, level, (long long)value); }))
+            return rc;
+    }
+    *n_vertices = s->n_vertices;
+    *n_triangles = s->n_triangles;
+    *out = s.release();
+    return FROG_OK;
+}
+
+int frog_isosurface_apply(frog_isosurface *s, frog_chain *c)
+{
+    if (!s || !c) return fail(FROG_E_INVALID, "bad arguments to frog_isosurface_apply");
+    if (c->device != s->device) return fail(FROG_E_INVALID, "frog_isosurface_apply: the chain is on another device");
+    if (!s->n_vertices) return FROG_OK;
+    KCHECK(hipSetDevice(s->device));
+    hipError_t e = chain_apply_f32_device(c, s->d_xyz.p, s->d_xyz.p, s->n_vertices);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail("frog_isosurface_apply", e);
+    return FROG_OK;
+}
+
+int frog_isosurface_get(frog_isosurface *s, float *xyz, uint32_t *triangles)
+{
+    if (!s || (s->n_vertices && !xyz) || (s->n_triangles && !triangles)) return fail(FROG_E_INVALID, "bad arguments to frog_isosurface_get");
+    KCHECK(hipSetDevice(s->device));
+    if (s->n_vertices) KCHECK(hipMemcpy(xyz, s->d_xyz.p, 3 * (size_t)s->n_vertices * sizeof(float), hipMemcpyDeviceToHost));
+    if (s->n_triangles) KCHECK(hipMemcpy(triangles, s->d_triangles.p, 3 * (size_t)s->n_triangles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return FROG_OK;
+}
+
+void frog_isosurface_destroy(frog_isosurface *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    delete s;
 }
 
 int frog_chain_check(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3],

@@ -919,6 +919,57 @@ int  frog_modes_project(frog_modes *a, const uint8_t *region, uint32_t n_modes, 
 int  frog_modes_eigen(uint32_t n, const double *gram, double divisor, double *values, double *vectors);
 void frog_modes_destroy(frog_modes *a);
 
+/* ---- iso-surfaces: a welded triangle mesh from a scalar volume at a level, or from a label map at a value (an extension; the
+ * reference has tools/MeshTransform.cxx for meshes made elsewhere, and nothing that makes one) ---------------------------------
+ * Marching tetrahedra on the Kuhn (Freudenthal) decomposition of every grid cell: translation invariant and face compatible,
+ * so neighbouring cells agree without a parity rule and the mesh is a closed 2-manifold wherever the surface does not touch the
+ * grid's border.  No hashing and no atomics: the output is the same bytes from run to run.
+ *   Nodes.  The voxels of `volume` (any FROG_V_* type), node (i, j, k) at origin + (i, j, k) * spacing in f64 per axis, as
+ *     frog_chain_sample forms it; node index = i + dims[0] * (j + dims[1] * k).
+ *   Inside. FROG_ISO_LEVEL: iff (double)v >= level (a NaN voxel is outside).  FROG_ISO_LABEL: iff the voxel as a signed 64-bit
+ *     integer equals `value`; integer types only.
+ *   Cells.  A cell belongs to its lowest node.  Its six tetrahedra are taken in the lexicographic order of the permutations pi
+ *     of the axes: xyz, xzy, yxz, yzx, zxy, zyx.  Tetrahedron pi has the vertices v0 = (0,0,0), v1 = v0 + e_pi0,
+ *     v2 = v1 + e_pi1, v3 = (1,1,1) of the cell.
+ *   Triangles of a tetrahedron, by its inside set; a triangle vertex is named by the tetrahedron edge it lies on, a pair of
+ *     tetrahedron vertex numbers:
+ *       0 or 4 inside                                  none
+ *       1 inside, a; the others b < c < d              (ab, ac, ad)
+ *       3 inside, b < c < d; a outside                 (ba, ca, da)
+ *       2 inside, a < b; c < d outside                 the quad (ac, ad, bd, bc) cut as (ac, ad, bd) and (ac, bd, bc)
+ *   Orientation.  With the triangle's vertices at the edges' midpoints in the unit cube: if normal . (mean of the outside
+ *     corners - mean of the inside corners) <= 0, its second and third vertices are swapped.  The product is never 0.  Normals
+ *     point from inside to outside; the first vertex never moves.
+ *   Vertices.  One per crossing edge (its ends differ in the inside test).  An edge belongs to its lower node, which owns seven:
+ *     (dx, dy, dz) != 0 with code dx + 2 dy + 4 dz - 1 -- three axis edges, three face diagonals, the body diagonal.  For the
+ *     owner a and the other end b, in f64:
+ *       FROG_ISO_LEVEL: t = (level - va) / (vb - va); t = 0.5 if va or vb is not finite.      FROG_ISO_LABEL: t = 0.5.
+ *       per axis p = pa + t * (pb - pa), stored as one (float) cast.
+ *     A voxel equal to the level gives t = 0 or 1; the degenerate triangles this makes are kept (dropping them opens the mesh).
+ *   Order, part of the interface.  Vertices ascend by owner node index, within a node by edge code.  Triangles ascend by cell
+ *     in the same node order, within a cell by tetrahedron, within a tetrahedron in the rule's order.  The vertex on an edge has
+ *     the index vertex_offset[owner] + popcount(mask[owner] & ((1 << code) - 1)), mask the owner's 7-bit set of crossing edges
+ *     and vertex_offset the exclusive sum of the masks' popcounts over the nodes.
+ * A grid with a dimension below 2, or with nothing inside: 0 vertices, 0 triangles, FROG_OK (and a handle).
+ * FROG_E_INVALID: a NULL argument; an unknown mode or dtype; a float dtype in label mode; a NaN level; more than 2^31 nodes
+ * (all before the device is touched); a result of 2^31 or more vertices or triangles, found from 64-bit totals before
+ * anything is allocated for it.
+ * Device memory while create runs: the volume, 6 bytes per node and the mesh (12 bytes per vertex and per triangle); the
+ * handle keeps the mesh. */
+enum { FROG_ISO_LEVEL = 0, FROG_ISO_LABEL = 1 };
+typedef struct frog_isosurface frog_isosurface;
+int  frog_isosurface_create(const frog_volume *volume, int mode, double level, int64_t value, int device,
+                            frog_isosurface **out, uint32_t *n_vertices, uint32_t *n_triangles);
+/* vertices <- (float)chain((double)vertex), on the device where they lie: frog_chain_apply_f32 without the copies.  A chain on
+ * another device -> FROG_E_INVALID. */
+int  frog_isosurface_apply(frog_isosurface *s, frog_chain *chain);
+/* n_vertices x 3 floats and n_triangles x 3 indices into host arrays (either may be NULL when its count is 0). */
+int  frog_isosurface_get(frog_isosurface *s, float *xyz, uint32_t *triangles);
+void frog_isosurface_destroy(frog_isosurface *s);
+/* out[i] = (float)chain((double)in[i]), n points of 3 floats (host arrays): frog_chain_apply on the widened points (the same
+ * device code), cast once.  What bin/MeshTransform moves a mesh's points with. */
+int  frog_chain_apply_f32(frog_chain *c, const float *in3n, float *out3n, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

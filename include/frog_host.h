@@ -229,6 +229,37 @@ int frog_score_metrics_from(const frog_score_sums *s, const uint64_t *histogram,
  * A missing file, a missing or malformed box, an empty box or spacing <= 0 -> FROG_E_INVALID. */
 int frog_bbox_grid(const char *bbox_json, double spacing, frog_volume *grid);
 
+/* ---- surface meshes (tools/MeshTransform.cxx:62-64: ReadPolyData / WritePolyData, chosen by the file's extension) --------------
+ * Points as f32 and faces as polygons of any size: face f has the point indices face_idx[face_ptr[f] .. face_ptr[f + 1]),
+ * face_ptr has n_faces + 1 entries and starts at 0.  Faces pass through a transform untouched.  Point normals, texture
+ * coordinates, colours and every other attribute are read past and not carried.
+ *   read   .obj   v lines; f lines in the forms i, i/t, i//n, i/t/n; negative (relative) indices; everything else ignored
+ *          .ply   ascii and binary_little_endian; vertex x y z as float or double; face lists (vertex_indices or vertex_index)
+ *                 with any integer count and index type; other properties and elements skipped by their declared sizes
+ *          .stl   binary and ASCII; points with equal bit patterns are merged, numbered in first-occurrence order
+ *          .vtk   legacy POLYDATA, ASCII and BINARY (big-endian); POINTS as float or double; POLYGONS, and TRIANGLE_STRIPS
+ *                 expanded to triangles; the classic and the OFFSETS / CONNECTIVITY layout of a cell section
+ *   write  .obj   %.9g, which round-trips an f32         .ply   binary_little_endian
+ *          .stl   binary; polygons are fan-triangulated (0, j, j + 1), the facet normal comes from the polygon's first three points
+ *          .vtk   ASCII, classic POLYGONS                .vtp   XML, format="ascii"
+ * VTK is absent from the image, so parity with its writers is unpinned, as for the NIfTI writer.
+ * A file that cannot be opened is FROG_E_IO; an unknown extension, a truncated or malformed file, or a face index outside the
+ * points is FROG_E_INVALID.  No reader reads past the end of the file, whatever its header promises.  frog_mesh_last_error
+ * returns the message of the calling thread's last refusal.  frog_mesh_view's pointers live until frog_mesh_free. */
+typedef struct frog_mesh {
+    uint32_t  n_points;
+    float    *xyz;              /* 3 per point                                                  */
+    uint32_t  n_faces;
+    uint32_t *face_ptr;         /* n_faces + 1                                                  */
+    uint32_t *face_idx;         /* face_ptr[n_faces]                                            */
+} frog_mesh;
+typedef struct frog_mesh_file frog_mesh_file;
+frog_mesh_file *frog_mesh_read(const char *path, int *status);
+void frog_mesh_view(const frog_mesh_file *f, frog_mesh *out);
+void frog_mesh_free(frog_mesh_file *f);
+int frog_mesh_write(const char *path, const frog_mesh *mesh);
+const char *frog_mesh_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif
