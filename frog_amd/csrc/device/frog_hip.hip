@@ -2804,6 +2804,47 @@ int frog_test_bspline_weights(int device, const double *f, size_t n, double *out
     return FROG_OK;
 }
 
+// one wavefront, lane = tap: the scatter's phase-2 accumulate over n points in order, by scatter_accumulate or by fmaf
+__global__ __launch_bounds__(64, 4) void test_scatter_accumulate_kernel(const float *sums, const float *weights, uint32_t n, const float *start,
+                                                                     float *out, int plain)
+{
+    const int lane = threadIdx.x;
+    f32x4 run = { start[4 * lane], start[4 * lane + 1], start[4 * lane + 2], start[4 * lane + 3] };
+    for (uint32_t q = 0; q < n; q++) {                  // `plain` and n are kernel-uniform: the matrix instruction ignores EXEC
+        const float w = weights[64 * (size_t)q + lane];
+        if (plain) {
+            #pragma unroll
+            for (int c = 0; c < 4; c++) run[c] = fmaf(w, sums[4 * (size_t)q + c], run[c]);
+        } else {
+            scatter_accumulate(run, sums[4 * (size_t)q + (lane & 3)], w);
+        }
+    }
+    #pragma unroll
+    for (int c = 0; c < 4; c++) out[4 * lane + c] = run[c];
+}
+
+int frog_test_scatter_accumulate(int device, const float *sums4n, const float *weights64n, size_t n, const float *start256, float *out256,
+                                 int plain)
+{
+    if (!start256 || !out256 || (n && (!sums4n || !weights64n))) return fail(FROG_E_INVALID, "null argument");
+    if (n > (1u << 20)) return fail(FROG_E_INVALID, "too many points");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(FROG_E_NODEVICE, "no HIP device");
+    if (device < 0 || device >= ndev) return fail(FROG_E_INVALID, "device index out of range");
+    FROG_HIP_CHECK(hipSetDevice(device));
+    DevBuf<float> ds, dw, d0, d1;
+    FROG_HIP_CHECK(ds.alloc(4 * n + 1)); FROG_HIP_CHECK(dw.alloc(64 * n + 1)); FROG_HIP_CHECK(d0.alloc(256)); FROG_HIP_CHECK(d1.alloc(256));
+    if (n) {
+        FROG_HIP_CHECK(hipMemcpy(ds.p, sums4n, 4 * n * sizeof(float), hipMemcpyHostToDevice));
+        FROG_HIP_CHECK(hipMemcpy(dw.p, weights64n, 64 * n * sizeof(float), hipMemcpyHostToDevice));
+    }
+    FROG_HIP_CHECK(hipMemcpy(d0.p, start256, 256 * sizeof(float), hipMemcpyHostToDevice));
+    test_scatter_accumulate_kernel<<<1, 64>>>(ds.p, dw.p, (uint32_t)n, d0.p, d1.p, plain);
+    FROG_HIP_CHECK(hipGetLastError());
+    FROG_HIP_CHECK(hipMemcpy(out256, d1.p, 256 * sizeof(float), hipMemcpyDeviceToHost));
+    return FROG_OK;
+}
+
 int frog_test_cull_ranges(frog_ctx *ctx, uint64_t *ranges, uint64_t *with_election)
 {
     CTX_GUARD(ctx);

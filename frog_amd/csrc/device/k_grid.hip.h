@@ -1011,7 +1011,8 @@ __device__ __forceinline__ void scatter_energy_block(const ScatterEnergy &en, co
 
 // Per-point values handed from phase 1 (lane = point) to phase 2 (lane = tap) through LDS, one array per value
 // (lane-consecutive writes and reads: no bank conflicts).  In phase 2 an instruction serves ONE point, and that loop is where a
-// block spends its time (per-block trace, -DFROG_SCATTER_TRACE + scripts/microbench/scatter_trace_an.py: 63 % of a block's 52 us).
+// block spends most of its time (per-block trace, -DFROG_SCATTER_TRACE + scripts/microbench/scatter_trace_an.py; the figures are at
+// the quads block below and in profiles/r08_scatter_mfma_ab.txt).
 #ifndef FROG_SCATTER_QUADS
 #define FROG_SCATTER_QUADS 1       // phase 2 reads the weights of FOUR points per LDS instruction (see there); 0: point by point (rounds 2-4)
 #endif
@@ -1022,42 +1023,39 @@ constexpr int SC_PTS = 64 + 4;                  // ... a group of four ahead, un
 constexpr int SC_PTS = 64 + SC_AHEAD;           // ... unconditionally, so up to SC_AHEAD entries past the batch are read (unused)
 #endif
 struct ScatterScratch {
-    // Round 5: the twelve weights as they are, multiplied in phase 2 (rounds 2-4 handed over the 16 products wx wy formed in
-    // phase 1) -- 68 instead of 100 bytes per point, 4.6 instead of 6.7 KB per block, which with the
-    // 5.5 KB tile is what decides how many one-wavefront blocks a CU holds: 16 (the register file's limit) instead of 12.  The
-    // per-block trace (scripts/microbench/scatter_trace_an.py) shows the launch as rounds of resident blocks -- 5 527 blocks of
-    // 23 us in 1.8 rounds of 3 072 on level 0 -- and phase 2 is not bound by its instruction count (a branch-free form for runs of
-    // one cell issued half the instructions per point and was no faster), so one more read and one more multiplication per
-    // point (wx wy, the same f32 product phase 1 used to form) cost less than the fourth block per SIMD gains.
+    // The twelve weights as they are, multiplied in phase 2 (rounds 2-4 handed over the 16 products wx wy formed in phase 1), and
+    // the four sums: 68 bytes per point, 4.6 KB per block, which with the 5.5 KB tile is what decides how many one-wavefront blocks
+    // a CU holds: 16, the register file's limit at <= 128 registers.  Every array is [value][point]: a lane of phase 2 reads ONE
+    // value of four consecutive points with one ds_read_b128 -- its tap's wx, wy, wz, and component (lane & 3) of the sums, which is
+    // the operand layout of the matrix instruction (scatter_accumulate) -- so phase 1 stores the sums as four ds_write_b32, not
+    // one ds_write_b128.  The block must not grow: the fourth block per SIMD is worth more than anything the scratch could save.
     float wx[4][SC_PTS], wy[4][SC_PTS];
     float wz[4][SC_PTS];
-    float4 sm[SC_PTS];          // sDisp xyz, sWeight
+    float sm[4][SC_PTS];        // sDisp x, y, z and sWeight: component-major, point-minor like the weights (see scatter_accumulate)
     int base[SC_PTS];           // tile offset of tap (0,0,0)
 };
-static_assert(offsetof(ScatterScratch, sm) % 16 == 0, "ScatterScratch::sm is read with ds_read_b128");
+#if FROG_SCATTER_QUADS
+static_assert(offsetof(ScatterScratch, sm) % 16 == 0 && SC_PTS % 4 == 0, "the rows of ScatterScratch are read with ds_read_b128");
+#endif
 
-// run += w * (the four values `s` holds in lane (t & ~3) + P): four v_fmac_f32 with quad_perm [P, P, P, P] on their first source -- the
-// broadcast inside the quad is a modifier of the multiply-add, not an instruction.  Written out because the compiler, given a builtin
-// DPP move and four multiply-adds, forms two v_pk_fma_f32 (which cannot take the modifier) behind four v_mov_b32_dpp: six
-// instructions for four.  ONE asm statement per point, led by s_nop 1: a DPP source written by a vector instruction needs two wait
-// states before it is read, the compiler's hazard recogniser cannot see inside an asm statement, and nothing can be scheduled
-// into the middle of one.
-#define FROG_FMAC_DPP(D, S, Q) "v_fmac_f32_dpp %" #D ", %" #S ", %8 quad_perm:[" #Q "," #Q "," #Q "," #Q "] row_mask:0xf bank_mask:0xf\n\t"
-// (Round 6, ADVICE r5: the statement is `volatile` now, and tests/test_gpu_round6.py holds this form against a build without it
-// bit for bit.  s_nop 4 -- which would also cover a vector write of EXEC, v_cmpx, right in front of the statement; the compiler
-// forms its masks with s_and_saveexec here -- was measured: scatter 0.0645 against 0.0629 ms, 650 steps 2 212 against 2 232 it/s.)
-#define FROG_FMAC4_DPP(Q) asm volatile("s_nop 1\n\t" FROG_FMAC_DPP(0, 4, Q) FROG_FMAC_DPP(1, 5, Q) FROG_FMAC_DPP(2, 6, Q) FROG_FMAC_DPP(3, 7, Q)      \
-                              : "+v"(run.x), "+v"(run.y), "+v"(run.z), "+v"(run.w) : "v"(s.x), "v"(s.y), "v"(s.z), "v"(s.w), "v"(w))
-template <int P> __device__ __forceinline__ void fmac4_quad_bcast(float4 &run, const float4 s, float w)
+// Phase 2's accumulate for ONE point, the whole wavefront at once: run[c] = fmaf(w, s[c], run[c]), c = 0..3, in every lane (= tap),
+// where w is the lane's own tap weight and s the point's four sums -- a rank-1 update of the 64 x 4 values the wavefront holds.
+// v_mfma_f32_4x4x1_16b_f32 is that update: 16 independent 4x4 blocks (block b = lanes 4b .. 4b+3), D[b][r][j] = A[b][r] B[b][j] +
+// C[b][r][j], with A[b][r] read from lane 4b + r, B[b][j] from lane 4b + j, and D/C register r of lane 4b + j holding row r of
+// column j.  So `s_comp` is component (lane & 3) of the point's sums -- every quad carries all four, which is why the scratch keeps
+// them component-major -- and w rides on the column.  K = 1: one product, one rounding, no flush of subnormals in the default
+// mode: the bits of fmaf, which is what the point-by-point form computes and tests/test_gpu_scatter_mfma.py holds it against
+// (frog_test_scatter_accumulate, and the whole kernel against the FROG_SCATTER_QUADS=0 build).  The instruction ignores EXEC: call
+// it under wave-uniform control flow only.
+__device__ __forceinline__ void scatter_accumulate(f32x4 &run, const float s_comp, const float w)
 {
-    static_assert(P >= 0 && P < 4, "quad lane");
-    if constexpr (P == 0) FROG_FMAC4_DPP(0);
-    if constexpr (P == 1) FROG_FMAC4_DPP(1);
-    if constexpr (P == 2) FROG_FMAC4_DPP(2);
-    if constexpr (P == 3) FROG_FMAC4_DPP(3);
+    run = __builtin_amdgcn_mfma_f32_4x4x1f32(s_comp, w, run, 0, 0, 0);
 }
 
-__global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const float4 *point_sums,
+// Four wavefronts per SIMD (<= 128 registers) is what the kernel is sized for, and saying so is what keeps the matrix instruction's
+// accumulator in VGPRs: with the full register budget of a 64-thread block the compiler puts it in AGPRs and copies it in and out
+// around every instruction.
+__global__ __launch_bounds__(64, 4) void scatter_kernel(const float4 *pos_b, const float4 *point_sums,
                                                      const float4 *group_sums, uint32_t own_points, uint32_t own_pt_begin,
                                                      const uint32_t *perm, const ScatterBlock *blocks, const uint32_t *n_blocks,
                                                      float4 *gradf, float4 *stage, unsigned int *stray, const GeomDev g,
@@ -1126,7 +1124,7 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 
-    float4 run = make_float4(0.f, 0.f, 0.f, 0.f);      // contributions of the current cell, this lane's tap
+    f32x4 run = { 0.f, 0.f, 0.f, 0.f };                // contributions of the current cell, this lane's tap
     int run_base = -1;
     for (uint32_t batch = blk.begin; batch < blk.end; batch += 64) {
         const uint32_t p_far = load_index(batch + 128 + lane);
@@ -1197,7 +1195,7 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
             for (int k = 0; k < 4; k++) { sc.wx[k][slot] = wx4[k]; sc.wy[k][slot] = wy4[k]; }
             #pragma unroll
             for (int k = 0; k < 4; k++) sc.wz[k][slot] = wz[k];
-            sc.sm[slot] = sm;
+            sc.sm[0][slot] = sm.x; sc.sm[1][slot] = sm.y; sc.sm[2][slot] = sm.z; sc.sm[3][slot] = sm.w;
             sc.base[slot] = base;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1218,43 +1216,55 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
             chg = __ballot(lane < n_live && mine != before);
         }
 #if FROG_SCATTER_QUADS
-        // Round 5.  The launch is bound by the LDS: point by point a tap's three weights are three ds_read_b32 (2 LDS cycles
-        // each for the wavefront, however many lanes share an address) and the sums a broadcast ds_read_b128 (4): 10 cycles per
-        // point and CU, 7 800 points per CU -> 33 us of a 64 us launch (level 0; on level 2 the tile's read-add-write at nearly
-        // every point adds 17 more).  A ds_read_b128 costs 4 cycles and brings the weights of FOUR consecutive points
-        // (the scratch is point-minor), and the four points' sums arrive with ONE more: lane t reads the sums of point q0 + (t & 3)
-        // and the quad hands them round by DPP, a modifier of the multiply-add (fmac4_quad_bcast), not an instruction: 16 cycles per four points.
+        // Four points per LDS instruction: a ds_read_b128 brings a lane one value of FOUR consecutive points (the scratch is
+        // point-minor) -- its tap's wx, wy, wz and component (lane & 3) of the sums: 16 LDS cycles per four points, where point by
+        // point three ds_read_b32 and a broadcast ds_read_b128 cost 40.  Per point then one v_pk_mul_f32's worth of (wx wy) wz and ONE
+        // matrix instruction (scatter_accumulate) for the 256 multiply-adds, where the vector ALU took four v_fmac_f32_dpp.
         // Same operations on the same values in the same order as point by point: identical bits.
+        // What bounds it, as measured (profiles/r08_scatter_mfma_ab.txt): not the LDS and
+        // not memory -- a block still spends more than half of its life here, at what ONE wavefront issues per point in series
+        // (the matrix instruction waits for its predecessor's accumulator, a scalar test and branch per point for the cell change
+        // and the batch's end) with four such wavefronts per SIMD, and the launch is 1.8 rounds of resident blocks on level 0, the
+        // second on a half-empty chip.  On level 2 nearly every point changes the cell: the tile's read-add-write and its wait
+        // (spill_and_restart) are the point's cost there, and the form of the accumulate barely shows.  A body without branches for
+        // four points of the running cell was measured again: level 0 faster (0.048 against 0.051 ms), level 2 slower (0.071
+        // against 0.068), the 650-step line the same: not kept.
         {
             const f32x4 *gwx = reinterpret_cast<const f32x4 *>(sc.wx[lane & 3]), *gwy = reinterpret_cast<const f32x4 *>(sc.wy[(lane >> 2) & 3]),
                         *gwz = reinterpret_cast<const f32x4 *>(sc.wz[lane >> 4]);
-            const float4 *gsm = sc.sm + (lane & 3);
-            f32x4 cwx = gwx[0], cwy = gwy[0], cwz = gwz[0];
-            float4 csm4 = gsm[0];
+            const f32x4 *gsm = reinterpret_cast<const f32x4 *>(sc.sm[lane & 3]);
             auto spill_and_restart = [&](int q) __attribute__((always_inline)) {
                 if (run_base >= 0) {
                     float4 t = tile[run_base + tap_off];
                     t.x += run.x; t.y += run.y; t.z += run.z; t.w += run.w;
                     tile[run_base + tap_off] = t;
                 }
-                run = make_float4(0.f, 0.f, 0.f, 0.f);
+                run = f32x4{ 0.f, 0.f, 0.f, 0.f };
                 run_base = __builtin_amdgcn_readfirstlane(sc.base[q]);
             };
-            for (int q0 = 0; q0 < n_live; q0 += 4) {
-                const int g1 = (q0 >> 2) + 1;
-                const f32x4 nwx = gwx[g1], nwy = gwy[g1], nwz = gwz[g1];       // the next group's, one trip ahead (unconditional)
-                const float4 nsm = gsm[4 * g1];
-                const f32x4 w4 = (cwx * cwy) * cwz;                              // (wx wy) wz, imageGroup.cxx:322 left to right
+            // the four points q0 .. q0 + 3 (those below n_live), in order
+            auto add_group = [&](const int q0, const f32x4 wx, const f32x4 wy, const f32x4 wz, const f32x4 sm4) __attribute__((always_inline)) {
+                const f32x4 w4 = (wx * wy) * wz;                                 // (wx wy) wz, imageGroup.cxx:322 left to right
                 const unsigned m = (unsigned)(chg >> q0) & 15u;
                 const int left = n_live - q0;                                    // >= 1
-#define FROG_SCATTER_ADD(P)                                                                                            \
+#define FROG_SCATTER_ADD(P)                                                                                           \
                 if (P < left) {                                                                                         \
                     if (m >> P & 1u) spill_and_restart(q0 + P);                                                         \
-                    fmac4_quad_bcast<P>(run, csm4, w4[P]);                                                              \
+                    scatter_accumulate(run, sm4[P], w4[P]);                                                             \
                 }
                 FROG_SCATTER_ADD(0) FROG_SCATTER_ADD(1) FROG_SCATTER_ADD(2) FROG_SCATTER_ADD(3)
 #undef FROG_SCATTER_ADD
-                cwx = nwx; cwy = nwy; cwz = nwz; csm4 = nsm;
+            };
+            // Two groups per trip, each read while the other is worked on, into its own registers: no copies at the end of a trip.
+            // Every read is unconditional; the last one reaches group 16 at most, the row's last four entries (unused).
+            f32x4 awx = gwx[0], awy = gwy[0], awz = gwz[0], asm4 = gsm[0];
+            for (int q0 = 0; q0 < n_live; q0 += 8) {
+                const int g1 = (q0 >> 2) + 1;
+                const f32x4 bwx = gwx[g1], bwy = gwy[g1], bwz = gwz[g1], bsm4 = gsm[g1];
+                add_group(q0, awx, awy, awz, asm4);
+                if (q0 + 4 >= n_live) break;
+                awx = gwx[g1 + 1]; awy = gwy[g1 + 1]; awz = gwz[g1 + 1]; asm4 = gsm[g1 + 1];
+                add_group(q0 + 4, bwx, bwy, bwz, bsm4);
             }
         }
 #else
@@ -1266,7 +1276,7 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
             rwx[slot] = lane_wx[q];
             rwy[slot] = lane_wy[q];
             rwz[slot] = lane_wz[q];
-            rsm[slot] = sc.sm[q];
+            rsm[slot] = make_float4(sc.sm[0][q], sc.sm[1][q], sc.sm[2][q], sc.sm[3][q]);
         };
         auto add_point = [&](int q, int slot) __attribute__((always_inline)) {
             if ((chg >> q) & 1ull) {                               // wave-uniform: cell changed -> spill the run
@@ -1275,7 +1285,7 @@ __global__ __launch_bounds__(64) void scatter_kernel(const float4 *pos_b, const 
                     t.x += run.x; t.y += run.y; t.z += run.z; t.w += run.w;
                     tile[run_base + tap_off] = t;
                 }
-                run = make_float4(0.f, 0.f, 0.f, 0.f);
+                run = f32x4{ 0.f, 0.f, 0.f, 0.f };
                 run_base = __builtin_amdgcn_readfirstlane(sc.base[q]);
             }
             const float w = (rwx[slot] * rwy[slot]) * rwz[slot];           // (wx wy) wz, imageGroup.cxx:322 left to right

@@ -302,6 +302,12 @@ int frog_test_bspline_weights(int device, const double *f, size_t n, double *out
  * was created (they are handled, through global atomics: slowly and in no fixed order).  Inside the lattice's box --
  * always, for the group's own points -- this must stay 0; a non-zero count means the (image, brick, cell) sort is broken. */
 int frog_test_stray_points(frog_ctx *ctx, uint64_t *n);
+/* Test hook: the accumulate of the B-spline scatter's phase 2 by itself.  One wavefront, lane = tap t, starts from
+ * start256[4 t + c] and adds n points in order: run[t][c] = fmaf(weights64n[64 q + t], sums4n[4 q + c], run[t][c]), c = 0..3,
+ * for q = 0 .. n-1; the results go to out256[4 t + c].  plain = 0: the kernel's own helper (one f32 matrix instruction per
+ * point); plain = 1: an fmaf per value in every lane.  The two must agree bit for bit (tests/test_gpu_scatter_mfma.py). */
+int frog_test_scatter_accumulate(int device, const float *sums4n, const float *weights64n, size_t n, const float *start256,
+                                 float *out256, int plain);
 /* test hook: non-empty (tile, partner group) ranges of the current culling list, and how many of them hold a step in
  * which two lanes carry the same point (those are swept with the lane election, the others without; k_cull.hip.h) */
 int frog_test_cull_ranges(frog_ctx *ctx, uint64_t *ranges, uint64_t *with_election);
