@@ -417,6 +417,11 @@ HIP_SYMBOLS = {
     "frog_isosurface_get": (C.c_int, [C.c_void_p, c_float_p, c_u32_p]),
     "frog_isosurface_destroy": (None, [C.c_void_p]),
     "frog_chain_apply_f32": (C.c_int, [C.c_void_p, c_float_p, c_float_p, C.c_size_t]),
+    "frog_mesh_smooth": (C.c_int, [c_float_p, C.c_size_t, c_u32_p, c_u32_p, C.c_size_t, C.c_uint32, C.c_double, C.c_double, C.c_int,
+                                   C.c_int]),
+    "frog_isosurface_smooth": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_int]),
+    "frog_isosurface_upload": (C.c_int, [c_float_p, C.c_uint32, c_u32_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "frog_isosurface_cluster": (C.c_int, [C.c_void_p, C.c_double, c_u32_p, c_u32_p, c_u32_p]),
     "frog_match_options_default": (None, [C.POINTER(FrogMatchOptions)]),
     "frog_matcher_create": (C.c_int, [C.POINTER(FrogKeypoints), C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "frog_matcher_destroy": (None, [C.c_void_p]),

@@ -1053,6 +1053,7 @@ __global__ __launch_bounds__(256) void wlabels_probability_kernel(size_t base, c
 #include "k_smooth.hip.h"
 #include "k_modes.hip.h"
 #include "k_iso.hip.h"
+#include "k_mesh.hip.h"
 
 } // namespace
 
@@ -3004,6 +3005,255 @@ int isosurface_typed(frog_isosurface *s, const frog_volume *v, size_t total, int
     return FROG_OK;
 }
 
+// ---- mesh filters (k_mesh.hip.h) --------------------------------------------------------------------------------------------------
+
+// The largest mesh the smoothing accepts: its adjacency sorts two 64-bit keys per face index, and hipcub's run-length pass counts
+// its items in a signed 32-bit integer.
+constexpr uint64_t MESH_MAX_POINTS = ((uint64_t)1 << 31) - 1;
+constexpr uint64_t MESH_MAX_INDICES = ((uint64_t)1 << 30) - 1;
+
+// floats per vertex of the passes' working copies: 3 (the mesh's own packed rows, smoothed in place against one second buffer)
+// or 4 (16-byte rows, one load per neighbour, padded in and out).  The two give the same bytes; DESIGN 31 measured the packed
+// rows faster, in the pass kernel and in the whole call, and FROG_MESH_STRIDE=3 or 4 chooses one of them.
+constexpr int MESH_STRIDE_DEFAULT = 3;
+
+int mesh_stride()
+{
+    static const int stride = [] {
+        const char *s = getenv("FROG_MESH_STRIDE");
+        const int v = s ? atoi(s) : 0;
+        return v == 3 || v == 4 ? v : MESH_STRIDE_DEFAULT;
+    }();
+    return stride;
+}
+
+int bit_length(uint64_t v)
+{
+    int bits = 0;
+    for (; v; v >>= 1) bits++;
+    return bits;
+}
+
+int mesh_smooth_arguments(const char *where, double lambda, double mu, int boundary)
+{
+    if (!std::isfinite(lambda) || !std::isfinite(mu)) return fail(FROG_E_INVALID, std::string(where) + ": lambda and mu are finite");
+    if (boundary != 0 && boundary != 1) return fail(FROG_E_INVALID, std::string(where) + ": boundary 0 or 1");
+    return FROG_OK;
+}
+
+// host arrays: every one of the count indices is below n
+int mesh_indices_below(const char *where, const uint32_t *idx, size_t count, uint64_t n)
+{
+    for (size_t i = 0; i < count; i++)
+        if (idx[i] >= n) return fail(FROG_E_INVALID, std::string(where) + ": face index " + std::to_string(idx[i]) + " with " + std::to_string(n) + " points");
+    return FROG_OK;
+}
+
+// the CSR of the header's N(v): ptr[n + 1], col[n_entries]
+struct MeshGraph {
+    frog::DevBuf<uint32_t> d_ptr, d_col;
+    uint32_t n_entries = 0;
+};
+
+// d_face_ptr == nullptr: triangles.  n > 0, 0 < n_indices <= MESH_MAX_INDICES.
+int mesh_graph_build(size_t n, const uint32_t *d_face_ptr, const uint32_t *d_face_idx, size_t n_faces, size_t n_indices, int boundary, MeshGraph &g)
+{
+    const size_t slots = 2 * n_indices;
+    frog::DevBuf<unsigned long long> d_keys, d_sorted;
+    frog::DevBuf<uint32_t> d_times, d_runs, d_raw, d_degree;
+    frog::DevBuf<unsigned char> d_temp;
+    KCHECK(d_keys.alloc(slots));
+    KCHECK(d_sorted.alloc(slots));
+    KCHECK(d_times.alloc(slots));
+    KCHECK(d_runs.alloc(1));
+    hipError_t e = chunked_launch(n_faces, [&](unsigned blocks, size_t base) {
+        mesh_edge_keys_kernel<<<blocks, MESH_BLOCK>>>(base, d_face_ptr, d_face_idx, n_faces, (uint32_t)n, d_keys.p);
+    });
+    if (e != hipSuccess) return hip_fail("mesh adjacency: keys", e);
+    const int end_bit = 32 + bit_length(n);             // the sentinel n << 32 | n included
+    size_t bytes = 0;
+    KCHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, bytes, d_keys.p, d_sorted.p, slots, 0, end_bit));
+    KCHECK(d_temp.alloc(std::max<size_t>(bytes, 1)));
+    KCHECK(hipcub::DeviceRadixSort::SortKeys(d_temp.p, bytes, d_keys.p, d_sorted.p, slots, 0, end_bit));
+    // the distinct keys go where the unsorted ones were
+    bytes = 0;
+    KCHECK(hipcub::DeviceRunLengthEncode::Encode(nullptr, bytes, d_sorted.p, d_keys.p, d_times.p, d_runs.p, (int)slots));
+    KCHECK(d_temp.alloc(std::max<size_t>(bytes, 1)));
+    KCHECK(hipcub::DeviceRunLengthEncode::Encode(d_temp.p, bytes, d_sorted.p, d_keys.p, d_times.p, d_runs.p, (int)slots));
+    uint32_t runs = 0;
+    KCHECK(hipMemcpy(&runs, d_runs.p, sizeof runs, hipMemcpyDeviceToHost));
+    unsigned long long last_key = 0;
+    if (runs) KCHECK(hipMemcpy(&last_key, d_keys.p + (runs - 1), sizeof last_key, hipMemcpyDeviceToHost));
+    const uint32_t raw_entries = runs && last_key == ((unsigned long long)n << 32 | n) ? runs - 1 : runs;
+
+    KCHECK(d_raw.alloc(n + 1));
+    KCHECK(d_degree.alloc(n + 1));
+    KCHECK(g.d_ptr.alloc(n + 1));
+    e = chunked_launch(n + 1, [&](unsigned blocks, size_t base) {
+        mesh_row_kernel<<<blocks, MESH_BLOCK>>>(base, d_keys.p, raw_entries, n, d_raw.p);
+    });
+    if (e == hipSuccess) {
+        e = chunked_launch(n + 1, [&](unsigned blocks, size_t base) {
+            mesh_degree_kernel<<<blocks, MESH_BLOCK>>>(base, d_raw.p, d_keys.p, d_times.p, n, boundary, d_degree.p);
+        });
+    }
+    if (e != hipSuccess) return hip_fail("mesh adjacency: rows", e);
+    bytes = 0;
+    KCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_degree.p, g.d_ptr.p, n + 1));
+    KCHECK(d_temp.alloc(std::max<size_t>(bytes, 1)));
+    KCHECK(hipcub::DeviceScan::ExclusiveSum(d_temp.p, bytes, d_degree.p, g.d_ptr.p, n + 1));
+    KCHECK(hipMemcpy(&g.n_entries, g.d_ptr.p + n, sizeof g.n_entries, hipMemcpyDeviceToHost));
+    if (!g.n_entries) return FROG_OK;
+    KCHECK(g.d_col.alloc(g.n_entries));
+    e = chunked_launch(n, [&](unsigned blocks, size_t base) {
+        mesh_fill_kernel<<<blocks, MESH_BLOCK>>>(base, d_raw.p, d_keys.p, d_times.p, n, boundary, g.d_ptr.p, g.d_col.p);
+    });
+    if (e == hipSuccess) e = hipDeviceSynchronize();        // the build's buffers are freed on return
+    if (e != hipSuccess) return hip_fail("mesh adjacency: fill", e);
+    return FROG_OK;
+}
+
+template <int STRIDE>
+hipError_t mesh_pass(size_t n, const MeshGraph &g, const float *from, float *to, double f)
+{
+    return chunked_launch(n, [&](unsigned blocks, size_t base) {
+        mesh_pass_kernel<STRIDE><<<blocks, MESH_BLOCK>>>(base, n, g.d_ptr.p, g.d_col.p, from, to, f);
+    });
+}
+
+// 2 x iterations passes over the graph on d_xyz (3 floats per vertex, on the current device); the result is back in d_xyz
+int mesh_passes(float *d_xyz, size_t n, const MeshGraph &g, uint32_t iterations, double lambda, double mu)
+{
+    const int stride = mesh_stride();
+    frog::DevBuf<float> d_a, d_b;
+    float *from = d_xyz, *to = nullptr;
+    hipError_t e = hipSuccess;
+    KCHECK(d_b.alloc((size_t)stride * n));
+    to = d_b.p;
+    if (stride == 4) {
+        KCHECK(d_a.alloc(4 * n));
+        from = d_a.p;
+        e = chunked_launch(n, [&](unsigned blocks, size_t base) { mesh_pad_kernel<<<blocks, MESH_BLOCK>>>(base, d_xyz, d_a.p, n); });
+    }
+    for (uint32_t it = 0; it < 2 * (uint64_t)iterations && e == hipSuccess; it++) {
+        const double f = it % 2 ? mu : lambda;
+        e = stride == 4 ? mesh_pass<4>(n, g, from, to, f) : mesh_pass<3>(n, g, from, to, f);
+        std::swap(from, to);
+    }
+    // an even number of passes: the result lies where the first pass read
+    if (e == hipSuccess && stride == 4)
+        e = chunked_launch(n, [&](unsigned blocks, size_t base) { mesh_unpad_kernel<<<blocks, MESH_BLOCK>>>(base, d_a.p, d_xyz, n); });
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail("mesh smoothing: passes", e);
+    return FROG_OK;
+}
+
+// frog_mesh_smooth and frog_isosurface_smooth after their argument checks, on the current device
+int mesh_smooth_device(const char *where, float *d_xyz, size_t n, const uint32_t *d_face_ptr, const uint32_t *d_face_idx, size_t n_faces,
+                       size_t n_indices, uint32_t iterations, double lambda, double mu, int boundary)
+{
+    if (n > MESH_MAX_POINTS || n_indices > MESH_MAX_INDICES)
+        return fail(FROG_E_INVALID, std::string(where) + ": " + std::to_string(n) + " points and " + std::to_string(n_indices) +
+                                        " face indices: at most " + std::to_string(MESH_MAX_POINTS) + " and " + std::to_string(MESH_MAX_INDICES));
+    if (!n || !n_indices || !iterations || (lambda == 0.0 && mu == 0.0)) return FROG_OK;
+    if (iterations > ((uint32_t)1 << 30)) return fail(FROG_E_INVALID, std::string(where) + ": at most 2^30 iterations");
+    MeshGraph g;
+    if (int rc = mesh_graph_build(n, d_face_ptr, d_face_idx, n_faces, n_indices, boundary, g)) return rc;
+    if (!g.n_entries) return FROG_OK;
+    return mesh_passes(d_xyz, n, g, iterations, lambda, mu);
+}
+
+// frog_isosurface_cluster on the current device; cell is a finite double > 0 and the mesh has a vertex
+int mesh_cluster_device(frog_isosurface *s, double cell, uint32_t *cluster_of)
+{
+    const size_t n = s->n_vertices, m = s->n_triangles;
+    const int bound_blocks = (int)std::min<size_t>(MESH_BOUNDS_BLOCKS, (n + MESH_BLOCK - 1) / MESH_BLOCK);
+    frog::DevBuf<MeshBounds> d_partial, d_bounds;
+    KCHECK(d_partial.alloc(bound_blocks));
+    KCHECK(d_bounds.alloc(1));
+    mesh_bounds_kernel<<<bound_blocks, MESH_BLOCK>>>(s->d_xyz.p, n, d_partial.p);
+    mesh_bounds_final_kernel<<<1, MESH_BLOCK>>>(d_partial.p, bound_blocks, d_bounds.p);
+    KCHECK(hipGetLastError());
+    MeshBounds b;
+    KCHECK(hipMemcpy(&b, d_bounds.p, sizeof b, hipMemcpyDeviceToHost));
+    if (b.bad) return fail(FROG_E_INVALID, "frog_isosurface_cluster: " + std::to_string(b.bad) + " coordinates are not finite");
+    MeshCells cells;
+    cells.cell = cell;
+    for (int k = 0; k < 3; k++) {
+        cells.lo[k] = (double)b.lo[k];
+        const double top = std::floor(((double)b.hi[k] - (double)b.lo[k]) / cell);      // the largest c on this axis: c ascends with x
+        if (!(top < 2097152.0)) return fail(FROG_E_INVALID, "frog_isosurface_cluster: more than 2^21 cells on an axis");
+        cells.count[k] = (unsigned long long)top + 1;
+    }
+
+    frog::DevBuf<unsigned long long> d_keys, d_sorted;
+    frog::DevBuf<uint32_t> d_order, d_members, d_times, d_first, d_runs, d_cluster_of, d_new_triangles;
+    frog::DevBuf<float> d_new_xyz;
+    frog::DevBuf<unsigned char> d_temp;
+    KCHECK(d_keys.alloc(n));
+    KCHECK(d_sorted.alloc(n));
+    KCHECK(d_order.alloc(n));
+    KCHECK(d_members.alloc(n));
+    KCHECK(d_times.alloc(n + 1));
+    KCHECK(d_first.alloc(n + 1));
+    KCHECK(d_runs.alloc(1));
+    KCHECK(d_cluster_of.alloc(n));
+    hipError_t e = chunked_launch(n, [&](unsigned blocks, size_t base) {
+        mesh_cell_keys_kernel<<<blocks, MESH_BLOCK>>>(base, s->d_xyz.p, n, cells, d_keys.p, d_order.p);
+    });
+    if (e != hipSuccess) return hip_fail("frog_isosurface_cluster: keys", e);
+    const int end_bit = std::max(1, bit_length(cells.count[0] * cells.count[1] * cells.count[2] - 1));      // <= 2^63 cells
+    size_t bytes = 0;
+    KCHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_keys.p, d_sorted.p, d_order.p, d_members.p, n, 0, end_bit));
+    KCHECK(d_temp.alloc(std::max<size_t>(bytes, 1)));
+    KCHECK(hipcub::DeviceRadixSort::SortPairs(d_temp.p, bytes, d_keys.p, d_sorted.p, d_order.p, d_members.p, n, 0, end_bit));
+    bytes = 0;
+    KCHECK(hipcub::DeviceRunLengthEncode::Encode(nullptr, bytes, d_sorted.p, d_keys.p, d_times.p, d_runs.p, (int)n));
+    KCHECK(d_temp.alloc(std::max<size_t>(bytes, 1)));
+    KCHECK(hipcub::DeviceRunLengthEncode::Encode(d_temp.p, bytes, d_sorted.p, d_keys.p, d_times.p, d_runs.p, (int)n));
+    uint32_t n_clusters = 0;
+    KCHECK(hipMemcpy(&n_clusters, d_runs.p, sizeof n_clusters, hipMemcpyDeviceToHost));
+    KCHECK(hipMemsetAsync(d_times.p + n_clusters, 0, sizeof(uint32_t), 0));
+    bytes = 0;
+    KCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_times.p, d_first.p, (size_t)n_clusters + 1));
+    KCHECK(d_temp.alloc(std::max<size_t>(bytes, 1)));
+    KCHECK(hipcub::DeviceScan::ExclusiveSum(d_temp.p, bytes, d_times.p, d_first.p, (size_t)n_clusters + 1));
+    KCHECK(d_new_xyz.alloc(3 * (size_t)n_clusters));
+    e = chunked_launch(n_clusters, [&](unsigned blocks, size_t base) {
+        mesh_cluster_kernel<<<blocks, MESH_BLOCK>>>(base, s->d_xyz.p, d_members.p, d_first.p, n_clusters, d_new_xyz.p, d_cluster_of.p);
+    });
+    if (e != hipSuccess) return hip_fail("frog_isosurface_cluster: means", e);
+
+    uint64_t kept = 0;
+    if (m) {
+        const size_t blocks = (m + MESH_BLOCK - 1) / MESH_BLOCK;
+        frog::DevBuf<unsigned long long> d_count, d_offset;
+        KCHECK(d_count.alloc(blocks + 1));
+        KCHECK(d_offset.alloc(blocks + 1));
+        KCHECK(hipMemsetAsync(d_count.p + blocks, 0, sizeof(unsigned long long), 0));
+        e = chunked_launch(m, [&](unsigned nb, size_t base) {
+            mesh_triangle_count_kernel<<<nb, MESH_BLOCK>>>(base, s->d_triangles.p, d_cluster_of.p, m, d_count.p);
+        });
+        if (e != hipSuccess) return hip_fail("frog_isosurface_cluster: count", e);
+        if (int rc = iso_block_offsets(d_count, d_offset, blocks, d_temp, &kept)) return rc;
+        if (kept) {
+            KCHECK(d_new_triangles.alloc(3 * (size_t)kept));
+            e = chunked_launch(m, [&](unsigned nb, size_t base) {
+                mesh_triangle_emit_kernel<<<nb, MESH_BLOCK>>>(base, s->d_triangles.p, d_cluster_of.p, m, d_offset.p, d_new_triangles.p);
+            });
+        }
+        if (e == hipSuccess) e = hipDeviceSynchronize();    // d_count and d_offset go out of scope
+        if (e != hipSuccess) return hip_fail("frog_isosurface_cluster: triangles", e);
+    }
+    if (cluster_of) KCHECK(hipMemcpy(cluster_of, d_cluster_of.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    KCHECK(hipDeviceSynchronize());
+    s->d_xyz.swap(d_new_xyz);
+    s->d_triangles.swap(d_new_triangles);
+    s->n_vertices = n_clusters;
+    s->n_triangles = (uint32_t)kept;
+    return FROG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -3144,6 +3394,82 @@ void frog_isosurface_destroy(frog_isosurface *s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     delete s;
+}
+
+int frog_mesh_smooth(float *xyz, size_t n_points, const uint32_t *face_ptr, const uint32_t *face_idx, size_t n_faces,
+                     uint32_t iterations, double lambda, double mu, int boundary, int device)
+{
+    const char *where = "frog_mesh_smooth";
+    if ((n_points && !xyz) || (n_faces && !face_ptr)) return fail(FROG_E_INVALID, "bad arguments to frog_mesh_smooth");
+    if (int rc = mesh_smooth_arguments(where, lambda, mu, boundary)) return rc;
+    if (n_faces >= ((uint64_t)1 << 32)) return fail(FROG_E_INVALID, "frog_mesh_smooth: more than 2^32 - 1 faces");
+    size_t n_indices = 0;
+    if (n_faces) {
+        if (face_ptr[0] != 0) return fail(FROG_E_INVALID, "frog_mesh_smooth: face_ptr starts at 0");
+        for (size_t f = 0; f < n_faces; f++)
+            if (face_ptr[f + 1] < face_ptr[f]) return fail(FROG_E_INVALID, "frog_mesh_smooth: face_ptr descends");
+        n_indices = face_ptr[n_faces];
+    }
+    if (n_indices && !face_idx) return fail(FROG_E_INVALID, "bad arguments to frog_mesh_smooth");
+    if (int rc = mesh_indices_below(where, face_idx, n_indices, n_points)) return rc;
+    if (n_points > MESH_MAX_POINTS || n_indices > MESH_MAX_INDICES)
+        return fail(FROG_E_INVALID, "frog_mesh_smooth: at most " + std::to_string(MESH_MAX_POINTS) + " points and " +
+                                        std::to_string(MESH_MAX_INDICES) + " face indices");
+    if (int rc = select_device(device)) return rc;
+    if (!n_points || !n_indices) return FROG_OK;
+    frog::DevBuf<float> d_xyz;
+    frog::DevBuf<uint32_t> d_ptr, d_idx;
+    KCHECK(d_xyz.alloc(3 * n_points));
+    KCHECK(d_ptr.alloc(n_faces + 1));
+    KCHECK(d_idx.alloc(n_indices));
+    KCHECK(hipMemcpy(d_xyz.p, xyz, 3 * n_points * sizeof(float), hipMemcpyHostToDevice));
+    KCHECK(hipMemcpy(d_ptr.p, face_ptr, (n_faces + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    KCHECK(hipMemcpy(d_idx.p, face_idx, n_indices * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = mesh_smooth_device(where, d_xyz.p, n_points, d_ptr.p, d_idx.p, n_faces, n_indices, iterations, lambda, mu, boundary)) return rc;
+    KCHECK(hipMemcpy(xyz, d_xyz.p, 3 * n_points * sizeof(float), hipMemcpyDeviceToHost));
+    return FROG_OK;
+}
+
+int frog_isosurface_smooth(frog_isosurface *s, uint32_t iterations, double lambda, double mu, int boundary)
+{
+    if (!s) return fail(FROG_E_INVALID, "bad arguments to frog_isosurface_smooth");
+    if (int rc = mesh_smooth_arguments("frog_isosurface_smooth", lambda, mu, boundary)) return rc;
+    KCHECK(hipSetDevice(s->device));
+    return mesh_smooth_device("frog_isosurface_smooth", s->d_xyz.p, s->n_vertices, nullptr, s->d_triangles.p, s->n_triangles,
+                              3 * (size_t)s->n_triangles, iterations, lambda, mu, boundary);
+}
+
+int frog_isosurface_upload(const float *xyz, uint32_t n, const uint32_t *triangles, uint32_t m, int device, frog_isosurface **out)
+{
+    if (!out || (n && !xyz) || (m && !triangles)) return fail(FROG_E_INVALID, "bad arguments to frog_isosurface_upload");
+    if (n >= ((uint32_t)1 << 31) || m >= ((uint32_t)1 << 31))
+        return fail(FROG_E_INVALID, "frog_isosurface_upload: a surface holds fewer than 2^31 vertices and triangles");
+    if (int rc = mesh_indices_below("frog_isosurface_upload", triangles, 3 * (size_t)m, n)) return rc;
+    if (int rc = select_device(device)) return rc;
+    std::unique_ptr<frog_isosurface> s(new (std::nothrow) frog_isosurface);
+    if (!s) return fail(FROG_E_NOMEM, "out of host memory");
+    s->device = device;
+    KCHECK(s->d_xyz.alloc(3 * (size_t)n));
+    KCHECK(s->d_triangles.alloc(3 * (size_t)m));
+    if (n) KCHECK(hipMemcpy(s->d_xyz.p, xyz, 3 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    if (m) KCHECK(hipMemcpy(s->d_triangles.p, triangles, 3 * (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice));
+    s->n_vertices = n;
+    s->n_triangles = m;
+    *out = s.release();
+    return FROG_OK;
+}
+
+int frog_isosurface_cluster(frog_isosurface *s, double cell, uint32_t *n_vertices, uint32_t *n_triangles, uint32_t *cluster_of)
+{
+    if (!s || !n_vertices || !n_triangles) return fail(FROG_E_INVALID, "bad arguments to frog_isosurface_cluster");
+    if (!(std::isfinite(cell) && cell > 0.0)) return fail(FROG_E_INVALID, "frog_isosurface_cluster: the cell is a finite size > 0");
+    if (s->n_vertices) {
+        KCHECK(hipSetDevice(s->device));
+        if (int rc = mesh_cluster_device(s, cell, cluster_of)) return rc;
+    }
+    *n_vertices = s->n_vertices;
+    *n_triangles = s->n_triangles;
+    return FROG_OK;
 }
 
 int frog_chain_check(frog_chain *c, const double origin[3], const double spacing[3], const uint32_t dims[3],

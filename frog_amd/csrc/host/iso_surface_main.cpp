@@ -1,9 +1,13 @@
 // IsoSurface: the surface of a scalar volume at a level, or of a label map at a value, as a welded triangle mesh extracted on the
 // GPU (frog_isosurface_*, frog_chain.h: marching tetrahedra on the Kuhn decomposition; an extension, the reference makes no mesh).
-//   IsoSurface volume (-l level | -v value | -v all) [-t transform] [-ti inverse_transform] [-o output.obj] [-dev n]
+//   IsoSurface volume (-l level | -v value | -v all) [-s iterations] [-sl lambda] [-sm mu] [-sb 0|1] [-c cell]
+//              [-t transform] [-ti inverse_transform] [-o output.obj] [-dev n]
 // -l: inside is voxel >= level.  -v: inside is voxel == value (integer volumes).  -v all: one surface per distinct non-zero
 // value, ascending, written to <stem>_<value>.<ext> of the output name.  -t / -ti compose as in MeshTransform and are applied to
 // the vertices on the device, before the copy back (frog_isosurface_apply).  Output by extension: .obj, .ply, .stl, .vtk, .vtp.
+// -s smooths the mesh on the device with Taubin's filter (frog_isosurface_smooth: -sl, -sm and -sb as MeshSmooth's -l, -m and -b,
+// defaults 0.5, -0.53, 1), -c decimates it by vertex clustering (frog_isosurface_cluster, as MeshDecimate).  Order: extract,
+// smooth, cluster, then -t / -ti, then write; with -v all per value.
 #include "tool_common.h"
 
 #include <cstring>
@@ -25,7 +29,8 @@ static void distinct_values(const frog_volume &v, std::set<long long> &values)
 
 int main(int argc, char *argv[])
 {
-    const char *usage = "Usage : IsoSurface volume (-l level | -v value | -v all) [-t transform] [-ti inverse_transform] [-o output.obj] [-dev n]";
+    const char *usage = "Usage : IsoSurface volume (-l level | -v value | -v all) [-s iterations] [-sl lambda] [-sm mu] [-sb 0|1] [-c cell] "
+                        "[-t transform] [-ti inverse_transform] [-o output.obj] [-dev n]";
     if (argc < 4) {
         std::cout << usage << std::endl;
         exit(1);
@@ -34,7 +39,10 @@ int main(int argc, char *argv[])
     int device = 0;
     bool haveLevel = false, haveValue = false, all = false;
     double level = 0;
-    long long value = 0;
+    long long value = 0, smoothIterations = 0;
+    double smoothLambda = 0.5, smoothMu = -0.53, cell = 0;
+    int smoothBoundary = 1;
+    bool haveCell = false;
     ChainArguments chainArguments;
     std::string error;
     auto die = [](const std::string &what) { std::cout << "Error : " << what << std::endl; exit(1); };
@@ -52,10 +60,16 @@ int main(int argc, char *argv[])
         if (strcmp(key, "-t") == 0 || strcmp(key, "-ti") == 0) {
             if (!chainArguments.add(arg, strcmp(key, "-ti") == 0, error)) die(error);
         }
+        if (strcmp(key, "-s") == 0) smoothIterations = atoll(arg);
+        if (strcmp(key, "-sl") == 0) smoothLambda = atof(arg);
+        if (strcmp(key, "-sm") == 0) smoothMu = atof(arg);
+        if (strcmp(key, "-sb") == 0) smoothBoundary = atoi(arg);
+        if (strcmp(key, "-c") == 0) { cell = atof(arg); haveCell = true; }
         if (strcmp(key, "-o") == 0) outputFile = arg;
         if (strcmp(key, "-dev") == 0) device = atoi(arg);
         argumentsIndex += 2;
     }
+    if (smoothIterations < 0 || smoothIterations > 0x7fffffffLL) die("-s takes a count of iterations");
     if (haveLevel == haveValue) die(std::string("one of -l and -v\n") + usage);
 
     int status = 0;
@@ -94,6 +108,9 @@ int main(int argc, char *argv[])
         uint32_t nVertices = 0, nTriangles = 0;
         if (frog_isosurface_create(&volume, haveLevel ? FROG_ISO_LEVEL : FROG_ISO_LABEL, level, v, device, &surface, &nVertices, &nTriangles))
             die(frog_last_error());
+        if (smoothIterations && frog_isosurface_smooth(surface, (uint32_t)smoothIterations, smoothLambda, smoothMu, smoothBoundary))
+            die(frog_last_error());
+        if (haveCell && frog_isosurface_cluster(surface, cell, &nVertices, &nTriangles, nullptr)) die(frog_last_error());
         if (chain && frog_isosurface_apply(surface, chain)) die(frog_last_error());
         xyz.resize(3 * (size_t)nVertices);
         triangles.resize(3 * (size_t)nTriangles);

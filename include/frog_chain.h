@@ -970,6 +970,68 @@ void frog_isosurface_destroy(frog_isosurface *s);
  * device code), cast once.  What bin/MeshTransform moves a mesh's points with. */
 int  frog_chain_apply_f32(frog_chain *c, const float *in3n, float *out3n, size_t n);
 
+/* ---- mesh filters: non-shrinking smoothing and decimation by vertex clustering, on the device (an extension) -----------------
+ * A mesh is n points (f32 xyz) and faces given as face_ptr / face_idx (u32), as in frog_mesh (frog_host.h); a frog_isosurface
+ * holds triangles, face f = indices 3 f .. 3 f + 2.  No hashing and no atomics: the same bytes from run to run.
+ *
+ * Edges, neighbours, boundary.
+ *   The edges of a face are its cyclic consecutive index pairs (the last index pairs with the first; a face of two indices
+ *     gives its pair twice, a face of one index a pair of equal indices).  A pair of two equal indices is ignored.
+ *   A boundary edge is an unordered pair {a, b} that occurs exactly once among all faces' edges, in whichever orientation: an
+ *     edge shared by three faces, or used twice by duplicated faces, is not a boundary edge.
+ *   A boundary vertex is an endpoint of at least one boundary edge.
+ *   N(v), v not on the boundary: the distinct w != v that share a face edge with v, in ascending index order.
+ *   N(v), v on the boundary: with boundary = 1 only the w for which {v, w} is a boundary edge, ascending (the border slides
+ *     along itself); with boundary = 0 N(v) is empty, and the neighbours of v still read it.
+ *   A vertex with empty N(v) (no face, only ignored pairs, or a boundary vertex with boundary = 0) never moves: its bytes stay.
+ * One pass with factor f (Jacobi: every read is of the previous pass's f32 positions).  Per vertex with N(v) not empty, per axis:
+ *     s  = the sum of (double)x_w over N(v) in ascending w, starting from +0
+ *     m  = s / (double)|N(v)|
+ *     x' = (float)((double)x_v + f * (m - (double)x_v))
+ *   every operation rounded on its own, none contracted into a fused multiply-add.  Coordinates that are not finite propagate
+ *   as IEEE arithmetic makes them: the same infinities and NaNs in the same places (a NaN's sign and payload are not stated).
+ * Smoothing (Taubin 1995): `iterations` times a pass with lambda, then a pass with mu.  iterations = 0, or lambda = mu = 0
+ *   (either sign of zero), runs no pass: the points keep their bytes.  lambda = mu > 0 is the plain Laplacian.  Faces are
+ *   never touched.  The tools' defaults: 20, 0.5, -0.53.
+ *
+ * Decimation by vertex clustering (Rossignac and Borrel 1993), triangles only, with a cell size `cell` in the units of the
+ * points, a finite double > 0:
+ *     lo      = the per-axis minimum of the f32 coordinates
+ *     c       = (int64)floor(((double)x - (double)lo) / cell) per axis
+ *     n_axis  = max c + 1 per axis (at most 2^21)
+ *     key     = (c_z * n_y + c_y) * n_x + c_x, 64 bits
+ *   New vertex k is the k-th occupied cell in ascending key order.  Its position per axis is (float)(S / (double)count), S the
+ *   sum of its members' (double)x in ascending old index, starting from +0.  cluster_of[v] is the new index of old vertex v.
+ *   A triangle whose three new indices are not all distinct is dropped; the others keep their relative order and their
+ *   orientation.  Nothing else is removed: coincident triangles and vertices without a face stay.  An empty mesh gives an
+ *   empty mesh.
+ *   What follows.  Every old vertex and its new vertex lie in one closed cell, so they are at most cell * sqrt(3) apart (plus
+ *     the f32 cast).  The map on directed edges commutes with reversal and a dropped triangle contributes a cancelling pair
+ *     (a -> b, b -> a) or loops, so the image of a closed oriented mesh still uses every directed edge as often as its reverse.
+ *   What does not.  The image need not be a 2-manifold: an edge may be used by more than two triangles, two sheets closer than
+ *     a cell merge, triangles may coincide (also with opposite orientation), and a vertex may be left without a face.
+ *
+ * Limits, refused with FROG_E_INVALID before anything is allocated: smoothing takes at most 2^31 - 1 points and 2^30 - 1 face
+ * indices (the adjacency sorts two 64-bit keys per index and the sort's counts are signed 32-bit); clustering and upload take
+ * fewer than 2^31 points and fewer than 2^31 triangles.
+ * FROG_E_INVALID as well: a NULL argument that is not marked optional; a face index >= n; face_ptr that does not start at 0 or
+ * descends; lambda or mu that is not finite; boundary other than 0 or 1; in cluster a cell that is not a finite double > 0, a
+ * coordinate that is not finite, more than 2^21 cells on an axis.
+ * Device memory while a call runs, beyond the mesh: smoothing 40 bytes per face index and the sort's workspace for the adjacency
+ * build, then 16 + 4 |N| bytes per vertex and a second copy of the points (12 bytes per vertex); clustering 40 bytes
+ * per vertex, the sort's workspace and the new mesh.  The f64 sum of a cluster is sequential (one thread per cluster, as the stated order is): a cell that swallows the
+ * whole mesh costs one thread's walk over all n vertices. */
+/* host arrays, polygons of any size; xyz is read and written */
+int  frog_mesh_smooth(float *xyz, size_t n_points, const uint32_t *face_ptr, const uint32_t *face_idx, size_t n_faces,
+                      uint32_t iterations, double lambda, double mu, int boundary, int device);
+/* the same device code on the handle's mesh, where it lies */
+int  frog_isosurface_smooth(frog_isosurface *s, uint32_t iterations, double lambda, double mu, int boundary);
+/* a device mesh from host arrays: n x 3 floats, m x 3 indices (either may be NULL when its count is 0) */
+int  frog_isosurface_upload(const float *xyz, uint32_t n, const uint32_t *triangles, uint32_t m, int device, frog_isosurface **out);
+/* replaces the handle's mesh by its clustering; cluster_of (host, the old n entries) is optional.  frog_isosurface_get and
+ * frog_isosurface_apply work on the result as before. */
+int  frog_isosurface_cluster(frog_isosurface *s, double cell, uint32_t *n_vertices, uint32_t *n_triangles, uint32_t *cluster_of);
+
 #ifdef __cplusplus
 }
 #endif
